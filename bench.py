@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/sec of the fused UAV-landing + tabular Double-Q training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4] [--envs E] [--dtype f32|f64] [--sync-period S]
+    python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4] [--envs E] [--dtype f32|f64] [--sync-period S] [--dump-outputs DIR] [--full]
 
 One "step" = one agent period (1/22.92 s of simulated time: 21-22 physics ticks + MDP + TD update) for every env of every rank.
+
+A plain run does only what the headline figure needs: set-up, pre-roll + W warm-up periods, ONE timed region of exactly K periods, the
+result line (its roofline is read off that region's own stream events).  `--full` adds everything else this script measures or checks, as
+before: 7 repetitions of the timed region (median reported), the eps = 0.1 leg, the kernel-timer pass, the small / large / float64 blocks,
+the curriculum leg, the CPU baseline and, with several ranks, the exchange legs and the replica check.  `--dump-outputs DIR` writes what
+the timed path computed in its last step (the tables, the per-env step outputs, the counters) as DIR/<name>.npy, float64.
 
 Workload (`--config`, default 4 at EVERY N — BASELINE.json quotes its whole-node metric on configs[4]; its per-GPU share fits one GPU):
   4  configs[4] share: 1 048 576 envs / 8 GPUs = 131 072 envs per GPU, per-env randomised sinusoidal platforms (r_x ~ U(1,3) m,
@@ -420,6 +426,34 @@ def compact_line(full: dict) -> dict:
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(eng, out_dir) -> None:
+    """--dump-outputs: what a caller of the timed path holds after its last step, as out_dir/<name>.npy in float64 — the three tables
+    (Q_table_a, Q_table_b, state_action_count), what TrainingLandingEnv.step returns for every env (Engine.step_outputs: idx_x, idx_y, reward,
+    done, code, step_count, cumulative_reward, was_reset) and the run's counters (stats: agent_steps, decisions, episodes, reward_sum,
+    physics_ticks, then the episode ends by CheckResult code).  Above half the budget the per-env arrays are a fixed, seeded sample of envs,
+    sorted, whose indices env_index.npy holds.  With several ranks: rank 0's shard."""
+    import numpy as np
+    from dql_multirotor_landing_amd.config import CHECK_NAMES
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    qa, qb, cnt = eng.get_tables()
+    st = eng.stats()
+    arrays = {"Q_table_a": qa, "Q_table_b": qb, "state_action_count": cnt,
+              "stats": [st["agent_steps"], st["decisions"], st["episodes"], st["reward_sum"], st["physics_ticks"], *(st["by_code"][k] for k in CHECK_NAMES)]}
+    per_env = eng.step_outputs()
+    cap = DUMP_LIMIT_BYTES // 2 // (8 * len(per_env))
+    if eng.n > cap:
+        idx = np.sort(np.random.default_rng(0).choice(eng.n, cap, replace=False))
+        arrays["env_index"] = idx
+        per_env = {k: v[idx] for k, v in per_env.items()}
+    arrays.update(per_env)
+    for k, v in arrays.items():
+        np.save(d / f"{k}.npy", np.asarray(v, dtype=np.float64))
+
+
 def emit(full: dict) -> str:
     """write the full record to DETAIL_FILE (next to this script; best effort) and return the compact line"""
     try:
@@ -443,9 +477,14 @@ def main():
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (weak scaling); overrides the preset")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
     ap.add_argument("--eps", type=float, default=1.0)
-    ap.add_argument("--repeats", type=int, default=7,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: 7 repetitions, the eps = 0.1 leg, the kernel-timer pass, the small / large / float64 blocks, the curriculum "
+                         "leg, the CPU baseline and, with several ranks, the exchange legs and the replica check (the options below that tune them act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (tables, per-env step outputs, counters) as DIR/<name>.npy, float64, <= 64 MB")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (exactly K steps between barrier + device sync) is run this many times back to back; `value` / `ms_per_step` / the roofline are the "
-                         "MEDIAN repetition's, min and max next to them (a single 20-step region is 0.5 ms: one draw says little)")
+                         "MEDIAN repetition's, min and max next to them (a single 20-step region is 0.5 ms: one draw says little).  Default 1, 7 with --full")
     ap.add_argument("--sync-period", type=int, default=16,
                     help="agent periods between table exchanges (N > 1).  Default 16 = periods per launch: the smallest window that costs no extra launch boundary; "
                          "a rank then acts on tables that miss at most the other ranks' last 16 + 16 (one-launch fold delay) + 16 (window in flight) = 48 periods")
@@ -476,6 +515,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
     if args.curriculum_seeds is None:
         args.curriculum_seeds = 12 if args.gpus == 1 else 2
     pre = PRESETS[args.config]
@@ -530,9 +571,11 @@ def main():
     # BOTH exchanges are set up on the one engine (round 5): the run's `value` is timed with --exchange (default RCCL), the other one gets its own
     # timed leg in the same run (sync.<name> block) — one `bench.py --gpus 8` answers which is faster.  The peer-to-peer set-up may be refused
     # (HIP IPC between these devices): then its leg is reported as skipped, with the reason; its wait is bounded (p2p_spin_limit), never a hang.
+    # A plain run sets up the peer-to-peer exchange only when it is the one timed.
     reducers, p2p_setup_error = {}, None
     if multi:
         reducers["rccl"] = RcclWindowReducer(eng, comm)
+    if multi and (args.full or args.exchange == "p2p"):
         try:
             eng.set_option("p2p_spin_limit", 4000000)  # ~ seconds: a peer that never shows up ends the leg, not the job's time limit
             reducers["p2p"] = P2PWindowReducer(eng, rank, world)
@@ -571,8 +614,10 @@ def main():
         print(f"bench.py rank {rank}: the timed region failed", file=sys.stderr)
         sys.exit(4)
     (wall, decisions, dev_ms), spread = median_rep(reps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
     sync_info = None
-    if multi:
+    if multi and args.full:
         identical = replicas_identical(eng, comm)   # the timed region ended on exchanged tables: every rank must hold the same three tables now
         EXCHANGE_TEXT = {"p2p": "flush + push of 11 340 int64 words into every rank's exchange buffer (HIP IPC, uncached) + flags + local sum + fold, on the engine's stream",
                          "rccl": "flush + ncclAllReduce(ncclInt64, ncclSum, 11 340 words = 90 720 B) + fold, on the engine's stream"}
@@ -607,7 +652,7 @@ def main():
     # SURVEY.md section 8d config 2 asks "eps = 1.0 then 0.1": the same engine carries on at eps = 0.1 on the tables it has learnt so far (longer
     # episodes, fewer resets, greedy choices from the table rows): a second, shorter timed leg
     eps01 = None
-    if not multi and abs(args.eps - 0.1) > 1e-12:
+    if args.full and not multi and abs(args.eps - 0.1) > 1e-12:
         r01 = timed(args.sync_period, args.steps, args.warmup, reps=3, eps=0.1)
         if r01 is not None:
             (w01, d01, ms01), sp01 = median_rep(r01)
@@ -620,19 +665,24 @@ def main():
     # rocprofv3's kernel summary of the same command reports.  Event PAIRS around single
     # launches (second figure) add the event records and an idle boundary per launch; with several ranks the timed region also
     # holds the exchange kernels, so there the pairs are the per-launch figure.
+    # A plain run takes the one-rank figure from the timed region alone; the pairs are a run of their own (--full), so a plain run with
+    # several ranks has no roofline.
     P = args.periods_per_launch
-    s1 = eng.stats()
-    eng.kernel_timer(True)
-    eng.train_steps(P * min(200, max(20, args.steps // (10 * P))), args.eps)
-    k_pairs_ms, k_n = eng.kernel_time_ms()
-    eng.kernel_timer(False)
-    s2 = eng.stats()
-    dec_per_launch = P * (s2["decisions"] - s1["decisions"]) / max(1, s2["agent_steps"] - s1["agent_steps"])  # one launch = P agent periods
     n_launch = -(-args.steps // P)  # ceil: the last launch of the timed region may hold fewer than P periods
-    k_ms = dev_ms / n_launch if not multi else k_pairs_ms
+    k_pairs_ms = k_n = k_ms = None
+    if args.full:
+        s1 = eng.stats()
+        eng.kernel_timer(True)
+        eng.train_steps(P * min(200, max(20, args.steps // (10 * P))), args.eps)
+        k_pairs_ms, k_n = eng.kernel_time_ms()
+        eng.kernel_timer(False)
+        s2 = eng.stats()
+        dec_per_launch = P * (s2["decisions"] - s1["decisions"]) / max(1, s2["agent_steps"] - s1["agent_steps"])  # one launch = P agent periods
+        k_ms = k_pairs_ms
     if not multi:
+        k_ms = dev_ms / n_launch
         dec_per_launch = decisions / n_launch  # average over the launches of the timed region (kernel_avg_ms is their average duration)
-    if multi:  # last use of the engine: a peer-to-peer leg that fails leaves dql_stats_get raising DQL_EPEER from then on
+    if multi and args.full:  # last use of the engine: a peer-to-peer leg that fails leaves dql_stats_get raising DQL_EPEER from then on
         # the OTHER exchange, same engine, same schedule, same run (its failure ends its leg, not the run: the line's value is already measured)
         other = "p2p" if args.exchange == "rccl" else "rccl"
         if other not in reducers:
@@ -655,7 +705,7 @@ def main():
     eng.close()
 
     curriculum = None
-    if not args.no_curriculum:
+    if args.full and not args.no_curriculum:
         curriculum = curriculum_leg(args, comm, world, rank, dev_index, dtype)
 
     if rank == 0:
@@ -682,14 +732,15 @@ def main():
         if sync_info:
             out["sync"] = sync_info
             out["sync_ms_per_step"] = sync_info["sync_ms_per_step"]
-        valu = valu_issue(args.envs, P, args.two_axis, args.randomize_platform, args.noise, args.dtype, k_ms, args.steps / n_launch if not multi else P)
-        if valu:
-            out["valu_issue"] = valu
-        out["roofline"] = roofline_block(args.envs, P, args.two_axis, args.randomize_platform, args.noise, k_ms, dec_per_launch, n_launch if not multi else k_n, k_pairs_ms, valu)
+        if k_ms is not None:
+            valu = valu_issue(args.envs, P, args.two_axis, args.randomize_platform, args.noise, args.dtype, k_ms, args.steps / n_launch if not multi else P)
+            if valu:
+                out["valu_issue"] = valu
+            out["roofline"] = roofline_block(args.envs, P, args.two_axis, args.randomize_platform, args.noise, k_ms, dec_per_launch, n_launch if not multi else k_n, k_pairs_ms, valu)
         if eps01:
             eps01["roofline_frac"] = ab * eps01["env_steps"] / -(-args.steps // P) / (eps01["kernel_avg_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS
             out["eps_0p1"] = eps01
-        if not multi:
+        if args.full and not multi:
             # secondary single-GPU blocks, each with its own roofline from stream events of THIS run
             if args.small_envs > 0 and not (args.envs == args.small_envs and not custom and args.config == 1):
                 p1 = PRESETS[1]
@@ -708,7 +759,7 @@ def main():
                 out["goal_hold_rate"] = curriculum["stage4_greedy_4096_episodes"]["trained_mean"]["goal_hold_rate"]
                 out["touchdown_rate"] = curriculum["stage4_greedy_4096_episodes"]["trained_mean"]["touchdown_rate"]
                 out["wall_to_stage4_s"] = curriculum["wall_to_stage4_s"]
-        if not args.no_cpu_baseline and not multi:
+        if args.full and not args.no_cpu_baseline and not multi:
             out["cpu_baseline"] = cpu_baseline(min(args.envs, 4096), args.cpu_steps, dtype, {k: v for k, v in cfg_kw.items()})
         print(emit(out), flush=True)
     if comm:

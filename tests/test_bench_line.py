@@ -153,3 +153,54 @@ def test_measured_clock_ignores_oversubscribed_batches():
     assert ghz is not None and 1.5 < ghz < 2.5 and src.startswith("r")
     v = bench.valu_issue(1048576, 16, 0, 1, 1, "f32", 2.04, 16)
     assert v is None or v.get("frac_at_measured_clock") is None or v["frac_at_measured_clock"] <= 1.0
+
+
+class _StubEngine:
+    """what dump_outputs reads of an Engine, with host arrays (the GPU leg runs bench.py --dump-outputs itself)"""
+
+    def __init__(self, n):
+        import numpy as np
+        from dql_multirotor_landing_amd.config import CHECK_NAMES, TABLE_SHAPE
+        self.n = n
+        self.tables = tuple(np.random.default_rng(k).random(TABLE_SHAPE) for k in range(3))
+        self.st = {"agent_steps": 20, "decisions": 7 * n, "episodes": 3, "reward_sum": -1.25, "physics_ticks": 430,
+                   "by_code": {c: i for i, c in enumerate(CHECK_NAMES)}}
+        i = np.arange(n)
+        self.out = {"idx_x": (i % 945).astype(np.int32), "idx_y": np.zeros(n, np.int32), "reward": i * 0.5, "done": (i % 2).astype(np.uint8),
+                    "code": (i % 5).astype(np.int8), "step_count": (i % 300).astype(np.int32), "cumulative_reward": -i * 0.25, "was_reset": (i % 3 == 0).astype(np.uint8)}
+
+    def get_tables(self):
+        return self.tables
+
+    def stats(self):
+        return self.st
+
+    def step_outputs(self):
+        return {k: v.copy() for k, v in self.out.items()}
+
+
+def test_dump_outputs_writes_float64_arrays_within_budget(tmp_path):
+    import numpy as np
+    eng = _StubEngine(4096)
+    bench.dump_outputs(eng, tmp_path / "out")
+    names = {p.stem for p in (tmp_path / "out").glob("*.npy")}
+    assert names == {"Q_table_a", "Q_table_b", "state_action_count", "stats", *eng.out}
+    for p in (tmp_path / "out").glob("*.npy"):
+        assert np.load(p).dtype == np.float64, p
+    assert np.array_equal(np.load(tmp_path / "out" / "Q_table_b.npy"), eng.tables[1])
+    assert np.array_equal(np.load(tmp_path / "out" / "code.npy"), eng.out["code"])
+    assert np.load(tmp_path / "out" / "stats.npy")[1] == 7 * 4096
+    # beyond half the budget: the same fixed sample of envs every time, named by env_index, and the whole dump stays within the limit
+    big = _StubEngine(1 << 20)
+    bench.dump_outputs(big, tmp_path / "a")
+    bench.dump_outputs(big, tmp_path / "b")
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert 0 < len(idx) < big.n and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "env_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "reward.npy"), big.out["reward"][idx.astype(np.int64)])
+    assert sum(p.stat().st_size for p in (tmp_path / "a").glob("*.npy")) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_plain_run_and_full_options():
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout

@@ -608,8 +608,11 @@ def test_step_dev_equals_step(mods):
     """dql_step_dev (actions already in device memory, e.g. written by the caller's own policy kernel) == dql_step with the same actions
     from the host: states, rewards, dones, every field."""
     import ctypes as C
+    from dql_multirotor_landing_amd import _lib
     from dql_multirotor_landing_amd.engine import Engine
-    hip = C.CDLL("libamdhip64.so")
+    # hipMalloc / hipMemcpy of the HIP runtime libdql_hip.so runs on (symbol lookup through its handle searches its dependencies): loaded by name,
+    # a second copy of the runtime can join the process (torch ships its own, loaded first when a torch test ran earlier) and it sees no device
+    hip = C.CDLL(str(_lib.LIB_PATH))
     n = 777
     a, b = Engine(DqlConfig(dtype=F32, t_max=3.0), n, seed=3), Engine(DqlConfig(dtype=F32, t_max=3.0), n, seed=3)
     dptr = C.c_void_p()

@@ -7,16 +7,16 @@ O=$R/gpurun_out/r2p
 mkdir -p $O
 cd $R
 if [ $WHAT != pmc ]; then
-python bench.py > $O/bench_4096.json 2> $O/bench_4096.err
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_4096_driver_args.json 2>> $O/bench_4096.err
+python bench.py --full > $O/bench_4096.json 2> $O/bench_4096.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_4096_driver_args.json 2>> $O/bench_4096.err
 echo bench done
-python bench.py --envs 32768 --no-curriculum --no-cpu-baseline --large-envs 0 > $O/bench_32768.json 2>> $O/bench.err
-python bench.py --envs 131072 --randomize-platform 1 --noise 1 --steps 1000 --warmup 100 --no-curriculum --no-cpu-baseline --large-envs 0 > $O/bench_config5_131072.json 2>> $O/bench.err
-python bench.py --envs 1048576 --steps 300 --warmup 32 --no-curriculum --no-cpu-baseline --large-envs 0 > $O/bench_1M.json 2>> $O/bench.err
-python bench.py --envs 65536 --two-axis 1 --steps 1000 --warmup 100 --no-cpu-baseline --large-envs 0 > $O/bench_2axis_65536.json 2>> $O/bench.err
+python bench.py --full --envs 32768 --no-curriculum --no-cpu-baseline --large-envs 0 > $O/bench_32768.json 2>> $O/bench.err
+python bench.py --full --envs 131072 --randomize-platform 1 --noise 1 --steps 1000 --warmup 100 --no-curriculum --no-cpu-baseline --large-envs 0 > $O/bench_config5_131072.json 2>> $O/bench.err
+python bench.py --full --envs 1048576 --steps 300 --warmup 32 --no-curriculum --no-cpu-baseline --large-envs 0 > $O/bench_1M.json 2>> $O/bench.err
+python bench.py --full --envs 65536 --two-axis 1 --steps 1000 --warmup 100 --no-cpu-baseline --large-envs 0 > $O/bench_2axis_65536.json 2>> $O/bench.err
 echo sizes done
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline --large-envs 0 --no-curriculum > $O/bench_under_rocprof.json 2> $O/rocprof_stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline --large-envs 0 --no-curriculum > $O/bench_under_rocprof.json 2> $O/rocprof_stats.err
 echo stats done
 fi
 if [ $WHAT != bench ]; then

@@ -7,17 +7,17 @@ O=$R/gpurun_out/r3p
 mkdir -p $O
 cd $R
 if [ $WHAT != pmc ]; then
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_args.json 2>> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_args.json 2>> $O/bench_default.err
 echo bench done
-for c in 1 2 3; do python bench.py --config $c --no-curriculum --no-cpu-baseline --small-envs 0 --large-envs 0 > $O/bench_config$c.json 2>> $O/bench.err; done
-python bench.py --exchange-rehearsal --no-curriculum --no-cpu-baseline > $O/bench_exchange_rehearsal.json 2>> $O/bench.err
-HSA_ENABLE_IPC_MODE_LEGACY=0 python bench.py --exchange-rehearsal --exchange p2p --no-curriculum --no-cpu-baseline > $O/bench_exchange_rehearsal_p2p.json 2>> $O/bench.err
+for c in 1 2 3; do python bench.py --full --config $c --no-curriculum --no-cpu-baseline --small-envs 0 --large-envs 0 > $O/bench_config$c.json 2>> $O/bench.err; done
+python bench.py --full --exchange-rehearsal --no-curriculum --no-cpu-baseline > $O/bench_exchange_rehearsal.json 2>> $O/bench.err
+HSA_ENABLE_IPC_MODE_LEGACY=0 python bench.py --full --exchange-rehearsal --exchange p2p --no-curriculum --no-cpu-baseline > $O/bench_exchange_rehearsal_p2p.json 2>> $O/bench.err
 python scripts/plumbing_config1.py > $O/config1_plumbing.json 2>> $O/bench.err
 echo configs done
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline --small-envs 0 --large-envs 0 --no-curriculum > $O/bench_under_rocprof.json 2> $O/rocprof_stats.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c1 -- python3 $R/bench.py --config 1 --no-cpu-baseline --small-envs 0 --large-envs 0 --no-curriculum > $O/bench_c1_under_rocprof.json 2>> $O/rocprof_stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline --small-envs 0 --large-envs 0 --no-curriculum > $O/bench_under_rocprof.json 2> $O/rocprof_stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c1 -- python3 $R/bench.py --full --config 1 --no-cpu-baseline --small-envs 0 --large-envs 0 --no-curriculum > $O/bench_c1_under_rocprof.json 2>> $O/rocprof_stats.err
 echo stats done
 fi
 if [ $WHAT != bench ]; then

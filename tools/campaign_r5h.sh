@@ -4,7 +4,7 @@ O=gpurun_out/r5h; mkdir -p $O
 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "periods_per_launch" > $O/pytest_p32.log 2>&1 || { tail -30 $O/pytest_p32.log; exit 1; }
 tail -2 $O/pytest_p32.log
 for P in 16 32; do for K in 2000 20; do
-python bench.py --periods-per-launch $P --steps $K --warmup $([ $K = 20 ] && echo 5 || echo 200) --no-f64-block --no-cpu-baseline --small-envs 0 --large-envs 0 --no-curriculum | python -c "
+python bench.py --full --periods-per-launch $P --steps $K --warmup $([ $K = 20 ] && echo 5 || echo 200) --no-f64-block --no-cpu-baseline --small-envs 0 --large-envs 0 --no-curriculum | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print('P $P K $K', '%.4g env-steps/s' % d['value'], '%.2f us/period' % (d['ms_per_step'] * 1e3), 'frac %.4f' % d['roofline']['frac'], d['repeats']['value_min'], d['repeats']['value_max'])
 "; done; done > $O/bench_p32.txt 2>&1
