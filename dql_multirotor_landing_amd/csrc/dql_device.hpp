@@ -29,10 +29,30 @@
 #else
 #define DQL_SECTION(name) do { } while (0)
 #endif
-#ifdef DQL_WAVE_CLOCK  // diagnostic build (tools/exp_wave_clock.py): the wave's clock when phase DQL_WAVE_CLOCK is complete
+// -DDQL_WAVE_CLOCK=k: diagnostic build (tools/exp_wave_clock.py): k_step writes each wave's start and end on the wall clock to the episode log buffer
+// instead of the masks.  End = the wave's clock when phase k (2 .. 6, DQL_MARK_T) is complete, 7: behind the kernel's last atomics; 8 writes where
+// the wave ran instead, HW_ID and the XCC id above it (tools/exp_placement.py).
+#ifdef DQL_WAVE_CLOCK
 #define DQL_MARK_T(e, k) do { if ((k) == DQL_WAVE_CLOCK) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); (e).mark = wall_clock64(); } } while (0)
+#define DQL_WAVE_BEGIN(t0) const unsigned long long t0 = wall_clock64()
+#define DQL_WAVE_END_VAR(t1) unsigned long long t1 = 0
+#define DQL_WAVE_STORED(e, t1) ((t1) = (e).mark)
+#define DQL_WAVE_END(t0, t1, elog, n, i, tid) do {                                                                                           \
+    if (DQL_WAVE_CLOCK == 7) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); t1 = wall_clock64(); }                            \
+    if (DQL_WAVE_CLOCK == 8) {                                                                                                               \
+      unsigned hw, xcc;                                                                                                                      \
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));                                                                     \
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));                                                                   \
+      t1 = ((unsigned long long)(xcc & 0xf) << 32) | hw;                                                                                     \
+    }                                                                                                                                        \
+    if ((elog) && ((tid) & 63) == 0) { const long long w = (i) >> 6, nw = ((n) + 63) >> 6; if (w < nw) { (elog)[w] = t0; (elog)[nw + w] = t1; } } \
+  } while (0)
 #else
 #define DQL_MARK_T(e, k) do { } while (0)
+#define DQL_WAVE_BEGIN(t0) do { } while (0)
+#define DQL_WAVE_END_VAR(t1) do { } while (0)
+#define DQL_WAVE_STORED(e, t1) do { } while (0)
+#define DQL_WAVE_END(t0, t1, elog, n, i, tid) do { } while (0)
 #endif
 
 // -DDQL_PHASE_CLOCK: diagnostic build (tools/exp_phase_clock.py): shader cycles (s_memtime) each wave spends per phase of a launch, summed over
@@ -42,8 +62,26 @@
 // latency is charged to the phase in which the wave stalls on it.
 #ifdef DQL_PHASE_CLOCK
 #define DQL_PHASE(e, k) do { const unsigned long long _t = __builtin_readcyclecounter(); (e).ph[k] += _t - (e).t_last; (e).t_last = _t; } while (0)
+#define DQL_PHASE_BEGIN(t0) const unsigned long long t0 = __builtin_readcyclecounter()
+#define DQL_PHASE_LOADED(e, t0) do { for (int k = 0; k < 7; ++k) (e).ph[k] = 0; (e).t_last = (t0); DQL_PHASE(e, 0); } while (0)
+#define DQL_PHASE_END(e, live, elog, n, i, tid) do {                                                                                         \
+    if (live) {                                                                                                                              \
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                                            \
+      DQL_PHASE(e, 6);                                                                                                                       \
+      if ((elog) && ((tid) & 63) == 0) { const long long w = (i) >> 6, nw = ((n) + 63) >> 6; for (int k = 0; k < 7; ++k) (elog)[(size_t)k * nw + w] = (e).ph[k]; } \
+    }                                                                                                                                        \
+  } while (0)
 #else
 #define DQL_PHASE(e, k) do { } while (0)
+#define DQL_PHASE_BEGIN(t0) do { } while (0)
+#define DQL_PHASE_LOADED(e, t0) do { } while (0)
+#define DQL_PHASE_END(e, live, elog, n, i, tid) do { } while (0)
+#endif
+// the diagnostic builds write their clocks to the episode log buffer, in place of the finished-episode masks
+#if defined(DQL_WAVE_CLOCK) || defined(DQL_PHASE_CLOCK)
+constexpr bool ELOG_MASKS = false;
+#else
+constexpr bool ELOG_MASKS = true;
 #endif
 
 namespace dql {
@@ -75,14 +113,7 @@ DQL_DEV double sqrt_(double a) { return __builtin_sqrt(a); }
 constexpr float SQRT_POS_MIN = 1e-30f;  // > 2^-102 = 1.97e-31
 DQL_DEV float sqrt_pos(float x) {
   const float y = __builtin_amdgcn_rsqf(x);
-#ifdef DQL_AB_SQRT_GOLDSCHMIDT  // A/B builds (tools/ab_build.sh): the 1 + 7 sequence
-  float g = x * y, h = 0.5f * y;
-  const float r = __builtin_fmaf(-h, g, 0.5f);
-  g = __builtin_fmaf(g, r, g);
-  h = __builtin_fmaf(h, r, h);
-#else
   const float g = x * y, h = 0.5f * y;
-#endif
   const float d = __builtin_fmaf(-g, g, x);
   return __builtin_fmaf(d, h, g);
 }
@@ -808,17 +839,11 @@ template <bool PRE_CLIPPED = false, typename T, typename K> DQL_DEV void rotor_f
     const T ref = (PRE_CLIPPED && Fast32<T>::on) ? cmd[i] : clip3(cmd[i], T(0.0), T(s.omax));  // cmd = sqrt(..) >= +0: min(cmd, omax); float32 tick: rotor_cmd() did it
     if constexpr (Fast32<T>::on) {  // om + (1 - a) (ref - om): the same filter, one instruction less
       const T d = ref - e.om[i];
-      // (round 5 tried max(fma(oup, d, om), fma(odn, d, om)) — the same value bit for bit since 0 < odn < oup, one instruction less and one instead of two in
-      // the four-cycle class: 19.20 vs 19.18 us per period, nothing: the tick sits within 7 % of its issue cost and 1 % is the noise of code placement)
-#ifdef DQL_AB_ROTOR_SELECT  // A/B builds (tools/ab_build.sh): the compare + select form
-      const T c = d > T(0.0) ? T(s.oup) : T(s.odn);
-      e.om[i] = fma_(c, d, e.om[i]);
-#else
       // the larger of the two candidates IS the selected one (0 < odn < oup: oup d > odn d for d > 0, < for d < 0, equal at 0): two fmas and a max — one
       // instruction of the four-cycle class per rotor instead of two (compare + select), bit for bit the same value
+      // (round 5 against compare + select: 18.10 -> 17.94 us per period, profiles/r5_ab_sgpr_spills.txt; a later A/B 19.20 vs 19.18, code-placement noise)
       const T up = fma_(T(s.oup), d, e.om[i]), dn = fma_(T(s.odn), d, e.om[i]);
       if constexpr (sizeof(T) == 4) e.om[i] = __builtin_fmaxf(up, dn); else e.om[i] = up > dn ? up : dn;
-#endif
     } else {
       const T a = ref > e.om[i] ? s.aup : s.adn;
       e.om[i] = fma_(a, e.om[i], (T(1.0) - a) * ref);
@@ -921,11 +946,8 @@ template <typename T> DQL_DEV void platform_eval(const SimK<T>& s, Env<T>& e) {
 // manager tick instead of a 45-instruction sincos.  The phase itself advances exactly as before and stays the persistent state: every period
 // starts again from sincos(phase), so the recurrence never runs for more than five steps (a few ulp).  sin / cos of delta: Taylor to delta^5 /
 // delta^6 for delta <= 0.25 rad (1e-8 relative; the reference platform steps 0.008 rad), det_sincos beyond (per lane).
-#ifdef DQL_PLATREC_LEAN  // A/B build: sin / cos of the step recomputed at every manager tick (9 instructions) instead of held in two registers across the tick loop
-template <typename T> struct PlatRec { T sn, cs; };
-#else
+// sin / cos of the step are held in two registers across the tick loop (recomputing them per manager tick, 9 instructions, was equal or slower: DESIGN.md).
 template <typename T> struct PlatRec { T sn, cs, sd, cd; };
-#endif
 template <typename T> DQL_DEV void platform_step_sincos(const SimK<T>& s, const Env<T>& e, T& sd, T& cd) {
   const T d = e.mp_w * s.mp_dt;
   if (d > T(0.25) || d < T(-0.25)) det_sincos(d, sd, cd);
@@ -937,9 +959,7 @@ template <typename T> DQL_DEV void platform_step_sincos(const SimK<T>& s, const 
 }
 template <typename T> DQL_DEV void platform_rec_begin(const SimK<T>& s, const Env<T>& e, PlatRec<T>& r) {
   det_sincos(e.mp_phase, r.sn, r.cs);
-#ifndef DQL_PLATREC_LEAN
   platform_step_sincos(s, e, r.sd, r.cd);
-#endif
 }
 // rec: the fused float32 step's per-period sine / cosine carry (null: evaluate sincos(phase) at this tick — float64, and the stand-alone operators)
 template <typename T> DQL_DEV void platform_update(const SimK<T>& s, Env<T>& e, PlatRec<T>* rec = nullptr, bool first_in_period = true) {
@@ -947,12 +967,7 @@ template <typename T> DQL_DEV void platform_update(const SimK<T>& s, Env<T>& e, 
     if (first_in_period) platform_rec_begin(s, e, *rec);
     platform_set(s, e, rec->sn, rec->cs);
     const T sn = rec->sn, cs = rec->cs;
-#ifdef DQL_PLATREC_LEAN
-    T sd, cd;
-    platform_step_sincos(s, e, sd, cd);
-#else
     const T sd = rec->sd, cd = rec->cd;
-#endif
     rec->sn = fma_(sn, cd, cs * sd);
     rec->cs = fma_(cs, cd, -(sn * sd));
   } else platform_eval(s, e);
@@ -1357,12 +1372,7 @@ DQL_DEV StepOut period_end_with(const SimK<T>& s, const M& m, Env<T>& e, const P
   quat_to_R(e.q, R);
   int idx, idy = -1;
   Bins bnx{0, 0, 0}, bny{0, 0, 0};
-#ifdef DQL_AB_NO_TANBIN  // A/B builds (tools/ab_build.sh): timing only, no parity
-  constexpr bool TANBIN = false;
-#else
-  constexpr bool TANBIN = Fast32<T>::on;
-#endif
-  if constexpr (TANBIN) {  // the angle bins straight from the rotation matrix (angle_bin_from_tangent): pitch = atan2(-R20, sqrt(R00^2 + R10^2)), roll = atan2(R21, R22)
+  if constexpr (Fast32<T>::on) {  // the angle bins straight from the rotation matrix (angle_bin_from_tangent): pitch = atan2(-R20, sqrt(R00^2 + R10^2)), roll = atan2(R21, R22)
     const int bin_x = angle_bin_from_tangent(m, -R[6], fma_(R[0], R[0], R[3] * R[3]), true);
     DQL_SECTION("end_discretise");
     idx = discretise_impl<true>(m, e.obs_px, e.obs_vx, e.obs_ax, T(0.0), bin_x, &bnx);
@@ -1452,25 +1462,17 @@ DQL_DEV StepOut period_end_with(const SimK<T>& s, const M& m, Env<T>& e, const P
 // held in rounds 1 - 2 (-9 % at 1 M envs) and stopped holding with the shorter round-3 tick: NOT unrolling is 5 - 6 % faster wherever
 // the plain / literal loop runs (in-run A/B, config 4 flags: 131 072 envs 24.7 vs 26.1 us, 262 144: 42.5 vs 45.0, 1 M: 150.2 vs 160.2;
 // unrolling by 3, 5, 7, 11 lands between the two)
-#ifndef DQL_TICK_UNROLL_F32
-#define DQL_TICK_UNROLL_F32 1
-#endif
-#ifndef DQL_TICK_UNROLL_F64
-#define DQL_TICK_UNROLL_F64 2
-#endif
-template <typename T> struct TickUnroll { static constexpr int n = sizeof(T) == 4 ? DQL_TICK_UNROLL_F32 : DQL_TICK_UNROLL_F64; };
-#ifndef DQL_GROUP
-#define DQL_GROUP 5  // manager_div of the reference: 500 Hz physics / 100 Hz observation
-#endif
+template <typename T> struct TickUnroll { static constexpr int n = sizeof(T) == 4 ? 1 : 2; };
+constexpr int GROUP = 5;  // manager_div of the reference: 500 Hz physics / 100 Hz observation
 // One agent period of one env in one lane.  HOT: hold the per-tick constants in VGPRs (small batches: one wave per SIMD,
 // registers are free and every avoided v_readlane shortens the dependency-bound stream; at full occupancy it costs a wave).
-// TICK: 0 plain loop on SGPR constants, 1 per-tick constants in VGPRs + the loop laid out per manager period, 2 the same with the
-// packed float32 tick (physics_tick_pk), 3 plain loop with the reference vehicle's constants as literals (LitK)
+// TICK: 0 plain loop on SGPR constants, 2 per-tick constants in VGPRs + the packed float32 tick (physics_tick_pk) laid out per
+// manager period, 3 plain loop with the reference vehicle's constants as literals (LitK)
 // 4: the packed tick (2) with the reference MDP's constants as literals at the period's end (LitM) — what the host picks for small batches when the MDP is the reference's
-enum { TICK_PLAIN = 0, TICK_LONE = 1, TICK_PACKED = 2, TICK_LIT = 3, TICK_PACKED_LITM = 4 };
+// (1 was the VGPR-constant loop without the packing; the value stays unused so that the kernels' names keep their numbers)
+enum { TICK_PLAIN = 0, TICK_PACKED = 2, TICK_LIT = 3, TICK_PACKED_LITM = 4 };
 constexpr bool tick_is_packed(int t) { return t == TICK_PACKED || t == TICK_PACKED_LITM; }
 template <int TICK, typename T> struct TickK { static DQL_DEV const SimK<T>& get(const SimK<T>& s) { return s; } };
-template <> struct TickK<TICK_LONE, float> { static DQL_DEV HotK<float> get(const SimK<float>& s) { return make_hot(s); } };
 template <> struct TickK<TICK_PACKED, float> { static DQL_DEV HotK<float> get(const SimK<float>& s) { return make_hot(s); } };
 template <> struct TickK<TICK_PACKED_LITM, float> { static DQL_DEV HotK<float> get(const SimK<float>& s) { return make_hot(s); } };
 template <> struct TickK<TICK_LIT, float> { static DQL_DEV LitK get(const SimK<float>& s) { return LitK{s.vz_sp, s.yw_sp}; } };
@@ -1489,37 +1491,32 @@ template <int TICK, typename T> struct TickConsts {
 enum { X_TWO = 0, X_ONLY = 1, X_RUNTIME = 2 };
 template <int TICK, int XMODE, typename T, typename TabPtr>
 DQL_DEV StepOut agent_period(const SimK<T>& s_in, const TickConsts<TICK, T>& tc, const MdpK<T> DQL_CONST_AS* mp, const MdpRun<T>& mr, Env<T>& e, const QRow& qx, TabPtr qa, TabPtr qb, int mode, uint32_t eps_thr,
-                             int ext_action, uint64_t seed, uint32_t env_id, long long step_index, long long mgr0, int sched, unsigned prio_role = 0u, const uint32_t* kv = nullptr) {
+                             int ext_action, uint64_t seed, uint32_t env_id, long long step_index, long long mgr0, int sched, const uint32_t* kv = nullptr) {
   SimK<T> s = s_in;
-#ifndef DQL_AB_NO_OPAQUE_FLAGS  // A/B builds (tools/ab_build.sh)
   // Every wave-uniform condition on the run's mode, quirk bits, working level and placement rule is loop-invariant, so the compiler evaluates each ONCE before
   // the period loop and keeps it as a 64-bit lane mask — a dozen SGPR pairs the kernel does not have: they were spilled into VGPR lanes and read back at every use
   // (two v_readlane + a hazard wait each).  Made opaque here, once per period, the conditions are re-derived where they are used: a scalar compare each.
   // (the packed layout — batches of at most one wave per SIMD — is indifferent: 4 096 envs +0.3 %, 32 768 / 65 536 -0.3 %: left alone)
   if constexpr (sizeof(T) == 4 && (TICK == TICK_LIT || TICK == TICK_PLAIN))
     asm volatile("" : "+s"(s.quirks), "+s"(s.working), "+s"(s.init_uniform), "+s"(mode));
-#endif
   DQL_SECTION("period_begin");
   const PeriodCtx c = period_begin(s, e, qx, qa, qb, mode, eps_thr, ext_action, seed, env_id, step_index, kv);
   T B[9];
   DQL_SECTION("make_B");
   make_B(e.pitch_sp, e.roll_sp, B);
   DQL_SECTION("tick_setup");
-  constexpr bool HOT = TICK == TICK_LONE || tick_is_packed(TICK);
+  constexpr bool HOT = tick_is_packed(TICK);
   const auto& h = tc.h;
   // The literal layout's constants are instruction literals — which gfx9's three-operand encodings (v_med3, v_fma with an inline constant) cannot carry: for the yaw
   // PID's clamp bounds and the yaw frame's 0.375 the compiler emitted an s_mov of the literal in front of EVERY use, three scalar instructions per physics tick.
   // Pinned to SGPRs here (opaque: nothing to rematerialise) they stay scalar operands — in VGPRs they cost more than the s_movs (three VGPR sources per v_med3).
   T yw_lo = T(h.yw_lo), yw_hi = T(h.yw_hi), yw_wind = T(h.yw_wind), c375 = T(0.375), low_z = T(h.low_z);
-#ifndef DQL_AB_NO_TICK_SREGS  // A/B builds (tools/ab_build.sh)
   if constexpr (sizeof(T) == 4 && TICK == TICK_LIT) {
     asm volatile("" : "+s"(yw_wind), "+s"(yw_hi), "+s"(c375));
-#ifndef DQL_AB_NO_LOWZ_SREG
-    asm volatile("" : "+s"(low_z));  // (the contact test's height: the literal was moved into a scalar register in front of the compare at every tick)
-#endif
+    // (the contact test's height: the literal was moved into a scalar register in front of the compare at every tick; 17.18 vs 17.25 us, profiles/r5_ab_tick_loop.txt)
+    asm volatile("" : "+s"(low_z));
     if (T(h.yw_lo) == -T(h.yw_hi)) yw_lo = -yw_hi;
   }
-#endif
   DQL_MARK_T(e, 3);
   DQL_PHASE(e, 1);
   T R[9], cy, sy, ct = T(1.0), rn = T(1.0);
@@ -1536,13 +1533,6 @@ DQL_DEV StepOut agent_period(const SimK<T>& s_in, const TickConsts<TICK, T>& tc,
   auto manager_tick = [&]() {
     DQL_SECTION("manager");
     DQL_PHASE(e, 2);
-#ifdef DQL_PRIO_TIME  // A/B: issue priority by wall-clock slice instead of by period (k_step)
-    { const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();
-      if ((((unsigned)(t_ >> DQL_PRIO_TIME)) ^ prio_role) & 1u) asm volatile("s_setprio 1"); else asm volatile("s_setprio 0"); }
-#endif
-#ifdef DQL_PRIO_MGR   // A/B: by manager-tick parity
-    if ((((unsigned)mgr_index) ^ prio_role) & 1u) asm volatile("s_setprio 1"); else asm volatile("s_setprio 0");
-#endif
     manager_states(R, cy, sy, e.v[2], e.vz_state, e.yw_state);
     manager_obs(s, e, cy, sy, mgr_index, c.k0, c.k1, c.step_lo, c.step_hi, env_id, mgr_in_step, mgr_in_step == last_mgr, &prec, kv);
     ++mgr_in_step; ++mgr_index;
@@ -1593,31 +1583,26 @@ DQL_DEV StepOut agent_period(const SimK<T>& s_in, const TickConsts<TICK, T>& tc,
         else physics_tick_pk<false>(h, pk, ts, rp, B01, B34, B67, B2, B5, B8, e.flags);
       } else physics_tick_pk<XMODE == X_ONLY>(h, pk, ts, rp, B01, B34, B67, B2, B5, B8, e.flags);
     };
-    if constexpr (!HOT) {
-#pragma unroll TickUnroll<T>::n
-      for (int i = 0; i < n_ticks; ++i) {
+    // the 21 / 22 ticks of a period = a few ticks up to the next manager tick, then whole manager periods (one manager tick + GROUP physics
+    // ticks, straight-line: no phase test, the filter histories rotate by renaming instead of moves), then the rest; any other manager_div
+    // runs tick by tick
+    int left = n_ticks;
+    for (;;) {
+      while (left > 0 && !(s.div == GROUP && phase == 0 && left >= GROUP)) {
         tick_pk(phase == 0);
         phase = (phase + 1 == s.div) ? 0 : phase + 1;
+        --left;
       }
-    } else {
-      int left = n_ticks;
-      for (;;) {
-        while (left > 0 && !(s.div == DQL_GROUP && phase == 0 && left >= DQL_GROUP)) {
-          tick_pk(phase == 0);
-          phase = (phase + 1 == s.div) ? 0 : phase + 1;
-          --left;
-        }
-        if (left == 0) break;
-        do {
-          tick_pk(true);
+      if (left == 0) break;
+      do {
+        tick_pk(true);
 #pragma unroll
-          for (int k = 1; k < DQL_GROUP; ++k) tick_pk(false);
-          left -= DQL_GROUP;
-        } while (left >= DQL_GROUP);
-      }
+        for (int k = 1; k < GROUP; ++k) tick_pk(false);
+        left -= GROUP;
+      } while (left >= GROUP);
     }
     unpack_tick(ts, e);
-  } else if constexpr (!(HOT && sizeof(T) == 4)) {
+  } else {
     // big batches (several waves per SIMD, registers decide the occupancy): the plain loop
     // (physics ticks to go until the next manager tick, counted down: a compare + branch per tick; the phase counted up and wrapped cost an add, a compare,
     //  a select and the compare + branch)
@@ -1629,57 +1614,18 @@ DQL_DEV StepOut agent_period(const SimK<T>& s_in, const TickConsts<TICK, T>& tc,
     //  twice in the code: 17.47 against 17.18 us per period, profiles/r5_ab_tick_loop.txt)
 #pragma unroll TickUnroll<T>::n
     for (int i = 0; i < n_ticks; ++i) {
-#ifndef DQL_AB_NO_F64_LDS_CONSTS
       if constexpr (sizeof(T) == 8) asm volatile("" ::: "memory");  // float64: the tick's constants live in LDS (k_step) and are read again in every tick, not held in registers
-#endif
       DQL_SECTION("rot");
       quat_to_R(e.q, R); yaw_cs(R, cy, sy, ct, rn, c375);
       if (togo == 0) { manager_tick(); togo = s.div; }
       --togo;
       control_and_plant();
     }
-  } else {
-    // one wave per SIMD (small batches, registers are free): the 21 / 22 ticks of a period = a few ticks up to the next manager
-    // tick, then whole manager periods (one manager tick + DQL_GROUP physics ticks, straight-line: no phase test, the filter
-    // histories rotate by renaming instead of moves), then the rest.  Same operations in the same order as the plain loop,
-    // which still serves any other manager_div.  Measured: -4 % at 4 096 envs.
-    int left = n_ticks;
-    for (;;) {
-      while (left > 0 && !(s.div == DQL_GROUP && phase == 0 && left >= DQL_GROUP)) {
-        DQL_SECTION("rot");
-        quat_to_R(e.q, R); yaw_cs(R, cy, sy, ct, rn);
-        if (phase == 0) manager_tick();
-        phase = (phase + 1 == s.div) ? 0 : phase + 1;
-        control_and_plant();
-        --left;
-      }
-      if (left == 0) break;
-      do {
-        DQL_SECTION("rot");
-        quat_to_R(e.q, R); yaw_cs(R, cy, sy, ct, rn);
-        manager_tick();
-        control_and_plant();
-#pragma unroll
-        for (int k = 1; k < DQL_GROUP; ++k) {
-          quat_to_R(e.q, R); yaw_cs(R, cy, sy, ct, rn);
-          control_and_plant();
-        }
-        left -= DQL_GROUP;
-      } while (left >= DQL_GROUP);
-    }
   }
   DQL_SECTION("epilogue");
   DQL_MARK_T(e, 4);
   DQL_PHASE(e, 2);
-#if defined(DQL_SCALAR_MDP_ALL)   // A/B builds (tools/ab_build.sh)
-  const StepOut o = period_end<MDP_SCALAR>(s, mp, mr, e, c, qa, qb, mode);
-#elif defined(DQL_SCALAR_MDP_NONE)
-  const StepOut o = period_end<MDP_VECTOR>(s, mp, mr, e, c, qa, qb, mode);
-#elif defined(DQL_AB_NO_LITERAL_MDP)
-  const StepOut o = period_end<HOT ? MDP_VECTOR : MDP_SCALAR>(s, mp, mr, e, c, qa, qb, mode);
-#else
   const StepOut o = period_end<(TICK == TICK_LIT || TICK == TICK_PACKED_LITM) ? MDP_LITERAL : (HOT ? MDP_VECTOR : MDP_SCALAR)>(s, mp, mr, e, c, qa, qb, mode);
-#endif
   DQL_MARK_T(e, 5);
   DQL_PHASE(e, 4);
   return o;

@@ -300,7 +300,7 @@ template <int BYTES> DQL_DEV void warm_kernarg() {
                  "s"(t0), "s"(t1), "s"(t2), "s"(t3), "s"(t4), "s"(t5), "s"(t6), "s"(t7));
 #undef DQL_LINE
 }
-// TICK: layout of the 500 Hz loop (dql_device.hpp, agent_period: TICK_PLAIN / TICK_LONE / TICK_PACKED / TICK_LIT; launch_step_b
+// TICK: layout of the 500 Hz loop (dql_device.hpp, agent_period: TICK_PLAIN / TICK_PACKED / TICK_LIT / TICK_PACKED_LITM; launch_step_b
 // chooses).  Resident waves per SIMD by workgroup size:
 // 64 .. 256 threads: at most 2 waves per SIMD (68 KB of LDS accumulators per workgroup, or the register-hungry layouts); 512 threads:
 // two workgroups per CU = 4 waves per SIMD, so the compiler must stay within 128 VGPRs (it parks ~35 cold values in scratch)
@@ -321,14 +321,10 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
   __shared__ unsigned long long sT[STAGED ? 2 * DQL_N_CELLS : 1];  // staged index = table * N_CELLS + cell (StepOut::cell)
   __shared__ unsigned int sM[STAGED ? 2 * DQL_N_CELLS : 1];
   __shared__ unsigned long long sStat[4 + 7];  // decisions, episodes, reward sum, (spare), then the terminal histogram (codes 0 .. TERMINAL_TIMEOUT)
-#ifdef DQL_PHASE_CLOCK
-  const unsigned long long clk_start = __builtin_readcyclecounter();
-#endif
+  DQL_PHASE_BEGIN(clk_start);
   warm_kernarg<(int)sizeof(StepArgs<T>)>();
   const int tid = threadIdx.x;
-#ifdef DQL_WAVE_CLOCK  // diagnostic build (tools/exp_wave_clock.py): wave start / end times in the episode log instead of the masks
-  const unsigned long long clk0 = wall_clock64();
-#endif
+  DQL_WAVE_BEGIN(clk0);
   if ((int)blockIdx.x >= a.env_blocks) {  // table-writer block (whole block takes this path: no barrier is skipped)
     const int c = ((int)blockIdx.x - a.env_blocks) * BLOCK + tid;
     if (c < DQL_N_CELLS) {
@@ -352,9 +348,7 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
   const long long i = (long long)blockIdx.x * BLOCK + tid;
   long long dec = 0, don = 0, rfx = 0;
   bool goal = false;
-#ifdef DQL_WAVE_CLOCK
-  unsigned long long clk1 = 0;
-#endif
+  DQL_WAVE_END_VAR(clk1);
   // P agent periods per launch (option "periods_per_launch", default 1): the env stays in registers between them, so the state
   // round trip through HBM, the launch boundary and the table-writer work are paid once per P periods; the acting tables are
   // those of the launch for all P periods, every period's TD targets go to the launch's accumulators
@@ -368,11 +362,7 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
     qx = load_qrow(a.qa, a.qb, (unsigned)iv.x < (unsigned)(DQL_N_CELLS / DQL_N_ACTIONS) ? iv.x : 0);
     load_env(e, a.sr, iv, a.n, i, XMODE == X_ONLY ? x_only(a.c) : a.c);
     DQL_MARK_T(e, 2);
-#ifdef DQL_PHASE_CLOCK
-    for (int k = 0; k < 7; ++k) e.ph[k] = 0;
-    e.t_last = clk_start;
-    DQL_PHASE(e, 0);
-#endif
+    DQL_PHASE_LOADED(e, clk_start);
   }
   long long dec_w = 0, don_w = 0, rfx_w = 0;  // per-wave totals over the periods of this launch (wave-uniform after the reductions)
   // the reward total is an integer (fixed point): every lane keeps its own sum over the launch's periods (< 32 x 2^50) and the wave adds them up ONCE, behind the
@@ -385,10 +375,7 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
   SimK<T> cfgk = a.c;
   if constexpr (XMODE == X_ONLY) cfgk.two_axis = 0;
   // register headroom (<= 2 waves per SIMD: 256 VGPRs): the manager tick's and the period's run-time constants move to VGPRs once per launch
-#ifndef DQL_AB_NO_VGPR_CONSTS  // A/B builds (tools/ab_build.sh)
   if constexpr (sizeof(T) == 4 && BLOCK < 512) cfgk = period_consts_in_vgprs(cfgk);
-#endif
-#ifndef DQL_AB_NO_F64_LDS_CONSTS  // A/B builds (tools/ab_build.sh)
   // float64: the tick's constants are read from LDS.  As kernel arguments they are SGPR PAIRS — some 150 of them against 100 scalar registers — and the
   // compiler parked the overflow in VGPR lanes: ~850 v_readlane_b32 per physics tick, three quarters of the tick's instructions, around 264 float64 operations.
   // One copy per workgroup, read back where used (agent_period's plain loop keeps the compiler from hoisting the reads out of the tick loop again).
@@ -398,20 +385,14 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
     __syncthreads();
   }
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
-#else
-  const TickConsts<TICK, T> tc(cfgk);
-#endif
   // the Philox round keys (a launch constant) in VGPRs, where there are registers to spare (philox4x32)
   uint32_t kv_[20];
   const uint32_t* kv = nullptr;
-#ifndef DQL_AB_NO_VGPR_KEYS  // A/B builds (tools/ab_build.sh)
   if constexpr (sizeof(T) == 4 && BLOCK < 512 && (TICK == TICK_LIT || TICK == TICK_PLAIN)) {  // (the VGPR-constant layouts have their registers spoken for: 112 SGPR spills with the keys against 47)
 #pragma unroll
     for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
     kv = kv_;
   }
-#endif
-#ifndef DQL_AB_NO_FAIR_PRIO
   // ROUND 5: the two waves of a SIMD take turns at the issue priority.  The arbiter serves priority first, then AGE: of two waves running the same
   // program the older one is nearly unimpeded and the younger gets the leftover slots — at exactly two waves per SIMD the older half of the env
   // waves finished a 16-period launch after 272 us and the younger half then ran ALONE, at a lone wave's issue rate, for another 55 us
@@ -430,13 +411,10 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
       prio_role = hw_id & 1u;  // wave slot parity: the two waves of a SIMD sit in slots 0 and 1
     }
   }
-#endif
   for (int p = 0; p < a.n_periods; ++p) {
-#if !defined(DQL_AB_NO_FAIR_PRIO) && !defined(DQL_PRIO_TIME) && !defined(DQL_PRIO_MGR)
     // (giving the older wave the even periods instead, or the launch's last period to the younger one: 19.46 / 19.38 against 19.18 us per period)
     // (other patterns — the younger wave ahead in 12 of 16 periods, in all, in none — change nothing or bring the tail back: 19.19 / 20.25 / 20.29 us)
     if (fair_prio) { if ((((unsigned)p) ^ prio_role) & 1u) asm volatile("s_setprio 1"); else asm volatile("s_setprio 0"); }
-#endif
     dec = 0; don = 0; rfx = 0; goal = false;
     int done_code = -1;
     if (i < a.n) {
@@ -445,13 +423,7 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
         const int ax = ext & 3, ay = (ext >> 2) & 3;
         if (ax > 2 || ay > 2 || (ext >> 4) || (!a.c.two_axis && ay != 0 && ay != 2)) atomicAdd(&a.stats->bad_actions, 1ull);
       }
-      const StepOut o = agent_period<TICK, XMODE>(cfgk, tc, a.mdp, a.mdp_run, e, qx, a.qa, a.qb, a.mode, a.eps_thr, ext, a.seed, (uint32_t)(a.env_id_offset + i), a.step_index + p, a.mgr0[p], a.sched[p],
-#ifndef DQL_AB_NO_FAIR_PRIO
-                                                          prio_role
-#else
-                                                          0u
-#endif
-                                                          , kv);
+      const StepOut o = agent_period<TICK, XMODE>(cfgk, tc, a.mdp, a.mdp_run, e, qx, a.qa, a.qb, a.mode, a.eps_thr, ext, a.seed, (uint32_t)(a.env_id_offset + i), a.step_index + p, a.mgr0[p], a.sched[p], kv);
       DQL_SECTION("accumulate");
       if (STAGED) {
         if (o.cell >= 0) { atomicAdd(&sT[o.cell], (unsigned long long)o.target_fx); atomicAdd(&sM[o.cell], 1u); }
@@ -465,19 +437,15 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
       dec = o.decision; don = o.done; rfx = o.reward_fx;
       if (o.done) { done_code = e.code; goal = e.code == DQL_TERMINAL_SUCCESS; }
     }
-#if !defined(DQL_WAVE_CLOCK) && !defined(DQL_PHASE_CLOCK)
-    if (a.elog) {  // finished episodes of this period in env order: one ballot pair per wave (pkg/trainer.py:218-224 needs the order)
+    if (ELOG_MASKS && a.elog) {  // finished episodes of this period in env order: one ballot pair per wave (pkg/trainer.py:218-224 needs the order)
       const unsigned long long dm = __ballot(don != 0), sm = __ballot(goal);
       const long long w = i >> 6, nw = (a.n + 63) >> 6;
       unsigned long long* row = a.elog + (size_t)p * 2 * (size_t)nw;
       if ((tid & 63) == 0 && w < nw) { row[w] = dm; row[nw + w] = sm; }
     }
-#endif
     // wave64 shuffle reductions -> per-wave totals
     dec_w += __popcll(__ballot(dec != 0)); don_w += __popcll(__ballot(don != 0)); rfx_lane += rfx;
-#ifdef DQL_PHASE_CLOCK
     if (i < a.n) DQL_PHASE(e, 5);
-#endif
     if (__ballot(done_code >= 0)) {  // wave-uniform: most periods of most waves finish no episode
 #pragma unroll
       for (int k = 0; k <= DQL_TERMINAL_TIMEOUT; ++k) code_w[k] += (unsigned)__popcll(__ballot(done_code == k));
@@ -487,9 +455,7 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
   if (i < a.n) {
     store_env(e, a.sr, a.si, a.n, i, XMODE == X_ONLY ? x_only(a.c) : a.c);  // the atomics went out first: their round trip hides behind the state stores
     DQL_MARK_T(e, 6);
-#ifdef DQL_WAVE_CLOCK
-    clk1 = e.mark;
-#endif
+    DQL_WAVE_STORED(e, clk1);
   }
   rfx_w = wave_sum(rfx_lane);
   dec = dec_w; don = don_w; rfx = rfx_w;
@@ -520,23 +486,8 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
 #pragma unroll
     for (int k = 0; k <= DQL_TERMINAL_TIMEOUT; ++k) if (code_w[k]) atomicAdd(&a.stats->by_code[k], (unsigned long long)code_w[k]);
   }
-#ifdef DQL_PHASE_CLOCK
-  if (i < a.n) {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    DQL_PHASE(e, 6);
-    if (a.elog && (tid & 63) == 0) { const long long w = i >> 6, nw = (a.n + 63) >> 6; for (int k = 0; k < 7; ++k) a.elog[(size_t)k * nw + w] = e.ph[k]; }
-  }
-#endif
-#ifdef DQL_WAVE_CLOCK
-  if (DQL_WAVE_CLOCK == 7) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); clk1 = wall_clock64(); }
-  if (DQL_WAVE_CLOCK == 8) {  // where the wave ran: HW_ID (wave / SIMD / CU / SH / SE) and the XCC id above it (tools/exp_placement.py)
-    unsigned hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    clk1 = ((unsigned long long)(xcc & 0xf) << 32) | hw;
-  }
-  if (a.elog && (tid & 63) == 0) { const long long w = i >> 6, nw = (a.n + 63) >> 6; if (w < nw) { a.elog[w] = clk0; a.elog[nw + w] = clk1; } }
-#endif
+  DQL_PHASE_END(e, i < a.n, a.elog, a.n, i, tid);
+  DQL_WAVE_END(clk0, clk1, a.elog, a.n, i, tid);
 }
 
 // fold the last launch's accumulators into the master tables outside a launch (host table access, level switch, rank sync)
@@ -1067,7 +1018,7 @@ template <typename T, int BLOCK, int TICK> static void launch_step_t(dql_ctx* x,
 //          literal constants beyond 65 536 envs when the vehicle is the reference's (round 2 took them with the 512-thread block only; with 16
 //          periods per launch and the round-3 fixes they also win at 256: 98 304 envs 26.2 us, 131 072 28.4 vs 30.6 plain, 262 144 / 512: 51.6
 //          vs 58.8); the plain loop otherwise.
-//          2 (VGPR constants + grouped loop, the small-batch layout of round 1) is kept as an option only.
+//          (2, round 1's small-batch layout — VGPR constants + grouped loop without the packing — is gone: the packed tick replaced it)
 // float64 has one layout (no packed f64 pipe to use, no 64-bit literals): plain.
 template <typename T> static void launch_step_b(dql_ctx* x, int mode, double eps, int np) {
   int block = x->block, tick = x->tick;
@@ -1077,7 +1028,7 @@ template <typename T> static void launch_step_b(dql_ctx* x, int mode, double eps
     else if (block == 128) launch_step_t<T, 128, TICK_PLAIN>(x, mode, eps, np);
     else launch_step_t<T, 256, TICK_PLAIN>(x, mode, eps, np);
   } else {
-    if (block == 0) block = (x->n <= 8192) ? 64 : (x->n <= 196608 || tick == 2 || tick == 3 ? 256 : 512);
+    if (block == 0) block = (x->n <= 8192) ? 64 : (x->n <= 196608 || tick == 3 ? 256 : 512);
     if (tick == 0) tick = x->n <= 65536 ? 3 : (x->lit_ok ? 4 : 1);  // round 3: literals win from two waves per SIMD on (131 072 envs, P = 16: 28.4 vs 30.6 us)
     if (tick == 4 && !x->lit_ok) tick = 1;
     if (block == 128 || (block == 512 && tick != 4)) tick = 1;
@@ -1087,9 +1038,9 @@ template <typename T> static void launch_step_b(dql_ctx* x, int mode, double eps
     } else if (block == 512) launch_step_t<T, 512, TICK_PLAIN>(x, mode, eps, np);
     else if (block == 128) launch_step_t<T, 128, TICK_PLAIN>(x, mode, eps, np);
     else if (block == 64) {
-      if (tick == 3 && x->litm_ok) launch_step_t<T, 64, TICK_PACKED_LITM>(x, mode, eps, np); else if (tick == 3) launch_step_t<T, 64, TICK_PACKED>(x, mode, eps, np); else if (tick == 2) launch_step_t<T, 64, TICK_LONE>(x, mode, eps, np); else launch_step_t<T, 64, TICK_PLAIN>(x, mode, eps, np);
+      if (tick == 3 && x->litm_ok) launch_step_t<T, 64, TICK_PACKED_LITM>(x, mode, eps, np); else if (tick == 3) launch_step_t<T, 64, TICK_PACKED>(x, mode, eps, np); else launch_step_t<T, 64, TICK_PLAIN>(x, mode, eps, np);
     } else {
-      if (tick == 3 && x->litm_ok) launch_step_t<T, 256, TICK_PACKED_LITM>(x, mode, eps, np); else if (tick == 3) launch_step_t<T, 256, TICK_PACKED>(x, mode, eps, np); else if (tick == 2) launch_step_t<T, 256, TICK_LONE>(x, mode, eps, np); else launch_step_t<T, 256, TICK_PLAIN>(x, mode, eps, np);
+      if (tick == 3 && x->litm_ok) launch_step_t<T, 256, TICK_PACKED_LITM>(x, mode, eps, np); else if (tick == 3) launch_step_t<T, 256, TICK_PACKED>(x, mode, eps, np); else launch_step_t<T, 256, TICK_PLAIN>(x, mode, eps, np);
     }
   }
 }
@@ -1818,7 +1769,7 @@ int dql_set_option(dql_ctx* x, const char* name, int32_t value) {
     return DQL_OK;
   }
   if (!strcmp(name, "tick")) {
-    if (value < 0 || value > 4) return fail(DQL_EINVAL, "tick must be 0 (auto), 1 (plain), 2 (VGPR constants), 3 (packed float32) or 4 (literal constants)");
+    if (value < 0 || value > 4 || value == 2) return fail(DQL_EINVAL, "tick must be 0 (auto), 1 (plain), 3 (packed float32) or 4 (literal constants)");
     if (value == 4 && !x->lit_ok) return fail(DQL_EINVAL, "tick 4 serves float32 contexts whose vehicle / controller / MDP constants are the reference's (tools/gen_refk.py); this context's differ");
     x->tick = value;
     return DQL_OK;

@@ -298,9 +298,9 @@ int dql_p2p_status(dql_ctx* ctx, int32_t* failed_seq);
 int dql_stats_get(dql_ctx* ctx, dql_stats* out);
 int dql_stats_reset(dql_ctx* ctx);
 /* knobs: "block" (0 = auto, 64, 128, 256 threads per workgroup; 512 = float32 at 4 waves per SIMD); "tick" (0 = auto; layout of the
- * 500 Hz loop: 1 plain loop on scalar-register constants, 2 constants in vector registers + loop laid out per manager period, 3 the
- * packed float32 tick, 4 constants as instruction literals — float32 contexts whose vehicle / controller constants are the
- * reference's, DQL_EINVAL otherwise: same arithmetic, bit for bit, in all);
+ * 500 Hz loop: 1 plain loop on scalar-register constants, 3 the packed float32 tick, 4 constants as instruction literals — float32
+ * contexts whose vehicle / controller constants are the reference's, DQL_EINVAL otherwise: same arithmetic, bit for bit, in all;
+ * 2, a retired layout, is DQL_EINVAL);
  * "periods_per_launch" P in 1..32 (default 1): dql_train_steps / dql_eval_steps run P agent periods per kernel launch — every env
  * stays in registers between them, so the state round trip through HBM and the launch boundary are paid once per P periods.
  * Table timing in units of launches is unchanged (a launch acts on every accumulator up to the launch before the previous one,

@@ -80,3 +80,15 @@ def test_no_cpu_fallback_without_gpu(lib):
 def test_product_never_imports_oracle():
     for p in (ROOT / "dql_multirotor_landing_amd").rglob("*.py"):
         assert "oracle" not in p.read_text().lower().replace("the oracle", "").replace("cpu oracle", ""), p
+
+
+def test_kernel_sources_have_no_build_switches():
+    """The step kernel compiles one way: a -D flag may only switch on the diagnostic builds (section markers, wave and phase clocks),
+    never an alternative form of the shipped arithmetic or schedule.  Every macro an #if / #ifdef / #ifndef / #elif tests is listed here."""
+    allowed = {"DQL_MARK", "DQL_WAVE_CLOCK", "DQL_PHASE_CLOCK", "DQL_H", "__cplusplus"}
+    tested = set()
+    for f in ("dql_multirotor_landing_amd/csrc/dql_hip.hip", "dql_multirotor_landing_amd/csrc/dql_device.hpp", "include/dql.h"):
+        for kind, cond in re.findall(r"^\s*#\s*(ifdef|ifndef|if|elif)\b(.*)$", (ROOT / f).read_text(), re.M):
+            cond = cond.split("//")[0].split("/*")[0]
+            tested |= set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}
+    assert tested and tested <= allowed, sorted(tested - allowed)

@@ -740,14 +740,14 @@ def test_double_q_learning_updates_both_tables_in_paper_mode(mods):
         _compare(eng, orc, exact=True, what="windowed double Q")
 
 
-@pytest.mark.parametrize("tick,block,kw", [(1, 0, {}), (2, 0, {}), (2, 256, {}), (3, 64, {}), (3, 256, {}), (4, 0, {}), (4, 64, {}), (4, 512, {}), (1, 512, {}),
+@pytest.mark.parametrize("tick,block,kw", [(1, 0, {}), (1, 128, {}), (1, 256, {}), (3, 64, {}), (3, 256, {}), (4, 0, {}), (4, 64, {}), (4, 512, {}), (1, 512, {}),
                                            (0, 512, dict(two_axis=1, trajectory=TRAJ_EIGHT)), (4, 512, dict(vz_setpoint=-0.4, working_curriculum_step=3, init_uniform=1)),
                                            (3, 0, dict(two_axis=1, per_env_platform=1, noise_pos_sd=0.25, noise_vel_sd=0.1)),
                                            # the bench's headline instance k_step<float,256,LIT> in TRAIN mode, 16 periods per launch: plain, and with the configs[4] flags + the Trainer's update rule
                                            (4, 256, dict(ppl=16)),
                                            (4, 256, dict(ppl=16, per_env_platform=1, noise_pos_sd=0.25, noise_vel_sd=0.1, quirks=Q_PAPER, fold_per_step=1))])
 def test_tick_layouts_bit_exact(mods, tick, block, kw):
-    """Options "tick" / "block": every layout of the 500 Hz loop (plain, VGPR constants, packed float32, literal constants) and every
+    """Options "tick" / "block": every layout of the 500 Hz loop (plain, packed float32, literal constants) and every
     workgroup size (64 .. 512 threads, the last with the register budget of 4 waves per SIMD: cold values in scratch) computes the
     same bits as the oracle.  n spans full and ragged workgroups; 3 periods per launch; episodes end inside launches."""
     Engine, Oracle = mods
@@ -769,12 +769,15 @@ def test_tick_layouts_bit_exact(mods, tick, block, kw):
 
 def test_literal_tick_needs_reference_vehicle(mods):
     """tick 4 is compiled with the reference vehicle's constants as literals (csrc/dql_refk.inc): a context whose constants differ
-    in any bit refuses the option, and its automatic choice falls back to run-time constants — checked against the oracle."""
+    in any bit refuses the option, and its automatic choice falls back to run-time constants — checked against the oracle.
+    tick 2 (a retired layout) is refused by every context."""
     Engine, Oracle = mods
     cfg = dict(dtype=F32, mass=0.75, t_max=4.0)
     eng = Engine(DqlConfig(**cfg), 700, seed=2); orc = Oracle(DqlConfig(**cfg), 700, seed=2)
     with pytest.raises(ValueError):
         eng.set_option("tick", 4)
+    with pytest.raises(ValueError):
+        eng.set_option("tick", 2)
     eng.set_option("block", 512)
     eng.train_steps(60, 0.5); orc.train_steps(60, 0.5)
     _compare(eng, orc, exact=True, what="modified vehicle, block 512")

@@ -7,7 +7,7 @@ from dql_multirotor_landing_amd.config import DqlConfig, F32
 from dql_multirotor_landing_amd.engine import Engine
 envs = [int(x) for x in (sys.argv[1].split(",") if len(sys.argv) > 1 else "4096,16384,32768,65536,131072,262144,1048576".split(","))]
 ppls = [int(x) for x in (sys.argv[2].split(",") if len(sys.argv) > 2 else "1,2,4".split(","))]
-ticks = [int(x) for x in (sys.argv[3].split(",") if len(sys.argv) > 3 else "0".split(","))]   # option "tick": 0 auto, 1 plain, 2 VGPR constants, 3 packed
+ticks = [int(x) for x in (sys.argv[3].split(",") if len(sys.argv) > 3 else "0".split(","))]   # option "tick": 0 auto, 1 plain, 3 packed, 4 literal constants
 blocks = [int(x) for x in (sys.argv[4].split(",") if len(sys.argv) > 4 else "0".split(","))]
 import itertools
 for n in envs:
