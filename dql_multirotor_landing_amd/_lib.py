@@ -124,7 +124,22 @@ SYMBOLS = {
     "dql_agent_transfer": (C.c_int, [C.c_int, _vp, _vp, _i32, _dbl]),
     "dql_agent_predict": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _vp]),
     "dql_agent_update": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _i64, C.c_uint32, _vp, _vp]),
+    # populations (include/dql.h dql_pop_*)
+    "dql_pop_create": (C.c_int, [_cfgp, C.c_int, _i32, _i64, _vp, C.POINTER(_vp)]),
+    "dql_pop_n_agents": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "dql_pop_train_steps": (C.c_int, [_vp, _i32, _vp, _vp]),
+    "dql_pop_eval_steps": (C.c_int, [_vp, _i32, _vp]),
+    "dql_pop_set_curriculum": (C.c_int, [_vp, _i32, _i32]),
+    "dql_pop_get_tables": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "dql_pop_set_tables": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "dql_pop_transfer": (C.c_int, [_vp, _i32, _i32, _dbl]),
+    "dql_pop_publish_tables": (C.c_int, [_vp, _i32]),
+    "dql_pop_stats_get": (C.c_int, [_vp, _i32, C.POINTER(DqlStatsC)]),
+    "dql_pop_get_step_index": (C.c_int, [_vp, _i32, C.POINTER(_i64)]),
+    "dql_pop_set_step_index": (C.c_int, [_vp, _i32, _i64]),
+    "dql_pop_index_faults": (C.c_int, [_vp, _i32, C.POINTER(_i64)]),
 }
+MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS
 
 _lib = None
 

@@ -300,6 +300,30 @@ template <int BYTES> DQL_DEV void warm_kernarg() {
                  "s"(t0), "s"(t1), "s"(t2), "s"(t3), "s"(t4), "s"(t5), "s"(t6), "s"(t7));
 #undef DQL_LINE
 }
+// Population launch (dql_pop_*): K agents' envs in one launch, agent-major (agent k owns envs [k E, (k+1) E), E a multiple of
+// 512, so that a workgroup of any size holds one agent).  What differs between agents comes from a descriptor per active agent the host builds for
+// the launch (launch_pop) from THAT agent's history; the kernel reads it with scalar loads (constant address space).
+struct PopAgentDesc {
+  const double* qa; const double* qb; unsigned long long* acc_cur;  // the agent's acting tables and accumulators of this launch (its own launch parity)
+  double* qa_m; double* qb_m; double* cnt_m; double* qa_pub; double* qb_pub; long long* acc_prev; long long* window;
+  StatsDev* stats;
+  const char DQL_CONST_AS* mdp;     // the agent's MdpK<T> (level dependent)
+  unsigned long long* elog;          // the episode-log row of the agent's next period (rows span all K E envs) or null
+  unsigned long long* faults;        // targets the bounds guard dropped (dql_pop_index_faults)
+  FoldK fold;                        // n_launch: the agent's pending periods
+  long long step_index;
+  unsigned long long seed;
+  long long mgr0[DQL_MAX_PERIODS];
+  int sched[DQL_MAX_PERIODS];
+  unsigned int eps_thr; int have_prev, working, pad_;
+};
+template <typename T> struct PopArgs {
+  StepArgs<T> s;  // what the agents share: c (its level replaced per agent), mdp_run, sr, si, n = K E, mode, n_periods, env_blocks = K E / BLOCK, fair_prio
+  const PopAgentDesc DQL_CONST_AS* desc;  // [n_active], in slot order
+  int blocks_per_agent, writer_blocks, n_active, pad_;
+  int agent[DQL_MAX_AGENTS];  // slot -> agent: the compact list of the launch's active agents
+};
+
 // TICK: layout of the 500 Hz loop (dql_device.hpp, agent_period: TICK_PLAIN / TICK_PACKED / TICK_LIT / TICK_PACKED_LITM; launch_step_b
 // chooses).  Resident waves per SIMD by workgroup size:
 // 64 .. 256 threads: at most 2 waves per SIMD (68 KB of LDS accumulators per workgroup, or the register-hungry layouts); 512 threads:
@@ -489,6 +513,209 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
   DQL_PHASE_END(e, i < a.n, a.elog, a.n, i, tid);
   DQL_WAVE_END(clk0, clk1, a.elog, a.n, i, tid);
 }
+
+// The population kernel's body: k_step's body with the launch's per-agent arguments from the agent's descriptor (mgr0 / sched per period) and the
+// bounds guard on the staged indices.  It is a copy on purpose: moving k_step's body into a shared force-inlined function — even without any change
+// to it — changes the register allocation and schedule of all 19 k_step instances (the body is then simplified as a function of its own before it
+// is inlined), and every measurement of this repository was taken on those instances.  A change to one of the two bodies belongs in the other.
+template <typename T, int BLOCK, int TICK, int XMODE>
+DQL_DEV void pop_step_body(const StepArgs<T>& a, const unsigned bid, const PopAgentDesc DQL_CONST_AS* d) {
+  // several waves per workgroup: TD targets meet in LDS first (4x fewer global atomics on the hot cells of a big batch);
+  // one wave per workgroup (small batches, latency-bound): 64 envs rarely share a cell, so each lane adds straight into the
+  // global accumulators and the wave needs no LDS clear, no barrier and no flush scan (measured: -1.5 us of 26 at 4096 envs)
+  constexpr bool STAGED = BLOCK > 64;
+  __shared__ unsigned long long sT[STAGED ? 2 * DQL_N_CELLS : 1];  // staged index = table * N_CELLS + cell (StepOut::cell)
+  __shared__ unsigned int sM[STAGED ? 2 * DQL_N_CELLS : 1];
+  __shared__ unsigned long long sStat[4 + 7];  // decisions, episodes, reward sum, (spare), then the terminal histogram (codes 0 .. TERMINAL_TIMEOUT)
+  DQL_PHASE_BEGIN(clk_start);
+  warm_kernarg<(int)sizeof(PopArgs<T>)>();
+  const int tid = threadIdx.x;
+  DQL_WAVE_BEGIN(clk0);
+  if ((int)bid >= a.env_blocks) {  // table-writer block (whole block takes this path: no barrier is skipped)
+    const int c = ((int)bid - a.env_blocks) * BLOCK + tid;
+    if (c < DQL_N_CELLS) {
+      double qa = a.qa_m[c], qb = a.qb_m[c];
+      if (a.have_prev) {
+        qa = fold_cell(a.fold, a.qa_m, a.cnt_m, a.acc_prev, a.window, a.windowed, c);
+        qb = fold_cell(a.fold, a.qb_m, a.cnt_m, a.acc_prev + DQL_ACC_B, a.window + DQL_ACC_B, a.windowed, c);
+      }
+      a.qa_pub[c] = qa; a.qb_pub[c] = qb;
+    }
+    return;
+  }
+  const int ncell = (a.c.working + 1) * DQL_CELLS_PER_LEVEL;
+  const int n_tab = (a.c.quirks & DQL_Q_UPDATE_TABLE_A_ONLY) ? 1 : 2;  // tables that can receive targets (wave-uniform)
+  if (STAGED) {
+    for (int t = 0; t < n_tab; ++t)
+      for (int c = tid; c < ncell; c += BLOCK) { sT[t * DQL_N_CELLS + c] = 0ull; sM[t * DQL_N_CELLS + c] = 0u; }
+    if (tid < 4 + 7) sStat[tid] = 0ull;
+    __syncthreads();
+  }
+  const long long i = (long long)bid * BLOCK + tid;
+  long long dec = 0, don = 0, rfx = 0;
+  bool goal = false;
+  DQL_WAVE_END_VAR(clk1);
+  // P agent periods per launch (option "periods_per_launch", default 1): the env stays in registers between them, so the state
+  // round trip through HBM, the launch boundary and the table-writer work are paid once per P periods; the acting tables are
+  // those of the launch for all P periods, every period's TD targets go to the launch's accumulators
+  Env<T> e;
+  QRow qx = QRow{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (i < a.n) {
+    // the packed ints go first: their state index addresses the acting-table row, whose request then rides along with the
+    // state quads instead of waiting for them (one memory round trip less at the head of the wave).  A fresh or reset env has
+    // no previous state (idx -1): its row is never used, but the address must stay inside the table
+    const int4 iv = a.si[i];
+    qx = load_qrow(a.qa, a.qb, (unsigned)iv.x < (unsigned)(DQL_N_CELLS / DQL_N_ACTIONS) ? iv.x : 0);
+    load_env(e, a.sr, iv, a.n, i, XMODE == X_ONLY ? x_only(a.c) : a.c);
+    DQL_MARK_T(e, 2);
+    DQL_PHASE_LOADED(e, clk_start);
+  }
+  long long dec_w = 0, don_w = 0, rfx_w = 0;  // per-wave totals over the periods of this launch (wave-uniform after the reductions)
+  // the reward total is an integer (fixed point): every lane keeps its own sum over the launch's periods (< 32 x 2^50) and the wave adds them up ONCE, behind the
+  // period loop — the 64-bit DPP reduction used to run in every period (45 instructions of each env wave's period)
+  long long rfx_lane = 0;
+  // terminal histogram of the wave over the launch: one ballot per CheckResult code and period instead of one global atomic per finished
+  // episode (thousands per period on a handful of addresses at large batches)
+  unsigned code_w[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  // XMODE (dql_device.hpp agent_period): in an x-axis kernel the config's two_axis is the constant 0 — every y-axis branch of the step folds away
+  SimK<T> cfgk = a.c;
+  if constexpr (XMODE == X_ONLY) cfgk.two_axis = 0;
+  // register headroom (<= 2 waves per SIMD: 256 VGPRs): the manager tick's and the period's run-time constants move to VGPRs once per launch
+  if constexpr (sizeof(T) == 4 && BLOCK < 512) cfgk = period_consts_in_vgprs(cfgk);
+  // float64: the tick's constants are read from LDS.  As kernel arguments they are SGPR PAIRS — some 150 of them against 100 scalar registers — and the
+  // compiler parked the overflow in VGPR lanes: ~850 v_readlane_b32 per physics tick, three quarters of the tick's instructions, around 264 float64 operations.
+  // One copy per workgroup, read back where used (agent_period's plain loop keeps the compiler from hoisting the reads out of the tick loop again).
+  __shared__ TickLds<T> sTickK;  // (float32: an unused byte)
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  // the Philox round keys (a launch constant) in VGPRs, where there are registers to spare (philox4x32)
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4 && BLOCK < 512 && (TICK == TICK_LIT || TICK == TICK_PLAIN)) {  // (the VGPR-constant layouts have their registers spoken for: 112 SGPR spills with the keys against 47)
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  // ROUND 5: the two waves of a SIMD take turns at the issue priority.  The arbiter serves priority first, then AGE: of two waves running the same
+  // program the older one is nearly unimpeded and the younger gets the leftover slots — at exactly two waves per SIMD the older half of the env
+  // waves finished a 16-period launch after 272 us and the younger half then ran ALONE, at a lone wave's issue rate, for another 55 us
+  // (profiles/r5_wave_tail.jsonl).  Alternating s_setprio by (period + hardware wave slot) parity gives each wave the head of the queue in every
+  // other period: both finish together and the SIMD never runs half empty.  (A wave that shares its SIMD with nobody is unaffected.)
+  // compiled into the layouts that serve several waves per SIMD only (the packed / VGPR-constant layouts fly batches of at most one env wave per SIMD:
+  // nobody to take turns with, and the extra code cost them 0.8 %), and switched on by the host when the batch has more env waves than the device SIMDs
+  constexpr bool FAIR = (TICK == TICK_PLAIN || TICK == TICK_LIT) && BLOCK >= 128;
+  unsigned prio_role = 0u;
+  bool fair_prio = false;
+  if constexpr (FAIR) {
+    fair_prio = a.fair_prio != 0;
+    if (fair_prio) {
+      unsigned hw_id;
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
+      prio_role = hw_id & 1u;  // wave slot parity: the two waves of a SIMD sit in slots 0 and 1
+    }
+  }
+  for (int p = 0; p < a.n_periods; ++p) {
+    // (giving the older wave the even periods instead, or the launch's last period to the younger one: 19.46 / 19.38 against 19.18 us per period)
+    // (other patterns — the younger wave ahead in 12 of 16 periods, in all, in none — change nothing or bring the tail back: 19.19 / 20.25 / 20.29 us)
+    if (fair_prio) { if ((((unsigned)p) ^ prio_role) & 1u) asm volatile("s_setprio 1"); else asm volatile("s_setprio 0"); }
+    dec = 0; don = 0; rfx = 0; goal = false;
+    int done_code = -1;
+    if (i < a.n) {
+      const int ext = (a.mode == MODE_EXTERNAL) ? (int)a.actions[i] : 2;
+      if (a.mode == MODE_EXTERNAL) {  // the caller's actions are checked here, not by a host loop (dql_step): ax | ay << 2, both in 0..2
+        const int ax = ext & 3, ay = (ext >> 2) & 3;
+        if (ax > 2 || ay > 2 || (ext >> 4) || (!a.c.two_axis && ay != 0 && ay != 2)) atomicAdd(&a.stats->bad_actions, 1ull);
+      }
+      const StepOut o = agent_period<TICK, XMODE>(cfgk, tc, a.mdp, a.mdp_run, e, qx, a.qa, a.qb, a.mode, a.eps_thr, ext, a.seed, (uint32_t)(a.env_id_offset + i), a.step_index + p, d->mgr0[p], d->sched[p], kv);
+      DQL_SECTION("accumulate");
+      // bounds guard (population only): a staged index outside [0, 2 N_CELLS) would land in another agent's accumulators when the
+      // workgroup adds straight into global memory; drop it and count it (dql_pop_index_faults; the tests hold it at zero)
+      const bool okx = (unsigned)o.cell < 2u * DQL_N_CELLS, oky = (unsigned)o.cell_y < 2u * DQL_N_CELLS;
+      if ((o.cell >= 0 && !okx) || (o.cell_y >= 0 && !oky)) atomicAdd(d->faults, (unsigned long long)((o.cell >= 0 && !okx) + (o.cell_y >= 0 && !oky)));
+      if (STAGED) {
+        if (okx) { atomicAdd(&sT[o.cell], (unsigned long long)o.target_fx); atomicAdd(&sM[o.cell], 1u); }
+        if (oky) { atomicAdd(&sT[o.cell_y], (unsigned long long)o.target_y_fx); atomicAdd(&sM[o.cell_y], 1u); }
+      } else {
+        if (okx) { const int g = o.cell + (o.cell >= DQL_N_CELLS ? DQL_N_CELLS : 0); atomicAdd(&a.acc_cur[g], (unsigned long long)o.target_fx); atomicAdd(&a.acc_cur[DQL_N_CELLS + g], 1ull); }
+        if (oky) { const int g = o.cell_y + (o.cell_y >= DQL_N_CELLS ? DQL_N_CELLS : 0); atomicAdd(&a.acc_cur[g], (unsigned long long)o.target_y_fx); atomicAdd(&a.acc_cur[DQL_N_CELLS + g], 1ull); }
+      }
+      qx = o.next;  // the row of the state this period ended in = the next period's greedy row (the launch's tables act for all P)
+      dec = o.decision; don = o.done; rfx = o.reward_fx;
+      if (o.done) { done_code = e.code; goal = e.code == DQL_TERMINAL_SUCCESS; }
+    }
+    if (ELOG_MASKS && a.elog) {  // finished episodes of this period in env order: one ballot pair per wave (pkg/trainer.py:218-224 needs the order)
+      const unsigned long long dm = __ballot(don != 0), sm = __ballot(goal);
+      const long long w = i >> 6, nw = (a.n + 63) >> 6;
+      unsigned long long* row = a.elog + (size_t)p * 2 * (size_t)nw;
+      if ((tid & 63) == 0 && w < nw) { row[w] = dm; row[nw + w] = sm; }
+    }
+    // wave64 shuffle reductions -> per-wave totals
+    dec_w += __popcll(__ballot(dec != 0)); don_w += __popcll(__ballot(don != 0)); rfx_lane += rfx;
+    if (i < a.n) DQL_PHASE(e, 5);
+    if (__ballot(done_code >= 0)) {  // wave-uniform: most periods of most waves finish no episode
+#pragma unroll
+      for (int k = 0; k <= DQL_TERMINAL_TIMEOUT; ++k) code_w[k] += (unsigned)__popcll(__ballot(done_code == k));
+    }
+  }
+  DQL_SECTION("store");
+  if (i < a.n) {
+    store_env(e, a.sr, a.si, a.n, i, XMODE == X_ONLY ? x_only(a.c) : a.c);  // the atomics went out first: their round trip hides behind the state stores
+    DQL_MARK_T(e, 6);
+    DQL_WAVE_STORED(e, clk1);
+  }
+  rfx_w = wave_sum(rfx_lane);
+  dec = dec_w; don = don_w; rfx = rfx_w;
+  if (STAGED) {
+    if ((tid & 63) == 0) {
+      if (dec) atomicAdd(&sStat[0], (unsigned long long)dec);
+      if (don) atomicAdd(&sStat[1], (unsigned long long)don);
+      if (rfx) atomicAdd(&sStat[2], (unsigned long long)rfx);
+#pragma unroll
+      for (int k = 0; k <= DQL_TERMINAL_TIMEOUT; ++k) if (code_w[k]) atomicAdd(&sStat[4 + k], (unsigned long long)code_w[k]);
+    }
+    __syncthreads();
+    for (int t = 0; t < n_tab; ++t)
+      for (int c = tid; c < ncell; c += BLOCK) {
+        const unsigned int m = sM[t * DQL_N_CELLS + c];
+        if (m) { atomicAdd(&a.acc_cur[t * DQL_ACC_B + c], sT[t * DQL_N_CELLS + c]); atomicAdd(&a.acc_cur[t * DQL_ACC_B + DQL_N_CELLS + c], (unsigned long long)m); }
+      }
+    if (tid == 0) {
+      dec = (long long)sStat[0]; don = (long long)sStat[1]; rfx = (long long)sStat[2];
+#pragma unroll
+      for (int k = 0; k <= DQL_TERMINAL_TIMEOUT; ++k) code_w[k] = (unsigned)sStat[4 + k];
+    }
+  }
+  if (tid == 0) {
+    if (dec) atomicAdd(&a.stats->decisions, (unsigned long long)dec);
+    if (don) atomicAdd(&a.stats->episodes, (unsigned long long)don);
+    if (rfx) atomicAdd((unsigned long long*)&a.stats->reward_fx, (unsigned long long)rfx);
+#pragma unroll
+    for (int k = 0; k <= DQL_TERMINAL_TIMEOUT; ++k) if (code_w[k]) atomicAdd(&a.stats->by_code[k], (unsigned long long)code_w[k]);
+  }
+  DQL_PHASE_END(e, i < a.n, a.elog, a.n, i, tid);
+  DQL_WAVE_END(clk0, clk1, a.elog, a.n, i, tid);
+}
+// grid: n_active x blocks_per_agent env blocks (slot-major), then n_active x writer_blocks table-writer blocks; a block serves one agent
+template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(step_min_waves_per_simd(BLOCK, (int)sizeof(T)), step_waves_per_simd(BLOCK)))) void k_step_pop(PopArgs<T> pa) {
+  const int b = (int)blockIdx.x, env_total = pa.n_active * pa.blocks_per_agent;
+  const int slot = b < env_total ? b / pa.blocks_per_agent : (b - env_total) / pa.writer_blocks;  // wave-uniform
+  const PopAgentDesc DQL_CONST_AS* d = pa.desc + slot;
+  const int k = pa.agent[slot];
+  const unsigned bid = b < env_total ? (unsigned)(k * pa.blocks_per_agent + (b - slot * pa.blocks_per_agent)) : (unsigned)(pa.s.env_blocks + (b - env_total - slot * pa.writer_blocks));
+  StepArgs<T> a = pa.s;
+  a.c.working = d->working;
+  a.mdp = (const MdpK<T> DQL_CONST_AS*)d->mdp;
+  a.qa = d->qa; a.qb = d->qb; a.acc_cur = d->acc_cur;
+  a.qa_m = d->qa_m; a.qb_m = d->qb_m; a.cnt_m = d->cnt_m; a.qa_pub = d->qa_pub; a.qb_pub = d->qb_pub; a.acc_prev = d->acc_prev; a.window = d->window;
+  a.fold = FoldK{d->fold.alpha_tab, d->fold.n_tab, d->fold.alpha_min, d->fold.per_step, d->fold.n_launch}; a.stats = d->stats; a.elog = d->elog;
+  a.env_id_offset = -(long long)k * pa.blocks_per_agent * BLOCK;  // the env's id within its agent keys the RNG, with the agent's seed
+  a.step_index = d->step_index; a.seed = d->seed; a.eps_thr = d->eps_thr; a.have_prev = d->have_prev; a.windowed = 0;
+  pop_step_body<T, BLOCK, TICK, XMODE>(a, bid, d);
+}
+
 
 // fold the last launch's accumulators into the master tables outside a launch (host table access, level switch, rank sync)
 struct FlushArgs { double* qa_m; double* qb_m; double* cnt_m; long long* acc; long long* window; FoldK fold; int windowed; };
@@ -906,7 +1133,21 @@ struct dql_ctx {
   bool p2p_pushed = false;  // a push is enqueued whose wait is not (dql_p2p_push_window / dql_p2p_wait_window)
   long long p2p_spin_limit = 60000000ll;  // option "p2p_spin_limit": a peer may be busy with a checkpoint or an evaluation for a while
   std::vector<hipEvent_t> sev;   // event pairs around the exchanges while the kernel timer is armed
+  // population (dql_pop_*): n_agents > 0.  The context holds the K E envs (agent-major); each agent's tables, accumulators, statistics, level, seed
+  // and launch history live in a context of its own (`agents`: no envs, the population's stream), so that every per-agent call is the
+  // single-agent call on that agent's context
+  int n_agents = 0;
+  long long pop_E = 0;
+  std::vector<dql_ctx*> agents;
+  bool owns_stream = true;
+  unsigned long long* pop_faults = nullptr;            // device [n_agents]: targets the step kernel's bounds guard dropped
+  struct PopAgentDesc* pop_h = nullptr;                 // pinned staging ring of launch descriptors: [DQL_POP_RING][DQL_MAX_AGENTS]
+  struct PopAgentDesc* pop_d = nullptr;                 // its device copy, read by k_step_pop
+  hipEvent_t pop_ev[8] = {nullptr};                     // per ring slot: recorded behind the slot's copy (the staging slot is free again once it fired)
+  bool pop_busy[8] = {false};
+  int pop_slot = 0;
 };
+#define DQL_POP_RING 8
 
 // first exchange of the peer-to-peer path that gave up on a missing peer (0 = none); synchronises the stream
 static int p2p_failed_seq(dql_ctx* x, unsigned long long* seq_out) {
@@ -969,6 +1210,20 @@ static unsigned int eps_threshold(double eps) {
 }
 static long long ticks_before(const dql_ctx* x, long long j) { return (long long)std::floor((double)j * (1.0 / (x->cfg.f_ag * x->cfg.dt))); }
 
+// the per-period tick schedule of the launch whose first agent period is j
+static void fill_schedule(const dql_ctx* x, long long j, long long* mgr0, int* sched) {
+  for (int p = 0; p < DQL_MAX_PERIODS; ++p) {
+    const long long g0 = ticks_before(x, j + p);
+    const int n_ticks = (int)(ticks_before(x, j + p + 1) - g0), div = x->cfg.manager_div;
+    const int phase = (int)(g0 % div);                                   // physics ticks since the last 100 Hz manager tick
+    mgr0[p] = g0 / div + (phase ? 1 : 0);                                // index of the next manager tick
+    const int first_mgr = phase ? div - phase : 0;
+    const int last_mgr = first_mgr < n_ticks ? (n_ticks - 1 - first_mgr) / div : 0;
+    sched[p] = n_ticks | (phase << 8) | (last_mgr << 16);                // check_config: n_ticks, manager_div <= 255
+  }
+}
+// a population launch: the active agents in slot order and their descriptors (already staged on the device)
+struct PopLaunch { int n_active; int agent[DQL_MAX_AGENTS]; const PopAgentDesc* desc; };
 template <typename T> static StepArgs<T> make_step_args(dql_ctx* x, int mode, double eps, int envs_per_block, int n_periods) {
   const long long j = x->step_index, l = x->launch_index;
   StepArgs<T> a;
@@ -982,21 +1237,32 @@ template <typename T> static StepArgs<T> make_step_args(dql_ctx* x, int mode, do
   a.fold = make_foldk(x, x->pending_periods); a.stats = x->stats; a.actions = x->ext_actions ? x->ext_actions : x->d_actions;
   a.elog = x->elog ? x->elog + (size_t)x->elog_n * 2 * (size_t)((x->n + 63) >> 6) : nullptr;
   a.n = x->n; a.env_id_offset = x->env_id_offset; a.step_index = j;
-  for (int p = 0; p < DQL_MAX_PERIODS; ++p) {
-    const long long g0 = ticks_before(x, j + p);
-    const int n_ticks = (int)(ticks_before(x, j + p + 1) - g0), div = x->cfg.manager_div;
-    const int phase = (int)(g0 % div);                                   // physics ticks since the last 100 Hz manager tick
-    a.mgr0[p] = g0 / div + (phase ? 1 : 0);                              // index of the next manager tick
-    const int first_mgr = phase ? div - phase : 0;
-    const int last_mgr = first_mgr < n_ticks ? (n_ticks - 1 - first_mgr) / div : 0;
-    a.sched[p] = n_ticks | (phase << 8) | (last_mgr << 16);              // check_config: n_ticks, manager_div <= 255
-  }
+  fill_schedule(x, j, a.mgr0, a.sched);
   a.seed = x->seed; a.eps_thr = eps_threshold(eps); a.pad_ = 0; a.mode = mode; a.n_periods = n_periods;
   a.env_blocks = (int)((x->n + envs_per_block - 1) / envs_per_block); a.have_prev = x->pending ? 1 : 0; a.windowed = x->windowed ? 1 : 0;
   a.fair_prio = x->fair_prio >= 0 ? x->fair_prio : (((x->n + 63) / 64 > x->n_simds) ? 1 : 0);
   return a;
 }
-template <typename T, int BLOCK, int TICK> static void launch_step_t(dql_ctx* x, int mode, double eps, int n_periods) {
+template <typename T, int BLOCK, int TICK> static void launch_pop_t(dql_ctx* x, int mode, int n_periods, const PopLaunch& pl) {
+  PopArgs<T> pa;
+  pa.s = make_step_args<T>(x, mode, 0.0, BLOCK, n_periods);  // the shared part; per-agent members come from the descriptors
+  const long long active_envs = (long long)pl.n_active * x->pop_E;
+  pa.s.fair_prio = x->fair_prio >= 0 ? x->fair_prio : (((active_envs + 63) / 64 > x->n_simds) ? 1 : 0);
+  pa.desc = (const PopAgentDesc DQL_CONST_AS*)pl.desc;
+  pa.blocks_per_agent = (int)(x->pop_E / BLOCK);  // exact: E is a multiple of 512
+  pa.writer_blocks = (DQL_N_CELLS + BLOCK - 1) / BLOCK;
+  pa.n_active = pl.n_active; pa.pad_ = 0;
+  for (int s = 0; s < DQL_MAX_AGENTS; ++s) pa.agent[s] = s < pl.n_active ? pl.agent[s] : 0;
+  const dim3 grid((unsigned)(pl.n_active * (pa.blocks_per_agent + pa.writer_blocks))), block(BLOCK);
+  if constexpr (sizeof(T) == 4 && TICK == TICK_PACKED_LITM) {
+    hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, pa);
+  } else if constexpr (sizeof(T) == 4 && (TICK == TICK_LIT || tick_is_packed(TICK))) {
+    if (x->cfg.two_axis) hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_TWO>), grid, block, 0, x->stream, pa);
+    else hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, pa);
+  } else hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_RUNTIME>), grid, block, 0, x->stream, pa);
+}
+template <typename T, int BLOCK, int TICK> static void launch_step_t(dql_ctx* x, int mode, double eps, int n_periods, const PopLaunch* pl) {
+  if (pl) { launch_pop_t<T, BLOCK, TICK>(x, mode, n_periods, *pl); return; }
   const StepArgs<T> a = make_step_args<T>(x, mode, eps, BLOCK, n_periods);
   const int writer_blocks = (DQL_N_CELLS + BLOCK - 1) / BLOCK;
   const dim3 grid((unsigned)(a.env_blocks + writer_blocks)), block(BLOCK);
@@ -1020,27 +1286,28 @@ template <typename T, int BLOCK, int TICK> static void launch_step_t(dql_ctx* x,
 //          vs 58.8); the plain loop otherwise.
 //          (2, round 1's small-batch layout — VGPR constants + grouped loop without the packing — is gone: the packed tick replaced it)
 // float64 has one layout (no packed f64 pipe to use, no 64-bit literals): plain.
-template <typename T> static void launch_step_b(dql_ctx* x, int mode, double eps, int np) {
+// (a population launch chooses by the population's whole batch, K E envs: the layout a context of that size would fly)
+template <typename T> static void launch_step_b(dql_ctx* x, int mode, double eps, int np, const PopLaunch* pl = nullptr) {
   int block = x->block, tick = x->tick;
   if constexpr (sizeof(T) == 8) {
     if (block == 0) block = (x->n <= 8192) ? 64 : 256;
-    if (block == 64) launch_step_t<T, 64, TICK_PLAIN>(x, mode, eps, np);
-    else if (block == 128) launch_step_t<T, 128, TICK_PLAIN>(x, mode, eps, np);
-    else launch_step_t<T, 256, TICK_PLAIN>(x, mode, eps, np);
+    if (block == 64) launch_step_t<T, 64, TICK_PLAIN>(x, mode, eps, np, pl);
+    else if (block == 128) launch_step_t<T, 128, TICK_PLAIN>(x, mode, eps, np, pl);
+    else launch_step_t<T, 256, TICK_PLAIN>(x, mode, eps, np, pl);
   } else {
     if (block == 0) block = (x->n <= 8192) ? 64 : (x->n <= 196608 || tick == 3 ? 256 : 512);
     if (tick == 0) tick = x->n <= 65536 ? 3 : (x->lit_ok ? 4 : 1);  // round 3: literals win from two waves per SIMD on (131 072 envs, P = 16: 28.4 vs 30.6 us)
     if (tick == 4 && !x->lit_ok) tick = 1;
     if (block == 128 || (block == 512 && tick != 4)) tick = 1;
     if (tick == 4) {
-      if (block == 64) launch_step_t<T, 64, TICK_LIT>(x, mode, eps, np); else if (block == 512) launch_step_t<T, 512, TICK_LIT>(x, mode, eps, np);
-      else launch_step_t<T, 256, TICK_LIT>(x, mode, eps, np);
-    } else if (block == 512) launch_step_t<T, 512, TICK_PLAIN>(x, mode, eps, np);
-    else if (block == 128) launch_step_t<T, 128, TICK_PLAIN>(x, mode, eps, np);
+      if (block == 64) launch_step_t<T, 64, TICK_LIT>(x, mode, eps, np, pl); else if (block == 512) launch_step_t<T, 512, TICK_LIT>(x, mode, eps, np, pl);
+      else launch_step_t<T, 256, TICK_LIT>(x, mode, eps, np, pl);
+    } else if (block == 512) launch_step_t<T, 512, TICK_PLAIN>(x, mode, eps, np, pl);
+    else if (block == 128) launch_step_t<T, 128, TICK_PLAIN>(x, mode, eps, np, pl);
     else if (block == 64) {
-      if (tick == 3 && x->litm_ok) launch_step_t<T, 64, TICK_PACKED_LITM>(x, mode, eps, np); else if (tick == 3) launch_step_t<T, 64, TICK_PACKED>(x, mode, eps, np); else launch_step_t<T, 64, TICK_PLAIN>(x, mode, eps, np);
+      if (tick == 3 && x->litm_ok) launch_step_t<T, 64, TICK_PACKED_LITM>(x, mode, eps, np, pl); else if (tick == 3) launch_step_t<T, 64, TICK_PACKED>(x, mode, eps, np, pl); else launch_step_t<T, 64, TICK_PLAIN>(x, mode, eps, np, pl);
     } else {
-      if (tick == 3 && x->litm_ok) launch_step_t<T, 256, TICK_PACKED_LITM>(x, mode, eps, np); else if (tick == 3) launch_step_t<T, 256, TICK_PACKED>(x, mode, eps, np); else launch_step_t<T, 256, TICK_PLAIN>(x, mode, eps, np);
+      if (tick == 3 && x->litm_ok) launch_step_t<T, 256, TICK_PACKED_LITM>(x, mode, eps, np, pl); else if (tick == 3) launch_step_t<T, 256, TICK_PACKED>(x, mode, eps, np, pl); else launch_step_t<T, 256, TICK_PLAIN>(x, mode, eps, np, pl);
     }
   }
 }
@@ -1063,6 +1330,68 @@ static int launch_period(dql_ctx* x, int mode, double eps, int n_periods = 1) {
   if (x->windowed && mode == MODE_TRAIN) x->window_launches += n_periods;  // counted in agent periods
   x->step_index += n_periods;
   x->launch_index += 1;
+  x->timer_launches += 1;
+  return DQL_OK;
+}
+// ONE population launch of n_periods agent periods for the active agents (active null = all): every active agent's launch arguments come from
+// ITS history (step index, launch parity, pending fold, level, seed, eps, episode-log row), exactly as launch_period builds them for a context of its own
+static int launch_pop(dql_ctx* x, int mode, const double* eps, const uint8_t* active, int n_periods) {
+  PopLaunch pl;
+  pl.n_active = 0;
+  for (int k = 0; k < x->n_agents; ++k) if (!active || active[k]) pl.agent[pl.n_active++] = k;
+  if (!pl.n_active) return DQL_OK;
+  for (int s = 0; s < pl.n_active; ++s)
+    if (x->elog && x->agents[pl.agent[s]]->elog_n + n_periods > x->elog_cap) return fail(DQL_ESTATE, "episode log full: read it with dql_episode_log_read before stepping on");
+  // staging: a pinned ring slot is rewritten only after the copy that last read it has run
+  const int slot = x->pop_slot;
+  x->pop_slot = (slot + 1) % DQL_POP_RING;
+  if (x->pop_busy[slot]) { HIP_TRY(hipEventSynchronize(x->pop_ev[slot])); x->pop_busy[slot] = false; }
+  PopAgentDesc* h = x->pop_h + (size_t)slot * DQL_MAX_AGENTS;
+  const size_t nw = (size_t)((x->n + 63) >> 6);
+  for (int s = 0; s < pl.n_active; ++s) {
+    const int k = pl.agent[s];
+    const dql_ctx* g = x->agents[k];
+    const long long j = g->step_index, l = g->launch_index;
+    PopAgentDesc& d = h[s];
+    memset(&d, 0, sizeof(d));
+    d.qa = g->tb[l & 1]; d.qb = g->tbb[l & 1]; d.acc_cur = (unsigned long long*)g->acc[l & 1];
+    d.qa_m = g->qa; d.qb_m = g->qb; d.cnt_m = g->count; d.qa_pub = g->tb[(l + 1) & 1]; d.qb_pub = g->tbb[(l + 1) & 1];
+    d.acc_prev = g->acc[(l + 1) & 1]; d.window = g->window;
+    d.stats = g->stats; d.mdp = (const char DQL_CONST_AS*)g->mdpk;
+    d.elog = x->elog ? x->elog + (size_t)g->elog_n * 2 * nw : nullptr;
+    d.faults = x->pop_faults + k;
+    d.fold = make_foldk(g, g->pending_periods);
+    d.step_index = j; d.seed = g->seed;
+    fill_schedule(g, j, d.mgr0, d.sched);
+    d.eps_thr = mode == MODE_TRAIN ? eps_threshold(eps[k]) : 0u;
+    d.have_prev = g->pending ? 1 : 0; d.working = g->cfg.working_curriculum_step;
+  }
+  PopAgentDesc* dd = x->pop_d + (size_t)slot * DQL_MAX_AGENTS;
+  HIP_TRY(hipMemcpyAsync(dd, h, (size_t)pl.n_active * sizeof(PopAgentDesc), hipMemcpyHostToDevice, x->stream));
+  HIP_TRY(hipEventRecord(x->pop_ev[slot], x->stream));
+  x->pop_busy[slot] = true;
+  pl.desc = dd;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (x->kernel_timer) {
+    HIP_TRY(hipEventCreate(&e0)); x->kev.push_back(e0);
+    if (hipEventCreate(&e1) != hipSuccess) { x->kev.pop_back(); (void)hipEventDestroy(e0); return fail(DQL_EHIP, "hipEventCreate failed"); }
+    x->kev.push_back(e1);
+    HIP_TRY(hipEventRecord(e0, x->stream));
+  }
+  if (x->dtype == DQL_F32) launch_step_b<float>(x, mode, 0.0, n_periods, &pl); else launch_step_b<double>(x, mode, 0.0, n_periods, &pl);
+  if (x->kernel_timer) HIP_TRY(hipEventRecord(e1, x->stream));
+  HIP_TRY(hipGetLastError());
+  int elog_n = 0;
+  for (int s = 0; s < pl.n_active; ++s) {  // what launch_period does to a context of its own
+    dql_ctx* g = x->agents[pl.agent[s]];
+    if (x->elog) g->elog_n += n_periods;
+    g->pending = (mode == MODE_TRAIN);
+    g->pending_periods = n_periods;
+    g->step_index += n_periods;
+    g->launch_index += 1;
+  }
+  for (dql_ctx* g : x->agents) elog_n = g->elog_n > elog_n ? g->elog_n : elog_n;
+  x->elog_n = elog_n;
   x->timer_launches += 1;
   return DQL_OK;
 }
@@ -1125,6 +1454,13 @@ template <typename T> static int get_obs_t(dql_ctx* x, double* out) {
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
+// on a population context (dql_pop_create) the single-agent calls act on agent 0 when it is the only one and are refused otherwise; external actions
+// and the multi-GPU exchanges are refused on every population
+static int pop_refused(const char* call, const char* instead) {
+  return fail(DQL_EINVAL, std::string(call) + " acts on one agent: on a population context with several agents use " + instead);
+}
+#define POP_SINGLE(x, call, instead, fwd) do { if ((x) && (x)->n_agents > 1) return pop_refused(call, instead); if ((x) && (x)->n_agents == 1) return (fwd); } while (0)
+#define POP_NEVER(x, call) do { if ((x) && (x)->n_agents) return fail(DQL_EINVAL, std::string(call) + " is not available on a population context (external actions and the multi-GPU exchanges are single-agent only)"); } while (0)
 extern "C" {
 
 int dql_abi_version(void) { return DQL_ABI_VERSION; }
@@ -1167,6 +1503,7 @@ int dql_config_default(dql_config* c) {
   return DQL_OK;
 }
 
+static int create_tables(dql_ctx* x);
 // allocation + initialisation of a fresh context; any failure leaves a partly built context for the caller to destroy
 static int create_impl(dql_ctx* x, const dql_config* cfg) {
 #define ALLOC(ptr, bytes) do { hipError_t _e = hipMalloc((void**)&(ptr), (bytes)); if (_e != hipSuccess) return fail(DQL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(_e)); } while (0)
@@ -1182,14 +1519,28 @@ static int create_impl(dql_ctx* x, const dql_config* cfg) {
   x->litm_ok = refm && !cfg->two_axis;
   ALLOC(x->sr, (size_t)NQ_REAL * (size_t)x->n * 4 * x->real_size);
   ALLOC(x->si, (size_t)x->n * sizeof(int4));
+  ALLOC(x->d_actions, (size_t)x->n);
+  HIP_TRY(hipMemsetAsync(x->sr, 0, (size_t)NQ_REAL * (size_t)x->n * 4 * x->real_size, x->stream));
+  HIP_TRY(hipMemsetAsync(x->d_actions, 2, (size_t)x->n, x->stream));
+  int rc = create_tables(x);
+  if (rc) return rc;
+  rc = (x->dtype == DQL_F32) ? launch_init<float>(x) : launch_init<double>(x);
+  if (rc) return rc;
+  // default alpha table (plateau only): callers install the reference schedule with dql_set_alpha_table
+  const double a0 = cfg->alpha_min;
+  return dql_set_alpha_table(x, &a0, 1);
+#undef ALLOC
+}
+// what a context needs besides its envs: tables, ping-pong copies, accumulators, window, statistics, MdpK (also the agents of a population)
+static int create_tables(dql_ctx* x) {
+#define ALLOC(ptr, bytes) do { hipError_t _e = hipMalloc((void**)&(ptr), (bytes)); if (_e != hipSuccess) return fail(DQL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(_e)); } while (0)
   ALLOC(x->qa, DQL_N_CELLS * sizeof(double)); ALLOC(x->qb, DQL_N_CELLS * sizeof(double)); ALLOC(x->count, DQL_N_CELLS * sizeof(double));
   ALLOC(x->qa_base, DQL_N_CELLS * sizeof(double)); ALLOC(x->count_base, DQL_N_CELLS * sizeof(double));
   ALLOC(x->qb_base, DQL_N_CELLS * sizeof(double));
   for (int k = 0; k < 2; ++k) { ALLOC(x->tb[k], DQL_N_CELLS * sizeof(double)); ALLOC(x->tbb[k], DQL_N_CELLS * sizeof(double)); ALLOC(x->acc[k], DQL_ACC_LEN * sizeof(long long)); }
   ALLOC(x->window_own, DQL_ACC_LEN * sizeof(long long)); x->window = x->window_own;
-  ALLOC(x->stats, sizeof(StatsDev)); ALLOC(x->d_actions, (size_t)x->n); ALLOC(x->mdpk, sizeof(MdpK<double>));
+  ALLOC(x->stats, sizeof(StatsDev)); ALLOC(x->mdpk, sizeof(MdpK<double>));
 #undef ALLOC
-  HIP_TRY(hipMemsetAsync(x->sr, 0, (size_t)NQ_REAL * (size_t)x->n * 4 * x->real_size, x->stream));
   HIP_TRY(hipMemsetAsync(x->qa, 0, DQL_N_CELLS * sizeof(double), x->stream)); HIP_TRY(hipMemsetAsync(x->qb, 0, DQL_N_CELLS * sizeof(double), x->stream));
   HIP_TRY(hipMemsetAsync(x->count, 0, DQL_N_CELLS * sizeof(double), x->stream));
   HIP_TRY(hipMemsetAsync(x->qa_base, 0, DQL_N_CELLS * sizeof(double), x->stream)); HIP_TRY(hipMemsetAsync(x->count_base, 0, DQL_N_CELLS * sizeof(double), x->stream));
@@ -1199,14 +1550,8 @@ static int create_impl(dql_ctx* x, const dql_config* cfg) {
     HIP_TRY(hipMemsetAsync(x->acc[k], 0, DQL_ACC_LEN * sizeof(long long), x->stream));
   }
   HIP_TRY(hipMemsetAsync(x->window, 0, DQL_ACC_LEN * sizeof(long long), x->stream));
-  HIP_TRY(hipMemsetAsync(x->stats, 0, sizeof(StatsDev), x->stream)); HIP_TRY(hipMemsetAsync(x->d_actions, 2, (size_t)x->n, x->stream));
-  int rc = upload_mdpk(x);
-  if (rc) return rc;
-  rc = (x->dtype == DQL_F32) ? launch_init<float>(x) : launch_init<double>(x);
-  if (rc) return rc;
-  // default alpha table (plateau only): callers install the reference schedule with dql_set_alpha_table
-  const double a0 = cfg->alpha_min;
-  return dql_set_alpha_table(x, &a0, 1);
+  HIP_TRY(hipMemsetAsync(x->stats, 0, sizeof(StatsDev), x->stream));
+  return upload_mdpk(x);
 }
 
 int dql_create(const dql_config* cfg, int device, int64_t n_envs, uint64_t seed, int64_t env_id_offset, dql_ctx** out) {
@@ -1238,6 +1583,11 @@ int dql_destroy(dql_ctx* x) {
   if (!x) return DQL_OK;
   (void)hipSetDevice(x->device);
   if (x->stream) (void)hipStreamSynchronize(x->stream);
+  for (dql_ctx* g : x->agents) (void)dql_destroy(g);
+  for (int s = 0; s < DQL_POP_RING; ++s) if (x->pop_ev[s]) (void)hipEventDestroy(x->pop_ev[s]);
+  if (x->pop_h) (void)hipHostFree(x->pop_h);
+  if (x->pop_d) (void)hipFree(x->pop_d);
+  if (x->pop_faults) (void)hipFree(x->pop_faults);
   for (hipEvent_t e : x->kev) (void)hipEventDestroy(e);
   for (hipEvent_t e : x->sev) (void)hipEventDestroy(e);
   for (int r = 0; r < DQL_P2P_MAX_RANKS; ++r) if (x->p2p_opened[r] && x->p2p_peer[r]) (void)hipIpcCloseMemHandle(x->p2p_peer[r]);
@@ -1248,7 +1598,7 @@ int dql_destroy(dql_ctx* x) {
   if (x->ev_actions) (void)hipEventDestroy(x->ev_actions);
   if (x->ev0) (void)hipEventDestroy(x->ev0);
   if (x->ev1) (void)hipEventDestroy(x->ev1);
-  if (x->stream) (void)hipStreamDestroy(x->stream);
+  if (x->stream && x->owns_stream) (void)hipStreamDestroy(x->stream);
   delete x;
   return DQL_OK;
 }
@@ -1296,11 +1646,13 @@ int dql_set_alpha_table(dql_ctx* x, const double* alpha, int32_t n) {
   HIP_TRY(hipMalloc((void**)&x->alpha_tab, (size_t)n * sizeof(double)));
   HIP_TRY(hipMemcpy(x->alpha_tab, alpha, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
   x->n_tab = n;
+  for (dql_ctx* g : x->agents) { int rc = dql_set_alpha_table(g, alpha, n); if (rc) return rc; }  // population: every agent
   return DQL_OK;
 }
 
 int dql_set_curriculum(dql_ctx* x, int32_t k) {
   CHECK_CTX(x);
+  POP_SINGLE(x, "dql_set_curriculum", "dql_pop_set_curriculum", dql_pop_set_curriculum(x, 0, k));
   if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "curriculum step must be in 0..4");
   HIP_TRY(hipSetDevice(x->device));
   int rc = flush_pending(x);
@@ -1330,6 +1682,7 @@ int dql_reset(dql_ctx* x, const uint8_t* mask) {
 
 int dql_step(dql_ctx* x, const uint8_t* actions) {
   CHECK_CTX(x);
+  POP_NEVER(x, "dql_step");
   if (!actions) return fail(DQL_EINVAL, "actions must not be null (use dql_train_steps / dql_eval_steps for on-device action selection)");
   HIP_TRY(hipSetDevice(x->device));
   // staged through pinned memory: the caller's buffer is free on return and nobody waits — except for the PREVIOUS step's read of the
@@ -1413,6 +1766,7 @@ int dql_step_outputs(dql_ctx* x, int32_t* idx_x, int32_t* idx_y, double* reward,
 }
 int dql_step_dev(dql_ctx* x, const uint8_t* dev_actions) {
   CHECK_CTX(x);
+  POP_NEVER(x, "dql_step_dev");
   if (!dev_actions) return fail(DQL_EINVAL, "dev_actions must not be null");
   HIP_TRY(hipSetDevice(x->device));
   x->ext_actions = dev_actions;
@@ -1422,6 +1776,7 @@ int dql_step_dev(dql_ctx* x, const uint8_t* dev_actions) {
 }
 int dql_train_steps(dql_ctx* x, int32_t n_steps, double eps) {
   CHECK_CTX(x);
+  POP_SINGLE(x, "dql_train_steps", "dql_pop_train_steps", dql_pop_train_steps(x, n_steps, &eps, nullptr));
   if (n_steps < 0) return fail(DQL_EINVAL, "n_steps must be >= 0");
   HIP_TRY(hipSetDevice(x->device));
   for (int i = 0; i < n_steps;) {
@@ -1433,6 +1788,7 @@ int dql_train_steps(dql_ctx* x, int32_t n_steps, double eps) {
 }
 int dql_eval_steps(dql_ctx* x, int32_t n_steps) {
   CHECK_CTX(x);
+  POP_SINGLE(x, "dql_eval_steps", "dql_pop_eval_steps", dql_pop_eval_steps(x, n_steps, nullptr));
   if (n_steps < 0) return fail(DQL_EINVAL, "n_steps must be >= 0");
   HIP_TRY(hipSetDevice(x->device));
   for (int i = 0; i < n_steps;) {
@@ -1551,10 +1907,12 @@ int dql_get_obs(dql_ctx* x, double* out) {
 int dql_flush(dql_ctx* x) {
   CHECK_CTX(x);
   HIP_TRY(hipSetDevice(x->device));
+  for (dql_ctx* g : x->agents) { int rc = flush_pending(g); if (rc) return rc; }  // population: every agent
   return flush_pending(x);
 }
 int dql_get_tables(dql_ctx* x, double* qa, double* qb, double* count) {
   CHECK_CTX(x);
+  POP_SINGLE(x, "dql_get_tables", "dql_pop_get_tables", dql_pop_get_tables(x, 0, qa, qb, count));
   HIP_TRY(hipSetDevice(x->device));
   { int rc = flush_pending(x); if (rc) return rc; }
   const size_t B = DQL_N_CELLS * sizeof(double);
@@ -1566,6 +1924,7 @@ int dql_get_tables(dql_ctx* x, double* qa, double* qb, double* count) {
 }
 int dql_set_tables(dql_ctx* x, const double* qa, const double* qb, const double* count) {
   CHECK_CTX(x);
+  POP_SINGLE(x, "dql_set_tables", "dql_pop_set_tables", dql_pop_set_tables(x, 0, qa, qb, count));
   HIP_TRY(hipSetDevice(x->device));
   { int rc = flush_pending(x); if (rc) return rc; }
   const size_t B = DQL_N_CELLS * sizeof(double);
@@ -1578,6 +1937,7 @@ int dql_set_tables(dql_ctx* x, const double* qa, const double* qb, const double*
 }
 int dql_transfer(dql_ctx* x, int32_t k, double ratio) {
   CHECK_CTX(x);
+  POP_SINGLE(x, "dql_transfer", "dql_pop_transfer", dql_pop_transfer(x, 0, k, ratio));
   if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "curriculum step must be in 0..4");
   HIP_TRY(hipSetDevice(x->device));
   { int rc = flush_pending(x); if (rc) return rc; }
@@ -1592,12 +1952,14 @@ int dql_transfer(dql_ctx* x, int32_t k, double ratio) {
 // ---- multi-GPU exchange ----
 int dql_set_sync_period(dql_ctx* x, int32_t k) {
   CHECK_CTX(x);
+  POP_NEVER(x, "dql_set_sync_period");
   if (k < 1) return fail(DQL_EINVAL, "sync period must be >= 1");
   x->sync_period = k;
   return DQL_OK;
 }
 int dql_set_windowed(dql_ctx* x, int32_t on) {
   CHECK_CTX(x);
+  POP_NEVER(x, "dql_set_windowed");
   HIP_TRY(hipSetDevice(x->device));
   { int rc = flush_pending(x); if (rc) return rc; }
   if (on && !x->windowed) {
@@ -1618,6 +1980,7 @@ int dql_diag_accum_dev_ptr(dql_ctx* x, void** dev_ptr, int64_t* n_int64) {
 }
 int dql_set_window_buffer(dql_ctx* x, void* dev_ptr) {
   CHECK_CTX(x);
+  POP_NEVER(x, "dql_set_window_buffer");
   HIP_TRY(hipSetDevice(x->device));
   { int rc = flush_pending(x); if (rc) return rc; }
   HIP_TRY(hipStreamSynchronize(x->stream));
@@ -1629,6 +1992,7 @@ int dql_set_window_buffer(dql_ctx* x, void* dev_ptr) {
 int dql_stream_handle(dql_ctx* x, void** s) { CHECK_CTX(x); if (s) *s = (void*)x->stream; return DQL_OK; }
 int dql_apply_accum(dql_ctx* x) {
   CHECK_CTX(x);
+  POP_NEVER(x, "dql_apply_accum");
   if (!x->windowed) return fail(DQL_ESTATE, "dql_apply_accum needs windowed accumulation (dql_set_windowed)");
   if (x->pending) return fail(DQL_ESTATE, "dql_apply_accum: call dql_flush before reducing the window (the last launch is not in it yet)");
   HIP_TRY(hipSetDevice(x->device));
@@ -1645,6 +2009,7 @@ int dql_apply_accum(dql_ctx* x) {
 }
 int dql_get_accum(dql_ctx* x, int64_t* out) {
   CHECK_CTX(x);
+  POP_NEVER(x, "dql_get_accum");
   HIP_TRY(hipSetDevice(x->device));
   { int rc = flush_pending(x); if (rc) return rc; }
   HIP_TRY(hipMemcpyAsync(out, x->window, DQL_ACC_LEN * sizeof(long long), hipMemcpyDeviceToHost, x->stream));
@@ -1653,15 +2018,17 @@ int dql_get_accum(dql_ctx* x, int64_t* out) {
 }
 int dql_set_accum(dql_ctx* x, const int64_t* in) {
   CHECK_CTX(x);
+  POP_NEVER(x, "dql_set_accum");
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipMemcpyAsync(x->window, in, DQL_ACC_LEN * sizeof(long long), hipMemcpyHostToDevice, x->stream));
   HIP_TRY(hipStreamSynchronize(x->stream));
   return DQL_OK;
 }
 
-int dql_get_step_index(dql_ctx* x, int64_t* step_index) { CHECK_CTX(x); if (!step_index) return fail(DQL_EINVAL, "null pointer"); *step_index = x->step_index; return DQL_OK; }
+int dql_get_step_index(dql_ctx* x, int64_t* step_index) { CHECK_CTX(x); POP_SINGLE(x, "dql_get_step_index", "dql_pop_get_step_index", dql_pop_get_step_index(x, 0, step_index)); if (!step_index) return fail(DQL_EINVAL, "null pointer"); *step_index = x->step_index; return DQL_OK; }
 int dql_set_step_index(dql_ctx* x, int64_t step_index) {
   CHECK_CTX(x);
+  POP_SINGLE(x, "dql_set_step_index", "dql_pop_set_step_index", dql_pop_set_step_index(x, 0, step_index));
   if (step_index < 0) return fail(DQL_EINVAL, "step_index must be >= 0");
   HIP_TRY(hipSetDevice(x->device));
   { int rc = flush_pending(x); if (rc) return rc; }
@@ -1674,6 +2041,7 @@ int dql_set_step_index(dql_ctx* x, int64_t step_index) {
 }
 int dql_publish_tables(dql_ctx* x) {
   CHECK_CTX(x);
+  POP_SINGLE(x, "dql_publish_tables", "dql_pop_publish_tables", dql_pop_publish_tables(x, 0));
   HIP_TRY(hipSetDevice(x->device));
   { int rc = flush_pending(x); if (rc) return rc; }
   return publish_master(x);
@@ -1682,6 +2050,7 @@ int dql_publish_tables(dql_ctx* x) {
 // ---- stats / timing / knobs ----
 int dql_stats_get(dql_ctx* x, dql_stats* out) {
   CHECK_CTX(x);
+  POP_SINGLE(x, "dql_stats_get", "dql_pop_stats_get", dql_pop_stats_get(x, 0, out));
   if (!out) return fail(DQL_EINVAL, "null pointer");
   HIP_TRY(hipSetDevice(x->device));
   StatsDev s;
@@ -1704,6 +2073,7 @@ int dql_stats_reset(dql_ctx* x) {
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipMemsetAsync(x->stats, 0, sizeof(StatsDev), x->stream));
   x->stats_step_base = x->step_index;
+  for (dql_ctx* g : x->agents) { int rc = dql_stats_reset(g); if (rc) return rc; }  // population: every agent
   return DQL_OK;
 }
 int dql_diag_timer_start(dql_ctx* x) {
@@ -1794,6 +2164,13 @@ int dql_set_option(dql_ctx* x, const char* name, int32_t value) {
 }
 
 // ---- episode log: which envs finished an episode in each agent period, and which of those reached the goal state ----
+// population: every agent's rows restart at the top, and the rows read so far are cleared (an agent that runs fewer periods than another leaves its words 0)
+static int pop_log_consumed(dql_ctx* x) {
+  if (!x->n_agents) return DQL_OK;
+  for (dql_ctx* g : x->agents) g->elog_n = 0;
+  if (x->elog_n) HIP_TRY(hipMemsetAsync(x->elog, 0, (size_t)x->elog_n * 2 * (size_t)((x->n + 63) >> 6) * sizeof(unsigned long long), x->stream));
+  return DQL_OK;
+}
 int dql_episode_log_enable(dql_ctx* x, int32_t capacity_periods) {
   CHECK_CTX(x);
   if (capacity_periods < 0) return fail(DQL_EINVAL, "capacity_periods must be >= 0");
@@ -1801,10 +2178,12 @@ int dql_episode_log_enable(dql_ctx* x, int32_t capacity_periods) {
   HIP_TRY(hipStreamSynchronize(x->stream));
   if (x->elog) { HIP_TRY(hipFree(x->elog)); x->elog = nullptr; }
   x->elog_cap = 0; x->elog_n = 0;
+  for (dql_ctx* g : x->agents) g->elog_n = 0;
   if (capacity_periods == 0) return DQL_OK;
   const size_t nw = (size_t)((x->n + 63) >> 6);
   if (hipMalloc((void**)&x->elog, (size_t)capacity_periods * 2 * nw * sizeof(unsigned long long)) != hipSuccess) { x->elog = nullptr; return fail(DQL_ENOMEM, "hipMalloc(episode log) failed"); }
   x->elog_cap = capacity_periods;
+  if (x->n_agents) HIP_TRY(hipMemsetAsync(x->elog, 0, (size_t)capacity_periods * 2 * nw * sizeof(unsigned long long), x->stream));  // words of agents that ran fewer periods read 0
   return DQL_OK;
 }
 int dql_episode_log_read(dql_ctx* x, uint64_t* done_masks, uint64_t* goal_masks, int32_t max_periods, int32_t* n_periods) {
@@ -1824,6 +2203,7 @@ int dql_episode_log_read(dql_ctx* x, uint64_t* done_masks, uint64_t* goal_masks,
     }
   }
   *n_periods = x->elog_n;
+  { int rc = pop_log_consumed(x); if (rc) return rc; }
   x->elog_n = 0;
   return DQL_OK;
 }
@@ -1849,6 +2229,7 @@ int dql_episode_log_read_words(dql_ctx* x, uint64_t* done_masks, uint64_t* goal_
     }
   }
   *n_periods = x->elog_n;
+  { int rc = pop_log_consumed(x); if (rc) return rc; }
   x->elog_n = 0;
   return DQL_OK;
 }
@@ -2468,12 +2849,14 @@ int dql_comm_barrier(dql_comm* c) {
 }
 
 int dql_attach_comm(dql_ctx* x, dql_comm* c) {
+  POP_NEVER(x, "dql_attach_comm");
   CHECK_CTX(x);
   if (c && c->device != x->device) return fail(DQL_EINVAL, "communicator and context live on different devices");
   x->comm = c;
   return DQL_OK;
 }
 int dql_allreduce_window(dql_ctx* x) {
+  POP_NEVER(x, "dql_allreduce_window");
   CHECK_CTX(x);
   if (!x->comm) return fail(DQL_ESTATE, "dql_allreduce_window: no communicator attached (dql_attach_comm)");
   if (!x->windowed) return fail(DQL_ESTATE, "dql_allreduce_window needs windowed accumulation (dql_set_windowed)");
@@ -2490,6 +2873,7 @@ int dql_allreduce_window(dql_ctx* x) {
 
 // ---- one-shot peer-to-peer exchange ----
 int dql_p2p_create(dql_ctx* x, int32_t rank, int32_t world, uint8_t* handle_out) {
+  POP_NEVER(x, "dql_p2p_create");
   CHECK_CTX(x);
   if (!handle_out) return fail(DQL_EINVAL, "null pointer");
   static_assert(sizeof(hipIpcMemHandle_t) == DQL_P2P_HANDLE_BYTES, "DQL_P2P_HANDLE_BYTES must be the size of hipIpcMemHandle_t");
@@ -2513,6 +2897,7 @@ int dql_p2p_create(dql_ctx* x, int32_t rank, int32_t world, uint8_t* handle_out)
   return DQL_OK;
 }
 int dql_p2p_connect(dql_ctx* x, const uint8_t* all_handles) {
+  POP_NEVER(x, "dql_p2p_connect");
   CHECK_CTX(x);
   if (!all_handles) return fail(DQL_EINVAL, "null pointer");
   if (!x->p2p_buf) return fail(DQL_ESTATE, "dql_p2p_connect: call dql_p2p_create first");
@@ -2529,6 +2914,7 @@ int dql_p2p_connect(dql_ctx* x, const uint8_t* all_handles) {
   return DQL_OK;
 }
 int dql_p2p_connect_local(dql_ctx* x, dql_ctx* const* peers) {
+  POP_NEVER(x, "dql_p2p_connect_local");
   CHECK_CTX(x);
   if (!peers) return fail(DQL_EINVAL, "null pointer");
   if (!x->p2p_buf) return fail(DQL_ESTATE, "dql_p2p_connect_local: call dql_p2p_create first");
@@ -2559,6 +2945,7 @@ static P2PPushArgs p2p_args(dql_ctx* x, unsigned long long seq) {
   return a;
 }
 int dql_p2p_push_window(dql_ctx* x) {
+  POP_NEVER(x, "dql_p2p_push_window");
   CHECK_CTX(x);
   { int rc = p2p_ready(x, "dql_p2p_push_window"); if (rc) return rc; }
   if (x->p2p_pushed) return fail(DQL_ESTATE, "dql_p2p_push_window: the previous push has not been waited for (dql_p2p_wait_window)");
@@ -2579,6 +2966,7 @@ int dql_p2p_push_window(dql_ctx* x) {
   return DQL_OK;
 }
 int dql_p2p_wait_window(dql_ctx* x) {
+  POP_NEVER(x, "dql_p2p_wait_window");
   CHECK_CTX(x);
   { int rc = p2p_ready(x, "dql_p2p_wait_window"); if (rc) return rc; }
   if (!x->p2p_pushed) return fail(DQL_ESTATE, "dql_p2p_wait_window: nothing pushed (dql_p2p_push_window)");
@@ -2593,6 +2981,7 @@ int dql_p2p_wait_window(dql_ctx* x) {
   return DQL_OK;
 }
 int dql_p2p_exchange_window(dql_ctx* x) {
+  POP_NEVER(x, "dql_p2p_exchange_window");
   const int rc = dql_p2p_push_window(x);
   return rc ? rc : dql_p2p_wait_window(x);
 }
@@ -2603,6 +2992,136 @@ int dql_p2p_status(dql_ctx* x, int32_t* failed_seq) {
   unsigned long long v = 0;
   { int rc = p2p_failed_seq(x, &v); if (rc) return rc; }
   *failed_seq = (int32_t)(v > 0x7fffffffull ? 0x7fffffffull : v);
+  return DQL_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// populations (include/dql.h dql_pop_*)
+// ---------------------------------------------------------------------------------------------
+static int pop_agent(dql_ctx* x, int32_t k, dql_ctx** g) {
+  CHECK_CTX(x);
+  if (!x->n_agents) return fail(DQL_EINVAL, "not a population context (dql_pop_create)");
+  if (k < 0 || k >= x->n_agents) return fail(DQL_EINVAL, "agent index out of range");
+  HIP_TRY(hipSetDevice(x->device));
+  *g = x->agents[k];
+  return DQL_OK;
+}
+template <typename T> static int launch_init_agent(dql_ctx* x, int k) {
+  // k_init over agent k's E envs alone: the state arrays keep the population's stride (n = K E), the base moves to the agent's first env, and the grid
+  // is exactly E threads (E is a multiple of 512), so that no thread reaches past the agent's slice
+  const dql_ctx* g = x->agents[k];
+  InitArgs<T> a;
+  a.c = make_simk<T>(x->cfg);
+  a.sr = (Quad<T>*)x->sr + k * x->pop_E; a.si = x->si + k * x->pop_E; a.n = x->n; a.seed = g->seed; a.env_id_offset = 0;
+  const dql_config& c = x->cfg;
+  a.hover = std::sqrt((T)(c.mass * c.gravity / (4.0 * c.k_f)));
+  a.vz_integ = (T)(c.mass * c.gravity / c.pid_vz[1]);
+  a.r_lo = (T)c.mp_r_lo; a.r_hi = (T)c.mp_r_hi; a.t_lo = (T)c.mp_t_lo; a.t_hi = (T)c.mp_t_hi;
+  const int B = 256;
+  hipLaunchKernelGGL(k_init<T>, dim3((unsigned)(x->pop_E / B)), dim3(B), 0, x->stream, a);
+  HIP_TRY(hipGetLastError());
+  return DQL_OK;
+}
+static int pop_create_impl(dql_ctx* x, const uint64_t* seeds) {
+  int rc = create_impl(x, &x->cfg);
+  if (rc) return rc;
+  for (int k = 0; k < x->n_agents; ++k) {
+    dql_ctx* g = new dql_ctx();
+    x->agents.push_back(g);
+    g->cfg = x->cfg; g->device = x->device; g->n = x->pop_E; g->seed = seeds[k]; g->env_id_offset = 0; g->dtype = x->dtype; g->real_size = x->real_size;
+    g->stream = x->stream; g->owns_stream = false; g->n_simds = x->n_simds; g->kal_fix = x->kal_fix; g->lit_ok = x->lit_ok; g->litm_ok = x->litm_ok;
+    rc = create_tables(g);
+    if (rc) return rc;
+    const double a0 = x->cfg.alpha_min;
+    rc = dql_set_alpha_table(g, &a0, 1);
+    if (rc) return rc;
+    rc = x->dtype == DQL_F32 ? launch_init_agent<float>(x, k) : launch_init_agent<double>(x, k);
+    if (rc) return rc;
+  }
+  const size_t ring = (size_t)DQL_POP_RING * DQL_MAX_AGENTS * sizeof(PopAgentDesc);
+  if (hipHostMalloc((void**)&x->pop_h, ring, hipHostMallocDefault) != hipSuccess) { x->pop_h = nullptr; return fail(DQL_ENOMEM, "hipHostMalloc(launch descriptors) failed"); }
+  if (hipMalloc((void**)&x->pop_d, ring) != hipSuccess) { x->pop_d = nullptr; return fail(DQL_ENOMEM, "hipMalloc(launch descriptors) failed"); }
+  if (hipMalloc((void**)&x->pop_faults, (size_t)x->n_agents * sizeof(unsigned long long)) != hipSuccess) { x->pop_faults = nullptr; return fail(DQL_ENOMEM, "hipMalloc(fault counters) failed"); }
+  HIP_TRY(hipMemsetAsync(x->pop_faults, 0, (size_t)x->n_agents * sizeof(unsigned long long), x->stream));
+  for (int s = 0; s < DQL_POP_RING; ++s) HIP_TRY(hipEventCreateWithFlags(&x->pop_ev[s], hipEventDisableTiming));
+  HIP_TRY(hipStreamSynchronize(x->stream));
+  return DQL_OK;
+}
+
+extern "C" {
+
+int dql_pop_create(const dql_config* cfg, int device, int32_t n_agents, int64_t envs_per_agent, const uint64_t* seeds, dql_ctx** out) {
+  if (!out) return fail(DQL_EINVAL, "null out pointer");
+  *out = nullptr;
+  int rc = check_config(cfg);
+  if (rc) return rc;
+  if (n_agents < 1 || n_agents > DQL_MAX_AGENTS) return fail(DQL_EINVAL, "n_agents must be in 1..16 (DQL_MAX_AGENTS)");
+  if (envs_per_agent < 512 || envs_per_agent % 512) return fail(DQL_EINVAL, "envs_per_agent must be a positive multiple of 512 (a workgroup of any size then holds one agent)");
+  if ((long long)n_agents * envs_per_agent > (1ll << 31)) return fail(DQL_EINVAL, "n_agents * envs_per_agent must be at most 2^31");
+  if (!seeds) return fail(DQL_EINVAL, "seeds must not be null (one per agent)");
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (ndev < 1) return fail(DQL_EHIP, "no HIP device visible: libdql_hip needs an MI355X (there is no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(DQL_EINVAL, "device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  dql_ctx* x = new dql_ctx();
+  x->cfg = *cfg; x->device = device; x->n = (long long)n_agents * envs_per_agent; x->seed = seeds[0]; x->env_id_offset = 0; x->dtype = cfg->dtype;
+  x->real_size = cfg->dtype == DQL_F32 ? 4 : 8;
+  x->n_agents = n_agents; x->pop_E = envs_per_agent;
+  rc = pop_create_impl(x, seeds);
+  if (rc) {
+    const std::string why = g_err;
+    dql_destroy(x);
+    return fail(rc, why);
+  }
+  *out = x;
+  return DQL_OK;
+}
+int dql_pop_n_agents(dql_ctx* x, int32_t* n) { CHECK_CTX(x); if (!n) return fail(DQL_EINVAL, "null pointer"); *n = x->n_agents; return DQL_OK; }
+static int pop_steps(dql_ctx* x, int mode, int32_t n_steps, const double* eps, const uint8_t* active) {
+  CHECK_CTX(x);
+  if (!x->n_agents) return fail(DQL_EINVAL, "not a population context (dql_pop_create)");
+  if (n_steps < 0) return fail(DQL_EINVAL, "n_steps must be >= 0");
+  if (mode == MODE_TRAIN && !eps) return fail(DQL_EINVAL, "eps must not be null (one per agent)");
+  HIP_TRY(hipSetDevice(x->device));
+  for (int i = 0; i < n_steps;) {
+    const int np = n_steps - i < x->periods_per_launch ? n_steps - i : x->periods_per_launch;
+    int rc = launch_pop(x, mode, eps, active, np); if (rc) return rc;
+    i += np;
+  }
+  return DQL_OK;
+}
+int dql_pop_train_steps(dql_ctx* x, int32_t n_steps, const double* eps, const uint8_t* active_or_null) { return pop_steps(x, MODE_TRAIN, n_steps, eps, active_or_null); }
+int dql_pop_eval_steps(dql_ctx* x, int32_t n_steps, const uint8_t* active_or_null) { return pop_steps(x, MODE_EVAL, n_steps, nullptr, active_or_null); }
+int dql_pop_set_curriculum(dql_ctx* x, int32_t agent, int32_t level) {
+  dql_ctx* g = nullptr;
+  int rc = pop_agent(x, agent, &g); if (rc) return rc;
+  if (level < 0 || level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "curriculum step must be in 0..4");
+  rc = flush_pending(g); if (rc) return rc;
+  rc = publish_master(g); if (rc) return rc;
+  g->cfg.working_curriculum_step = level;
+  rc = upload_mdpk(g); if (rc) return rc;
+  hipLaunchKernelGGL(k_mark_reset, dim3((unsigned)((x->pop_E + 255) / 256)), dim3(256), 0, x->stream, x->si + agent * x->pop_E, (const uint8_t*)nullptr, (long long)x->pop_E);
+  HIP_TRY(hipGetLastError());
+  return DQL_OK;
+}
+int dql_pop_get_tables(dql_ctx* x, int32_t agent, double* qa, double* qb, double* count) { dql_ctx* g = nullptr; int rc = pop_agent(x, agent, &g); return rc ? rc : dql_get_tables(g, qa, qb, count); }
+int dql_pop_set_tables(dql_ctx* x, int32_t agent, const double* qa, const double* qb, const double* count) { dql_ctx* g = nullptr; int rc = pop_agent(x, agent, &g); return rc ? rc : dql_set_tables(g, qa, qb, count); }
+int dql_pop_transfer(dql_ctx* x, int32_t agent, int32_t k, double ratio) { dql_ctx* g = nullptr; int rc = pop_agent(x, agent, &g); return rc ? rc : dql_transfer(g, k, ratio); }
+int dql_pop_publish_tables(dql_ctx* x, int32_t agent) { dql_ctx* g = nullptr; int rc = pop_agent(x, agent, &g); return rc ? rc : dql_publish_tables(g); }
+int dql_pop_stats_get(dql_ctx* x, int32_t agent, dql_stats* out) { dql_ctx* g = nullptr; int rc = pop_agent(x, agent, &g); return rc ? rc : dql_stats_get(g, out); }
+int dql_pop_get_step_index(dql_ctx* x, int32_t agent, int64_t* j) { dql_ctx* g = nullptr; int rc = pop_agent(x, agent, &g); return rc ? rc : dql_get_step_index(g, j); }
+int dql_pop_set_step_index(dql_ctx* x, int32_t agent, int64_t j) { dql_ctx* g = nullptr; int rc = pop_agent(x, agent, &g); return rc ? rc : dql_set_step_index(g, j); }
+int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
+  dql_ctx* g = nullptr;
+  int rc = pop_agent(x, agent, &g); if (rc) return rc;
+  if (!n) return fail(DQL_EINVAL, "null pointer");
+  unsigned long long v = 0;
+  HIP_TRY(hipMemcpyAsync(&v, x->pop_faults + agent, sizeof(v), hipMemcpyDeviceToHost, x->stream));
+  HIP_TRY(hipStreamSynchronize(x->stream));
+  *n = (int64_t)v;
   return DQL_OK;
 }
 

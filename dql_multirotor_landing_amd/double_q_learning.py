@@ -7,6 +7,7 @@ does (B1, B4)."""
 from __future__ import annotations
 
 import os
+import threading
 from pathlib import Path
 from typing import Tuple, Union
 
@@ -111,7 +112,7 @@ class DoubleQLearningAgent:
     def save(self, save_path: Path):
         save_path = Path(save_path)
         for name, arr in (("Q_table_a.npy", self.Q_table_a), ("Q_table_b.npy", self.Q_table_b), ("state_action_count.npy", self.state_action_counter)):
-            tmp = save_path / f".{name}.{os.getpid()}.tmp"  # same bytes as the reference's np.save; a reader never sees half a table
+            tmp = save_path / f".{name}.{os.getpid()}.{threading.get_ident()}.tmp"  # (per thread too: trainers of a population share a process)  # same bytes as the reference's np.save; a reader never sees half a table
             with open(tmp, "wb") as f:
                 np.save(f, np.ascontiguousarray(arr, dtype=np.float64))
             os.replace(tmp, save_path / name)

@@ -103,7 +103,7 @@ class Trainer:
                  judge_envs: Optional[int] = 1, eps_episode_scale: float = 1.0, quirks: Optional[int] = None, checkpoint_env_state: bool = True,
                  periods_per_launch: int = 1, eps_tail: Optional[float] = None, eps_tail_after: float = 0.0, population_gate: Optional[float] = None,
                  env_kw: Optional[Dict[str, Any]] = None, restart_after: Optional[float] = None, transfer_counts: float = 0.0, step_back_after: Optional[int] = None, max_step_backs: int = 3,
-                 comm=None, reducer_factory=None) -> None:
+                 comm=None, reducer_factory=None, engine_factory=None) -> None:
         np.random.seed(seed)
         if mode not in ("reference", "paper"):
             raise ValueError("mode must be 'reference' or 'paper'")
@@ -187,6 +187,11 @@ class Trainer:
         self._reducer_factory = reducer_factory
         self._rank = self._comm.rank if self._comm else 0
         self._world = self._comm.world if self._comm else 1
+        # engine_factory(cfg, n_envs, seed, device) -> the engine to train on instead of Engine(...), e.g. one agent of a population
+        # (population.PopulationWave); single-process, unwindowed runs only
+        if engine_factory is not None and (self._world > 1 or reducer_factory is not None or self._sync_period is not None):
+            raise ValueError("engine_factory serves single-process runs without a reducer or sync_period")
+        self._engine_factory = engine_factory
         self.history = []  # one record per finished curriculum level
         self._engine: Optional[Engine] = None
         self._progress: Optional[Dict[str, Any]] = None  # bookkeeping of the level in flight (what a checkpoint has to carry)
@@ -351,6 +356,11 @@ class Trainer:
 
     # ---- pkg/trainer.py:169-245 ----
     def _make_engine(self, cfg):
+        if self._engine_factory is not None:
+            eng = self._engine_factory(cfg, self._n_envs, self._seed, self._device)
+            if self._periods_per_launch != 1:
+                eng.set_option("periods_per_launch", self._periods_per_launch)
+            return eng, ShardedRunner(eng, None)
         sync = self._sync_period if self._sync_period is not None else (2 if (self._world > 1 or self._reducer_factory is not None) else None)
         if self._world > 1 or self._reducer_factory is not None or sync is not None:
             if self._chunk_steps % sync or sync % self._periods_per_launch:

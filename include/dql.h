@@ -431,6 +431,34 @@ int dql_agent_update(int device, double* qa, double* qb, double* count, const in
 /* DoubleQLearningAgent.transfer_learning (pkg/double_q_learning.py:77-89) on host tables: Q[k] = Q[k-1] * ratio (k = 0 wraps, B6) */
 int dql_agent_transfer(int device, double* qa, double* qb, int32_t k, double ratio);
 
+/* ---- populations: K independent agents in one context, stepped by one launch ----
+ * Agent k owns envs [k E, (k+1) E) (E = envs_per_agent, a multiple of 512) and has its own Q tables, visit counters, accumulators,
+ * curriculum level, seed, step index, statistics and exploration rate.  Agent k is bit-identical to a context made with
+ * dql_create(cfg, device, E, seeds[k], env_id_offset = 0) and driven through the same per-agent calls; launches in which it is inactive
+ * do not touch it (the stand-alone context skips them).
+ * Whole-context calls act on all K E envs in agent-major order: dql_reset, dql_get_states / rewards / dones / actions / obs,
+ * dql_step_outputs, dql_get/set_sim_state, dql_get/set_sim_ints, dql_episode_log_* (a period row spans all K E envs; agent k's rows
+ * are its own periods since the last read, words of agents that ran fewer periods are 0), dql_set_option (periods_per_launch, block,
+ * tick), dql_set_alpha_table (every agent), dql_flush (every agent), dql_stats_reset (every agent), dql_sync, dql_n_envs, dql_destroy.
+ * With n_agents > 1 the single-agent calls (dql_train_steps, dql_eval_steps, dql_get/set_tables, dql_transfer, dql_set_curriculum,
+ * dql_publish_tables, dql_stats_get, dql_get/set_step_index) return DQL_EINVAL naming their dql_pop_* form; with n_agents == 1 they act
+ * on agent 0.  External actions (dql_step, dql_step_dev) and everything windowed, RCCL or peer-to-peer are refused on every population.
+ * active_or_null: uint8[n_agents], non-zero = step this agent (null = all).  eps: double[n_agents]. */
+#define DQL_MAX_AGENTS 16
+int dql_pop_create(const dql_config* cfg, int device, int32_t n_agents, int64_t envs_per_agent, const uint64_t* seeds, dql_ctx** out);
+int dql_pop_n_agents(dql_ctx* ctx, int32_t* n);
+int dql_pop_train_steps(dql_ctx* ctx, int32_t n_steps, const double* eps, const uint8_t* active_or_null);
+int dql_pop_eval_steps(dql_ctx* ctx, int32_t n_steps, const uint8_t* active_or_null);
+int dql_pop_set_curriculum(dql_ctx* ctx, int32_t agent, int32_t level); /* flush, publish, level, reset of that agent's envs only */
+int dql_pop_get_tables(dql_ctx* ctx, int32_t agent, double* qa, double* qb, double* count);
+int dql_pop_set_tables(dql_ctx* ctx, int32_t agent, const double* qa, const double* qb, const double* count);
+int dql_pop_transfer(dql_ctx* ctx, int32_t agent, int32_t k, double ratio);
+int dql_pop_publish_tables(dql_ctx* ctx, int32_t agent);
+int dql_pop_stats_get(dql_ctx* ctx, int32_t agent, dql_stats* out);
+int dql_pop_get_step_index(dql_ctx* ctx, int32_t agent, int64_t* j);
+int dql_pop_set_step_index(dql_ctx* ctx, int32_t agent, int64_t j);
+int dql_pop_index_faults(dql_ctx* ctx, int32_t agent, int64_t* n); /* targets dropped by the step kernel's bounds guard (0 unless a bug) */
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,8 @@ if __name__ == "__main__":
     ap.add_argument("--attempts", type=int, default=1, help="whole curricula to train (seed + 7919 j) until one has every level promoted by the rule and lands >= --accept-touchdown of 4 096 greedy "
                                                           "episodes (dql_multirotor_landing_amd/attempts.py); none accepted: the best seen is kept.  1 (default): one run, the reference's situation; bench.py: 6")
     ap.add_argument("--accept-touchdown", type=float, default=0.875, help="default: what the reference's own stage-4 tables land in such a batch")
+    ap.add_argument("--concurrent", type=int, default=1, help="with --attempts: fly this many attempts at once as the agents of one population (one GPU, "
+                                                               "one launch per chunk; single process, no --sync-period); the chosen attempt and its tables are those of --concurrent 1")
     ap.add_argument("--seed", type=int, default=42)
     a = ap.parse_args()
     import os
@@ -77,12 +79,13 @@ if __name__ == "__main__":
     from dql_multirotor_landing_amd.comm import RcclComm
     comm = RcclComm.from_env(local) if world > 1 else None  # ONE communicator for every attempt
 
-    def make_trainer(j):
+    def make_trainer(j, engine_factory=None):
         out = a.out if (a.attempts == 1 or a.out is None) else f"{a.out}/attempt{j}"
         return Trainer(n_envs=a.envs, mode=a.mode, save_path=out, dtype=F32 if a.dtype == "f32" else F64, chunk_steps=a.chunk, device=local if world > 1 else None,
                        promotion_rule=a.promotion_rule, sync_period=a.sync_period, curriculum_steps=a.levels, t_max=a.t_max, judge_envs=a.judge_envs,
                        successive_successful_episodes=a.window, seed=attempt_seed(a.seed, j), comm=comm,
-                       max_steps_per_level=a.max_steps_per_level, max_num_episodes=a.max_episodes, quiet=not a.verbose, fold_per_step=a.fold_per_step, eps_floor=a.eps_floor, success_rate=a.success_rate, **extra)
+                       max_steps_per_level=a.max_steps_per_level, max_num_episodes=a.max_episodes, quiet=not a.verbose, fold_per_step=a.fold_per_step, eps_floor=a.eps_floor, success_rate=a.success_rate,
+                       engine_factory=engine_factory, **extra)
 
     if a.attempts == 1:
         tr = make_trainer(0)
@@ -95,7 +98,7 @@ if __name__ == "__main__":
         def score(t):
             q = Q_PAPER if a.mode == "paper" else Q_REFERENCE  # (the worlds scripts/simulation.py --mode flies)
             return landing_score(t._double_q_learning_agent._padded(), 4096, a.levels - 1, seed=SELECTION_SEED, device=t._device, quirks=q)
-        res = curriculum_attempts(make_trainer, score, max_attempts=a.attempts, accept_touchdown=a.accept_touchdown, comm=comm, rank=rank)
+        res = curriculum_attempts(make_trainer, score, max_attempts=a.attempts, accept_touchdown=a.accept_touchdown, comm=comm, rank=rank, concurrency=a.concurrent)
         tr, hist = res["trainer"], res["history"]
         out = {"history": hist, "save_path": str(tr._save_path), "world": world, "chosen_attempt": res["chosen"], "accepted": res["accepted"], "attempts": res["attempts"]}
     if rank == 0:
