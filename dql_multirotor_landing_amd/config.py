@@ -208,6 +208,37 @@ class DqlConfig:
             raise ValueError("alpha table too short: plateau alpha_min not reached")
         return tab
 
+    def max_abs_td_target(self) -> float:
+        """Largest |TD target| r + gamma * Q(s', a') this MDP can produce.  Per axis and step, the reward of
+        pkg/mdp.py:441-541 is bounded at level k by its clipped shaping terms |w_p| lim_v dt and |w_v| lim_a dt, the unclipped pitch
+        term |w_theta|^2 / theta_max lim_v (|pitch set point| <= theta_max), |w_dur| lim_v dt and the terminal term max(|w_succ|, |w_fail|) r_max.
+        With |r| <= R and tables that start within R / (1 - gamma) (zero, or the reference's stage-4 tables), every target and every
+        fold (a convex combination of the cell and its mean target) stays within Q* = R / (1 - gamma).  2^-10 relative margin for the
+        float32 reward's rounding.  inf for gamma >= 1."""
+        dt = 1.0 / self.f_ag
+        r = 0.0
+        for k in range(MAX_LEVELS):
+            rp, rv = abs(self.w_p) * self.lim_v[k] * dt, abs(self.w_v) * self.lim_a[k] * dt
+            rth_max = abs(self.w_theta) * (self.delta_theta / self.theta_max) * self.lim_v[k]
+            rd = abs(self.w_dur) * self.lim_v[k] * dt
+            rth = abs(self.w_theta) * abs(self.w_theta) / self.theta_max * self.lim_v[k]
+            r = max(r, rp + rv + rth + rd + max(abs(self.w_succ), abs(self.w_fail)) * (rp + rv + rth_max + rd))
+        return math.inf if self.gamma >= 1.0 else r / (1.0 - self.gamma) * (1.0 + 2.0 ** -10)
+
+    def accum_visit_limit(self) -> int:
+        """Most targets one int64 accumulator cell may sum (fixed point, TARGET_FRAC_BITS fraction bits) without leaving int64:
+        (2^63 - 1) // (ceil(Q* 2^TARGET_FRAC_BITS) + 1), the + 1 for the rounding of each target.  A target is saturated at 2^50 in
+        fixed point, which bounds it when Q* does not."""
+        t = min(self.max_abs_td_target() * 2.0 ** TARGET_FRAC_BITS, 2.0 ** 50)
+        return ((1 << 63) - 1) // (math.ceil(t) + 1)
+
+    def check_accum_headroom(self, visits_per_cell: int, what: str) -> None:
+        """ValueError naming the limit when `visits_per_cell` targets could overflow one accumulator cell"""
+        lim = self.accum_visit_limit()
+        if visits_per_cell > lim:
+            raise ValueError(f"{what}: up to {visits_per_cell} TD targets could land in one table cell, more than the {lim} an int64 "
+                             f"accumulator holds at |target| <= {self.max_abs_td_target():.6g} (DqlConfig.accum_visit_limit)")
+
 
 def training_config(level: int = 0, **kw) -> DqlConfig:
     """TrainingLandingEnv as the Trainer builds it (pkg/trainer.py:176-183)."""

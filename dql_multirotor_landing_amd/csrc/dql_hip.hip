@@ -1146,6 +1146,7 @@ struct dql_ctx {
   hipEvent_t pop_ev[8] = {nullptr};                     // per ring slot: recorded behind the slot's copy (the staging slot is free again once it fired)
   bool pop_busy[8] = {false};
   int pop_slot = 0;
+  int last_step[5] = {0, 0, 0, 0, 0};  // the step kernel the latest launch ran (dql_diag_step_instance): sizeof(T), BLOCK, TICK, XMODE, population
 };
 #define DQL_POP_RING 8
 
@@ -1222,6 +1223,10 @@ static void fill_schedule(const dql_ctx* x, long long j, long long* mgr0, int* s
     sched[p] = n_ticks | (phase << 8) | (last_mgr << 16);                // check_config: n_ticks, manager_div <= 255
   }
 }
+// the template arguments of the step kernel a launch runs, for dql_diag_step_instance (tests assert which instance the host picked)
+static void note_step(dql_ctx* x, int bytes, int block, int tick, int xmode, int pop) {
+  x->last_step[0] = bytes; x->last_step[1] = block; x->last_step[2] = tick; x->last_step[3] = xmode; x->last_step[4] = pop;
+}
 // a population launch: the active agents in slot order and their descriptors (already staged on the device)
 struct PopLaunch { int n_active; int agent[DQL_MAX_AGENTS]; const PopAgentDesc* desc; };
 template <typename T> static StepArgs<T> make_step_args(dql_ctx* x, int mode, double eps, int envs_per_block, int n_periods) {
@@ -1255,11 +1260,11 @@ template <typename T, int BLOCK, int TICK> static void launch_pop_t(dql_ctx* x, 
   for (int s = 0; s < DQL_MAX_AGENTS; ++s) pa.agent[s] = s < pl.n_active ? pl.agent[s] : 0;
   const dim3 grid((unsigned)(pl.n_active * (pa.blocks_per_agent + pa.writer_blocks))), block(BLOCK);
   if constexpr (sizeof(T) == 4 && TICK == TICK_PACKED_LITM) {
-    hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, pa);
+    note_step(x, sizeof(T), BLOCK, TICK, X_ONLY, 1); hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, pa);
   } else if constexpr (sizeof(T) == 4 && (TICK == TICK_LIT || tick_is_packed(TICK))) {
-    if (x->cfg.two_axis) hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_TWO>), grid, block, 0, x->stream, pa);
-    else hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, pa);
-  } else hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_RUNTIME>), grid, block, 0, x->stream, pa);
+    if (x->cfg.two_axis) { note_step(x, sizeof(T), BLOCK, TICK, X_TWO, 1); hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_TWO>), grid, block, 0, x->stream, pa); }
+    else { note_step(x, sizeof(T), BLOCK, TICK, X_ONLY, 1); hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, pa); }
+  } else { note_step(x, sizeof(T), BLOCK, TICK, X_RUNTIME, 1); hipLaunchKernelGGL((k_step_pop<T, BLOCK, TICK, X_RUNTIME>), grid, block, 0, x->stream, pa); }
 }
 template <typename T, int BLOCK, int TICK> static void launch_step_t(dql_ctx* x, int mode, double eps, int n_periods, const PopLaunch* pl) {
   if (pl) { launch_pop_t<T, BLOCK, TICK>(x, mode, n_periods, *pl); return; }
@@ -1268,11 +1273,11 @@ template <typename T, int BLOCK, int TICK> static void launch_step_t(dql_ctx* x,
   const dim3 grid((unsigned)(a.env_blocks + writer_blocks)), block(BLOCK);
   // the layouts launch_step_b picks by itself come in an x-axis and a two-axis instance (agent_period's XMODE); the others decide at run time
   if constexpr (sizeof(T) == 4 && TICK == TICK_PACKED_LITM) {  // x-axis configs only (create_impl: litm_ok)
-    hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, a);
+    note_step(x, sizeof(T), BLOCK, TICK, X_ONLY, 0); hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, a);
   } else if constexpr (sizeof(T) == 4 && (TICK == TICK_LIT || tick_is_packed(TICK))) {
-    if (x->cfg.two_axis) hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_TWO>), grid, block, 0, x->stream, a);
-    else hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, a);
-  } else hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_RUNTIME>), grid, block, 0, x->stream, a);
+    if (x->cfg.two_axis) { note_step(x, sizeof(T), BLOCK, TICK, X_TWO, 0); hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_TWO>), grid, block, 0, x->stream, a); }
+    else { note_step(x, sizeof(T), BLOCK, TICK, X_ONLY, 0); hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, a); }
+  } else { note_step(x, sizeof(T), BLOCK, TICK, X_RUNTIME, 0); hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_RUNTIME>), grid, block, 0, x->stream, a); }
 }
 // Which k_step variant serves a launch (options "block" and "tick"; 0 = auto).  Measured on MI355X, periods_per_launch 4
 // (profiles/r2_sweep_tick.jsonl, r2_sweep_occupancy.jsonl):
@@ -2110,6 +2115,12 @@ int dql_diag_kernel_time_ms(dql_ctx* x, double* avg_ms, int64_t* launches) {
   for (size_t i = 0; i + 1 < x->kev.size(); i += 2) { float f = 0; HIP_TRY(hipEventElapsedTime(&f, x->kev[i], x->kev[i + 1])); tot += f; ++n; }
   if (avg_ms) *avg_ms = n ? tot / (double)n : 0.0;
   if (launches) *launches = n;
+  return DQL_OK;
+}
+int dql_diag_step_instance(dql_ctx* x, int32_t* out5) {
+  CHECK_CTX(x);
+  if (!out5) return fail(DQL_EINVAL, "null pointer");
+  for (int k = 0; k < 5; ++k) out5[k] = x->last_step[k];
   return DQL_OK;
 }
 int dql_diag_delay(dql_ctx* x, double microseconds) {

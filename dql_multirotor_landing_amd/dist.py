@@ -80,6 +80,13 @@ class LocalWindowReducer:
         self.engine.flush()
 
 
+def window_headroom(engine, sync_period: int, world: int, n_envs: int = None):
+    """The window accumulators sum every target of `sync_period` periods of all `world` ranks' envs (two per env and period on two axes)
+    into one int64 per cell: refuse a schedule that could overflow it (DqlConfig.accum_visit_limit)."""
+    n = engine.n * int(world) if n_envs is None else int(n_envs)
+    engine.cfg.check_accum_headroom(n * int(sync_period) * (2 if engine.cfg.two_axis else 1), f"sync_period {sync_period} x {n} envs")
+
+
 class ShardedRunner:
     """Runs `n_steps` agent periods on this rank's shard and synchronises the tables every `sync_period` periods."""
 
@@ -89,6 +96,8 @@ class ShardedRunner:
         self.engine, self.reducer, self.sync_period = engine, reducer, int(sync_period)
         self._since = 0
         if reducer is not None:
+            world = getattr(reducer, "world", None) or getattr(getattr(reducer, "comm", None), "world", 1)
+            window_headroom(engine, self.sync_period, world)
             engine.set_windowed(True)
 
     def train_steps(self, n_steps: int, eps: float):
@@ -120,6 +129,7 @@ class ShardedGroup:
         if sync_period < 1:
             raise ValueError("sync_period must be >= 1")
         self.engines, self.sync_period = list(engines), int(sync_period)
+        window_headroom(self.engines[0], self.sync_period, len(self.engines), n_envs=sum(e.n for e in self.engines))
         self.reducers = P2PWindowReducer.local_group(self.engines)
         self._since = 0
         for e in self.engines:

@@ -24,6 +24,7 @@ class Engine:
         self.cfg = cfg
         self.n = int(n_envs)
         self._c = cfg.to_c()
+        cfg.check_accum_headroom(self.n * (2 if cfg.two_axis else 1), "n_envs")  # one period per launch until the option says more
         h = C.c_void_p()
         _lib.check(self.lib.dql_create(C.byref(self._c), device, self.n, seed, env_id_offset, C.byref(h)))
         self._h = h
@@ -290,10 +291,21 @@ class Engine:
         _lib.check(self.lib.dql_diag_kernel_time_ms(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def step_instance(self) -> str:
+        """the step kernel the latest launch ran, as its template arguments: e.g. "k_step<float,256,LIT,X_ONLY>" ("" before the first launch)"""
+        v = (C.c_int32 * 5)()
+        _lib.check(self.lib.dql_diag_step_instance(self._h, v))
+        if v[0] == 0:
+            return ""
+        tick = {0: "PLAIN", 2: "PACKED", 3: "LIT", 4: "PACKED_LITM"}[v[2]]
+        return f"{'k_step_pop' if v[4] else 'k_step'}<{'float' if v[0] == 4 else 'double'},{v[1]},{tick},{('X_TWO', 'X_ONLY', 'X_RUNTIME')[v[3]]}>"
+
     def delay(self, microseconds: float):
         _lib.check(self.lib.dql_diag_delay(self._h, float(microseconds)))
 
     def set_option(self, name: str, value: int):
+        if name == "periods_per_launch":  # one launch's accumulators hold every target of its periods
+            self.cfg.check_accum_headroom(self.n * int(value) * (2 if self.cfg.two_axis else 1), "periods_per_launch")
         _lib.check(self.lib.dql_set_option(self._h, name.encode(), int(value)))
 
     # ---- episode log (completion order for the promotion rule, pkg/trainer.py:218-232) ----

@@ -22,6 +22,9 @@ int dql_diag_kernel_timer(dql_ctx* ctx, int32_t on);
 int dql_diag_kernel_time_ms(dql_ctx* ctx, double* avg_ms, int64_t* launches);
 /* average device time of the exchanges (all-reduce or peer-to-peer push / wait / sum, + fold) made while the kernel timer was armed */
 int dql_diag_sync_time_ms(dql_ctx* ctx, double* avg_ms, int64_t* syncs);
+/* the step kernel the context's latest launch ran: out5 = {sizeof(real) in bytes, BLOCK, TICK (csrc/dql_device.hpp TICK_*), XMODE (X_TWO 0, X_ONLY 1,
+ * X_RUNTIME 2), 1 for the population kernel k_step_pop}: the template arguments of its name; all 0 before the first launch */
+int dql_diag_step_instance(dql_ctx* ctx, int32_t* out5);
 /* holds the context's stream for this long (a one-wave timer kernel): phase offset between contexts that share a GPU (tools/exp_cohorts.py) */
 int dql_diag_delay(dql_ctx* ctx, double microseconds);
 /* the window accumulators' device buffer (4 * 2835 int64), for a caller that wants to reduce it with a collective of its own; the product path

@@ -132,6 +132,48 @@ def test_population_agents_equal_contexts_of_their_own(dtype, two_axis, E, block
             e.close()
 
 
+CFG4 = dict(per_env_platform=1, noise_pos_sd=0.25, noise_vel_sd=0.1)  # BASELINE configs[4] flags
+SIZE_CASES = [  # agents, envs per agent, config flags, launches, instance of the population's launches, instance of its twins' launches
+    (4, 32768, CFG4, 3, "k_step_pop<float,256,LIT,X_ONLY>", "k_step<float,256,PACKED_LITM,X_ONLY>"),   # tools/exp_population.py
+    (16, 512, {}, 12, "k_step_pop<float,64,PACKED_LITM,X_ONLY>", "k_step<float,64,PACKED_LITM,X_ONLY>"),  # DQL_MAX_AGENTS
+]
+
+
+@pytest.mark.parametrize("K,E,kw,launches,pop_instance,twin_instance", SIZE_CASES, ids=["4x32768-configs4", "16x512"])
+def test_population_at_product_sizes(K, E, kw, launches, pop_instance, twin_instance):
+    """The measured population (4 x 32 768, whose whole batch picks the literal-constant 256-thread layout while each twin alone picks
+    the packed one) and the DQL_MAX_AGENTS limit (16 agents), auto layout, 16 periods per launch, non-contiguous active subsets that
+    change every launch, more launches than the descriptor ring (DQL_POP_RING = 8) has slots: every agent equals its twin context."""
+    from dql_multirotor_landing_amd.engine import Engine
+    from dql_multirotor_landing_amd.population import Population
+    cfg = DqlConfig(dtype=F32, t_max=4.0, **kw)
+    seeds = [1000 + 37 * k for k in range(K)]
+    pop = Population(cfg, K, E, seeds)
+    engs = [Engine(cfg, E, seed=s) for s in seeds]
+    try:
+        for x in [pop] + engs:
+            x.set_option("periods_per_launch", 16)
+        for k, e in enumerate(engs):
+            pop.set_curriculum(k, k % 5)
+            e.set_curriculum(k % 5)
+        rng = np.random.default_rng(K)
+        for j in range(launches):
+            active = [0, K - 1] if j == 0 else sorted(int(a) for a in rng.choice(K, size=max(2, K // 2), replace=False))
+            eps = {k: 1.0 if j == 0 else 0.1 + 0.05 * ((k + j) % 7) for k in active}
+            pop.pop_train_steps(16, eps)
+            assert pop.step_instance() == pop_instance
+            for k in active:
+                engs[k].train_steps(16, eps[k])
+                assert engs[k].step_instance() == twin_instance
+        for k in range(K):
+            _same_state(pop, k, engs[k])
+        assert sum(pop.agent_stats(k)["decisions"] > 0 for k in range(K)) >= 2
+    finally:
+        pop.close()
+        for e in engs:
+            e.close()
+
+
 def test_one_agent_population_is_a_plain_context():
     from dql_multirotor_landing_amd.engine import Engine
     from dql_multirotor_landing_amd.population import Population
