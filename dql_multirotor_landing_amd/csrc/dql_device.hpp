@@ -17,6 +17,17 @@
 //   rotors_gazebo_plugins/src/gazebo_motor_model.cpp:358-364,434-500, include/.../common.h:147-183  rotor model
 //   pkg/landing_simulation_env.py:167-282  reset / step sequencing
 #pragma once
+// The inline-asm statements that only steer gfx950 code generation: register pins, block markers, an opaque SGPR -> VGPR copy, three-address fmas.
+// Defined BEFORE the runtime header on purpose: the host emulation of this header (tests/host_emu: the step kernel's device code run on the CPU
+// under ASan / UBSan and held to the oracle) compiles it against a stand-in for <hip/hip_runtime.h> that redefines them as nothing, a compiler
+// barrier, the copy and the fma they spell — as it defines __ballot and the amdgcn builtins.  The kernel itself compiles one way.
+#define DQL_ASM_PIN(...) asm volatile("" : __VA_ARGS__)    // opaque to the optimiser: the operands stay in the registers the constraints name
+#define DQL_ASM_BLOCK(text) asm volatile(text ::: "memory")  // a comment line in the ISA listing that the scheduler may not move code across
+#define DQL_ASM_VMOV(dst, src) asm("v_mov_b32 %0, %1" : "=v"(dst) : "s"(src))  // an SGPR value copied to a VGPR, opaquely (to_vgpr)
+// d = x * k + y in a register of the instruction's own choosing (fma3): k an instruction literal (float constant), a VGPR, an SGPR
+#define DQL_ASM_FMA_LIT(d, x, k, y) asm("v_fmamk_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "n"(__builtin_bit_cast(int, k)), "v"(y))
+#define DQL_ASM_FMA_V(d, x, k, y) asm("v_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(k), "v"(y))
+#define DQL_ASM_FMA_S(d, x, k, y) asm("v_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "s"(k), "v"(y))
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -327,8 +338,8 @@ template <typename T> struct SimK {
 // Per-tick constants held in VECTOR registers for the duration of the tick loop.  The loop wants ~50 constants on top of its
 // loop state; as wave-uniform scalars they overflow the SGPR file and every use of a spilled one costs a v_readlane.  A VALU
 // operand may just as well be a VGPR: one v_mov per constant before the loop (opaque to the compiler, so it stays there).
-DQL_DEV float to_vgpr(float x) { float y; asm("v_mov_b32 %0, %1" : "=v"(y) : "s"(x)); return y; }
-DQL_DEV uint32_t to_vgpr(uint32_t x) { uint32_t y; asm("v_mov_b32 %0, %1" : "=v"(y) : "s"(x)); return y; }
+DQL_DEV float to_vgpr(float x) { float y; DQL_ASM_VMOV(y, x); return y; }
+DQL_DEV uint32_t to_vgpr(uint32_t x) { uint32_t y; DQL_ASM_VMOV(y, x); return y; }
 template <typename T> struct HotK {
   T dt, g, inv_m, I[3], inv_I[3], l, h, kf, lkf, kmkf, aup, adn, omax, cd, crd;
   T dtm, dtg, dtI[3], oup, odn, nlcd, hdt, low_z;
@@ -639,11 +650,11 @@ template <typename Tag, typename K> DQL_DEV float fma3(const K& c, float x, floa
   float d;
   if constexpr (__is_same(K, LitK)) {
     constexpr float k = Tag::get(K{});
-    asm("v_fmamk_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "n"(__builtin_bit_cast(int, k)), "v"(y));
+    DQL_ASM_FMA_LIT(d, x, k, y);
   } else if constexpr (__is_same(K, HotK<float>)) {
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(Tag::get(c)), "v"(y));
+    DQL_ASM_FMA_V(d, x, Tag::get(c), y);
   } else {
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "s"((float)Tag::get(c)), "v"(y));
+    DQL_ASM_FMA_S(d, x, (float)Tag::get(c), y);
   }
   return d;
 }
@@ -1033,7 +1044,7 @@ template <typename T, typename K> DQL_DEV void platform_contact(const K& s, Env<
   if constexpr (Fast32<T>::on) low = e.p[2] <= low_z;  // round 4b: against the host's mp_top + bottom (low_z: s.low_z, from a register of the caller's choosing)
   else low = e.p[2] - s.bottom <= s.mp_top;
   if (__ballot(low) != 0ull) {
-    asm volatile("; footprint test" ::: "memory");  // keeps the block a block: the compiler otherwise flattens it into selects again
+    DQL_ASM_BLOCK("; footprint test");  // keeps the block a block: the compiler otherwise flattens it into selects again
     if (low && abs_(e.p[0] - e.mp_x) <= s.mp_hx && abs_(e.p[1] - e.mp_y) <= s.mp_hy) e.flags |= FL_CONTACT;
   }
 }
@@ -1253,7 +1264,7 @@ DQL_DEV void physics_tick_pk(const K& c, const PkK& k, TickPk& s, const RotPk& r
   s.mp_xy = pfma(s.mp_uv, bc2(c.dt), s.mp_xy);
   const bool low = s.p2 <= (float)c.low_z;
   if (__ballot(low) != 0ull) {  // see platform_contact
-    asm volatile("; footprint test" ::: "memory");
+    DQL_ASM_BLOCK("; footprint test");
     const f2 dxy = s.p01 - s.mp_xy;
     if (low && abs_(dxy.x) <= c.mp_hx && abs_(dxy.y) <= c.mp_hy) flags |= FL_CONTACT;
   }
@@ -1498,7 +1509,7 @@ DQL_DEV StepOut agent_period(const SimK<T>& s_in, const TickConsts<TICK, T>& tc,
   // (two v_readlane + a hazard wait each).  Made opaque here, once per period, the conditions are re-derived where they are used: a scalar compare each.
   // (the packed layout — batches of at most one wave per SIMD — is indifferent: 4 096 envs +0.3 %, 32 768 / 65 536 -0.3 %: left alone)
   if constexpr (sizeof(T) == 4 && (TICK == TICK_LIT || TICK == TICK_PLAIN))
-    asm volatile("" : "+s"(s.quirks), "+s"(s.working), "+s"(s.init_uniform), "+s"(mode));
+    DQL_ASM_PIN("+s"(s.quirks), "+s"(s.working), "+s"(s.init_uniform), "+s"(mode));
   DQL_SECTION("period_begin");
   const PeriodCtx c = period_begin(s, e, qx, qa, qb, mode, eps_thr, ext_action, seed, env_id, step_index, kv);
   T B[9];
@@ -1512,9 +1523,9 @@ DQL_DEV StepOut agent_period(const SimK<T>& s_in, const TickConsts<TICK, T>& tc,
   // Pinned to SGPRs here (opaque: nothing to rematerialise) they stay scalar operands — in VGPRs they cost more than the s_movs (three VGPR sources per v_med3).
   T yw_lo = T(h.yw_lo), yw_hi = T(h.yw_hi), yw_wind = T(h.yw_wind), c375 = T(0.375), low_z = T(h.low_z);
   if constexpr (sizeof(T) == 4 && TICK == TICK_LIT) {
-    asm volatile("" : "+s"(yw_wind), "+s"(yw_hi), "+s"(c375));
+    DQL_ASM_PIN("+s"(yw_wind), "+s"(yw_hi), "+s"(c375));
     // (the contact test's height: the literal was moved into a scalar register in front of the compare at every tick; 17.18 vs 17.25 us, profiles/r5_ab_tick_loop.txt)
-    asm volatile("" : "+s"(low_z));
+    DQL_ASM_PIN("+s"(low_z));
     if (T(h.yw_lo) == -T(h.yw_hi)) yw_lo = -yw_hi;
   }
   DQL_MARK_T(e, 3);
