@@ -110,6 +110,10 @@ SYMBOLS = {
     "dql_pid_run": (C.c_int, [_cfgp, C.c_int, _vp, _vp, _i64, _vp, _vp]),
     "dql_attitude_run": (C.c_int, [_cfgp, C.c_int, _vp, _vp, _vp, _i64, _i32, _vp]),
     "dql_platform_run": (C.c_int, [_cfgp, C.c_int, _i64, _i32, _vp]),
+    "dql_rollout_n_fields": (C.c_int, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "dql_rollout_field_name": (C.c_char_p, [_i32, _i32]),
+    "dql_rollout": (C.c_int, [_cfgp, C.c_int, _i32, _i64, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "dql_diag_rollout_last": (C.c_int, [C.POINTER(_dbl), _vp]),
     "dql_diag_selftest_sqrt": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_i64)]),
     "dql_place": (C.c_int, [_cfgp, C.c_int, _vp, _vp, _i64, _vp]),
     "dql_agent_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),

@@ -29,6 +29,7 @@
 
 #include "dql_device.hpp"
 #include "dql_host_consts.hpp"
+#include "dql_rollout.hpp"
 #include "../../include/dql_diag.h"
 
 using namespace dql;
@@ -967,6 +968,52 @@ __global__ void k_p2p_sum(unsigned long long* mine, long long* window, int world
   unsigned long long sum = 0;
   for (int r = 0; r < world; ++r) sum += __builtin_nontemporal_load(&p2p_slot(mine, world, parity, r)[c]);
   window[c] = (long long)sum;
+}
+
+// ---- greedy roll-outs (dql_rollout) ----
+// One env per lane flies its FIRST episode from reset to termination (csrc/dql_rollout.hpp: rollout_episode); workgroups of one wave: evaluation batches are
+// small, a lone wave per SIMD needs no LDS staging, no barrier, and there are no accumulators, table-writer blocks or statistics here.  Table set k serves
+// blocks [k B, (k + 1) B), B = envs_per_table / 64, so that the set's tables are a wave-uniform pointer; env i of every set has env id i (paired episodes).
+// The tick schedule of periods 0 .. max_steps sits in a device buffer read as constant memory (scalar loads by the wave-uniform period counter).
+template <typename T> struct RolloutArgs {
+  SimK<T> c;
+  const MdpK<T> DQL_CONST_AS* mdp;
+  MdpRun<T> mdp_run;
+  RolloutInit<T> init;
+  const double* qa; const double* qb;                                  // [n_tables][DQL_N_CELLS]
+  const long long DQL_CONST_AS* mgr0; const int DQL_CONST_AS* sched;   // [max_steps + 1] (fill_schedule)
+  RolloutOut out;
+  unsigned long long seed;
+  int blocks_per_table, max_steps;
+};
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_rollout(RolloutArgs<T> a) {
+  const int tid = threadIdx.x;
+  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
+  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
+  const long long g = (long long)blockIdx.x * 64 + tid;                // output column: every lane of the grid is an env (envs_per_table is a multiple of 64)
+  // the launch's constants in the layout's form, as k_step makes them for a 64-thread workgroup
+  SimK<T> cl = a.c;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
+  const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
+  const bool trace_wave = a.out.trace != nullptr && blockIdx.x == 0;   // the first trace_envs <= 64 envs of table set 0: wave 0 of the grid, nobody else
+  rollout_episode<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.mgr0, a.sched, kv, a.out, g, trace_wave,
+                               trace_wave && tid < a.out.trace_envs);
 }
 
 struct dql_ctx {
@@ -2327,6 +2374,87 @@ int dql_place(const dql_config* cfg, int device, const double* x0, const double*
   else hipLaunchKernelGGL(k_place<double>, dim3(grid), dim3(256), 0, 0, (int)cfg->init_uniform, (double)cfg->p_max, (const double*)a.p, (const double*)b.p, (long long)n, (double*)o.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, o.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  return DQL_OK;
+}
+
+// ---- greedy roll-outs ----
+static thread_local double g_rollout_ms = -1.0;
+static thread_local int g_rollout_inst[3] = {0, 0, 0};
+extern "C++" {
+template <typename T, int XMODE> static void launch_rollout(const dql_config& cfg, const void* mdpk, const double* qa, const double* qb, const long long* mgr0, const int* sched,
+                                                           const RolloutOut& out, unsigned long long seed, int n_tables, long long envs_per_table, int max_steps) {
+  RolloutArgs<T> a;
+  a.c = make_simk<T>(cfg);
+  a.mdp = (const MdpK<T> DQL_CONST_AS*)mdpk;
+  a.mdp_run = MdpRun<T>{cfg.gamma, (T)(cfg.t_max * cfg.f_ag), cfg.goal_logic};
+  a.init = make_rollout_init<T>(cfg);
+  a.qa = qa; a.qb = qb;
+  a.mgr0 = (const long long DQL_CONST_AS*)mgr0; a.sched = (const int DQL_CONST_AS*)sched;
+  a.out = out; a.seed = seed; a.blocks_per_table = (int)(envs_per_table / 64); a.max_steps = max_steps;
+  g_rollout_inst[0] = (int)sizeof(T); g_rollout_inst[1] = TICK_PLAIN; g_rollout_inst[2] = XMODE;
+  hipLaunchKernelGGL((k_rollout<T, TICK_PLAIN, XMODE>), dim3((unsigned)((long long)n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
+}
+}  // extern "C++"
+int dql_rollout_n_fields(int32_t* n_record, int32_t* n_trace) { if (n_record) *n_record = RO_N_RECORD; if (n_trace) *n_trace = RO_N_TRACE; return DQL_OK; }
+const char* dql_rollout_field_name(int32_t i, int32_t is_trace) { return (i >= 0 && i < (is_trace ? RO_N_TRACE : RO_N_RECORD)) ? k_rollout_field_names[i] : nullptr; }
+int dql_rollout(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, uint64_t seed, int32_t max_steps, const double* qa, const double* qb,
+                int32_t* code, int32_t* steps, double* rec, int32_t trace_envs, double* trace_or_null) {
+  int rc = check_config(cfg); if (rc) return rc;
+  // every argument is checked before the device is touched: a refused call starts no kernel
+  if (n_tables < 1 || n_tables > DQL_ROLLOUT_MAX_TABLES) return fail(DQL_EINVAL, "dql_rollout: n_tables must be in 1..16 (DQL_ROLLOUT_MAX_TABLES); nothing was launched");
+  if (envs_per_table < 64 || envs_per_table % 64 != 0) return fail(DQL_EINVAL, "dql_rollout: envs_per_table must be a positive multiple of 64 (one wave per workgroup, whole waves per table set); nothing was launched");
+  if ((long long)n_tables * envs_per_table > (1ll << 30)) return fail(DQL_EINVAL, "dql_rollout: n_tables * envs_per_table must be at most 2^30; nothing was launched");
+  if (max_steps < 1 || max_steps > DQL_ROLLOUT_MAX_STEPS) return fail(DQL_EINVAL, "dql_rollout: max_steps must be in 1..4096 (DQL_ROLLOUT_MAX_STEPS); nothing was launched");
+  if (trace_envs < 0 || trace_envs > 64) return fail(DQL_EINVAL, "dql_rollout: trace_envs must be in 0..64 (the trace stays inside one wave); nothing was launched");
+  if (trace_envs > 0 && !trace_or_null) return fail(DQL_EINVAL, "dql_rollout: trace_envs > 0 needs a trace buffer; nothing was launched");
+  if (!qa || !qb || !code || !steps || !rec) return fail(DQL_EINVAL, "dql_rollout: null array; nothing was launched");
+  OP_PROLOGUE(device)
+  const long long n_total = (long long)n_tables * envs_per_table;
+  const int n_per = max_steps + 1;
+  std::vector<long long> h_mgr0((size_t)n_per);
+  std::vector<int> h_sched((size_t)n_per);
+  fill_schedule(*cfg, 0, h_mgr0.data(), h_sched.data(), n_per);
+  DevBuf d_qa, d_qb, d_mgr0, d_sched, d_mdp, d_code, d_steps, d_rec, d_trace;
+  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
+  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
+  UP(d_mgr0, h_mgr0.data(), (size_t)n_per * sizeof(long long)); UP(d_sched, h_sched.data(), (size_t)n_per * sizeof(int));
+  if (cfg->dtype == DQL_F32) { const MdpK<float> m = make_mdpk<float>(*cfg); UP(d_mdp, &m, sizeof(m)); }
+  else { const MdpK<double> m = make_mdpk<double>(*cfg); UP(d_mdp, &m, sizeof(m)); }
+  if (d_code.alloc((size_t)n_total * sizeof(int)) || d_steps.alloc((size_t)n_total * sizeof(int)) || d_rec.alloc((size_t)RO_N_RECORD * n_total * sizeof(double))) return fail(DQL_ENOMEM, "hipMalloc failed");
+  const size_t trace_bytes = (size_t)n_per * RO_N_TRACE * (size_t)trace_envs * sizeof(double);
+  if (trace_envs > 0) {
+    if (d_trace.alloc(trace_bytes)) return fail(DQL_ENOMEM, "hipMalloc failed");
+    HIP_TRY(hipMemset(d_trace.p, 0xff, trace_bytes));  // all ones = NaN: what a row keeps after its env's last period
+  }
+  const RolloutOut out{(int*)d_code.p, (int*)d_steps.p, (double*)d_rec.p, trace_envs > 0 ? (double*)d_trace.p : nullptr, n_total, trace_envs};
+  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
+  HIP_TRY(hipEventCreate(&e0.e)); HIP_TRY(hipEventCreate(&e1.e));
+  HIP_TRY(hipEventRecord(e0.e, 0));
+  const bool two = cfg->two_axis != 0;
+  if (cfg->dtype == DQL_F32) {
+    if (two) launch_rollout<float, X_TWO>(*cfg, d_mdp.p, (const double*)d_qa.p, (const double*)d_qb.p, (const long long*)d_mgr0.p, (const int*)d_sched.p, out, seed, n_tables, envs_per_table, max_steps);
+    else launch_rollout<float, X_ONLY>(*cfg, d_mdp.p, (const double*)d_qa.p, (const double*)d_qb.p, (const long long*)d_mgr0.p, (const int*)d_sched.p, out, seed, n_tables, envs_per_table, max_steps);
+  } else {
+    if (two) launch_rollout<double, X_TWO>(*cfg, d_mdp.p, (const double*)d_qa.p, (const double*)d_qb.p, (const long long*)d_mgr0.p, (const int*)d_sched.p, out, seed, n_tables, envs_per_table, max_steps);
+    else launch_rollout<double, X_ONLY>(*cfg, d_mdp.p, (const double*)d_qa.p, (const double*)d_qb.p, (const long long*)d_mgr0.p, (const int*)d_sched.p, out, seed, n_tables, envs_per_table, max_steps);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e1.e, 0));
+  HIP_TRY(hipMemcpy(code, d_code.p, (size_t)n_total * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(steps, d_steps.p, (size_t)n_total * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rec, d_rec.p, (size_t)RO_N_RECORD * n_total * sizeof(double), hipMemcpyDeviceToHost));
+  if (trace_envs > 0) HIP_TRY(hipMemcpy(trace_or_null, d_trace.p, trace_bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipEventSynchronize(e1.e));
+  float ms = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
+  g_rollout_ms = (double)ms;
+  return DQL_OK;
+}
+int dql_diag_rollout_last(double* kernel_ms, int32_t* out3) {
+  if (!kernel_ms || !out3) return fail(DQL_EINVAL, "null pointer");
+  if (g_rollout_ms < 0.0) return fail(DQL_ESTATE, "no dql_rollout call has completed on this thread");
+  *kernel_ms = g_rollout_ms;
+  for (int k = 0; k < 3; ++k) out3[k] = g_rollout_inst[k];
   return DQL_OK;
 }
 

@@ -124,9 +124,10 @@ static unsigned int eps_threshold(double eps) {
 }
 static long long ticks_before(const dql_config& c, long long j) { return (long long)std::floor((double)j * (1.0 / (c.f_ag * c.dt))); }
 
-// the per-period tick schedule of the launch whose first agent period is j
-static void fill_schedule(const dql_config& c, long long j, long long* mgr0, int* sched) {
-  for (int p = 0; p < DQL_MAX_PERIODS; ++p) {
+// the per-period tick schedule of `count` agent periods from period j on (a step launch's kernel arguments hold DQL_MAX_PERIODS entries; a roll-out
+// uploads one per period of the episode)
+static void fill_schedule(const dql_config& c, long long j, long long* mgr0, int* sched, int count = DQL_MAX_PERIODS) {
+  for (int p = 0; p < count; ++p) {
     const long long g0 = ticks_before(c, j + p);
     const int n_ticks = (int)(ticks_before(c, j + p + 1) - g0), div = c.manager_div;
     const int phase = (int)(g0 % div);                                   // physics ticks since the last 100 Hz manager tick

@@ -179,3 +179,60 @@ def agent_update(qa, qb, count, sa, ns, alpha, gamma, reward, quirks: int = Q_RE
             raise ValueError("coin / done must have one entry per transition")
     _lib.check(_lib.load().dql_agent_update(device, _p(qa), _p(qb), _p(count), _p(sa), _p(ns), _p(alpha), float(gamma), _p(reward), len(sa), quirks,
                                             None if coin is None else _p(coin), None if done is None else _p(done)))
+
+
+ROLLOUT_MAX_STEPS, ROLLOUT_MAX_TABLES = 4096, 16  # include/dql.h DQL_ROLLOUT_MAX_STEPS / DQL_ROLLOUT_MAX_TABLES
+# include/dql.h dql_rollout_field_name (csrc/dql_rollout.hpp): a record's fields, and what a trace row adds
+ROLLOUT_RECORD_FIELDS = ("cum_x", "cum_y", "reward", "px", "py", "pz", "vx", "vy", "vz", "mp_x", "mp_u", "mp_y", "mp_v", "qw", "qx", "qy", "qz", "pitch_sp", "roll_sp")
+ROLLOUT_TRACE_FIELDS = ROLLOUT_RECORD_FIELDS + ("action", "idx_x", "idx_y")
+
+
+def _table_sets(tables):
+    """`tables`: one (qa, qb[, count]) set or a list of them -> ([K][2835] qa, [K][2835] qb), checked"""
+    if len(tables) in (2, 3) and all(np.ndim(t) >= 1 and np.size(t) == 2835 for t in tables[:2]) and (len(tables) == 2 or np.size(tables[2]) == 2835):
+        tables = [tables]
+    tables = list(tables)
+    if not 1 <= len(tables) <= ROLLOUT_MAX_TABLES:
+        raise ValueError(f"between 1 and {ROLLOUT_MAX_TABLES} table sets per roll-out, not {len(tables)}")
+    qa, qb = [], []
+    for k, t in enumerate(tables):
+        if len(t) < 2 or np.size(t[0]) != 2835 or np.size(t[1]) != 2835:
+            raise ValueError(f"table set {k} must be (Q_table_a, Q_table_b[, counter]) of 2835 cells each")
+        qa.append(_f64(t[0]).ravel()); qb.append(_f64(t[1]).ravel())
+    return np.ascontiguousarray(np.stack(qa)), np.ascontiguousarray(np.stack(qb))
+
+
+def rollout(cfg: DqlConfig, tables, envs_per_table: int, seed: int, max_steps: int = 600, trace_envs: int = 0, device: int = 0, timing: dict = None):
+    """Every env's FIRST greedy episode from reset to termination in one launch, for up to 16 table sets at once (include/dql.h dql_rollout).
+
+    `tables`: one (qa, qb) pair or a list of them (a third element, the counter, is ignored).  Every set flies the same `envs_per_table` episodes (env i
+    has the RNG key and start of env i of `Engine(cfg, envs_per_table, seed)`).  Returns a dict of arrays [n_tables, envs_per_table]: `code` (the terminal
+    CheckResult code, -1 while still flying after `max_steps`), `steps` and one entry per ROLLOUT_RECORD_FIELDS, all taken from the env's state at the end of
+    the period its episode ended in; `trace` [max_steps + 1, len(ROLLOUT_TRACE_FIELDS), trace_envs] of table set 0's first envs (NaN after an env's end) or
+    None, and `trace_fields`.  `timing`: a dict that receives `kernel_ms` and `instance` of this call."""
+    qa, qb = _table_sets(tables)
+    K, n, max_steps, trace_envs = len(qa), int(envs_per_table), int(max_steps), int(trace_envs)
+    if n < 64 or n % 64:
+        raise ValueError(f"envs_per_table must be a positive multiple of 64, not {n}")
+    if not 1 <= max_steps <= ROLLOUT_MAX_STEPS:
+        raise ValueError(f"max_steps must be in 1..{ROLLOUT_MAX_STEPS}, not {max_steps}")
+    if not 0 <= trace_envs <= 64:
+        raise ValueError(f"trace_envs must be in 0..64, not {trace_envs}")
+    lib = _lib.load()
+    nr, nt = C.c_int32(), C.c_int32()
+    _lib.check(lib.dql_rollout_n_fields(C.byref(nr), C.byref(nt)))
+    names = tuple(lib.dql_rollout_field_name(i, 1).decode() for i in range(nt.value))
+    if names != ROLLOUT_TRACE_FIELDS or nr.value != len(ROLLOUT_RECORD_FIELDS):
+        raise RuntimeError("libdql_hip.so's roll-out fields are not the ones this module names")
+    code = np.zeros((K, n), np.int32); steps = np.zeros((K, n), np.int32); rec = np.zeros((nr.value, K, n))
+    trace = np.zeros((max_steps + 1, nt.value, trace_envs)) if trace_envs else None
+    c = cfg.to_c()
+    _lib.check(lib.dql_rollout(C.byref(c), device, K, n, int(seed), max_steps, _p(qa), _p(qb), _p(code), _p(steps), _p(rec), trace_envs, None if trace is None else _p(trace)))
+    if timing is not None:
+        ms, inst = C.c_double(), (C.c_int32 * 3)()
+        _lib.check(lib.dql_diag_rollout_last(C.byref(ms), inst))
+        timing["kernel_ms"] = ms.value
+        timing["instance"] = f"k_rollout<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    out = {"code": code, "steps": steps, "trace": trace, "trace_fields": ROLLOUT_TRACE_FIELDS}
+    out.update({f: rec[k] for k, f in enumerate(ROLLOUT_RECORD_FIELDS)})
+    return out

@@ -380,6 +380,24 @@ int dql_platform_run(const dql_config* cfg, int device, int64_t n, int32_t carry
 /* start coordinate of the drone along one axis for n (random offset x0, platform coordinate) pairs: the placement arithmetic of
  * TrainingLandingEnv.reset / SimulationLandingEnv.reset selected by cfg->init_uniform (see dql_config) */
 int dql_place(const dql_config* cfg, int device, const double* x0, const double* mp, int64_t n, double* out);
+/* ---- greedy roll-outs: every env's FIRST episode from reset to termination in one launch, for up to 16 table sets at once ----
+ * Table set k (qa / qb [n_tables][DQL_N_CELLS]) flies envs_per_table envs; env i of every set has the RNG key (i, seed) and the initial state of env i
+ * of a context made with dql_create(cfg, device, envs_per_table, seed, 0), so the sets are compared on paired episodes.  Row (k, i) — output column
+ * k * envs_per_table + i — is what that context, its tables set to set k and driven by dql_eval_steps(ctx, 1) once for the reset period and then max_steps
+ * more times, shows at the first period after which env i is done: its terminal code, its step_count and the record fields of its state (the names:
+ * dql_rollout_field_name), bit for bit in float32 and float64.  An env still in its first episode after max_steps periods has code -1 and the fields
+ * of its state after the last period.
+ *   code, steps  int32 [n_tables * envs_per_table];  rec  double [n_record][n_tables * envs_per_table]
+ *   trace (trace_envs > 0): double [max_steps + 1][n_trace][trace_envs], the trace fields (the record's, then action, idx_x, idx_y) of the first
+ *   trace_envs envs of table set 0 after every period they fly; rows after an env's last period are NaN.
+ * DQL_EINVAL (and no launch) unless 1 <= n_tables <= DQL_ROLLOUT_MAX_TABLES, envs_per_table is a positive multiple of 64, 1 <= max_steps <=
+ * DQL_ROLLOUT_MAX_STEPS, 0 <= trace_envs <= 64, a trace buffer comes with trace_envs > 0 and no other pointer is null. */
+#define DQL_ROLLOUT_MAX_STEPS 4096
+#define DQL_ROLLOUT_MAX_TABLES 16
+int dql_rollout_n_fields(int32_t* n_record, int32_t* n_trace);
+const char* dql_rollout_field_name(int32_t i, int32_t is_trace);
+int dql_rollout(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, uint64_t seed, int32_t max_steps, const double* qa,
+                const double* qb, int32_t* code, int32_t* steps, double* rec, int32_t trace_envs, double* trace_or_null);
 /* ---- a DoubleQLearningAgent's tables RESIDENT on the device (pkg/double_q_learning.py:32-146) ----
  * The stateless dql_agent_predict / dql_agent_update below ship all three tables (3 x 22 680 B) both ways per call — fine for a batch,
  * 6x slower than the reference's own Python for a caller that steps ONE env (BASELINE configs[0]).  A dql_agent keeps them in device

@@ -31,6 +31,10 @@ int dql_diag_delay(dql_ctx* ctx, double microseconds);
  * never needs the pointer (dql_allreduce_window / dql_p2p_exchange_window reduce it in place) */
 int dql_diag_accum_dev_ptr(dql_ctx* ctx, void** dev_ptr, int64_t* n_int64);
 
+/* device duration (HIP events around the kernel) of the calling thread's latest completed dql_rollout, and the kernel it ran: out3 = {sizeof(real) in
+ * bytes, TICK, XMODE}, the template arguments of k_rollout's name */
+int dql_diag_rollout_last(double* kernel_ms, int32_t* out3);
+
 /* ---- self-test ---- */
 /* The float32 tick's square root (csrc/dql_device.hpp sqrt_pos: v_rsq_f32 + one residual correction; until the end of round 5 with a Goldschmidt step in between): counts the inputs with bit
  * patterns lo_bits .. hi_bits whose result is NOT the correctly rounded sqrt.  The CPU oracle computes sqrtf(); parity is bit for bit only while

@@ -3,7 +3,11 @@
 pair of Q tables in the vectorised simulator and reports how the episodes end.
 
     python scripts/simulation.py [--tables DIR] [--envs 4096] [--level 4] [--flavour simulation|training] [--mode paper|reference]
+                                 [--rollout] [--report] [--trace-out FILE.npz [--trace-envs 8]]
 Default tables: tests/golden/assets (a data copy of the reference's stage-4 policy).
+--rollout flies all first episodes in one launch (dql_rollout) instead of one launch per agent period; --report prints what the episodes looked like at
+their end (the counterpart of the `info` dictionary the reference prints per episode, scripts/simulation.py:52-56) and --trace-out saves the per-period
+flight record of the first envs; both imply --rollout.
 """
 import argparse
 import json
@@ -13,12 +17,20 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 
-def evaluate(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, **cfg_kw):
+def evaluate(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, method="stepwise", **cfg_kw):
     """Greedy roll-outs of the tables saved in `tables_dir`; returns the terminal histogram of the FIRST episode of every env."""
     from dql_multirotor_landing_amd.double_q_learning import DoubleQLearningAgent
     from dql_multirotor_landing_amd.evaluation import first_episode_outcomes
     agent = DoubleQLearningAgent.load(Path(tables_dir))
-    return first_episode_outcomes(agent._padded(), n_envs, level, max_steps, seed, dtype, flavour, device, **cfg_kw)
+    return first_episode_outcomes(agent._padded(), n_envs, level, max_steps, seed, dtype, flavour, device, method=method, **cfg_kw)
+
+
+def evaluate_records(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, trace_envs=0, **cfg_kw):
+    """The per-episode records (and the trace of the first `trace_envs` envs) of the same roll-outs, from the one-launch operator."""
+    from dql_multirotor_landing_amd.double_q_learning import DoubleQLearningAgent
+    from dql_multirotor_landing_amd.evaluation import rollout_records
+    agent = DoubleQLearningAgent.load(Path(tables_dir))
+    return rollout_records([agent._padded()], n_envs, level, max_steps, seed, dtype, flavour, device, trace_envs=trace_envs, **cfg_kw)
 
 
 if __name__ == "__main__":
@@ -30,11 +42,31 @@ if __name__ == "__main__":
     ap.add_argument("--mode", default="paper", choices=["paper", "reference"],
                     help="observation / MDP quirk set of the roll-outs: 'paper' (default; what scripts/training.py --mode paper trains under) or the "
                          "reference's code as it is (frozen acceleration reference B19, sticky checks B8, ...: DESIGN.md section 3)")
+    ap.add_argument("--rollout", action="store_true", help="fly all first episodes in one launch (dql_rollout) instead of one launch per agent period")
+    ap.add_argument("--report", action="store_true", help="print episode_report: length, return and touchdown quantiles of the first episodes (implies --rollout)")
+    ap.add_argument("--trace-out", default=None, metavar="FILE.npz", help="save the per-period trace of the first --trace-envs envs with its field names (implies --rollout)")
+    ap.add_argument("--trace-envs", type=int, default=8)
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build_hip()
     from dql_multirotor_landing_amd.config import Q_PAPER, Q_REFERENCE
-    h = evaluate(a.tables, a.envs, a.level, flavour=a.flavour, quirks=Q_PAPER if a.mode == "paper" else Q_REFERENCE)
+    quirks = Q_PAPER if a.mode == "paper" else Q_REFERENCE
     n = a.envs
-    print(json.dumps({"tables": a.tables, "envs": n, "level": a.level, "flavour": a.flavour, "mode": a.mode, "first_episode_outcomes": h,
-                      "touchdown_rate": h["TERMINAL_CONTACT"] / n, "goal_rate": h["TERMINAL_SUCCESS"] / n}, indent=1))
+    out = {"tables": a.tables, "envs": n, "level": a.level, "flavour": a.flavour, "mode": a.mode}
+    if a.report or a.trace_out:
+        import numpy as np
+        from dql_multirotor_landing_amd.evaluation import episode_report
+        rec = evaluate_records(a.tables, n, a.level, flavour=a.flavour, trace_envs=a.trace_envs if a.trace_out else 0, quirks=quirks)
+        rep = episode_report(rec)[0]
+        h = rep["histogram"]
+        out["method"] = "rollout"
+        if a.report:
+            out["episode_report"] = rep
+        if a.trace_out:
+            np.savez(a.trace_out, trace=rec["trace"], fields=np.array(rec["trace_fields"]), code=rec["code"][0, :a.trace_envs], steps=rec["steps"][0, :a.trace_envs])
+            out["trace"] = {"file": a.trace_out, "envs": a.trace_envs, "shape": list(rec["trace"].shape)}
+    else:
+        h = evaluate(a.tables, n, a.level, flavour=a.flavour, method="rollout" if a.rollout else "stepwise", quirks=quirks)
+        out["method"] = "rollout" if a.rollout else "stepwise"
+    out.update({"first_episode_outcomes": h, "touchdown_rate": h["TERMINAL_CONTACT"] / n, "goal_rate": h["TERMINAL_SUCCESS"] / n})
+    print(json.dumps(out, indent=1))

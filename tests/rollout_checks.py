@@ -1,0 +1,104 @@
+"""Shared by the roll-out tests (CPU emulation and GPU): the stepwise yardstick and the bitwise comparison.
+
+`stepwise_first_episodes` drives anything with the Engine / Oracle interface (set_tables, eval_steps, get_fields) one agent period at a time — the reset
+period, then `max_steps` more — and keeps, per env, what `get_fields()` shows at the first period after which the env has FL_DONE: the equality contract of
+`dql_rollout` (include/dql.h)."""
+from pathlib import Path
+
+import numpy as np
+
+from dql_multirotor_landing_amd.config import CHECK_NAMES, F32, F64, Q_PAPER, simulation_config, training_config
+
+GOLDEN = Path(__file__).resolve().parent / "golden" / "assets"
+FL_DONE = 1
+RECORD_FIELDS = ("cum_x", "cum_y", "reward", "px", "py", "pz", "vx", "vy", "vz", "mp_x", "mp_u", "mp_y", "mp_v", "qw", "qx", "qy", "qz", "pitch_sp", "roll_sp")
+TRACE_FIELDS = RECORD_FIELDS + ("action", "idx_x", "idx_y")
+CONTACT, SUCCESS, FLY_X, FLY_Y, MIN_ALT = (CHECK_NAMES.index(n) for n in ("TERMINAL_CONTACT", "TERMINAL_SUCCESS", "TERMINAL_FLYZONE_X", "TERMINAL_FLYZONE_Y", "TERMINAL_MINIMUM_ALTITUDE"))
+
+
+def stage4_tables():
+    """the reference's stage-4 tables, flat"""
+    return tuple(np.load(GOLDEN / f).ravel().astype(np.float64) for f in ("Q_table_a.npy", "Q_table_b.npy"))
+
+
+def three_table_sets():
+    """the reference's tables, all zeros, and the reference's with Q_table_b negated"""
+    qa, qb = stage4_tables()
+    return [(qa, qb), (np.zeros_like(qa), np.zeros_like(qb)), (qa, -qb)]
+
+
+# the six equality cases: (id, config builder, dtype)
+CASES = [
+    ("simulation-f32", lambda dt: simulation_config(working_curriculum_step=4, quirks=Q_PAPER, dtype=dt), F32),
+    ("simulation-f64", lambda dt: simulation_config(working_curriculum_step=4, quirks=Q_PAPER, dtype=dt), F64),
+    ("training4-f32", lambda dt: training_config(4, quirks=Q_PAPER, dtype=dt), F32),
+    ("training4-f64", lambda dt: training_config(4, quirks=Q_PAPER, dtype=dt), F64),
+    ("simulation-two-axis-f32", lambda dt: simulation_config(working_curriculum_step=4, two_axis=1, quirks=Q_PAPER, dtype=dt), F32),
+    ("training0-per-env-platform-noise-f32", lambda dt: training_config(0, per_env_platform=1, noise_pos_sd=0.25, noise_vel_sd=0.1, quirks=Q_PAPER, dtype=dt), F32),
+]
+
+
+def case_config(case_id):
+    for cid, make, dt in CASES:
+        if cid == case_id:
+            return make(dt)
+    raise KeyError(case_id)
+
+
+def stepwise_first_episodes(stepper, tables, max_steps, trace_envs=0):
+    """{"code", "steps" int32 [n], <record field> float64 [n], "trace" [max_steps + 1][n_trace][trace_envs] or None} of `stepper`'s first episodes.
+    `stepper`: a fresh Engine or Oracle (step index 0, no period flown)."""
+    qa, qb = tables
+    stepper.set_tables(qa, qb, None)
+    rn, inames = stepper.field_names(False), stepper.field_names(True)
+    ri = [rn.index(f) for f in RECORD_FIELDS]
+    ii = {f: inames.index(f) for f in ("code", "step_count", "flags", "action", "idx_x", "idx_y")}
+    n = None
+    for j in range(max_steps + 1):
+        stepper.eval_steps(1)
+        reals, ints = stepper.get_fields()
+        if n is None:
+            n = reals.shape[1]
+            code = np.full(n, -1, np.int32); steps = np.zeros(n, np.int32); rec = np.zeros((len(RECORD_FIELDS), n))
+            flying = np.ones(n, bool)
+            trace = np.full((max_steps + 1, len(TRACE_FIELDS), trace_envs), np.nan) if trace_envs else None
+        if trace_envs:
+            m = flying[:trace_envs]
+            row = np.concatenate([reals[ri][:, :trace_envs], ints[[ii["action"], ii["idx_x"], ii["idx_y"]]][:, :trace_envs].astype(np.float64)])
+            trace[j][:, m] = row[:, m]
+        done = flying & ((ints[ii["flags"]] & FL_DONE) != 0)
+        code[done] = ints[ii["code"]][done]; steps[done] = ints[ii["step_count"]][done]; rec[:, done] = reals[ri][:, done]
+        flying &= ~done
+        if not flying.any():
+            break
+    steps[flying] = ints[ii["step_count"]][flying]; rec[:, flying] = reals[ri][:, flying]  # still flying: the state after the last period
+    out = {"code": code, "steps": steps, "trace": trace}
+    out.update({f: rec[k] for k, f in enumerate(RECORD_FIELDS)})
+    return out
+
+
+def histogram(code):
+    h = {CHECK_NAMES[k]: int((code == k).sum()) for k in range(len(CHECK_NAMES))}
+    h["unfinished"] = int((code < 0).sum())
+    return h
+
+
+def assert_rows_equal(got, want, what, row=None):
+    """bit for bit on code, steps and every record field; `row`: the table set of `got` ([n_tables, n] arrays) to compare"""
+    pick = (lambda a: a) if row is None else (lambda a: a[row])
+    for f in ("code", "steps"):
+        g, w = pick(got[f]), want[f]
+        assert g.shape == w.shape and np.array_equal(g, w), f"{what}: {f} differs in {np.count_nonzero(g != w)} of {w.size} envs (first: env {int(np.flatnonzero(g != w)[0])}, {g[g != w][0]} vs {w[g != w][0]})"
+    for f in RECORD_FIELDS:
+        g, w = np.ascontiguousarray(pick(got[f]), np.float64), np.ascontiguousarray(want[f], np.float64)
+        bad = g.view(np.uint64) != w.view(np.uint64)  # bitwise: signed zeros and NaN payloads included
+        assert not bad.any(), f"{what}: field {f} differs in {np.count_nonzero(bad)} of {w.size} envs (first: env {int(np.flatnonzero(bad)[0])}, {g[bad][0]!r} vs {w[bad][0]!r})"
+
+
+def assert_trace_equal(got, want, what):
+    assert got.shape == want.shape, f"{what}: trace shape {got.shape} vs {want.shape}"
+    gn, wn = np.isnan(got), np.isnan(want)
+    assert np.array_equal(gn, wn), f"{what}: the NaN rows (periods after an env's end) differ in {np.count_nonzero(gn != wn)} entries"
+    g, w = np.where(gn, 0.0, got), np.where(wn, 0.0, want)
+    bad = g.view(np.uint64) != w.view(np.uint64)
+    assert not bad.any(), f"{what}: trace differs in {np.count_nonzero(bad)} entries, first at (period, field, env) {tuple(int(v[0]) for v in np.nonzero(bad))}"
