@@ -261,21 +261,16 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
   }
   const int ncell = (a.c.working + 1) * DQL_CELLS_PER_LEVEL;
   const int n_tab = (a.c.quirks & DQL_Q_UPDATE_TABLE_A_ONLY) ? 1 : 2;  // tables that can receive targets (wave-uniform)
-  if (STAGED) {
-    for (int t = 0; t < n_tab; ++t)
-      for (int c = tid; c < ncell; c += BLOCK) { sT[t * DQL_N_CELLS + c] = 0ull; sM[t * DQL_N_CELLS + c] = 0u; }
-    if (tid < 4 + 7) sStat[tid] = 0ull;
-    __syncthreads();
-  }
   const long long i = (long long)blockIdx.x * BLOCK + tid;
   long long dec = 0, don = 0, rfx = 0;
   bool goal = false;
-  DQL_WAVE_END_VAR(clk1);
   // P agent periods per launch (option "periods_per_launch", default 1): the env stays in registers between them, so the state
   // round trip through HBM, the launch boundary and the table-writer work are paid once per P periods; the acting tables are
   // those of the launch for all P periods, every period's TD targets go to the launch's accumulators
   Env<T> e;
   QRow qx = QRow{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  // The launch's head in the order of its latencies: the state's loads are ISSUED first, and what does not depend on them — the constants' moves to
+  // VGPRs, the LDS clear and its barrier — runs while they travel (the clear and the barrier used to come first, with nothing in flight behind them)
   if (i < a.n) {
     // the packed ints go first: their state index addresses the acting-table row, whose request then rides along with the
     // state quads instead of waiting for them (one memory round trip less at the head of the wave).  A fresh or reset env has
@@ -283,6 +278,28 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
     const int4 iv = a.si[i];
     qx = load_qrow(a.qa, a.qb, (unsigned)iv.x < (unsigned)(DQL_N_CELLS / DQL_N_ACTIONS) ? iv.x : 0);
     load_env(e, a.sr, iv, a.n, i, XMODE == X_ONLY ? x_only(a.c) : a.c);
+  }
+  // XMODE (dql_device.hpp agent_period): in an x-axis kernel the config's two_axis is the constant 0 — every y-axis branch of the step folds away
+  SimK<T> cfgk = a.c;
+  if constexpr (XMODE == X_ONLY) cfgk.two_axis = 0;
+  // register headroom (<= 2 waves per SIMD: 256 VGPRs): the manager tick's and the period's run-time constants move to VGPRs once per launch
+  if constexpr (sizeof(T) == 4 && BLOCK < 512) cfgk = period_consts_in_vgprs(cfgk);
+  // the Philox round keys (a launch constant) in VGPRs, where there are registers to spare (philox4x32)
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4 && BLOCK < 512 && (TICK == TICK_LIT || TICK == TICK_PLAIN)) {  // (the VGPR-constant layouts have their registers spoken for: 112 SGPR spills with the keys against 47)
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  if (STAGED) {
+    for (int t = 0; t < n_tab; ++t)
+      for (int c = tid; c < ncell; c += BLOCK) { sT[t * DQL_N_CELLS + c] = 0ull; sM[t * DQL_N_CELLS + c] = 0u; }
+    if (tid < 4 + 7) sStat[tid] = 0ull;
+    __syncthreads();
+  }
+  DQL_WAVE_END_VAR(clk1);
+  if (i < a.n) {
     DQL_MARK_T(e, 2);
     DQL_PHASE_LOADED(e, clk_start);
   }
@@ -293,11 +310,6 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
   // terminal histogram of the wave over the launch: one ballot per CheckResult code and period instead of one global atomic per finished
   // episode (thousands per period on a handful of addresses at large batches)
   unsigned code_w[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
-  // XMODE (dql_device.hpp agent_period): in an x-axis kernel the config's two_axis is the constant 0 — every y-axis branch of the step folds away
-  SimK<T> cfgk = a.c;
-  if constexpr (XMODE == X_ONLY) cfgk.two_axis = 0;
-  // register headroom (<= 2 waves per SIMD: 256 VGPRs): the manager tick's and the period's run-time constants move to VGPRs once per launch
-  if constexpr (sizeof(T) == 4 && BLOCK < 512) cfgk = period_consts_in_vgprs(cfgk);
   // float64: the tick's constants are read from LDS.  As kernel arguments they are SGPR PAIRS — some 150 of them against 100 scalar registers — and the
   // compiler parked the overflow in VGPR lanes: ~850 v_readlane_b32 per physics tick, three quarters of the tick's instructions, around 264 float64 operations.
   // One copy per workgroup, read back where used (agent_period's plain loop keeps the compiler from hoisting the reads out of the tick loop again).
@@ -307,14 +319,6 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
     __syncthreads();
   }
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
-  // the Philox round keys (a launch constant) in VGPRs, where there are registers to spare (philox4x32)
-  uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4 && BLOCK < 512 && (TICK == TICK_LIT || TICK == TICK_PLAIN)) {  // (the VGPR-constant layouts have their registers spoken for: 112 SGPR spills with the keys against 47)
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
   // ROUND 5: the two waves of a SIMD take turns at the issue priority.  The arbiter serves priority first, then AGE: of two waves running the same
   // program the older one is nearly unimpeded and the younger gets the leftover slots — at exactly two waves per SIMD the older half of the env
   // waves finished a 16-period launch after 272 us and the younger half then ran ALONE, at a lone wave's issue rate, for another 55 us
@@ -382,26 +386,27 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
   rfx_w = wave_sum(rfx_lane);
   dec = dec_w; don = don_w; rfx = rfx_w;
   if (STAGED) {
-    if ((tid & 63) == 0) {
-      if (dec) atomicAdd(&sStat[0], (unsigned long long)dec);
-      if (don) atomicAdd(&sStat[1], (unsigned long long)don);
-      if (rfx) atomicAdd(&sStat[2], (unsigned long long)rfx);
+    // the wave's statistics (wave-uniform) go out from lanes 0 .. 10, one value per lane: one LDS atomic per wave and, behind the barrier, one global
+    // atomic per workgroup — not eleven of each from a single lane, one after the other
+    const int lane = tid & 63;
+    unsigned long long sv = lane == 0 ? (unsigned long long)dec : lane == 1 ? (unsigned long long)don : lane == 2 ? (unsigned long long)rfx : 0ull;
 #pragma unroll
-      for (int k = 0; k <= DQL_TERMINAL_TIMEOUT; ++k) if (code_w[k]) atomicAdd(&sStat[4 + k], (unsigned long long)code_w[k]);
-    }
+    for (int k = 0; k <= DQL_TERMINAL_TIMEOUT; ++k) if (lane == 4 + k) sv = (unsigned long long)code_w[k];
+    if (lane < 4 + 7 && sv) atomicAdd(&sStat[lane], sv);
     __syncthreads();
+    if (tid < 4 + 7) {
+      const unsigned long long v = sStat[tid];
+      unsigned long long* g = tid == 0 ? &a.stats->decisions : tid == 1 ? &a.stats->episodes : tid == 2 ? (unsigned long long*)&a.stats->reward_fx : &a.stats->by_code[tid < 4 ? 0 : tid - 4];
+      if (v) atomicAdd(g, v);  // (slot 3 is spare and stays 0)
+    }
     for (int t = 0; t < n_tab; ++t)
       for (int c = tid; c < ncell; c += BLOCK) {
         const unsigned int m = sM[t * DQL_N_CELLS + c];
-        if (m) { atomicAdd(&a.acc_cur[t * DQL_ACC_B + c], sT[t * DQL_N_CELLS + c]); atomicAdd(&a.acc_cur[t * DQL_ACC_B + DQL_N_CELLS + c], (unsigned long long)m); }
+        const unsigned long long s = sT[t * DQL_N_CELLS + c];
+        if (s) atomicAdd(&a.acc_cur[t * DQL_ACC_B + c], s);
+        if (m) atomicAdd(&a.acc_cur[t * DQL_ACC_B + DQL_N_CELLS + c], (unsigned long long)m);
       }
-    if (tid == 0) {
-      dec = (long long)sStat[0]; don = (long long)sStat[1]; rfx = (long long)sStat[2];
-#pragma unroll
-      for (int k = 0; k <= DQL_TERMINAL_TIMEOUT; ++k) code_w[k] = (unsigned)sStat[4 + k];
-    }
-  }
-  if (tid == 0) {
+  } else if (tid == 0) {
     if (dec) atomicAdd(&a.stats->decisions, (unsigned long long)dec);
     if (don) atomicAdd(&a.stats->episodes, (unsigned long long)don);
     if (rfx) atomicAdd((unsigned long long*)&a.stats->reward_fx, (unsigned long long)rfx);
