@@ -143,6 +143,24 @@ SYMBOLS = {
     "dql_pop_get_step_index": (C.c_int, [_vp, _i32, C.POINTER(_i64)]),
     "dql_pop_set_step_index": (C.c_int, [_vp, _i32, _i64]),
     "dql_pop_index_faults": (C.c_int, [_vp, _i32, C.POINTER(_i64)]),
+    # ensembles of sequential learners (include/dql.h dql_ensemble_*)
+    "dql_ensemble_create": (C.c_int, [_cfgp, C.c_int, _i64, _u64, _i32, C.POINTER(_vp)]),
+    "dql_ensemble_destroy": (C.c_int, [_vp]),
+    "dql_ensemble_n_learners": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "dql_ensemble_set_schedules": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32]),
+    "dql_ensemble_set_level": (C.c_int, [_vp, _i32]),
+    "dql_ensemble_rearm": (C.c_int, [_vp]),
+    "dql_ensemble_run": (C.c_int, [_vp, _i64]),
+    "dql_ensemble_get_period_index": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "dql_ensemble_n_live": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "dql_ensemble_transfer": (C.c_int, [_vp, _i32, _dbl]),
+    "dql_ensemble_get_tables": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "dql_ensemble_set_tables": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "dql_ensemble_get_counters": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dql_ensemble_get_episode_log": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
+    "dql_ensemble_get_state": (C.c_int, [_vp, _vp, _vp]),
+    "dql_ensemble_index_faults": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "dql_diag_ensemble_last": (C.c_int, [_vp, C.POINTER(_dbl)]),
 }
 MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS
 

@@ -30,6 +30,7 @@
 #include "dql_device.hpp"
 #include "dql_host_consts.hpp"
 #include "dql_rollout.hpp"
+#include "dql_learner.hpp"
 #include "../../include/dql_diag.h"
 
 using namespace dql;
@@ -1019,6 +1020,53 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   const bool trace_wave = a.out.trace != nullptr && blockIdx.x == 0;   // the first trace_envs <= 64 envs of table set 0: wave 0 of the grid, nobody else
   rollout_episode<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.mgr0, a.sched, kv, a.out, g, trace_wave,
                                trace_wave && tid < a.out.trace_envs);
+}
+
+// ---- sequential learners (dql_ensemble) ----
+// One learner per lane (csrc/dql_learner.hpp: learner_periods), workgroups of one wave as in k_rollout; the env stays in registers for all periods of the launch,
+// the tables are the lane's own [DQL_N_CELLS] slices (per-lane global pointers, ordinary vector loads and stores, no atomics).
+template <typename T> struct LearnArgs {
+  SimK<T> c;
+  const MdpK<T> DQL_CONST_AS* mdp;
+  MdpRun<T> mdp_run;
+  LearnSched sched;
+  LearnMem mem;
+  Quad<T>* sr; int4* si;
+  const long long DQL_CONST_AS* mgr0; const int DQL_CONST_AS* tick_sched;  // [n_periods] (fill_schedule from period j0)
+  unsigned long long seed;
+  long long j0;
+  int n_periods;
+};
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_learn(LearnArgs<T> a) {
+  const int tid = threadIdx.x;
+  const long long l = (long long)blockIdx.x * 64 + tid;
+  SimK<T> cl = a.c;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  learner_periods<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.sched, a.mem, a.sr, a.si, a.seed, l, l < a.mem.n, a.j0, a.n_periods, a.mgr0, a.tick_sched, kv);
+}
+// transfer_learning on every learner's tables: Q[l][k] = Q[l][src] * ratio (k_transfer's arithmetic)
+__global__ void k_ens_transfer(double* qa, double* qb, long long n, int k, int src, double ratio) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * DQL_CELLS_PER_LEVEL) return;
+  const long long l = t / DQL_CELLS_PER_LEVEL; const int i = (int)(t - l * DQL_CELLS_PER_LEVEL);
+  double* a = qa + l * DQL_N_CELLS; double* b = qb + l * DQL_N_CELLS;
+  a[k * DQL_CELLS_PER_LEVEL + i] = a[src * DQL_CELLS_PER_LEVEL + i] * ratio;
+  b[k * DQL_CELLS_PER_LEVEL + i] = b[src * DQL_CELLS_PER_LEVEL + i] * ratio;
 }
 
 struct dql_ctx {
@@ -2460,6 +2508,317 @@ int dql_diag_rollout_last(double* kernel_ms, int32_t* out3) {
   if (g_rollout_ms < 0.0) return fail(DQL_ESTATE, "no dql_rollout call has completed on this thread");
   *kernel_ms = g_rollout_ms;
   for (int k = 0; k < 3; ++k) out3[k] = g_rollout_inst[k];
+  return DQL_OK;
+}
+
+// ---- ensembles of sequential learners ----
+struct dql_ensemble {
+  dql_config cfg;
+  int device = 0;
+  long long n = 0;
+  unsigned long long seed = 0;
+  long long j = 0;  // the ensemble's period index (period 0 is the reset period)
+  void* sr = nullptr; int4* si = nullptr; void* mdpk = nullptr;
+  LearnMem mem{};
+  LearnSched sched{};
+  double* alpha_tab = nullptr; uint32_t* eps_tab = nullptr;
+  long long* d_mgr0 = nullptr; int* d_sched = nullptr;  // [LEARN_MAX_PERIODS]
+  double last_ms = -1.0;
+};
+#define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
+static void ens_free(dql_ensemble* x) {
+  void* ptrs[] = {x->sr, x->si, x->mdpk, x->mem.qa, x->mem.qb, x->mem.count, x->mem.decisions, x->mem.by_code, x->mem.episodes, x->mem.successes, x->mem.level_episodes,
+                  x->mem.win_count, x->mem.win_bits, x->mem.promoted, x->mem.frozen, x->mem.log_code, x->mem.log_len, x->mem.log_n, x->mem.faults, x->alpha_tab, x->eps_tab,
+                  x->d_mgr0, x->d_sched};
+  for (void* p : ptrs) if (p) (void)hipFree(p);
+  delete x;
+}
+static int ens_upload_mdpk(dql_ensemble* x) {
+  if (x->cfg.dtype == DQL_F32) { const MdpK<float> m = make_mdpk<float>(x->cfg); HIP_TRY(hipMemcpy(x->mdpk, &m, sizeof(m), hipMemcpyHostToDevice)); }
+  else { const MdpK<double> m = make_mdpk<double>(x->cfg); HIP_TRY(hipMemcpy(x->mdpk, &m, sizeof(m), hipMemcpyHostToDevice)); }
+  return DQL_OK;
+}
+// per-level episode counts, windows, promotion records and frozen flags back to "just started"
+static int ens_rearm(dql_ensemble* x) {
+  const size_t n = (size_t)x->n;
+  HIP_TRY(hipMemset(x->mem.level_episodes, 0, n * sizeof(int)));
+  HIP_TRY(hipMemset(x->mem.win_count, 0, n * sizeof(int)));
+  HIP_TRY(hipMemset(x->mem.win_bits, 0, 2 * n * sizeof(unsigned long long)));
+  HIP_TRY(hipMemset(x->mem.promoted, 0xff, n * sizeof(int)));
+  HIP_TRY(hipMemset(x->mem.frozen, 0, n * sizeof(int)));
+  return DQL_OK;
+}
+extern "C++" {
+template <typename T> static int ens_init(dql_ensemble* x) {
+  InitArgs<T> a;
+  a.c = make_simk<T>(x->cfg);
+  a.sr = (Quad<T>*)x->sr; a.si = x->si; a.n = x->n; a.seed = x->seed; a.env_id_offset = 0;
+  const RolloutInit<T> r = make_rollout_init<T>(x->cfg);
+  a.hover = r.hover; a.vz_integ = r.vz_integ; a.r_lo = r.r_lo; a.r_hi = r.r_hi; a.t_lo = r.t_lo; a.t_hi = r.t_hi;
+  hipLaunchKernelGGL(k_init<T>, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, a);
+  HIP_TRY(hipGetLastError());
+  return DQL_OK;
+}
+template <typename T> static void ens_launch(dql_ensemble* x, int n_periods) {
+  LearnArgs<T> a;
+  a.c = make_simk<T>(x->cfg);
+  a.mdp = (const MdpK<T> DQL_CONST_AS*)x->mdpk;
+  a.mdp_run = MdpRun<T>{x->cfg.gamma, (T)(x->cfg.t_max * x->cfg.f_ag), x->cfg.goal_logic};
+  a.sched = x->sched; a.mem = x->mem;
+  a.sr = (Quad<T>*)x->sr; a.si = x->si;
+  a.mgr0 = (const long long DQL_CONST_AS*)x->d_mgr0; a.tick_sched = (const int DQL_CONST_AS*)x->d_sched;
+  a.seed = x->seed; a.j0 = x->j; a.n_periods = n_periods;
+  hipLaunchKernelGGL((k_learn<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)((x->n + 63) / 64)), dim3(64), 0, 0, a);
+}
+template <typename T> static int ens_get_state_t(dql_ensemble* x, double* out) {
+  const long long n = x->n;
+  std::vector<T> h((size_t)NQ_REAL * n * 4);
+  HIP_TRY(hipMemcpy(h.data(), x->sr, h.size() * sizeof(T), hipMemcpyDeviceToHost));
+  for (int f = 0; f < NF_REAL; ++f) { const int q = f / 4, k = f % 4; for (long long i = 0; i < n; ++i) out[(long long)f * n + i] = (double)h[((size_t)q * n + i) * 4 + k]; }
+  return DQL_OK;
+}
+}  // extern "C++"
+#define ENS_ALLOC(ptr, bytes) do { if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { (ptr) = nullptr; ens_free(x); return fail(DQL_ENOMEM, "hipMalloc failed"); } \
+                                   if (hipMemset((ptr), 0, (bytes)) != hipSuccess) { ens_free(x); return fail(DQL_EHIP, "hipMemset failed"); } } while (0)
+int dql_ensemble_create(const dql_config* cfg, int device, int64_t n_learners, uint64_t seed, int32_t log_capacity, dql_ensemble** out) {
+  int rc = check_config(cfg); if (rc) return rc;
+  if (!out) return fail(DQL_EINVAL, "dql_ensemble_create: null pointer; nothing was launched");
+  if (cfg->two_axis) return fail(DQL_EINVAL, "dql_ensemble_create: two-axis configs are refused (the reference's learner is x-only); nothing was launched");
+  if (cfg->trajectory == DQL_TRAJ_EIGHT) return fail(DQL_EINVAL, "dql_ensemble_create: the figure-eight trajectory is refused (the reference's learner is x-only); nothing was launched");
+  if (n_learners < 1 || n_learners > DQL_ENSEMBLE_MAX_LEARNERS) return fail(DQL_EINVAL, "dql_ensemble_create: n_learners must be in 1..2^20 (DQL_ENSEMBLE_MAX_LEARNERS); nothing was launched");
+  if (log_capacity < 0 || log_capacity > DQL_ENSEMBLE_MAX_LOG) return fail(DQL_EINVAL, "dql_ensemble_create: log_capacity must be in 0..2^20 (DQL_ENSEMBLE_MAX_LOG); nothing was launched");
+  OP_PROLOGUE(device)
+  dql_ensemble* x = new dql_ensemble;
+  x->cfg = *cfg; x->device = device; x->n = n_learners; x->seed = seed;
+  const size_t n = (size_t)n_learners, real = cfg->dtype == DQL_F32 ? 4 : 8;
+  const size_t TB = n * DQL_N_CELLS * sizeof(double);
+  ENS_ALLOC(x->sr, (size_t)NQ_REAL * n * 4 * real);
+  ENS_ALLOC(x->si, n * sizeof(int4));
+  ENS_ALLOC(x->mdpk, cfg->dtype == DQL_F32 ? sizeof(MdpK<float>) : sizeof(MdpK<double>));
+  ENS_ALLOC(x->mem.qa, TB); ENS_ALLOC(x->mem.qb, TB); ENS_ALLOC(x->mem.count, TB);
+  ENS_ALLOC(x->mem.decisions, n * sizeof(unsigned long long));
+  ENS_ALLOC(x->mem.by_code, (size_t)DQL_N_CHECK_CODES * n * sizeof(unsigned long long));
+  ENS_ALLOC(x->mem.episodes, n * sizeof(int)); ENS_ALLOC(x->mem.successes, n * sizeof(int));
+  ENS_ALLOC(x->mem.level_episodes, n * sizeof(int)); ENS_ALLOC(x->mem.win_count, n * sizeof(int));
+  ENS_ALLOC(x->mem.win_bits, 2 * n * sizeof(unsigned long long));
+  ENS_ALLOC(x->mem.promoted, n * sizeof(int)); ENS_ALLOC(x->mem.frozen, n * sizeof(int));
+  ENS_ALLOC(x->mem.log_code, n * (size_t)(log_capacity ? log_capacity : 1)); ENS_ALLOC(x->mem.log_len, n * (size_t)(log_capacity ? log_capacity : 1) * sizeof(uint16_t));
+  ENS_ALLOC(x->mem.log_n, n * sizeof(int));
+  ENS_ALLOC(x->mem.faults, sizeof(unsigned long long));
+  ENS_ALLOC(x->d_mgr0, (size_t)LEARN_MAX_PERIODS * sizeof(long long)); ENS_ALLOC(x->d_sched, (size_t)LEARN_MAX_PERIODS * sizeof(int));
+  x->mem.n = n_learners; x->mem.log_cap = log_capacity;
+  rc = ens_upload_mdpk(x);
+  if (!rc) rc = ens_rearm(x);
+  if (!rc) rc = cfg->dtype == DQL_F32 ? ens_init<float>(x) : ens_init<double>(x);
+  // default schedules: the plateau learning rate, no exploration, the reference's window (100 episodes, 97 successes) and no episode budget
+  const double a0 = cfg->alpha_min; const double e0 = 0.0;
+  if (!rc) rc = dql_ensemble_set_schedules(x, &a0, 1, &e0, 1, 100, 97, INT32_MAX);
+  if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(DQL_EHIP, "hipDeviceSynchronize failed");
+  if (rc) { ens_free(x); return rc; }
+  *out = x;
+  return DQL_OK;
+}
+int dql_ensemble_destroy(dql_ensemble* x) {
+  if (!x) return DQL_OK;
+  (void)hipSetDevice(x->device);
+  (void)hipDeviceSynchronize();
+  ens_free(x);
+  return DQL_OK;
+}
+int dql_ensemble_n_learners(dql_ensemble* x, int64_t* n) {
+  CHECK_ENS(x);
+  if (!n) return fail(DQL_EINVAL, "null pointer");
+  *n = x->n;
+  return DQL_OK;
+}
+int dql_ensemble_set_schedules(dql_ensemble* x, const double* alpha, int32_t n_alpha, const double* eps, int32_t n_eps, int32_t window, int32_t min_successes,
+                               int32_t max_episodes) {
+  CHECK_ENS(x);
+  if (!alpha || !eps) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: null table");
+  if (n_alpha < 1 || n_alpha > (1 << 22) || n_eps < 1 || n_eps > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: table lengths must be in 1..2^22");
+  if (window < 1 || window > DQL_ENSEMBLE_MAX_WINDOW) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: the promotion window must be in 1..128 (DQL_ENSEMBLE_MAX_WINDOW)");
+  if (min_successes < 1 || max_episodes < 1) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: min_successes and max_episodes must be positive");
+  for (int i = 0; i < n_alpha; ++i) if (!(alpha[i] >= 0.0 && alpha[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: learning rates must be in [0, 1]");
+  for (int i = 0; i < n_eps; ++i) if (!(eps[i] >= 0.0 && eps[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: exploration rates must be in [0, 1]");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<uint32_t> thr((size_t)n_eps);
+  for (int i = 0; i < n_eps; ++i) thr[(size_t)i] = eps_threshold(eps[i]);
+  double* d_a = nullptr; uint32_t* d_e = nullptr;
+  if (hipMalloc((void**)&d_a, (size_t)n_alpha * sizeof(double)) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc failed");
+  if (hipMalloc((void**)&d_e, (size_t)n_eps * sizeof(uint32_t)) != hipSuccess) { (void)hipFree(d_a); return fail(DQL_ENOMEM, "hipMalloc failed"); }
+  if (hipMemcpy(d_a, alpha, (size_t)n_alpha * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_e, thr.data(), (size_t)n_eps * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d_a); (void)hipFree(d_e);
+    return fail(DQL_EHIP, "hipMemcpy failed");
+  }
+  if (x->alpha_tab) (void)hipFree(x->alpha_tab);
+  if (x->eps_tab) (void)hipFree(x->eps_tab);
+  x->alpha_tab = d_a; x->eps_tab = d_e;
+  x->sched = LearnSched{d_a, n_alpha, x->cfg.alpha_min, d_e, n_eps, window, min_successes, max_episodes};
+  return DQL_OK;
+}
+int dql_ensemble_rearm(dql_ensemble* x) {
+  CHECK_ENS(x);
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  return ens_rearm(x);
+}
+int dql_ensemble_set_level(dql_ensemble* x, int32_t k) {
+  CHECK_ENS(x);
+  if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_level: curriculum step must be in 0..4");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  x->cfg.working_curriculum_step = k;
+  int rc = ens_upload_mdpk(x); if (rc) return rc;
+  hipLaunchKernelGGL(k_mark_reset, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->si, (const uint8_t*)nullptr, (long long)x->n);  // every env re-enters through reset
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  return ens_rearm(x);
+}
+int dql_ensemble_n_live(dql_ensemble* x, int64_t* n_live) {
+  CHECK_ENS(x);
+  if (!n_live) return fail(DQL_EINVAL, "null pointer");
+  HIP_TRY(hipSetDevice(x->device));
+  std::vector<int> h((size_t)x->n);
+  HIP_TRY(hipMemcpy(h.data(), x->mem.frozen, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+  int64_t live = 0;
+  for (int v : h) live += v ? 0 : 1;
+  *n_live = live;
+  return DQL_OK;
+}
+int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
+  CHECK_ENS(x);
+  if (periods < 1 || periods > (1ll << 40)) return fail(DQL_EINVAL, "dql_ensemble_run: periods must be in 1..2^40; nothing was launched");
+  HIP_TRY(hipSetDevice(x->device));
+  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
+  HIP_TRY(hipEventCreate(&e0.e)); HIP_TRY(hipEventCreate(&e1.e));
+  HIP_TRY(hipEventRecord(e0.e, 0));
+  std::vector<long long> h_mgr0((size_t)LEARN_MAX_PERIODS);
+  std::vector<int> h_sched((size_t)LEARN_MAX_PERIODS);
+  long long left = periods;
+  while (left > 0) {
+    const int k = (int)(left < LEARN_MAX_PERIODS ? left : LEARN_MAX_PERIODS);
+    if (left != periods) {  // between the launches of a long run: nothing left to fly ends it (the period index still advances by `periods`)
+      int64_t live = 0;
+      int rc = dql_ensemble_n_live(x, &live); if (rc) return rc;
+      if (live == 0) { x->j += left; break; }
+    }
+    fill_schedule(x->cfg, x->j, h_mgr0.data(), h_sched.data(), k);
+    HIP_TRY(hipMemcpy(x->d_mgr0, h_mgr0.data(), (size_t)k * sizeof(long long), hipMemcpyHostToDevice));  // (synchronous: the previous launch has read its schedule)
+    HIP_TRY(hipMemcpy(x->d_sched, h_sched.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice));
+    if (x->cfg.dtype == DQL_F32) ens_launch<float>(x, k); else ens_launch<double>(x, k);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    x->j += k; left -= k;
+  }
+  HIP_TRY(hipEventRecord(e1.e, 0));
+  HIP_TRY(hipEventSynchronize(e1.e));
+  float ms = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
+  x->last_ms = (double)ms;
+  return DQL_OK;
+}
+int dql_ensemble_get_period_index(dql_ensemble* x, int64_t* j) {
+  CHECK_ENS(x);
+  if (!j) return fail(DQL_EINVAL, "null pointer");
+  *j = x->j;
+  return DQL_OK;
+}
+int dql_ensemble_transfer(dql_ensemble* x, int32_t k, double ratio) {
+  CHECK_ENS(x);
+  if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_transfer: curriculum step must be in 0..4");
+  HIP_TRY(hipSetDevice(x->device));
+  const long long total = x->n * DQL_CELLS_PER_LEVEL;
+  hipLaunchKernelGGL(k_ens_transfer, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, x->mem.qa, x->mem.qb, (long long)x->n, (int)k,
+                     (int)((k - 1 + DQL_MAX_LEVELS) % DQL_MAX_LEVELS), ratio);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  return DQL_OK;
+}
+static int ens_slice(dql_ensemble* x, int64_t first, int64_t count, const char* who) {
+  if (first < 0 || count < 1 || first > x->n || count > x->n - first) return fail(DQL_EINVAL, std::string(who) + ": the slice [first, first + count) must lie inside [0, n_learners) and hold at least one learner");
+  return DQL_OK;
+}
+int dql_ensemble_get_tables(dql_ensemble* x, int64_t first, int64_t count, double* qa_or_null, double* qb_or_null, double* count_or_null) {
+  CHECK_ENS(x);
+  int rc = ens_slice(x, first, count, "dql_ensemble_get_tables"); if (rc) return rc;
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t off = (size_t)first * DQL_N_CELLS, bytes = (size_t)count * DQL_N_CELLS * sizeof(double);
+  if (qa_or_null) HIP_TRY(hipMemcpy(qa_or_null, x->mem.qa + off, bytes, hipMemcpyDeviceToHost));
+  if (qb_or_null) HIP_TRY(hipMemcpy(qb_or_null, x->mem.qb + off, bytes, hipMemcpyDeviceToHost));
+  if (count_or_null) HIP_TRY(hipMemcpy(count_or_null, x->mem.count + off, bytes, hipMemcpyDeviceToHost));
+  return DQL_OK;
+}
+int dql_ensemble_set_tables(dql_ensemble* x, int64_t first, int64_t count, const double* qa_or_null, const double* qb_or_null, const double* count_or_null) {
+  CHECK_ENS(x);
+  int rc = ens_slice(x, first, count, "dql_ensemble_set_tables"); if (rc) return rc;
+  if (count_or_null)  // the counters index the learning-rate table on the device
+    for (size_t i = 0; i < (size_t)count * DQL_N_CELLS; ++i)
+      if (!(count_or_null[i] >= 0.0 && count_or_null[i] < 9007199254740992.0)) return fail(DQL_EINVAL, "dql_ensemble_set_tables: visit counters must be in [0, 2^53)");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t off = (size_t)first * DQL_N_CELLS, bytes = (size_t)count * DQL_N_CELLS * sizeof(double);
+  if (qa_or_null) HIP_TRY(hipMemcpy(x->mem.qa + off, qa_or_null, bytes, hipMemcpyHostToDevice));
+  if (qb_or_null) HIP_TRY(hipMemcpy(x->mem.qb + off, qb_or_null, bytes, hipMemcpyHostToDevice));
+  if (count_or_null) HIP_TRY(hipMemcpy(x->mem.count + off, count_or_null, bytes, hipMemcpyHostToDevice));
+  return DQL_OK;
+}
+int dql_ensemble_get_counters(dql_ensemble* x, int64_t* decisions, int64_t* episodes, int64_t* successes, int64_t* by_code, int32_t* promoted, int32_t* level_episodes,
+                              uint8_t* frozen) {
+  CHECK_ENS(x);
+  if (!decisions || !episodes || !successes || !by_code || !promoted || !level_episodes || !frozen) return fail(DQL_EINVAL, "dql_ensemble_get_counters: null array");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t n = (size_t)x->n;
+  std::vector<int> h(n);
+  HIP_TRY(hipMemcpy(decisions, x->mem.decisions, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(by_code, x->mem.by_code, (size_t)DQL_N_CHECK_CODES * n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h.data(), x->mem.episodes, n * sizeof(int), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; ++i) episodes[i] = h[i];
+  HIP_TRY(hipMemcpy(h.data(), x->mem.successes, n * sizeof(int), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; ++i) successes[i] = h[i];
+  HIP_TRY(hipMemcpy(promoted, x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(level_episodes, x->mem.level_episodes, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h.data(), x->mem.frozen, n * sizeof(int), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; ++i) frozen[i] = h[i] ? 1 : 0;
+  return DQL_OK;
+}
+int dql_ensemble_get_episode_log(dql_ensemble* x, uint8_t* code, uint16_t* length, int32_t capacity, int32_t* n_episodes) {
+  CHECK_ENS(x);
+  if (!code || !length || !n_episodes) return fail(DQL_EINVAL, "dql_ensemble_get_episode_log: null array");
+  if (capacity != x->mem.log_cap || capacity < 1) return fail(DQL_EINVAL, "dql_ensemble_get_episode_log: capacity must be the (positive) log capacity the ensemble was created with");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t n = (size_t)x->n * (size_t)capacity;
+  HIP_TRY(hipMemcpy(code, x->mem.log_code, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(length, x->mem.log_len, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n_episodes, x->mem.log_n, (size_t)x->n * sizeof(int), hipMemcpyDeviceToHost));
+  return DQL_OK;
+}
+int dql_ensemble_get_state(dql_ensemble* x, double* reals, int32_t* ints) {
+  CHECK_ENS(x);
+  if (!reals || !ints) return fail(DQL_EINVAL, "dql_ensemble_get_state: null array");
+  HIP_TRY(hipSetDevice(x->device));
+  int rc = x->cfg.dtype == DQL_F32 ? ens_get_state_t<float>(x, reals) : ens_get_state_t<double>(x, reals);
+  if (rc) return rc;
+  const long long n = x->n;
+  std::vector<int4> h((size_t)n);
+  HIP_TRY(hipMemcpy(h.data(), x->si, (size_t)n * sizeof(int4), hipMemcpyDeviceToHost));
+  for (long long i = 0; i < n; ++i) {
+    ints[0 * n + i] = h[i].x; ints[1 * n + i] = h[i].y; ints[2 * n + i] = h[i].z & 0xffff; ints[3 * n + i] = (h[i].z >> 16) & 0xffff;
+    ints[4 * n + i] = h[i].w & 0xff; ints[5 * n + i] = (h[i].w >> 8) & 0xff; ints[6 * n + i] = (h[i].w >> 16) & 0xff;
+  }
+  return DQL_OK;
+}
+int dql_ensemble_index_faults(dql_ensemble* x, int64_t* n) {
+  CHECK_ENS(x);
+  if (!n) return fail(DQL_EINVAL, "null pointer");
+  HIP_TRY(hipSetDevice(x->device));
+  unsigned long long v = 0;
+  HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
+  *n = (int64_t)v;
+  return DQL_OK;
+}
+int dql_diag_ensemble_last(dql_ensemble* x, double* run_ms) {
+  CHECK_ENS(x);
+  if (!run_ms) return fail(DQL_EINVAL, "null pointer");
+  if (x->last_ms < 0.0) return fail(DQL_ESTATE, "no dql_ensemble_run call has completed on this ensemble");
+  *run_ms = x->last_ms;
   return DQL_OK;
 }
 

@@ -1,0 +1,255 @@
+"""`SequentialEnsemble`: L independent copies of the reference's OWN training loop — one env, one agent, update after every step
+(pkg/trainer.py:187-236) — flown by one kernel launch, one learner per GPU lane (include/dql.h dql_ensemble_*).
+
+Where `Engine` trains one set of tables on N envs with the batched mean-target fold, every learner here keeps its own `Q_table_a`, `Q_table_b` and
+`state_action_counter` and applies `DoubleQLearningAgent.update` right after each of its agent periods.  A learner freezes when the reference's
+promotion rule fires for it (successes among its last `window` episodes at the level reach `min_successes`) or when its episode budget is spent;
+`train_level` / `curriculum` are `Trainer.curriculum_training` for the whole ensemble: run until all learners are frozen, transfer, next level.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from types import SimpleNamespace
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from .config import CHECK_NAMES, DqlConfig, N_CELLS
+
+MAX_PERIODS_PER_LAUNCH = 4096  # include/dql.h DQL_ENSEMBLE_MAX_PERIODS
+MAX_WINDOW = 128               # DQL_ENSEMBLE_MAX_WINDOW
+MAX_LEARNERS = 1 << 20         # DQL_ENSEMBLE_MAX_LEARNERS
+N_CODES = len(CHECK_NAMES)
+GOAL = CHECK_NAMES.index("TERMINAL_SUCCESS")
+STATE_REAL_FIELDS = ("cum_x", "reward", "px", "py", "pz", "vx", "vy", "vz", "mp_x", "mp_u", "qw", "qx", "qy", "qz", "pitch_sp")
+STATE_INT_FIELDS = ("idx_x", "step_count", "code", "flags", "action")
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def eps_threshold(eps: float) -> int:
+    """csrc/dql_host_consts.hpp eps_threshold: the number of k in [0, 2^24) with k 2^-24 < eps; explore <=> (r >> 8) < threshold"""
+    if not eps > 0.0:
+        return 0
+    return min(int(math.ceil(eps * 16777216.0)), 16777216)
+
+
+def exploration_rates(level: int, n: int = 2001) -> np.ndarray:
+    """`Trainer.exploration_rate(e, level)` for the episode index e = 0 .. n - 1 within the level (pkg/trainer.py:112-126); a learner past the table's end
+    keeps its last entry (2 001 entries reach the 0.01 floor of level 0).  Levels above 0 do not explore: one zero."""
+    from .trainer import Trainer
+    if level > 0:
+        return np.zeros(1)
+    me = SimpleNamespace()
+    return np.array([Trainer.exploration_rate(me, e, level) for e in range(int(n))], dtype=np.float64)
+
+
+def eps_threshold_table(level: int, n: int = 2001) -> np.ndarray:
+    """the thresholds the kernel compares the action word with, per episode index within the level"""
+    return np.array([eps_threshold(float(e)) for e in exploration_rates(level, n)], dtype=np.uint32)
+
+
+def min_successes_for(window: int = 100, success_rate: float = 0.96) -> int:
+    """The reference promotes when `sum(deque) / window > success_rate`, with the divisor `window` also while the deque fills (pkg/trainer.py:219-236):
+    the smallest success count that does it — 97 for (100, 0.96)."""
+    if window < 1 or not 0.0 <= success_rate < 1.0:
+        raise ValueError("window must be positive and success_rate in [0, 1)")
+    k = 0
+    while not k / window > success_rate:
+        k += 1
+    return k
+
+
+class SequentialEnsemble:
+    def __init__(self, cfg: DqlConfig, n_learners: int, seed: int = 42, device: int = 0, log_capacity: int = 0, alpha_table=None, eps=None, window: int = 100,
+                 min_successes: Optional[int] = None, max_episodes: int = 50000):
+        n_learners, log_capacity = int(n_learners), int(log_capacity)
+        if cfg.two_axis:
+            raise ValueError("two-axis configs are refused: the reference's learner is x-only")
+        if cfg.trajectory != 0:
+            raise ValueError("the figure-eight trajectory is refused: the reference's learner is x-only")
+        if not 1 <= n_learners <= MAX_LEARNERS:
+            raise ValueError(f"n_learners must be in 1..{MAX_LEARNERS}")
+        if log_capacity < 0:
+            raise ValueError("log_capacity must not be negative")
+        self.lib = _lib.load()
+        self.cfg = cfg
+        self.n = n_learners
+        self.log_capacity = log_capacity
+        self._c = cfg.to_c()
+        h = C.c_void_p()
+        _lib.check(self.lib.dql_ensemble_create(C.byref(self._c), int(device), self.n, int(seed), log_capacity, C.byref(h)))
+        self._h = h
+        self.set_schedules(alpha_table, eps, window, min_successes, max_episodes)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.dql_ensemble_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- schedules and level ----
+    def set_schedules(self, alpha_table=None, eps=None, window: int = 100, min_successes: Optional[int] = None, max_episodes: int = 50000):
+        """alpha_table: alpha(count), default the config's; eps: exploration rate per episode index within the level, default the reference's for the
+        config's level; window / min_successes: the promotion rule (default: the reference's 0.96 of the window); max_episodes: budget per level"""
+        alpha = self.cfg.alpha_table() if alpha_table is None else np.ascontiguousarray(alpha_table, dtype=np.float64).ravel()
+        e = exploration_rates(self.cfg.working_curriculum_step) if eps is None else np.ascontiguousarray(eps, dtype=np.float64).ravel()
+        window = int(window)
+        if not 1 <= window <= MAX_WINDOW:
+            raise ValueError(f"window must be in 1..{MAX_WINDOW}")
+        ms = min_successes_for(window) if min_successes is None else int(min_successes)
+        if ms < 1 or int(max_episodes) < 1:
+            raise ValueError("min_successes and max_episodes must be positive")
+        if alpha.size < 1 or e.size < 1:
+            raise ValueError("the alpha and eps tables must not be empty")
+        _lib.check(self.lib.dql_ensemble_set_schedules(self._h, _p(alpha), alpha.size, _p(e), e.size, window, ms, int(max_episodes)))
+        self.window, self.min_successes, self.max_episodes = window, ms, int(max_episodes)
+
+    def set_level(self, level: int):
+        """new working level: every env re-enters through reset, per-level episode counts and windows are cleared, all learners re-armed"""
+        _lib.check(self.lib.dql_ensemble_set_level(self._h, int(level)))
+        self.cfg.working_curriculum_step = int(level)
+
+    def rearm(self):
+        _lib.check(self.lib.dql_ensemble_rearm(self._h))
+
+    def transfer(self, k: int, ratio: float):
+        """`DoubleQLearningAgent.transfer_learning` on every learner's tables (k = 0 wraps to the last level, B6)"""
+        _lib.check(self.lib.dql_ensemble_transfer(self._h, int(k), float(ratio)))
+
+    # ---- stepping ----
+    def run(self, periods: int):
+        if int(periods) < 1:
+            raise ValueError("periods must be positive")
+        _lib.check(self.lib.dql_ensemble_run(self._h, int(periods)))
+
+    def n_live(self) -> int:
+        v = C.c_int64()
+        _lib.check(self.lib.dql_ensemble_n_live(self._h, C.byref(v)))
+        return int(v.value)
+
+    def period_index(self) -> int:
+        v = C.c_int64()
+        _lib.check(self.lib.dql_ensemble_get_period_index(self._h, C.byref(v)))
+        return int(v.value)
+
+    def index_faults(self) -> int:
+        v = C.c_int64()
+        _lib.check(self.lib.dql_ensemble_index_faults(self._h, C.byref(v)))
+        return int(v.value)
+
+    # ---- tables ----
+    def _slice(self, first, count):
+        first = int(first)
+        count = self.n - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.n:
+            raise ValueError(f"the slice [first, first + count) must lie inside [0, {self.n}) and hold at least one learner")
+        return first, count
+
+    def get_tables(self, first: int = 0, count: Optional[int] = None):
+        """(Q_table_a, Q_table_b, state_action_counter), float64 [count][N_CELLS] each, of learners first .. first + count - 1"""
+        first, count = self._slice(first, count)
+        qa, qb, cnt = (np.empty((count, N_CELLS), dtype=np.float64) for _ in range(3))
+        _lib.check(self.lib.dql_ensemble_get_tables(self._h, first, count, _p(qa), _p(qb), _p(cnt)))
+        return qa, qb, cnt
+
+    def set_tables(self, qa=None, qb=None, count=None, first: int = 0):
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(-1, N_CELLS) for a in (qa, qb, count)]
+        given = [a for a in arrs if a is not None]
+        if not given:
+            raise ValueError("no table given")
+        if len({a.shape[0] for a in given}) != 1:
+            raise ValueError("the tables must cover the same learners")
+        first, n = self._slice(first, given[0].shape[0])
+        _lib.check(self.lib.dql_ensemble_set_tables(self._h, first, n, *(_p(a) for a in arrs)))
+
+    # ---- outputs ----
+    def counters(self):
+        n = self.n
+        dec, eps, suc = (np.zeros(n, dtype=np.int64) for _ in range(3))
+        by_code = np.zeros((N_CODES, n), dtype=np.int64)
+        promoted, lvl = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        frozen = np.zeros(n, dtype=np.uint8)
+        _lib.check(self.lib.dql_ensemble_get_counters(self._h, _p(dec), _p(eps), _p(suc), _p(by_code), _p(promoted), _p(lvl), _p(frozen)))
+        return {"decisions": dec, "episodes": eps, "successes": suc, "by_code": by_code, "promotion_episode": promoted, "level_episodes": lvl,
+                "frozen": frozen.astype(bool)}
+
+    def episode_log(self):
+        """(code uint8 [L][capacity], length uint16 [L][capacity], n int32 [L]): learner l's episode k < min(n[l], capacity); n counts on beyond it"""
+        if self.log_capacity < 1:
+            raise ValueError("the ensemble was created without an episode log (log_capacity = 0)")
+        code = np.zeros((self.n, self.log_capacity), dtype=np.uint8)
+        length = np.zeros((self.n, self.log_capacity), dtype=np.uint16)
+        cnt = np.zeros(self.n, dtype=np.int32)
+        _lib.check(self.lib.dql_ensemble_get_episode_log(self._h, _p(code), _p(length), self.log_capacity, _p(cnt)))
+        return code, length, cnt
+
+    def state(self):
+        """the env state after the last period: {field: float64 [L]} for STATE_REAL_FIELDS, {field: int32 [L]} for STATE_INT_FIELDS"""
+        reals = np.zeros((64, self.n), dtype=np.float64)
+        ints = np.zeros((7, self.n), dtype=np.int32)
+        _lib.check(self.lib.dql_ensemble_get_state(self._h, _p(reals), _p(ints)))
+        rn = [self.lib.dql_field_name(i, 0).decode() for i in range(64)]
+        inn = [self.lib.dql_field_name(i, 1).decode() for i in range(7)]
+        out = {f: reals[rn.index(f)].copy() for f in STATE_REAL_FIELDS}
+        out.update({f: ints[inn.index(f)].copy() for f in STATE_INT_FIELDS})
+        return out
+
+    def learning_curve(self, block: int = 1000):
+        """Per learner, in the shape of tests/g14_learning_curve.py::curve: goal share and mean length per `block` logged episodes, and the first promotion
+        episode (None where the window never filled)."""
+        code, length, cnt = self.episode_log()
+        promoted = self.counters()["promotion_episode"]
+        out = []
+        for l in range(self.n):
+            m = min(int(cnt[l]), self.log_capacity)
+            goal = (code[l, :m] == GOAL).astype(int)
+            steps = length[l, :m].astype(np.float64)
+            starts = range(0, m - block + 1, block)
+            out.append({"goal_share_per_1000_episodes" if block == 1000 else f"goal_share_per_{block}_episodes": [round(float(goal[a:a + block].mean()), 3) for a in starts],
+                        "mean_steps_per_1000_episodes" if block == 1000 else f"mean_steps_per_{block}_episodes": [round(float(steps[a:a + block].mean()), 1) for a in starts],
+                        "first_promotion_episode": int(promoted[l]) if promoted[l] >= 0 else None})
+        return out
+
+
+def train_level(ens: SequentialEnsemble, chunk_periods: int = 16 * MAX_PERIODS_PER_LAUNCH, max_periods: Optional[int] = None, on_chunk=None) -> int:
+    """Run the current level until every learner is frozen (promoted, or out of episodes) or `max_periods` are flown; -> periods flown."""
+    flown = 0
+    while ens.n_live() > 0 and (max_periods is None or flown < max_periods):
+        k = int(chunk_periods) if max_periods is None else min(int(chunk_periods), int(max_periods) - flown)
+        ens.run(k)
+        flown += k
+        if on_chunk is not None:
+            on_chunk(ens, flown)
+    return flown
+
+
+def curriculum(ens: SequentialEnsemble, levels: int = 5, first_level: int = 0, ratios=None, max_episodes: Optional[int] = None, max_periods_per_level: Optional[int] = None,
+               window: int = 100, success_rate: float = 0.96, on_level=None):
+    """`Trainer.curriculum_training` for the ensemble: per level, run until all learners are frozen, `transfer_learning` of the finished level with the
+    reference's ratio, next level.  -> per level, the counters at its end."""
+    from .trainer import Trainer
+    me = SimpleNamespace(_scale_modification_value=(0.8172650252856599, 0.8211253690681617, 0.8257273369742982, 0.8311571820651724))
+    history = []
+    for k in range(int(first_level), int(levels)):
+        if k != ens.cfg.working_curriculum_step or k != first_level:
+            ens.set_level(k)
+        ens.set_schedules(eps=exploration_rates(k), window=window, min_successes=min_successes_for(window, success_rate),
+                          max_episodes=ens.max_episodes if max_episodes is None else max_episodes)
+        flown = train_level(ens, max_periods=max_periods_per_level)
+        c = ens.counters()
+        history.append({"level": k, "periods": flown, "promotion_episode": c["promotion_episode"].copy(), "level_episodes": c["level_episodes"].copy()})
+        if on_level is not None:
+            on_level(ens, history[-1])
+        ratio = float(ratios[k]) if ratios is not None else float(Trainer.transfer_learning_ratio(me, k))
+        ens.transfer(k, ratio)
+    return history

@@ -477,6 +477,54 @@ int dql_pop_get_step_index(dql_ctx* ctx, int32_t agent, int64_t* j);
 int dql_pop_set_step_index(dql_ctx* ctx, int32_t agent, int64_t j);
 int dql_pop_index_faults(dql_ctx* ctx, int32_t agent, int64_t* n); /* targets dropped by the step kernel's bounds guard (0 unless a bug) */
 
+/* ---- ensembles of sequential learners: L independent Double-Q learners with ONE env each, stepped by one launch ----
+ * Learner l owns env l of a context made with dql_create(cfg, device, n_learners, seed, 0) and its own Q_table_a, Q_table_b and
+ * state_action_counter.  All learners share the period index j (period 0 is the reset period; a learner whose episode ended in period j
+ * resets in period j + 1).  In a non-reset period a learner explores iff its action word says so against ITS eps threshold (the eps table
+ * at min(e, n_eps - 1), e = episodes it has finished at the current level), else acts greedily on its CURRENT tables; right after the
+ * period it applies DoubleQLearningAgent.update (pkg/double_q_learning.py:91-146: learning rate from the alpha table at the pre-increment
+ * count, alpha_min of the config beyond it; quirks as in dql_agent_update) to its own cells.  No accumulators, no fold, no delay: the
+ * reference's loop (pkg/trainer.py:187-236), bit for bit in float32 and float64.
+ * A learner FREEZES (env, tables and counters untouched until re-armed) when the successes among its last `window` episodes at this level
+ * reach min_successes (promotion: the reference's window = 100, min_successes = 97) or when it has finished max_episodes at this level.
+ * Tables: double [n_learners][DQL_N_CELLS] each, whole or the slice [first, first + count) of the learners.
+ * Two-axis configs and the figure-eight trajectory are refused.  Every refused call returns DQL_EINVAL with a message and launches nothing. */
+#define DQL_ENSEMBLE_MAX_PERIODS 4096   /* agent periods per kernel launch; the run call loops launches for longer runs */
+#define DQL_ENSEMBLE_MAX_WINDOW 128
+#define DQL_ENSEMBLE_MAX_LEARNERS (1 << 20)
+#define DQL_ENSEMBLE_MAX_LOG (1 << 20)
+typedef struct dql_ensemble dql_ensemble;
+/* log_capacity > 0: keep terminal code and length of every learner's first log_capacity episodes (later ones are counted, not logged) */
+int dql_ensemble_create(const dql_config* cfg, int device, int64_t n_learners, uint64_t seed, int32_t log_capacity, dql_ensemble** out);
+int dql_ensemble_destroy(dql_ensemble* ens);
+int dql_ensemble_n_learners(dql_ensemble* ens, int64_t* n);
+/* alpha double[n_alpha], eps double[n_eps] (turned into thresholds as the step kernel's eps is); window in 1..DQL_ENSEMBLE_MAX_WINDOW */
+int dql_ensemble_set_schedules(dql_ensemble* ens, const double* alpha, int32_t n_alpha, const double* eps, int32_t n_eps, int32_t window,
+                               int32_t min_successes, int32_t max_episodes);
+/* new working level for all learners: every env re-enters through reset, then dql_ensemble_rearm */
+int dql_ensemble_set_level(dql_ensemble* ens, int32_t level);
+/* clears the per-level episode counts, windows, promotion records and frozen flags of all learners */
+int dql_ensemble_rearm(dql_ensemble* ens);
+/* `periods` agent periods for every learner that is not frozen; two runs of a and b periods equal one run of a + b, bit for bit */
+int dql_ensemble_run(dql_ensemble* ens, int64_t periods);
+int dql_ensemble_get_period_index(dql_ensemble* ens, int64_t* j);
+int dql_ensemble_n_live(dql_ensemble* ens, int64_t* n_live); /* learners not frozen */
+/* dql_agent_transfer's arithmetic on every learner's tables: Q[k] = Q[k-1] * ratio, k = 0 wraps (B6) */
+int dql_ensemble_transfer(dql_ensemble* ens, int32_t k, double ratio);
+int dql_ensemble_get_tables(dql_ensemble* ens, int64_t first, int64_t count, double* qa_or_null, double* qb_or_null, double* count_or_null);
+int dql_ensemble_set_tables(dql_ensemble* ens, int64_t first, int64_t count, const double* qa_or_null, const double* qb_or_null,
+                            const double* count_or_null);
+/* per learner: decisions, episodes, successes int64[n]; by_code int64[DQL_N_CHECK_CODES][n] (all since creation); promoted int32[n] = number of
+ * episodes at this level when the window filled, or -1; level_episodes int32[n]; frozen uint8[n] */
+int dql_ensemble_get_counters(dql_ensemble* ens, int64_t* decisions, int64_t* episodes, int64_t* successes, int64_t* by_code, int32_t* promoted,
+                              int32_t* level_episodes, uint8_t* frozen);
+/* code uint8[n][capacity], length uint16[n][capacity], n_episodes int32[n] (counts on beyond capacity); capacity = the creation's log_capacity */
+int dql_ensemble_get_episode_log(dql_ensemble* ens, uint8_t* code, uint16_t* length, int32_t capacity, int32_t* n_episodes);
+/* env state after the last period in the layout of dql_get_sim_state / dql_get_sim_ints (names: dql_field_name): reals double[64][n], ints int32[7][n];
+ * the x-axis fields are live, those of the y axis keep their initial values */
+int dql_ensemble_get_state(dql_ensemble* ens, double* reals, int32_t* ints);
+int dql_ensemble_index_faults(dql_ensemble* ens, int64_t* n); /* updates dropped by the kernel's bounds guard (0 unless a bug) */
+
 #ifdef __cplusplus
 }
 #endif

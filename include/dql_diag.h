@@ -35,6 +35,9 @@ int dql_diag_accum_dev_ptr(dql_ctx* ctx, void** dev_ptr, int64_t* n_int64);
  * bytes, TICK, XMODE}, the template arguments of k_rollout's name */
 int dql_diag_rollout_last(double* kernel_ms, int32_t* out3);
 
+/* wall duration on the device (HIP events around all launches) of the ensemble's latest completed dql_ensemble_run */
+int dql_diag_ensemble_last(dql_ensemble* ens, double* run_ms);
+
 /* ---- self-test ---- */
 /* The float32 tick's square root (csrc/dql_device.hpp sqrt_pos: v_rsq_f32 + one residual correction; until the end of round 5 with a Goldschmidt step in between): counts the inputs with bit
  * patterns lo_bits .. hi_bits whose result is NOT the correctly rounded sqrt.  The CPU oracle computes sqrtf(); parity is bit for bit only while

@@ -1,0 +1,149 @@
+"""Shared by the sequential-ensemble tests (CPU emulation and GPU): the reference loop and the `==` comparison.
+
+`Reference` is the ensemble's equality contract spelled out with the unchanged oracle: ONE `Oracle(cfg, L, seed)` stepped with external actions, the action
+word from `oracle.philox((j_lo, j_hi, l, STREAM_ACTION), (seed_lo, seed_hi))`, the greedy choice from `oracle.agent_predict` on per-learner numpy tables,
+the update from `oracle.agent_update(..., coin=, done=)` with alpha at the pre-increment count, and the freeze rules applied with a literal `deque`.  A frozen
+learner's env is put back to its bytes at the freeze point after every oracle step (the oracle steps all L envs), so it is untouched until re-armed."""
+import math
+from collections import deque
+
+import numpy as np
+
+from dql_multirotor_landing_amd.config import CHECK_NAMES, N_CELLS
+from oracle import oracle as orc
+from oracle.oracle import Oracle
+
+GOAL = CHECK_NAMES.index("TERMINAL_SUCCESS")
+N_CODES = len(CHECK_NAMES)
+STREAM_ACTION = 0
+EPS_TABLE = [1.0, 1.0, 0.5, 0.1, 0.0]  # per episode index within the level
+STATE_REAL_FIELDS = ("cum_x", "reward", "px", "py", "pz", "vx", "vy", "vz", "mp_x", "mp_u", "qw", "qx", "qy", "qz", "pitch_sp")
+STATE_INT_FIELDS = ("idx_x", "step_count", "code", "flags", "action")
+Q_REFERENCE, Q_BENCH, Q_PAPER = 0x7F, 0x60, 0x40  # the reference; the bench recipe (B1/B2 update, paper reward and mask); Double Q-learning with the coin
+
+
+def eps_thr(eps):
+    return 0 if not eps > 0.0 else min(int(math.ceil(eps * 16777216.0)), 16777216)
+
+
+class Reference:
+    def __init__(self, cfg, n, seed, eps=EPS_TABLE, window=100, min_successes=97, max_episodes=1 << 30, log_capacity=64, alpha_tab=None):
+        self.cfg, self.n, self.seed = cfg, int(n), int(seed)
+        self.o = Oracle(cfg, self.n, seed=self.seed)
+        self.qa, self.qb, self.cnt = (np.zeros((self.n, N_CELLS)) for _ in range(3))
+        self.alpha = cfg.alpha_table() if alpha_tab is None else np.asarray(alpha_tab, np.float64)
+        self.thr = [eps_thr(e) for e in eps]
+        self.W, self.min_successes, self.max_episodes, self.cap = int(window), int(min_successes), int(max_episodes), int(log_capacity)
+        self.j = 0
+        self.same_state = 0  # transitions with s' == s: the carried row of the next greedy choice must show the write
+        self.decisions, self.episodes, self.successes = (np.zeros(self.n, np.int64) for _ in range(3))
+        self.by_code = np.zeros((N_CODES, self.n), np.int64)
+        self.log_code = np.zeros((self.n, self.cap), np.uint8); self.log_len = np.zeros((self.n, self.cap), np.uint16); self.log_n = np.zeros(self.n, np.int32)
+        rn, inn = self.o.field_names(False), self.o.field_names(True)
+        self.ri = {f: rn.index(f) for f in STATE_REAL_FIELDS}
+        self.ii = {f: inn.index(f) for f in STATE_INT_FIELDS}
+        self.es = self.o.env_size
+        self.rearm()
+
+    def rearm(self):
+        self.level_episodes = np.zeros(self.n, np.int32)
+        self.windows = [deque([], maxlen=self.W) for _ in range(self.n)]
+        self.promoted = np.full(self.n, -1, np.int32)
+        self.frozen = np.zeros(self.n, bool)
+        self.snap = {}
+
+    def set_level(self, k):
+        for l, b in self.snap.items():  # the frozen envs as they were left, then every env re-enters through reset
+            self.o.envs[l * self.es:(l + 1) * self.es] = b
+        self.o.set_curriculum(k)
+        self.rearm()
+
+    def transfer(self, k, ratio):
+        for l in range(self.n):
+            orc.transfer(self.qa[l], self.qb[l], k, ratio)
+
+    def run(self, periods):
+        o, n = self.o, self.n
+        i_idx, i_fl, i_code, i_sc, i_rew = self.ii["idx_x"], self.ii["flags"], self.ii["code"], self.ii["step_count"], self.ri["reward"]
+        k0, k1 = self.seed & 0xffffffff, (self.seed >> 32) & 0xffffffff
+        act = np.zeros(n, np.uint8)
+        for _ in range(int(periods)):
+            j = self.j
+            _, ints = o.get_fields()
+            s = ints[i_idx].copy(); was_done = (ints[i_fl] & 1) != 0
+            words = {}
+            for l in range(n):
+                act[l] = 2
+                if self.frozen[l] or was_done[l]:
+                    continue
+                r = orc.philox((j & 0xffffffff, (j >> 32) & 0xffffffff, l, STREAM_ACTION), (k0, k1))
+                words[l] = r
+                e = int(self.level_episodes[l])
+                if (int(r[0]) >> 8) < self.thr[min(e, len(self.thr) - 1)]:
+                    act[l] = (int(r[1]) * 3) >> 32
+                else:
+                    act[l] = int(orc.agent_predict(self.qa[l], self.qb[l], [int(s[l])])[0])
+            o.step(act)
+            for l, b in self.snap.items():
+                o.envs[l * self.es:(l + 1) * self.es] = b
+            reals, ints = o.get_fields()
+            for l, r in words.items():
+                a, ns = int(act[l]), int(ints[i_idx][l])
+                sa = 3 * int(s[l]) + a
+                c = int(self.cnt[l][sa])
+                al = self.alpha[c] if c < len(self.alpha) else self.cfg.alpha_min
+                done = bool(ints[i_fl][l] & 1)
+                orc.agent_update(self.qa[l], self.qb[l], self.cnt[l], [sa], [ns], [al], self.cfg.gamma, [reals[i_rew][l]], quirks=self.cfg.quirks,
+                                 coin=[int(r[2]) >> 31], done=[int(done)])
+                self.decisions[l] += 1
+                self.same_state += int(ns == int(s[l]))
+                if done:
+                    code = int(ints[i_code][l])
+                    self.episodes[l] += 1; self.successes[l] += code == GOAL; self.by_code[code][l] += 1
+                    if self.log_n[l] < self.cap:
+                        self.log_code[l][self.log_n[l]] = code; self.log_len[l][self.log_n[l]] = int(ints[i_sc][l])
+                    self.log_n[l] += 1
+                    self.windows[l].append(int(code == GOAL)); self.level_episodes[l] += 1
+                    if sum(self.windows[l]) >= self.min_successes:
+                        self.promoted[l] = self.level_episodes[l]; self.frozen[l] = True
+                    elif self.level_episodes[l] >= self.max_episodes:
+                        self.frozen[l] = True
+                    if self.frozen[l]:
+                        self.snap[l] = o.envs[l * self.es:(l + 1) * self.es].copy()
+            self.j += 1
+
+    def result(self):
+        reals, ints = self.o.get_fields()
+        out = {"qa": self.qa, "qb": self.qb, "count": self.cnt, "decisions": self.decisions, "episodes": self.episodes, "successes": self.successes,
+               "by_code": self.by_code, "promotion_episode": self.promoted, "level_episodes": self.level_episodes, "frozen": self.frozen,
+               "log_code": self.log_code, "log_len": self.log_len, "log_n": self.log_n}
+        out.update({f: reals[k] for f, k in self.ri.items()})
+        out.update({f: ints[k] for f, k in self.ii.items()})
+        return {k: np.array(v, copy=True) for k, v in out.items()}
+
+
+def ensemble_result(ens):
+    """the same dictionary from a SequentialEnsemble"""
+    qa, qb, cnt = ens.get_tables()
+    out = {"qa": qa, "qb": qb, "count": cnt}
+    out.update(ens.counters())
+    code, length, n = ens.episode_log()
+    out.update({"log_code": code, "log_len": length, "log_n": n})
+    out.update(ens.state())
+    return out
+
+
+def assert_equal(got, want, what, learners=None):
+    """`==` on every table, counter, log entry, promotion episode and state field (floats by their bits); `learners`: (rows of got, rows of want) to compare"""
+    assert set(want) <= set(got), sorted(set(want) - set(got))
+    for k, w in want.items():
+        g = np.asarray(got[k]); w = np.asarray(w)
+        if learners is not None:
+            ax = 1 if k == "by_code" else 0
+            g, w = np.take(g, learners[0], axis=ax), np.take(w, learners[1], axis=ax)
+        assert g.shape == w.shape, f"{what}: {k} has shape {g.shape}, want {w.shape}"
+        if w.dtype.kind == "f":
+            bad = np.ascontiguousarray(g, np.float64).view(np.uint64) != np.ascontiguousarray(w, np.float64).view(np.uint64)
+        else:
+            bad = g.astype(np.int64) != w.astype(np.int64)
+        assert not bad.any(), f"{what}: {k} differs in {np.count_nonzero(bad)} of {w.size} entries, first at {tuple(int(v[0]) for v in np.nonzero(bad))}: {g[bad][0]!r} vs {w[bad][0]!r}"

@@ -19,6 +19,7 @@ def normalise(text):
     text = re.sub(r"\.LBB\d+_", ".LBB_", text)
     text = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", text)
     text = re.sub(r"\.Ltmp\d+", ".Ltmp", text)
+    text = re.sub(r"(Header|header|Loop|Child Loop)( *=? *)BB\d+_", r"\1\2BB_", text)  # the same function number inside the assembler's loop comments
     return text
 
 
