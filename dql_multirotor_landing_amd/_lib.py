@@ -114,6 +114,8 @@ SYMBOLS = {
     "dql_rollout_field_name": (C.c_char_p, [_i32, _i32]),
     "dql_rollout": (C.c_int, [_cfgp, C.c_int, _i32, _i64, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "dql_diag_rollout_last": (C.c_int, [C.POINTER(_dbl), _vp]),
+    "dql_score": (C.c_int, [_cfgp, C.c_int, _i64, _i64, _i32, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dql_diag_score_last": (C.c_int, [C.POINTER(_dbl), _vp]),
     "dql_diag_selftest_sqrt": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_i64)]),
     "dql_place": (C.c_int, [_cfgp, C.c_int, _vp, _vp, _i64, _vp]),
     "dql_agent_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
@@ -160,6 +162,7 @@ SYMBOLS = {
     "dql_ensemble_get_episode_log": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
     "dql_ensemble_get_state": (C.c_int, [_vp, _vp, _vp]),
     "dql_ensemble_index_faults": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "dql_ensemble_score": (C.c_int, [_vp, _cfgp, _i64, _i64, _i64, _i32, _u64, _i32, _vp, _vp, _vp, _vp]),
     "dql_diag_ensemble_last": (C.c_int, [_vp, C.POINTER(_dbl)]),
 }
 MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS

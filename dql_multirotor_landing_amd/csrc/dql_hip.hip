@@ -31,6 +31,7 @@
 #include "dql_host_consts.hpp"
 #include "dql_rollout.hpp"
 #include "dql_learner.hpp"
+#include "dql_score.hpp"
 #include "../../include/dql_diag.h"
 
 using namespace dql;
@@ -1067,6 +1068,56 @@ __global__ void k_ens_transfer(double* qa, double* qb, long long n, int k, int s
   double* a = qa + l * DQL_N_CELLS; double* b = qb + l * DQL_N_CELLS;
   a[k * DQL_CELLS_PER_LEVEL + i] = a[src * DQL_CELLS_PER_LEVEL + i] * ratio;
   b[k * DQL_CELLS_PER_LEVEL + i] = b[src * DQL_CELLS_PER_LEVEL + i] * ratio;
+}
+
+// ---- greedy scoring (dql_score / dql_ensemble_score) ----
+// k_rollout's shape — one env per lane, workgroups of one wave, table set k serves blocks [k B, (k + 1) B), env i of every set has RNG key (i, seed) — but a
+// lane flies episode after episode (csrc/dql_score.hpp: score_episodes) and what leaves the wave is its tally: one atomicAdd per non-zero column into the
+// table set's row of a buffer zeroed before the launch.  Integer sums: the result does not depend on the order the waves arrive in.
+template <typename T> struct ScoreArgs {
+  SimK<T> c;
+  const MdpK<T> DQL_CONST_AS* mdp;
+  MdpRun<T> mdp_run;
+  RolloutInit<T> init;
+  const double* qa; const double* qb;                                  // [n_tables][DQL_N_CELLS]
+  const long long DQL_CONST_AS* mgr0; const int DQL_CONST_AS* sched;   // [max_steps + 1] (fill_schedule)
+  unsigned long long* by_code;                                         // [n_tables][SCORE_N_COLS]
+  unsigned long long* steps_sum;                                       // [n_tables]
+  ScoreLog log;
+  unsigned long long seed;
+  int blocks_per_table, max_steps, episodes;
+};
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_score(ScoreArgs<T> a) {
+  const int tid = threadIdx.x;
+  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
+  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
+  const long long g = (long long)blockIdx.x * 64 + tid;                // log column: every lane of the grid is an env (envs_per_table is a multiple of 64)
+  SimK<T> cl = a.c;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
+  const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
+  const ScoreTally t = score_episodes<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.episodes, a.mgr0, a.sched, kv, a.log, g);
+  if (tid == 0) {
+    unsigned long long* row = a.by_code + (size_t)k * SCORE_N_COLS;
+#pragma unroll
+    for (int col = 0; col < SCORE_N_COLS; ++col) if (t.by_code[col]) atomicAdd(&row[col], (unsigned long long)t.by_code[col]);
+    if (t.steps) atomicAdd(&a.steps_sum[k], t.steps);
+  }
 }
 
 struct dql_ctx {
@@ -2511,6 +2562,109 @@ int dql_diag_rollout_last(double* kernel_ms, int32_t* out3) {
   return DQL_OK;
 }
 
+// ---- greedy scoring ----
+static thread_local double g_score_ms = -1.0;
+static thread_local int g_score_inst[3] = {0, 0, 0};
+extern "C++" {
+template <typename T, int XMODE> static void launch_score(const dql_config& cfg, const void* mdpk, const double* qa, const double* qb, const long long* mgr0, const int* sched,
+                                                         unsigned long long* by_code, unsigned long long* steps_sum, const ScoreLog& log, unsigned long long seed,
+                                                         long long n_tables, long long envs_per_table, int episodes, int max_steps) {
+  ScoreArgs<T> a;
+  a.c = make_simk<T>(cfg);
+  a.mdp = (const MdpK<T> DQL_CONST_AS*)mdpk;
+  a.mdp_run = MdpRun<T>{cfg.gamma, (T)(cfg.t_max * cfg.f_ag), cfg.goal_logic};
+  a.init = make_rollout_init<T>(cfg);
+  a.qa = qa; a.qb = qb;
+  a.mgr0 = (const long long DQL_CONST_AS*)mgr0; a.sched = (const int DQL_CONST_AS*)sched;
+  a.by_code = by_code; a.steps_sum = steps_sum; a.log = log;
+  a.seed = seed; a.blocks_per_table = (int)(envs_per_table / 64); a.max_steps = max_steps; a.episodes = episodes;
+  g_score_inst[0] = (int)sizeof(T); g_score_inst[1] = TICK_PLAIN; g_score_inst[2] = XMODE;
+  hipLaunchKernelGGL((k_score<T, TICK_PLAIN, XMODE>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
+}
+}  // extern "C++"
+// every argument both entry points share, checked before the device is touched: a refused call starts no kernel
+static int score_check(const char* who, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, int32_t max_steps, const int64_t* by_code, const int64_t* steps_sum,
+                       const uint8_t* ep_code, const uint16_t* ep_steps) {
+  const std::string w(who);
+  if (n_tables < 1 || n_tables > DQL_SCORE_MAX_TABLES) return fail(DQL_EINVAL, w + ": the number of table sets must be in 1..2^20 (DQL_SCORE_MAX_TABLES); nothing was launched");
+  if (envs_per_table < 64 || envs_per_table % 64 != 0) return fail(DQL_EINVAL, w + ": the envs per table set must be a positive multiple of 64 (one wave per workgroup, whole waves per table set); nothing was launched");
+  if (envs_per_table > (1ll << 30) || n_tables * envs_per_table > (1ll << 30)) return fail(DQL_EINVAL, w + ": table sets x envs must be at most 2^30; nothing was launched");
+  if (episodes_per_env < 1 || episodes_per_env > DQL_SCORE_MAX_EPISODES) return fail(DQL_EINVAL, w + ": episodes_per_env must be in 1..64 (DQL_SCORE_MAX_EPISODES); nothing was launched");
+  if (max_steps < 1 || max_steps > DQL_SCORE_MAX_STEPS) return fail(DQL_EINVAL, w + ": max_steps must be in 1..4096 (DQL_SCORE_MAX_STEPS); nothing was launched");
+  if ((ep_code == nullptr) != (ep_steps == nullptr)) return fail(DQL_EINVAL, w + ": the episode log needs both arrays or neither; nothing was launched");
+  if (!by_code || !steps_sum) return fail(DQL_EINVAL, w + ": null array; nothing was launched");
+  return DQL_OK;
+}
+// d_qa / d_qb: [n_tables][DQL_N_CELLS] on the current device
+static int score_run(const dql_config* cfg, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, const double* d_qa, const double* d_qb,
+                     int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code, uint16_t* ep_steps) {
+  const long long n_total = n_tables * envs_per_table;
+  const int n_per = max_steps + 1;
+  std::vector<long long> h_mgr0((size_t)n_per);
+  std::vector<int> h_sched((size_t)n_per);
+  fill_schedule(*cfg, 0, h_mgr0.data(), h_sched.data(), n_per);
+  DevBuf d_mgr0, d_sched, d_mdp, d_sums, d_code, d_steps;
+  UP(d_mgr0, h_mgr0.data(), (size_t)n_per * sizeof(long long)); UP(d_sched, h_sched.data(), (size_t)n_per * sizeof(int));
+  if (cfg->dtype == DQL_F32) { const MdpK<float> m = make_mdpk<float>(*cfg); UP(d_mdp, &m, sizeof(m)); }
+  else { const MdpK<double> m = make_mdpk<double>(*cfg); UP(d_mdp, &m, sizeof(m)); }
+  // one buffer for both sums: [n_tables][SCORE_N_COLS] counts, then [n_tables] step totals
+  const size_t sums_bytes = (size_t)n_tables * (SCORE_N_COLS + 1) * sizeof(unsigned long long);
+  if (d_sums.alloc(sums_bytes)) return fail(DQL_ENOMEM, "hipMalloc failed");
+  HIP_TRY(hipMemset(d_sums.p, 0, sums_bytes));
+  const size_t log_n = (size_t)episodes * (size_t)n_total;
+  if (ep_code) {
+    if (d_code.alloc(log_n) || d_steps.alloc(log_n * sizeof(uint16_t))) return fail(DQL_ENOMEM, "hipMalloc failed");
+    HIP_TRY(hipMemset(d_code.p, 0xff, log_n));  // not finished
+    HIP_TRY(hipMemset(d_steps.p, 0, log_n * sizeof(uint16_t)));
+  }
+  unsigned long long* d_by_code = (unsigned long long*)d_sums.p;
+  unsigned long long* d_steps_sum = d_by_code + (size_t)n_tables * SCORE_N_COLS;
+  const ScoreLog log{(uint8_t*)d_code.p, (uint16_t*)d_steps.p, n_total};
+  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
+  HIP_TRY(hipEventCreate(&e0.e)); HIP_TRY(hipEventCreate(&e1.e));
+  HIP_TRY(hipEventRecord(e0.e, 0));
+  const bool two = cfg->two_axis != 0;
+  const long long* mg = (const long long*)d_mgr0.p; const int* sc = (const int*)d_sched.p;
+  if (cfg->dtype == DQL_F32) {
+    if (two) launch_score<float, X_TWO>(*cfg, d_mdp.p, d_qa, d_qb, mg, sc, d_by_code, d_steps_sum, log, seed, n_tables, envs_per_table, episodes, max_steps);
+    else launch_score<float, X_ONLY>(*cfg, d_mdp.p, d_qa, d_qb, mg, sc, d_by_code, d_steps_sum, log, seed, n_tables, envs_per_table, episodes, max_steps);
+  } else {
+    if (two) launch_score<double, X_TWO>(*cfg, d_mdp.p, d_qa, d_qb, mg, sc, d_by_code, d_steps_sum, log, seed, n_tables, envs_per_table, episodes, max_steps);
+    else launch_score<double, X_ONLY>(*cfg, d_mdp.p, d_qa, d_qb, mg, sc, d_by_code, d_steps_sum, log, seed, n_tables, envs_per_table, episodes, max_steps);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e1.e, 0));
+  HIP_TRY(hipMemcpy(by_code, d_by_code, (size_t)n_tables * SCORE_N_COLS * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(steps_sum, d_steps_sum, (size_t)n_tables * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (ep_code) {
+    HIP_TRY(hipMemcpy(ep_code, d_code.p, log_n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ep_steps, d_steps.p, log_n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  }
+  HIP_TRY(hipEventSynchronize(e1.e));
+  float ms = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
+  g_score_ms = (double)ms;
+  return DQL_OK;
+}
+int dql_score(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
+              const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null) {
+  int rc = check_config(cfg); if (rc) return rc;
+  rc = score_check("dql_score", n_tables, envs_per_table, episodes_per_env, max_steps, by_code, steps_sum, ep_code_or_null, ep_steps_or_null); if (rc) return rc;
+  if (!qa || !qb) return fail(DQL_EINVAL, "dql_score: null array; nothing was launched");
+  OP_PROLOGUE(device)
+  DevBuf d_qa, d_qb;
+  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
+  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
+  return score_run(cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, (const double*)d_qa.p, (const double*)d_qb.p, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
+}
+int dql_diag_score_last(double* kernel_ms, int32_t* inst3) {
+  if (!kernel_ms || !inst3) return fail(DQL_EINVAL, "null pointer");
+  if (g_score_ms < 0.0) return fail(DQL_ESTATE, "no dql_score or dql_ensemble_score call has completed on this thread");
+  *kernel_ms = g_score_ms;
+  for (int k = 0; k < 3; ++k) inst3[k] = g_score_inst[k];
+  return DQL_OK;
+}
+
 // ---- ensembles of sequential learners ----
 struct dql_ensemble {
   dql_config cfg;
@@ -2813,6 +2967,17 @@ int dql_ensemble_index_faults(dql_ensemble* x, int64_t* n) {
   HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
   *n = (int64_t)v;
   return DQL_OK;
+}
+// the learners' tables are read where they live (the ensemble's device arrays are [L][DQL_N_CELLS] double already): k_score only reads them and touches nothing else of the ensemble
+int dql_ensemble_score(dql_ensemble* x, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env, uint64_t seed,
+                       int32_t max_steps, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null) {
+  CHECK_ENS(x);
+  int rc = check_config(eval_cfg); if (rc) return rc;
+  rc = score_check("dql_ensemble_score", count, envs_per_learner, episodes_per_env, max_steps, by_code, steps_sum, ep_code_or_null, ep_steps_or_null); if (rc) return rc;
+  if (first < 0 || first > x->n || count > x->n - first) return fail(DQL_EINVAL, "dql_ensemble_score: the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t off = (size_t)first * DQL_N_CELLS;
+  return score_run(eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, x->mem.qa + off, x->mem.qb + off, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
 }
 int dql_diag_ensemble_last(dql_ensemble* x, double* run_ms) {
   CHECK_ENS(x);

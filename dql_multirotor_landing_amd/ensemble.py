@@ -172,6 +172,28 @@ class SequentialEnsemble:
         first, n = self._slice(first, given[0].shape[0])
         _lib.check(self.lib.dql_ensemble_set_tables(self._h, first, n, *(_p(a) for a in arrs)))
 
+    # ---- greedy scoring of the resident tables (include/dql.h dql_ensemble_score) ----
+    def score(self, eval_cfg: DqlConfig, envs_per_learner: int = 64, seed: int = 123, episodes: int = 1, max_steps: int = 600, log: bool = False, first: int = 0,
+              count: Optional[int] = None, timing: dict = None):
+        """`ops.score` of learners first .. first + count - 1 on their tables where they live (no host copy), under `eval_cfg` — any valid config, not
+        necessarily the ensemble's own.  The ensemble is left as it was.  Returns what `ops.score` returns, table set k = learner first + k."""
+        from . import ops
+        first, count = self._slice(first, count)
+        n, episodes, max_steps = int(envs_per_learner), int(episodes), int(max_steps)
+        ops.score_check_args(count, n, episodes, max_steps)
+        by_code, steps_sum, ep_code, ep_steps = ops.score_buffers(count, n, episodes, log)
+        c = eval_cfg.to_c()
+        _lib.check(self.lib.dql_ensemble_score(self._h, C.byref(c), first, count, n, episodes, int(seed), max_steps, _p(by_code), _p(steps_sum), _p(ep_code), _p(ep_steps)))
+        return ops.score_result(self.lib, by_code, steps_sum, ep_code, ep_steps, timing)
+
+    def landing_rates(self, n_envs: int = 4096, episodes: int = 1, level: int = 4, seed: int = 123, dtype=None, quirks=None, max_steps: int = 600, first: int = 0,
+                      count: Optional[int] = None, timing: dict = None):
+        """`evaluation.landing_rates` of the resident tables: `touchdown_rate` and `goal_hold_rate` per learner, two launches"""
+        from . import evaluation
+        quirks = evaluation.Q_PAPER if quirks is None else quirks
+        return evaluation.landing_rates_with(lambda cfg, n, sd, ep, ms, t: self.score(cfg, n, sd, ep, ms, first=first, count=count, timing=t),
+                                             n_envs, episodes, level, seed, dtype, quirks, max_steps, timing)
+
     # ---- outputs ----
     def counters(self):
         n = self.n

@@ -96,6 +96,36 @@ def landing_scores(list_of_tables, n_envs: int = 4096, level: int = 4, seed: int
             for k in range(len(list_of_tables))]
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# the scoring operator (ops.score, include/dql.h dql_score): any number of table sets, several episodes per env, counts only
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+LANDING_BAR = 0.875  # attempts.py's acceptance bar on the touchdown rate
+# episodes per env of the scripts: lane re-use against fresh lanes is measured in profiles/score_timing.jsonl
+DEFAULT_SCORE_EPISODES = 1
+
+
+def landing_rates_with(score_fn, n_envs: int = 4096, episodes: int = 1, level: int = 4, seed: int = 123, dtype=None, quirks: int = Q_PAPER, max_steps: int = 600,
+                       timing: dict = None):
+    """the two launches of `landing_rates`, one per flavour, through `score_fn(cfg, n_envs, seed, episodes, max_steps, timing)` -> a score result"""
+    ts, tt = {}, {}
+    sim = score_fn(_flavour_config("simulation", level, dtype, {"quirks": quirks}), n_envs, seed, episodes, max_steps, ts)
+    trn = score_fn(_flavour_config("training", level, dtype, {"quirks": quirks}), n_envs, seed, episodes, max_steps, tt)
+    if timing is not None:
+        timing["kernel_ms"] = ts["kernel_ms"] + tt["kernel_ms"]
+        timing["instance"] = [ts["instance"], tt["instance"]]
+    return {"touchdown_rate": ops.rates_from_counts(sim["by_code"], "TERMINAL_CONTACT"), "goal_hold_rate": ops.rates_from_counts(trn["by_code"], "TERMINAL_SUCCESS"),
+            "simulation_by_code": sim["by_code"], "training_by_code": trn["by_code"], "columns": sim["columns"]}
+
+
+def landing_rates(qa, qb, n_envs: int = 4096, episodes: int = 1, level: int = 4, seed: int = 123, dtype=None, device=0, quirks: int = Q_PAPER, max_steps: int = 600,
+                  timing: dict = None):
+    """`landing_scores`' two figures for K table sets (`qa`, `qb`: [K, 2835]), K up to 2^20, in two launches, one per flavour: a dict with `touchdown_rate` [K]
+    and `goal_hold_rate` [K] — the share of the n_envs * episodes episodes per set that ended in TERMINAL_CONTACT in the simulation flavour and in
+    TERMINAL_SUCCESS in the training flavour — and the two count tables.  With episodes = 1 these are `landing_scores`' numbers."""
+    return landing_rates_with(lambda cfg, n, sd, ep, ms, t: ops.score(cfg, qa, qb, n, sd, episodes=ep, max_steps=ms, device=device, timing=t),
+                              n_envs, episodes, level, seed, dtype, quirks, max_steps, timing)
+
+
 QUANTILES = (0.05, 0.5, 0.95)
 
 

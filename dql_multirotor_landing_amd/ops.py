@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .config import DqlConfig, Q_REFERENCE
+from .config import CHECK_NAMES, DqlConfig, Q_REFERENCE
 
 
 def _p(a):
@@ -236,3 +236,70 @@ def rollout(cfg: DqlConfig, tables, envs_per_table: int, seed: int, max_steps: i
     out = {"code": code, "steps": steps, "trace": trace, "trace_fields": ROLLOUT_TRACE_FIELDS}
     out.update({f: rec[k] for k, f in enumerate(ROLLOUT_RECORD_FIELDS)})
     return out
+
+
+SCORE_MAX_TABLES, SCORE_MAX_EPISODES, SCORE_MAX_STEPS = 1 << 20, 64, 4096  # include/dql.h DQL_SCORE_MAX_*
+SCORE_MAX_LANES = 1 << 30
+SCORE_COLUMNS = tuple(CHECK_NAMES) + ("unfinished",)  # the columns of `by_code`
+
+
+def score_check_args(n_tables: int, envs_per_table: int, episodes: int, max_steps: int):
+    """the argument checks of dql_score / dql_ensemble_score, made before the library is touched"""
+    if not 1 <= n_tables <= SCORE_MAX_TABLES:
+        raise ValueError(f"between 1 and {SCORE_MAX_TABLES} table sets per call, not {n_tables}")
+    if envs_per_table < 64 or envs_per_table % 64:
+        raise ValueError(f"envs_per_table must be a positive multiple of 64, not {envs_per_table}")
+    if n_tables * envs_per_table > SCORE_MAX_LANES:
+        raise ValueError(f"table sets x envs must be at most 2^30, not {n_tables * envs_per_table}")
+    if not 1 <= episodes <= SCORE_MAX_EPISODES:
+        raise ValueError(f"episodes must be in 1..{SCORE_MAX_EPISODES}, not {episodes}")
+    if not 1 <= max_steps <= SCORE_MAX_STEPS:
+        raise ValueError(f"max_steps must be in 1..{SCORE_MAX_STEPS}, not {max_steps}")
+
+
+def score_buffers(n_tables: int, envs_per_table: int, episodes: int, log: bool):
+    """(by_code, steps_sum, ep_code or None, ep_steps or None) as the C calls fill them"""
+    by_code = np.zeros((n_tables, len(SCORE_COLUMNS)), np.int64); steps_sum = np.zeros(n_tables, np.int64)
+    ep_code = np.zeros((episodes, n_tables * envs_per_table), np.uint8) if log else None
+    ep_steps = np.zeros((episodes, n_tables * envs_per_table), np.uint16) if log else None
+    return by_code, steps_sum, ep_code, ep_steps
+
+
+def score_result(lib, by_code, steps_sum, ep_code, ep_steps, timing):
+    if timing is not None:
+        ms, inst = C.c_double(), (C.c_int32 * 3)()
+        _lib.check(lib.dql_diag_score_last(C.byref(ms), inst))
+        timing["kernel_ms"] = ms.value
+        timing["instance"] = f"k_score<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    return {"by_code": by_code, "steps_sum": steps_sum, "ep_code": ep_code, "ep_steps": ep_steps, "columns": SCORE_COLUMNS}
+
+
+def rates_from_counts(by_code, column: str):
+    """share of all episodes asked for (finished or not) that ended with the check code `column`, per table set: by_code[:, column] / by_code.sum(axis=1)"""
+    by_code = np.atleast_2d(np.asarray(by_code, dtype=np.int64))
+    if by_code.shape[1] != len(SCORE_COLUMNS):
+        raise ValueError(f"by_code must have {len(SCORE_COLUMNS)} columns")
+    total = by_code.sum(axis=1)
+    if (total <= 0).any():
+        raise ValueError("a row of by_code counts no episode")
+    return by_code[:, SCORE_COLUMNS.index(column)] / total
+
+
+def score(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, episodes: int = 1, max_steps: int = 600, log: bool = False, device: int = 0, timing: dict = None):
+    """How the greedy episodes of K table sets end, counted on the device in one launch (include/dql.h dql_score).
+
+    `qa`, `qb`: float64 [K, 2835] (one set: [2835]).  Every set flies `envs_per_table` envs (env i has the RNG key and start of env i of
+    `Engine(cfg, envs_per_table, seed)`), each until it has finished `episodes` episodes or `max_steps` periods are over.  Returns a dict: `by_code` int64
+    [K, len(SCORE_COLUMNS)] (finished episodes by terminal code, last column the episodes not finished), `steps_sum` int64 [K], `columns`, and with `log`
+    `ep_code` uint8 / `ep_steps` uint16 [episodes, K * envs_per_table] (0xff / 0: not finished), else None.  `timing`: receives `kernel_ms` and `instance`."""
+    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
+    if qa.ndim != 2 or qa.shape[1] != 2835 or qb.shape != qa.shape:
+        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    K, n, episodes, max_steps = len(qa), int(envs_per_table), int(episodes), int(max_steps)
+    score_check_args(K, n, episodes, max_steps)
+    lib = _lib.load()
+    by_code, steps_sum, ep_code, ep_steps = score_buffers(K, n, episodes, log)
+    c = cfg.to_c()
+    _lib.check(lib.dql_score(C.byref(c), device, K, n, episodes, int(seed), max_steps, _p(qa), _p(qb), _p(by_code), _p(steps_sum),
+                             None if ep_code is None else _p(ep_code), None if ep_steps is None else _p(ep_steps)))
+    return score_result(lib, by_code, steps_sum, ep_code, ep_steps, timing)

@@ -398,6 +398,27 @@ int dql_rollout_n_fields(int32_t* n_record, int32_t* n_trace);
 const char* dql_rollout_field_name(int32_t i, int32_t is_trace);
 int dql_rollout(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, uint64_t seed, int32_t max_steps, const double* qa,
                 const double* qb, int32_t* code, int32_t* steps, double* rec, int32_t trace_envs, double* trace_or_null);
+/* ---- greedy scoring: how the episodes of up to 2^20 table sets end, counted on the device in one launch ----
+ * Table set k (qa / qb [n_tables][DQL_N_CELLS]) flies envs_per_table envs as in dql_rollout (env i of every set has the RNG key (i, seed)), but an env does
+ * not stop at its first episode: it flies on, through reset, until it has finished episodes_per_env episodes or max_steps periods are over.
+ * The equality contract: take a context from dql_create(cfg, device, envs_per_table, seed, 0) with the tables of set k and drive it with
+ * dql_eval_steps(ctx, 1) once for the reset period and then max_steps more times.  The m-th time (m = 0, 1, ... < episodes_per_env) env i shows FL_DONE after
+ * a period, its code and its step_count are ep_code[m][k * envs_per_table + i] and ep_steps[m][k * envs_per_table + i] — whichever block or tick layout
+ * that context picked —, and by_code[k] / steps_sum[k] are the sums of exactly those entries:
+ *   by_code    int64 [n_tables][DQL_N_CHECK_CODES + 1]: finished episodes by terminal code; the last column, "unfinished", is envs_per_table *
+ *              episodes_per_env minus the finished episodes
+ *   steps_sum  int64 [n_tables]: the total length (step_count) of the finished episodes
+ *   ep_code    uint8 [episodes_per_env][n_tables * envs_per_table], 0xff = not finished;  ep_steps uint16, same shape, 0 = not finished (both or neither)
+ * The counts are integer sums: bit-reproducible.  With episodes_per_env = 1, code and steps are those of dql_rollout.  Episodes beyond the first are NOT
+ * paired across table sets: when episode m starts depends on when episode m - 1 ended, and the Philox counter is the period index.
+ * dql_ensemble_score (below, with the ensembles) scores the tables of an ensemble's learners where they live.
+ * DQL_EINVAL (and no launch) unless 1 <= n_tables <= DQL_SCORE_MAX_TABLES, envs_per_table is a positive multiple of 64, n_tables * envs_per_table <= 2^30,
+ * 1 <= episodes_per_env <= DQL_SCORE_MAX_EPISODES, 1 <= max_steps <= DQL_SCORE_MAX_STEPS, both log pointers are given or neither, and no other pointer is null. */
+#define DQL_SCORE_MAX_TABLES (1 << 20)
+#define DQL_SCORE_MAX_EPISODES 64
+#define DQL_SCORE_MAX_STEPS 4096
+int dql_score(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
+              const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null);
 /* ---- a DoubleQLearningAgent's tables RESIDENT on the device (pkg/double_q_learning.py:32-146) ----
  * The stateless dql_agent_predict / dql_agent_update below ship all three tables (3 x 22 680 B) both ways per call — fine for a batch,
  * 6x slower than the reference's own Python for a caller that steps ONE env (BASELINE configs[0]).  A dql_agent keeps them in device
@@ -524,6 +545,12 @@ int dql_ensemble_get_episode_log(dql_ensemble* ens, uint8_t* code, uint16_t* len
  * the x-axis fields are live, those of the y axis keep their initial values */
 int dql_ensemble_get_state(dql_ensemble* ens, double* reals, int32_t* ints);
 int dql_ensemble_index_faults(dql_ensemble* ens, int64_t* n); /* updates dropped by the kernel's bounds guard (0 unless a bug) */
+/* dql_score on the tables of learners [first, first + count), read in the ensemble's device memory (no host copy): table set k is learner first + k, outputs
+ * and refusals as for dql_score (count in place of n_tables; the slice must lie inside the ensemble).  eval_cfg is any valid config and need not be the
+ * ensemble's own (another level, the simulation flavour, two axes, the other dtype).  The ensemble is left exactly as it was: env state, tables, counters,
+ * windows and period index. */
+int dql_ensemble_score(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
+                       uint64_t seed, int32_t max_steps, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null);
 
 #ifdef __cplusplus
 }

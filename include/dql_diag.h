@@ -35,6 +35,10 @@ int dql_diag_accum_dev_ptr(dql_ctx* ctx, void** dev_ptr, int64_t* n_int64);
  * bytes, TICK, XMODE}, the template arguments of k_rollout's name */
 int dql_diag_rollout_last(double* kernel_ms, int32_t* out3);
 
+/* the same for the calling thread's latest completed dql_score or dql_ensemble_score: inst3 = {sizeof(real) in bytes, TICK, XMODE}, the template arguments
+ * of k_score's name */
+int dql_diag_score_last(double* kernel_ms, int32_t* inst3);
+
 /* wall duration on the device (HIP events around all launches) of the ensemble's latest completed dql_ensemble_run */
 int dql_diag_ensemble_last(dql_ensemble* ens, double* run_ms);
 

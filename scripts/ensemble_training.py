@@ -2,9 +2,12 @@
 """The reference's curriculum training (`Trainer.curriculum_training`: one env, one agent, update after every step) for many independent seeds at once,
 one learner per GPU lane (dql_multirotor_landing_amd/ensemble.py).
 
-    python scripts/ensemble_training.py --learners 4096 --seed 42 [--launched] [--levels 5] [--episodes 50000] --out run.npz
+    python scripts/ensemble_training.py --learners 4096 --seed 42 [--launched] [--levels 5] [--episodes 50000] [--score ENVS] --out run.npz
 
 --launched: the parameters the reference's manager node ran with under roslaunch (config.as_launched_config) instead of the launch file's.
+--score ENVS: after the curriculum, fly every learner's tables greedily where they live (SequentialEnsemble.landing_rates: ENVS envs per learner and flavour,
+two launches), store `touchdown_rate` and `goal_hold_rate` in the .npz and print the share of learners at or above the acceptance bar of attempts.py (0.875
+touchdowns), with the figures of the reference's published tables from the same call of `evaluation.landing_rates` (same envs, seed and episodes) beside it.
 Writes every learner's tables and, per level, its first-promotion episode (-1: the episode budget ran out first)."""
 import argparse
 import json
@@ -16,7 +19,34 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from dql_multirotor_landing_amd.config import F32, F64, Q_REFERENCE, as_launched_config, training_config  # noqa: E402
+from dql_multirotor_landing_amd import evaluation  # noqa: E402
 from dql_multirotor_landing_amd.ensemble import SequentialEnsemble, curriculum  # noqa: E402
+
+
+def rate_summary(x):
+    x = np.asarray(x, dtype=np.float64)
+    q = np.quantile(x, (0.0, 0.05, 0.25, 0.5, 0.75, 0.95, 1.0))
+    return {"mean": float(x.mean()), **{k: float(v) for k, v in zip(("min", "q05", "q25", "q50", "q75", "q95", "max"), q)}}
+
+
+def score_report(ens, a):
+    """both landing rates of every learner (resident tables, two launches) and of the reference's tables, as one JSON-able dict + the two arrays"""
+    level = a.levels - 1
+    kw = dict(n_envs=a.score, episodes=a.score_episodes, level=level, seed=a.score_seed)
+    t = {}
+    r = ens.landing_rates(timing=t, **kw)
+    td, gh = r["touchdown_rate"], r["goal_hold_rate"]
+    rep = {"what": "ensemble_landing_rates", "learners": int(td.size), "envs_per_learner": a.score, "episodes_per_env": a.score_episodes, "level": level,
+           "levels_trained": a.levels, "episode_budget_per_level": a.episodes, "launched": bool(a.launched), "seed": a.score_seed, "bar": evaluation.LANDING_BAR, "learners_at_or_above_bar": int((td >= evaluation.LANDING_BAR).sum()),
+           "share_at_or_above_bar": float((td >= evaluation.LANDING_BAR).mean()), "touchdown_rate": rate_summary(td), "goal_hold_rate": rate_summary(gh),
+           "unfinished_episodes": {"simulation": int(r["simulation_by_code"][:, -1].sum()), "training": int(r["training_by_code"][:, -1].sum())},
+           "kernel_ms": t["kernel_ms"], "instance": t["instance"], "reference_tables": None}
+    ref = Path(a.reference_tables)
+    if (ref / "Q_table_a.npy").exists() and (ref / "Q_table_b.npy").exists():
+        qa, qb = (np.load(ref / f).ravel().astype(np.float64) for f in ("Q_table_a.npy", "Q_table_b.npy"))
+        rr = evaluation.landing_rates(qa, qb, device=a.device, **kw)
+        rep["reference_tables"] = {"touchdown_rate": float(rr["touchdown_rate"][0]), "goal_hold_rate": float(rr["goal_hold_rate"][0])}
+    return rep, td, gh
 
 
 def main():
@@ -28,6 +58,11 @@ def main():
     ap.add_argument("--episodes", type=int, default=50000, help="episode budget per level and learner")
     ap.add_argument("--f64", action="store_true")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--score", type=int, default=0, metavar="ENVS", help="fly every learner on ENVS envs per flavour after the curriculum (a multiple of 64; 0: do not)")
+    ap.add_argument("--score-episodes", type=int, default=evaluation.DEFAULT_SCORE_EPISODES, help="episodes per env of the scoring run")
+    ap.add_argument("--score-seed", type=int, default=123)
+    ap.add_argument("--reference-tables", default=str(ROOT / "tests" / "golden" / "assets"), help="directory with the reference's Q_table_a.npy / Q_table_b.npy")
+    ap.add_argument("--score-json", default=None, help="also write the scoring report to this file")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     dtype = F64 if a.f64 else F32
@@ -39,8 +74,19 @@ def main():
             print(json.dumps({"level": h["level"], "periods": h["periods"], "promoted": int((p >= 0).sum()), "of": int(p.size),
                               "median_promotion_episode": None if not (p >= 0).any() else int(np.median(p[p >= 0]))}), flush=True)
         hist = curriculum(ens, levels=a.levels, max_episodes=a.episodes, on_level=report)
+        extra = {}
+        if a.score:
+            rep, td, gh = score_report(ens, a)
+            extra = {"touchdown_rate": td, "goal_hold_rate": gh}
+            print(json.dumps(rep), flush=True)
+            ref = rep["reference_tables"]
+            print(f"{rep['learners_at_or_above_bar']} of {rep['learners']} learners ({100.0 * rep['share_at_or_above_bar']:.1f} %) reach a touchdown rate of "
+                  f"{evaluation.LANDING_BAR}; median touchdown {rep['touchdown_rate']['q50']:.4f}, goal hold {rep['goal_hold_rate']['q50']:.4f}; the reference's tables: "
+                  + ("not found" if ref is None else f"touchdown {ref['touchdown_rate']:.4f}, goal hold {ref['goal_hold_rate']:.4f}"), flush=True)
+            if a.score_json:
+                Path(a.score_json).write_text(json.dumps(rep) + "\n")
         qa, qb, cnt = ens.get_tables()
-        np.savez_compressed(a.out, Q_table_a=qa, Q_table_b=qb, state_action_counter=cnt,
+        np.savez_compressed(a.out, Q_table_a=qa, Q_table_b=qb, state_action_counter=cnt, **extra,
                             promotion_episode=np.stack([h["promotion_episode"] for h in hist]), periods=np.array([h["periods"] for h in hist]))
     finally:
         ens.close()

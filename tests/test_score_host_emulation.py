@@ -1,0 +1,154 @@
+"""The scoring kernel's per-lane body (csrc/dql_score.hpp) run on the CPU and held to the oracle's STEPWISE loop with == (CPU only, no GPU).
+
+tests/host_emu/score_emu.cpp compiles the real device headers as host C++ and flies every env episode after episode, lane by lane, exactly as k_score
+does, adding each lane's tally to its table set's row.  The yardstick is the unchanged oracle driven one period at a time (tests/score_checks.py:
+`Oracle.eval_steps(1)` repeated, every FL_DONE of every env noted), which knows nothing of the scoring: the per-episode log, by_code and steps_sum must be
+equal.  Built twice: plain, and with ASan + UBSan (any report fails).
+
+Every case asserts on the ORACLE's result, before comparing, that it is not vacuous."""
+import os
+import shutil
+import struct
+import subprocess
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from oracle.oracle import Oracle
+
+import rollout_checks as rc
+import score_checks as sc
+
+ROOT = Path(__file__).resolve().parent.parent
+EMU = ROOT / "tests" / "host_emu"
+CSRC = ROOT / "dql_multirotor_landing_amd" / "csrc"
+
+N_ENVS, SEED, EPISODES = 64, 123, 3
+MAX_STEPS = 900      # three episodes of every env of every case end before it (asserted on the oracle)
+CASE_IDS = ("simulation-f64", "training4-f32")
+N_COLS = sc.N_CODES + 1
+X_TWO, X_ONLY = 0, 1  # dql_device.hpp
+
+PLAIN_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-mfma"]
+SAN_FLAGS = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off"]
+SAN_ENV = {"ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1"}
+SAN_MARKERS = ("runtime error:", "ERROR: AddressSanitizer", "ERROR: LeakSanitizer", "SUMMARY: ")
+
+
+def _clangxx():
+    rocm = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
+    for c in (rocm / "llvm" / "bin" / "clang++", rocm / "lib" / "llvm" / "bin" / "clang++"):
+        if c.exists():
+            return str(c)
+    c = shutil.which("clang++")
+    assert c, "the host emulation needs clang++ (ROCm's llvm/bin/clang++): dql_device.hpp uses clang vector extensions"
+    return c
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    """the two builds of tests/host_emu/score_emu.cpp: {"plain": path, "san": path}"""
+    out = tmp_path_factory.mktemp("score_emu")
+    cxx = _clangxx()
+    common = ["-I", str(EMU), "-I", str(CSRC), "-Wno-pass-failed", str(EMU / "score_emu.cpp")]
+    builds = {"plain": PLAIN_FLAGS, "san": SAN_FLAGS}
+
+    def build(kind):
+        exe = out / f"score_emu_{kind}"
+        r = subprocess.run([cxx, *builds[kind], *common, "-o", str(exe)], capture_output=True, text=True)
+        assert r.returncode == 0, f"{kind} build of score_emu failed:\n{r.stderr[-4000:]}"
+        return exe
+
+    with ThreadPoolExecutor(2) as ex:
+        return dict(zip(builds, ex.map(build, builds)))
+
+
+def run_emu(exe, cfg, sets, n, seed, max_steps, episodes, tmp, log=True, sanitized=False):
+    """the score of the table sets `sets` as ops.score returns it"""
+    K = len(sets)
+    c = bytes(cfg.to_c())
+    hdr = struct.pack("<8i", len(c), cfg.dtype, X_TWO if cfg.two_axis else X_ONLY, K, max_steps, episodes, 1 if log else 0, 0) + struct.pack("<2q", n, seed)
+    qa = np.stack([np.ascontiguousarray(s[0], np.float64).ravel() for s in sets]); qb = np.stack([np.ascontiguousarray(s[1], np.float64).ravel() for s in sets])
+    job, res = tmp / "score_job.bin", tmp / "score_res.bin"
+    job.write_bytes(hdr + c + qa.tobytes() + qb.tobytes())
+    env = dict(os.environ, **SAN_ENV) if sanitized else None
+    r = subprocess.run([str(exe), str(job), str(res)], capture_output=True, text=True, env=env, timeout=1800)
+    assert r.returncode == 0, f"score_emu ({'sanitized' if sanitized else 'plain'}) failed:\n{r.stderr[-6000:]}"
+    assert not any(m in r.stderr for m in SAN_MARKERS), f"sanitizer report:\n{r.stderr[-6000:]}"
+    b = res.read_bytes()
+    nt = K * n
+    o = 0
+    by_code = np.frombuffer(b, np.int64, K * N_COLS, o).reshape(K, N_COLS); o += 8 * K * N_COLS
+    steps_sum = np.frombuffer(b, np.int64, K, o); o += 8 * K
+    ep_code = ep_steps = None
+    if log:
+        ep_code = np.frombuffer(b, np.uint8, episodes * nt, o).reshape(episodes, nt); o += episodes * nt
+        ep_steps = np.frombuffer(b, np.uint16, episodes * nt, o).reshape(episodes, nt); o += 2 * episodes * nt
+    assert o == len(b)
+    return {"by_code": by_code, "steps_sum": steps_sum, "ep_code": ep_code, "ep_steps": ep_steps}
+
+
+_YARDSTICKS = {}
+
+
+def oracle_yardsticks(case_id, max_steps):
+    """the stepwise result of each of the three table sets, computed once per (case, max_steps) and left unchanged"""
+    key = (case_id, max_steps)
+    if key not in _YARDSTICKS:
+        cfg = rc.case_config(case_id)
+        _YARDSTICKS[key] = [sc.stepwise_episodes(Oracle(cfg, N_ENVS, seed=SEED), t, max_steps, EPISODES) for t in rc.three_table_sets()]
+    return _YARDSTICKS[key]
+
+
+def cut_for(case_id):
+    """a max_steps, chosen on the oracle's full run, at which the reference's tables have finished first episodes and unfinished later ones: the median period
+    at which a second episode ends (lengths + one reset period per episode)"""
+    w = oracle_yardsticks(case_id, MAX_STEPS)[0]
+    end_of_second = w["ep_steps"][0].astype(np.int64) + w["ep_steps"][1].astype(np.int64) + 1
+    return int(np.median(end_of_second))
+
+
+@pytest.mark.parametrize("case_id", CASE_IDS)
+def test_three_episodes_of_three_table_sets_equal_the_oracle_s_stepwise_loop(emu, case_id, tmp_path):
+    cfg = rc.case_config(case_id)
+    want = oracle_yardsticks(case_id, MAX_STEPS)
+    for k, w in enumerate(want):  # not vacuous: everything finished, and the sets end differently
+        assert w["by_code"][sc.UNFINISHED] == 0 and w["by_code"].sum() == N_ENVS * EPISODES, f"{case_id} set {k}: {w['by_code'].tolist()}"
+        assert w["ep_steps"].min() >= 1
+    assert np.count_nonzero(want[0]["by_code"]) >= 2, want[0]["by_code"].tolist()
+    assert want[0]["by_code"].tolist() != want[1]["by_code"].tolist()
+    got = run_emu(emu["plain"], cfg, rc.three_table_sets(), N_ENVS, SEED, MAX_STEPS, EPISODES, tmp_path)
+    assert got["by_code"].shape == (3, N_COLS) and got["ep_code"].shape == (EPISODES, 3 * N_ENVS)
+    for k, w in enumerate(want):
+        sc.assert_set_equal(got, k, N_ENVS, w, f"{case_id} table set {k}")
+    nolog = run_emu(emu["plain"], cfg, rc.three_table_sets(), N_ENVS, SEED, MAX_STEPS, EPISODES, tmp_path, log=False)
+    assert nolog["ep_code"] is None and np.array_equal(nolog["by_code"], got["by_code"]) and np.array_equal(nolog["steps_sum"], got["steps_sum"])
+
+
+@pytest.mark.parametrize("case_id", CASE_IDS)
+def test_a_cut_off_run_has_finished_and_unfinished_episodes_and_counts_both(emu, case_id, tmp_path):
+    cfg = rc.case_config(case_id)
+    cut = cut_for(case_id)
+    want = oracle_yardsticks(case_id, cut)
+    w = want[0]
+    finished, unfinished = int(w["by_code"][:sc.UNFINISHED].sum()), int(w["by_code"][sc.UNFINISHED])
+    assert finished >= N_ENVS and unfinished >= N_ENVS // 4 and finished + unfinished == N_ENVS * EPISODES, f"cut at {cut}: {w['by_code'].tolist()}"
+    assert (w["ep_code"][0] != sc.NO_CODE).any() and (w["ep_code"][EPISODES - 1] == sc.NO_CODE).any()
+    assert ((w["ep_code"] == sc.NO_CODE) == (w["ep_steps"] == sc.NO_STEPS)).all()
+    got = run_emu(emu["plain"], cfg, rc.three_table_sets(), N_ENVS, SEED, cut, EPISODES, tmp_path)
+    for k, wk in enumerate(want):
+        sc.assert_set_equal(got, k, N_ENVS, wk, f"{case_id} cut at {cut}, table set {k}")
+    assert (got["by_code"].sum(axis=1) == N_ENVS * EPISODES).all()
+
+
+@pytest.mark.parametrize("case_id", CASE_IDS)
+def test_score_clean_under_asan_and_ubsan(emu, case_id, tmp_path):
+    """the cut-off run (both kinds of log entry are written) through the ASan + UBSan build: no report, and still the oracle's result"""
+    cfg = rc.case_config(case_id)
+    cut = cut_for(case_id)
+    want = oracle_yardsticks(case_id, cut)
+    got = run_emu(emu["san"], cfg, rc.three_table_sets(), N_ENVS, SEED, cut, EPISODES, tmp_path, sanitized=True)
+    for k, wk in enumerate(want):
+        sc.assert_set_equal(got, k, N_ENVS, wk, f"sanitized {case_id} cut at {cut}, table set {k}")
