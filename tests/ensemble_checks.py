@@ -50,7 +50,18 @@ class Reference:
         self.windows = [deque([], maxlen=self.W) for _ in range(self.n)]
         self.promoted = np.full(self.n, -1, np.int32)
         self.frozen = np.zeros(self.n, bool)
+        self.freeze_period = np.full(self.n, -1, np.int64)  # the period index in which the learner froze (not part of result(): the ensemble does not keep it)
         self.snap = {}
+
+    def set_schedules(self, eps, window, min_successes, max_episodes):
+        """`SequentialEnsemble.set_schedules` without the learning rates: a new exploration table and new freeze rules for the learners as they stand.  A deque
+        cannot change its length with entries in it, so the window may only change while every deque is empty (right after the start or a `set_level`)."""
+        self.thr = [eps_thr(e) for e in eps]
+        if int(window) != self.W:
+            assert all(len(w) == 0 for w in self.windows), "the window length changes with outcomes in a deque"
+            self.W = int(window)
+            self.windows = [deque([], maxlen=self.W) for _ in range(self.n)]
+        self.min_successes, self.max_episodes = int(min_successes), int(max_episodes)
 
     def set_level(self, k):
         for l, b in self.snap.items():  # the frozen envs as they were left, then every env re-enters through reset
@@ -109,6 +120,7 @@ class Reference:
                     elif self.level_episodes[l] >= self.max_episodes:
                         self.frozen[l] = True
                     if self.frozen[l]:
+                        self.freeze_period[l] = j
                         self.snap[l] = o.envs[l * self.es:(l + 1) * self.es].copy()
             self.j += 1
 
@@ -147,3 +159,36 @@ def assert_equal(got, want, what, learners=None):
         else:
             bad = g.astype(np.int64) != w.astype(np.int64)
         assert not bad.any(), f"{what}: {k} differs in {np.count_nonzero(bad)} of {w.size} entries, first at {tuple(int(v[0]) for v in np.nonzero(bad))}: {g[bad][0]!r} vs {w[bad][0]!r}"
+
+
+# ---- the long case shared by tests/test_gpu_ensemble_long.py and tests/test_learner_host_emulation.py ----
+# 16 learners at level 0 with a promotion window of 72 episodes (two ring words), 28 successes to promote, 100 episodes at most, and 8 200 periods: three
+# launches (4 096 + 4 096 + 8) in one call.  On the reference loop the learners fall into four classes, each of which takes another path through the ring.
+RING_CASE = dict(eps=[0.3], window=72, min_successes=28, max_episodes=100, log_capacity=128)
+RING_LEARNERS, RING_SEED, RING_PERIODS = 16, 11, 8200
+
+
+def ring_classes(res):
+    """learner masks by where the promotion ring stood when the learner froze: promoted with only word 0 written (episode <= 64), promoted by an episode
+    written to word 1 (65 .. window), promoted after the ring wrapped and evicted (> window), out of episodes"""
+    p, w = res["promotion_episode"], RING_CASE["window"]
+    return {"word 0": (p >= 1) & (p <= 64), "word 1": (p >= 65) & (p <= w), "wrapped": p > w,
+            "exhausted": (p < 0) & res["frozen"] & (res["level_episodes"] == RING_CASE["max_episodes"])}
+
+
+def ring_reference(cfg):
+    """(result, freeze periods) of the reference loop on the long case, after asserting ON IT that every path the case is for is taken"""
+    ref = Reference(cfg, RING_LEARNERS, RING_SEED, **RING_CASE)
+    ref.run(RING_PERIODS)
+    want = ref.result()
+    classes = ring_classes(want)
+    print("ring case:", {k: int(v.sum()) for k, v in classes.items()}, "promotion episodes", want["promotion_episode"].tolist(), "largest visit count", want["count"].max())
+    for name, m in classes.items():
+        assert m.sum() >= 1, f"no learner of the class '{name}': {want['promotion_episode'].tolist()}"
+    assert sum(int(m.sum()) for m in classes.values()) == RING_LEARNERS and want["frozen"].all()
+    assert want["log_n"].max() == RING_CASE["max_episodes"] and want["log_n"].max() < RING_CASE["log_capacity"]
+    # a learner flies one reset period per episode and one decision in every other period until it freezes: the identity the GPU test dates the waves with
+    assert np.array_equal(ref.freeze_period, want["decisions"] + want["episodes"] - 1)
+    # frozen in different periods, some in the first launch of 4 096 periods and some beyond it
+    assert ref.freeze_period.min() < 4096 < ref.freeze_period.max() and len(set(ref.freeze_period.tolist())) == RING_LEARNERS
+    return want, ref.freeze_period.copy()

@@ -48,6 +48,11 @@ def sums_of_log(ep_code, ep_steps):
     return {"by_code": by_code, "steps_sum": int(ep_steps.astype(np.int64).sum())}
 
 
+def lane_sums(want):
+    """(unfinished episodes, total length of the finished ones) per env of a yardstick: what a lane of the kernel hands to the wave's sums over bit planes"""
+    return (want["ep_code"] == NO_CODE).sum(axis=0).astype(np.int64), want["ep_steps"].astype(np.int64).sum(axis=0)
+
+
 def assert_set_equal(got, k, n, want, what):
     """table set `k` (log columns [k n, (k + 1) n)) of a score result against the yardstick of that set: log, by_code and steps_sum, all =="""
     gc, gs = got["ep_code"][:, k * n:(k + 1) * n], got["ep_steps"][:, k * n:(k + 1) * n]

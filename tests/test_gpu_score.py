@@ -2,6 +2,7 @@
 of include/dql.h — the m-th time env i shows FL_DONE, its code and step count are entry (m, k * envs + i) of the log, and by_code / steps_sum are the sums of
 those entries.  Every comparison is ==."""
 import ctypes as C
+import time
 
 import numpy as np
 import pytest
@@ -114,6 +115,49 @@ def test_three_hundred_table_sets_repeat_the_rows_of_three():
     assert np.array_equal(big["by_code"], three["by_code"][idx]) and np.array_equal(big["steps_sum"], three["steps_sum"][idx])
     assert np.array_equal(big["ep_code"].reshape(EPISODES, K, n), three["ep_code"].reshape(EPISODES, 3, n)[:, idx])
     assert np.array_equal(big["ep_steps"].reshape(EPISODES, K, n), three["ep_steps"].reshape(EPISODES, 3, n)[:, idx])
+
+
+@pytest.mark.parametrize("case_id", ["simulation-f32", "simulation-f64"])
+def test_sixty_four_unfinished_episodes_per_lane_set_the_highest_plane_of_the_count(case_id):
+    """64 episodes per env, cut at max_steps = 5: no episode ends in 6 periods, so every lane reports 64 unfinished episodes — bit 6 of the per-lane count,
+    the highest of the 7 planes the wave's sum is taken over"""
+    cfg = rc.case_config(case_id)
+    n, episodes, cut = 64, ops.SCORE_MAX_EPISODES, 5
+    want = engine_yardsticks(case_id, n, cut, episodes)
+    for w in want:  # on the stepwise Engine: nothing finished
+        assert w["by_code"][sc.UNFINISHED] == n * episodes and w["by_code"][:sc.UNFINISHED].sum() == 0 and w["steps_sum"] == 0
+    got = ops.score(cfg, *stacked(rc.three_table_sets()), n, SEED, episodes=episodes, max_steps=cut, log=True)
+    for k, w in enumerate(want):
+        sc.assert_set_equal(got, k, n, w, f"{case_id}, 64 unfinished episodes per lane, table set {k}")
+    assert (got["by_code"][:, sc.UNFINISHED] == n * episodes).all() and (got["by_code"][:, :sc.UNFINISHED] == 0).all() and (got["steps_sum"] == 0).all()
+    assert (got["ep_code"] == sc.NO_CODE).all() and (got["ep_steps"] == sc.NO_STEPS).all()
+    nolog = ops.score(cfg, *stacked(rc.three_table_sets()), n, SEED, episodes=episodes, max_steps=cut)
+    assert np.array_equal(nolog["by_code"], got["by_code"]) and np.array_equal(nolog["steps_sum"], got["steps_sum"])
+
+
+def test_a_long_score_sets_every_plane_of_the_lane_sums():
+    """64 episodes per env within 4 096 periods, the reference's tables, `training4-f32`: per lane 26 - 37 episodes stay unfinished and the finished ones add
+    up to 3 805 - 4 070 steps, so planes 0 - 5 of `unfinished` and 0 - 11 of `lane_steps` all carry a set bit in some lane (asserted on the stepwise Engine).
+    `simulation-f32`, the case of the other tests here, leaves 41 - 44 episodes unfinished per lane and never sets bit 4; plane 12 of `lane_steps` needs a sum of
+    4 096 steps, which max_steps <= 4 096 with a reset period per episode cannot give."""
+    case_id, n, episodes, max_steps = "training4-f32", 64, ops.SCORE_MAX_EPISODES, 4096
+    cfg = rc.case_config(case_id)
+    tables = rc.stage4_tables()
+    t0 = time.perf_counter()
+    eng = Engine(cfg, n, seed=SEED)
+    try:
+        want = sc.stepwise_episodes(eng, tables, max_steps, episodes)
+    finally:
+        eng.close()
+    print(f"stepwise Engine, {max_steps + 1} periods: {time.perf_counter() - t0:.2f} s")
+    unfinished, steps = sc.lane_sums(want)
+    print("unfinished per lane", int(unfinished.min()), "..", int(unfinished.max()), "steps per lane", int(steps.min()), "..", int(steps.max()), want["by_code"].tolist())
+    assert int(np.bitwise_or.reduce(unfinished)) & 0x3f == 0x3f, sorted(set(unfinished.tolist()))
+    assert int(np.bitwise_or.reduce(steps)) & 0xfff == 0xfff and steps.max() < 1 << 13
+    got = ops.score(cfg, tables[0][None], tables[1][None], n, SEED, episodes=episodes, max_steps=max_steps, log=True)
+    sc.assert_set_equal(got, 0, n, want, f"{case_id}, {episodes} episodes within {max_steps} periods")
+    nolog = ops.score(cfg, tables[0][None], tables[1][None], n, SEED, episodes=episodes, max_steps=max_steps)
+    assert nolog["ep_code"] is None and np.array_equal(nolog["by_code"], got["by_code"]) and np.array_equal(nolog["steps_sum"], got["steps_sum"])
 
 
 def ensemble_snapshot(ens):

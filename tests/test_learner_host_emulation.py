@@ -13,7 +13,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from dql_multirotor_landing_amd.config import F32, F64, N_CELLS, training_config
+from dql_multirotor_landing_amd.config import F32, F64, N_CELLS, as_launched_config, training_config
 
 import ensemble_checks as ec
 
@@ -55,11 +55,11 @@ def emu(tmp_path_factory):
         return dict(zip(builds, ex.map(build, builds)))
 
 
-def run_emu(exe, cfg, n, seed, runs, tmp, eps=ec.EPS_TABLE, window=100, min_successes=97, max_episodes=1 << 30, sanitized=False):
+def run_emu(exe, cfg, n, seed, runs, tmp, eps=ec.EPS_TABLE, window=100, min_successes=97, max_episodes=1 << 30, sanitized=False, log_capacity=LOG_CAP, alpha_tab=None):
     c = bytes(cfg.to_c())
-    alpha = cfg.alpha_table()
+    alpha = cfg.alpha_table() if alpha_tab is None else np.ascontiguousarray(alpha_tab, np.float64)
     r4 = list(runs) + [0] * (4 - len(runs))
-    hdr = struct.pack("<16i", len(c), cfg.dtype, n, len(runs), *r4, len(alpha), len(eps), window, min_successes, max_episodes, LOG_CAP, 0, 0) + struct.pack("<q", seed)
+    hdr = struct.pack("<16i", len(c), cfg.dtype, n, len(runs), *r4, len(alpha), len(eps), window, min_successes, max_episodes, log_capacity, 0, 0) + struct.pack("<q", seed)
     job, res = tmp / "learner_job.bin", tmp / "learner_res.bin"
     job.write_bytes(hdr + c + alpha.tobytes() + np.asarray(eps, np.float64).tobytes())
     env = dict(os.environ, **SAN_ENV) if sanitized else None
@@ -79,7 +79,7 @@ def run_emu(exe, cfg, n, seed, runs, tmp, eps=ec.EPS_TABLE, window=100, min_succ
     out = {"qa": take(np.float64, (n, N_CELLS)), "qb": take(np.float64, (n, N_CELLS)), "count": take(np.float64, (n, N_CELLS)),
            "decisions": take(np.int64, (n,)), "by_code": take(np.int64, (ec.N_CODES, n)), "episodes": take(np.int32, (n,)), "successes": take(np.int32, (n,)),
            "level_episodes": take(np.int32, (n,)), "promotion_episode": take(np.int32, (n,)), "frozen": take(np.int32, (n,)), "log_n": take(np.int32, (n,)),
-           "log_code": take(np.uint8, (n, LOG_CAP)), "log_len": take(np.uint16, (n, LOG_CAP))}
+           "log_code": take(np.uint8, (n, log_capacity)), "log_len": take(np.uint16, (n, log_capacity))}
     reals, ints = take(np.float64, (64, n)), take(np.int32, (7, n))
     faults = take(np.int64, (1,))
     assert o == len(b)
@@ -121,3 +121,60 @@ def test_learner_clean_under_asan_and_ubsan(emu, reference, dtype, tmp_path):
     cfg = training_config(0, quirks=ec.Q_PAPER, dtype=dtype)
     got = run_emu(emu["san"], cfg, L, SEED, RUNS, tmp_path, sanitized=True)
     ec.assert_equal(got, reference(dtype, ec.Q_PAPER), f"sanitized dtype {dtype}")
+
+
+# ---- beyond 300 periods: the paths of learner_periods that the cases above do not reach ----
+RING_RUNS = (4096, 4096, 8)  # what dql_ensemble_run makes of run(8200): learner_periods clamps at 4 096 periods as the host loop does
+
+
+@pytest.fixture(scope="module")
+def ring():
+    """the reference loop on ensemble_checks' long case (about ten seconds), computed once; its asserts on the reference are in ring_reference"""
+    assert sum(RING_RUNS) == ec.RING_PERIODS
+    return ec.ring_reference(training_config(0, quirks=ec.Q_REFERENCE, dtype=F32))[0]
+
+
+def test_ring_second_word_and_wrap_in_three_launches_equal_the_reference_loop(emu, ring, tmp_path):
+    """window 72: learners promoted from ring word 0, from word 1, after the wrap (eviction), and out of episodes; launches of 4 096 + 4 096 + 8 periods, the
+    later ones entered by frozen learners"""
+    cfg = training_config(0, quirks=ec.Q_REFERENCE, dtype=F32)
+    got = run_emu(emu["plain"], cfg, ec.RING_LEARNERS, ec.RING_SEED, RING_RUNS, tmp_path, **ec.RING_CASE)
+    ec.assert_equal(got, ring, "ring case")
+
+
+def test_ring_case_clean_under_asan_and_ubsan(emu, ring, tmp_path):
+    """the first 4 learners of the long case through the sanitized build"""
+    first = list(range(4))
+    p = ring["promotion_episode"][first]
+    assert (p > 64).any() and (p < 0).any(), p.tolist()  # on the reference: one of them writes ring word 1, one spends its 100 episodes (the ring wraps)
+    cfg = training_config(0, quirks=ec.Q_REFERENCE, dtype=F32)
+    got = run_emu(emu["san"], cfg, len(first), ec.RING_SEED, RING_RUNS, tmp_path, sanitized=True, **ec.RING_CASE)
+    ec.assert_equal(got, ring, "sanitized ring case, learners 0 - 3", learners=(first, first))
+
+
+def test_alpha_min_beyond_the_table_and_a_full_episode_log(emu, tmp_path):
+    """a learning-rate table of 32 entries and a log of 8 episodes: visit counts pass the table's end (alpha_min from count 32 on, the table's last entry at
+    31) and log_n counts on beyond the log, which keeps the first 8 episodes"""
+    n, seed, periods, cap = 16, 11, 1500, 8
+    cfg = training_config(0, quirks=ec.Q_REFERENCE, dtype=F32)
+    tab = cfg.alpha_table()[:32]
+    assert tab[31] != cfg.alpha_min and len(tab) == 32  # the table's end is not on the plateau: an off-by-one at count 32 or 31 changes a learning rate
+    ref = ec.Reference(cfg, n, seed, eps=[0.3], log_capacity=cap, alpha_tab=tab)
+    ref.run(periods)
+    want = ref.result()
+    assert want["count"].max() > 64 and ((want["count"] > 32).sum(axis=1) >= 1).all() and want["log_n"].min() > cap and not want["frozen"].any()
+    assert want["log_code"].shape == (n, cap) and (want["log_len"] > 0).all()
+    got = run_emu(emu["plain"], cfg, n, seed, (1000, 500), tmp_path, eps=[0.3], log_capacity=cap, alpha_tab=tab)
+    ec.assert_equal(got, want, "short alpha table, log of 8")
+
+
+def test_as_launched_parameters_equal_the_reference_loop(emu, tmp_path):
+    """as_launched_config (observation noise 0.25 m / 0.1 m/s, platform at 1 m/s): what the G14 figures were flown with"""
+    cfg = as_launched_config(0, dtype=F32)
+    assert cfg.noise_pos_sd > 0.0 and cfg.noise_vel_sd > 0.0 and cfg.mp_t_x != training_config(0).mp_t_x and cfg.quirks == ec.Q_REFERENCE
+    ref = ec.Reference(cfg, L, SEED, log_capacity=LOG_CAP)
+    ref.run(300)
+    want = ref.result()
+    assert want["episodes"].min() >= 1 and len(set(want["log_code"][want["log_code"] > 0].tolist())) >= 2 and (want["qa"] != 0).any()
+    got = run_emu(emu["plain"], as_launched_config(0, dtype=F32), L, SEED, (7, 293), tmp_path)
+    ec.assert_equal(got, want, "as-launched parameters")

@@ -152,3 +152,38 @@ def test_score_clean_under_asan_and_ubsan(emu, case_id, tmp_path):
     got = run_emu(emu["san"], cfg, rc.three_table_sets(), N_ENVS, SEED, cut, EPISODES, tmp_path, sanitized=True)
     for k, wk in enumerate(want):
         sc.assert_set_equal(got, k, N_ENVS, wk, f"sanitized {case_id} cut at {cut}, table set {k}")
+
+
+# ---- the high bit planes of the lane sums (7 planes for the unfinished episodes, 13 for the steps) ----
+@pytest.mark.parametrize("case_id", ("simulation-f32", "simulation-f64"))
+def test_sixty_four_unfinished_episodes_per_lane_set_the_highest_plane_of_the_count(emu, case_id, tmp_path):
+    """64 episodes per env, cut at max_steps = 5: no episode ends in 6 periods, so every lane reports 64 unfinished episodes, bit 6 of its count"""
+    cfg = rc.case_config(case_id)
+    episodes, cut = 64, 5
+    want = [sc.stepwise_episodes(Oracle(cfg, N_ENVS, seed=SEED), t, cut, episodes) for t in rc.three_table_sets()]
+    for w in want:  # on the oracle: nothing finished
+        assert w["by_code"][sc.UNFINISHED] == N_ENVS * episodes and w["by_code"][:sc.UNFINISHED].sum() == 0 and w["steps_sum"] == 0
+        assert (sc.lane_sums(w)[0] == 64).all()
+    got = run_emu(emu["plain"], cfg, rc.three_table_sets(), N_ENVS, SEED, cut, episodes, tmp_path)
+    for k, w in enumerate(want):
+        sc.assert_set_equal(got, k, N_ENVS, w, f"{case_id}, 64 unfinished episodes per lane, table set {k}")
+    assert (got["by_code"][:, sc.UNFINISHED] == N_ENVS * episodes).all() and (got["steps_sum"] == 0).all() and (got["ep_code"] == sc.NO_CODE).all()
+    nolog = run_emu(emu["plain"], cfg, rc.three_table_sets(), N_ENVS, SEED, cut, episodes, tmp_path, log=False)
+    assert np.array_equal(nolog["by_code"], got["by_code"]) and np.array_equal(nolog["steps_sum"], got["steps_sum"])
+
+
+def test_a_long_score_sets_every_plane_of_the_lane_sums(emu, tmp_path):
+    """64 episodes per env within 4 096 periods, the reference's tables, `training4-f32`: on the oracle the lanes leave 26 - 37 episodes unfinished and sum
+    3 805 - 4 070 steps, so planes 0 - 5 of the count and 0 - 11 of the steps all carry a set bit in some lane (`simulation-f32` leaves 41 - 44 unfinished:
+    bit 4 never set)"""
+    case_id, episodes, max_steps = "training4-f32", 64, 4096
+    cfg = rc.case_config(case_id)
+    tables = rc.stage4_tables()
+    want = sc.stepwise_episodes(Oracle(cfg, N_ENVS, seed=SEED), tables, max_steps, episodes)
+    unfinished, steps = sc.lane_sums(want)
+    assert int(np.bitwise_or.reduce(unfinished)) & 0x3f == 0x3f, sorted(set(unfinished.tolist()))
+    assert int(np.bitwise_or.reduce(steps)) & 0xfff == 0xfff and steps.max() < 1 << 13
+    got = run_emu(emu["plain"], cfg, [tables], N_ENVS, SEED, max_steps, episodes, tmp_path)
+    sc.assert_set_equal(got, 0, N_ENVS, want, f"{case_id}, {episodes} episodes within {max_steps} periods")
+    nolog = run_emu(emu["plain"], cfg, [tables], N_ENVS, SEED, max_steps, episodes, tmp_path, log=False)
+    assert nolog["ep_code"] is None and np.array_equal(nolog["by_code"], got["by_code"]) and np.array_equal(nolog["steps_sum"], got["steps_sum"])
