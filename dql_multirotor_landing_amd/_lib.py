@@ -164,6 +164,12 @@ SYMBOLS = {
     "dql_ensemble_index_faults": (C.c_int, [_vp, C.POINTER(_i64)]),
     "dql_ensemble_score": (C.c_int, [_vp, _cfgp, _i64, _i64, _i64, _i32, _u64, _i32, _vp, _vp, _vp, _vp]),
     "dql_diag_ensemble_last": (C.c_int, [_vp, C.POINTER(_dbl)]),
+    "dql_diag_ensemble_launches": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    # per-learner curriculum levels (include/dql.h)
+    "dql_ensemble_set_curriculum": (C.c_int, [_vp, _i32, _i32, _vp, _i32]),
+    "dql_ensemble_set_level_schedules": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32]),
+    "dql_ensemble_get_levels": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "dql_ensemble_n_unfinished": (C.c_int, [_vp, C.POINTER(_i64)]),
 }
 MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS
 

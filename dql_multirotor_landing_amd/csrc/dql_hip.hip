@@ -31,6 +31,7 @@
 #include "dql_host_consts.hpp"
 #include "dql_rollout.hpp"
 #include "dql_learner.hpp"
+#include "dql_advance.hpp"
 #include "dql_score.hpp"
 #include "../../include/dql_diag.h"
 
@@ -1068,6 +1069,56 @@ __global__ void k_ens_transfer(double* qa, double* qb, long long n, int k, int s
   double* a = qa + l * DQL_N_CELLS; double* b = qb + l * DQL_N_CELLS;
   a[k * DQL_CELLS_PER_LEVEL + i] = a[src * DQL_CELLS_PER_LEVEL + i] * ratio;
   b[k * DQL_CELLS_PER_LEVEL + i] = b[src * DQL_CELLS_PER_LEVEL + i] * ratio;
+}
+
+// ---- per-learner curriculum levels ----
+// k_learn over a worklist (csrc/dql_advance.hpp: build_worklist): wave w flies the learners worklist[64 w .. 64 w + 63] (-1: an inactive lane), all of
+// them at level wave_level[w] — a scalar load — from which follow SimK::working, the level's MdpK (a.a.mdp is the array of all five) and the level's
+// exploration table and freeze rules.  After that the call to learner_periods is k_learn's.
+template <typename T> struct LearnLevelsArgs {
+  LearnArgs<T> a;                          // a.mdp: [DQL_MAX_LEVELS]; a.sched: the learning rates (its per-level members are replaced by lv[level])
+  const LevelSched DQL_CONST_AS* lv;       // [DQL_MAX_LEVELS]
+  const int* worklist;                     // [64 n_waves]
+  const int DQL_CONST_AS* wave_level;      // [n_waves]
+  int n_waves;
+};
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_learn_levels(LearnLevelsArgs<T> g) {
+  const LearnArgs<T>& a = g.a;
+  const int tid = threadIdx.x;
+  const int w = (int)blockIdx.x;
+  if (w >= g.n_waves) return;
+  const int level = g.wave_level[w];
+  if ((unsigned)level >= (unsigned)DQL_MAX_LEVELS) { if (tid == 0) a.mem.faults[0] += 1ull; return; }  // never taken unless a bug (the host builds the worklist)
+  const long long l = (long long)g.worklist[(long long)w * 64 + tid];
+  SimK<T> cl = a.c;
+  cl.working = level;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // as in k_learn
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  const LevelSched DQL_CONST_AS* lv = g.lv + level;
+  const LearnSched sc{a.sched.alpha_tab, a.sched.n_alpha, a.sched.alpha_min, lv->eps_tab, lv->n_eps, lv->window, lv->min_successes, lv->max_episodes};
+  learner_periods<TICK, XMODE>(cl, cfgk, tc, a.mdp + level, a.mdp_run, sc, a.mem, a.sr, a.si, a.seed, l, l >= 0 && l < a.mem.n, a.j0, a.n_periods, a.mgr0, a.tick_sched, kv);
+}
+// an advance point: every learner takes advance_learner's step by itself (its own thread moves its own 2 x 567 cells; ordinary vector stores, nothing shared)
+// -- but for the `faults` word: advance_learner's `faults[0] += 1` is a plain add that threads of all waves may make at once, as learner_periods' is.  Counts
+// can be lost, a nonzero word cannot become zero, and nonzero is all that index_faults() is read for.
+__global__ void k_ens_advance(LearnMem mem, AdvanceMem adv, AdvanceRule rule, int4* si, long long j, int n_cells) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= mem.n) return;
+  (void)advance_learner(mem, adv, rule, si, l, j, n_cells);
 }
 
 // ---- greedy scoring (dql_score / dql_ensemble_score) ----
@@ -2678,18 +2729,51 @@ struct dql_ensemble {
   double* alpha_tab = nullptr; uint32_t* eps_tab = nullptr;
   long long* d_mgr0 = nullptr; int* d_sched = nullptr;  // [LEARN_MAX_PERIODS]
   double last_ms = -1.0;
+  // per-learner curriculum levels; advance_every = 0: the mode is off
+  AdvanceMem adv{};
+  AdvanceRule rule{};
+  int advance_every = 0;
+  void* mdpk5 = nullptr;                                      // [DQL_MAX_LEVELS] MdpK<T>, entry k with working = k
+  LevelSched* d_lv = nullptr; LevelSched h_lv[DQL_MAX_LEVELS]{}; bool have_lv[DQL_MAX_LEVELS]{};
+  int* d_worklist = nullptr; int* d_wave_level = nullptr; long long wl_slots = 0;
+  long long n_launches = 0, launched_periods = 0, launched_wave_periods = 0;  // since creation (dql_diag_ensemble_launches)
 };
 #define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
 static void ens_free(dql_ensemble* x) {
   void* ptrs[] = {x->sr, x->si, x->mdpk, x->mem.qa, x->mem.qb, x->mem.count, x->mem.decisions, x->mem.by_code, x->mem.episodes, x->mem.successes, x->mem.level_episodes,
                   x->mem.win_count, x->mem.win_bits, x->mem.promoted, x->mem.frozen, x->mem.log_code, x->mem.log_len, x->mem.log_n, x->mem.faults, x->alpha_tab, x->eps_tab,
-                  x->d_mgr0, x->d_sched};
+                  x->d_mgr0, x->d_sched, x->adv.level, x->adv.promoted_at, x->adv.episodes_at, x->adv.entered_period, x->mdpk5, x->d_lv, x->d_worklist, x->d_wave_level,
+                  (void*)x->h_lv[0].eps_tab, (void*)x->h_lv[1].eps_tab, (void*)x->h_lv[2].eps_tab, (void*)x->h_lv[3].eps_tab, (void*)x->h_lv[4].eps_tab};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   delete x;
 }
 static int ens_upload_mdpk(dql_ensemble* x) {
   if (x->cfg.dtype == DQL_F32) { const MdpK<float> m = make_mdpk<float>(x->cfg); HIP_TRY(hipMemcpy(x->mdpk, &m, sizeof(m), hipMemcpyHostToDevice)); }
   else { const MdpK<double> m = make_mdpk<double>(x->cfg); HIP_TRY(hipMemcpy(x->mdpk, &m, sizeof(m), hipMemcpyHostToDevice)); }
+  return DQL_OK;
+}
+// every learner to level k: the per-level history from level k on is cleared, level k is entered at the present period index
+static int ens_set_levels(dql_ensemble* x, int k) {
+  const size_t n = (size_t)x->n;
+  if (x->j == 0) HIP_TRY(hipMemset(x->adv.entered_period, 0xff, (size_t)DQL_MAX_LEVELS * n * sizeof(long long)));  // nothing was flown: no level below k was ever entered
+  std::vector<int> lv(n, k);
+  HIP_TRY(hipMemcpy(x->adv.level, lv.data(), n * sizeof(int), hipMemcpyHostToDevice));
+  const size_t from = (size_t)k * n, rest = (size_t)(DQL_MAX_LEVELS - k) * n;
+  HIP_TRY(hipMemset(x->adv.promoted_at + from, 0xff, rest * sizeof(int)));
+  HIP_TRY(hipMemset(x->adv.episodes_at + from, 0, rest * sizeof(int)));
+  HIP_TRY(hipMemset(x->adv.entered_period + from, 0xff, rest * sizeof(long long)));
+  std::vector<long long> at(n, x->j);
+  HIP_TRY(hipMemcpy(x->adv.entered_period + from, at.data(), n * sizeof(long long), hipMemcpyHostToDevice));
+  return DQL_OK;
+}
+// the five levels' MdpK (they differ in `working` only), read by k_learn_levels at the wave's level
+static int ens_upload_mdpk5(dql_ensemble* x) {
+  dql_config c = x->cfg;
+  for (int k = 0; k < DQL_MAX_LEVELS; ++k) {
+    c.working_curriculum_step = k;
+    if (x->cfg.dtype == DQL_F32) { const MdpK<float> m = make_mdpk<float>(c); HIP_TRY(hipMemcpy((MdpK<float>*)x->mdpk5 + k, &m, sizeof(m), hipMemcpyHostToDevice)); }
+    else { const MdpK<double> m = make_mdpk<double>(c); HIP_TRY(hipMemcpy((MdpK<double>*)x->mdpk5 + k, &m, sizeof(m), hipMemcpyHostToDevice)); }
+  }
   return DQL_OK;
 }
 // per-level episode counts, windows, promotion records and frozen flags back to "just started"
@@ -2723,6 +2807,19 @@ template <typename T> static void ens_launch(dql_ensemble* x, int n_periods) {
   a.mgr0 = (const long long DQL_CONST_AS*)x->d_mgr0; a.tick_sched = (const int DQL_CONST_AS*)x->d_sched;
   a.seed = x->seed; a.j0 = x->j; a.n_periods = n_periods;
   hipLaunchKernelGGL((k_learn<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)((x->n + 63) / 64)), dim3(64), 0, 0, a);
+}
+template <typename T> static void ens_launch_levels(dql_ensemble* x, int n_periods, int n_waves) {
+  LearnLevelsArgs<T> g;
+  LearnArgs<T>& a = g.a;
+  a.c = make_simk<T>(x->cfg);
+  a.mdp = (const MdpK<T> DQL_CONST_AS*)x->mdpk5;
+  a.mdp_run = MdpRun<T>{x->cfg.gamma, (T)(x->cfg.t_max * x->cfg.f_ag), x->cfg.goal_logic};
+  a.sched = x->sched; a.mem = x->mem;
+  a.sr = (Quad<T>*)x->sr; a.si = x->si;
+  a.mgr0 = (const long long DQL_CONST_AS*)x->d_mgr0; a.tick_sched = (const int DQL_CONST_AS*)x->d_sched;
+  a.seed = x->seed; a.j0 = x->j; a.n_periods = n_periods;
+  g.lv = (const LevelSched DQL_CONST_AS*)x->d_lv; g.worklist = x->d_worklist; g.wave_level = (const int DQL_CONST_AS*)x->d_wave_level; g.n_waves = n_waves;
+  hipLaunchKernelGGL((k_learn_levels<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
 }
 template <typename T> static int ens_get_state_t(dql_ensemble* x, double* out) {
   const long long n = x->n;
@@ -2760,8 +2857,18 @@ int dql_ensemble_create(const dql_config* cfg, int device, int64_t n_learners, u
   ENS_ALLOC(x->mem.log_n, n * sizeof(int));
   ENS_ALLOC(x->mem.faults, sizeof(unsigned long long));
   ENS_ALLOC(x->d_mgr0, (size_t)LEARN_MAX_PERIODS * sizeof(long long)); ENS_ALLOC(x->d_sched, (size_t)LEARN_MAX_PERIODS * sizeof(int));
+  ENS_ALLOC(x->adv.level, n * sizeof(int));
+  ENS_ALLOC(x->adv.promoted_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int)); ENS_ALLOC(x->adv.episodes_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int));
+  ENS_ALLOC(x->adv.entered_period, (size_t)DQL_MAX_LEVELS * n * sizeof(long long));
+  ENS_ALLOC(x->mdpk5, (size_t)DQL_MAX_LEVELS * (cfg->dtype == DQL_F32 ? sizeof(MdpK<float>) : sizeof(MdpK<double>)));
+  ENS_ALLOC(x->d_lv, (size_t)DQL_MAX_LEVELS * sizeof(LevelSched));
+  x->wl_slots = worklist_capacity(n_learners);
+  ENS_ALLOC(x->d_worklist, (size_t)x->wl_slots * sizeof(int)); ENS_ALLOC(x->d_wave_level, (size_t)(x->wl_slots / ADV_WAVE) * sizeof(int));
   x->mem.n = n_learners; x->mem.log_cap = log_capacity;
   rc = ens_upload_mdpk(x);
+  if (!rc) rc = ens_upload_mdpk5(x);
+  if (!rc) rc = ens_set_levels(x, 0);  // the whole history cleared ...
+  if (!rc) rc = ens_set_levels(x, cfg->working_curriculum_step);  // ... and the config's level entered at period 0
   if (!rc) rc = ens_rearm(x);
   if (!rc) rc = cfg->dtype == DQL_F32 ? ens_init<float>(x) : ens_init<double>(x);
   // default schedules: the plateau learning rate, no exploration, the reference's window (100 episodes, 97 successes) and no episode budget
@@ -2821,6 +2928,8 @@ int dql_ensemble_rearm(dql_ensemble* x) {
 int dql_ensemble_set_level(dql_ensemble* x, int32_t k) {
   CHECK_ENS(x);
   if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_level: curriculum step must be in 0..4");
+  if (x->advance_every && k > x->rule.last_level)
+    return fail(DQL_EINVAL, "dql_ensemble_set_level: in curriculum mode the level must not exceed last_level (raise it with dql_ensemble_set_curriculum first); nothing was changed");
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipDeviceSynchronize());
   x->cfg.working_curriculum_step = k;
@@ -2828,6 +2937,7 @@ int dql_ensemble_set_level(dql_ensemble* x, int32_t k) {
   hipLaunchKernelGGL(k_mark_reset, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->si, (const uint8_t*)nullptr, (long long)x->n);  // every env re-enters through reset
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
+  rc = ens_set_levels(x, k); if (rc) return rc;
   return ens_rearm(x);
 }
 int dql_ensemble_n_live(dql_ensemble* x, int64_t* n_live) {
@@ -2841,10 +2951,81 @@ int dql_ensemble_n_live(dql_ensemble* x, int64_t* n_live) {
   *n_live = live;
   return DQL_OK;
 }
+// frozen, level and promoted of every learner -> host; the learners that are not finished for good
+static int ens_fetch_levels(dql_ensemble* x, std::vector<int>& frozen, std::vector<int>& level, std::vector<int>& promoted, int64_t* unfinished) {
+  const size_t n = (size_t)x->n;
+  frozen.resize(n); level.resize(n); promoted.resize(n);
+  HIP_TRY(hipMemcpy(frozen.data(), x->mem.frozen, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(level.data(), x->adv.level, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(promoted.data(), x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
+  int64_t u = 0;
+  for (size_t l = 0; l < n; ++l) u += learner_finished(frozen[l], level[l], promoted[l], x->rule) ? 0 : 1;
+  *unfinished = u;
+  return DQL_OK;
+}
+// dql_ensemble_run in curriculum mode: the launches are cut at the multiples of advance_every; at such a period index j, before period j is flown, every
+// learner takes advance_learner's step; each launch flies the live learners regrouped by level (build_worklist)
+static int ens_run_levels(dql_ensemble* x, int64_t periods) {
+  std::vector<int> frozen, level, promoted;
+  int64_t unfinished = 0;
+  int rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
+  // the level a learner stands on is flown whatever last_level says, so its schedule is asked for first; then every level on its way up to last_level
+  for (size_t l = 0; l < (size_t)x->n; ++l) {
+    bool ok = level[l] >= 0 && level[l] < DQL_MAX_LEVELS && x->have_lv[level[l]];
+    for (int k = level[l] + 1; ok && k <= x->rule.last_level && k < DQL_MAX_LEVELS; ++k) ok = x->have_lv[k];
+    if (!ok) return fail(DQL_EINVAL, "dql_ensemble_run: curriculum mode needs dql_ensemble_set_level_schedules for every level from the learners' up to last_level; nothing was launched");
+  }
+  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
+  HIP_TRY(hipEventCreate(&e0.e)); HIP_TRY(hipEventCreate(&e1.e));
+  HIP_TRY(hipEventRecord(e0.e, 0));
+  std::vector<long long> h_mgr0((size_t)LEARN_MAX_PERIODS);
+  std::vector<int> h_sched((size_t)LEARN_MAX_PERIODS);
+  std::vector<int> worklist((size_t)x->wl_slots), wave_level((size_t)(x->wl_slots / ADV_WAVE));
+  const long long E = x->advance_every;
+  long long left = periods;
+  while (left > 0) {
+    if (x->j % E == 0) {  // an advance point
+      hipLaunchKernelGGL(k_ens_advance, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->mem, x->adv, x->rule, x->si, (long long)x->j, (int)DQL_CELLS_PER_LEVEL);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipDeviceSynchronize());
+    }
+    rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
+    if (unfinished == 0) { x->j += left; break; }  // nothing left to fly or to advance, now or later (the period index still advances by `periods`)
+    const long long to_point = E - x->j % E;
+    const int k = (int)(left < to_point ? left : to_point);  // <= advance_every <= LEARN_MAX_PERIODS
+    unsigned long long wl_faults = 0ull;
+    const int n_waves = build_worklist(frozen.data(), level.data(), x->n, worklist.data(), wave_level.data(), x->wl_slots, &wl_faults);
+    if (wl_faults) {
+      unsigned long long v = 0;
+      HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
+      v += wl_faults;
+      HIP_TRY(hipMemcpy(x->mem.faults, &v, sizeof(v), hipMemcpyHostToDevice));
+    }
+    if (n_waves > 0) {  // (nobody live: everyone unfinished waits for the next advance point)
+      fill_schedule(x->cfg, x->j, h_mgr0.data(), h_sched.data(), k);
+      HIP_TRY(hipMemcpy(x->d_mgr0, h_mgr0.data(), (size_t)k * sizeof(long long), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(x->d_sched, h_sched.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(x->d_worklist, worklist.data(), (size_t)n_waves * ADV_WAVE * sizeof(int), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(x->d_wave_level, wave_level.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
+      if (x->cfg.dtype == DQL_F32) ens_launch_levels<float>(x, k, n_waves); else ens_launch_levels<double>(x, k, n_waves);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipDeviceSynchronize());
+      x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += (long long)n_waves * k;
+    }
+    x->j += k; left -= k;
+  }
+  HIP_TRY(hipEventRecord(e1.e, 0));
+  HIP_TRY(hipEventSynchronize(e1.e));
+  float ms = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
+  x->last_ms = (double)ms;
+  return DQL_OK;
+}
 int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
   CHECK_ENS(x);
   if (periods < 1 || periods > (1ll << 40)) return fail(DQL_EINVAL, "dql_ensemble_run: periods must be in 1..2^40; nothing was launched");
   HIP_TRY(hipSetDevice(x->device));
+  if (x->advance_every) return ens_run_levels(x, periods);
   struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
   HIP_TRY(hipEventCreate(&e0.e)); HIP_TRY(hipEventCreate(&e1.e));
   HIP_TRY(hipEventRecord(e0.e, 0));
@@ -2864,6 +3045,7 @@ int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
     if (x->cfg.dtype == DQL_F32) ens_launch<float>(x, k); else ens_launch<double>(x, k);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
+    x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += ((x->n + 63) / 64) * k;
     x->j += k; left -= k;
   }
   HIP_TRY(hipEventRecord(e1.e, 0));
@@ -2872,6 +3054,94 @@ int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
   HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
   x->last_ms = (double)ms;
   return DQL_OK;
+}
+// ---- per-learner curriculum levels ----
+int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t advance_every, const double* ratios, int32_t advance_exhausted) {
+  CHECK_ENS(x);
+  if (advance_every < 0 || advance_every > ADV_MAX_EVERY) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_every must be in 0..4096 (0 turns the mode off); nothing was changed");
+  if (advance_every == 0) {
+    // the plain launch flies everyone at the config's level: switching off is refused while a learner stands on another one (dql_ensemble_set_level first)
+    if (x->advance_every) {
+      HIP_TRY(hipSetDevice(x->device));
+      HIP_TRY(hipDeviceSynchronize());
+      std::vector<int> lv((size_t)x->n);
+      HIP_TRY(hipMemcpy(lv.data(), x->adv.level, lv.size() * sizeof(int), hipMemcpyDeviceToHost));
+      for (int v : lv)
+        if (v != x->cfg.working_curriculum_step)
+          return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the mode cannot be switched off (advance_every = 0) while learners stand on different levels; call dql_ensemble_set_level first; nothing was changed");
+    }
+    x->advance_every = 0;
+    return DQL_OK;
+  }
+  if (!ratios) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: null ratios; nothing was changed");
+  for (int k = 0; k < DQL_MAX_LEVELS; ++k) if (!std::isfinite(ratios[k])) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the five transfer ratios must be finite; nothing was changed");
+  if (advance_exhausted != 0 && advance_exhausted != 1) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_exhausted must be 0 or 1; nothing was changed");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<int> level((size_t)x->n);
+  HIP_TRY(hipMemcpy(level.data(), x->adv.level, level.size() * sizeof(int), hipMemcpyDeviceToHost));
+  int top = 0;
+  for (int v : level) top = v > top ? v : top;
+  if (last_level < top || last_level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: last_level must lie between the learners' current level and 4; nothing was changed");
+  int rc = ens_upload_mdpk5(x); if (rc) return rc;
+  for (int k = 0; k < DQL_MAX_LEVELS; ++k) x->rule.ratios[k] = ratios[k];
+  x->rule.last_level = last_level; x->rule.advance_exhausted = advance_exhausted;
+  x->advance_every = advance_every;
+  return DQL_OK;
+}
+int dql_ensemble_set_level_schedules(dql_ensemble* x, int32_t level, const double* eps, int32_t n_eps, int32_t window, int32_t min_successes, int32_t max_episodes) {
+  CHECK_ENS(x);
+  if (level < 0 || level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: the level must be in 0..4");
+  if (!eps) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: null table");
+  if (n_eps < 1 || n_eps > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: the table length must be in 1..2^22");
+  if (window < 1 || window > DQL_ENSEMBLE_MAX_WINDOW) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: the promotion window must be in 1..128 (DQL_ENSEMBLE_MAX_WINDOW)");
+  if (min_successes < 1 || max_episodes < 1) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: min_successes and max_episodes must be positive");
+  for (int i = 0; i < n_eps; ++i) if (!(eps[i] >= 0.0 && eps[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: exploration rates must be in [0, 1]");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<uint32_t> thr((size_t)n_eps);
+  for (int i = 0; i < n_eps; ++i) thr[(size_t)i] = eps_threshold(eps[i]);
+  uint32_t* d_e = nullptr;
+  if (hipMalloc((void**)&d_e, (size_t)n_eps * sizeof(uint32_t)) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc failed");
+  LevelSched lv[DQL_MAX_LEVELS];
+  for (int k = 0; k < DQL_MAX_LEVELS; ++k) lv[k] = x->h_lv[k];
+  lv[level] = LevelSched{d_e, n_eps, window, min_successes, max_episodes};
+  if (hipMemcpy(d_e, thr.data(), (size_t)n_eps * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(x->d_lv, lv, sizeof(lv), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d_e);
+    return fail(DQL_EHIP, "hipMemcpy failed");
+  }
+  if (x->h_lv[level].eps_tab) (void)hipFree((void*)x->h_lv[level].eps_tab);
+  x->h_lv[level] = lv[level]; x->have_lv[level] = true;
+  return DQL_OK;
+}
+int dql_ensemble_get_levels(dql_ensemble* x, int32_t* level, int32_t* promoted_at, int32_t* episodes_at, int64_t* entered_period) {
+  CHECK_ENS(x);
+  if (!level || !promoted_at || !episodes_at || !entered_period) return fail(DQL_EINVAL, "dql_ensemble_get_levels: null array");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t n = (size_t)x->n;
+  HIP_TRY(hipMemcpy(level, x->adv.level, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(promoted_at, x->adv.promoted_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(episodes_at, x->adv.episodes_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(entered_period, x->adv.entered_period, (size_t)DQL_MAX_LEVELS * n * sizeof(long long), hipMemcpyDeviceToHost));
+  // the level a learner stands on has no history entry yet: its row shows the counters as they are
+  std::vector<int> promoted(n), lvl_eps(n);
+  HIP_TRY(hipMemcpy(promoted.data(), x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(lvl_eps.data(), x->mem.level_episodes, n * sizeof(int), hipMemcpyDeviceToHost));
+  for (size_t l = 0; l < n; ++l) {
+    const int k = level[l];
+    if (k < 0 || k >= DQL_MAX_LEVELS) continue;
+    promoted_at[(size_t)k * n + l] = promoted[l]; episodes_at[(size_t)k * n + l] = lvl_eps[l];
+  }
+  return DQL_OK;
+}
+int dql_ensemble_n_unfinished(dql_ensemble* x, int64_t* n) {
+  CHECK_ENS(x);
+  if (!n) return fail(DQL_EINVAL, "null pointer");
+  if (!x->advance_every) return dql_ensemble_n_live(x, n);
+  HIP_TRY(hipSetDevice(x->device));
+  std::vector<int> frozen, level, promoted;
+  return ens_fetch_levels(x, frozen, level, promoted, n);
 }
 int dql_ensemble_get_period_index(dql_ensemble* x, int64_t* j) {
   CHECK_ENS(x);
@@ -2978,6 +3248,12 @@ int dql_ensemble_score(dql_ensemble* x, const dql_config* eval_cfg, int64_t firs
   HIP_TRY(hipSetDevice(x->device));
   const size_t off = (size_t)first * DQL_N_CELLS;
   return score_run(eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, x->mem.qa + off, x->mem.qb + off, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
+}
+int dql_diag_ensemble_launches(dql_ensemble* x, int64_t* launches, int64_t* periods, int64_t* wave_periods) {
+  CHECK_ENS(x);
+  if (!launches || !periods || !wave_periods) return fail(DQL_EINVAL, "null pointer");
+  *launches = x->n_launches; *periods = x->launched_periods; *wave_periods = x->launched_wave_periods;
+  return DQL_OK;
 }
 int dql_diag_ensemble_last(dql_ensemble* x, double* run_ms) {
   CHECK_ENS(x);

@@ -21,6 +21,9 @@ from .config import CHECK_NAMES, DqlConfig, N_CELLS
 MAX_PERIODS_PER_LAUNCH = 4096  # include/dql.h DQL_ENSEMBLE_MAX_PERIODS
 MAX_WINDOW = 128               # DQL_ENSEMBLE_MAX_WINDOW
 MAX_LEARNERS = 1 << 20         # DQL_ENSEMBLE_MAX_LEARNERS
+MAX_LEVELS = 5
+MAX_ADVANCE_EVERY = 4096       # csrc/dql_advance.hpp ADV_MAX_EVERY
+REFERENCE_RATIOS = (1.0, 0.8172650252856599, 0.8211253690681617, 0.8257273369742982, 0.8311571820651724)  # Trainer.transfer_learning_ratio(k), k = 0 .. 4
 N_CODES = len(CHECK_NAMES)
 GOAL = CHECK_NAMES.index("TERMINAL_SUCCESS")
 STATE_REAL_FIELDS = ("cum_x", "reward", "px", "py", "pz", "vx", "vy", "vz", "mp_x", "mp_u", "qw", "qx", "qy", "qz", "pitch_sp")
@@ -121,6 +124,52 @@ class SequentialEnsemble:
 
     def rearm(self):
         _lib.check(self.lib.dql_ensemble_rearm(self._h))
+
+    # ---- per-learner curriculum levels (include/dql.h) ----
+    def set_curriculum(self, last_level: int = 4, advance_every: int = MAX_ADVANCE_EVERY, ratios=None, advance_exhausted: bool = True):
+        """Curriculum mode: at every period index that is a multiple of `advance_every`, a frozen learner below `last_level` that promoted (or ran out of
+        episodes, with `advance_exhausted`) transfers ITS finished level with `ratios[level]`, moves up a level and flies on.  advance_every = 0: mode off.
+        ratios: five transfer ratios, default the reference's."""
+        last_level, advance_every = int(last_level), int(advance_every)
+        if not 0 <= advance_every <= MAX_ADVANCE_EVERY:
+            raise ValueError(f"advance_every must be in 0..{MAX_ADVANCE_EVERY}")
+        r = np.ascontiguousarray(REFERENCE_RATIOS if ratios is None else ratios, dtype=np.float64).ravel()
+        if advance_every:
+            if not 0 <= last_level < MAX_LEVELS:
+                raise ValueError("last_level must be in 0..4")
+            if r.size != MAX_LEVELS or not np.isfinite(r).all():
+                raise ValueError("ratios must be five finite numbers")
+        _lib.check(self.lib.dql_ensemble_set_curriculum(self._h, last_level, advance_every, _p(r), 1 if advance_exhausted else 0))
+
+    def set_level_schedules(self, level: int, eps=None, window: int = 100, min_successes: Optional[int] = None, max_episodes: int = 50000):
+        """`set_schedules` without the learning rates, for the learners that stand on `level` in curriculum mode (eps default: the reference's for it)"""
+        level, window = int(level), int(window)
+        if not 0 <= level < MAX_LEVELS:
+            raise ValueError("level must be in 0..4")
+        e = exploration_rates(level) if eps is None else np.ascontiguousarray(eps, dtype=np.float64).ravel()
+        if not 1 <= window <= MAX_WINDOW:
+            raise ValueError(f"window must be in 1..{MAX_WINDOW}")
+        ms = min_successes_for(window) if min_successes is None else int(min_successes)
+        if ms < 1 or int(max_episodes) < 1:
+            raise ValueError("min_successes and max_episodes must be positive")
+        if e.size < 1:
+            raise ValueError("the eps table must not be empty")
+        _lib.check(self.lib.dql_ensemble_set_level_schedules(self._h, level, _p(e), e.size, window, ms, int(max_episodes)))
+
+    def levels(self):
+        """{"level": int32 [L], "promoted_at": int32 [5][L] (episode at level k at which the learner promoted, or -1), "episodes_at": int32 [5][L],
+        "entered_period": int64 [5][L] (or -1)}; the row of a learner's current level shows its counters as they stand"""
+        level = np.zeros(self.n, dtype=np.int32)
+        promoted_at, episodes_at = (np.zeros((MAX_LEVELS, self.n), dtype=np.int32) for _ in range(2))
+        entered = np.zeros((MAX_LEVELS, self.n), dtype=np.int64)
+        _lib.check(self.lib.dql_ensemble_get_levels(self._h, _p(level), _p(promoted_at), _p(episodes_at), _p(entered)))
+        return {"level": level, "promoted_at": promoted_at, "episodes_at": episodes_at, "entered_period": entered}
+
+    def n_unfinished(self) -> int:
+        """learners that still have something to fly or a level to advance to (curriculum mode off: `n_live`)"""
+        v = C.c_int64()
+        _lib.check(self.lib.dql_ensemble_n_unfinished(self._h, C.byref(v)))
+        return int(v.value)
 
     def transfer(self, k: int, ratio: float):
         """`DoubleQLearningAgent.transfer_learning` on every learner's tables (k = 0 wraps to the last level, B6)"""
@@ -275,3 +324,26 @@ def curriculum(ens: SequentialEnsemble, levels: int = 5, first_level: int = 0, r
         ratio = float(ratios[k]) if ratios is not None else float(Trainer.transfer_learning_ratio(me, k))
         ens.transfer(k, ratio)
     return history
+
+
+def curriculum_per_learner(ens: SequentialEnsemble, last_level: int = 4, advance_every: int = MAX_ADVANCE_EVERY, ratios=None, advance_exhausted: bool = True,
+                           max_episodes: Optional[int] = None, window: int = 100, success_rate: float = 0.96, chunk_periods: int = 16 * MAX_PERIODS_PER_LAUNCH,
+                           max_periods: Optional[int] = None, on_chunk=None):
+    """`curriculum` without the ensemble-wide barrier: every learner walks the levels by itself (`SequentialEnsemble.set_curriculum`).  The five levels get
+    the schedules `curriculum` gives them (`exploration_rates(k)`, `min_successes_for`, the reference's ratios), then the ensemble runs until nobody is
+    unfinished or `max_periods` are flown.  -> `ens.levels()` plus "periods", the periods run."""
+    ms = min_successes_for(window, success_rate)
+    budget = ens.max_episodes if max_episodes is None else int(max_episodes)
+    for k in range(MAX_LEVELS):
+        ens.set_level_schedules(k, exploration_rates(k), window, ms, budget)
+    ens.set_curriculum(last_level, advance_every, ratios, advance_exhausted)
+    flown = 0
+    while ens.n_unfinished() > 0 and (max_periods is None or flown < max_periods):
+        k = int(chunk_periods) if max_periods is None else min(int(chunk_periods), int(max_periods) - flown)
+        ens.run(k)
+        flown += k
+        if on_chunk is not None:
+            on_chunk(ens, flown)
+    out = ens.levels()
+    out["periods"] = flown
+    return out

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DQL_ABI_VERSION 6 /* 6: dql_agent_mirror_update_deferred / _complete; 5: tick replay operators (dql_*_run), measurement symbols moved to dql_diag.h as dql_diag_* */
+#define DQL_ABI_VERSION 6 /* 6: dql_agent_mirror_update_deferred / _complete (added since, without a new number: dql_ensemble_set_curriculum, _set_level_schedules, _get_levels, _n_unfinished); 5: tick replay operators (dql_*_run), measurement symbols moved to dql_diag.h as dql_diag_* */
 
 typedef enum dql_status {
   DQL_OK = 0,
@@ -551,6 +551,35 @@ int dql_ensemble_index_faults(dql_ensemble* ens, int64_t* n); /* updates dropped
  * windows and period index. */
 int dql_ensemble_score(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
                        uint64_t seed, int32_t max_steps, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null);
+
+/* ---- per-learner curriculum levels ----
+ * Every learner has its own working level (it starts at the config's working_curriculum_step; dql_ensemble_set_level sets everybody's and clears the history
+ * from that level on).  CURRICULUM MODE — off by default, and while it is off every call above behaves as described there — lets a learner walk the levels by
+ * itself.  At a period index j that is a multiple of advance_every, before period j is flown and nowhere else (dql_ensemble_run cuts its launches there),
+ * every frozen learner below last_level that promoted, or that ran out of episodes while advance_exhausted is 1, records its history entry, applies
+ * dql_ensemble_transfer's arithmetic for k = its finished level with ratios[k] to ITS OWN two tables (the k = 0 wrap included), moves up one level,
+ * re-enters through reset and has its per-level counters, window, promotion record and frozen flag cleared.  A learner frozen at last_level — or out of
+ * episodes with advance_exhausted 0 — is finished and never touched again.  Between advance points a learner flies as described above with ITS level's
+ * limits, exploration table, window, min_successes and max_episodes (dql_ensemble_set_level_schedules; the learning rates stay those of
+ * dql_ensemble_set_schedules); the RNG key stays (learner, seed).  Advance points depend on j only: two runs of a and b periods equal one run of a + b bit
+ * for bit, and a learner's whole history is independent of which other learners exist.  promoted / level_episodes of dql_ensemble_get_counters refer to
+ * each learner's current level.
+ * Refused with DQL_EINVAL, a message and no launch: advance_every outside 0..4096, last_level below a learner's current level or above 4, a ratio that is
+ * not finite, advance_exhausted other than 0 / 1, a level outside 0..4, schedule arguments dql_ensemble_set_schedules refuses, and dql_ensemble_run in
+ * curriculum mode before every level from the learners' up to last_level has its schedules (a learner's own level first, whatever last_level is); also
+ * dql_ensemble_set_level above last_level while the mode is on, and advance_every = 0 while learners stand on different levels (the plain launch flies
+ * everyone at the config's level: dql_ensemble_set_level first). */
+/* ratios double[5]: ratios[k] is applied when level k is finished; advance_every = 0 turns the mode off (the other arguments are then ignored) */
+int dql_ensemble_set_curriculum(dql_ensemble* ens, int32_t last_level, int32_t advance_every, const double* ratios, int32_t advance_exhausted);
+/* eps double[n_eps] per episode index within the level, window / min_successes / max_episodes as in dql_ensemble_set_schedules, for one level */
+int dql_ensemble_set_level_schedules(dql_ensemble* ens, int32_t level, const double* eps, int32_t n_eps, int32_t window, int32_t min_successes,
+                                     int32_t max_episodes);
+/* level int32[n]; per level k and learner: promoted_at int32[5][n] (episode at level k at which the window filled, or -1), episodes_at int32[5][n] (episodes
+ * spent at level k), entered_period int64[5][n] (period index at which level k was entered, or -1).  The row of a learner's current level shows its counters
+ * as they stand. */
+int dql_ensemble_get_levels(dql_ensemble* ens, int32_t* level, int32_t* promoted_at, int32_t* episodes_at, int64_t* entered_period);
+/* learners that still have something to fly or a level to advance to; with the mode off: dql_ensemble_n_live */
+int dql_ensemble_n_unfinished(dql_ensemble* ens, int64_t* n);
 
 #ifdef __cplusplus
 }

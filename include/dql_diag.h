@@ -41,6 +41,9 @@ int dql_diag_score_last(double* kernel_ms, int32_t* inst3);
 
 /* wall duration on the device (HIP events around all launches) of the ensemble's latest completed dql_ensemble_run */
 int dql_diag_ensemble_last(dql_ensemble* ens, double* run_ms);
+/* since the ensemble's creation: k_learn / k_learn_levels launches, their agent periods summed, and waves x periods summed (what a launch may fly at most:
+ * a wave leaves its loop once none of its lanes is live) */
+int dql_diag_ensemble_launches(dql_ensemble* ens, int64_t* launches, int64_t* periods, int64_t* wave_periods);
 
 /* ---- self-test ---- */
 /* The float32 tick's square root (csrc/dql_device.hpp sqrt_pos: v_rsq_f32 + one residual correction; until the end of round 5 with a Goldschmidt step in between): counts the inputs with bit

@@ -3,12 +3,17 @@
 one learner per GPU lane (dql_multirotor_landing_amd/ensemble.py).
 
     python scripts/ensemble_training.py --learners 4096 --seed 42 [--launched] [--levels 5] [--episodes 50000] [--score ENVS] --out run.npz
+                                        [--per-learner [--advance-every E] [--drop-exhausted]]
 
 --launched: the parameters the reference's manager node ran with under roslaunch (config.as_launched_config) instead of the launch file's.
 --score ENVS: after the curriculum, fly every learner's tables greedily where they live (SequentialEnsemble.landing_rates: ENVS envs per learner and flavour,
 two launches), store `touchdown_rate` and `goal_hold_rate` in the .npz and print the share of learners at or above the acceptance bar of attempts.py (0.875
 touchdowns), with the figures of the reference's published tables from the same call of `evaluation.landing_rates` (same envs, seed and episodes) beside it.
-Writes every learner's tables and, per level, its first-promotion episode (-1: the episode budget ran out first)."""
+--per-learner: every learner walks the levels by itself (ensemble.curriculum_per_learner) instead of waiting at each level for the slowest
+learner of the ensemble; a learner advances at the next period index that is a multiple of E (--advance-every, default 4096); --drop-exhausted: a learner whose
+episode budget ran out stays where it is instead of advancing as the reference's loop does.
+Writes every learner's tables and, per level, its first-promotion episode (-1: the episode budget ran out first); with --per-learner also each learner's level,
+the episodes it spent at each level and the period index at which it entered it."""
 import argparse
 import json
 import sys
@@ -20,7 +25,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from dql_multirotor_landing_amd.config import F32, F64, Q_REFERENCE, as_launched_config, training_config  # noqa: E402
 from dql_multirotor_landing_amd import evaluation  # noqa: E402
-from dql_multirotor_landing_amd.ensemble import SequentialEnsemble, curriculum  # noqa: E402
+from dql_multirotor_landing_amd.ensemble import SequentialEnsemble, curriculum, curriculum_per_learner  # noqa: E402
 
 
 def rate_summary(x):
@@ -63,6 +68,9 @@ def main():
     ap.add_argument("--score-seed", type=int, default=123)
     ap.add_argument("--reference-tables", default=str(ROOT / "tests" / "golden" / "assets"), help="directory with the reference's Q_table_a.npy / Q_table_b.npy")
     ap.add_argument("--score-json", default=None, help="also write the scoring report to this file")
+    ap.add_argument("--per-learner", action="store_true", help="every learner advances through the levels by itself")
+    ap.add_argument("--advance-every", type=int, default=4096, metavar="E", help="with --per-learner: learners advance at the period indices that are multiples of E (1..4096)")
+    ap.add_argument("--drop-exhausted", action="store_true", help="with --per-learner: a learner out of episodes stays frozen instead of advancing")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     dtype = F64 if a.f64 else F32
@@ -73,11 +81,20 @@ def main():
             p = h["promotion_episode"]
             print(json.dumps({"level": h["level"], "periods": h["periods"], "promoted": int((p >= 0).sum()), "of": int(p.size),
                               "median_promotion_episode": None if not (p >= 0).any() else int(np.median(p[p >= 0]))}), flush=True)
-        hist = curriculum(ens, levels=a.levels, max_episodes=a.episodes, on_level=report)
         extra = {}
+        if a.per_learner:
+            def progress(e, flown):
+                lv = e.levels()["level"]
+                print(json.dumps({"periods": flown, "unfinished": e.n_unfinished(), "learners_per_level": np.bincount(lv, minlength=5).tolist()}), flush=True)
+            h = curriculum_per_learner(ens, last_level=a.levels - 1, advance_every=a.advance_every, advance_exhausted=not a.drop_exhausted, max_episodes=a.episodes,
+                                       on_chunk=progress)
+            hist = [{"promotion_episode": h["promoted_at"][k], "periods": h["periods"]} for k in range(a.levels)]
+            extra = {"level": h["level"], "episodes_at": h["episodes_at"], "entered_period": h["entered_period"]}
+        else:
+            hist = curriculum(ens, levels=a.levels, max_episodes=a.episodes, on_level=report)
         if a.score:
             rep, td, gh = score_report(ens, a)
-            extra = {"touchdown_rate": td, "goal_hold_rate": gh}
+            extra.update({"touchdown_rate": td, "goal_hold_rate": gh})
             print(json.dumps(rep), flush=True)
             ref = rep["reference_tables"]
             print(f"{rep['learners_at_or_above_bar']} of {rep['learners']} learners ({100.0 * rep['share_at_or_above_bar']:.1f} %) reach a touchdown rate of "

@@ -1,0 +1,180 @@
+"""Per-learner curriculum levels on the CPU: csrc/dql_advance.hpp's worklist and advance step, with csrc/dql_learner.hpp's
+learner_periods, held `==` to the yardstick of tests/advance_checks.py (CPU only, no GPU).
+
+tests/host_emu/advance_emu.cpp compiles the real headers as host C++ and does what dql_ensemble_run does in curriculum mode: advance at the multiples of E,
+worklist, wave by wave.  It is a stand-alone program run as its own process, built twice: plain, and with ASan + UBSan (any report fails).  The cases are those
+of tests/test_gpu_ensemble_advance.py; the sanitized build flies the first 24 learners for 384 periods."""
+import os
+import struct
+import subprocess
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+from dql_multirotor_landing_amd import ensemble
+from dql_multirotor_landing_amd.config import F32, F64, N_CELLS
+from dql_multirotor_landing_amd.ensemble import SequentialEnsemble
+
+import advance_checks as ac
+import ensemble_checks as ec
+from test_learner_host_emulation import CSRC, EMU, PLAIN_FLAGS, SAN_ENV, SAN_FLAGS, SAN_MARKERS, _clangxx
+
+CASE = ac.CASE
+CELLS_PER_LEVEL = N_CELLS // 5
+SHORT = 384
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    out = tmp_path_factory.mktemp("advance_emu")
+    cxx = _clangxx()
+    common = ["-I", str(EMU), "-I", str(CSRC), "-Wno-pass-failed", str(EMU / "advance_emu.cpp")]
+    builds = {"plain": PLAIN_FLAGS, "san": SAN_FLAGS}
+
+    def build(kind):
+        exe = out / f"advance_emu_{kind}"
+        r = subprocess.run([cxx, *builds[kind], *common, "-o", str(exe)], capture_output=True, text=True)
+        assert r.returncode == 0, f"{kind} build of advance_emu failed:\n{r.stderr[-4000:]}"
+        return exe
+
+    with ThreadPoolExecutor(2) as ex:
+        return dict(zip(builds, ex.map(build, builds)))
+
+
+def run_emu(exe, tmp, runs, n=None, dtype=F32, sanitized=False, **over):
+    c = dict(CASE, **over)
+    n = c["n"] if n is None else n
+    cfg = ac.level0(dtype)
+    cb = bytes(cfg.to_c())
+    alpha = cfg.alpha_table()
+    sch = ac.case_schedules(c)
+    r8 = list(runs) + [0] * (8 - len(runs))
+    hdr = [len(cb), cfg.dtype, n, len(runs), *r8, len(alpha), c["E"], c["last_level"], int(c.get("advance_exhausted", True)), c["log_capacity"]]
+    for s in sch:
+        hdr += [len(s["eps"]), s["window"], s["min_successes"], s["max_episodes"]]
+    hdr += [0] * (40 - len(hdr))
+    job, res = tmp / "advance_job.bin", tmp / "advance_res.bin"
+    job.write_bytes(struct.pack("<40i", *hdr) + struct.pack("<q", c["seed"]) + cb + np.asarray(ensemble.REFERENCE_RATIOS, np.float64).tobytes() + alpha.tobytes()
+                    + b"".join(np.asarray(s["eps"], np.float64).tobytes() for s in sch))
+    env = dict(os.environ, **SAN_ENV) if sanitized else None
+    r = subprocess.run([str(exe), str(job), str(res)], capture_output=True, text=True, env=env, timeout=1800)
+    assert r.returncode == 0, f"advance_emu ({'sanitized' if sanitized else 'plain'}) failed:\n{r.stderr[-6000:]}"
+    assert not any(m in r.stderr for m in SAN_MARKERS), f"sanitizer report:\n{r.stderr[-6000:]}"
+    b = res.read_bytes()
+    o = 0
+
+    def take(dt, shape):
+        nonlocal o
+        a = np.frombuffer(b, dt, int(np.prod(shape)), o).reshape(shape)
+        o += a.nbytes
+        return a
+
+    cap = c["log_capacity"]
+    out = {"qa": take(np.float64, (n, N_CELLS)), "qb": take(np.float64, (n, N_CELLS)), "count": take(np.float64, (n, N_CELLS)),
+           "decisions": take(np.int64, (n,)), "by_code": take(np.int64, (ec.N_CODES, n)), "episodes": take(np.int32, (n,)), "successes": take(np.int32, (n,)),
+           "level_episodes": take(np.int32, (n,)), "promotion_episode": take(np.int32, (n,)), "frozen": take(np.int32, (n,)), "log_n": take(np.int32, (n,)),
+           "log_code": take(np.uint8, (n, cap)), "log_len": take(np.uint16, (n, cap))}
+    reals, ints = take(np.float64, (64, n)), take(np.int32, (7, n))
+    faults = take(np.int64, (1,))
+    out.update({"level": take(np.int32, (n,)), "promoted_at": take(np.int32, (5, n)), "episodes_at": take(np.int32, (5, n)), "entered_period": take(np.int64, (5, n))})
+    j = int(take(np.int64, (1,))[0])
+    assert o == len(b)
+    assert faults[0] == 0, "a range check counted a fault"
+    assert j == sum(runs)
+    ref = ec.Reference(cfg, 1, 0)
+    out.update({f: reals[k] for f, k in ref.ri.items()})
+    out.update({f: ints[k] for f, k in ref.ii.items()})
+    return out
+
+
+@pytest.fixture(scope="module")
+def yard():
+    y = ac.case_yardstick()
+    ac.assert_case_conditions(y)
+    return y, y.result()
+
+
+@pytest.fixture(scope="module")
+def main(emu, tmp_path_factory):
+    return run_emu(emu["plain"], tmp_path_factory.mktemp("advance_main"), (CASE["periods"],))
+
+
+def test_python_argument_checks_come_before_the_library_is_touched():
+    class Untouchable:
+        def __getattr__(self, name):
+            raise AssertionError(f"the library was touched: {name}")
+
+    ens = object.__new__(SequentialEnsemble)
+    ens.n, ens.lib, ens._h = 8, Untouchable(), None
+    for bad in (dict(advance_every=-1), dict(advance_every=4097), dict(last_level=5), dict(last_level=-1), dict(ratios=[1.0] * 4), dict(ratios=[1.0, np.nan, 1.0, 1.0, 1.0]),
+                dict(ratios=[1.0, 1.0, np.inf, 1.0, 1.0])):
+        with pytest.raises(ValueError):
+            ens.set_curriculum(**{"last_level": 4, "advance_every": 64, **bad})
+    for bad in (dict(level=-1), dict(level=5), dict(window=0), dict(window=129), dict(min_successes=0), dict(max_episodes=0), dict(eps=[])):
+        with pytest.raises(ValueError):
+            ens.set_level_schedules(**{"level": 1, "eps": [0.0], "window": 4, "min_successes": 3, "max_episodes": 6, **bad})
+    ens._h = None  # (nothing to close)
+
+
+def test_whole_run_equals_the_yardstick_f32(yard, main):
+    ac.assert_equal(main, yard[1], "run(1024), float32")
+
+
+def test_whole_run_equals_the_yardstick_f64(emu, tmp_path):
+    y = ac.case_yardstick(dtype=F64, n=ac.SMALL, periods=SHORT)
+    want = y.result()
+    assert len(set(want["level"].tolist())) >= 3 and y.advanced_exhausted >= 1
+    ac.assert_equal(run_emu(emu["plain"], tmp_path, (SHORT,), n=ac.SMALL, dtype=F64), want, "run(384), float64")
+
+
+@pytest.mark.parametrize("runs", [(7, 1017), (7, 100, 917), (64, 1, 63, 896)], ids=lambda r: "+".join(map(str, r)))
+def test_splits_equal_one_run(emu, main, runs, tmp_path):
+    assert sum(runs) == CASE["periods"]
+    ac.assert_equal(run_emu(emu["plain"], tmp_path, runs), main, f"runs {runs} against run(1024)")
+
+
+def test_first_24_learners_do_not_depend_on_the_other_56(emu, main, tmp_path):
+    first = list(range(ac.SMALL))
+    ac.assert_equal(main, run_emu(emu["plain"], tmp_path, (CASE["periods"],), n=ac.SMALL), "L = 80 against L = 24", learners=(first, first))
+
+
+def test_exhausted_learners_stay_where_they_froze_when_they_do_not_advance(emu, tmp_path):
+    y = ac.case_yardstick(advance_exhausted=False)
+    want = y.result()
+    assert y.advanced_exhausted == 0 and y.advanced_promoted >= 1 and y.n_unfinished() == 0 and (want["level"] == 1).any()
+    got = run_emu(emu["plain"], tmp_path, (CASE["periods"],), advance_exhausted=False)
+    ac.assert_equal(got, want, "advance_exhausted = 0")
+    again = run_emu(emu["plain"], tmp_path, (CASE["periods"], 3, 200), advance_exhausted=False)
+    ac.assert_equal(again, got, "run(3); run(200) with everyone finished")
+
+
+def test_last_level_2_is_never_exceeded(emu, main, tmp_path):
+    got = run_emu(emu["plain"], tmp_path, (CASE["periods"],), last_level=2)
+    assert got["level"].max() == 2 and (got["frozen"].astype(bool) & (got["level"] == 2)).any() and (got["entered_period"][3:] == -1).all()
+    for t in ("qa", "qb", "count"):
+        assert not got[t][:, 3 * CELLS_PER_LEVEL:].any(), f"{t}: cells of levels 3 and 4 were written"
+    # a learner's way up to level 2 does not depend on where the curriculum ends
+    assert np.array_equal(got["entered_period"][:3], main["entered_period"][:3]) and (got["entered_period"][2] >= 0).any()
+    assert np.array_equal(got["promoted_at"][:2], main["promoted_at"][:2]) and np.array_equal(got["episodes_at"][:2], main["episodes_at"][:2])
+
+
+def test_ring_is_cleared_on_advance(emu, tmp_path):
+    """`advance_checks.RING_CASE`: one success promotes above level 0, and learners arrive there with level-0 successes in their ring"""
+    y = ac.case_yardstick(**ac.RING_CASE)
+    want = y.result()
+    ac.assert_ring_case_conditions(y, want)
+    ac.assert_equal(run_emu(emu["plain"], tmp_path, (7, ac.RING_CASE["periods"] - 7), **ac.RING_CASE), want, "the ring case")
+
+
+@pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
+def test_clean_under_asan_and_ubsan(emu, yard, dtype, tmp_path):
+    """the first 24 learners, 7 + 377 periods, through the sanitized build; float32 against the first 24 of the yardstick's 80 (a learner does not depend on the others)"""
+    first = list(range(ac.SMALL))
+    got = run_emu(emu["san"], tmp_path, (7, SHORT - 7), n=ac.SMALL, dtype=dtype, sanitized=True)
+    if dtype == F32:
+        y = ac.case_yardstick(n=ac.SMALL, periods=SHORT)
+    else:
+        y = ac.case_yardstick(dtype=F64, n=ac.SMALL, periods=SHORT)
+    assert y.advanced_exhausted >= 1 and len(set(y.level.tolist())) >= 3
+    ac.assert_equal(got, y.result(), f"sanitized, dtype {dtype}", learners=(first, first))
