@@ -20,12 +20,14 @@ from oracle.oracle import Oracle
 import ensemble_checks as ec
 
 LEVELS = 5
+CELLS_PER_LEVEL = N_CELLS // LEVELS
 HISTORY = ("level", "promoted_at", "episodes_at", "entered_period")
 
 
 class Yardstick:
-    def __init__(self, cfg, n, seed, schedules, ratios, last_level, advance_every, advance_exhausted=True, log_capacity=64):
-        """schedules: per level 0..4 a dict(eps=, window=, min_successes=, max_episodes=); cfg: the config of the starting level"""
+    def __init__(self, cfg, n, seed, schedules, ratios, last_level, advance_every, advance_exhausted=True, log_capacity=64, tables=None):
+        """schedules: per level 0..4 a dict(eps=, window=, min_successes=, max_episodes=); cfg: the config of the starting level; tables: initial (qa, qb,
+        count), [n][N_CELLS] each (copied), default zeros"""
         self.cfg, self.n, self.seed = cfg, int(n), int(seed)
         self.start = int(cfg.working_curriculum_step)
         self.os = []
@@ -35,7 +37,7 @@ class Yardstick:
             self.os.append(Oracle(c, self.n, seed=self.seed))
         self.sched = [dict(thr=[ec.eps_thr(e) for e in s["eps"]], W=int(s["window"]), ms=int(s["min_successes"]), me=int(s["max_episodes"])) for s in schedules]
         self.ratios, self.last_level, self.E, self.advance_exhausted = [float(r) for r in ratios], int(last_level), int(advance_every), bool(advance_exhausted)
-        self.qa, self.qb, self.cnt = (np.zeros((self.n, N_CELLS)) for _ in range(3))
+        self.qa, self.qb, self.cnt = (np.zeros((self.n, N_CELLS)) for _ in range(3)) if tables is None else (np.array(t, np.float64).reshape(self.n, N_CELLS) for t in tables)
         self.alpha = cfg.alpha_table()
         self.cap = int(log_capacity)
         self.j = 0
@@ -61,6 +63,12 @@ class Yardstick:
         # what the case's conditions are asserted on: per launch (period index, live learners per level, learners per level), and who advanced how
         self.launches = []
         self.advanced_promoted, self.advanced_exhausted = 0, 0
+        self.promoted_from, self.exhausted_from = np.zeros(LEVELS, np.int64), np.zeros(LEVELS, np.int64)  # advances by the level they left
+        self.wrap_sources = []       # per advance from level 0: (level-4 block of qa has a non-zero cell, the same of qb) before the transfer
+        self.qb_blocks_moved = 0     # transfers whose source block of qb has a non-zero cell
+        self.arrived_promoted = {}   # learner -> the level it promoted from, until its first episode at the next level ends
+        self.first_failed_after_promotion = np.zeros(LEVELS, np.int64)  # by the level promoted from: that first episode was no success
+        self.finished_by_promotion_beside_lower = 0  # learners that promoted at the last level while another learner stood below it
 
     def _slot(self, l):
         return slice(l * self.es, (l + 1) * self.es)
@@ -89,9 +97,13 @@ class Yardstick:
             if self.promoted[l] < 0 and not self.advance_exhausted:
                 continue
             if self.promoted[l] >= 0:
-                self.advanced_promoted += 1
+                self.advanced_promoted += 1; self.promoted_from[k] += 1; self.arrived_promoted[l] = k
             else:
-                self.advanced_exhausted += 1
+                self.advanced_exhausted += 1; self.exhausted_from[k] += 1; self.arrived_promoted.pop(l, None)
+            src = slice(((k - 1) % LEVELS) * CELLS_PER_LEVEL, ((k - 1) % LEVELS + 1) * CELLS_PER_LEVEL)
+            if k == 0:
+                self.wrap_sources.append((bool(self.qa[l][src].any()), bool(self.qb[l][src].any())))
+            self.qb_blocks_moved += bool(self.qb[l][src].any())
             self.promoted_at[k][l] = self.promoted[l]; self.episodes_at[k][l] = self.level_episodes[l]
             orc.transfer(self.qa[l], self.qb[l], k, self.ratios[k])
             b = np.ascontiguousarray(self.snap.pop(l)).copy()
@@ -152,8 +164,11 @@ class Yardstick:
                         self.log_code[l][self.log_n[l]] = code; self.log_len[l][self.log_n[l]] = int(ints[i_sc][l])
                     self.log_n[l] += 1
                     self.windows[l].append(int(code == ec.GOAL)); self.level_episodes[l] += 1
+                    if l in self.arrived_promoted:
+                        self.first_failed_after_promotion[self.arrived_promoted.pop(l)] += code != ec.GOAL
                     if sum(self.windows[l]) >= self.sched[k]["ms"]:
                         self.promoted[l] = self.level_episodes[l]; self.frozen[l] = True
+                        self.finished_by_promotion_beside_lower += k == self.last_level and bool((self.level < self.last_level).any())
                     elif self.level_episodes[l] >= self.sched[k]["me"]:
                         self.frozen[l] = True
                     if self.frozen[l]:
@@ -208,23 +223,63 @@ SMALL = 24  # the first learners of the case as an ensemble of their own (and th
 RING_CASE = dict(CASE, n=SMALL, periods=768, max_episodes=(6, 3, 3, 3, 3), min_successes=(None, 1, 1, 1, 1))
 
 
+# Two cases that start from TRAINED tables (`ensemble_checks.trained_tables`: the reference's stage-4 tables, perturbed per learner, the stored visit counts):
+# greedy at every level, learners land, so they promote through the ring above level 0, the transfer moves non-zero blocks of BOTH tables, and the k = 0 wrap
+# reads a level-4 block that is not zero.  TRAINED_CASE's ratios are not the reference's and hold no 1.0, so every ratio shows in the tables, ratios[0]
+# included.  E = 32: 32 advance points in 1 024 periods; 80 learners are two waves at level 0.  Quirks 0x7f (table A alone is updated, learners also run out of
+# episodes) or 0x40 (the coin: both tables are updated).
+TRAINED_RATIOS = (0.75, 0.5, 1.25, 0.625, 0.875)
+TRAINED_CASE = dict(n=80, seed=11, E=32, periods=1024, window=2, min_successes=(1,) * 5, max_episodes=(3,) * 5, eps=((0.0,),) * 5, last_level=4, log_capacity=64,
+                    start_level=0, quirks=ec.Q_REFERENCE, ratios=TRAINED_RATIOS, trained=True)
+TRAINED_CASE_PAPER = dict(TRAINED_CASE, quirks=ec.Q_PAPER)
+# An ensemble CREATED at level 3 (the config's level is the starting level), the reference's ratios: someone finishes at level 4 by promotion while others are
+# still at level 3 (settled on the yardstick: the first learner to do so promotes at level 4 between periods 1 024 and 1 280).
+TRAINED_FROM_3 = dict(TRAINED_CASE, n=SMALL, periods=1280, window=4, min_successes=(2,) * 5, max_episodes=(6,) * 5, start_level=3, ratios=ensemble.REFERENCE_RATIOS)
+
+
 def level0(dtype=F32):
     return training_config(0, quirks=ec.Q_REFERENCE, dtype=dtype)
 
 
+def case_config(case=CASE, dtype=F32):
+    """the config of the case's starting level with the case's quirks (default: level 0, the reference's quirks)"""
+    return training_config(case.get("start_level", 0), quirks=case.get("quirks", ec.Q_REFERENCE), dtype=dtype)
+
+
+def case_ratios(case=CASE):
+    return tuple(case.get("ratios", ensemble.REFERENCE_RATIOS))
+
+
+def case_tables(case, n):
+    """the case's initial (qa, qb, count) for n learners, or None where it starts from zeros"""
+    return ec.trained_tables(n) if case.get("trained") else None
+
+
 def case_schedules(case=CASE):
-    ms = ensemble.min_successes_for(case["window"], case["success_rate"])
     own = case.get("min_successes", (None,) * LEVELS)  # a level's own figure where the case names one
-    return [dict(eps=ensemble.exploration_rates(k), window=case["window"], min_successes=ms if own[k] is None else own[k], max_episodes=case["max_episodes"][k])
-            for k in range(LEVELS)]
+    ms = None if all(m is not None for m in own) else ensemble.min_successes_for(case["window"], case["success_rate"])
+    eps = case.get("eps", (None,) * LEVELS)  # a level's own exploration table where the case names one
+    return [dict(eps=ensemble.exploration_rates(k) if eps[k] is None else np.asarray(eps[k], np.float64), window=case["window"],
+                 min_successes=ms if own[k] is None else own[k], max_episodes=case["max_episodes"][k]) for k in range(LEVELS)]
 
 
-def case_yardstick(dtype=F32, n=None, periods=None, **over):
-    """the yardstick flown through the case; -> the Yardstick (its result(), launches and advance counts)"""
+def case_yardstick(dtype=F32, n=None, periods=None, checkpoint_every=None, **over):
+    """the yardstick flown through the case; -> the Yardstick (its result(), launches and advance counts).  checkpoint_every: fly in runs of that many periods
+    and keep, after each, (period index, n_unfinished(), what `SequentialEnsemble.levels()` shows) in `y.checkpoints`"""
     c = dict(CASE, **over)
-    y = Yardstick(level0(dtype), c["n"] if n is None else n, c["seed"], case_schedules(c), ensemble.REFERENCE_RATIOS, c["last_level"], c["E"],
-                  c.get("advance_exhausted", True), c["log_capacity"])
-    y.run(c["periods"] if periods is None else periods)
+    n = c["n"] if n is None else n
+    y = Yardstick(case_config(c, dtype), n, c["seed"], case_schedules(c), case_ratios(c), c["last_level"], c["E"], c.get("advance_exhausted", True),
+                  c["log_capacity"], tables=case_tables(c, n))
+    periods = c["periods"] if periods is None else periods
+    if checkpoint_every is None:
+        y.run(periods)
+        return y
+    assert periods % checkpoint_every == 0
+    y.checkpoints = []
+    for _ in range(periods // checkpoint_every):
+        y.run(checkpoint_every)
+        r = y.result()
+        y.checkpoints.append((y.j, y.n_unfinished(), {k: r[k] for k in ("level",) + HISTORY[1:]}))
     return y
 
 
@@ -232,10 +287,14 @@ def case_ensemble(n=None, dtype=F32, **over):
     """a SequentialEnsemble set up for the case (curriculum mode on), not yet run"""
     from dql_multirotor_landing_amd.ensemble import SequentialEnsemble
     c = dict(CASE, **over)
-    ens = SequentialEnsemble(level0(dtype), c["n"] if n is None else n, seed=c["seed"], log_capacity=c["log_capacity"])
+    n = c["n"] if n is None else n
+    ens = SequentialEnsemble(case_config(c, dtype), n, seed=c["seed"], log_capacity=c["log_capacity"])
     for k, s in enumerate(case_schedules(c)):
         ens.set_level_schedules(k, s["eps"], s["window"], s["min_successes"], s["max_episodes"])
-    ens.set_curriculum(c["last_level"], c["E"], ensemble.REFERENCE_RATIOS, c.get("advance_exhausted", True))
+    ens.set_curriculum(c["last_level"], c["E"], case_ratios(c), c.get("advance_exhausted", True))
+    tables = case_tables(c, n)
+    if tables is not None:
+        ens.set_tables(*tables)
     return ens
 
 
@@ -266,3 +325,29 @@ def assert_ring_case_conditions(y, want):
     assert y.advanced_promoted >= 1 and (up & (want["promoted_at"][0] < 0) & (want["successes"] >= 1)).any(), "nobody carries successes into level 1"
     assert (want["episodes_at"][1][want["level"] >= 2] == 3).all() and (want["level"] >= 2).any(), "a learner left level 1 before its budget ran out"
     assert (want["promoted_at"][1:] == -1).all()
+
+
+def assert_trained_case_conditions(y, case):
+    """what TRAINED_CASE / TRAINED_FROM_3 are for, asserted ON THE YARDSTICK before an ensemble or an emulation is looked at"""
+    start = int(case.get("start_level", 0))
+    print("promoted advances by level left", y.promoted_from.tolist(), "exhausted", y.exhausted_from.tolist(), "levels at the end", np.bincount(y.level, minlength=LEVELS).tolist(),
+          "advances from level 0 (qa, qb level-4 block non-zero)", len(y.wrap_sources), "transfers of a non-zero qb block", y.qb_blocks_moved,
+          "failed first episodes after a promotion, by level left", y.first_failed_after_promotion.tolist(), "promoted at the last level beside lower learners",
+          y.finished_by_promotion_beside_lower, "unfinished", y.n_unfinished())
+    assert len(set(case_ratios(case))) == LEVELS or start > 0, "two levels share a ratio: one taken for the other would not show"
+    if start == 0:
+        assert 1.0 not in case_ratios(case), "a ratio of 1.0 does not show in the tables"
+        assert y.promoted_from[0] >= 1 and (y.promoted_from[1:] > 0).sum() >= 2, "promoted advances at level 0 and at two levels above it are needed"
+        assert y.wrap_sources and all(a and b for a, b in y.wrap_sources), "an advance from level 0 reads a level-4 block of zeros"
+    else:
+        assert y.promoted_from[start] >= 1 and not y.promoted_from[:start].any() and (y.entered_period[:start] == -1).all()
+    assert y.qb_blocks_moved >= 1, "no transfer moves a non-zero block of Q_table_b"
+    assert y.first_failed_after_promotion[1:].sum() >= 1, "no promoted advance from a level >= 1 is followed by a failed first episode: an uncleared ring would not show"
+    assert y.finished_by_promotion_beside_lower >= 1, "nobody finishes at the last level by promotion while others are below it"
+    if case["quirks"] == ec.Q_REFERENCE:
+        assert y.advanced_exhausted >= 1 and y.advanced_promoted >= 1, "both ways of advancing are needed"
+    else:
+        assert (y.qb != case_tables(case, y.n)[1])[:, start * CELLS_PER_LEVEL:(start + 1) * CELLS_PER_LEVEL].any(), "the coin never picked Q_table_b"
+    if y.n > 64:
+        assert any(c > 64 for _, live, _ in y.launches for c in live), "no level ever holds more than 64 live learners (two waves of one level)"
+        assert any(c % 64 != 0 for _, live, _ in y.launches for c in live), "no padded segment"

@@ -6,6 +6,7 @@ the update from `oracle.agent_update(..., coin=, done=)` with alpha at the pre-i
 learner's env is put back to its bytes at the freeze point after every oracle step (the oracle steps all L envs), so it is untouched until re-armed."""
 import math
 from collections import deque
+from pathlib import Path
 
 import numpy as np
 
@@ -26,16 +27,54 @@ def eps_thr(eps):
     return 0 if not eps > 0.0 else min(int(math.ceil(eps * 16777216.0)), 16777216)
 
 
+# ---- trained starting tables: the reference's stage-4 tables (tests/golden/assets), every learner with its own small perturbation ----
+GOLDEN_ASSETS = Path(__file__).resolve().parent / "golden" / "assets"
+TRAINED_SEED, TRAINED_NOISE = 5, 0.01
+
+
+def trained_tables(n):
+    """(qa, qb, count), float64 [n][N_CELLS]: learner l starts from Q * (1 + TRAINED_NOISE * N(0, 1)) per cell, the visit counts as stored (up to 1 955, beyond
+    the learning-rate table of 1 536 entries).  The noise is drawn [learner][table][cell], so learner l's tables do not depend on n."""
+    qa, qb, cnt = (np.load(GOLDEN_ASSETS / f).ravel().astype(np.float64) for f in ("Q_table_a.npy", "Q_table_b.npy", "state_action_count.npy"))
+    assert qa.size == qb.size == cnt.size == N_CELLS
+    z = np.random.default_rng(TRAINED_SEED).standard_normal((int(n), 2, N_CELLS))
+    return qa * (1.0 + TRAINED_NOISE * z[:, 0]), qb * (1.0 + TRAINED_NOISE * z[:, 1]), np.tile(cnt, (int(n), 1))
+
+
+# ---- plain learners from trained tables (tests/test_gpu_ensemble.py and tests/test_learner_host_emulation.py): greedy, window 4, 2 successes, 6 episodes ----
+TRAINED_LEARNERS_CASE = dict(eps=[0.0], window=4, min_successes=2, max_episodes=6, log_capacity=32)
+TRAINED_LEARNERS_SEED, TRAINED_LEARNERS_PERIODS, TRAINED_LEARNERS_SPLIT = 11, 400, (7, 393)
+
+
+def trained_reference(cfg, n):
+    """the result of the reference loop flown from `trained_tables(n)` at the config's level, after asserting ON IT what the case is for"""
+    tables = trained_tables(n)
+    ref = Reference(cfg, n, TRAINED_LEARNERS_SEED, tables=tables, **TRAINED_LEARNERS_CASE)
+    ref.run(TRAINED_LEARNERS_PERIODS)
+    want = ref.result()
+    promoted, failures = want["promotion_episode"] >= 0, int((want["episodes"] - want["successes"]).sum())
+    print(f"level {cfg.working_curriculum_step} quirks {cfg.quirks:#x}: promoted", int(promoted.sum()), "of", n, "live", int((~want["frozen"]).sum()), "successes", int(want["successes"].sum()),
+          "failures", failures, "cells written a / b", int((want["qa"] != tables[0]).sum()), int((want["qb"] != tables[1]).sum()), "updates inside / beyond the learning-rate table",
+          ref.updates_inside, ref.updates_beyond, "same-state periods", ref.same_state)
+    assert cfg.working_curriculum_step >= 1 and promoted.any() and not want["frozen"].all(), "a learner promoting through the ring above level 0 and a live one are needed"
+    assert want["successes"].sum() >= 1 and failures >= 1, "successes and failures are both needed"
+    assert (want["qa"] != tables[0]).any() and ((want["qb"] != tables[1]).any() or cfg.quirks != Q_PAPER), "under the coin both tables are to be written"
+    assert ref.updates_inside >= 1 and ref.updates_beyond >= 1 and (want["count"] > len(ref.alpha)).any(), "learning rates from the table and alpha_min beyond it are both needed"
+    return want, tables
+
+
 class Reference:
-    def __init__(self, cfg, n, seed, eps=EPS_TABLE, window=100, min_successes=97, max_episodes=1 << 30, log_capacity=64, alpha_tab=None):
+    def __init__(self, cfg, n, seed, eps=EPS_TABLE, window=100, min_successes=97, max_episodes=1 << 30, log_capacity=64, alpha_tab=None, tables=None):
+        """tables: initial (qa, qb, count), [n][N_CELLS] each (copied); default zeros"""
         self.cfg, self.n, self.seed = cfg, int(n), int(seed)
         self.o = Oracle(cfg, self.n, seed=self.seed)
-        self.qa, self.qb, self.cnt = (np.zeros((self.n, N_CELLS)) for _ in range(3))
+        self.qa, self.qb, self.cnt = (np.zeros((self.n, N_CELLS)) for _ in range(3)) if tables is None else (np.array(t, np.float64).reshape(self.n, N_CELLS) for t in tables)
         self.alpha = cfg.alpha_table() if alpha_tab is None else np.asarray(alpha_tab, np.float64)
         self.thr = [eps_thr(e) for e in eps]
         self.W, self.min_successes, self.max_episodes, self.cap = int(window), int(min_successes), int(max_episodes), int(log_capacity)
         self.j = 0
         self.same_state = 0  # transitions with s' == s: the carried row of the next greedy choice must show the write
+        self.updates_inside, self.updates_beyond = 0, 0  # updates whose learning rate came from the table / was alpha_min beyond its end
         self.decisions, self.episodes, self.successes = (np.zeros(self.n, np.int64) for _ in range(3))
         self.by_code = np.zeros((N_CODES, self.n), np.int64)
         self.log_code = np.zeros((self.n, self.cap), np.uint8); self.log_len = np.zeros((self.n, self.cap), np.uint16); self.log_n = np.zeros(self.n, np.int32)
@@ -103,6 +142,7 @@ class Reference:
                 sa = 3 * int(s[l]) + a
                 c = int(self.cnt[l][sa])
                 al = self.alpha[c] if c < len(self.alpha) else self.cfg.alpha_min
+                self.updates_inside += c < len(self.alpha); self.updates_beyond += c >= len(self.alpha)
                 done = bool(ints[i_fl][l] & 1)
                 orc.agent_update(self.qa[l], self.qb[l], self.cnt[l], [sa], [ns], [al], self.cfg.gamma, [reals[i_rew][l]], quirks=self.cfg.quirks,
                                  coin=[int(r[2]) >> 31], done=[int(done)])

@@ -25,13 +25,13 @@ using namespace dql;
 namespace {
 
 struct Job {
-  int dtype, n_runs, runs[8], n_alpha, every, last_level, advance_exhausted, log_cap;
+  int dtype, n_runs, runs[8], n_alpha, every, last_level, advance_exhausted, log_cap, has_tables;
   int n_eps[ADV_MAX_LEVELS], window[ADV_MAX_LEVELS], min_successes[ADV_MAX_LEVELS], max_episodes[ADV_MAX_LEVELS];
   long long n;
   unsigned long long seed;
   dql_config cfg;
   double ratios[ADV_MAX_LEVELS];
-  std::vector<double> alpha, eps[ADV_MAX_LEVELS];
+  std::vector<double> alpha, eps[ADV_MAX_LEVELS], qa, qb, count;  // the tables: zeros, or the job's initial ones ([L][DQL_N_CELLS] each, after the eps tables)
 };
 
 template <typename V> void read_into(FILE* f, V* p, size_t n) {
@@ -42,7 +42,7 @@ Job read_job(const char* path) {
   FILE* f = std::fopen(path, "rb");
   if (!f) { std::perror(path); std::exit(2); }
   Job j;
-  int32_t hdr[40];  // cfg size, dtype, L, n_runs, runs[8], n_alpha, every, last_level, advance_exhausted, log_cap, then per level {n_eps, window, min_successes, max_episodes}, 0 ...
+  int32_t hdr[40];  // cfg size, dtype, L, n_runs, runs[8], n_alpha, every, last_level, advance_exhausted, log_cap, then per level {n_eps, window, min_successes, max_episodes}, has_tables, 0 ...
   int64_t seed;
   read_into(f, hdr, 40); read_into(f, &seed, 1);
   if (hdr[0] != (int32_t)sizeof(dql_config)) { std::fprintf(stderr, "dql_config size %d != %d\n", hdr[0], (int)sizeof(dql_config)); std::exit(2); }
@@ -50,7 +50,7 @@ Job read_job(const char* path) {
   j.dtype = hdr[1]; j.n = hdr[2]; j.n_runs = hdr[3];
   for (int k = 0; k < 8; ++k) j.runs[k] = hdr[4 + k];
   j.seed = (unsigned long long)seed;
-  j.n_alpha = hdr[12]; j.every = hdr[13]; j.last_level = hdr[14]; j.advance_exhausted = hdr[15]; j.log_cap = hdr[16];
+  j.n_alpha = hdr[12]; j.every = hdr[13]; j.last_level = hdr[14]; j.advance_exhausted = hdr[15]; j.log_cap = hdr[16]; j.has_tables = hdr[37];
   bool ok = j.n >= 1 && j.n_runs >= 1 && j.n_runs <= 8 && j.n_alpha >= 1 && j.every >= 1 && j.every <= ADV_MAX_EVERY && j.last_level >= j.cfg.working_curriculum_step &&
             j.last_level < ADV_MAX_LEVELS && j.log_cap >= 1 && !j.cfg.two_axis && j.cfg.trajectory != DQL_TRAJ_EIGHT;
   for (int k = 0; k < ADV_MAX_LEVELS; ++k) {
@@ -63,6 +63,9 @@ Job read_job(const char* path) {
   j.alpha.resize((size_t)j.n_alpha);
   read_into(f, j.alpha.data(), j.alpha.size());
   for (int k = 0; k < ADV_MAX_LEVELS; ++k) { j.eps[k].resize((size_t)j.n_eps[k]); read_into(f, j.eps[k].data(), j.eps[k].size()); }
+  const size_t TB = (size_t)j.n * DQL_N_CELLS;
+  j.qa.assign(TB, 0.0); j.qb.assign(TB, 0.0); j.count.assign(TB, 0.0);
+  if (j.has_tables) { read_into(f, j.qa.data(), TB); read_into(f, j.qb.data(), TB); read_into(f, j.count.data(), TB); }
   std::fclose(f);
   return j;
 }
@@ -104,8 +107,9 @@ template <typename T> int launch(Job& j, const char* out_path) {
     for (int i = 0; i < j.n_eps[k]; ++i) thr[k][(size_t)i] = eps_threshold(j.eps[k][(size_t)i]);
     lv[k] = LevelSched{thr[k].data(), j.n_eps[k], j.window[k], j.min_successes[k], j.max_episodes[k]};
   }
-  const size_t TB = n * DQL_N_CELLS;
-  std::vector<double> qa(TB, 0.0), qb(TB, 0.0), count(TB, 0.0);
+  std::vector<double>& qa = j.qa;
+  std::vector<double>& qb = j.qb;
+  std::vector<double>& count = j.count;
   std::vector<unsigned long long> decisions(n, 0ull), by_code((size_t)DQL_N_CHECK_CODES * n, 0ull), win_bits(2 * n, 0ull), faults(1, 0ull);
   std::vector<int> episodes(n, 0), successes(n, 0), lvl(n, 0), win_count(n, 0), promoted(n, -1), frozen(n, 0), log_n(n, 0);
   std::vector<uint8_t> log_code(n * (size_t)j.log_cap, 0);

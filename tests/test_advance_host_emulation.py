@@ -3,7 +3,8 @@ learner_periods, held `==` to the yardstick of tests/advance_checks.py (CPU only
 
 tests/host_emu/advance_emu.cpp compiles the real headers as host C++ and does what dql_ensemble_run does in curriculum mode: advance at the multiples of E,
 worklist, wave by wave.  It is a stand-alone program run as its own process, built twice: plain, and with ASan + UBSan (any report fails).  The cases are those
-of tests/test_gpu_ensemble_advance.py; the sanitized build flies the first 24 learners for 384 periods."""
+of tests/test_gpu_ensemble_advance.py; the sanitized build flies the first 24 learners for 384 periods, and the 24 learners of the cases from trained tables
+(`advance_checks.TRAINED_CASE`, `TRAINED_CASE_PAPER`, `TRAINED_FROM_3`) whole."""
 import os
 import struct
 import subprocess
@@ -45,7 +46,8 @@ def emu(tmp_path_factory):
 def run_emu(exe, tmp, runs, n=None, dtype=F32, sanitized=False, **over):
     c = dict(CASE, **over)
     n = c["n"] if n is None else n
-    cfg = ac.level0(dtype)
+    cfg = ac.case_config(c, dtype)
+    tables = ac.case_tables(c, n)
     cb = bytes(cfg.to_c())
     alpha = cfg.alpha_table()
     sch = ac.case_schedules(c)
@@ -53,10 +55,12 @@ def run_emu(exe, tmp, runs, n=None, dtype=F32, sanitized=False, **over):
     hdr = [len(cb), cfg.dtype, n, len(runs), *r8, len(alpha), c["E"], c["last_level"], int(c.get("advance_exhausted", True)), c["log_capacity"]]
     for s in sch:
         hdr += [len(s["eps"]), s["window"], s["min_successes"], s["max_episodes"]]
+    hdr += [int(tables is not None)]
     hdr += [0] * (40 - len(hdr))
     job, res = tmp / "advance_job.bin", tmp / "advance_res.bin"
-    job.write_bytes(struct.pack("<40i", *hdr) + struct.pack("<q", c["seed"]) + cb + np.asarray(ensemble.REFERENCE_RATIOS, np.float64).tobytes() + alpha.tobytes()
-                    + b"".join(np.asarray(s["eps"], np.float64).tobytes() for s in sch))
+    job.write_bytes(struct.pack("<40i", *hdr) + struct.pack("<q", c["seed"]) + cb + np.asarray(ac.case_ratios(c), np.float64).tobytes() + alpha.tobytes()
+                    + b"".join(np.asarray(s["eps"], np.float64).tobytes() for s in sch)
+                    + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ())))
     env = dict(os.environ, **SAN_ENV) if sanitized else None
     r = subprocess.run([str(exe), str(job), str(res)], capture_output=True, text=True, env=env, timeout=1800)
     assert r.returncode == 0, f"advance_emu ({'sanitized' if sanitized else 'plain'}) failed:\n{r.stderr[-6000:]}"
@@ -178,3 +182,68 @@ def test_clean_under_asan_and_ubsan(emu, yard, dtype, tmp_path):
         y = ac.case_yardstick(dtype=F64, n=ac.SMALL, periods=SHORT)
     assert y.advanced_exhausted >= 1 and len(set(y.level.tolist())) >= 3
     ac.assert_equal(got, y.result(), f"sanitized, dtype {dtype}", learners=(first, first))
+
+
+# ---- from trained tables: promotions through the ring above level 0, transfers of non-zero blocks of both tables, the k = 0 wrap with a ratio that shows ----
+TRAINED = {"0x7f": ac.TRAINED_CASE, "0x40": ac.TRAINED_CASE_PAPER, "from-3": ac.TRAINED_FROM_3}
+
+
+@pytest.fixture(scope="module")
+def trained_yard():
+    """per (case, dtype, overrides): the yardstick of the case's first 24 learners (3 - 5 s each on the CPU), its conditions asserted, and its result"""
+    cache = {}
+
+    def get(name, dtype=F32, **over):
+        key = (name, dtype, tuple(sorted(over.items())))
+        if key not in cache:
+            c = dict(TRAINED[name], n=ac.SMALL, **over)
+            y = ac.case_yardstick(dtype=dtype, **c)
+            if not over:
+                ac.assert_trained_case_conditions(y, c)
+            cache[key] = (y, y.result(), c)
+        return cache[key]
+    return get
+
+
+@pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
+@pytest.mark.parametrize("name", list(TRAINED))
+def test_trained_whole_run_equals_the_yardstick(emu, trained_yard, name, dtype, tmp_path):
+    y, want, c = trained_yard(name, dtype)
+    ac.assert_equal(run_emu(emu["plain"], tmp_path, (c["periods"],), dtype=dtype, **c), want, f"trained case {name}, dtype {dtype}")
+
+
+@pytest.mark.parametrize("runs", [(7, 1017), (33, 31, 960)], ids=lambda r: "+".join(map(str, r)))
+@pytest.mark.parametrize("name", ["0x7f", "0x40"])
+def test_trained_splits_equal_the_yardstick(emu, trained_yard, name, runs, tmp_path):
+    """cuts off the multiples of E = 32, one period after one, and on one"""
+    y, want, c = trained_yard(name)
+    assert sum(runs) == c["periods"] and any(r % c["E"] for r in runs)
+    ac.assert_equal(run_emu(emu["plain"], tmp_path, runs, **c), want, f"trained case {name}, runs {runs}")
+
+
+@pytest.mark.parametrize("name", ["0x7f", "0x40"])
+def test_trained_last_level_2_is_never_exceeded(emu, trained_yard, name, tmp_path):
+    y, want, c = trained_yard(name, last_level=2)
+    done = want["frozen"].astype(bool) & (want["level"] == 2)
+    assert want["level"].max() == 2 and (done & (want["promotion_episode"] >= 0)).any(), "on the yardstick nobody finishes at level 2 by promotion"
+    assert (want["entered_period"][3:] == -1).all() and y.promoted_from[1] >= 1
+    got = run_emu(emu["plain"], tmp_path, (c["periods"],), **c)
+    ac.assert_equal(got, want, f"trained case {name}, last_level = 2")
+    tables = ac.case_tables(c, c["n"])
+    for t, w in zip(("qa", "qb", "count"), tables):
+        assert np.array_equal(got[t][:, 3 * CELLS_PER_LEVEL:], w[:, 3 * CELLS_PER_LEVEL:]), f"{t}: cells of levels 3 and 4 were written"
+
+
+def test_trained_exhausted_learners_do_not_advance(emu, trained_yard, tmp_path):
+    """advance_exhausted = 0 on the 0x7f case: learners that promoted above level 0 go on, the ones out of episodes stay where they froze"""
+    y, want, c = trained_yard("0x7f", advance_exhausted=False)
+    exhausted = want["frozen"].astype(bool) & (want["promotion_episode"] < 0)
+    assert y.advanced_exhausted == 0 and (y.promoted_from[1:] > 0).sum() >= 2 and (exhausted & (want["level"] >= 1) & (want["level"] < 4)).any()
+    ac.assert_equal(run_emu(emu["plain"], tmp_path, (c["periods"],), **c), want, "trained case 0x7f, advance_exhausted = 0")
+
+
+@pytest.mark.parametrize("name,dtype", [("0x7f", F32), ("0x40", F64), ("from-3", F32)], ids=["0x7f-f32", "0x40-f64", "from-3-f32"])
+def test_trained_clean_under_asan_and_ubsan(emu, trained_yard, name, dtype, tmp_path):
+    """the whole case of 24 learners through the sanitized build, in two runs"""
+    y, want, c = trained_yard(name, dtype)
+    ac.assert_equal(run_emu(emu["san"], tmp_path, (7, c["periods"] - 7), dtype=dtype, sanitized=True, **c), want, f"sanitized trained case {name}, dtype {dtype}")

@@ -159,6 +159,29 @@ def test_same_state_in_consecutive_periods_reads_the_written_row():
         ens.close()
 
 
+@pytest.mark.parametrize("quirks", [ec.Q_PAPER, ec.Q_REFERENCE], ids=["quirks-0x40", "quirks-0x7f"])
+@pytest.mark.parametrize("level", [4, 2], ids=["level-4", "level-2"])
+@pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
+def test_trained_tables_70_learners_400_periods(dtype, level, quirks):
+    """greedy from the reference's stage-4 tables (`ensemble_checks.trained_tables`), window 4, 2 successes, 6 episodes, a second wave of 6 lanes: the coin
+    picking B, argmax over non-trivial rows, alpha_min beyond the table beside table entries, promotions through the ring above level 0; then 7 + 393"""
+    n = 70
+    cfg = training_config(level, quirks=quirks, dtype=dtype)
+    want, tables = ec.trained_reference(cfg, n)
+    kw = {k: v for k, v in ec.TRAINED_LEARNERS_CASE.items() if k != "log_capacity"}
+    assert ec.TRAINED_LEARNERS_CASE["log_capacity"] == LOG_CAP
+    for runs in ((ec.TRAINED_LEARNERS_PERIODS,), ec.TRAINED_LEARNERS_SPLIT):
+        ens = make(cfg, n, ec.TRAINED_LEARNERS_SEED, **kw)
+        try:
+            ens.set_tables(*tables)
+            for r in runs:
+                ens.run(r)
+            ec.assert_equal(ec.ensemble_result(ens), want, f"trained tables, runs {runs}, level {level} dtype {dtype} quirks {quirks:#x}")
+            assert ens.index_faults() == 0 and ens.period_index() == ec.TRAINED_LEARNERS_PERIODS and ens.n_live() == int((~want["frozen"]).sum())
+        finally:
+            ens.close()
+
+
 def test_refused_calls_launch_nothing():
     lib = _lib.load()
     cfg = training_config(0, dtype=F32)

@@ -2,7 +2,8 @@
 
 The yardstick is tests/advance_checks.py (the unchanged oracle, one per level); every comparison is `==`, floats by their bits.  The case's conditions — three
 levels at once, two waves of one level, padding, an empty level between populated ones, both ways of advancing, finished and unfinished learners at the end —
-are asserted on the yardstick before an ensemble is looked at."""
+are asserted on the yardstick before an ensemble is looked at.  The cases from trained tables at the end of the file are there for what tables of zeros never reach:
+promotions through the ring above level 0, transfers of non-zero blocks of both tables, the k = 0 wrap with a source block and a ratio that show."""
 import ctypes as C
 
 import numpy as np
@@ -281,3 +282,122 @@ def test_the_mode_is_not_switched_off_while_learners_stand_on_different_levels()
         assert ens.period_index() == 405 and ens.index_faults() == 0 and (ens.levels()["level"] == 1).all()
     finally:
         ens.close()
+
+
+# ---- from trained tables (advance_checks.TRAINED_CASE / TRAINED_FROM_3): promotions through the ring above level 0, transfers of non-zero blocks of both
+# tables, the k = 0 wrap reading a level-4 block that is not zero with a ratio that is not 1.0 ----
+TRAINED = {"0x7f": ac.TRAINED_CASE, "0x40": ac.TRAINED_CASE_PAPER, "from-3": ac.TRAINED_FROM_3}
+EVERY = 256
+FIRST = list(range(ac.SMALL))
+
+
+@pytest.fixture(scope="module")
+def trained_yard():
+    """per (case, dtype, learners, overrides): the yardstick (its conditions asserted where the case is flown as it stands), its result and the case.  On the
+    CPU about 12 s (0x7f) and 9 s (0x40) with 80 learners, 3 - 5 s with 24."""
+    cache = {}
+
+    def get(name, dtype=F32, n=None, **over):
+        key = (name, dtype, n, tuple(sorted(over.items())))
+        if key not in cache:
+            c = dict(TRAINED[name], **over)
+            if n is not None:
+                c["n"] = n
+            y = ac.case_yardstick(dtype=dtype, checkpoint_every=EVERY, **c)
+            if not over:
+                ac.assert_trained_case_conditions(y, c)
+            cache[key] = (y, y.result(), c)
+        return cache[key]
+    return get
+
+
+@pytest.fixture(scope="module")
+def trained_main():
+    """per case: the float32 ensemble's result after ONE run of the case's periods"""
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            c = TRAINED[name]
+            got, j, unfinished = flown(ac.case_ensemble(**c), c["periods"])
+            assert j == c["periods"]
+            cache[name] = (got, unfinished)
+        return cache[name]
+    return get
+
+
+@pytest.mark.parametrize("name", list(TRAINED))
+def test_trained_whole_run_equals_the_yardstick_f32(trained_yard, trained_main, name):
+    """80 learners (two waves at level 0, padded segments), or the 24 created at level 3"""
+    y, want, c = trained_yard(name)
+    got, unfinished = trained_main(name)
+    ac.assert_equal(got, want, f"trained case {name}, float32")
+    assert unfinished == y.n_unfinished()
+
+
+@pytest.mark.parametrize("name", list(TRAINED))
+def test_trained_whole_run_equals_the_yardstick_f64(trained_yard, name):
+    y, want, c = trained_yard(name, F64, ac.SMALL)
+    got, j, unfinished = flown(ac.case_ensemble(dtype=F64, **c), c["periods"])
+    ac.assert_equal(got, want, f"trained case {name}, float64")
+    assert j == c["periods"] and unfinished == y.n_unfinished()
+
+
+@pytest.mark.parametrize("runs", [(7, 1017), (33, 31, 960)], ids=lambda r: "+".join(map(str, r)))
+@pytest.mark.parametrize("name", ["0x7f", "0x40"])
+def test_trained_splits_equal_one_run(trained_main, name, runs):
+    """cuts off the multiples of E = 32, one period after one, and on one"""
+    c = TRAINED[name]
+    assert sum(runs) == c["periods"] and any(r % c["E"] for r in runs)
+    got, j, _ = flown(ac.case_ensemble(**c), *runs)
+    assert j == c["periods"]
+    ac.assert_equal(got, trained_main(name)[0], f"trained case {name}, runs {runs} against one run")
+
+
+@pytest.mark.parametrize("name", ["0x7f", "0x40"])
+def test_trained_first_24_learners_do_not_depend_on_the_other_56(trained_yard, trained_main, name):
+    c = TRAINED[name]
+    got, _, _ = flown(ac.case_ensemble(**dict(c, n=ac.SMALL)), c["periods"])
+    ac.assert_equal(trained_main(name)[0], got, f"trained case {name}, L = 80 against L = 24", learners=(FIRST, FIRST))
+    ac.assert_equal(got, trained_yard(name)[1], f"trained case {name}, L = 24 against the yardstick", learners=(FIRST, FIRST))
+
+
+@pytest.mark.parametrize("name", list(TRAINED))
+def test_trained_levels_and_unfinished_after_every_256_periods(trained_yard, trained_main, name):
+    y, want, c = trained_yard(name)
+    assert len(y.checkpoints) == c["periods"] // EVERY and len({u for _, u, _ in y.checkpoints}) >= 2  # the number of unfinished learners moves
+    ens = ac.case_ensemble(**c)
+    try:
+        for j, unfinished, levels in y.checkpoints:
+            ens.run(EVERY)
+            got = ens.levels()
+            assert ens.period_index() == j and ens.n_unfinished() == unfinished, f"period {j}: {ens.n_unfinished()} unfinished, the yardstick has {unfinished}"
+            for k, w in levels.items():
+                assert np.array_equal(got[k].astype(np.int64), w.astype(np.int64)), f"period {j}: {k} differs: {got[k].tolist()} vs {w.tolist()}"
+        ac.assert_equal(ac.ensemble_result(ens), trained_main(name)[0], f"trained case {name}, runs of {EVERY} against one run")
+        assert ens.index_faults() == 0
+    finally:
+        ens.close()
+
+
+@pytest.mark.parametrize("name", ["0x7f", "0x40"])
+def test_trained_last_level_2_is_never_exceeded(trained_yard, name):
+    y, want, c = trained_yard(name, n=ac.SMALL, last_level=2)
+    done = want["frozen"] & (want["level"] == 2)
+    assert want["level"].max() == 2 and (done & (want["promotion_episode"] >= 0)).any(), "on the yardstick nobody finishes at level 2 by promotion"
+    assert (want["entered_period"][3:] == -1).all() and y.promoted_from[1] >= 1
+    got, j, unfinished = flown(ac.case_ensemble(**c), c["periods"])
+    ac.assert_equal(got, want, f"trained case {name}, last_level = 2")
+    assert unfinished == y.n_unfinished()
+    for t, w in zip(("qa", "qb", "count"), ac.case_tables(c, c["n"])):
+        assert np.array_equal(got[t][:, 3 * CELLS_PER_LEVEL:], w[:, 3 * CELLS_PER_LEVEL:]), f"{t}: cells of levels 3 and 4 were written"
+
+
+def test_trained_exhausted_learners_do_not_advance(trained_yard):
+    """advance_exhausted = 0 on the 0x7f case: learners that promoted above level 0 go on, the ones out of episodes stay where they froze"""
+    y, want, c = trained_yard("0x7f", n=ac.SMALL, advance_exhausted=False)
+    exhausted = want["frozen"] & (want["promotion_episode"] < 0)
+    assert y.advanced_exhausted == 0 and (y.promoted_from[1:] > 0).sum() >= 2 and (exhausted & (want["level"] >= 1) & (want["level"] < 4)).any()
+    got, j, unfinished = flown(ac.case_ensemble(**c), c["periods"])
+    ac.assert_equal(got, want, "trained case 0x7f, advance_exhausted = 0")
+    assert unfinished == y.n_unfinished()

@@ -55,13 +55,13 @@ def emu(tmp_path_factory):
         return dict(zip(builds, ex.map(build, builds)))
 
 
-def run_emu(exe, cfg, n, seed, runs, tmp, eps=ec.EPS_TABLE, window=100, min_successes=97, max_episodes=1 << 30, sanitized=False, log_capacity=LOG_CAP, alpha_tab=None):
+def run_emu(exe, cfg, n, seed, runs, tmp, eps=ec.EPS_TABLE, window=100, min_successes=97, max_episodes=1 << 30, sanitized=False, log_capacity=LOG_CAP, alpha_tab=None, tables=None):
     c = bytes(cfg.to_c())
     alpha = cfg.alpha_table() if alpha_tab is None else np.ascontiguousarray(alpha_tab, np.float64)
     r4 = list(runs) + [0] * (4 - len(runs))
-    hdr = struct.pack("<16i", len(c), cfg.dtype, n, len(runs), *r4, len(alpha), len(eps), window, min_successes, max_episodes, log_capacity, 0, 0) + struct.pack("<q", seed)
+    hdr = struct.pack("<16i", len(c), cfg.dtype, n, len(runs), *r4, len(alpha), len(eps), window, min_successes, max_episodes, log_capacity, int(tables is not None), 0) + struct.pack("<q", seed)
     job, res = tmp / "learner_job.bin", tmp / "learner_res.bin"
-    job.write_bytes(hdr + c + alpha.tobytes() + np.asarray(eps, np.float64).tobytes())
+    job.write_bytes(hdr + c + alpha.tobytes() + np.asarray(eps, np.float64).tobytes() + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ())))
     env = dict(os.environ, **SAN_ENV) if sanitized else None
     r = subprocess.run([str(exe), str(job), str(res)], capture_output=True, text=True, env=env, timeout=1800)
     assert r.returncode == 0, f"learner_emu ({'sanitized' if sanitized else 'plain'}) failed:\n{r.stderr[-6000:]}"
@@ -178,3 +178,30 @@ def test_as_launched_parameters_equal_the_reference_loop(emu, tmp_path):
     assert want["episodes"].min() >= 1 and len(set(want["log_code"][want["log_code"] > 0].tolist())) >= 2 and (want["qa"] != 0).any()
     got = run_emu(emu["plain"], as_launched_config(0, dtype=F32), L, SEED, (7, 293), tmp_path)
     ec.assert_equal(got, want, "as-launched parameters")
+
+
+# ---- from trained tables (ensemble_checks.trained_tables): the coin picking B, argmax over non-trivial rows, alpha_min together with table entries, promotions
+# through the ring above level 0 ----
+TRAINED_L = 26  # on the reference loop learner 25 is the first to fail an episode at level 2 under quirks 0x40: fewer learners leave that case without a failure
+
+
+@pytest.mark.parametrize("quirks", [ec.Q_PAPER, ec.Q_REFERENCE], ids=["quirks-0x40", "quirks-0x7f"])
+@pytest.mark.parametrize("level", [4, 2], ids=["level-4", "level-2"])
+@pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
+def test_trained_tables_400_periods_equal_the_reference_loop(emu, dtype, level, quirks, tmp_path):
+    """greedy from the reference's stage-4 tables, window 4, 2 successes, 6 episodes: one run of 400 periods and 7 + 393"""
+    cfg = training_config(level, quirks=quirks, dtype=dtype)
+    want, tables = ec.trained_reference(cfg, TRAINED_L)
+    kw = dict(ec.TRAINED_LEARNERS_CASE, tables=tables)
+    got = run_emu(emu["plain"], cfg, TRAINED_L, ec.TRAINED_LEARNERS_SEED, (ec.TRAINED_LEARNERS_PERIODS,), tmp_path, **kw)
+    ec.assert_equal(got, want, f"trained tables, level {level} dtype {dtype} quirks {quirks:#x}")
+    split = run_emu(emu["plain"], cfg, TRAINED_L, ec.TRAINED_LEARNERS_SEED, ec.TRAINED_LEARNERS_SPLIT, tmp_path, **kw)
+    ec.assert_equal(split, want, f"trained tables, 7 + 393, level {level} dtype {dtype} quirks {quirks:#x}")
+
+
+@pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
+def test_trained_tables_clean_under_asan_and_ubsan(emu, dtype, tmp_path):
+    cfg = training_config(4, quirks=ec.Q_PAPER, dtype=dtype)
+    want, tables = ec.trained_reference(cfg, TRAINED_L)
+    got = run_emu(emu["san"], cfg, TRAINED_L, ec.TRAINED_LEARNERS_SEED, ec.TRAINED_LEARNERS_SPLIT, tmp_path, sanitized=True, **dict(ec.TRAINED_LEARNERS_CASE, tables=tables))
+    ec.assert_equal(got, want, f"sanitized, trained tables, dtype {dtype}")
