@@ -2,7 +2,7 @@
 // level between launches, and the step a frozen learner takes from its finished level to the next.
 //
 // Everything level-dependent in agent_period is wave-uniform (SimK::working is pinned to an SGPR, MdpK is read with scalar loads), so a learner's level is
-// never a lane's property: build_worklist lays the live learners out so that every wave of k_learn_levels (dql_hip.hip) holds learners of ONE level, and
+// never a lane's property: build_worklist lays the live learners out so that every wave of k_learn_levels (dql_ensemble.inc) holds learners of ONE level, and
 // advance_learner moves a learner to the next level between launches.  learner_periods (dql_learner.hpp) is what flies them, unchanged.
 //
 // Both are plain functions that also compile as host C++ (tests/host_emu/advance_emu.cpp).  Every loop is bounded by an argument on every path, every

@@ -1,0 +1,603 @@
+// dql_ensemble.inc: ensembles of sequential Double-Q learners (include/dql.h dql_ensemble_*, DESIGN.md sections 12 and 14): the lane kernels, struct dql_ensemble
+// and its C calls.  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype, OP_PROLOGUE, DevOwned, upload_mdpk,
+// upload_schedule, EvTimer, quads_to_fields / unpack_ints, check_config, InitArgs / k_init, k_mark_reset, TickLds; dql_learner.hpp, dql_advance.hpp; and
+// score_check / score_run of dql_greedy.inc (dql_ensemble_score).
+// ---- sequential learners (dql_ensemble, DESIGN.md section 12) ----
+// One learner per lane (csrc/dql_learner.hpp: learner_periods), workgroups of one wave as in k_rollout; the env stays in registers for all periods of the launch,
+// the tables are the lane's own [DQL_N_CELLS] slices (per-lane global pointers, ordinary vector loads and stores, no atomics).
+template <typename T> struct LearnArgs {
+  SimK<T> c;
+  const MdpK<T> DQL_CONST_AS* mdp;
+  MdpRun<T> mdp_run;
+  LearnSched sched;
+  LearnMem mem;
+  Quad<T>* sr; int4* si;
+  const long long DQL_CONST_AS* mgr0; const int DQL_CONST_AS* tick_sched;  // [n_periods] (fill_schedule from period j0)
+  unsigned long long seed;
+  long long j0;
+  int n_periods;
+};
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_learn(LearnArgs<T> a) {
+  const int tid = threadIdx.x;
+  const long long l = (long long)blockIdx.x * 64 + tid;
+  SimK<T> cl = a.c;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  learner_periods<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.sched, a.mem, a.sr, a.si, a.seed, l, l < a.mem.n, a.j0, a.n_periods, a.mgr0, a.tick_sched, kv);
+}
+// transfer_learning on every learner's tables: Q[l][k] = Q[l][src] * ratio (k_transfer's arithmetic)
+__global__ void k_ens_transfer(double* qa, double* qb, long long n, int k, int src, double ratio) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * DQL_CELLS_PER_LEVEL) return;
+  const long long l = t / DQL_CELLS_PER_LEVEL; const int i = (int)(t - l * DQL_CELLS_PER_LEVEL);
+  double* a = qa + l * DQL_N_CELLS; double* b = qb + l * DQL_N_CELLS;
+  a[k * DQL_CELLS_PER_LEVEL + i] = a[src * DQL_CELLS_PER_LEVEL + i] * ratio;
+  b[k * DQL_CELLS_PER_LEVEL + i] = b[src * DQL_CELLS_PER_LEVEL + i] * ratio;
+}
+
+// ---- per-learner curriculum levels (DESIGN.md section 14) ----
+// k_learn over a worklist (csrc/dql_advance.hpp: build_worklist): wave w flies the learners worklist[64 w .. 64 w + 63] (-1: an inactive lane), all of
+// them at level wave_level[w] — a scalar load — from which follow SimK::working, the level's MdpK (a.a.mdp is the array of all five) and the level's
+// exploration table and freeze rules.  After that the call to learner_periods is k_learn's.
+template <typename T> struct LearnLevelsArgs {
+  LearnArgs<T> a;                          // a.mdp: [DQL_MAX_LEVELS]; a.sched: the learning rates (its per-level members are replaced by lv[level])
+  const LevelSched DQL_CONST_AS* lv;       // [DQL_MAX_LEVELS]
+  const int* worklist;                     // [64 n_waves]
+  const int DQL_CONST_AS* wave_level;      // [n_waves]
+  int n_waves;
+};
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_learn_levels(LearnLevelsArgs<T> g) {
+  const LearnArgs<T>& a = g.a;
+  const int tid = threadIdx.x;
+  const int w = (int)blockIdx.x;
+  if (w >= g.n_waves) return;
+  const int level = g.wave_level[w];
+  if ((unsigned)level >= (unsigned)DQL_MAX_LEVELS) { if (tid == 0) a.mem.faults[0] += 1ull; return; }  // never taken unless a bug (the host builds the worklist)
+  const long long l = (long long)g.worklist[(long long)w * 64 + tid];
+  SimK<T> cl = a.c;
+  cl.working = level;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // as in k_learn
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  const LevelSched DQL_CONST_AS* lv = g.lv + level;
+  const LearnSched sc{a.sched.alpha_tab, a.sched.n_alpha, a.sched.alpha_min, lv->eps_tab, lv->n_eps, lv->window, lv->min_successes, lv->max_episodes};
+  learner_periods<TICK, XMODE>(cl, cfgk, tc, a.mdp + level, a.mdp_run, sc, a.mem, a.sr, a.si, a.seed, l, l >= 0 && l < a.mem.n, a.j0, a.n_periods, a.mgr0, a.tick_sched, kv);
+}
+// an advance point: every learner takes advance_learner's step by itself (its own thread moves its own 2 x 567 cells; ordinary vector stores, nothing shared)
+// -- but for the `faults` word: advance_learner's `faults[0] += 1` is a plain add that threads of all waves may make at once, as learner_periods' is.  Counts
+// can be lost, a nonzero word cannot become zero, and nonzero is all that index_faults() is read for.
+__global__ void k_ens_advance(LearnMem mem, AdvanceMem adv, AdvanceRule rule, int4* si, long long j, int n_cells) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= mem.n) return;
+  (void)advance_learner(mem, adv, rule, si, l, j, n_cells);
+}
+
+// ---- ensembles of sequential learners (DESIGN.md section 12) ----
+struct dql_ensemble {
+  dql_config cfg;
+  int device = 0;
+  long long n = 0;
+  unsigned long long seed = 0;
+  long long j = 0;  // the ensemble's period index (period 0 is the reset period)
+  DevOwned dev;     // every device allocation below, the replaceable schedule tables included
+  void* sr = nullptr; int4* si = nullptr; void* mdpk = nullptr;
+  LearnMem mem{};
+  LearnSched sched{};
+  double* alpha_tab = nullptr; uint32_t* eps_tab = nullptr;
+  long long* d_mgr0 = nullptr; int* d_sched = nullptr;  // [LEARN_MAX_PERIODS]
+  double last_ms = -1.0;
+  // per-learner curriculum levels (DESIGN.md section 14); advance_every = 0: the mode is off
+  AdvanceMem adv{};
+  AdvanceRule rule{};
+  int advance_every = 0;
+  void* mdpk5 = nullptr;                                      // [DQL_MAX_LEVELS] MdpK<T>, entry k with working = k
+  LevelSched* d_lv = nullptr; LevelSched h_lv[DQL_MAX_LEVELS]{}; bool have_lv[DQL_MAX_LEVELS]{};
+  int* d_worklist = nullptr; int* d_wave_level = nullptr; long long wl_slots = 0;
+  long long n_launches = 0, launched_periods = 0, launched_wave_periods = 0;  // since creation (dql_diag_ensemble_launches)
+};
+#define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
+static void ens_free(dql_ensemble* x) {
+  x->dev.free_all();
+  delete x;
+}
+// every learner to level k: the per-level history from level k on is cleared, level k is entered at the present period index
+static int ens_set_levels(dql_ensemble* x, int k) {
+  const size_t n = (size_t)x->n;
+  if (x->j == 0) HIP_TRY(hipMemset(x->adv.entered_period, 0xff, (size_t)DQL_MAX_LEVELS * n * sizeof(long long)));  // nothing was flown: no level below k was ever entered
+  std::vector<int> lv(n, k);
+  HIP_TRY(hipMemcpy(x->adv.level, lv.data(), n * sizeof(int), hipMemcpyHostToDevice));
+  const size_t from = (size_t)k * n, rest = (size_t)(DQL_MAX_LEVELS - k) * n;
+  HIP_TRY(hipMemset(x->adv.promoted_at + from, 0xff, rest * sizeof(int)));
+  HIP_TRY(hipMemset(x->adv.episodes_at + from, 0, rest * sizeof(int)));
+  HIP_TRY(hipMemset(x->adv.entered_period + from, 0xff, rest * sizeof(long long)));
+  std::vector<long long> at(n, x->j);
+  HIP_TRY(hipMemcpy(x->adv.entered_period + from, at.data(), n * sizeof(long long), hipMemcpyHostToDevice));
+  return DQL_OK;
+}
+// the five levels' MdpK (they differ in `working` only), read by k_learn_levels at the wave's level
+static int ens_upload_mdpk5(dql_ensemble* x) {
+  dql_config c = x->cfg;
+  for (int k = 0; k < DQL_MAX_LEVELS; ++k) {
+    c.working_curriculum_step = k;
+    const int rc = upload_mdpk(c, (char*)x->mdpk5 + (size_t)k * mdpk_bytes(c.dtype)); if (rc) return rc;
+  }
+  return DQL_OK;
+}
+// per-level episode counts, windows, promotion records and frozen flags back to "just started"
+static int ens_rearm(dql_ensemble* x) {
+  const size_t n = (size_t)x->n;
+  HIP_TRY(hipMemset(x->mem.level_episodes, 0, n * sizeof(int)));
+  HIP_TRY(hipMemset(x->mem.win_count, 0, n * sizeof(int)));
+  HIP_TRY(hipMemset(x->mem.win_bits, 0, 2 * n * sizeof(unsigned long long)));
+  HIP_TRY(hipMemset(x->mem.promoted, 0xff, n * sizeof(int)));
+  HIP_TRY(hipMemset(x->mem.frozen, 0, n * sizeof(int)));
+  return DQL_OK;
+}
+// what k_learn and k_learn_levels share: mdp = the config's MdpK or the five levels'
+template <typename T> static LearnArgs<T> make_learn_args(dql_ensemble* x, const void* mdp, int n_periods) {
+  LearnArgs<T> a;
+  a.c = make_simk<T>(x->cfg);
+  a.mdp = (const MdpK<T> DQL_CONST_AS*)mdp;
+  a.mdp_run = MdpRun<T>{x->cfg.gamma, (T)(x->cfg.t_max * x->cfg.f_ag), x->cfg.goal_logic};
+  a.sched = x->sched; a.mem = x->mem;
+  a.sr = (Quad<T>*)x->sr; a.si = x->si;
+  a.mgr0 = (const long long DQL_CONST_AS*)x->d_mgr0; a.tick_sched = (const int DQL_CONST_AS*)x->d_sched;
+  a.seed = x->seed; a.j0 = x->j; a.n_periods = n_periods;
+  return a;
+}
+// one launch of k periods from period x->j on n_waves waves: the tick schedule, the kernel (by level through the worklist, or every learner at the config's level),
+// its completion, the launch accounting
+static int ens_fly(dql_ensemble* x, int k, int n_waves, bool by_level) {
+  int rc = upload_schedule(x->cfg, x->j, k, x->d_mgr0, x->d_sched); if (rc) return rc;  // (synchronous: the previous launch has read its schedule)
+  by_dtype(x->cfg.dtype, [&](auto t) {
+    using T = decltype(t);
+    if (by_level) {
+      LearnLevelsArgs<T> g;
+      g.a = make_learn_args<T>(x, x->mdpk5, k);
+      g.lv = (const LevelSched DQL_CONST_AS*)x->d_lv; g.worklist = x->d_worklist; g.wave_level = (const int DQL_CONST_AS*)x->d_wave_level; g.n_waves = n_waves;
+      hipLaunchKernelGGL((k_learn_levels<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
+    } else {
+      hipLaunchKernelGGL((k_learn<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, make_learn_args<T>(x, x->mdpk, k));
+    }
+  });
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += (long long)n_waves * k;
+  return DQL_OK;
+}
+extern "C" {
+#define ENS_ALLOC(ptr, bytes) do { if (x->dev.alloc((void**)&(ptr), (bytes)) != hipSuccess) { ens_free(x); return fail(DQL_ENOMEM, "hipMalloc failed"); } \
+                                   if (hipMemset((ptr), 0, (bytes)) != hipSuccess) { ens_free(x); return fail(DQL_EHIP, "hipMemset failed"); } } while (0)
+int dql_ensemble_create(const dql_config* cfg, int device, int64_t n_learners, uint64_t seed, int32_t log_capacity, dql_ensemble** out) {
+  int rc = check_config(cfg); if (rc) return rc;
+  if (!out) return fail(DQL_EINVAL, "dql_ensemble_create: null pointer; nothing was launched");
+  if (cfg->two_axis) return fail(DQL_EINVAL, "dql_ensemble_create: two-axis configs are refused (the reference's learner is x-only); nothing was launched");
+  if (cfg->trajectory == DQL_TRAJ_EIGHT) return fail(DQL_EINVAL, "dql_ensemble_create: the figure-eight trajectory is refused (the reference's learner is x-only); nothing was launched");
+  if (n_learners < 1 || n_learners > DQL_ENSEMBLE_MAX_LEARNERS) return fail(DQL_EINVAL, "dql_ensemble_create: n_learners must be in 1..2^20 (DQL_ENSEMBLE_MAX_LEARNERS); nothing was launched");
+  if (log_capacity < 0 || log_capacity > DQL_ENSEMBLE_MAX_LOG) return fail(DQL_EINVAL, "dql_ensemble_create: log_capacity must be in 0..2^20 (DQL_ENSEMBLE_MAX_LOG); nothing was launched");
+  OP_PROLOGUE(device)
+  dql_ensemble* x = new dql_ensemble;
+  x->cfg = *cfg; x->device = device; x->n = n_learners; x->seed = seed;
+  const size_t n = (size_t)n_learners, mdpk_size = mdpk_bytes(cfg->dtype), real = by_dtype(cfg->dtype, [](auto t) { return sizeof(t); });
+  const size_t TB = n * DQL_N_CELLS * sizeof(double);
+  ENS_ALLOC(x->sr, (size_t)NQ_REAL * n * 4 * real);
+  ENS_ALLOC(x->si, n * sizeof(int4));
+  ENS_ALLOC(x->mdpk, mdpk_size);
+  ENS_ALLOC(x->mem.qa, TB); ENS_ALLOC(x->mem.qb, TB); ENS_ALLOC(x->mem.count, TB);
+  ENS_ALLOC(x->mem.decisions, n * sizeof(unsigned long long));
+  ENS_ALLOC(x->mem.by_code, (size_t)DQL_N_CHECK_CODES * n * sizeof(unsigned long long));
+  ENS_ALLOC(x->mem.episodes, n * sizeof(int)); ENS_ALLOC(x->mem.successes, n * sizeof(int));
+  ENS_ALLOC(x->mem.level_episodes, n * sizeof(int)); ENS_ALLOC(x->mem.win_count, n * sizeof(int));
+  ENS_ALLOC(x->mem.win_bits, 2 * n * sizeof(unsigned long long));
+  ENS_ALLOC(x->mem.promoted, n * sizeof(int)); ENS_ALLOC(x->mem.frozen, n * sizeof(int));
+  ENS_ALLOC(x->mem.log_code, n * (size_t)(log_capacity ? log_capacity : 1)); ENS_ALLOC(x->mem.log_len, n * (size_t)(log_capacity ? log_capacity : 1) * sizeof(uint16_t));
+  ENS_ALLOC(x->mem.log_n, n * sizeof(int));
+  ENS_ALLOC(x->mem.faults, sizeof(unsigned long long));
+  ENS_ALLOC(x->d_mgr0, (size_t)LEARN_MAX_PERIODS * sizeof(long long)); ENS_ALLOC(x->d_sched, (size_t)LEARN_MAX_PERIODS * sizeof(int));
+  ENS_ALLOC(x->adv.level, n * sizeof(int));
+  ENS_ALLOC(x->adv.promoted_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int)); ENS_ALLOC(x->adv.episodes_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int));
+  ENS_ALLOC(x->adv.entered_period, (size_t)DQL_MAX_LEVELS * n * sizeof(long long));
+  ENS_ALLOC(x->mdpk5, (size_t)DQL_MAX_LEVELS * mdpk_size);
+  ENS_ALLOC(x->d_lv, (size_t)DQL_MAX_LEVELS * sizeof(LevelSched));
+  x->wl_slots = worklist_capacity(n_learners);
+  ENS_ALLOC(x->d_worklist, (size_t)x->wl_slots * sizeof(int)); ENS_ALLOC(x->d_wave_level, (size_t)(x->wl_slots / ADV_WAVE) * sizeof(int));
+  x->mem.n = n_learners; x->mem.log_cap = log_capacity;
+  rc = upload_mdpk(x->cfg, x->mdpk);
+  if (!rc) rc = ens_upload_mdpk5(x);
+  if (!rc) rc = ens_set_levels(x, 0);  // the whole history cleared ...
+  if (!rc) rc = ens_set_levels(x, cfg->working_curriculum_step);  // ... and the config's level entered at period 0
+  if (!rc) rc = ens_rearm(x);
+  if (!rc) rc = by_dtype(cfg->dtype, [&](auto t) { return launch_init<decltype(t)>(x->cfg, x->sr, x->si, x->n, x->n, x->seed, 0, nullptr); });
+  // default schedules: the plateau learning rate, no exploration, the reference's window (100 episodes, 97 successes) and no episode budget
+  const double a0 = cfg->alpha_min; const double e0 = 0.0;
+  if (!rc) rc = dql_ensemble_set_schedules(x, &a0, 1, &e0, 1, 100, 97, INT32_MAX);
+  if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(DQL_EHIP, "hipDeviceSynchronize failed");
+  if (rc) { ens_free(x); return rc; }
+  *out = x;
+  return DQL_OK;
+}
+int dql_ensemble_destroy(dql_ensemble* x) {
+  if (!x) return DQL_OK;
+  (void)hipSetDevice(x->device);
+  (void)hipDeviceSynchronize();
+  ens_free(x);
+  return DQL_OK;
+}
+int dql_ensemble_n_learners(dql_ensemble* x, int64_t* n) {
+  CHECK_ENS(x);
+  if (!n) return fail(DQL_EINVAL, "null pointer");
+  *n = x->n;
+  return DQL_OK;
+}
+// the checks and the exploration-table upload dql_ensemble_set_schedules and dql_ensemble_set_level_schedules share (who: the call's name, the prefix of its error texts)
+static int ens_check_promotion(const std::string& who, int32_t window, int32_t min_successes, int32_t max_episodes) {
+  if (window < 1 || window > DQL_ENSEMBLE_MAX_WINDOW) return fail(DQL_EINVAL, who + ": the promotion window must be in 1..128 (DQL_ENSEMBLE_MAX_WINDOW)");
+  if (min_successes < 1 || max_episodes < 1) return fail(DQL_EINVAL, who + ": min_successes and max_episodes must be positive");
+  return DQL_OK;
+}
+// range check, then (the device idle) the rates as eps_threshold words in a new device table the ensemble owns
+static int ens_upload_eps(dql_ensemble* x, const std::string& who, const double* eps, int32_t n_eps, uint32_t** d_out) {
+  for (int i = 0; i < n_eps; ++i) if (!(eps[i] >= 0.0 && eps[i] <= 1.0)) return fail(DQL_EINVAL, who + ": exploration rates must be in [0, 1]");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<uint32_t> thr((size_t)n_eps);
+  for (int i = 0; i < n_eps; ++i) thr[(size_t)i] = eps_threshold(eps[i]);
+  if (x->dev.alloc((void**)d_out, (size_t)n_eps * sizeof(uint32_t)) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc failed");
+  if (hipMemcpy(*d_out, thr.data(), (size_t)n_eps * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) { (void)x->dev.release(*d_out); return fail(DQL_EHIP, "hipMemcpy failed"); }
+  return DQL_OK;
+}
+int dql_ensemble_set_schedules(dql_ensemble* x, const double* alpha, int32_t n_alpha, const double* eps, int32_t n_eps, int32_t window, int32_t min_successes,
+                               int32_t max_episodes) {
+  CHECK_ENS(x);
+  if (!alpha || !eps) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: null table");
+  if (n_alpha < 1 || n_alpha > (1 << 22) || n_eps < 1 || n_eps > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: table lengths must be in 1..2^22");
+  int rc = ens_check_promotion("dql_ensemble_set_schedules", window, min_successes, max_episodes); if (rc) return rc;
+  for (int i = 0; i < n_alpha; ++i) if (!(alpha[i] >= 0.0 && alpha[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: learning rates must be in [0, 1]");
+  double* d_a = nullptr; uint32_t* d_e = nullptr;
+  rc = ens_upload_eps(x, "dql_ensemble_set_schedules", eps, n_eps, &d_e); if (rc) return rc;
+  if (x->dev.alloc((void**)&d_a, (size_t)n_alpha * sizeof(double)) != hipSuccess) { (void)x->dev.release(d_e); return fail(DQL_ENOMEM, "hipMalloc failed"); }
+  if (hipMemcpy(d_a, alpha, (size_t)n_alpha * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)x->dev.release(d_a); (void)x->dev.release(d_e);
+    return fail(DQL_EHIP, "hipMemcpy failed");
+  }
+  (void)x->dev.release(x->alpha_tab); (void)x->dev.release(x->eps_tab);  // the tables they replace
+  x->alpha_tab = d_a; x->eps_tab = d_e;
+  x->sched = LearnSched{d_a, n_alpha, x->cfg.alpha_min, d_e, n_eps, window, min_successes, max_episodes};
+  return DQL_OK;
+}
+int dql_ensemble_rearm(dql_ensemble* x) {
+  CHECK_ENS(x);
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  return ens_rearm(x);
+}
+int dql_ensemble_set_level(dql_ensemble* x, int32_t k) {
+  CHECK_ENS(x);
+  if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_level: curriculum step must be in 0..4");
+  if (x->advance_every && k > x->rule.last_level)
+    return fail(DQL_EINVAL, "dql_ensemble_set_level: in curriculum mode the level must not exceed last_level (raise it with dql_ensemble_set_curriculum first); nothing was changed");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  x->cfg.working_curriculum_step = k;
+  int rc = upload_mdpk(x->cfg, x->mdpk); if (rc) return rc;
+  hipLaunchKernelGGL(k_mark_reset, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->si, (const uint8_t*)nullptr, (long long)x->n);  // every env re-enters through reset
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  rc = ens_set_levels(x, k); if (rc) return rc;
+  return ens_rearm(x);
+}
+int dql_ensemble_n_live(dql_ensemble* x, int64_t* n_live) {
+  CHECK_ENS(x);
+  if (!n_live) return fail(DQL_EINVAL, "null pointer");
+  HIP_TRY(hipSetDevice(x->device));
+  std::vector<int> h((size_t)x->n);
+  HIP_TRY(hipMemcpy(h.data(), x->mem.frozen, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+  int64_t live = 0;
+  for (int v : h) live += v ? 0 : 1;
+  *n_live = live;
+  return DQL_OK;
+}
+// frozen, level and promoted of every learner -> host; the learners that are not finished for good
+static int ens_fetch_levels(dql_ensemble* x, std::vector<int>& frozen, std::vector<int>& level, std::vector<int>& promoted, int64_t* unfinished) {
+  const size_t n = (size_t)x->n;
+  frozen.resize(n); level.resize(n); promoted.resize(n);
+  HIP_TRY(hipMemcpy(frozen.data(), x->mem.frozen, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(level.data(), x->adv.level, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(promoted.data(), x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
+  int64_t u = 0;
+  for (size_t l = 0; l < n; ++l) u += learner_finished(frozen[l], level[l], promoted[l], x->rule) ? 0 : 1;
+  *unfinished = u;
+  return DQL_OK;
+}
+// dql_ensemble_run in curriculum mode: the launches are cut at the multiples of advance_every; at such a period index j, before period j is flown, every
+// learner takes advance_learner's step; each launch flies the live learners regrouped by level (build_worklist)
+static int ens_run_levels(dql_ensemble* x, int64_t periods) {
+  std::vector<int> frozen, level, promoted;
+  int64_t unfinished = 0;
+  int rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
+  // the level a learner stands on is flown whatever last_level says, so its schedule is asked for first; then every level on its way up to last_level
+  for (size_t l = 0; l < (size_t)x->n; ++l) {
+    bool ok = level[l] >= 0 && level[l] < DQL_MAX_LEVELS && x->have_lv[level[l]];
+    for (int k = level[l] + 1; ok && k <= x->rule.last_level && k < DQL_MAX_LEVELS; ++k) ok = x->have_lv[k];
+    if (!ok) return fail(DQL_EINVAL, "dql_ensemble_run: curriculum mode needs dql_ensemble_set_level_schedules for every level from the learners' up to last_level; nothing was launched");
+  }
+  EvTimer timer;
+  rc = timer.start(); if (rc) return rc;
+  std::vector<int> worklist((size_t)x->wl_slots), wave_level((size_t)(x->wl_slots / ADV_WAVE));
+  const long long E = x->advance_every;
+  long long left = periods;
+  while (left > 0) {
+    if (x->j % E == 0) {  // an advance point
+      hipLaunchKernelGGL(k_ens_advance, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->mem, x->adv, x->rule, x->si, (long long)x->j, (int)DQL_CELLS_PER_LEVEL);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipDeviceSynchronize());
+    }
+    rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
+    if (unfinished == 0) { x->j += left; break; }  // nothing left to fly or to advance, now or later (the period index still advances by `periods`)
+    const long long to_point = E - x->j % E;
+    const int k = (int)(left < to_point ? left : to_point);  // <= advance_every <= LEARN_MAX_PERIODS
+    unsigned long long wl_faults = 0ull;
+    const int n_waves = build_worklist(frozen.data(), level.data(), x->n, worklist.data(), wave_level.data(), x->wl_slots, &wl_faults);
+    if (wl_faults) {
+      unsigned long long v = 0;
+      HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
+      v += wl_faults;
+      HIP_TRY(hipMemcpy(x->mem.faults, &v, sizeof(v), hipMemcpyHostToDevice));
+    }
+    if (n_waves > 0) {  // (nobody live: everyone unfinished waits for the next advance point)
+      HIP_TRY(hipMemcpy(x->d_worklist, worklist.data(), (size_t)n_waves * ADV_WAVE * sizeof(int), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(x->d_wave_level, wave_level.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
+      rc = ens_fly(x, k, n_waves, true); if (rc) return rc;
+    }
+    x->j += k; left -= k;
+  }
+  return timer.stop_ms(&x->last_ms);
+}
+int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
+  CHECK_ENS(x);
+  if (periods < 1 || periods > (1ll << 40)) return fail(DQL_EINVAL, "dql_ensemble_run: periods must be in 1..2^40; nothing was launched");
+  HIP_TRY(hipSetDevice(x->device));
+  if (x->advance_every) return ens_run_levels(x, periods);
+  int rc = DQL_OK;
+  EvTimer timer;
+  rc = timer.start(); if (rc) return rc;
+  long long left = periods;
+  while (left > 0) {
+    const int k = (int)(left < LEARN_MAX_PERIODS ? left : LEARN_MAX_PERIODS);
+    if (left != periods) {  // between the launches of a long run: nothing left to fly ends it (the period index still advances by `periods`)
+      int64_t live = 0;
+      rc = dql_ensemble_n_live(x, &live); if (rc) return rc;
+      if (live == 0) { x->j += left; break; }
+    }
+    rc = ens_fly(x, k, (int)((x->n + 63) / 64), false); if (rc) return rc;
+    x->j += k; left -= k;
+  }
+  return timer.stop_ms(&x->last_ms);
+}
+// ---- per-learner curriculum levels (DESIGN.md section 14) ----
+int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t advance_every, const double* ratios, int32_t advance_exhausted) {
+  CHECK_ENS(x);
+  if (advance_every < 0 || advance_every > ADV_MAX_EVERY) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_every must be in 0..4096 (0 turns the mode off); nothing was changed");
+  if (advance_every == 0) {
+    // the plain launch flies everyone at the config's level: switching off is refused while a learner stands on another one (dql_ensemble_set_level first)
+    if (x->advance_every) {
+      HIP_TRY(hipSetDevice(x->device));
+      HIP_TRY(hipDeviceSynchronize());
+      std::vector<int> lv((size_t)x->n);
+      HIP_TRY(hipMemcpy(lv.data(), x->adv.level, lv.size() * sizeof(int), hipMemcpyDeviceToHost));
+      for (int v : lv)
+        if (v != x->cfg.working_curriculum_step)
+          return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the mode cannot be switched off (advance_every = 0) while learners stand on different levels; call dql_ensemble_set_level first; nothing was changed");
+    }
+    x->advance_every = 0;
+    return DQL_OK;
+  }
+  if (!ratios) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: null ratios; nothing was changed");
+  for (int k = 0; k < DQL_MAX_LEVELS; ++k) if (!std::isfinite(ratios[k])) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the five transfer ratios must be finite; nothing was changed");
+  if (advance_exhausted != 0 && advance_exhausted != 1) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_exhausted must be 0 or 1; nothing was changed");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<int> level((size_t)x->n);
+  HIP_TRY(hipMemcpy(level.data(), x->adv.level, level.size() * sizeof(int), hipMemcpyDeviceToHost));
+  int top = 0;
+  for (int v : level) top = v > top ? v : top;
+  if (last_level < top || last_level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: last_level must lie between the learners' current level and 4; nothing was changed");
+  int rc = ens_upload_mdpk5(x); if (rc) return rc;
+  for (int k = 0; k < DQL_MAX_LEVELS; ++k) x->rule.ratios[k] = ratios[k];
+  x->rule.last_level = last_level; x->rule.advance_exhausted = advance_exhausted;
+  x->advance_every = advance_every;
+  return DQL_OK;
+}
+int dql_ensemble_set_level_schedules(dql_ensemble* x, int32_t level, const double* eps, int32_t n_eps, int32_t window, int32_t min_successes, int32_t max_episodes) {
+  CHECK_ENS(x);
+  if (level < 0 || level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: the level must be in 0..4");
+  if (!eps) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: null table");
+  if (n_eps < 1 || n_eps > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: the table length must be in 1..2^22");
+  int rc = ens_check_promotion("dql_ensemble_set_level_schedules", window, min_successes, max_episodes); if (rc) return rc;
+  uint32_t* d_e = nullptr;
+  rc = ens_upload_eps(x, "dql_ensemble_set_level_schedules", eps, n_eps, &d_e); if (rc) return rc;
+  LevelSched lv[DQL_MAX_LEVELS];
+  for (int k = 0; k < DQL_MAX_LEVELS; ++k) lv[k] = x->h_lv[k];
+  lv[level] = LevelSched{d_e, n_eps, window, min_successes, max_episodes};
+  if (hipMemcpy(x->d_lv, lv, sizeof(lv), hipMemcpyHostToDevice) != hipSuccess) { (void)x->dev.release(d_e); return fail(DQL_EHIP, "hipMemcpy failed"); }
+  (void)x->dev.release((void*)x->h_lv[level].eps_tab);  // the table it replaces
+  x->h_lv[level] = lv[level]; x->have_lv[level] = true;
+  return DQL_OK;
+}
+int dql_ensemble_get_levels(dql_ensemble* x, int32_t* level, int32_t* promoted_at, int32_t* episodes_at, int64_t* entered_period) {
+  CHECK_ENS(x);
+  if (!level || !promoted_at || !episodes_at || !entered_period) return fail(DQL_EINVAL, "dql_ensemble_get_levels: null array");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t n = (size_t)x->n;
+  HIP_TRY(hipMemcpy(level, x->adv.level, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(promoted_at, x->adv.promoted_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(episodes_at, x->adv.episodes_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(entered_period, x->adv.entered_period, (size_t)DQL_MAX_LEVELS * n * sizeof(long long), hipMemcpyDeviceToHost));
+  // the level a learner stands on has no history entry yet: its row shows the counters as they are
+  std::vector<int> promoted(n), lvl_eps(n);
+  HIP_TRY(hipMemcpy(promoted.data(), x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(lvl_eps.data(), x->mem.level_episodes, n * sizeof(int), hipMemcpyDeviceToHost));
+  for (size_t l = 0; l < n; ++l) {
+    const int k = level[l];
+    if (k < 0 || k >= DQL_MAX_LEVELS) continue;
+    promoted_at[(size_t)k * n + l] = promoted[l]; episodes_at[(size_t)k * n + l] = lvl_eps[l];
+  }
+  return DQL_OK;
+}
+int dql_ensemble_n_unfinished(dql_ensemble* x, int64_t* n) {
+  CHECK_ENS(x);
+  if (!n) return fail(DQL_EINVAL, "null pointer");
+  if (!x->advance_every) return dql_ensemble_n_live(x, n);
+  HIP_TRY(hipSetDevice(x->device));
+  std::vector<int> frozen, level, promoted;
+  return ens_fetch_levels(x, frozen, level, promoted, n);
+}
+int dql_ensemble_get_period_index(dql_ensemble* x, int64_t* j) {
+  CHECK_ENS(x);
+  if (!j) return fail(DQL_EINVAL, "null pointer");
+  *j = x->j;
+  return DQL_OK;
+}
+int dql_ensemble_transfer(dql_ensemble* x, int32_t k, double ratio) {
+  CHECK_ENS(x);
+  if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_transfer: curriculum step must be in 0..4");
+  HIP_TRY(hipSetDevice(x->device));
+  const long long total = x->n * DQL_CELLS_PER_LEVEL;
+  hipLaunchKernelGGL(k_ens_transfer, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, x->mem.qa, x->mem.qb, (long long)x->n, (int)k,
+                     (int)((k - 1 + DQL_MAX_LEVELS) % DQL_MAX_LEVELS), ratio);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  return DQL_OK;
+}
+static int ens_slice(dql_ensemble* x, int64_t first, int64_t count, const char* who) {
+  if (first < 0 || count < 1 || first > x->n || count > x->n - first) return fail(DQL_EINVAL, std::string(who) + ": the slice [first, first + count) must lie inside [0, n_learners) and hold at least one learner");
+  return DQL_OK;
+}
+int dql_ensemble_get_tables(dql_ensemble* x, int64_t first, int64_t count, double* qa_or_null, double* qb_or_null, double* count_or_null) {
+  CHECK_ENS(x);
+  int rc = ens_slice(x, first, count, "dql_ensemble_get_tables"); if (rc) return rc;
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t off = (size_t)first * DQL_N_CELLS, bytes = (size_t)count * DQL_N_CELLS * sizeof(double);
+  if (qa_or_null) HIP_TRY(hipMemcpy(qa_or_null, x->mem.qa + off, bytes, hipMemcpyDeviceToHost));
+  if (qb_or_null) HIP_TRY(hipMemcpy(qb_or_null, x->mem.qb + off, bytes, hipMemcpyDeviceToHost));
+  if (count_or_null) HIP_TRY(hipMemcpy(count_or_null, x->mem.count + off, bytes, hipMemcpyDeviceToHost));
+  return DQL_OK;
+}
+int dql_ensemble_set_tables(dql_ensemble* x, int64_t first, int64_t count, const double* qa_or_null, const double* qb_or_null, const double* count_or_null) {
+  CHECK_ENS(x);
+  int rc = ens_slice(x, first, count, "dql_ensemble_set_tables"); if (rc) return rc;
+  if (count_or_null)  // the counters index the learning-rate table on the device
+    for (size_t i = 0; i < (size_t)count * DQL_N_CELLS; ++i)
+      if (!(count_or_null[i] >= 0.0 && count_or_null[i] < 9007199254740992.0)) return fail(DQL_EINVAL, "dql_ensemble_set_tables: visit counters must be in [0, 2^53)");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t off = (size_t)first * DQL_N_CELLS, bytes = (size_t)count * DQL_N_CELLS * sizeof(double);
+  if (qa_or_null) HIP_TRY(hipMemcpy(x->mem.qa + off, qa_or_null, bytes, hipMemcpyHostToDevice));
+  if (qb_or_null) HIP_TRY(hipMemcpy(x->mem.qb + off, qb_or_null, bytes, hipMemcpyHostToDevice));
+  if (count_or_null) HIP_TRY(hipMemcpy(x->mem.count + off, count_or_null, bytes, hipMemcpyHostToDevice));
+  return DQL_OK;
+}
+int dql_ensemble_get_counters(dql_ensemble* x, int64_t* decisions, int64_t* episodes, int64_t* successes, int64_t* by_code, int32_t* promoted, int32_t* level_episodes,
+                              uint8_t* frozen) {
+  CHECK_ENS(x);
+  if (!decisions || !episodes || !successes || !by_code || !promoted || !level_episodes || !frozen) return fail(DQL_EINVAL, "dql_ensemble_get_counters: null array");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t n = (size_t)x->n;
+  std::vector<int> h(n);
+  HIP_TRY(hipMemcpy(decisions, x->mem.decisions, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(by_code, x->mem.by_code, (size_t)DQL_N_CHECK_CODES * n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h.data(), x->mem.episodes, n * sizeof(int), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; ++i) episodes[i] = h[i];
+  HIP_TRY(hipMemcpy(h.data(), x->mem.successes, n * sizeof(int), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; ++i) successes[i] = h[i];
+  HIP_TRY(hipMemcpy(promoted, x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(level_episodes, x->mem.level_episodes, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h.data(), x->mem.frozen, n * sizeof(int), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; ++i) frozen[i] = h[i] ? 1 : 0;
+  return DQL_OK;
+}
+int dql_ensemble_get_episode_log(dql_ensemble* x, uint8_t* code, uint16_t* length, int32_t capacity, int32_t* n_episodes) {
+  CHECK_ENS(x);
+  if (!code || !length || !n_episodes) return fail(DQL_EINVAL, "dql_ensemble_get_episode_log: null array");
+  if (capacity != x->mem.log_cap || capacity < 1) return fail(DQL_EINVAL, "dql_ensemble_get_episode_log: capacity must be the (positive) log capacity the ensemble was created with");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t n = (size_t)x->n * (size_t)capacity;
+  HIP_TRY(hipMemcpy(code, x->mem.log_code, n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(length, x->mem.log_len, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n_episodes, x->mem.log_n, (size_t)x->n * sizeof(int), hipMemcpyDeviceToHost));
+  return DQL_OK;
+}
+int dql_ensemble_get_state(dql_ensemble* x, double* reals, int32_t* ints) {
+  CHECK_ENS(x);
+  if (!reals || !ints) return fail(DQL_EINVAL, "dql_ensemble_get_state: null array");
+  HIP_TRY(hipSetDevice(x->device));
+  const long long n = x->n;
+  int rc = by_dtype(x->cfg.dtype, [&](auto t) -> int {
+    std::vector<decltype(t)> h((size_t)NQ_REAL * n * 4);
+    HIP_TRY(hipMemcpy(h.data(), x->sr, h.size() * sizeof(t), hipMemcpyDeviceToHost));
+    quads_to_fields(h.data(), n, reals);
+    return DQL_OK;
+  });
+  if (rc) return rc;
+  std::vector<int4> h((size_t)n);
+  HIP_TRY(hipMemcpy(h.data(), x->si, (size_t)n * sizeof(int4), hipMemcpyDeviceToHost));
+  unpack_ints(h.data(), n, ints);
+  return DQL_OK;
+}
+int dql_ensemble_index_faults(dql_ensemble* x, int64_t* n) {
+  CHECK_ENS(x);
+  if (!n) return fail(DQL_EINVAL, "null pointer");
+  HIP_TRY(hipSetDevice(x->device));
+  unsigned long long v = 0;
+  HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
+  *n = (int64_t)v;
+  return DQL_OK;
+}
+// the learners' tables are read where they live (the ensemble's device arrays are [L][DQL_N_CELLS] double already): k_score only reads them and touches nothing else of the ensemble
+int dql_ensemble_score(dql_ensemble* x, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env, uint64_t seed,
+                       int32_t max_steps, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null) {
+  CHECK_ENS(x);
+  int rc = check_config(eval_cfg); if (rc) return rc;
+  rc = score_check("dql_ensemble_score", count, envs_per_learner, episodes_per_env, max_steps, by_code, steps_sum, ep_code_or_null, ep_steps_or_null); if (rc) return rc;
+  if (first < 0 || first > x->n || count > x->n - first) return fail(DQL_EINVAL, "dql_ensemble_score: the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t off = (size_t)first * DQL_N_CELLS;
+  return score_run(eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, x->mem.qa + off, x->mem.qb + off, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
+}
+int dql_diag_ensemble_launches(dql_ensemble* x, int64_t* launches, int64_t* periods, int64_t* wave_periods) {
+  CHECK_ENS(x);
+  if (!launches || !periods || !wave_periods) return fail(DQL_EINVAL, "null pointer");
+  *launches = x->n_launches; *periods = x->launched_periods; *wave_periods = x->launched_wave_periods;
+  return DQL_OK;
+}
+int dql_diag_ensemble_last(dql_ensemble* x, double* run_ms) {
+  CHECK_ENS(x);
+  if (!run_ms) return fail(DQL_EINVAL, "null pointer");
+  if (x->last_ms < 0.0) return fail(DQL_ESTATE, "no dql_ensemble_run call has completed on this ensemble");
+  *run_ms = x->last_ms;
+  return DQL_OK;
+}
+}  // extern "C"

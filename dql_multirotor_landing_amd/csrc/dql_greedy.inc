@@ -1,0 +1,249 @@
+// dql_greedy.inc: greedy flight of given tables in one launch: the roll-outs with flight records (dql_rollout, DESIGN.md section 11) and the scorer (dql_score,
+// DESIGN.md section 13; score_check / score_run also serve dql_ensemble_score).  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail /
+// HIP_TRY, by_dtype_axes, DevBuf / OP_PROLOGUE / UP / OUT / DOWN, upload_mdpk, upload_schedule, EvTimer, check_config, TickLds; and dql_rollout.hpp, dql_score.hpp.
+// ---- greedy roll-outs (dql_rollout, DESIGN.md section 11) ----
+// One env per lane flies its FIRST episode from reset to termination (csrc/dql_rollout.hpp: rollout_episode); workgroups of one wave: evaluation batches are
+// small, a lone wave per SIMD needs no LDS staging, no barrier, and there are no accumulators, table-writer blocks or statistics here.  Table set k serves
+// blocks [k B, (k + 1) B), B = envs_per_table / 64, so that the set's tables are a wave-uniform pointer; env i of every set has env id i (paired episodes).
+// The tick schedule of periods 0 .. max_steps sits in a device buffer read as constant memory (scalar loads by the wave-uniform period counter).
+template <typename T> struct RolloutArgs {
+  SimK<T> c;
+  const MdpK<T> DQL_CONST_AS* mdp;
+  MdpRun<T> mdp_run;
+  RolloutInit<T> init;
+  const double* qa; const double* qb;                                  // [n_tables][DQL_N_CELLS]
+  const long long DQL_CONST_AS* mgr0; const int DQL_CONST_AS* sched;   // [max_steps + 1] (fill_schedule)
+  RolloutOut out;
+  unsigned long long seed;
+  int blocks_per_table, max_steps;
+};
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_rollout(RolloutArgs<T> a) {
+  const int tid = threadIdx.x;
+  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
+  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
+  const long long g = (long long)blockIdx.x * 64 + tid;                // output column: every lane of the grid is an env (envs_per_table is a multiple of 64)
+  // the launch's constants in the layout's form, as k_step makes them for a 64-thread workgroup
+  SimK<T> cl = a.c;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
+  const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
+  const bool trace_wave = a.out.trace != nullptr && blockIdx.x == 0;   // the first trace_envs <= 64 envs of table set 0: wave 0 of the grid, nobody else
+  rollout_episode<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.mgr0, a.sched, kv, a.out, g, trace_wave,
+                               trace_wave && tid < a.out.trace_envs);
+}
+
+// ---- greedy scoring (dql_score / dql_ensemble_score, DESIGN.md section 13) ----
+// k_rollout's shape — one env per lane, workgroups of one wave, table set k serves blocks [k B, (k + 1) B), env i of every set has RNG key (i, seed) — but a
+// lane flies episode after episode (csrc/dql_score.hpp: score_episodes) and what leaves the wave is its tally: one atomicAdd per non-zero column into the
+// table set's row of a buffer zeroed before the launch.  Integer sums: the result does not depend on the order the waves arrive in.
+template <typename T> struct ScoreArgs {
+  SimK<T> c;
+  const MdpK<T> DQL_CONST_AS* mdp;
+  MdpRun<T> mdp_run;
+  RolloutInit<T> init;
+  const double* qa; const double* qb;                                  // [n_tables][DQL_N_CELLS]
+  const long long DQL_CONST_AS* mgr0; const int DQL_CONST_AS* sched;   // [max_steps + 1] (fill_schedule)
+  unsigned long long* by_code;                                         // [n_tables][SCORE_N_COLS]
+  unsigned long long* steps_sum;                                       // [n_tables]
+  ScoreLog log;
+  unsigned long long seed;
+  int blocks_per_table, max_steps, episodes;
+};
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_score(ScoreArgs<T> a) {
+  const int tid = threadIdx.x;
+  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
+  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
+  const long long g = (long long)blockIdx.x * 64 + tid;                // log column: every lane of the grid is an env (envs_per_table is a multiple of 64)
+  SimK<T> cl = a.c;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
+  const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
+  const ScoreTally t = score_episodes<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.episodes, a.mgr0, a.sched, kv, a.log, g);
+  if (tid == 0) {
+    unsigned long long* row = a.by_code + (size_t)k * SCORE_N_COLS;
+#pragma unroll
+    for (int col = 0; col < SCORE_N_COLS; ++col) if (t.by_code[col]) atomicAdd(&row[col], (unsigned long long)t.by_code[col]);
+    if (t.steps) atomicAdd(&a.steps_sum[k], t.steps);
+  }
+}
+
+// what RolloutArgs<T> and ScoreArgs<T> have in common (mgr0 / sched: device arrays of upload_schedule, mdpk: of upload_mdpk)
+template <typename T, typename A> static void fill_greedy_args(A& a, const dql_config& cfg, const void* mdpk, const double* qa, const double* qb, const void* mgr0, const void* sched,
+                                                               unsigned long long seed, long long envs_per_table, int max_steps) {
+  a.c = make_simk<T>(cfg);
+  a.mdp = (const MdpK<T> DQL_CONST_AS*)mdpk;
+  a.mdp_run = MdpRun<T>{cfg.gamma, (T)(cfg.t_max * cfg.f_ag), cfg.goal_logic};
+  a.init = make_rollout_init<T>(cfg);
+  a.qa = qa; a.qb = qb;
+  a.mgr0 = (const long long DQL_CONST_AS*)mgr0; a.sched = (const int DQL_CONST_AS*)sched;
+  a.seed = seed; a.blocks_per_table = (int)(envs_per_table / 64); a.max_steps = max_steps;
+}
+
+extern "C" {
+// ---- greedy roll-outs ----
+static thread_local double g_rollout_ms = -1.0;
+static thread_local int g_rollout_inst[3] = {0, 0, 0};
+int dql_rollout_n_fields(int32_t* n_record, int32_t* n_trace) { if (n_record) *n_record = RO_N_RECORD; if (n_trace) *n_trace = RO_N_TRACE; return DQL_OK; }
+const char* dql_rollout_field_name(int32_t i, int32_t is_trace) { return (i >= 0 && i < (is_trace ? RO_N_TRACE : RO_N_RECORD)) ? k_rollout_field_names[i] : nullptr; }
+int dql_rollout(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, uint64_t seed, int32_t max_steps, const double* qa, const double* qb,
+                int32_t* code, int32_t* steps, double* rec, int32_t trace_envs, double* trace_or_null) {
+  int rc = check_config(cfg); if (rc) return rc;
+  // every argument is checked before the device is touched: a refused call starts no kernel
+  if (n_tables < 1 || n_tables > DQL_ROLLOUT_MAX_TABLES) return fail(DQL_EINVAL, "dql_rollout: n_tables must be in 1..16 (DQL_ROLLOUT_MAX_TABLES); nothing was launched");
+  if (envs_per_table < 64 || envs_per_table % 64 != 0) return fail(DQL_EINVAL, "dql_rollout: envs_per_table must be a positive multiple of 64 (one wave per workgroup, whole waves per table set); nothing was launched");
+  if ((long long)n_tables * envs_per_table > (1ll << 30)) return fail(DQL_EINVAL, "dql_rollout: n_tables * envs_per_table must be at most 2^30; nothing was launched");
+  if (max_steps < 1 || max_steps > DQL_ROLLOUT_MAX_STEPS) return fail(DQL_EINVAL, "dql_rollout: max_steps must be in 1..4096 (DQL_ROLLOUT_MAX_STEPS); nothing was launched");
+  if (trace_envs < 0 || trace_envs > 64) return fail(DQL_EINVAL, "dql_rollout: trace_envs must be in 0..64 (the trace stays inside one wave); nothing was launched");
+  if (trace_envs > 0 && !trace_or_null) return fail(DQL_EINVAL, "dql_rollout: trace_envs > 0 needs a trace buffer; nothing was launched");
+  if (!qa || !qb || !code || !steps || !rec) return fail(DQL_EINVAL, "dql_rollout: null array; nothing was launched");
+  OP_PROLOGUE(device)
+  const long long n_total = (long long)n_tables * envs_per_table;
+  const int n_per = max_steps + 1;
+  DevBuf d_qa, d_qb, d_mgr0, d_sched, d_mdp, d_code, d_steps, d_rec, d_trace;
+  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
+  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
+  OUT(d_mgr0, (size_t)n_per * sizeof(long long)); OUT(d_sched, (size_t)n_per * sizeof(int)); OUT(d_mdp, mdpk_bytes(cfg->dtype));
+  rc = upload_schedule(*cfg, 0, n_per, d_mgr0.p, d_sched.p); if (rc) return rc;
+  rc = upload_mdpk(*cfg, d_mdp.p); if (rc) return rc;
+  OUT(d_code, (size_t)n_total * sizeof(int)); OUT(d_steps, (size_t)n_total * sizeof(int)); OUT(d_rec, (size_t)RO_N_RECORD * n_total * sizeof(double));
+  const size_t trace_bytes = (size_t)n_per * RO_N_TRACE * (size_t)trace_envs * sizeof(double);
+  if (trace_envs > 0) {
+    OUT(d_trace, trace_bytes);
+    HIP_TRY(hipMemset(d_trace.p, 0xff, trace_bytes));  // all ones = NaN: what a row keeps after its env's last period
+  }
+  const RolloutOut out{(int*)d_code.p, (int*)d_steps.p, (double*)d_rec.p, trace_envs > 0 ? (double*)d_trace.p : nullptr, n_total, trace_envs};
+  EvTimer timer;
+  rc = timer.start(); if (rc) return rc;
+  by_dtype_axes(cfg->dtype, cfg->two_axis, [&](auto t, auto xmode) {
+    using T = decltype(t);
+    constexpr int XMODE = decltype(xmode)::value;
+    RolloutArgs<T> a;
+    fill_greedy_args<T>(a, *cfg, d_mdp.p, (const double*)d_qa.p, (const double*)d_qb.p, d_mgr0.p, d_sched.p, seed, envs_per_table, max_steps);
+    a.out = out;
+    g_rollout_inst[0] = (int)sizeof(T); g_rollout_inst[1] = TICK_PLAIN; g_rollout_inst[2] = XMODE;
+    hipLaunchKernelGGL((k_rollout<T, TICK_PLAIN, XMODE>), dim3((unsigned)((long long)n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
+  });
+  HIP_TRY(hipGetLastError());
+  double ms = 0.0;
+  rc = timer.stop_ms(&ms); if (rc) return rc;
+  DOWN(code, d_code, (size_t)n_total * sizeof(int));
+  DOWN(steps, d_steps, (size_t)n_total * sizeof(int));
+  DOWN(rec, d_rec, (size_t)RO_N_RECORD * n_total * sizeof(double));
+  if (trace_envs > 0) DOWN(trace_or_null, d_trace, trace_bytes);
+  g_rollout_ms = ms;
+  return DQL_OK;
+}
+// kernel time and instance (sizeof(T), TICK, XMODE) of this thread's latest completed call
+static int diag_last(double ms, const int* inst, double* kernel_ms, int32_t* out3, const char* none_yet) {
+  if (!kernel_ms || !out3) return fail(DQL_EINVAL, "null pointer");
+  if (ms < 0.0) return fail(DQL_ESTATE, none_yet);
+  *kernel_ms = ms;
+  for (int k = 0; k < 3; ++k) out3[k] = inst[k];
+  return DQL_OK;
+}
+int dql_diag_rollout_last(double* kernel_ms, int32_t* out3) { return diag_last(g_rollout_ms, g_rollout_inst, kernel_ms, out3, "no dql_rollout call has completed on this thread"); }
+
+// ---- greedy scoring ----
+static thread_local double g_score_ms = -1.0;
+static thread_local int g_score_inst[3] = {0, 0, 0};
+// every argument both entry points share, checked before the device is touched: a refused call starts no kernel
+static int score_check(const char* who, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, int32_t max_steps, const int64_t* by_code, const int64_t* steps_sum,
+                       const uint8_t* ep_code, const uint16_t* ep_steps) {
+  const std::string w(who);
+  if (n_tables < 1 || n_tables > DQL_SCORE_MAX_TABLES) return fail(DQL_EINVAL, w + ": the number of table sets must be in 1..2^20 (DQL_SCORE_MAX_TABLES); nothing was launched");
+  if (envs_per_table < 64 || envs_per_table % 64 != 0) return fail(DQL_EINVAL, w + ": the envs per table set must be a positive multiple of 64 (one wave per workgroup, whole waves per table set); nothing was launched");
+  if (envs_per_table > (1ll << 30) || n_tables * envs_per_table > (1ll << 30)) return fail(DQL_EINVAL, w + ": table sets x envs must be at most 2^30; nothing was launched");
+  if (episodes_per_env < 1 || episodes_per_env > DQL_SCORE_MAX_EPISODES) return fail(DQL_EINVAL, w + ": episodes_per_env must be in 1..64 (DQL_SCORE_MAX_EPISODES); nothing was launched");
+  if (max_steps < 1 || max_steps > DQL_SCORE_MAX_STEPS) return fail(DQL_EINVAL, w + ": max_steps must be in 1..4096 (DQL_SCORE_MAX_STEPS); nothing was launched");
+  if ((ep_code == nullptr) != (ep_steps == nullptr)) return fail(DQL_EINVAL, w + ": the episode log needs both arrays or neither; nothing was launched");
+  if (!by_code || !steps_sum) return fail(DQL_EINVAL, w + ": null array; nothing was launched");
+  return DQL_OK;
+}
+// d_qa / d_qb: [n_tables][DQL_N_CELLS] on the current device
+static int score_run(const dql_config* cfg, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, const double* d_qa, const double* d_qb,
+                     int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code, uint16_t* ep_steps) {
+  const long long n_total = n_tables * envs_per_table;
+  const int n_per = max_steps + 1;
+  DevBuf d_mgr0, d_sched, d_mdp, d_sums, d_code, d_steps;
+  OUT(d_mgr0, (size_t)n_per * sizeof(long long)); OUT(d_sched, (size_t)n_per * sizeof(int)); OUT(d_mdp, mdpk_bytes(cfg->dtype));
+  int rc = upload_schedule(*cfg, 0, n_per, d_mgr0.p, d_sched.p); if (rc) return rc;
+  rc = upload_mdpk(*cfg, d_mdp.p); if (rc) return rc;
+  // one buffer for both sums: [n_tables][SCORE_N_COLS] counts, then [n_tables] step totals
+  const size_t sums_bytes = (size_t)n_tables * (SCORE_N_COLS + 1) * sizeof(unsigned long long);
+  OUT(d_sums, sums_bytes);
+  HIP_TRY(hipMemset(d_sums.p, 0, sums_bytes));
+  const size_t log_n = (size_t)episodes * (size_t)n_total;
+  if (ep_code) {
+    OUT(d_code, log_n); OUT(d_steps, log_n * sizeof(uint16_t));
+    HIP_TRY(hipMemset(d_code.p, 0xff, log_n));  // not finished
+    HIP_TRY(hipMemset(d_steps.p, 0, log_n * sizeof(uint16_t)));
+  }
+  unsigned long long* d_by_code = (unsigned long long*)d_sums.p;
+  unsigned long long* d_steps_sum = d_by_code + (size_t)n_tables * SCORE_N_COLS;
+  const ScoreLog log{(uint8_t*)d_code.p, (uint16_t*)d_steps.p, n_total};
+  EvTimer timer;
+  rc = timer.start(); if (rc) return rc;
+  by_dtype_axes(cfg->dtype, cfg->two_axis, [&](auto t, auto xmode) {
+    using T = decltype(t);
+    constexpr int XMODE = decltype(xmode)::value;
+    ScoreArgs<T> a;
+    fill_greedy_args<T>(a, *cfg, d_mdp.p, d_qa, d_qb, d_mgr0.p, d_sched.p, seed, envs_per_table, max_steps);
+    a.by_code = d_by_code; a.steps_sum = d_steps_sum; a.log = log; a.episodes = episodes;
+    g_score_inst[0] = (int)sizeof(T); g_score_inst[1] = TICK_PLAIN; g_score_inst[2] = XMODE;
+    hipLaunchKernelGGL((k_score<T, TICK_PLAIN, XMODE>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
+  });
+  HIP_TRY(hipGetLastError());
+  double ms = 0.0;
+  rc = timer.stop_ms(&ms); if (rc) return rc;
+  HIP_TRY(hipMemcpy(by_code, d_by_code, (size_t)n_tables * SCORE_N_COLS * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(steps_sum, d_steps_sum, (size_t)n_tables * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (ep_code) {
+    DOWN(ep_code, d_code, log_n);
+    DOWN(ep_steps, d_steps, log_n * sizeof(uint16_t));
+  }
+  g_score_ms = ms;
+  return DQL_OK;
+}
+int dql_score(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
+              const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null) {
+  int rc = check_config(cfg); if (rc) return rc;
+  rc = score_check("dql_score", n_tables, envs_per_table, episodes_per_env, max_steps, by_code, steps_sum, ep_code_or_null, ep_steps_or_null); if (rc) return rc;
+  if (!qa || !qb) return fail(DQL_EINVAL, "dql_score: null array; nothing was launched");
+  OP_PROLOGUE(device)
+  DevBuf d_qa, d_qb;
+  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
+  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
+  return score_run(cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, (const double*)d_qa.p, (const double*)d_qb.p, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
+}
+int dql_diag_score_last(double* kernel_ms, int32_t* inst3) { return diag_last(g_score_ms, g_score_inst, kernel_ms, inst3, "no dql_score or dql_ensemble_score call has completed on this thread"); }
+}  // extern "C"

@@ -11,7 +11,11 @@
 //                            the table update has no kernel and no time of its own (tables act with one period of delay).
 //   k_flush                  same fold outside a launch (host table access, level switch, rank sync).
 //   k_apply_window           multi-GPU: folds the all-reduced window accumulators into the base tables.
-//   small stateless kernels  drop-in single-call operators (discretise, mdp transition, predict, ordered update).
+//
+// This file is the root of the library's one translation unit.  It holds the error plumbing and the shared host helpers, the step engine (the kernels above,
+// dql_ctx, the step launch path, the dql_ctx calls, the dql_pop_* calls), and at its end includes one fragment per other subsystem, kernels and host code and
+// C calls together: dql_ops.inc (stateless operators), dql_greedy.inc (roll-outs, scorer), dql_ensemble.inc (sequential learners),
+// dql_agent.inc (drop-in agent), dql_comm.inc (RCCL, peer-to-peer exchange).
 #include <hip/hip_runtime.h>
 #include <limits>
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so is dlopen'ed on first use (dql_comm_*)
@@ -25,6 +29,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "dql_device.hpp"
@@ -48,6 +53,94 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
     if (_e != hipSuccess) return fail(DQL_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e));          \
   } while (0)
 #define CHECK_CTX(ctx) do { if (!(ctx)) return fail(DQL_EINVAL, "null context"); } while (0)
+
+// ---------------------------------------------------------------------------------------------
+// shared host helpers (this file and every subsystem file it includes)
+// ---------------------------------------------------------------------------------------------
+// the typed code for a run-time dtype: f(float{}) or f(double{}); by_dtype_axes adds the config's X_TWO / X_ONLY instance as a compile-time second argument
+template <typename F> static auto by_dtype(int dtype, F&& f) { return dtype == DQL_F32 ? f(float{}) : f(double{}); }
+template <typename F> static auto by_dtype_axes(int dtype, int two_axis, F&& f) {
+  return by_dtype(dtype, [&](auto t) { return two_axis ? f(t, std::integral_constant<int, X_TWO>{}) : f(t, std::integral_constant<int, X_ONLY>{}); });
+}
+static size_t mdpk_bytes(int dtype) { return by_dtype(dtype, [](auto t) { return sizeof(MdpK<decltype(t)>); }); }
+
+// device memory of one call (the stateless operators, the roll-outs, the scorer)
+struct DevBuf {
+  void* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  int alloc(size_t b) { hipError_t e = hipMalloc(&p, b ? b : 1); return e == hipSuccess ? 0 : -1; }
+};
+#define OP_PROLOGUE(device)                                                                \
+  int _ndev = 0;                                                                           \
+  HIP_TRY(hipGetDeviceCount(&_ndev));                                                      \
+  if (_ndev < 1) return fail(DQL_EHIP, "no HIP device visible (there is no CPU fallback)"); \
+  if ((device) < 0 || (device) >= _ndev) return fail(DQL_EINVAL, "device index out of range"); \
+  HIP_TRY(hipSetDevice(device));
+#define OUT(buf, bytes) do { if ((buf).alloc(bytes)) return fail(DQL_ENOMEM, "hipMalloc failed"); } while (0)
+#define UP(buf, host, bytes) do { OUT(buf, bytes); HIP_TRY(hipMemcpy((buf).p, (host), (bytes), hipMemcpyHostToDevice)); } while (0)
+#define DOWN(host, buf, bytes) HIP_TRY(hipMemcpy((host), (buf).p, (bytes), hipMemcpyDeviceToHost))
+
+namespace {  // (internal linkage: the library exports its C calls, not these)
+// the device memory an object owns for life: alloc() records what it hands out, so no member can be missing from a free list; release() frees one pointer early
+// (a table that is being replaced)
+struct DevOwned {
+  std::vector<void*> ptrs;
+  hipError_t alloc(void** p, size_t bytes) { const hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) adopt(*p); else *p = nullptr; return e; }
+  void adopt(void* p) { ptrs.push_back(p); }
+  hipError_t release(void* p) {
+    for (void*& q : ptrs) if (p && q == p) { q = ptrs.back(); ptrs.pop_back(); return hipFree(p); }
+    return hipSuccess;
+  }
+  void free_all() { for (void* p : ptrs) (void)hipFree(p); ptrs.clear(); }
+};
+// device time of a stretch of null-stream work: start(), the work, stop_ms() (which waits for the work)
+struct EvTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~EvTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+  int start() { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, 0)); return DQL_OK; }
+  int stop_ms(double* ms) {
+    HIP_TRY(hipEventRecord(e1, 0));
+    HIP_TRY(hipEventSynchronize(e1));
+    float f = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&f, e0, e1));
+    *ms = (double)f;
+    return DQL_OK;
+  }
+};
+}  // namespace
+
+// make_mdpk<T>(cfg) -> device memory at dst: a synchronous copy, or on stream st followed by its synchronisation (the source is a stack temporary)
+static int upload_mdpk(const dql_config& cfg, void* dst, hipStream_t st = nullptr) {
+  return by_dtype(cfg.dtype, [&](auto t) -> int {
+    const MdpK<decltype(t)> m = make_mdpk<decltype(t)>(cfg);
+    if (!st) { HIP_TRY(hipMemcpy(dst, &m, sizeof(m), hipMemcpyHostToDevice)); return DQL_OK; }
+    HIP_TRY(hipMemcpyAsync(dst, &m, sizeof(m), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DQL_OK;
+  });
+}
+// the tick schedule of periods j0 .. j0 + n - 1 (fill_schedule) -> device arrays of at least n entries (synchronous copies)
+static int upload_schedule(const dql_config& cfg, long long j0, int n, void* d_mgr0, void* d_sched) {
+  std::vector<long long> h_mgr0((size_t)n);
+  std::vector<int> h_sched((size_t)n);
+  fill_schedule(cfg, j0, h_mgr0.data(), h_sched.data(), n);
+  HIP_TRY(hipMemcpy(d_mgr0, h_mgr0.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_sched, h_sched.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  return DQL_OK;
+}
+// the real state as the device holds it, Quad<T>[NQ_REAL][n], <-> field-major doubles [NF_REAL][n]; the packed discrete state int4[n] -> field-major ints [NF_INT][n]
+template <typename T> static void quads_to_fields(const T* h, long long n, double* out) {
+  for (int f = 0; f < NF_REAL; ++f) { const int q = f / 4, k = f % 4; for (long long i = 0; i < n; ++i) out[(long long)f * n + i] = (double)h[((size_t)q * n + i) * 4 + k]; }
+}
+template <typename T> static void fields_to_quads(const double* in, long long n, T* h) {
+  for (int f = 0; f < NF_REAL; ++f) { const int q = f / 4, k = f % 4; for (long long i = 0; i < n; ++i) h[((size_t)q * n + i) * 4 + k] = (T)in[(long long)f * n + i]; }
+}
+static void unpack_ints(const int4* h, long long n, int32_t* out) {
+  for (long long i = 0; i < n; ++i) {
+    out[0 * n + i] = h[i].x; out[1 * n + i] = h[i].y; out[2 * n + i] = h[i].z & 0xffff; out[3 * n + i] = (h[i].z >> 16) & 0xffff;
+    out[4 * n + i] = h[i].w & 0xff; out[5 * n + i] = (h[i].w >> 8) & 0xff; out[6 * n + i] = (h[i].w >> 16) & 0xff;
+  }
+}
 
 struct StatsDev { unsigned long long decisions, episodes, by_code[DQL_N_CHECK_CODES]; long long reward_fx; unsigned long long agent_steps, bad_actions; };
 
@@ -670,241 +763,6 @@ __global__ void k_transfer(double* qa, double* qb, int k, int src, double ratio)
   qb[k * DQL_CELLS_PER_LEVEL + i] = qb[src * DQL_CELLS_PER_LEVEL + i] * ratio;
 }
 
-// ---- stateless operators ----
-template <typename T> __global__ void k_discretise(MdpK<T> c, const double* p, const double* v, const double* acc, const double* ang, long long n, int* out) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = discretise(c, (T)p[i], (T)v[i], (T)acc[i], (T)ang[i]);
-}
-template <typename T>
-__global__ void k_mdp_transition(MdpK<T> c, long long n, uint32_t stages, const uint8_t* action, const double* obs, double* ms, const int* prev_idx,
-                                 int* idx_io, double* reward_out, uint8_t* done_out) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  T sp = (T)ms[0 * n + i], shp_p = (T)ms[1 * n + i], shp_v = (T)ms[2 * n + i], shp_a = (T)ms[3 * n + i], cum = (T)ms[4 * n + i];
-  int step_count = (int)ms[5 * n + i], cur_check = (int)ms[6 * n + i], code = (int)ms[7 * n + i];
-  const T px = (T)obs[0 * n + i], py = (T)obs[1 * n + i], vx = (T)obs[2 * n + i], ax = (T)obs[3 * n + i], pitch = (T)obs[4 * n + i], z = (T)obs[5 * n + i];
-  const bool contact = obs[6 * n + i] != 0.0;
-  if (stages & DQL_MDP_ACTION) sp = continuous_action(c, sp, (int)action[i]);
-  int idx = idx_io[i];
-  if (stages & DQL_MDP_DISCRETISE) { idx = discretise(c, px, vx, ax, pitch); idx_io[i] = idx; }
-  const int sidx = idx < 0 ? 0 : idx;
-  if (stages & DQL_MDP_CHECK) {
-    // SimulationMdp.check has no goal logic: feeding prev = -1 disables that branch (pkg/mdp.py:784-845)
-    code = mdp_check(c, step_count, cur_check, code, (stages & DQL_MDP_SIMULATION) ? -1 : prev_idx[i], sidx, contact, px, py, z);
-    done_out[i] = code <= DQL_TERMINAL_TIMEOUT;
-  }
-  if (stages & DQL_MDP_REWARD) reward_out[i] = (double)mdp_reward(c, shp_p, shp_v, shp_a, cum, code, sidx, px, vx, sp);
-  ms[0 * n + i] = sp; ms[1 * n + i] = shp_p; ms[2 * n + i] = shp_v; ms[3 * n + i] = shp_a; ms[4 * n + i] = cum;
-  ms[5 * n + i] = step_count; ms[6 * n + i] = cur_check; ms[7 * n + i] = code;
-}
-// the 100 Hz manager tick of the fused kernel (manager_states + manager_obs) replayed over scripted series, one lane per series
-template <typename T>
-__global__ void k_manager_run(SimK<T> c, long long n_series, long long n_ticks, const double* in, const uint8_t* contact, unsigned long long seed, double* out) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_series) return;
-  Env<T> e;
-  memset(&e, 0, sizeof(e));
-  e.kal_x_P = T(1.0); e.kal_y_P = T(1.0); e.mp_r = c.mp_r; e.mp_w = c.mp_w;
-  for (long long t = 0; t < n_ticks; ++t) {
-    const double* r = in + (i * n_ticks + t) * 14;
-    for (int k = 0; k < 3; ++k) { e.p[k] = (T)r[k]; e.v[k] = (T)r[3 + k]; }
-    for (int k = 0; k < 4; ++k) e.q[k] = (T)r[6 + k];
-    e.mp_x = (T)r[10]; e.mp_y = (T)r[11]; e.mp_u = (T)r[12]; e.mp_v = (T)r[13];
-    if (contact[i * n_ticks + t]) e.flags |= FL_CONTACT;
-    T R[9], cy, sy;
-    quat_to_R(e.q, R); yaw_cs(R, cy, sy);
-    manager_states(R, cy, sy, e.v[2], e.vz_state, e.yw_state);
-    manager_obs(c, e, cy, sy, t, (uint32_t)seed, (uint32_t)(seed >> 32), 0u, 0u, (uint32_t)i, (uint32_t)t);
-    double* o = out + (i * n_ticks + t) * 12;
-    o[0] = e.obs_px; o[1] = e.obs_py; o[2] = e.obs_vx; o[3] = e.obs_vy; o[4] = e.obs_ax; o[5] = e.obs_ay;
-    o[6] = e.vz_state; o[7] = e.yw_state; o[8] = e.mp_x; o[9] = e.mp_y; o[10] = e.mp_u; o[11] = e.mp_v;
-  }
-}
-// the plant of the fused kernel (plant_step + rotor_filter + platform_contact) replayed open loop, one lane per series (dql_plant_run)
-template <typename T>
-__global__ void k_plant_run(SimK<T> c, long long n_series, long long n_ticks, const double* init, const double* rotor_cmd, double* out) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_series) return;
-  Env<T> e;
-  memset(&e, 0, sizeof(e));
-  const double* s0 = init + i * 21;
-  for (int k = 0; k < 3; ++k) { e.p[k] = (T)s0[k]; e.v[k] = (T)s0[3 + k]; e.w[k] = (T)s0[10 + k]; }
-  for (int k = 0; k < 4; ++k) { e.q[k] = (T)s0[6 + k]; e.om[k] = (T)s0[13 + k]; }
-  e.mp_x = (T)s0[17]; e.mp_y = (T)s0[18]; e.mp_u = (T)s0[19]; e.mp_v = (T)s0[20];
-  for (long long t = 0; t < n_ticks; ++t) {
-    const double* r = rotor_cmd + (i * n_ticks + t) * 4;
-    const T cmd[4] = {(T)r[0], (T)r[1], (T)r[2], (T)r[3]};
-    T R[9];
-    quat_to_R(e.q, R);
-    plant_step(c, e, R);
-    rotor_filter(c, e, cmd);
-    platform_contact(c, e);
-    double* o = out + (i * n_ticks + t) * 20;
-    for (int k = 0; k < 3; ++k) { o[k] = e.p[k]; o[3 + k] = e.v[k]; o[10 + k] = e.w[k]; }
-    for (int k = 0; k < 4; ++k) { o[6 + k] = e.q[k]; o[13 + k] = e.om[k]; }
-    o[17] = e.mp_x; o[18] = e.mp_y; o[19] = (e.flags & FL_CONTACT) ? 1.0 : 0.0;
-  }
-}
-// ---- the control-side functions of the tick replayed alone (dql_butterworth_run, dql_kalman_run, dql_pid_run, dql_attitude_run,
-// dql_platform_run): the SAME device functions the fused step calls, one lane, so that each can be held against the reference's own
-// outputs (golden vectors G8, G9, G11) in float64 AND in the float32 forms every throughput figure runs on ----
-template <typename T> struct FiltK { T dt, bw_k1, bw_k2, bw_inv, bw_b2, bw_a2, bw_a3; };
-template <typename T> static FiltK<T> make_filtk(double bc) {  // pkg/filters.py:94-106, as make_simk has it
-  const double denom = 1 + bc * bc + 1.414 * bc;
-  FiltK<T> d;
-  d.dt = T(0); d.bw_inv = (T)(1.0 / denom); d.bw_k1 = (T)(bc * bc - 1.414 * bc + 1); d.bw_k2 = (T)(-2 * bc * bc + 2);
-  d.bw_b2 = (T)(2.0 / denom); d.bw_a2 = (T)((-2 * bc * bc + 2) / denom); d.bw_a3 = (T)((bc * bc - 1.414 * bc + 1) / denom);
-  return d;
-}
-template <typename T> __global__ void k_butterworth_run(FiltK<T> c, const double* x, long long n, double* y) {  // pkg/filters.py:98-109 from zero histories
-  if (blockIdx.x || threadIdx.x) return;
-  T x1 = T(0), x2 = T(0), y1 = T(0), y2 = T(0), y3 = T(0);
-  for (long long i = 0; i < n; ++i) y[i] = (double)butterworth(c, (T)x[i], x1, x2, y1, y2, y3);
-}
-// KalmanFilter3D.filter over a velocity series (pkg/filters.py:53-80): z = dv / dt with the timestamps 0.01 i, dt <= 0 -> 0.01 (dt_le0[i] forces that branch)
-template <typename T> __global__ void k_kalman_run(T Q, T Rm, const double* vel, const uint8_t* dt_le0, long long n, double* acc) {
-  if (blockIdx.x || threadIdx.x) return;
-  T x[3] = {T(0), T(0), T(0)}, P[3] = {T(1), T(1), T(1)};
-  for (long long i = 1; i < n; ++i) {
-    T dt_ = dt_le0[i] ? T(0.0) : (T)(0.01 * (double)i) - (T)(0.01 * (double)(i - 1));
-    if (dt_ <= T(0.0)) dt_ = T(0.01);
-    for (int k = 0; k < 3; ++k) acc[(i - 1) * 3 + k] = (double)kalman1d(x[k], P[k], Q, Rm, ((T)vel[i * 3 + k] - (T)vel[(i - 1) * 3 + k]) / dt_);
-  }
-}
-// PID.output replay (pkg/pid.py:62-104, Kd = 0): the plant state is sampled every 5th tick, tick times are 0.002 (i + 1)
-template <typename T> struct PidP { T kp, ki, lo, hi, wind, sp; };
-template <typename T> __global__ void k_pid_run(FiltK<T> c, PidP<T> p, const double* state, long long n, double* effort, double* integral) {
-  if (blockIdx.x || threadIdx.x) return;
-  T integ = T(0), x1 = T(0), x2 = T(0), y1 = T(0), y2 = T(0), y3 = T(0), st = T(0), prev_t = T(0);
-  for (long long i = 0; i < n; ++i) {
-    const T t = (T)(0.002 * (double)(i + 1));
-    if (i % 5 == 0) st = (T)state[i];
-    c.dt = t - prev_t;
-    effort[i] = (double)pid_output(c, p.kp, p.ki, p.lo, p.hi, p.wind, p.sp, st, integ, x1, x2, y1, y2, y3);
-    integral[i] = (double)integ;
-    prev_t = t;
-  }
-}
-// AttitudeController.compute_rotor_velocities (pkg/attitude_controller.py:107-156) for n samples: quaternion (x, y, z, w) as ROS has it, body rates,
-// cmd = roll, pitch, yaw rate, thrust -> commanded rotor speeds.  xonly: the x-axis closed form the x-axis kernels compile in (roll command exactly 0)
-template <typename T> __global__ void k_attitude_run(SimK<T> s, const double* quat_xyzw, const double* omega, const double* cmd, long long n, int xonly, double* rotor) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const T q[4] = {(T)quat_xyzw[i * 4 + 3], (T)quat_xyzw[i * 4 + 0], (T)quat_xyzw[i * 4 + 1], (T)quat_xyzw[i * 4 + 2]};
-  const T w[3] = {(T)omega[i * 3], (T)omega[i * 3 + 1], (T)omega[i * 3 + 2]};
-  T R[9], cy, sy, ct, rn, B[9], out[4];
-  quat_to_R(q, R); yaw_cs(R, cy, sy, ct, rn);
-  make_B((T)cmd[i * 4 + 1], (T)cmd[i * 4 + 0], B);
-  attitude(s, R, w, B, cy, sy, ct, rn, (T)cmd[i * 4 + 2], (T)cmd[i * 4 + 3], out, xonly != 0);
-  for (int k = 0; k < 4; ++k) rotor[i * 4 + k] = (double)out[k];
-}
-// MovingPlatform.compute_trajectory (pkg/moving_platform.py:87-127) from phase 0: x, y, u, v at successive 100 Hz ticks.  carry > 0: sine and cosine
-// are evaluated at every carry-th tick only and rotated through the constant phase step in between — what the fused float32 step does inside an
-// agent period (platform_update with a PlatRec; four or five manager ticks per period)
-template <typename T> __global__ void k_platform_run(SimK<T> s, long long n, int carry, double* out) {
-  if (blockIdx.x || threadIdx.x) return;
-  Env<T> e;
-  memset(&e, 0, sizeof(e));
-  e.mp_r = s.mp_r; e.mp_w = s.mp_w;
-  PlatRec<T> rec = PlatRec<T>{};
-  for (long long i = 0; i < n; ++i) {
-    if (carry > 0) platform_update(s, e, &rec, i % carry == 0);
-    else platform_update(s, e);
-    out[i * 4] = (double)e.mp_x; out[i * 4 + 1] = (double)e.mp_y; out[i * 4 + 2] = (double)e.mp_u; out[i * 4 + 3] = (double)e.mp_v;
-  }
-}
-// exhaustive self-test of sqrt_pos (dql_diag_selftest_sqrt): inputs with bit patterns lo .. hi against (float)sqrt((double)x)
-__global__ void k_selftest_sqrt(unsigned lo, unsigned hi, unsigned long long* bad) {
-  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-  unsigned long long n = 0;
-  for (unsigned long long b = lo + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; b <= hi; b += stride) {
-    const float x = __uint_as_float((unsigned)b);
-    if (__float_as_uint(sqrt_pos(x)) != __float_as_uint((float)__builtin_sqrt((double)x))) ++n;
-  }
-  if (n) atomicAdd(bad, n);
-}
-template <typename T> __global__ void k_place(int init_mode, T p_max, const double* x0, const double* mp, long long n, double* out) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = (double)place_axis(init_mode, (T)x0[i], (T)mp[i], p_max);
-}
-__global__ void k_predict(const double* qa, const double* qb, const int* idx, long long n, uint8_t* out) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = (uint8_t)agent_predict(qa, qb, idx[i]);
-}
-// ordered replay of DoubleQLearningAgent.update (pkg/double_q_learning.py:91-146): inherently sequential -> one lane
-// one DoubleQLearningAgent.update (pkg/double_q_learning.py:91-146); returns the updated cell's new value
-DQL_DEV double agent_update_one(double* qa, double* qb, double* count, int sa, int ns, double alpha, double gamma, double reward, uint32_t quirks, bool coin, bool done) {
-  const bool dbl = !(quirks & DQL_Q_UPDATE_TABLE_A_ONLY);  // Double Q-learning: coin picks the table, the other one values (B1/B2 off)
-  count[sa] += 1;
-  const bool sel_b = dbl && coin;
-  double* qsel = sel_b ? qb : qa;
-  const double* qval = dbl ? (sel_b ? qa : qb) : qa;
-  const double q0 = qsel[ns * 3], q1 = qsel[ns * 3 + 1], q2 = qsel[ns * 3 + 2];
-  const int b = argmax3(q0, q1, q2);
-  const double best = qval[ns * 3 + b];
-  const int mask = (quirks & DQL_Q_BOOTSTRAP_ON_POS_CHANGE) ? (idx_pos(sa / 3) != idx_pos(ns)) : !done;
-  const double loss = alpha * (reward + (gamma * best) * (double)mask - qsel[sa]);
-  qsel[sa] += loss;
-  return qsel[sa];
-}
-__global__ void k_update_seq(double* qa, double* qb, double* count, const int* sa, const int* ns, const double* alpha, double gamma,
-                             const double* reward, long long n, uint32_t quirks, const uint8_t* coin, const uint8_t* done) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  for (long long i = 0; i < n; ++i) agent_update_one(qa, qb, count, sa[i], ns[i], alpha[i], gamma, reward[i], quirks, coin && coin[i] != 0, done && done[i] != 0);
-}
-// resident agent (dql_agent_*): arguments and results in pinned host memory, read and written by the kernel itself
-struct AgentUpdIn { int sa, ns; double alpha, reward; int coin, done; };
-struct AgentUpdOut { double q_new, count_new; };
-struct AgentUpdTail { int next_action; int pad; };  // predict(next state of the LAST transition) on the updated tables: the reference's loop asks for it next
-__global__ void k_update_resident(double* qa, double* qb, double* count, const AgentUpdIn* in, AgentUpdOut* out, long long n, double gamma, uint32_t quirks) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  for (long long i = 0; i < n; ++i) {
-    const AgentUpdIn u = in[i];
-    out[i].q_new = agent_update_one(qa, qb, count, u.sa, u.ns, u.alpha, gamma, u.reward, quirks, u.coin != 0, u.done != 0);
-    out[i].count_new = count[u.sa];
-  }
-  AgentUpdTail* tail = (AgentUpdTail*)(out + n);
-  tail->next_action = agent_predict((const double*)qa, (const double*)qb, in[n - 1].ns);
-  __threadfence_system();
-}
-// one transition, arguments by value (dql_agent_mirror_update): nothing to read over PCIe, one record to write.  The arithmetic of
-// agent_update_one + agent_predict, spelled so that all eight table reads (both tables' row of the next state, the cell, its counter) are
-// independent and issue together: on an otherwise idle GPU each dependent read is a full trip to HBM, and five of them were the kernel.
-// `seq`: the call's sequence number, stored LAST (system-scope release): the host reads the record as soon as it sees the number, without
-// waiting for the stream to report the kernel complete (wait_posted)
-struct AgentOneOut { double q_new, count_new; int next_action; unsigned seq; };
-__global__ void k_update_one(double* qa, double* qb, double* count, int sa, int ns, double alpha, double gamma, double reward, uint32_t quirks, int coin, int done, AgentOneOut* out, unsigned seq) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  const bool dbl = !(quirks & DQL_Q_UPDATE_TABLE_A_ONLY);
-  const bool sel_b = dbl && coin != 0;
-  double ra[3], rb[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { ra[k] = qa[ns * 3 + k]; rb[k] = qb[ns * 3 + k]; }
-  double* qsel = sel_b ? qb : qa;
-  const double cur = qsel[sa], cnt = count[sa] + 1;
-  const bool val_b = dbl && !sel_b;  // the table that values the greedy action: the other one (Double Q-learning) or Q_table_a itself (B2)
-  const int b = sel_b ? argmax3(rb[0], rb[1], rb[2]) : argmax3(ra[0], ra[1], ra[2]);
-  const double va = b == 0 ? ra[0] : (b == 1 ? ra[1] : ra[2]), vb = b == 0 ? rb[0] : (b == 1 ? rb[1] : rb[2]);
-  const double best = val_b ? vb : va;
-  const int mask = (quirks & DQL_Q_BOOTSTRAP_ON_POS_CHANGE) ? (idx_pos(sa / 3) != idx_pos(ns)) : !done;
-  const double loss = alpha * (reward + (gamma * best) * (double)mask - cur);
-  const double q_new = cur + loss;
-  qsel[sa] = q_new; count[sa] = cnt;
-  if (sa / 3 == ns) {  // the next state's row contains the updated cell
-    const int k = sa % 3;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) if (j == k) { if (sel_b) rb[j] = q_new; else ra[j] = q_new; }
-  }
-  out->q_new = q_new; out->count_new = cnt;
-  out->next_action = argmax3((ra[0] + rb[0]) / 2, (ra[1] + rb[1]) / 2, (ra[2] + rb[2]) / 2);
-  __threadfence_system();
-  __hip_atomic_store(&out->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__global__ void k_predict_resident(const double* qa, const double* qb, const int* idx, long long n, uint8_t* out) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = (uint8_t)agent_predict(qa, qb, idx[i]);
-  __threadfence_system();
-}
 // what TrainingLandingEnv.step returns, gathered per env into pinned host memory (dql_step_outputs)
 struct StepOutRec { int idx_x, idx_y, step_count, code_flags; double reward, cum; };
 template <typename T> __global__ void k_step_outputs(const Quad<T>* __restrict__ sr, const int4* __restrict__ si, long long n, StepOutRec* out,
@@ -928,249 +786,7 @@ template <typename T> __global__ void k_step_outputs(const Quad<T>* __restrict__
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
-// ---- one-shot peer-to-peer exchange of the window accumulators (second step) ----
-// Exchange buffer of a rank: slots[2 parities][world][DQL_ACC_LEN] int64, then flags[2 parities][DQL_P2P_MAX_RANKS] (the sequence
-// number of the last exchange a peer has pushed for that parity).  Every rank writes its window into slot [parity][its rank] of
-// EVERY rank's buffer (its own included) — world concurrent writes over the direct links, 90 KB each — then raises its flag in every
-// buffer (system-scope release); the receiver waits for all flags of the parity (system-scope acquire, bounded spin) and sums the slots
-// in rank order into its window: one hop, no ring.  Two parities suffice: a rank can only be one exchange ahead of a peer (its next
-// wait needs that peer's next flag).  Buffers are uncached device memory, so a peer's writes are never shadowed by a stale L2 line.
-struct P2PPushArgs { const long long* window; unsigned long long* peer[DQL_P2P_MAX_RANKS]; int rank, world, parity; };
-DQL_DEV unsigned long long* p2p_slot(unsigned long long* buf, int world, int parity, int r) { return buf + ((size_t)parity * world + r) * DQL_ACC_LEN; }
-DQL_DEV unsigned long long* p2p_flags(unsigned long long* buf, int world, int parity) { return buf + (size_t)2 * world * DQL_ACC_LEN + (size_t)parity * DQL_P2P_MAX_RANKS; }
-__global__ void k_p2p_push(P2PPushArgs a) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= DQL_ACC_LEN) return;
-  const unsigned long long v = (unsigned long long)a.window[c];
-  for (int r = 0; r < a.world; ++r) __builtin_nontemporal_store(v, &p2p_slot(a.peer[r], a.world, a.parity, a.rank)[c]);
-}
-// after the push kernel has completed (stream order: its writes are released at the kernel boundary)
-__global__ void k_p2p_signal(P2PPushArgs a, unsigned long long seq) {
-  const int r = threadIdx.x;
-  if (r < a.world) __hip_atomic_store(&p2p_flags(a.peer[r], a.world, a.parity)[a.rank], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-// ONE waiter per exchange (a single wave; lane r polls peer r's flag): the verdict it leaves — verdict[0] = the last exchange every
-// peer showed up for, verdict[1] = the first exchange that was given up on (0 = none) — is what the sum kernel obeys, so a window is
-// either the full sum or untouched, never summed by some workgroups and not by others
-__global__ void k_p2p_wait(const unsigned long long* mine, int world, int parity, unsigned long long seq, unsigned long long* verdict, long long spin_limit) {
-  const int r = threadIdx.x;
-  bool good = true;
-  if (r < world) {
-    const unsigned long long* f = p2p_flags(const_cast<unsigned long long*>(mine), world, parity);
-    long long spins = 0;  // every lane reaches an exit: spin_limit polls, then the exchange is reported as failed
-    while (__hip_atomic_load(&f[r], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < seq) {
-      if (++spins > spin_limit) { good = false; break; }
-      __builtin_amdgcn_s_sleep(8);
-    }
-  }
-  const bool all_good = __ballot(!good) == 0ull;
-  if (r == 0) {
-    if (all_good) verdict[0] = seq;
-    else if (verdict[1] == 0ull) verdict[1] = seq;
-  }
-}
-__global__ void k_p2p_sum(unsigned long long* mine, long long* window, int world, int parity, unsigned long long seq, const unsigned long long* verdict) {
-  if (verdict[0] != seq) return;  // given up on: the window stays this rank's own (wave-uniform, whole grid)
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= DQL_ACC_LEN) return;
-  unsigned long long sum = 0;
-  for (int r = 0; r < world; ++r) sum += __builtin_nontemporal_load(&p2p_slot(mine, world, parity, r)[c]);
-  window[c] = (long long)sum;
-}
-
-// ---- greedy roll-outs (dql_rollout) ----
-// One env per lane flies its FIRST episode from reset to termination (csrc/dql_rollout.hpp: rollout_episode); workgroups of one wave: evaluation batches are
-// small, a lone wave per SIMD needs no LDS staging, no barrier, and there are no accumulators, table-writer blocks or statistics here.  Table set k serves
-// blocks [k B, (k + 1) B), B = envs_per_table / 64, so that the set's tables are a wave-uniform pointer; env i of every set has env id i (paired episodes).
-// The tick schedule of periods 0 .. max_steps sits in a device buffer read as constant memory (scalar loads by the wave-uniform period counter).
-template <typename T> struct RolloutArgs {
-  SimK<T> c;
-  const MdpK<T> DQL_CONST_AS* mdp;
-  MdpRun<T> mdp_run;
-  RolloutInit<T> init;
-  const double* qa; const double* qb;                                  // [n_tables][DQL_N_CELLS]
-  const long long DQL_CONST_AS* mgr0; const int DQL_CONST_AS* sched;   // [max_steps + 1] (fill_schedule)
-  RolloutOut out;
-  unsigned long long seed;
-  int blocks_per_table, max_steps;
-};
-template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_rollout(RolloutArgs<T> a) {
-  const int tid = threadIdx.x;
-  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
-  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
-  const long long g = (long long)blockIdx.x * 64 + tid;                // output column: every lane of the grid is an env (envs_per_table is a multiple of 64)
-  // the launch's constants in the layout's form, as k_step makes them for a 64-thread workgroup
-  SimK<T> cl = a.c;
-  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
-  SimK<T> cfgk = cl;
-  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
-  __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
-  if constexpr (sizeof(T) == 8) {
-    if (tid == 0) sTickK.k = cfgk;
-    __syncthreads();
-  }
-  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
-  uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
-  const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
-  const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
-  const bool trace_wave = a.out.trace != nullptr && blockIdx.x == 0;   // the first trace_envs <= 64 envs of table set 0: wave 0 of the grid, nobody else
-  rollout_episode<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.mgr0, a.sched, kv, a.out, g, trace_wave,
-                               trace_wave && tid < a.out.trace_envs);
-}
-
-// ---- sequential learners (dql_ensemble) ----
-// One learner per lane (csrc/dql_learner.hpp: learner_periods), workgroups of one wave as in k_rollout; the env stays in registers for all periods of the launch,
-// the tables are the lane's own [DQL_N_CELLS] slices (per-lane global pointers, ordinary vector loads and stores, no atomics).
-template <typename T> struct LearnArgs {
-  SimK<T> c;
-  const MdpK<T> DQL_CONST_AS* mdp;
-  MdpRun<T> mdp_run;
-  LearnSched sched;
-  LearnMem mem;
-  Quad<T>* sr; int4* si;
-  const long long DQL_CONST_AS* mgr0; const int DQL_CONST_AS* tick_sched;  // [n_periods] (fill_schedule from period j0)
-  unsigned long long seed;
-  long long j0;
-  int n_periods;
-};
-template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_learn(LearnArgs<T> a) {
-  const int tid = threadIdx.x;
-  const long long l = (long long)blockIdx.x * 64 + tid;
-  SimK<T> cl = a.c;
-  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
-  SimK<T> cfgk = cl;
-  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
-  __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
-  if constexpr (sizeof(T) == 8) {
-    if (tid == 0) sTickK.k = cfgk;
-    __syncthreads();
-  }
-  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
-  uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
-  learner_periods<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.sched, a.mem, a.sr, a.si, a.seed, l, l < a.mem.n, a.j0, a.n_periods, a.mgr0, a.tick_sched, kv);
-}
-// transfer_learning on every learner's tables: Q[l][k] = Q[l][src] * ratio (k_transfer's arithmetic)
-__global__ void k_ens_transfer(double* qa, double* qb, long long n, int k, int src, double ratio) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n * DQL_CELLS_PER_LEVEL) return;
-  const long long l = t / DQL_CELLS_PER_LEVEL; const int i = (int)(t - l * DQL_CELLS_PER_LEVEL);
-  double* a = qa + l * DQL_N_CELLS; double* b = qb + l * DQL_N_CELLS;
-  a[k * DQL_CELLS_PER_LEVEL + i] = a[src * DQL_CELLS_PER_LEVEL + i] * ratio;
-  b[k * DQL_CELLS_PER_LEVEL + i] = b[src * DQL_CELLS_PER_LEVEL + i] * ratio;
-}
-
-// ---- per-learner curriculum levels ----
-// k_learn over a worklist (csrc/dql_advance.hpp: build_worklist): wave w flies the learners worklist[64 w .. 64 w + 63] (-1: an inactive lane), all of
-// them at level wave_level[w] — a scalar load — from which follow SimK::working, the level's MdpK (a.a.mdp is the array of all five) and the level's
-// exploration table and freeze rules.  After that the call to learner_periods is k_learn's.
-template <typename T> struct LearnLevelsArgs {
-  LearnArgs<T> a;                          // a.mdp: [DQL_MAX_LEVELS]; a.sched: the learning rates (its per-level members are replaced by lv[level])
-  const LevelSched DQL_CONST_AS* lv;       // [DQL_MAX_LEVELS]
-  const int* worklist;                     // [64 n_waves]
-  const int DQL_CONST_AS* wave_level;      // [n_waves]
-  int n_waves;
-};
-template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_learn_levels(LearnLevelsArgs<T> g) {
-  const LearnArgs<T>& a = g.a;
-  const int tid = threadIdx.x;
-  const int w = (int)blockIdx.x;
-  if (w >= g.n_waves) return;
-  const int level = g.wave_level[w];
-  if ((unsigned)level >= (unsigned)DQL_MAX_LEVELS) { if (tid == 0) a.mem.faults[0] += 1ull; return; }  // never taken unless a bug (the host builds the worklist)
-  const long long l = (long long)g.worklist[(long long)w * 64 + tid];
-  SimK<T> cl = a.c;
-  cl.working = level;
-  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
-  SimK<T> cfgk = cl;
-  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
-  __shared__ TickLds<T> sTickK;  // as in k_learn
-  if constexpr (sizeof(T) == 8) {
-    if (tid == 0) sTickK.k = cfgk;
-    __syncthreads();
-  }
-  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
-  uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
-  const LevelSched DQL_CONST_AS* lv = g.lv + level;
-  const LearnSched sc{a.sched.alpha_tab, a.sched.n_alpha, a.sched.alpha_min, lv->eps_tab, lv->n_eps, lv->window, lv->min_successes, lv->max_episodes};
-  learner_periods<TICK, XMODE>(cl, cfgk, tc, a.mdp + level, a.mdp_run, sc, a.mem, a.sr, a.si, a.seed, l, l >= 0 && l < a.mem.n, a.j0, a.n_periods, a.mgr0, a.tick_sched, kv);
-}
-// an advance point: every learner takes advance_learner's step by itself (its own thread moves its own 2 x 567 cells; ordinary vector stores, nothing shared)
-// -- but for the `faults` word: advance_learner's `faults[0] += 1` is a plain add that threads of all waves may make at once, as learner_periods' is.  Counts
-// can be lost, a nonzero word cannot become zero, and nonzero is all that index_faults() is read for.
-__global__ void k_ens_advance(LearnMem mem, AdvanceMem adv, AdvanceRule rule, int4* si, long long j, int n_cells) {
-  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (l >= mem.n) return;
-  (void)advance_learner(mem, adv, rule, si, l, j, n_cells);
-}
-
-// ---- greedy scoring (dql_score / dql_ensemble_score) ----
-// k_rollout's shape — one env per lane, workgroups of one wave, table set k serves blocks [k B, (k + 1) B), env i of every set has RNG key (i, seed) — but a
-// lane flies episode after episode (csrc/dql_score.hpp: score_episodes) and what leaves the wave is its tally: one atomicAdd per non-zero column into the
-// table set's row of a buffer zeroed before the launch.  Integer sums: the result does not depend on the order the waves arrive in.
-template <typename T> struct ScoreArgs {
-  SimK<T> c;
-  const MdpK<T> DQL_CONST_AS* mdp;
-  MdpRun<T> mdp_run;
-  RolloutInit<T> init;
-  const double* qa; const double* qb;                                  // [n_tables][DQL_N_CELLS]
-  const long long DQL_CONST_AS* mgr0; const int DQL_CONST_AS* sched;   // [max_steps + 1] (fill_schedule)
-  unsigned long long* by_code;                                         // [n_tables][SCORE_N_COLS]
-  unsigned long long* steps_sum;                                       // [n_tables]
-  ScoreLog log;
-  unsigned long long seed;
-  int blocks_per_table, max_steps, episodes;
-};
-template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_score(ScoreArgs<T> a) {
-  const int tid = threadIdx.x;
-  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
-  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
-  const long long g = (long long)blockIdx.x * 64 + tid;                // log column: every lane of the grid is an env (envs_per_table is a multiple of 64)
-  SimK<T> cl = a.c;
-  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
-  SimK<T> cfgk = cl;
-  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
-  __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
-  if constexpr (sizeof(T) == 8) {
-    if (tid == 0) sTickK.k = cfgk;
-    __syncthreads();
-  }
-  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
-  uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
-  const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
-  const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
-  const ScoreTally t = score_episodes<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.episodes, a.mgr0, a.sched, kv, a.log, g);
-  if (tid == 0) {
-    unsigned long long* row = a.by_code + (size_t)k * SCORE_N_COLS;
-#pragma unroll
-    for (int col = 0; col < SCORE_N_COLS; ++col) if (t.by_code[col]) atomicAdd(&row[col], (unsigned long long)t.by_code[col]);
-    if (t.steps) atomicAdd(&a.steps_sum[k], t.steps);
-  }
-}
-
+#define DQL_POP_RING 8  // staging slots of population launch descriptors
 struct dql_ctx {
   dql_config cfg;
   int device = 0;
@@ -1179,6 +795,7 @@ struct dql_ctx {
   long long env_id_offset = 0;
   int dtype = DQL_F32;
   size_t real_size = 4;
+  DevOwned dev;         // every plain device allocation below (freed by dql_destroy)
   void* sr = nullptr;  // Quad<T>[NQ_REAL][n]
   int4* si = nullptr;
   double *qa = nullptr, *qb = nullptr, *count = nullptr;          // MASTER tables: every accumulator folded except the last launch's (`pending`)
@@ -1242,12 +859,11 @@ struct dql_ctx {
   unsigned long long* pop_faults = nullptr;            // device [n_agents]: targets the step kernel's bounds guard dropped
   struct PopAgentDesc* pop_h = nullptr;                 // pinned staging ring of launch descriptors: [DQL_POP_RING][DQL_MAX_AGENTS]
   struct PopAgentDesc* pop_d = nullptr;                 // its device copy, read by k_step_pop
-  hipEvent_t pop_ev[8] = {nullptr};                     // per ring slot: recorded behind the slot's copy (the staging slot is free again once it fired)
-  bool pop_busy[8] = {false};
+  hipEvent_t pop_ev[DQL_POP_RING] = {nullptr};                     // per ring slot: recorded behind the slot's copy (the staging slot is free again once it fired)
+  bool pop_busy[DQL_POP_RING] = {false};
   int pop_slot = 0;
   int last_step[5] = {0, 0, 0, 0, 0};  // the step kernel the latest launch ran (dql_diag_step_instance): sizeof(T), BLOCK, TICK, XMODE, population
 };
-#define DQL_POP_RING 8
 
 // first exchange of the peer-to-peer path that gave up on a missing peer (0 = none); synchronises the stream
 static int p2p_failed_seq(dql_ctx* x, unsigned long long* seq_out) {
@@ -1280,22 +896,15 @@ static int check_config(const dql_config* c) {
   return DQL_OK;
 }
 
-static int upload_mdpk(dql_ctx* x) {
-  if (x->dtype == DQL_F32) { const MdpK<float> m = make_mdpk<float>(x->cfg); HIP_TRY(hipMemcpyAsync(x->mdpk, &m, sizeof(m), hipMemcpyHostToDevice, x->stream)); }
-  else { const MdpK<double> m = make_mdpk<double>(x->cfg); HIP_TRY(hipMemcpyAsync(x->mdpk, &m, sizeof(m), hipMemcpyHostToDevice, x->stream)); }
-  HIP_TRY(hipStreamSynchronize(x->stream));  // the source is a stack temporary
-  return DQL_OK;
-}
-template <typename T> static int launch_init(dql_ctx* x) {
+// k_init over `count` envs from sr / si on, arrays of stride n: a context's envs, one agent's slice of a population, an ensemble's learners
+template <typename T> static int launch_init(const dql_config& c, void* sr, int4* si, long long n, long long count, unsigned long long seed, long long env_id_offset, hipStream_t st) {
   InitArgs<T> a;
-  a.c = make_simk<T>(x->cfg);
-  a.sr = (Quad<T>*)x->sr; a.si = x->si; a.n = x->n; a.seed = x->seed; a.env_id_offset = x->env_id_offset;
-  const dql_config& c = x->cfg;
-  a.hover = std::sqrt((T)(c.mass * c.gravity / (4.0 * c.k_f)));
-  a.vz_integ = (T)(c.mass * c.gravity / c.pid_vz[1]);
-  a.r_lo = (T)c.mp_r_lo; a.r_hi = (T)c.mp_r_hi; a.t_lo = (T)c.mp_t_lo; a.t_hi = (T)c.mp_t_hi;
+  a.c = make_simk<T>(c);
+  a.sr = (Quad<T>*)sr; a.si = si; a.n = n; a.seed = seed; a.env_id_offset = env_id_offset;
+  const RolloutInit<T> r = make_rollout_init<T>(c);
+  a.hover = r.hover; a.vz_integ = r.vz_integ; a.r_lo = r.r_lo; a.r_hi = r.r_hi; a.t_lo = r.t_lo; a.t_hi = r.t_hi;
   const int B = 256;
-  hipLaunchKernelGGL(k_init<T>, dim3((unsigned)((x->n + B - 1) / B)), dim3(B), 0, x->stream, a);
+  hipLaunchKernelGGL(k_init<T>, dim3((unsigned)((count + B - 1) / B)), dim3(B), 0, st, a);
   HIP_TRY(hipGetLastError());
   return DQL_OK;
 }
@@ -1506,14 +1115,13 @@ template <typename T> static int fetch_quads(dql_ctx* x, int q0, int nq, std::ve
 }
 template <typename T> static int get_sim_state_t(dql_ctx* x, double* out) {
   std::vector<T> h; int rc = fetch_quads<T>(x, 0, NQ_REAL, h); if (rc) return rc;
-  const long long n = x->n;
-  for (int f = 0; f < NF_REAL; ++f) { const int q = f / 4, k = f % 4; for (long long i = 0; i < n; ++i) out[(long long)f * n + i] = (double)h[((size_t)q * n + i) * 4 + k]; }
+  quads_to_fields(h.data(), x->n, out);
   return DQL_OK;
 }
 template <typename T> static int set_sim_state_t(dql_ctx* x, const double* in) {
   const long long n = x->n;
   std::vector<T> h((size_t)NQ_REAL * n * 4);
-  for (int f = 0; f < NF_REAL; ++f) { const int q = f / 4, k = f % 4; for (long long i = 0; i < n; ++i) h[((size_t)q * n + i) * 4 + k] = (T)in[(long long)f * n + i]; }
+  fields_to_quads(in, n, h.data());
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipMemcpyAsync(x->sr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, x->stream));
   HIP_TRY(hipStreamSynchronize(x->stream));
@@ -1587,55 +1195,43 @@ int dql_config_default(dql_config* c) {
 }
 
 static int create_tables(dql_ctx* x);
+#define ALLOC(ptr, bytes) do { hipError_t _e = x->dev.alloc((void**)&(ptr), (bytes)); if (_e != hipSuccess) return fail(DQL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(_e)); } while (0)
+#define ZALLOC(ptr, bytes) do { ALLOC(ptr, bytes); HIP_TRY(hipMemsetAsync((ptr), 0, (bytes), x->stream)); } while (0)
 // allocation + initialisation of a fresh context; any failure leaves a partly built context for the caller to destroy
 static int create_impl(dql_ctx* x, const dql_config* cfg) {
-#define ALLOC(ptr, bytes) do { hipError_t _e = hipMalloc((void**)&(ptr), (bytes)); if (_e != hipSuccess) return fail(DQL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(_e)); } while (0)
   HIP_TRY(hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
   HIP_TRY(hipEventCreate(&x->ev0)); HIP_TRY(hipEventCreate(&x->ev1));
   { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, x->device) == hipSuccess && cus > 0) x->n_simds = 4ll * cus; }
-  if (cfg->dtype == DQL_F32) { const SimK<float> k = make_simk<float>(*cfg); x->kal_fix = KalFix{(double)k.kal_pss, (double)k.kal_kss, true}; }
-  else { const SimK<double> k = make_simk<double>(*cfg); x->kal_fix = KalFix{k.kal_pss, k.kal_kss, true}; }
+  by_dtype(cfg->dtype, [&](auto t) { const SimK<decltype(t)> k = make_simk<decltype(t)>(*cfg); x->kal_fix = KalFix{(double)k.kal_pss, (double)k.kal_kss, true}; });
   const bool refm = cfg->dtype == DQL_F32 && refm_matches(make_mdpk<float>(*cfg));
   x->lit_ok = refm && refk_matches(make_simk<float>(*cfg, &x->kal_fix));
   // x-axis configs only: the two-axis instance of this layout (k_step<float, *, TICK_PACKED_LITM, X_TWO>) faults on its first launch (a memory access the
   // source does not explain — same source as the two instances it combines, both of which are parity-green); it is never selected
   x->litm_ok = refm && !cfg->two_axis;
-  ALLOC(x->sr, (size_t)NQ_REAL * (size_t)x->n * 4 * x->real_size);
+  ZALLOC(x->sr, (size_t)NQ_REAL * (size_t)x->n * 4 * x->real_size);
   ALLOC(x->si, (size_t)x->n * sizeof(int4));
   ALLOC(x->d_actions, (size_t)x->n);
-  HIP_TRY(hipMemsetAsync(x->sr, 0, (size_t)NQ_REAL * (size_t)x->n * 4 * x->real_size, x->stream));
   HIP_TRY(hipMemsetAsync(x->d_actions, 2, (size_t)x->n, x->stream));
   int rc = create_tables(x);
   if (rc) return rc;
-  rc = (x->dtype == DQL_F32) ? launch_init<float>(x) : launch_init<double>(x);
+  rc = by_dtype(x->dtype, [&](auto t) { return launch_init<decltype(t)>(x->cfg, x->sr, x->si, x->n, x->n, x->seed, x->env_id_offset, x->stream); });
   if (rc) return rc;
   // default alpha table (plateau only): callers install the reference schedule with dql_set_alpha_table
   const double a0 = cfg->alpha_min;
   return dql_set_alpha_table(x, &a0, 1);
-#undef ALLOC
 }
 // what a context needs besides its envs: tables, ping-pong copies, accumulators, window, statistics, MdpK (also the agents of a population)
 static int create_tables(dql_ctx* x) {
-#define ALLOC(ptr, bytes) do { hipError_t _e = hipMalloc((void**)&(ptr), (bytes)); if (_e != hipSuccess) return fail(DQL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(_e)); } while (0)
-  ALLOC(x->qa, DQL_N_CELLS * sizeof(double)); ALLOC(x->qb, DQL_N_CELLS * sizeof(double)); ALLOC(x->count, DQL_N_CELLS * sizeof(double));
-  ALLOC(x->qa_base, DQL_N_CELLS * sizeof(double)); ALLOC(x->count_base, DQL_N_CELLS * sizeof(double));
-  ALLOC(x->qb_base, DQL_N_CELLS * sizeof(double));
-  for (int k = 0; k < 2; ++k) { ALLOC(x->tb[k], DQL_N_CELLS * sizeof(double)); ALLOC(x->tbb[k], DQL_N_CELLS * sizeof(double)); ALLOC(x->acc[k], DQL_ACC_LEN * sizeof(long long)); }
-  ALLOC(x->window_own, DQL_ACC_LEN * sizeof(long long)); x->window = x->window_own;
-  ALLOC(x->stats, sizeof(StatsDev)); ALLOC(x->mdpk, sizeof(MdpK<double>));
-#undef ALLOC
-  HIP_TRY(hipMemsetAsync(x->qa, 0, DQL_N_CELLS * sizeof(double), x->stream)); HIP_TRY(hipMemsetAsync(x->qb, 0, DQL_N_CELLS * sizeof(double), x->stream));
-  HIP_TRY(hipMemsetAsync(x->count, 0, DQL_N_CELLS * sizeof(double), x->stream));
-  HIP_TRY(hipMemsetAsync(x->qa_base, 0, DQL_N_CELLS * sizeof(double), x->stream)); HIP_TRY(hipMemsetAsync(x->count_base, 0, DQL_N_CELLS * sizeof(double), x->stream));
-  HIP_TRY(hipMemsetAsync(x->qb_base, 0, DQL_N_CELLS * sizeof(double), x->stream));
-  for (int k = 0; k < 2; ++k) {
-    HIP_TRY(hipMemsetAsync(x->tb[k], 0, DQL_N_CELLS * sizeof(double), x->stream)); HIP_TRY(hipMemsetAsync(x->tbb[k], 0, DQL_N_CELLS * sizeof(double), x->stream));
-    HIP_TRY(hipMemsetAsync(x->acc[k], 0, DQL_ACC_LEN * sizeof(long long), x->stream));
-  }
-  HIP_TRY(hipMemsetAsync(x->window, 0, DQL_ACC_LEN * sizeof(long long), x->stream));
-  HIP_TRY(hipMemsetAsync(x->stats, 0, sizeof(StatsDev), x->stream));
-  return upload_mdpk(x);
+  const size_t TB = DQL_N_CELLS * sizeof(double), AB = DQL_ACC_LEN * sizeof(long long);
+  ZALLOC(x->qa, TB); ZALLOC(x->qb, TB); ZALLOC(x->count, TB);
+  ZALLOC(x->qa_base, TB); ZALLOC(x->count_base, TB); ZALLOC(x->qb_base, TB);
+  for (int k = 0; k < 2; ++k) { ZALLOC(x->tb[k], TB); ZALLOC(x->tbb[k], TB); ZALLOC(x->acc[k], AB); }
+  ZALLOC(x->window_own, AB); x->window = x->window_own;
+  ZALLOC(x->stats, sizeof(StatsDev)); ALLOC(x->mdpk, sizeof(MdpK<double>));
+  return upload_mdpk(x->cfg, x->mdpk, x->stream);
 }
+#undef ZALLOC
+#undef ALLOC
 
 int dql_create(const dql_config* cfg, int device, int64_t n_envs, uint64_t seed, int64_t env_id_offset, dql_ctx** out) {
   if (!out) return fail(DQL_EINVAL, "null out pointer");
@@ -1669,13 +1265,10 @@ int dql_destroy(dql_ctx* x) {
   for (dql_ctx* g : x->agents) (void)dql_destroy(g);
   for (int s = 0; s < DQL_POP_RING; ++s) if (x->pop_ev[s]) (void)hipEventDestroy(x->pop_ev[s]);
   if (x->pop_h) (void)hipHostFree(x->pop_h);
-  if (x->pop_d) (void)hipFree(x->pop_d);
-  if (x->pop_faults) (void)hipFree(x->pop_faults);
   for (hipEvent_t e : x->kev) (void)hipEventDestroy(e);
   for (hipEvent_t e : x->sev) (void)hipEventDestroy(e);
   for (int r = 0; r < DQL_P2P_MAX_RANKS; ++r) if (x->p2p_opened[r] && x->p2p_peer[r]) (void)hipIpcCloseMemHandle(x->p2p_peer[r]);
-  void* ptrs[] = {x->sr, x->si, x->qa, x->qb, x->count, x->tb[0], x->tb[1], x->tbb[0], x->tbb[1], x->qa_base, x->qb_base, x->count_base, x->acc[0], x->acc[1], x->window_own, x->alpha_tab, x->stats, x->d_actions, x->mdpk, x->elog, x->d_mask, x->p2p_buf, x->p2p_status};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
+  x->dev.free_all();
   if (x->h_actions) (void)hipHostFree(x->h_actions);
   if (x->h_out) (void)hipHostFree(x->h_out);
   if (x->ev_actions) (void)hipEventDestroy(x->ev_actions);
@@ -1724,9 +1317,9 @@ int dql_set_alpha_table(dql_ctx* x, const double* alpha, int32_t n) {
   HIP_TRY(hipSetDevice(x->device));
   { int rc = flush_pending(x); if (rc) return rc; }
   HIP_TRY(hipStreamSynchronize(x->stream));
-  if (x->alpha_tab) HIP_TRY(hipFree(x->alpha_tab));
+  HIP_TRY(x->dev.release(x->alpha_tab));
   x->alpha_tab = nullptr;
-  HIP_TRY(hipMalloc((void**)&x->alpha_tab, (size_t)n * sizeof(double)));
+  HIP_TRY(x->dev.alloc((void**)&x->alpha_tab, (size_t)n * sizeof(double)));
   HIP_TRY(hipMemcpy(x->alpha_tab, alpha, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
   x->n_tab = n;
   for (dql_ctx* g : x->agents) { int rc = dql_set_alpha_table(g, alpha, n); if (rc) return rc; }  // population: every agent
@@ -1743,7 +1336,7 @@ int dql_set_curriculum(dql_ctx* x, int32_t k) {
   rc = publish_master(x);  // the new level starts acting on everything learnt so far
   if (rc) return rc;
   x->cfg.working_curriculum_step = k;
-  rc = upload_mdpk(x);
+  rc = upload_mdpk(x->cfg, x->mdpk, x->stream);
   if (rc) return rc;
   return dql_reset(x, nullptr);
 }
@@ -1753,7 +1346,7 @@ int dql_reset(dql_ctx* x, const uint8_t* mask) {
   HIP_TRY(hipSetDevice(x->device));
   const uint8_t* dmask = nullptr;
   if (mask) {
-    if (!x->d_mask && hipMalloc((void**)&x->d_mask, (size_t)x->n) != hipSuccess) { x->d_mask = nullptr; return fail(DQL_ENOMEM, "hipMalloc(reset mask) failed"); }
+    if (!x->d_mask && x->dev.alloc((void**)&x->d_mask, (size_t)x->n) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc(reset mask) failed");
     HIP_TRY(hipMemcpyAsync(x->d_mask, mask, (size_t)x->n, hipMemcpyHostToDevice, x->stream));
     HIP_TRY(hipStreamSynchronize(x->stream));  // the caller's buffer may be reused right after return
     dmask = x->d_mask;
@@ -1911,7 +1504,7 @@ int dql_get_actions(dql_ctx* x, uint8_t* actions) {
 int dql_get_sim_state(dql_ctx* x, double* out, int32_t cap) {
   CHECK_CTX(x);
   if (!out || cap < NF_REAL) return fail(DQL_EINVAL, "out buffer must hold 64 fields x n_envs doubles");
-  return x->dtype == DQL_F32 ? get_sim_state_t<float>(x, out) : get_sim_state_t<double>(x, out);
+  return by_dtype(x->dtype, [&](auto t) { return get_sim_state_t<decltype(t)>(x, out); });
 }
 static int real_field_index(const char* name);  // (the name table sits further down, with dql_field_name)
 int dql_set_sim_state(dql_ctx* x, const double* in, int32_t nf) {
@@ -1922,17 +1515,13 @@ int dql_set_sim_state(dql_ctx* x, const double* in, int32_t nf) {
     for (long long i = 0; f_roll >= 0 && i < x->n; ++i)
       if (in[(long long)f_roll * x->n + i] != 0.0) return fail(DQL_EINVAL, "roll_sp must be 0 in an x-axis float32 context (its attitude law is the closed form for a zero roll set-point); use two_axis = 1 or dtype float64");
   }
-  return x->dtype == DQL_F32 ? set_sim_state_t<float>(x, in) : set_sim_state_t<double>(x, in);
+  return by_dtype(x->dtype, [&](auto t) { return set_sim_state_t<decltype(t)>(x, in); });
 }
 int dql_get_sim_ints(dql_ctx* x, int32_t* out, int32_t cap) {
   CHECK_CTX(x);
   if (!out || cap < NF_INT) return fail(DQL_EINVAL, "out buffer must hold 7 fields x n_envs int32");
   std::vector<int4> h; int rc = fetch_ints(x, h); if (rc) return rc;
-  const long long n = x->n;
-  for (long long i = 0; i < n; ++i) {
-    out[0 * n + i] = h[i].x; out[1 * n + i] = h[i].y; out[2 * n + i] = h[i].z & 0xffff; out[3 * n + i] = (h[i].z >> 16) & 0xffff;
-    out[4 * n + i] = h[i].w & 0xff; out[5 * n + i] = (h[i].w >> 8) & 0xff; out[6 * n + i] = (h[i].w >> 16) & 0xff;
-  }
+  unpack_ints(h.data(), x->n, out);
   return DQL_OK;
 }
 int dql_set_sim_ints(dql_ctx* x, const int32_t* in, int32_t nf) {
@@ -1978,12 +1567,12 @@ const char* dql_field_name(int32_t i, int32_t is_int) {
 int dql_get_rewards(dql_ctx* x, double* rewards) {
   CHECK_CTX(x);
   if (!rewards) return fail(DQL_EINVAL, "null pointer");
-  return x->dtype == DQL_F32 ? get_rewards_t<float>(x, rewards) : get_rewards_t<double>(x, rewards);
+  return by_dtype(x->dtype, [&](auto t) { return get_rewards_t<decltype(t)>(x, rewards); });
 }
 int dql_get_obs(dql_ctx* x, double* out) {
   CHECK_CTX(x);
   if (!out) return fail(DQL_EINVAL, "null pointer");
-  return x->dtype == DQL_F32 ? get_obs_t<float>(x, out) : get_obs_t<double>(x, out);
+  return by_dtype(x->dtype, [&](auto t) { return get_obs_t<decltype(t)>(x, out); });
 }
 
 // ---- tables ----
@@ -2265,12 +1854,12 @@ int dql_episode_log_enable(dql_ctx* x, int32_t capacity_periods) {
   if (capacity_periods < 0) return fail(DQL_EINVAL, "capacity_periods must be >= 0");
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipStreamSynchronize(x->stream));
-  if (x->elog) { HIP_TRY(hipFree(x->elog)); x->elog = nullptr; }
+  if (x->elog) { HIP_TRY(x->dev.release(x->elog)); x->elog = nullptr; }
   x->elog_cap = 0; x->elog_n = 0;
   for (dql_ctx* g : x->agents) g->elog_n = 0;
   if (capacity_periods == 0) return DQL_OK;
   const size_t nw = (size_t)((x->n + 63) >> 6);
-  if (hipMalloc((void**)&x->elog, (size_t)capacity_periods * 2 * nw * sizeof(unsigned long long)) != hipSuccess) { x->elog = nullptr; return fail(DQL_ENOMEM, "hipMalloc(episode log) failed"); }
+  if (x->dev.alloc((void**)&x->elog, (size_t)capacity_periods * 2 * nw * sizeof(unsigned long long)) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc(episode log) failed");
   x->elog_cap = capacity_periods;
   if (x->n_agents) HIP_TRY(hipMemsetAsync(x->elog, 0, (size_t)capacity_periods * 2 * nw * sizeof(unsigned long long), x->stream));  // words of agents that ran fewer periods read 0
   return DQL_OK;
@@ -2323,1498 +1912,6 @@ int dql_episode_log_read_words(dql_ctx* x, uint64_t* done_masks, uint64_t* goal_
   return DQL_OK;
 }
 
-// ---- stateless operators ----
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t b) { hipError_t e = hipMalloc(&p, b ? b : 1); return e == hipSuccess ? 0 : -1; }
-};
-#define OP_PROLOGUE(device)                                                                \
-  int _ndev = 0;                                                                           \
-  HIP_TRY(hipGetDeviceCount(&_ndev));                                                      \
-  if (_ndev < 1) return fail(DQL_EHIP, "no HIP device visible (there is no CPU fallback)"); \
-  if ((device) < 0 || (device) >= _ndev) return fail(DQL_EINVAL, "device index out of range"); \
-  HIP_TRY(hipSetDevice(device));
-#define UP(buf, host, bytes) do { if ((buf).alloc(bytes)) return fail(DQL_ENOMEM, "hipMalloc failed"); HIP_TRY(hipMemcpy((buf).p, (host), (bytes), hipMemcpyHostToDevice)); } while (0)
-
-int dql_discretise(const dql_config* cfg, int device, const double* rel_p, const double* rel_v, const double* rel_a, const double* angle, int64_t n, int32_t* idx_out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (n < 0 || (n > 0 && (!rel_p || !rel_v || !rel_a || !angle || !idx_out))) return fail(DQL_EINVAL, "null array");
-  if (n == 0) return DQL_OK;
-  OP_PROLOGUE(device)
-  DevBuf p, v, a, t, o;
-  const size_t B = (size_t)n * sizeof(double);
-  UP(p, rel_p, B); UP(v, rel_v, B); UP(a, rel_a, B); UP(t, angle, B);
-  if (o.alloc((size_t)n * sizeof(int))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  if (cfg->dtype == DQL_F32) hipLaunchKernelGGL(k_discretise<float>, dim3(grid), dim3(256), 0, 0, make_mdpk<float>(*cfg), (const double*)p.p, (const double*)v.p, (const double*)a.p, (const double*)t.p, (long long)n, (int*)o.p);
-  else hipLaunchKernelGGL(k_discretise<double>, dim3(grid), dim3(256), 0, 0, make_mdpk<double>(*cfg), (const double*)p.p, (const double*)v.p, (const double*)a.p, (const double*)t.p, (long long)n, (int*)o.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(idx_out, o.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_mdp_transition(const dql_config* cfg, int device, int64_t n, uint32_t stages, const uint8_t* action, const double* obs, double* mdp_state,
-                       const int32_t* prev_idx, int32_t* idx_io, double* reward_out, uint8_t* done_out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (n < 0 || (n > 0 && (!action || !obs || !mdp_state || !prev_idx || !idx_io || !reward_out || !done_out))) return fail(DQL_EINVAL, "null array");
-  if (n == 0) return DQL_OK;
-  if ((stages & DQL_MDP_ALL) == 0) return fail(DQL_EINVAL, "no stage selected");
-  for (int64_t i = 0; i < n; ++i) if (action[i] > 2) return fail(DQL_EINVAL, "action must be 0, 1 or 2");
-  if ((stages & (DQL_MDP_CHECK | DQL_MDP_REWARD)) && !(stages & DQL_MDP_DISCRETISE))
-    for (int64_t i = 0; i < n; ++i) if (idx_io[i] < 0 || idx_io[i] >= DQL_N_STATES) return fail(DQL_ESTATE, "Cannot check an empty state: call discrete_state first");
-  OP_PROLOGUE(device)
-  DevBuf a, o, ms, pi, io, ro, dn;
-  UP(a, action, (size_t)n); UP(o, obs, (size_t)n * 7 * sizeof(double)); UP(ms, mdp_state, (size_t)n * 8 * sizeof(double)); UP(pi, prev_idx, (size_t)n * sizeof(int));
-  UP(io, idx_io, (size_t)n * sizeof(int)); UP(ro, reward_out, (size_t)n * sizeof(double)); UP(dn, done_out, (size_t)n);
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  if (cfg->dtype == DQL_F32) hipLaunchKernelGGL(k_mdp_transition<float>, dim3(grid), dim3(256), 0, 0, make_mdpk<float>(*cfg), (long long)n, stages, (const uint8_t*)a.p, (const double*)o.p, (double*)ms.p, (const int*)pi.p, (int*)io.p, (double*)ro.p, (uint8_t*)dn.p);
-  else hipLaunchKernelGGL(k_mdp_transition<double>, dim3(grid), dim3(256), 0, 0, make_mdpk<double>(*cfg), (long long)n, stages, (const uint8_t*)a.p, (const double*)o.p, (double*)ms.p, (const int*)pi.p, (int*)io.p, (double*)ro.p, (uint8_t*)dn.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(mdp_state, ms.p, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(idx_io, io.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(reward_out, ro.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(done_out, dn.p, (size_t)n, hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_manager_run(const dql_config* cfg, int device, int64_t n_series, int64_t n_ticks, const double* in, const uint8_t* contact, uint64_t seed, double* out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (n_series < 0 || n_ticks < 0 || ((n_series > 0 && n_ticks > 0) && (!in || !contact || !out))) return fail(DQL_EINVAL, "null array");
-  if (n_series == 0 || n_ticks == 0) return DQL_OK;
-  OP_PROLOGUE(device)
-  DevBuf a, b, o;
-  const size_t cells = (size_t)n_series * (size_t)n_ticks;
-  UP(a, in, cells * 14 * sizeof(double)); UP(b, contact, cells);
-  if (o.alloc(cells * 12 * sizeof(double))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  dql_config c2 = *cfg;
-  c2.two_axis = 1;  // the reference's estimator always runs on every axis; x-axis training configs simply never read y
-  const unsigned grid = (unsigned)((n_series + 63) / 64);
-  if (cfg->dtype == DQL_F32) hipLaunchKernelGGL(k_manager_run<float>, dim3(grid), dim3(64), 0, 0, make_simk<float>(c2), (long long)n_series, (long long)n_ticks, (const double*)a.p, (const uint8_t*)b.p, (unsigned long long)seed, (double*)o.p);
-  else hipLaunchKernelGGL(k_manager_run<double>, dim3(grid), dim3(64), 0, 0, make_simk<double>(c2), (long long)n_series, (long long)n_ticks, (const double*)a.p, (const uint8_t*)b.p, (unsigned long long)seed, (double*)o.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, o.p, cells * 12 * sizeof(double), hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_plant_run(const dql_config* cfg, int device, int64_t n_series, int64_t n_ticks, const double* init, const double* rotor_cmd, double* out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (n_series < 0 || n_ticks < 0 || ((n_series > 0 && n_ticks > 0) && (!init || !rotor_cmd || !out))) return fail(DQL_EINVAL, "null array");
-  if (n_series == 0 || n_ticks == 0) return DQL_OK;
-  const size_t cells = (size_t)n_series * (size_t)n_ticks;
-  for (size_t k = 0; k < cells * 4; ++k) if (!(rotor_cmd[k] >= 0.0)) return fail(DQL_EINVAL, "rotor commands must be >= 0 (the attitude law commands sqrt(max(w^2, 0)))");
-  OP_PROLOGUE(device)
-  DevBuf a, b, o;
-  UP(a, init, (size_t)n_series * 21 * sizeof(double)); UP(b, rotor_cmd, cells * 4 * sizeof(double));
-  if (o.alloc(cells * 20 * sizeof(double))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  const unsigned grid = (unsigned)((n_series + 63) / 64);
-  if (cfg->dtype == DQL_F32) hipLaunchKernelGGL(k_plant_run<float>, dim3(grid), dim3(64), 0, 0, make_simk<float>(*cfg), (long long)n_series, (long long)n_ticks, (const double*)a.p, (const double*)b.p, (double*)o.p);
-  else hipLaunchKernelGGL(k_plant_run<double>, dim3(grid), dim3(64), 0, 0, make_simk<double>(*cfg), (long long)n_series, (long long)n_ticks, (const double*)a.p, (const double*)b.p, (double*)o.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, o.p, cells * 20 * sizeof(double), hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_butterworth_run(const dql_config* cfg, int device, const double* x, int64_t n, double* y_out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (n < 0 || (n > 0 && (!x || !y_out))) return fail(DQL_EINVAL, "null array");
-  if (n == 0) return DQL_OK;
-  OP_PROLOGUE(device)
-  DevBuf a, o;
-  UP(a, x, (size_t)n * sizeof(double));
-  if (o.alloc((size_t)n * sizeof(double))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  if (cfg->dtype == DQL_F32) hipLaunchKernelGGL(k_butterworth_run<float>, dim3(1), dim3(64), 0, 0, make_filtk<float>(cfg->bw_c), (const double*)a.p, (long long)n, (double*)o.p);
-  else hipLaunchKernelGGL(k_butterworth_run<double>, dim3(1), dim3(64), 0, 0, make_filtk<double>(cfg->bw_c), (const double*)a.p, (long long)n, (double*)o.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(y_out, o.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_kalman_run(const dql_config* cfg, int device, const double* vel, const uint8_t* dt_le0, int64_t n, double* acc_out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (n < 0 || (n > 1 && (!vel || !dt_le0 || !acc_out))) return fail(DQL_EINVAL, "null array");
-  if (n <= 1) return DQL_OK;
-  OP_PROLOGUE(device)
-  DevBuf a, b, o;
-  UP(a, vel, (size_t)n * 3 * sizeof(double)); UP(b, dt_le0, (size_t)n);
-  if (o.alloc((size_t)(n - 1) * 3 * sizeof(double))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  const double r = cfg->noise_vel_sd * cfg->noise_vel_sd;  // pkg/filters.py:49
-  if (cfg->dtype == DQL_F32) hipLaunchKernelGGL(k_kalman_run<float>, dim3(1), dim3(64), 0, 0, (float)cfg->kalman_q, (float)r, (const double*)a.p, (const uint8_t*)b.p, (long long)n, (double*)o.p);
-  else hipLaunchKernelGGL(k_kalman_run<double>, dim3(1), dim3(64), 0, 0, (double)cfg->kalman_q, r, (const double*)a.p, (const uint8_t*)b.p, (long long)n, (double*)o.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(acc_out, o.p, (size_t)(n - 1) * 3 * sizeof(double), hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_pid_run(const dql_config* cfg, int device, const double* params, const double* state, int64_t n, double* effort_out, double* integral_out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (!params || n < 0 || (n > 0 && (!state || !effort_out || !integral_out))) return fail(DQL_EINVAL, "null array");
-  if (params[2] != 0.0) return fail(DQL_EINVAL, "Kd != 0 is not supported (the reference launches both controllers with Kd = 0, launch/drone.launch:37,51)");
-  if (n == 0) return DQL_OK;
-  OP_PROLOGUE(device)
-  DevBuf a, o, g;
-  UP(a, state, (size_t)n * sizeof(double));
-  if (o.alloc((size_t)n * sizeof(double)) || g.alloc((size_t)n * sizeof(double))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  if (cfg->dtype == DQL_F32) {
-    const PidP<float> p{(float)params[0], (float)params[1], (float)params[3], (float)params[4], (float)params[5], (float)params[6]};
-    hipLaunchKernelGGL(k_pid_run<float>, dim3(1), dim3(64), 0, 0, make_filtk<float>(cfg->bw_c), p, (const double*)a.p, (long long)n, (double*)o.p, (double*)g.p);
-  } else {
-    const PidP<double> p{params[0], params[1], params[3], params[4], params[5], params[6]};
-    hipLaunchKernelGGL(k_pid_run<double>, dim3(1), dim3(64), 0, 0, make_filtk<double>(cfg->bw_c), p, (const double*)a.p, (long long)n, (double*)o.p, (double*)g.p);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(effort_out, o.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(integral_out, g.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_attitude_run(const dql_config* cfg, int device, const double* quat_xyzw, const double* omega, const double* cmd, int64_t n, int32_t xonly, double* rotor_out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (n < 0 || (n > 0 && (!quat_xyzw || !omega || !cmd || !rotor_out))) return fail(DQL_EINVAL, "null array");
-  if (xonly && cfg->dtype != DQL_F32) return fail(DQL_EINVAL, "the x-axis closed form of the attitude law exists in float32 only");
-  if (xonly) for (int64_t i = 0; i < n; ++i) if (cmd[i * 4] != 0.0) return fail(DQL_EINVAL, "the x-axis closed form needs a roll command of exactly 0");
-  if (n == 0) return DQL_OK;
-  OP_PROLOGUE(device)
-  DevBuf a, b, c, o;
-  UP(a, quat_xyzw, (size_t)n * 4 * sizeof(double)); UP(b, omega, (size_t)n * 3 * sizeof(double)); UP(c, cmd, (size_t)n * 4 * sizeof(double));
-  if (o.alloc((size_t)n * 4 * sizeof(double))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  const unsigned grid = (unsigned)((n + 63) / 64);
-  if (cfg->dtype == DQL_F32) hipLaunchKernelGGL(k_attitude_run<float>, dim3(grid), dim3(64), 0, 0, make_simk<float>(*cfg), (const double*)a.p, (const double*)b.p, (const double*)c.p, (long long)n, (int)xonly, (double*)o.p);
-  else hipLaunchKernelGGL(k_attitude_run<double>, dim3(grid), dim3(64), 0, 0, make_simk<double>(*cfg), (const double*)a.p, (const double*)b.p, (const double*)c.p, (long long)n, (int)xonly, (double*)o.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(rotor_out, o.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_platform_run(const dql_config* cfg, int device, int64_t n, int32_t carry, double* out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (n < 0 || carry < 0 || (n > 0 && !out)) return fail(DQL_EINVAL, "bad argument");
-  if (carry && cfg->dtype != DQL_F32) return fail(DQL_EINVAL, "the carried sine / cosine exists in the float32 step only");
-  if (n == 0) return DQL_OK;
-  OP_PROLOGUE(device)
-  DevBuf o;
-  if (o.alloc((size_t)n * 4 * sizeof(double))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  if (cfg->dtype == DQL_F32) hipLaunchKernelGGL(k_platform_run<float>, dim3(1), dim3(64), 0, 0, make_simk<float>(*cfg), (long long)n, (int)carry, (double*)o.p);
-  else hipLaunchKernelGGL(k_platform_run<double>, dim3(1), dim3(64), 0, 0, make_simk<double>(*cfg), (long long)n, (int)carry, (double*)o.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, o.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_diag_selftest_sqrt(int device, uint32_t lo_bits, uint32_t hi_bits, int64_t* not_correctly_rounded) {
-  if (!not_correctly_rounded) return fail(DQL_EINVAL, "null pointer");
-  if (lo_bits > hi_bits || hi_bits > 0x7f7fffffu) return fail(DQL_EINVAL, "bit patterns must satisfy lo <= hi <= 0x7f7fffff (largest finite float32)");
-  OP_PROLOGUE(device)
-  DevBuf b;
-  if (b.alloc(sizeof(unsigned long long))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  HIP_TRY(hipMemset(b.p, 0, sizeof(unsigned long long)));
-  hipLaunchKernelGGL(k_selftest_sqrt, dim3(256 * 32), dim3(256), 0, 0, (unsigned)lo_bits, (unsigned)hi_bits, (unsigned long long*)b.p);
-  HIP_TRY(hipGetLastError());
-  unsigned long long n = 0;
-  HIP_TRY(hipMemcpy(&n, b.p, sizeof(n), hipMemcpyDeviceToHost));
-  *not_correctly_rounded = (int64_t)n;
-  return DQL_OK;
-}
-
-int dql_place(const dql_config* cfg, int device, const double* x0, const double* mp, int64_t n, double* out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (n < 0 || (n > 0 && (!x0 || !mp || !out))) return fail(DQL_EINVAL, "null array");
-  if (n == 0) return DQL_OK;
-  OP_PROLOGUE(device)
-  DevBuf a, b, o;
-  UP(a, x0, (size_t)n * sizeof(double)); UP(b, mp, (size_t)n * sizeof(double));
-  if (o.alloc((size_t)n * sizeof(double))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  if (cfg->dtype == DQL_F32) hipLaunchKernelGGL(k_place<float>, dim3(grid), dim3(256), 0, 0, (int)cfg->init_uniform, (float)cfg->p_max, (const double*)a.p, (const double*)b.p, (long long)n, (double*)o.p);
-  else hipLaunchKernelGGL(k_place<double>, dim3(grid), dim3(256), 0, 0, (int)cfg->init_uniform, (double)cfg->p_max, (const double*)a.p, (const double*)b.p, (long long)n, (double*)o.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, o.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-// ---- greedy roll-outs ----
-static thread_local double g_rollout_ms = -1.0;
-static thread_local int g_rollout_inst[3] = {0, 0, 0};
-extern "C++" {
-template <typename T, int XMODE> static void launch_rollout(const dql_config& cfg, const void* mdpk, const double* qa, const double* qb, const long long* mgr0, const int* sched,
-                                                           const RolloutOut& out, unsigned long long seed, int n_tables, long long envs_per_table, int max_steps) {
-  RolloutArgs<T> a;
-  a.c = make_simk<T>(cfg);
-  a.mdp = (const MdpK<T> DQL_CONST_AS*)mdpk;
-  a.mdp_run = MdpRun<T>{cfg.gamma, (T)(cfg.t_max * cfg.f_ag), cfg.goal_logic};
-  a.init = make_rollout_init<T>(cfg);
-  a.qa = qa; a.qb = qb;
-  a.mgr0 = (const long long DQL_CONST_AS*)mgr0; a.sched = (const int DQL_CONST_AS*)sched;
-  a.out = out; a.seed = seed; a.blocks_per_table = (int)(envs_per_table / 64); a.max_steps = max_steps;
-  g_rollout_inst[0] = (int)sizeof(T); g_rollout_inst[1] = TICK_PLAIN; g_rollout_inst[2] = XMODE;
-  hipLaunchKernelGGL((k_rollout<T, TICK_PLAIN, XMODE>), dim3((unsigned)((long long)n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
-}
-}  // extern "C++"
-int dql_rollout_n_fields(int32_t* n_record, int32_t* n_trace) { if (n_record) *n_record = RO_N_RECORD; if (n_trace) *n_trace = RO_N_TRACE; return DQL_OK; }
-const char* dql_rollout_field_name(int32_t i, int32_t is_trace) { return (i >= 0 && i < (is_trace ? RO_N_TRACE : RO_N_RECORD)) ? k_rollout_field_names[i] : nullptr; }
-int dql_rollout(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, uint64_t seed, int32_t max_steps, const double* qa, const double* qb,
-                int32_t* code, int32_t* steps, double* rec, int32_t trace_envs, double* trace_or_null) {
-  int rc = check_config(cfg); if (rc) return rc;
-  // every argument is checked before the device is touched: a refused call starts no kernel
-  if (n_tables < 1 || n_tables > DQL_ROLLOUT_MAX_TABLES) return fail(DQL_EINVAL, "dql_rollout: n_tables must be in 1..16 (DQL_ROLLOUT_MAX_TABLES); nothing was launched");
-  if (envs_per_table < 64 || envs_per_table % 64 != 0) return fail(DQL_EINVAL, "dql_rollout: envs_per_table must be a positive multiple of 64 (one wave per workgroup, whole waves per table set); nothing was launched");
-  if ((long long)n_tables * envs_per_table > (1ll << 30)) return fail(DQL_EINVAL, "dql_rollout: n_tables * envs_per_table must be at most 2^30; nothing was launched");
-  if (max_steps < 1 || max_steps > DQL_ROLLOUT_MAX_STEPS) return fail(DQL_EINVAL, "dql_rollout: max_steps must be in 1..4096 (DQL_ROLLOUT_MAX_STEPS); nothing was launched");
-  if (trace_envs < 0 || trace_envs > 64) return fail(DQL_EINVAL, "dql_rollout: trace_envs must be in 0..64 (the trace stays inside one wave); nothing was launched");
-  if (trace_envs > 0 && !trace_or_null) return fail(DQL_EINVAL, "dql_rollout: trace_envs > 0 needs a trace buffer; nothing was launched");
-  if (!qa || !qb || !code || !steps || !rec) return fail(DQL_EINVAL, "dql_rollout: null array; nothing was launched");
-  OP_PROLOGUE(device)
-  const long long n_total = (long long)n_tables * envs_per_table;
-  const int n_per = max_steps + 1;
-  std::vector<long long> h_mgr0((size_t)n_per);
-  std::vector<int> h_sched((size_t)n_per);
-  fill_schedule(*cfg, 0, h_mgr0.data(), h_sched.data(), n_per);
-  DevBuf d_qa, d_qb, d_mgr0, d_sched, d_mdp, d_code, d_steps, d_rec, d_trace;
-  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
-  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
-  UP(d_mgr0, h_mgr0.data(), (size_t)n_per * sizeof(long long)); UP(d_sched, h_sched.data(), (size_t)n_per * sizeof(int));
-  if (cfg->dtype == DQL_F32) { const MdpK<float> m = make_mdpk<float>(*cfg); UP(d_mdp, &m, sizeof(m)); }
-  else { const MdpK<double> m = make_mdpk<double>(*cfg); UP(d_mdp, &m, sizeof(m)); }
-  if (d_code.alloc((size_t)n_total * sizeof(int)) || d_steps.alloc((size_t)n_total * sizeof(int)) || d_rec.alloc((size_t)RO_N_RECORD * n_total * sizeof(double))) return fail(DQL_ENOMEM, "hipMalloc failed");
-  const size_t trace_bytes = (size_t)n_per * RO_N_TRACE * (size_t)trace_envs * sizeof(double);
-  if (trace_envs > 0) {
-    if (d_trace.alloc(trace_bytes)) return fail(DQL_ENOMEM, "hipMalloc failed");
-    HIP_TRY(hipMemset(d_trace.p, 0xff, trace_bytes));  // all ones = NaN: what a row keeps after its env's last period
-  }
-  const RolloutOut out{(int*)d_code.p, (int*)d_steps.p, (double*)d_rec.p, trace_envs > 0 ? (double*)d_trace.p : nullptr, n_total, trace_envs};
-  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
-  HIP_TRY(hipEventCreate(&e0.e)); HIP_TRY(hipEventCreate(&e1.e));
-  HIP_TRY(hipEventRecord(e0.e, 0));
-  const bool two = cfg->two_axis != 0;
-  if (cfg->dtype == DQL_F32) {
-    if (two) launch_rollout<float, X_TWO>(*cfg, d_mdp.p, (const double*)d_qa.p, (const double*)d_qb.p, (const long long*)d_mgr0.p, (const int*)d_sched.p, out, seed, n_tables, envs_per_table, max_steps);
-    else launch_rollout<float, X_ONLY>(*cfg, d_mdp.p, (const double*)d_qa.p, (const double*)d_qb.p, (const long long*)d_mgr0.p, (const int*)d_sched.p, out, seed, n_tables, envs_per_table, max_steps);
-  } else {
-    if (two) launch_rollout<double, X_TWO>(*cfg, d_mdp.p, (const double*)d_qa.p, (const double*)d_qb.p, (const long long*)d_mgr0.p, (const int*)d_sched.p, out, seed, n_tables, envs_per_table, max_steps);
-    else launch_rollout<double, X_ONLY>(*cfg, d_mdp.p, (const double*)d_qa.p, (const double*)d_qb.p, (const long long*)d_mgr0.p, (const int*)d_sched.p, out, seed, n_tables, envs_per_table, max_steps);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e1.e, 0));
-  HIP_TRY(hipMemcpy(code, d_code.p, (size_t)n_total * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(steps, d_steps.p, (size_t)n_total * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(rec, d_rec.p, (size_t)RO_N_RECORD * n_total * sizeof(double), hipMemcpyDeviceToHost));
-  if (trace_envs > 0) HIP_TRY(hipMemcpy(trace_or_null, d_trace.p, trace_bytes, hipMemcpyDeviceToHost));
-  HIP_TRY(hipEventSynchronize(e1.e));
-  float ms = 0.0f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
-  g_rollout_ms = (double)ms;
-  return DQL_OK;
-}
-int dql_diag_rollout_last(double* kernel_ms, int32_t* out3) {
-  if (!kernel_ms || !out3) return fail(DQL_EINVAL, "null pointer");
-  if (g_rollout_ms < 0.0) return fail(DQL_ESTATE, "no dql_rollout call has completed on this thread");
-  *kernel_ms = g_rollout_ms;
-  for (int k = 0; k < 3; ++k) out3[k] = g_rollout_inst[k];
-  return DQL_OK;
-}
-
-// ---- greedy scoring ----
-static thread_local double g_score_ms = -1.0;
-static thread_local int g_score_inst[3] = {0, 0, 0};
-extern "C++" {
-template <typename T, int XMODE> static void launch_score(const dql_config& cfg, const void* mdpk, const double* qa, const double* qb, const long long* mgr0, const int* sched,
-                                                         unsigned long long* by_code, unsigned long long* steps_sum, const ScoreLog& log, unsigned long long seed,
-                                                         long long n_tables, long long envs_per_table, int episodes, int max_steps) {
-  ScoreArgs<T> a;
-  a.c = make_simk<T>(cfg);
-  a.mdp = (const MdpK<T> DQL_CONST_AS*)mdpk;
-  a.mdp_run = MdpRun<T>{cfg.gamma, (T)(cfg.t_max * cfg.f_ag), cfg.goal_logic};
-  a.init = make_rollout_init<T>(cfg);
-  a.qa = qa; a.qb = qb;
-  a.mgr0 = (const long long DQL_CONST_AS*)mgr0; a.sched = (const int DQL_CONST_AS*)sched;
-  a.by_code = by_code; a.steps_sum = steps_sum; a.log = log;
-  a.seed = seed; a.blocks_per_table = (int)(envs_per_table / 64); a.max_steps = max_steps; a.episodes = episodes;
-  g_score_inst[0] = (int)sizeof(T); g_score_inst[1] = TICK_PLAIN; g_score_inst[2] = XMODE;
-  hipLaunchKernelGGL((k_score<T, TICK_PLAIN, XMODE>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
-}
-}  // extern "C++"
-// every argument both entry points share, checked before the device is touched: a refused call starts no kernel
-static int score_check(const char* who, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, int32_t max_steps, const int64_t* by_code, const int64_t* steps_sum,
-                       const uint8_t* ep_code, const uint16_t* ep_steps) {
-  const std::string w(who);
-  if (n_tables < 1 || n_tables > DQL_SCORE_MAX_TABLES) return fail(DQL_EINVAL, w + ": the number of table sets must be in 1..2^20 (DQL_SCORE_MAX_TABLES); nothing was launched");
-  if (envs_per_table < 64 || envs_per_table % 64 != 0) return fail(DQL_EINVAL, w + ": the envs per table set must be a positive multiple of 64 (one wave per workgroup, whole waves per table set); nothing was launched");
-  if (envs_per_table > (1ll << 30) || n_tables * envs_per_table > (1ll << 30)) return fail(DQL_EINVAL, w + ": table sets x envs must be at most 2^30; nothing was launched");
-  if (episodes_per_env < 1 || episodes_per_env > DQL_SCORE_MAX_EPISODES) return fail(DQL_EINVAL, w + ": episodes_per_env must be in 1..64 (DQL_SCORE_MAX_EPISODES); nothing was launched");
-  if (max_steps < 1 || max_steps > DQL_SCORE_MAX_STEPS) return fail(DQL_EINVAL, w + ": max_steps must be in 1..4096 (DQL_SCORE_MAX_STEPS); nothing was launched");
-  if ((ep_code == nullptr) != (ep_steps == nullptr)) return fail(DQL_EINVAL, w + ": the episode log needs both arrays or neither; nothing was launched");
-  if (!by_code || !steps_sum) return fail(DQL_EINVAL, w + ": null array; nothing was launched");
-  return DQL_OK;
-}
-// d_qa / d_qb: [n_tables][DQL_N_CELLS] on the current device
-static int score_run(const dql_config* cfg, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, const double* d_qa, const double* d_qb,
-                     int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code, uint16_t* ep_steps) {
-  const long long n_total = n_tables * envs_per_table;
-  const int n_per = max_steps + 1;
-  std::vector<long long> h_mgr0((size_t)n_per);
-  std::vector<int> h_sched((size_t)n_per);
-  fill_schedule(*cfg, 0, h_mgr0.data(), h_sched.data(), n_per);
-  DevBuf d_mgr0, d_sched, d_mdp, d_sums, d_code, d_steps;
-  UP(d_mgr0, h_mgr0.data(), (size_t)n_per * sizeof(long long)); UP(d_sched, h_sched.data(), (size_t)n_per * sizeof(int));
-  if (cfg->dtype == DQL_F32) { const MdpK<float> m = make_mdpk<float>(*cfg); UP(d_mdp, &m, sizeof(m)); }
-  else { const MdpK<double> m = make_mdpk<double>(*cfg); UP(d_mdp, &m, sizeof(m)); }
-  // one buffer for both sums: [n_tables][SCORE_N_COLS] counts, then [n_tables] step totals
-  const size_t sums_bytes = (size_t)n_tables * (SCORE_N_COLS + 1) * sizeof(unsigned long long);
-  if (d_sums.alloc(sums_bytes)) return fail(DQL_ENOMEM, "hipMalloc failed");
-  HIP_TRY(hipMemset(d_sums.p, 0, sums_bytes));
-  const size_t log_n = (size_t)episodes * (size_t)n_total;
-  if (ep_code) {
-    if (d_code.alloc(log_n) || d_steps.alloc(log_n * sizeof(uint16_t))) return fail(DQL_ENOMEM, "hipMalloc failed");
-    HIP_TRY(hipMemset(d_code.p, 0xff, log_n));  // not finished
-    HIP_TRY(hipMemset(d_steps.p, 0, log_n * sizeof(uint16_t)));
-  }
-  unsigned long long* d_by_code = (unsigned long long*)d_sums.p;
-  unsigned long long* d_steps_sum = d_by_code + (size_t)n_tables * SCORE_N_COLS;
-  const ScoreLog log{(uint8_t*)d_code.p, (uint16_t*)d_steps.p, n_total};
-  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
-  HIP_TRY(hipEventCreate(&e0.e)); HIP_TRY(hipEventCreate(&e1.e));
-  HIP_TRY(hipEventRecord(e0.e, 0));
-  const bool two = cfg->two_axis != 0;
-  const long long* mg = (const long long*)d_mgr0.p; const int* sc = (const int*)d_sched.p;
-  if (cfg->dtype == DQL_F32) {
-    if (two) launch_score<float, X_TWO>(*cfg, d_mdp.p, d_qa, d_qb, mg, sc, d_by_code, d_steps_sum, log, seed, n_tables, envs_per_table, episodes, max_steps);
-    else launch_score<float, X_ONLY>(*cfg, d_mdp.p, d_qa, d_qb, mg, sc, d_by_code, d_steps_sum, log, seed, n_tables, envs_per_table, episodes, max_steps);
-  } else {
-    if (two) launch_score<double, X_TWO>(*cfg, d_mdp.p, d_qa, d_qb, mg, sc, d_by_code, d_steps_sum, log, seed, n_tables, envs_per_table, episodes, max_steps);
-    else launch_score<double, X_ONLY>(*cfg, d_mdp.p, d_qa, d_qb, mg, sc, d_by_code, d_steps_sum, log, seed, n_tables, envs_per_table, episodes, max_steps);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e1.e, 0));
-  HIP_TRY(hipMemcpy(by_code, d_by_code, (size_t)n_tables * SCORE_N_COLS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(steps_sum, d_steps_sum, (size_t)n_tables * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (ep_code) {
-    HIP_TRY(hipMemcpy(ep_code, d_code.p, log_n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ep_steps, d_steps.p, log_n * sizeof(uint16_t), hipMemcpyDeviceToHost));
-  }
-  HIP_TRY(hipEventSynchronize(e1.e));
-  float ms = 0.0f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
-  g_score_ms = (double)ms;
-  return DQL_OK;
-}
-int dql_score(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
-              const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null) {
-  int rc = check_config(cfg); if (rc) return rc;
-  rc = score_check("dql_score", n_tables, envs_per_table, episodes_per_env, max_steps, by_code, steps_sum, ep_code_or_null, ep_steps_or_null); if (rc) return rc;
-  if (!qa || !qb) return fail(DQL_EINVAL, "dql_score: null array; nothing was launched");
-  OP_PROLOGUE(device)
-  DevBuf d_qa, d_qb;
-  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
-  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
-  return score_run(cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, (const double*)d_qa.p, (const double*)d_qb.p, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
-}
-int dql_diag_score_last(double* kernel_ms, int32_t* inst3) {
-  if (!kernel_ms || !inst3) return fail(DQL_EINVAL, "null pointer");
-  if (g_score_ms < 0.0) return fail(DQL_ESTATE, "no dql_score or dql_ensemble_score call has completed on this thread");
-  *kernel_ms = g_score_ms;
-  for (int k = 0; k < 3; ++k) inst3[k] = g_score_inst[k];
-  return DQL_OK;
-}
-
-// ---- ensembles of sequential learners ----
-struct dql_ensemble {
-  dql_config cfg;
-  int device = 0;
-  long long n = 0;
-  unsigned long long seed = 0;
-  long long j = 0;  // the ensemble's period index (period 0 is the reset period)
-  void* sr = nullptr; int4* si = nullptr; void* mdpk = nullptr;
-  LearnMem mem{};
-  LearnSched sched{};
-  double* alpha_tab = nullptr; uint32_t* eps_tab = nullptr;
-  long long* d_mgr0 = nullptr; int* d_sched = nullptr;  // [LEARN_MAX_PERIODS]
-  double last_ms = -1.0;
-  // per-learner curriculum levels; advance_every = 0: the mode is off
-  AdvanceMem adv{};
-  AdvanceRule rule{};
-  int advance_every = 0;
-  void* mdpk5 = nullptr;                                      // [DQL_MAX_LEVELS] MdpK<T>, entry k with working = k
-  LevelSched* d_lv = nullptr; LevelSched h_lv[DQL_MAX_LEVELS]{}; bool have_lv[DQL_MAX_LEVELS]{};
-  int* d_worklist = nullptr; int* d_wave_level = nullptr; long long wl_slots = 0;
-  long long n_launches = 0, launched_periods = 0, launched_wave_periods = 0;  // since creation (dql_diag_ensemble_launches)
-};
-#define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
-static void ens_free(dql_ensemble* x) {
-  void* ptrs[] = {x->sr, x->si, x->mdpk, x->mem.qa, x->mem.qb, x->mem.count, x->mem.decisions, x->mem.by_code, x->mem.episodes, x->mem.successes, x->mem.level_episodes,
-                  x->mem.win_count, x->mem.win_bits, x->mem.promoted, x->mem.frozen, x->mem.log_code, x->mem.log_len, x->mem.log_n, x->mem.faults, x->alpha_tab, x->eps_tab,
-                  x->d_mgr0, x->d_sched, x->adv.level, x->adv.promoted_at, x->adv.episodes_at, x->adv.entered_period, x->mdpk5, x->d_lv, x->d_worklist, x->d_wave_level,
-                  (void*)x->h_lv[0].eps_tab, (void*)x->h_lv[1].eps_tab, (void*)x->h_lv[2].eps_tab, (void*)x->h_lv[3].eps_tab, (void*)x->h_lv[4].eps_tab};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  delete x;
-}
-static int ens_upload_mdpk(dql_ensemble* x) {
-  if (x->cfg.dtype == DQL_F32) { const MdpK<float> m = make_mdpk<float>(x->cfg); HIP_TRY(hipMemcpy(x->mdpk, &m, sizeof(m), hipMemcpyHostToDevice)); }
-  else { const MdpK<double> m = make_mdpk<double>(x->cfg); HIP_TRY(hipMemcpy(x->mdpk, &m, sizeof(m), hipMemcpyHostToDevice)); }
-  return DQL_OK;
-}
-// every learner to level k: the per-level history from level k on is cleared, level k is entered at the present period index
-static int ens_set_levels(dql_ensemble* x, int k) {
-  const size_t n = (size_t)x->n;
-  if (x->j == 0) HIP_TRY(hipMemset(x->adv.entered_period, 0xff, (size_t)DQL_MAX_LEVELS * n * sizeof(long long)));  // nothing was flown: no level below k was ever entered
-  std::vector<int> lv(n, k);
-  HIP_TRY(hipMemcpy(x->adv.level, lv.data(), n * sizeof(int), hipMemcpyHostToDevice));
-  const size_t from = (size_t)k * n, rest = (size_t)(DQL_MAX_LEVELS - k) * n;
-  HIP_TRY(hipMemset(x->adv.promoted_at + from, 0xff, rest * sizeof(int)));
-  HIP_TRY(hipMemset(x->adv.episodes_at + from, 0, rest * sizeof(int)));
-  HIP_TRY(hipMemset(x->adv.entered_period + from, 0xff, rest * sizeof(long long)));
-  std::vector<long long> at(n, x->j);
-  HIP_TRY(hipMemcpy(x->adv.entered_period + from, at.data(), n * sizeof(long long), hipMemcpyHostToDevice));
-  return DQL_OK;
-}
-// the five levels' MdpK (they differ in `working` only), read by k_learn_levels at the wave's level
-static int ens_upload_mdpk5(dql_ensemble* x) {
-  dql_config c = x->cfg;
-  for (int k = 0; k < DQL_MAX_LEVELS; ++k) {
-    c.working_curriculum_step = k;
-    if (x->cfg.dtype == DQL_F32) { const MdpK<float> m = make_mdpk<float>(c); HIP_TRY(hipMemcpy((MdpK<float>*)x->mdpk5 + k, &m, sizeof(m), hipMemcpyHostToDevice)); }
-    else { const MdpK<double> m = make_mdpk<double>(c); HIP_TRY(hipMemcpy((MdpK<double>*)x->mdpk5 + k, &m, sizeof(m), hipMemcpyHostToDevice)); }
-  }
-  return DQL_OK;
-}
-// per-level episode counts, windows, promotion records and frozen flags back to "just started"
-static int ens_rearm(dql_ensemble* x) {
-  const size_t n = (size_t)x->n;
-  HIP_TRY(hipMemset(x->mem.level_episodes, 0, n * sizeof(int)));
-  HIP_TRY(hipMemset(x->mem.win_count, 0, n * sizeof(int)));
-  HIP_TRY(hipMemset(x->mem.win_bits, 0, 2 * n * sizeof(unsigned long long)));
-  HIP_TRY(hipMemset(x->mem.promoted, 0xff, n * sizeof(int)));
-  HIP_TRY(hipMemset(x->mem.frozen, 0, n * sizeof(int)));
-  return DQL_OK;
-}
-extern "C++" {
-template <typename T> static int ens_init(dql_ensemble* x) {
-  InitArgs<T> a;
-  a.c = make_simk<T>(x->cfg);
-  a.sr = (Quad<T>*)x->sr; a.si = x->si; a.n = x->n; a.seed = x->seed; a.env_id_offset = 0;
-  const RolloutInit<T> r = make_rollout_init<T>(x->cfg);
-  a.hover = r.hover; a.vz_integ = r.vz_integ; a.r_lo = r.r_lo; a.r_hi = r.r_hi; a.t_lo = r.t_lo; a.t_hi = r.t_hi;
-  hipLaunchKernelGGL(k_init<T>, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, a);
-  HIP_TRY(hipGetLastError());
-  return DQL_OK;
-}
-template <typename T> static void ens_launch(dql_ensemble* x, int n_periods) {
-  LearnArgs<T> a;
-  a.c = make_simk<T>(x->cfg);
-  a.mdp = (const MdpK<T> DQL_CONST_AS*)x->mdpk;
-  a.mdp_run = MdpRun<T>{x->cfg.gamma, (T)(x->cfg.t_max * x->cfg.f_ag), x->cfg.goal_logic};
-  a.sched = x->sched; a.mem = x->mem;
-  a.sr = (Quad<T>*)x->sr; a.si = x->si;
-  a.mgr0 = (const long long DQL_CONST_AS*)x->d_mgr0; a.tick_sched = (const int DQL_CONST_AS*)x->d_sched;
-  a.seed = x->seed; a.j0 = x->j; a.n_periods = n_periods;
-  hipLaunchKernelGGL((k_learn<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)((x->n + 63) / 64)), dim3(64), 0, 0, a);
-}
-template <typename T> static void ens_launch_levels(dql_ensemble* x, int n_periods, int n_waves) {
-  LearnLevelsArgs<T> g;
-  LearnArgs<T>& a = g.a;
-  a.c = make_simk<T>(x->cfg);
-  a.mdp = (const MdpK<T> DQL_CONST_AS*)x->mdpk5;
-  a.mdp_run = MdpRun<T>{x->cfg.gamma, (T)(x->cfg.t_max * x->cfg.f_ag), x->cfg.goal_logic};
-  a.sched = x->sched; a.mem = x->mem;
-  a.sr = (Quad<T>*)x->sr; a.si = x->si;
-  a.mgr0 = (const long long DQL_CONST_AS*)x->d_mgr0; a.tick_sched = (const int DQL_CONST_AS*)x->d_sched;
-  a.seed = x->seed; a.j0 = x->j; a.n_periods = n_periods;
-  g.lv = (const LevelSched DQL_CONST_AS*)x->d_lv; g.worklist = x->d_worklist; g.wave_level = (const int DQL_CONST_AS*)x->d_wave_level; g.n_waves = n_waves;
-  hipLaunchKernelGGL((k_learn_levels<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
-}
-template <typename T> static int ens_get_state_t(dql_ensemble* x, double* out) {
-  const long long n = x->n;
-  std::vector<T> h((size_t)NQ_REAL * n * 4);
-  HIP_TRY(hipMemcpy(h.data(), x->sr, h.size() * sizeof(T), hipMemcpyDeviceToHost));
-  for (int f = 0; f < NF_REAL; ++f) { const int q = f / 4, k = f % 4; for (long long i = 0; i < n; ++i) out[(long long)f * n + i] = (double)h[((size_t)q * n + i) * 4 + k]; }
-  return DQL_OK;
-}
-}  // extern "C++"
-#define ENS_ALLOC(ptr, bytes) do { if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { (ptr) = nullptr; ens_free(x); return fail(DQL_ENOMEM, "hipMalloc failed"); } \
-                                   if (hipMemset((ptr), 0, (bytes)) != hipSuccess) { ens_free(x); return fail(DQL_EHIP, "hipMemset failed"); } } while (0)
-int dql_ensemble_create(const dql_config* cfg, int device, int64_t n_learners, uint64_t seed, int32_t log_capacity, dql_ensemble** out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (!out) return fail(DQL_EINVAL, "dql_ensemble_create: null pointer; nothing was launched");
-  if (cfg->two_axis) return fail(DQL_EINVAL, "dql_ensemble_create: two-axis configs are refused (the reference's learner is x-only); nothing was launched");
-  if (cfg->trajectory == DQL_TRAJ_EIGHT) return fail(DQL_EINVAL, "dql_ensemble_create: the figure-eight trajectory is refused (the reference's learner is x-only); nothing was launched");
-  if (n_learners < 1 || n_learners > DQL_ENSEMBLE_MAX_LEARNERS) return fail(DQL_EINVAL, "dql_ensemble_create: n_learners must be in 1..2^20 (DQL_ENSEMBLE_MAX_LEARNERS); nothing was launched");
-  if (log_capacity < 0 || log_capacity > DQL_ENSEMBLE_MAX_LOG) return fail(DQL_EINVAL, "dql_ensemble_create: log_capacity must be in 0..2^20 (DQL_ENSEMBLE_MAX_LOG); nothing was launched");
-  OP_PROLOGUE(device)
-  dql_ensemble* x = new dql_ensemble;
-  x->cfg = *cfg; x->device = device; x->n = n_learners; x->seed = seed;
-  const size_t n = (size_t)n_learners, real = cfg->dtype == DQL_F32 ? 4 : 8;
-  const size_t TB = n * DQL_N_CELLS * sizeof(double);
-  ENS_ALLOC(x->sr, (size_t)NQ_REAL * n * 4 * real);
-  ENS_ALLOC(x->si, n * sizeof(int4));
-  ENS_ALLOC(x->mdpk, cfg->dtype == DQL_F32 ? sizeof(MdpK<float>) : sizeof(MdpK<double>));
-  ENS_ALLOC(x->mem.qa, TB); ENS_ALLOC(x->mem.qb, TB); ENS_ALLOC(x->mem.count, TB);
-  ENS_ALLOC(x->mem.decisions, n * sizeof(unsigned long long));
-  ENS_ALLOC(x->mem.by_code, (size_t)DQL_N_CHECK_CODES * n * sizeof(unsigned long long));
-  ENS_ALLOC(x->mem.episodes, n * sizeof(int)); ENS_ALLOC(x->mem.successes, n * sizeof(int));
-  ENS_ALLOC(x->mem.level_episodes, n * sizeof(int)); ENS_ALLOC(x->mem.win_count, n * sizeof(int));
-  ENS_ALLOC(x->mem.win_bits, 2 * n * sizeof(unsigned long long));
-  ENS_ALLOC(x->mem.promoted, n * sizeof(int)); ENS_ALLOC(x->mem.frozen, n * sizeof(int));
-  ENS_ALLOC(x->mem.log_code, n * (size_t)(log_capacity ? log_capacity : 1)); ENS_ALLOC(x->mem.log_len, n * (size_t)(log_capacity ? log_capacity : 1) * sizeof(uint16_t));
-  ENS_ALLOC(x->mem.log_n, n * sizeof(int));
-  ENS_ALLOC(x->mem.faults, sizeof(unsigned long long));
-  ENS_ALLOC(x->d_mgr0, (size_t)LEARN_MAX_PERIODS * sizeof(long long)); ENS_ALLOC(x->d_sched, (size_t)LEARN_MAX_PERIODS * sizeof(int));
-  ENS_ALLOC(x->adv.level, n * sizeof(int));
-  ENS_ALLOC(x->adv.promoted_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int)); ENS_ALLOC(x->adv.episodes_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int));
-  ENS_ALLOC(x->adv.entered_period, (size_t)DQL_MAX_LEVELS * n * sizeof(long long));
-  ENS_ALLOC(x->mdpk5, (size_t)DQL_MAX_LEVELS * (cfg->dtype == DQL_F32 ? sizeof(MdpK<float>) : sizeof(MdpK<double>)));
-  ENS_ALLOC(x->d_lv, (size_t)DQL_MAX_LEVELS * sizeof(LevelSched));
-  x->wl_slots = worklist_capacity(n_learners);
-  ENS_ALLOC(x->d_worklist, (size_t)x->wl_slots * sizeof(int)); ENS_ALLOC(x->d_wave_level, (size_t)(x->wl_slots / ADV_WAVE) * sizeof(int));
-  x->mem.n = n_learners; x->mem.log_cap = log_capacity;
-  rc = ens_upload_mdpk(x);
-  if (!rc) rc = ens_upload_mdpk5(x);
-  if (!rc) rc = ens_set_levels(x, 0);  // the whole history cleared ...
-  if (!rc) rc = ens_set_levels(x, cfg->working_curriculum_step);  // ... and the config's level entered at period 0
-  if (!rc) rc = ens_rearm(x);
-  if (!rc) rc = cfg->dtype == DQL_F32 ? ens_init<float>(x) : ens_init<double>(x);
-  // default schedules: the plateau learning rate, no exploration, the reference's window (100 episodes, 97 successes) and no episode budget
-  const double a0 = cfg->alpha_min; const double e0 = 0.0;
-  if (!rc) rc = dql_ensemble_set_schedules(x, &a0, 1, &e0, 1, 100, 97, INT32_MAX);
-  if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(DQL_EHIP, "hipDeviceSynchronize failed");
-  if (rc) { ens_free(x); return rc; }
-  *out = x;
-  return DQL_OK;
-}
-int dql_ensemble_destroy(dql_ensemble* x) {
-  if (!x) return DQL_OK;
-  (void)hipSetDevice(x->device);
-  (void)hipDeviceSynchronize();
-  ens_free(x);
-  return DQL_OK;
-}
-int dql_ensemble_n_learners(dql_ensemble* x, int64_t* n) {
-  CHECK_ENS(x);
-  if (!n) return fail(DQL_EINVAL, "null pointer");
-  *n = x->n;
-  return DQL_OK;
-}
-int dql_ensemble_set_schedules(dql_ensemble* x, const double* alpha, int32_t n_alpha, const double* eps, int32_t n_eps, int32_t window, int32_t min_successes,
-                               int32_t max_episodes) {
-  CHECK_ENS(x);
-  if (!alpha || !eps) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: null table");
-  if (n_alpha < 1 || n_alpha > (1 << 22) || n_eps < 1 || n_eps > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: table lengths must be in 1..2^22");
-  if (window < 1 || window > DQL_ENSEMBLE_MAX_WINDOW) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: the promotion window must be in 1..128 (DQL_ENSEMBLE_MAX_WINDOW)");
-  if (min_successes < 1 || max_episodes < 1) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: min_successes and max_episodes must be positive");
-  for (int i = 0; i < n_alpha; ++i) if (!(alpha[i] >= 0.0 && alpha[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: learning rates must be in [0, 1]");
-  for (int i = 0; i < n_eps; ++i) if (!(eps[i] >= 0.0 && eps[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: exploration rates must be in [0, 1]");
-  HIP_TRY(hipSetDevice(x->device));
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<uint32_t> thr((size_t)n_eps);
-  for (int i = 0; i < n_eps; ++i) thr[(size_t)i] = eps_threshold(eps[i]);
-  double* d_a = nullptr; uint32_t* d_e = nullptr;
-  if (hipMalloc((void**)&d_a, (size_t)n_alpha * sizeof(double)) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc failed");
-  if (hipMalloc((void**)&d_e, (size_t)n_eps * sizeof(uint32_t)) != hipSuccess) { (void)hipFree(d_a); return fail(DQL_ENOMEM, "hipMalloc failed"); }
-  if (hipMemcpy(d_a, alpha, (size_t)n_alpha * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_e, thr.data(), (size_t)n_eps * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d_a); (void)hipFree(d_e);
-    return fail(DQL_EHIP, "hipMemcpy failed");
-  }
-  if (x->alpha_tab) (void)hipFree(x->alpha_tab);
-  if (x->eps_tab) (void)hipFree(x->eps_tab);
-  x->alpha_tab = d_a; x->eps_tab = d_e;
-  x->sched = LearnSched{d_a, n_alpha, x->cfg.alpha_min, d_e, n_eps, window, min_successes, max_episodes};
-  return DQL_OK;
-}
-int dql_ensemble_rearm(dql_ensemble* x) {
-  CHECK_ENS(x);
-  HIP_TRY(hipSetDevice(x->device));
-  HIP_TRY(hipDeviceSynchronize());
-  return ens_rearm(x);
-}
-int dql_ensemble_set_level(dql_ensemble* x, int32_t k) {
-  CHECK_ENS(x);
-  if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_level: curriculum step must be in 0..4");
-  if (x->advance_every && k > x->rule.last_level)
-    return fail(DQL_EINVAL, "dql_ensemble_set_level: in curriculum mode the level must not exceed last_level (raise it with dql_ensemble_set_curriculum first); nothing was changed");
-  HIP_TRY(hipSetDevice(x->device));
-  HIP_TRY(hipDeviceSynchronize());
-  x->cfg.working_curriculum_step = k;
-  int rc = ens_upload_mdpk(x); if (rc) return rc;
-  hipLaunchKernelGGL(k_mark_reset, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->si, (const uint8_t*)nullptr, (long long)x->n);  // every env re-enters through reset
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  rc = ens_set_levels(x, k); if (rc) return rc;
-  return ens_rearm(x);
-}
-int dql_ensemble_n_live(dql_ensemble* x, int64_t* n_live) {
-  CHECK_ENS(x);
-  if (!n_live) return fail(DQL_EINVAL, "null pointer");
-  HIP_TRY(hipSetDevice(x->device));
-  std::vector<int> h((size_t)x->n);
-  HIP_TRY(hipMemcpy(h.data(), x->mem.frozen, h.size() * sizeof(int), hipMemcpyDeviceToHost));
-  int64_t live = 0;
-  for (int v : h) live += v ? 0 : 1;
-  *n_live = live;
-  return DQL_OK;
-}
-// frozen, level and promoted of every learner -> host; the learners that are not finished for good
-static int ens_fetch_levels(dql_ensemble* x, std::vector<int>& frozen, std::vector<int>& level, std::vector<int>& promoted, int64_t* unfinished) {
-  const size_t n = (size_t)x->n;
-  frozen.resize(n); level.resize(n); promoted.resize(n);
-  HIP_TRY(hipMemcpy(frozen.data(), x->mem.frozen, n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(level.data(), x->adv.level, n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(promoted.data(), x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
-  int64_t u = 0;
-  for (size_t l = 0; l < n; ++l) u += learner_finished(frozen[l], level[l], promoted[l], x->rule) ? 0 : 1;
-  *unfinished = u;
-  return DQL_OK;
-}
-// dql_ensemble_run in curriculum mode: the launches are cut at the multiples of advance_every; at such a period index j, before period j is flown, every
-// learner takes advance_learner's step; each launch flies the live learners regrouped by level (build_worklist)
-static int ens_run_levels(dql_ensemble* x, int64_t periods) {
-  std::vector<int> frozen, level, promoted;
-  int64_t unfinished = 0;
-  int rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
-  // the level a learner stands on is flown whatever last_level says, so its schedule is asked for first; then every level on its way up to last_level
-  for (size_t l = 0; l < (size_t)x->n; ++l) {
-    bool ok = level[l] >= 0 && level[l] < DQL_MAX_LEVELS && x->have_lv[level[l]];
-    for (int k = level[l] + 1; ok && k <= x->rule.last_level && k < DQL_MAX_LEVELS; ++k) ok = x->have_lv[k];
-    if (!ok) return fail(DQL_EINVAL, "dql_ensemble_run: curriculum mode needs dql_ensemble_set_level_schedules for every level from the learners' up to last_level; nothing was launched");
-  }
-  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
-  HIP_TRY(hipEventCreate(&e0.e)); HIP_TRY(hipEventCreate(&e1.e));
-  HIP_TRY(hipEventRecord(e0.e, 0));
-  std::vector<long long> h_mgr0((size_t)LEARN_MAX_PERIODS);
-  std::vector<int> h_sched((size_t)LEARN_MAX_PERIODS);
-  std::vector<int> worklist((size_t)x->wl_slots), wave_level((size_t)(x->wl_slots / ADV_WAVE));
-  const long long E = x->advance_every;
-  long long left = periods;
-  while (left > 0) {
-    if (x->j % E == 0) {  // an advance point
-      hipLaunchKernelGGL(k_ens_advance, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->mem, x->adv, x->rule, x->si, (long long)x->j, (int)DQL_CELLS_PER_LEVEL);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipDeviceSynchronize());
-    }
-    rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
-    if (unfinished == 0) { x->j += left; break; }  // nothing left to fly or to advance, now or later (the period index still advances by `periods`)
-    const long long to_point = E - x->j % E;
-    const int k = (int)(left < to_point ? left : to_point);  // <= advance_every <= LEARN_MAX_PERIODS
-    unsigned long long wl_faults = 0ull;
-    const int n_waves = build_worklist(frozen.data(), level.data(), x->n, worklist.data(), wave_level.data(), x->wl_slots, &wl_faults);
-    if (wl_faults) {
-      unsigned long long v = 0;
-      HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
-      v += wl_faults;
-      HIP_TRY(hipMemcpy(x->mem.faults, &v, sizeof(v), hipMemcpyHostToDevice));
-    }
-    if (n_waves > 0) {  // (nobody live: everyone unfinished waits for the next advance point)
-      fill_schedule(x->cfg, x->j, h_mgr0.data(), h_sched.data(), k);
-      HIP_TRY(hipMemcpy(x->d_mgr0, h_mgr0.data(), (size_t)k * sizeof(long long), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(x->d_sched, h_sched.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(x->d_worklist, worklist.data(), (size_t)n_waves * ADV_WAVE * sizeof(int), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(x->d_wave_level, wave_level.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
-      if (x->cfg.dtype == DQL_F32) ens_launch_levels<float>(x, k, n_waves); else ens_launch_levels<double>(x, k, n_waves);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipDeviceSynchronize());
-      x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += (long long)n_waves * k;
-    }
-    x->j += k; left -= k;
-  }
-  HIP_TRY(hipEventRecord(e1.e, 0));
-  HIP_TRY(hipEventSynchronize(e1.e));
-  float ms = 0.0f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
-  x->last_ms = (double)ms;
-  return DQL_OK;
-}
-int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
-  CHECK_ENS(x);
-  if (periods < 1 || periods > (1ll << 40)) return fail(DQL_EINVAL, "dql_ensemble_run: periods must be in 1..2^40; nothing was launched");
-  HIP_TRY(hipSetDevice(x->device));
-  if (x->advance_every) return ens_run_levels(x, periods);
-  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
-  HIP_TRY(hipEventCreate(&e0.e)); HIP_TRY(hipEventCreate(&e1.e));
-  HIP_TRY(hipEventRecord(e0.e, 0));
-  std::vector<long long> h_mgr0((size_t)LEARN_MAX_PERIODS);
-  std::vector<int> h_sched((size_t)LEARN_MAX_PERIODS);
-  long long left = periods;
-  while (left > 0) {
-    const int k = (int)(left < LEARN_MAX_PERIODS ? left : LEARN_MAX_PERIODS);
-    if (left != periods) {  // between the launches of a long run: nothing left to fly ends it (the period index still advances by `periods`)
-      int64_t live = 0;
-      int rc = dql_ensemble_n_live(x, &live); if (rc) return rc;
-      if (live == 0) { x->j += left; break; }
-    }
-    fill_schedule(x->cfg, x->j, h_mgr0.data(), h_sched.data(), k);
-    HIP_TRY(hipMemcpy(x->d_mgr0, h_mgr0.data(), (size_t)k * sizeof(long long), hipMemcpyHostToDevice));  // (synchronous: the previous launch has read its schedule)
-    HIP_TRY(hipMemcpy(x->d_sched, h_sched.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice));
-    if (x->cfg.dtype == DQL_F32) ens_launch<float>(x, k); else ens_launch<double>(x, k);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += ((x->n + 63) / 64) * k;
-    x->j += k; left -= k;
-  }
-  HIP_TRY(hipEventRecord(e1.e, 0));
-  HIP_TRY(hipEventSynchronize(e1.e));
-  float ms = 0.0f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
-  x->last_ms = (double)ms;
-  return DQL_OK;
-}
-// ---- per-learner curriculum levels ----
-int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t advance_every, const double* ratios, int32_t advance_exhausted) {
-  CHECK_ENS(x);
-  if (advance_every < 0 || advance_every > ADV_MAX_EVERY) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_every must be in 0..4096 (0 turns the mode off); nothing was changed");
-  if (advance_every == 0) {
-    // the plain launch flies everyone at the config's level: switching off is refused while a learner stands on another one (dql_ensemble_set_level first)
-    if (x->advance_every) {
-      HIP_TRY(hipSetDevice(x->device));
-      HIP_TRY(hipDeviceSynchronize());
-      std::vector<int> lv((size_t)x->n);
-      HIP_TRY(hipMemcpy(lv.data(), x->adv.level, lv.size() * sizeof(int), hipMemcpyDeviceToHost));
-      for (int v : lv)
-        if (v != x->cfg.working_curriculum_step)
-          return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the mode cannot be switched off (advance_every = 0) while learners stand on different levels; call dql_ensemble_set_level first; nothing was changed");
-    }
-    x->advance_every = 0;
-    return DQL_OK;
-  }
-  if (!ratios) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: null ratios; nothing was changed");
-  for (int k = 0; k < DQL_MAX_LEVELS; ++k) if (!std::isfinite(ratios[k])) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the five transfer ratios must be finite; nothing was changed");
-  if (advance_exhausted != 0 && advance_exhausted != 1) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_exhausted must be 0 or 1; nothing was changed");
-  HIP_TRY(hipSetDevice(x->device));
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<int> level((size_t)x->n);
-  HIP_TRY(hipMemcpy(level.data(), x->adv.level, level.size() * sizeof(int), hipMemcpyDeviceToHost));
-  int top = 0;
-  for (int v : level) top = v > top ? v : top;
-  if (last_level < top || last_level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: last_level must lie between the learners' current level and 4; nothing was changed");
-  int rc = ens_upload_mdpk5(x); if (rc) return rc;
-  for (int k = 0; k < DQL_MAX_LEVELS; ++k) x->rule.ratios[k] = ratios[k];
-  x->rule.last_level = last_level; x->rule.advance_exhausted = advance_exhausted;
-  x->advance_every = advance_every;
-  return DQL_OK;
-}
-int dql_ensemble_set_level_schedules(dql_ensemble* x, int32_t level, const double* eps, int32_t n_eps, int32_t window, int32_t min_successes, int32_t max_episodes) {
-  CHECK_ENS(x);
-  if (level < 0 || level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: the level must be in 0..4");
-  if (!eps) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: null table");
-  if (n_eps < 1 || n_eps > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: the table length must be in 1..2^22");
-  if (window < 1 || window > DQL_ENSEMBLE_MAX_WINDOW) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: the promotion window must be in 1..128 (DQL_ENSEMBLE_MAX_WINDOW)");
-  if (min_successes < 1 || max_episodes < 1) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: min_successes and max_episodes must be positive");
-  for (int i = 0; i < n_eps; ++i) if (!(eps[i] >= 0.0 && eps[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: exploration rates must be in [0, 1]");
-  HIP_TRY(hipSetDevice(x->device));
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<uint32_t> thr((size_t)n_eps);
-  for (int i = 0; i < n_eps; ++i) thr[(size_t)i] = eps_threshold(eps[i]);
-  uint32_t* d_e = nullptr;
-  if (hipMalloc((void**)&d_e, (size_t)n_eps * sizeof(uint32_t)) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc failed");
-  LevelSched lv[DQL_MAX_LEVELS];
-  for (int k = 0; k < DQL_MAX_LEVELS; ++k) lv[k] = x->h_lv[k];
-  lv[level] = LevelSched{d_e, n_eps, window, min_successes, max_episodes};
-  if (hipMemcpy(d_e, thr.data(), (size_t)n_eps * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(x->d_lv, lv, sizeof(lv), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d_e);
-    return fail(DQL_EHIP, "hipMemcpy failed");
-  }
-  if (x->h_lv[level].eps_tab) (void)hipFree((void*)x->h_lv[level].eps_tab);
-  x->h_lv[level] = lv[level]; x->have_lv[level] = true;
-  return DQL_OK;
-}
-int dql_ensemble_get_levels(dql_ensemble* x, int32_t* level, int32_t* promoted_at, int32_t* episodes_at, int64_t* entered_period) {
-  CHECK_ENS(x);
-  if (!level || !promoted_at || !episodes_at || !entered_period) return fail(DQL_EINVAL, "dql_ensemble_get_levels: null array");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t n = (size_t)x->n;
-  HIP_TRY(hipMemcpy(level, x->adv.level, n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(promoted_at, x->adv.promoted_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(episodes_at, x->adv.episodes_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(entered_period, x->adv.entered_period, (size_t)DQL_MAX_LEVELS * n * sizeof(long long), hipMemcpyDeviceToHost));
-  // the level a learner stands on has no history entry yet: its row shows the counters as they are
-  std::vector<int> promoted(n), lvl_eps(n);
-  HIP_TRY(hipMemcpy(promoted.data(), x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(lvl_eps.data(), x->mem.level_episodes, n * sizeof(int), hipMemcpyDeviceToHost));
-  for (size_t l = 0; l < n; ++l) {
-    const int k = level[l];
-    if (k < 0 || k >= DQL_MAX_LEVELS) continue;
-    promoted_at[(size_t)k * n + l] = promoted[l]; episodes_at[(size_t)k * n + l] = lvl_eps[l];
-  }
-  return DQL_OK;
-}
-int dql_ensemble_n_unfinished(dql_ensemble* x, int64_t* n) {
-  CHECK_ENS(x);
-  if (!n) return fail(DQL_EINVAL, "null pointer");
-  if (!x->advance_every) return dql_ensemble_n_live(x, n);
-  HIP_TRY(hipSetDevice(x->device));
-  std::vector<int> frozen, level, promoted;
-  return ens_fetch_levels(x, frozen, level, promoted, n);
-}
-int dql_ensemble_get_period_index(dql_ensemble* x, int64_t* j) {
-  CHECK_ENS(x);
-  if (!j) return fail(DQL_EINVAL, "null pointer");
-  *j = x->j;
-  return DQL_OK;
-}
-int dql_ensemble_transfer(dql_ensemble* x, int32_t k, double ratio) {
-  CHECK_ENS(x);
-  if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_transfer: curriculum step must be in 0..4");
-  HIP_TRY(hipSetDevice(x->device));
-  const long long total = x->n * DQL_CELLS_PER_LEVEL;
-  hipLaunchKernelGGL(k_ens_transfer, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, x->mem.qa, x->mem.qb, (long long)x->n, (int)k,
-                     (int)((k - 1 + DQL_MAX_LEVELS) % DQL_MAX_LEVELS), ratio);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  return DQL_OK;
-}
-static int ens_slice(dql_ensemble* x, int64_t first, int64_t count, const char* who) {
-  if (first < 0 || count < 1 || first > x->n || count > x->n - first) return fail(DQL_EINVAL, std::string(who) + ": the slice [first, first + count) must lie inside [0, n_learners) and hold at least one learner");
-  return DQL_OK;
-}
-int dql_ensemble_get_tables(dql_ensemble* x, int64_t first, int64_t count, double* qa_or_null, double* qb_or_null, double* count_or_null) {
-  CHECK_ENS(x);
-  int rc = ens_slice(x, first, count, "dql_ensemble_get_tables"); if (rc) return rc;
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t off = (size_t)first * DQL_N_CELLS, bytes = (size_t)count * DQL_N_CELLS * sizeof(double);
-  if (qa_or_null) HIP_TRY(hipMemcpy(qa_or_null, x->mem.qa + off, bytes, hipMemcpyDeviceToHost));
-  if (qb_or_null) HIP_TRY(hipMemcpy(qb_or_null, x->mem.qb + off, bytes, hipMemcpyDeviceToHost));
-  if (count_or_null) HIP_TRY(hipMemcpy(count_or_null, x->mem.count + off, bytes, hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-int dql_ensemble_set_tables(dql_ensemble* x, int64_t first, int64_t count, const double* qa_or_null, const double* qb_or_null, const double* count_or_null) {
-  CHECK_ENS(x);
-  int rc = ens_slice(x, first, count, "dql_ensemble_set_tables"); if (rc) return rc;
-  if (count_or_null)  // the counters index the learning-rate table on the device
-    for (size_t i = 0; i < (size_t)count * DQL_N_CELLS; ++i)
-      if (!(count_or_null[i] >= 0.0 && count_or_null[i] < 9007199254740992.0)) return fail(DQL_EINVAL, "dql_ensemble_set_tables: visit counters must be in [0, 2^53)");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t off = (size_t)first * DQL_N_CELLS, bytes = (size_t)count * DQL_N_CELLS * sizeof(double);
-  if (qa_or_null) HIP_TRY(hipMemcpy(x->mem.qa + off, qa_or_null, bytes, hipMemcpyHostToDevice));
-  if (qb_or_null) HIP_TRY(hipMemcpy(x->mem.qb + off, qb_or_null, bytes, hipMemcpyHostToDevice));
-  if (count_or_null) HIP_TRY(hipMemcpy(x->mem.count + off, count_or_null, bytes, hipMemcpyHostToDevice));
-  return DQL_OK;
-}
-int dql_ensemble_get_counters(dql_ensemble* x, int64_t* decisions, int64_t* episodes, int64_t* successes, int64_t* by_code, int32_t* promoted, int32_t* level_episodes,
-                              uint8_t* frozen) {
-  CHECK_ENS(x);
-  if (!decisions || !episodes || !successes || !by_code || !promoted || !level_episodes || !frozen) return fail(DQL_EINVAL, "dql_ensemble_get_counters: null array");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t n = (size_t)x->n;
-  std::vector<int> h(n);
-  HIP_TRY(hipMemcpy(decisions, x->mem.decisions, n * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(by_code, x->mem.by_code, (size_t)DQL_N_CHECK_CODES * n * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h.data(), x->mem.episodes, n * sizeof(int), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; ++i) episodes[i] = h[i];
-  HIP_TRY(hipMemcpy(h.data(), x->mem.successes, n * sizeof(int), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; ++i) successes[i] = h[i];
-  HIP_TRY(hipMemcpy(promoted, x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(level_episodes, x->mem.level_episodes, n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h.data(), x->mem.frozen, n * sizeof(int), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; ++i) frozen[i] = h[i] ? 1 : 0;
-  return DQL_OK;
-}
-int dql_ensemble_get_episode_log(dql_ensemble* x, uint8_t* code, uint16_t* length, int32_t capacity, int32_t* n_episodes) {
-  CHECK_ENS(x);
-  if (!code || !length || !n_episodes) return fail(DQL_EINVAL, "dql_ensemble_get_episode_log: null array");
-  if (capacity != x->mem.log_cap || capacity < 1) return fail(DQL_EINVAL, "dql_ensemble_get_episode_log: capacity must be the (positive) log capacity the ensemble was created with");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t n = (size_t)x->n * (size_t)capacity;
-  HIP_TRY(hipMemcpy(code, x->mem.log_code, n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(length, x->mem.log_len, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(n_episodes, x->mem.log_n, (size_t)x->n * sizeof(int), hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-int dql_ensemble_get_state(dql_ensemble* x, double* reals, int32_t* ints) {
-  CHECK_ENS(x);
-  if (!reals || !ints) return fail(DQL_EINVAL, "dql_ensemble_get_state: null array");
-  HIP_TRY(hipSetDevice(x->device));
-  int rc = x->cfg.dtype == DQL_F32 ? ens_get_state_t<float>(x, reals) : ens_get_state_t<double>(x, reals);
-  if (rc) return rc;
-  const long long n = x->n;
-  std::vector<int4> h((size_t)n);
-  HIP_TRY(hipMemcpy(h.data(), x->si, (size_t)n * sizeof(int4), hipMemcpyDeviceToHost));
-  for (long long i = 0; i < n; ++i) {
-    ints[0 * n + i] = h[i].x; ints[1 * n + i] = h[i].y; ints[2 * n + i] = h[i].z & 0xffff; ints[3 * n + i] = (h[i].z >> 16) & 0xffff;
-    ints[4 * n + i] = h[i].w & 0xff; ints[5 * n + i] = (h[i].w >> 8) & 0xff; ints[6 * n + i] = (h[i].w >> 16) & 0xff;
-  }
-  return DQL_OK;
-}
-int dql_ensemble_index_faults(dql_ensemble* x, int64_t* n) {
-  CHECK_ENS(x);
-  if (!n) return fail(DQL_EINVAL, "null pointer");
-  HIP_TRY(hipSetDevice(x->device));
-  unsigned long long v = 0;
-  HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
-  *n = (int64_t)v;
-  return DQL_OK;
-}
-// the learners' tables are read where they live (the ensemble's device arrays are [L][DQL_N_CELLS] double already): k_score only reads them and touches nothing else of the ensemble
-int dql_ensemble_score(dql_ensemble* x, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env, uint64_t seed,
-                       int32_t max_steps, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null) {
-  CHECK_ENS(x);
-  int rc = check_config(eval_cfg); if (rc) return rc;
-  rc = score_check("dql_ensemble_score", count, envs_per_learner, episodes_per_env, max_steps, by_code, steps_sum, ep_code_or_null, ep_steps_or_null); if (rc) return rc;
-  if (first < 0 || first > x->n || count > x->n - first) return fail(DQL_EINVAL, "dql_ensemble_score: the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t off = (size_t)first * DQL_N_CELLS;
-  return score_run(eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, x->mem.qa + off, x->mem.qb + off, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
-}
-int dql_diag_ensemble_launches(dql_ensemble* x, int64_t* launches, int64_t* periods, int64_t* wave_periods) {
-  CHECK_ENS(x);
-  if (!launches || !periods || !wave_periods) return fail(DQL_EINVAL, "null pointer");
-  *launches = x->n_launches; *periods = x->launched_periods; *wave_periods = x->launched_wave_periods;
-  return DQL_OK;
-}
-int dql_diag_ensemble_last(dql_ensemble* x, double* run_ms) {
-  CHECK_ENS(x);
-  if (!run_ms) return fail(DQL_EINVAL, "null pointer");
-  if (x->last_ms < 0.0) return fail(DQL_ESTATE, "no dql_ensemble_run call has completed on this ensemble");
-  *run_ms = x->last_ms;
-  return DQL_OK;
-}
-
-// ---- resident agent ----
-struct dql_agent {
-  int device = 0;
-  double *qa = nullptr, *qb = nullptr, *count = nullptr;
-  hipStream_t stream = nullptr;
-  void* pin = nullptr; void* pin_dev = nullptr; size_t pin_bytes = 0;  // pinned + device-visible: arguments in, results out
-  // dql_agent_mirror_*: what the device tables hold, as the caller's arrays would have to look ([3][DQL_N_CELLS], pinned), and the answer
-  // the last update left for the next predict
-  double* shadow = nullptr; bool shadow_valid = false; int shadow_levels = 0;
-  int next_idx = -1, next_action = 0;
-  unsigned seq = 0;
-  void* post = nullptr; void* post_dev = nullptr;  // the mirror calls' own pinned page: [0] AgentOneOut, [64] predict's index, [128] its answer
-  // dql_agent_mirror_update_deferred: an update whose kernel is in flight and whose cell has not been patched into the caller's arrays yet
-  bool pending = false; double* p_q = nullptr; double* p_count = nullptr; int p_sa = 0, p_t = 0, p_ns = -1; unsigned p_seq = 0;
-};
-static int mirror_complete(dql_agent* a);
-static int agent_pin(dql_agent* a, size_t bytes) {
-  if (bytes <= a->pin_bytes) return DQL_OK;
-  if (a->pin) { HIP_TRY(hipStreamSynchronize(a->stream)); HIP_TRY(hipHostFree(a->pin)); a->pin = nullptr; a->pin_bytes = 0; }
-  bytes = (bytes + 4095) & ~(size_t)4095;
-  if (hipHostMalloc(&a->pin, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { a->pin = nullptr; return fail(DQL_ENOMEM, "hipHostMalloc(agent staging) failed"); }
-  memset(a->pin, 0, bytes);
-  HIP_TRY(hipHostGetDevicePointer(&a->pin_dev, a->pin, 0));
-  a->pin_bytes = bytes;
-  return DQL_OK;
-}
-#define CHECK_AGENT(a) do { if (!(a)) return fail(DQL_EINVAL, "null agent"); } while (0)
-int dql_agent_create(int device, dql_agent** out) {
-  if (!out) return fail(DQL_EINVAL, "null out pointer");
-  *out = nullptr;
-  OP_PROLOGUE(device)
-  dql_agent* a = new dql_agent();
-  a->device = device;
-  const size_t B = DQL_N_CELLS * sizeof(double);
-  int rc = DQL_OK;
-  do {
-    if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess) { rc = fail(DQL_EHIP, "hipStreamCreate failed"); break; }
-    if (hipMalloc((void**)&a->qa, B) != hipSuccess || hipMalloc((void**)&a->qb, B) != hipSuccess || hipMalloc((void**)&a->count, B) != hipSuccess) { rc = fail(DQL_ENOMEM, "hipMalloc failed"); break; }
-    if (hipMemsetAsync(a->qa, 0, B, a->stream) != hipSuccess || hipMemsetAsync(a->qb, 0, B, a->stream) != hipSuccess || hipMemsetAsync(a->count, 0, B, a->stream) != hipSuccess) { rc = fail(DQL_EHIP, "hipMemset failed"); break; }
-    rc = agent_pin(a, 4096);
-    if (rc) break;
-    if (hipHostMalloc(&a->post, 4096, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { a->post = nullptr; rc = fail(DQL_ENOMEM, "hipHostMalloc(agent results) failed"); break; }
-    memset(a->post, 0, 4096);
-    if (hipHostGetDevicePointer(&a->post_dev, a->post, 0) != hipSuccess) { rc = fail(DQL_EHIP, "hipHostGetDevicePointer failed"); break; }
-  } while (0);
-  if (rc) { const std::string why = g_err; dql_agent_destroy(a); return fail(rc, why); }
-  *out = a;
-  return DQL_OK;
-}
-int dql_agent_destroy(dql_agent* a) {
-  if (!a) return DQL_OK;
-  (void)hipSetDevice(a->device);
-  if (a->stream) (void)hipStreamSynchronize(a->stream);
-  if (a->qa) (void)hipFree(a->qa);
-  if (a->qb) (void)hipFree(a->qb);
-  if (a->count) (void)hipFree(a->count);
-  if (a->pin) (void)hipHostFree(a->pin);
-  if (a->shadow) (void)hipHostFree(a->shadow);
-  if (a->post) (void)hipHostFree(a->post);
-  if (a->stream) (void)hipStreamDestroy(a->stream);
-  delete a;
-  return DQL_OK;
-}
-int dql_agent_set_tables(dql_agent* a, const double* qa, const double* qb, const double* count) {
-  CHECK_AGENT(a);
-  { int rc = mirror_complete(a); if (rc) return rc; }
-  HIP_TRY(hipSetDevice(a->device));
-  const size_t B = DQL_N_CELLS * sizeof(double);
-  if (qa) HIP_TRY(hipMemcpyAsync(a->qa, qa, B, hipMemcpyHostToDevice, a->stream));
-  if (qb) HIP_TRY(hipMemcpyAsync(a->qb, qb, B, hipMemcpyHostToDevice, a->stream));
-  if (count) HIP_TRY(hipMemcpyAsync(a->count, count, B, hipMemcpyHostToDevice, a->stream));
-  HIP_TRY(hipStreamSynchronize(a->stream));  // the caller's arrays may change right after return
-  a->shadow_valid = false; a->next_idx = -1;
-  return DQL_OK;
-}
-int dql_agent_get_tables(dql_agent* a, double* qa, double* qb, double* count) {
-  CHECK_AGENT(a);
-  { int rc = mirror_complete(a); if (rc) return rc; }
-  HIP_TRY(hipSetDevice(a->device));
-  const size_t B = DQL_N_CELLS * sizeof(double);
-  if (qa) HIP_TRY(hipMemcpyAsync(qa, a->qa, B, hipMemcpyDeviceToHost, a->stream));
-  if (qb) HIP_TRY(hipMemcpyAsync(qb, a->qb, B, hipMemcpyDeviceToHost, a->stream));
-  if (count) HIP_TRY(hipMemcpyAsync(count, a->count, B, hipMemcpyDeviceToHost, a->stream));
-  HIP_TRY(hipStreamSynchronize(a->stream));
-  return DQL_OK;
-}
-int dql_agent_predict_resident(dql_agent* a, const int32_t* idx, int64_t n, uint8_t* action_out) {
-  CHECK_AGENT(a);
-  { int rc = mirror_complete(a); if (rc) return rc; }
-  if (n < 0 || (n > 0 && (!idx || !action_out))) return fail(DQL_EINVAL, "null array");
-  if (n == 0) return DQL_OK;
-  for (int64_t i = 0; i < n; ++i) if (idx[i] < 0 || idx[i] >= DQL_N_STATES) return fail(DQL_EINVAL, "state index out of range");
-  HIP_TRY(hipSetDevice(a->device));
-  const size_t in_b = ((size_t)n * sizeof(int32_t) + 63) & ~(size_t)63;
-  { int rc = agent_pin(a, in_b + (size_t)n); if (rc) return rc; }
-  memcpy(a->pin, idx, (size_t)n * sizeof(int32_t));
-  hipLaunchKernelGGL(k_predict_resident, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, a->stream, (const double*)a->qa, (const double*)a->qb, (const int*)a->pin_dev, (long long)n,
-                     (uint8_t*)a->pin_dev + in_b);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(wait_stream(a->stream));
-  memcpy(action_out, (const char*)a->pin + in_b, (size_t)n);
-  return DQL_OK;
-}
-int dql_agent_update_resident(dql_agent* a, const int32_t* sa, const int32_t* ns, const double* alpha, double gamma, const double* reward, int64_t n,
-                              uint32_t quirks, const uint8_t* coin, const uint8_t* done, double* q_new, double* count_new, uint8_t* next_action) {
-  CHECK_AGENT(a);
-  { int rc = mirror_complete(a); if (rc) return rc; }
-  if (n < 0 || (n > 0 && (!sa || !ns || !alpha || !reward))) return fail(DQL_EINVAL, "null array");
-  if (n == 0) return DQL_OK;
-  if (!(quirks & DQL_Q_UPDATE_TABLE_A_ONLY) && !coin) return fail(DQL_EINVAL, "Double Q-learning (DQL_Q_UPDATE_TABLE_A_ONLY cleared) needs the caller's coin per transition");
-  if (!(quirks & DQL_Q_BOOTSTRAP_ON_POS_CHANGE) && !done) return fail(DQL_EINVAL, "bootstrapping on non-terminal transitions (DQL_Q_BOOTSTRAP_ON_POS_CHANGE cleared) needs the done flags");
-  for (int64_t i = 0; i < n; ++i) if (sa[i] < 0 || sa[i] >= DQL_N_CELLS || ns[i] < 0 || ns[i] >= DQL_N_STATES) return fail(DQL_EINVAL, "index out of range");
-  HIP_TRY(hipSetDevice(a->device));
-  const size_t in_b = (size_t)n * sizeof(AgentUpdIn);
-  { int rc = agent_pin(a, in_b + (size_t)n * sizeof(AgentUpdOut) + sizeof(AgentUpdTail)); if (rc) return rc; }
-  AgentUpdIn* in = (AgentUpdIn*)a->pin;
-  for (int64_t i = 0; i < n; ++i) in[i] = AgentUpdIn{sa[i], ns[i], alpha[i], reward[i], coin ? (int)coin[i] : 0, done ? (int)done[i] : 0};
-  hipLaunchKernelGGL(k_update_resident, dim3(1), dim3(64), 0, a->stream, a->qa, a->qb, a->count, (const AgentUpdIn*)a->pin_dev, (AgentUpdOut*)((char*)a->pin_dev + in_b), (long long)n, gamma, quirks);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(wait_stream(a->stream));
-  const AgentUpdOut* o = (const AgentUpdOut*)((const char*)a->pin + in_b);
-  for (int64_t i = 0; i < n; ++i) { if (q_new) q_new[i] = o[i].q_new; if (count_new) count_new[i] = o[i].count_new; }
-  if (next_action) *next_action = (uint8_t)((const AgentUpdTail*)(o + n))->next_action;
-  a->shadow_valid = false; a->next_idx = -1;
-  return DQL_OK;
-}
-// ---- host-mirrored single transitions ----
-// brings the device tables up to the caller's arrays; what changed is found by comparing with the shadow of the last upload
-// a deferred update's second half: wait for its kernel (it has usually finished while the caller was busy), patch the one cell and its visit counter into
-// the caller's arrays and into the shadow, keep the kernel's answer for the next predict
-static int mirror_complete(dql_agent* a) {
-  if (!a->pending) return DQL_OK;
-  a->pending = false;
-  HIP_TRY(hipSetDevice(a->device));
-  AgentOneOut* o = (AgentOneOut*)a->post;
-  if (!wait_posted(&o->seq, a->p_seq)) HIP_TRY(wait_stream(a->stream));
-  a->p_q[a->p_sa] = o->q_new; a->p_count[a->p_sa] = o->count_new;
-  a->shadow[(size_t)a->p_t * DQL_N_CELLS + a->p_sa] = o->q_new; a->shadow[(size_t)2 * DQL_N_CELLS + a->p_sa] = o->count_new;
-  a->next_idx = a->p_ns; a->next_action = o->next_action;
-  return DQL_OK;
-}
-static int mirror_refresh(dql_agent* a, const double* qa, const double* qb, const double* count, int32_t n_levels) {
-  if (!qa || !qb || !count) return fail(DQL_EINVAL, "null table");
-  { int rc = mirror_complete(a); if (rc) return rc; }
-  if (n_levels < 1 || n_levels > DQL_MAX_LEVELS) return fail(DQL_EINVAL, "n_levels must be in 1..5");
-  HIP_TRY(hipSetDevice(a->device));
-  const size_t B = DQL_N_CELLS * sizeof(double), used = (size_t)n_levels * DQL_STATES_PER_LEVEL * 3 * sizeof(double);
-  if (!a->shadow) {
-    if (hipHostMalloc((void**)&a->shadow, 3 * B, hipHostMallocDefault) != hipSuccess) { a->shadow = nullptr; return fail(DQL_ENOMEM, "hipHostMalloc(table shadow) failed"); }
-    a->shadow_valid = false;
-  }
-  const double* host[3] = {qa, qb, count};
-  double* dev[3] = {a->qa, a->qb, a->count};
-  bool sent = false;
-  for (int t = 0; t < 3; ++t) {
-    double* sh = a->shadow + (size_t)t * DQL_N_CELLS;
-    if (a->shadow_valid && a->shadow_levels == n_levels && memcmp(sh, host[t], used) == 0) continue;
-    memcpy(sh, host[t], used);
-    memset((char*)sh + used, 0, B - used);
-    HIP_TRY(hipMemcpyAsync(dev[t], sh, B, hipMemcpyHostToDevice, a->stream));
-    sent = true;
-  }
-  if (sent) { HIP_TRY(hipStreamSynchronize(a->stream)); a->next_idx = -1; }  // the shadow may be patched right after return
-  a->shadow_valid = true; a->shadow_levels = n_levels;
-  return DQL_OK;
-}
-int dql_agent_mirror_predict(dql_agent* a, const double* qa, const double* qb, const double* count, int32_t n_levels, int32_t idx, uint8_t* action_out) {
-  CHECK_AGENT(a);
-  if (!action_out) return fail(DQL_EINVAL, "null action_out");
-  { int rc = mirror_refresh(a, qa, qb, count, n_levels); if (rc) return rc; }
-  if (idx < 0 || idx >= n_levels * DQL_STATES_PER_LEVEL) return fail(DQL_EINVAL, "state index outside the table's levels");
-  if (idx == a->next_idx) { *action_out = (uint8_t)a->next_action; return DQL_OK; }  // the last update's kernel answered this on the tables as they are
-  *(int*)((char*)a->post + 64) = idx;
-  hipLaunchKernelGGL(k_predict_resident, dim3(1), dim3(64), 0, a->stream, (const double*)a->qa, (const double*)a->qb, (const int*)((char*)a->post_dev + 64), 1ll, (uint8_t*)a->post_dev + 128);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(wait_stream(a->stream));
-  *action_out = *((const uint8_t*)a->post + 128);
-  return DQL_OK;
-}
-int dql_agent_mirror_update_deferred(dql_agent* a, double* qa, double* qb, double* count, int32_t n_levels, int32_t sa, int32_t ns, double alpha, double gamma,
-                                     double reward, uint32_t quirks, int32_t coin, int32_t done) {
-  CHECK_AGENT(a);
-  { int rc = mirror_refresh(a, qa, qb, count, n_levels); if (rc) return rc; }
-  if (sa < 0 || sa >= n_levels * DQL_STATES_PER_LEVEL * 3 || ns < 0 || ns >= n_levels * DQL_STATES_PER_LEVEL) return fail(DQL_EINVAL, "index outside the table's levels");
-  const unsigned seq = ++a->seq;
-  hipLaunchKernelGGL(k_update_one, dim3(1), dim3(64), 0, a->stream, a->qa, a->qb, a->count, (int)sa, (int)ns, alpha, gamma, reward, quirks, (int)coin, (int)done, (AgentOneOut*)a->post_dev, seq);
-  HIP_TRY(hipGetLastError());
-  const int t = (!(quirks & DQL_Q_UPDATE_TABLE_A_ONLY) && coin) ? 1 : 0;  // the table agent_update_one writes
-  a->pending = true; a->p_q = t ? qb : qa; a->p_count = count; a->p_sa = sa; a->p_t = t; a->p_ns = ns; a->p_seq = seq;
-  a->next_idx = -1;  // (the device tables are ahead of the caller's arrays until mirror_complete)
-  return DQL_OK;
-}
-int dql_agent_mirror_complete(dql_agent* a) {
-  CHECK_AGENT(a);
-  return mirror_complete(a);
-}
-int dql_agent_mirror_update(dql_agent* a, double* qa, double* qb, double* count, int32_t n_levels, int32_t sa, int32_t ns, double alpha, double gamma,
-                            double reward, uint32_t quirks, int32_t coin, int32_t done) {
-  const int rc = dql_agent_mirror_update_deferred(a, qa, qb, count, n_levels, sa, ns, alpha, gamma, reward, quirks, coin, done);
-  return rc ? rc : mirror_complete(a);
-}
-
-int dql_agent_transfer(int device, double* qa, double* qb, int32_t k, double ratio) {
-  if (!qa || !qb) return fail(DQL_EINVAL, "null array");
-  if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "curriculum step must be in 0..4");
-  OP_PROLOGUE(device)
-  DevBuf a, b;
-  const size_t B = DQL_N_CELLS * sizeof(double);
-  UP(a, qa, B); UP(b, qb, B);
-  hipLaunchKernelGGL(k_transfer, dim3((DQL_CELLS_PER_LEVEL + 255) / 256), dim3(256), 0, 0, (double*)a.p, (double*)b.p, (int)k, (int)((k - 1 + DQL_MAX_LEVELS) % DQL_MAX_LEVELS), ratio);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(qa, a.p, B, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(qb, b.p, B, hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_agent_predict(int device, const double* qa, const double* qb, const int32_t* idx, int64_t n, uint8_t* action_out) {
-  if (n < 0 || !qa || !qb || (n > 0 && (!idx || !action_out))) return fail(DQL_EINVAL, "null array");
-  if (n == 0) return DQL_OK;
-  for (int64_t i = 0; i < n; ++i) if (idx[i] < 0 || idx[i] >= DQL_N_STATES) return fail(DQL_EINVAL, "state index out of range");
-  OP_PROLOGUE(device)
-  DevBuf a, b, ix, o;
-  UP(a, qa, DQL_N_CELLS * sizeof(double)); UP(b, qb, DQL_N_CELLS * sizeof(double)); UP(ix, idx, (size_t)n * sizeof(int));
-  if (o.alloc((size_t)n)) return fail(DQL_ENOMEM, "hipMalloc failed");
-  hipLaunchKernelGGL(k_predict, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const double*)a.p, (const double*)b.p, (const int*)ix.p, (long long)n, (uint8_t*)o.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(action_out, o.p, (size_t)n, hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-int dql_agent_update(int device, double* qa, double* qb, double* count, const int32_t* sa, const int32_t* ns, const double* alpha, double gamma,
-                     const double* reward, int64_t n, uint32_t quirks, const uint8_t* coin, const uint8_t* done) {
-  if (n < 0 || !qa || !qb || !count || (n > 0 && (!sa || !ns || !alpha || !reward))) return fail(DQL_EINVAL, "null array");
-  if (n == 0) return DQL_OK;
-  if (!(quirks & DQL_Q_UPDATE_TABLE_A_ONLY) && !coin) return fail(DQL_EINVAL, "Double Q-learning (DQL_Q_UPDATE_TABLE_A_ONLY cleared) needs the caller's coin per transition");
-  if (!(quirks & DQL_Q_BOOTSTRAP_ON_POS_CHANGE) && !done) return fail(DQL_EINVAL, "bootstrapping on non-terminal transitions (DQL_Q_BOOTSTRAP_ON_POS_CHANGE cleared) needs the done flags");
-  for (int64_t i = 0; i < n; ++i) if (sa[i] < 0 || sa[i] >= DQL_N_CELLS || ns[i] < 0 || ns[i] >= DQL_N_STATES) return fail(DQL_EINVAL, "index out of range");
-  OP_PROLOGUE(device)
-  DevBuf a, b, c, s, t, al, rw, cn, dn;
-  const size_t B = DQL_N_CELLS * sizeof(double);
-  UP(a, qa, B); UP(b, qb, B); UP(c, count, B); UP(s, sa, (size_t)n * sizeof(int)); UP(t, ns, (size_t)n * sizeof(int)); UP(al, alpha, (size_t)n * sizeof(double)); UP(rw, reward, (size_t)n * sizeof(double));
-  if (coin) UP(cn, coin, (size_t)n);
-  if (done) UP(dn, done, (size_t)n);
-  hipLaunchKernelGGL(k_update_seq, dim3(1), dim3(64), 0, 0, (double*)a.p, (double*)b.p, (double*)c.p, (const int*)s.p, (const int*)t.p, (const double*)al.p, gamma, (const double*)rw.p, (long long)n, quirks,
-                     (const uint8_t*)cn.p, (const uint8_t*)dn.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(qa, a.p, B, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(qb, b.p, B, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(count, c.p, B, hipMemcpyDeviceToHost));
-  return DQL_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// RCCL communicator.  librccl.so is half a gigabyte: it is loaded with dlopen the first time a
-// communicator is asked for, so a single-GPU process never maps it.
-// ---------------------------------------------------------------------------------------------
-struct RcclApi {
-  void* handle = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-  const char* (*GetErrorString)(ncclResult_t) = nullptr;
-};
-static RcclApi g_rccl;
-static int load_rccl() {
-  if (g_rccl.handle) return DQL_OK;
-  const char* env = getenv("DQL_RCCL_PATH");
-  const char* names[] = {env, "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-  void* h = nullptr;
-  std::string tried;
-  for (const char* nm : names) {
-    if (!nm || !*nm) continue;
-    h = dlopen(nm, RTLD_NOW | RTLD_LOCAL);
-    if (h) break;
-    tried += std::string(" ") + nm + " (" + dlerror() + ")";
-  }
-  if (!h) return fail(DQL_ERCCL, "cannot load librccl:" + tried);
-#define DQL_SYM(field, name) do { *(void**)(&g_rccl.field) = dlsym(h, name); if (!g_rccl.field) { dlclose(h); return fail(DQL_ERCCL, std::string("librccl lacks ") + name); } } while (0)
-  DQL_SYM(GetUniqueId, "ncclGetUniqueId"); DQL_SYM(CommInitRank, "ncclCommInitRank"); DQL_SYM(CommDestroy, "ncclCommDestroy");
-  DQL_SYM(AllReduce, "ncclAllReduce"); DQL_SYM(AllGather, "ncclAllGather"); DQL_SYM(GetErrorString, "ncclGetErrorString");
-#undef DQL_SYM
-  g_rccl.handle = h;
-  return DQL_OK;
-}
-#define NCCL_TRY(expr)                                                                                         \
-  do {                                                                                                         \
-    ncclResult_t _r = (expr);                                                                                  \
-    if (_r != ncclSuccess) return fail(DQL_ERCCL, std::string(#expr) + ": " + g_rccl.GetErrorString(_r));      \
-  } while (0)
-
-struct dql_comm {
-  int device = 0, rank = 0, world = 1;
-  ncclComm_t nccl = nullptr;
-  hipStream_t stream = nullptr;
-  void* stage = nullptr;  // device staging of the host-buffer collectives
-  size_t stage_bytes = 0;
-};
-static int comm_stage(dql_comm* c, size_t bytes) {
-  if (bytes <= c->stage_bytes) return DQL_OK;
-  if (c->stage) { HIP_TRY(hipFree(c->stage)); c->stage = nullptr; c->stage_bytes = 0; }
-  bytes = (bytes + 4095) & ~(size_t)4095;
-  if (hipMalloc(&c->stage, bytes) != hipSuccess) { c->stage = nullptr; return fail(DQL_ENOMEM, "hipMalloc(comm staging) failed"); }
-  c->stage_bytes = bytes;
-  return DQL_OK;
-}
-#define CHECK_COMM(c) do { if (!(c)) return fail(DQL_EINVAL, "null communicator"); } while (0)
-
-extern "C" {
-
-int dql_comm_unique_id(uint8_t* id_out) {
-  if (!id_out) return fail(DQL_EINVAL, "null pointer");
-  static_assert(sizeof(ncclUniqueId) == DQL_COMM_ID_BYTES, "DQL_COMM_ID_BYTES must be the size of ncclUniqueId");
-  { int rc = load_rccl(); if (rc) return rc; }
-  ncclUniqueId id;
-  NCCL_TRY(g_rccl.GetUniqueId(&id));
-  memcpy(id_out, &id, sizeof(id));
-  return DQL_OK;
-}
-int dql_comm_create(int device, int32_t rank, int32_t world, const uint8_t* id, dql_comm** out) {
-  if (!out) return fail(DQL_EINVAL, "null out pointer");
-  *out = nullptr;
-  if (!id) return fail(DQL_EINVAL, "null unique id");
-  if (world < 1 || rank < 0 || rank >= world) return fail(DQL_EINVAL, "rank must be in 0 .. world-1");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return fail(DQL_EHIP, "no HIP device visible (there is no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(DQL_EINVAL, "device index out of range");
-  { int rc = load_rccl(); if (rc) return rc; }
-  HIP_TRY(hipSetDevice(device));
-  dql_comm* c = new dql_comm();
-  c->device = device; c->rank = rank; c->world = world;
-  ncclUniqueId uid;
-  memcpy(&uid, id, sizeof(uid));
-  int rc = DQL_OK;
-  do {
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { rc = fail(DQL_EHIP, "hipStreamCreate failed"); break; }
-    // RCCL 2.27 prints a version banner on STDOUT from ncclCommInitRank (no switch for it): a launcher that reads one result line
-    // from rank 0's stdout must not find it there.  Park fd 1 on stderr for the duration of the call (one host thread per
-    // process talks to this library while a communicator is created).
-    fflush(stdout);
-    const int saved_out = dup(1);
-    if (saved_out >= 0) (void)dup2(2, 1);
-    const ncclResult_t r = g_rccl.CommInitRank(&c->nccl, world, uid, rank);
-    fflush(stdout);
-    if (saved_out >= 0) { (void)dup2(saved_out, 1); (void)close(saved_out); }
-    if (r != ncclSuccess) { c->nccl = nullptr; rc = fail(DQL_ERCCL, std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r)); break; }
-  } while (0);
-  if (rc) { const std::string why = g_err; dql_comm_destroy(c); return fail(rc, why); }
-  *out = c;
-  return DQL_OK;
-}
-int dql_comm_destroy(dql_comm* c) {
-  if (!c) return DQL_OK;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->nccl) (void)g_rccl.CommDestroy(c->nccl);
-  if (c->stage) (void)hipFree(c->stage);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-  return DQL_OK;
-}
-int dql_comm_info(dql_comm* c, int32_t* rank, int32_t* world, int32_t* device) {
-  CHECK_COMM(c);
-  if (rank) *rank = c->rank;
-  if (world) *world = c->world;
-  if (device) *device = c->device;
-  return DQL_OK;
-}
-static int comm_allreduce(dql_comm* c, void* inout, int64_t n, ncclDataType_t dt, int32_t op) {
-  CHECK_COMM(c);
-  if (n < 0 || (n > 0 && !inout)) return fail(DQL_EINVAL, "null array");
-  if (op != DQL_OP_SUM && op != DQL_OP_MAX) return fail(DQL_EINVAL, "op must be DQL_OP_SUM or DQL_OP_MAX");
-  if (n == 0) return DQL_OK;
-  const size_t bytes = (size_t)n * 8;
-  HIP_TRY(hipSetDevice(c->device));
-  { int rc = comm_stage(c, bytes); if (rc) return rc; }
-  HIP_TRY(hipMemcpyAsync(c->stage, inout, bytes, hipMemcpyHostToDevice, c->stream));
-  NCCL_TRY(g_rccl.AllReduce(c->stage, c->stage, (size_t)n, dt, op == DQL_OP_SUM ? ncclSum : ncclMax, c->nccl, c->stream));
-  HIP_TRY(hipMemcpyAsync(inout, c->stage, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return DQL_OK;
-}
-int dql_comm_allreduce_f64(dql_comm* c, double* inout, int64_t n, int32_t op) { return comm_allreduce(c, inout, n, ncclDouble, op); }
-int dql_comm_allreduce_i64(dql_comm* c, int64_t* inout, int64_t n, int32_t op) { return comm_allreduce(c, inout, n, ncclInt64, op); }
-int dql_comm_allgather_u64(dql_comm* c, const uint64_t* in, int64_t n, uint64_t* out) {
-  CHECK_COMM(c);
-  if (n < 0 || (n > 0 && (!in || !out))) return fail(DQL_EINVAL, "null array");
-  if (n == 0) return DQL_OK;
-  const size_t bytes = (size_t)n * 8;
-  HIP_TRY(hipSetDevice(c->device));
-  { int rc = comm_stage(c, bytes * (size_t)(c->world + 1)); if (rc) return rc; }
-  char* send = (char*)c->stage;
-  char* recv = send + bytes;
-  HIP_TRY(hipMemcpyAsync(send, in, bytes, hipMemcpyHostToDevice, c->stream));
-  NCCL_TRY(g_rccl.AllGather(send, recv, (size_t)n, ncclUint64, c->nccl, c->stream));
-  HIP_TRY(hipMemcpyAsync(out, recv, bytes * (size_t)c->world, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return DQL_OK;
-}
-int dql_comm_barrier(dql_comm* c) {
-  int64_t one = 1;
-  return dql_comm_allreduce_i64(c, &one, 1, DQL_OP_SUM);
-}
-
-int dql_attach_comm(dql_ctx* x, dql_comm* c) {
-  POP_NEVER(x, "dql_attach_comm");
-  CHECK_CTX(x);
-  if (c && c->device != x->device) return fail(DQL_EINVAL, "communicator and context live on different devices");
-  x->comm = c;
-  return DQL_OK;
-}
-int dql_allreduce_window(dql_ctx* x) {
-  POP_NEVER(x, "dql_allreduce_window");
-  CHECK_CTX(x);
-  if (!x->comm) return fail(DQL_ESTATE, "dql_allreduce_window: no communicator attached (dql_attach_comm)");
-  if (!x->windowed) return fail(DQL_ESTATE, "dql_allreduce_window needs windowed accumulation (dql_set_windowed)");
-  HIP_TRY(hipSetDevice(x->device));
-  { int rc = flush_pending(x); if (rc) return rc; }  // the last launch's accumulators enter the window here
-  if (x->kernel_timer) {
-    if (x->sev.size() & 1) { (void)hipEventDestroy(x->sev.back()); x->sev.pop_back(); }  // an exchange that was never folded
-    hipEvent_t e0 = nullptr;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventRecord(e0, x->stream)); x->sev.push_back(e0);
-  }
-  NCCL_TRY(g_rccl.AllReduce(x->window, x->window, (size_t)DQL_ACC_LEN, ncclInt64, ncclSum, x->comm->nccl, x->stream));
-  return DQL_OK;
-}
-
-// ---- one-shot peer-to-peer exchange ----
-int dql_p2p_create(dql_ctx* x, int32_t rank, int32_t world, uint8_t* handle_out) {
-  POP_NEVER(x, "dql_p2p_create");
-  CHECK_CTX(x);
-  if (!handle_out) return fail(DQL_EINVAL, "null pointer");
-  static_assert(sizeof(hipIpcMemHandle_t) == DQL_P2P_HANDLE_BYTES, "DQL_P2P_HANDLE_BYTES must be the size of hipIpcMemHandle_t");
-  if (world < 1 || world > DQL_P2P_MAX_RANKS || rank < 0 || rank >= world) return fail(DQL_EINVAL, "rank must be in 0 .. world-1, world at most DQL_P2P_MAX_RANKS");
-  if (x->p2p_buf) return fail(DQL_ESTATE, "dql_p2p_create: this context already has an exchange buffer");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t words = (size_t)2 * world * DQL_ACC_LEN + (size_t)2 * DQL_P2P_MAX_RANKS;
-  if (hipExtMallocWithFlags((void**)&x->p2p_buf, words * sizeof(unsigned long long), hipDeviceMallocUncached) != hipSuccess) { x->p2p_buf = nullptr; return fail(DQL_ENOMEM, "hipExtMallocWithFlags(exchange buffer) failed"); }
-  if (hipMalloc((void**)&x->p2p_status, 2 * sizeof(unsigned long long)) != hipSuccess) { x->p2p_status = nullptr; return fail(DQL_ENOMEM, "hipMalloc failed"); }
-  HIP_TRY(hipMemsetAsync(x->p2p_buf, 0, words * sizeof(unsigned long long), x->stream));
-  HIP_TRY(hipMemsetAsync(x->p2p_status, 0, 2 * sizeof(unsigned long long), x->stream));
-  HIP_TRY(hipStreamSynchronize(x->stream));
-  hipIpcMemHandle_t h;
-  {
-    const hipError_t e = hipIpcGetMemHandle(&h, x->p2p_buf);
-    if (e != hipSuccess) return fail(DQL_EHIP, std::string("hipIpcGetMemHandle: ") + hipGetErrorString(e) + " (ranks sharing one GPU need HSA_ENABLE_IPC_MODE_LEGACY=0 in the environment before the first HIP call)");
-  }
-  memcpy(handle_out, &h, sizeof(h));
-  x->p2p_rank = rank; x->p2p_world = world; x->p2p_seq = 0;
-  x->p2p_peer[rank] = x->p2p_buf;
-  return DQL_OK;
-}
-int dql_p2p_connect(dql_ctx* x, const uint8_t* all_handles) {
-  POP_NEVER(x, "dql_p2p_connect");
-  CHECK_CTX(x);
-  if (!all_handles) return fail(DQL_EINVAL, "null pointer");
-  if (!x->p2p_buf) return fail(DQL_ESTATE, "dql_p2p_connect: call dql_p2p_create first");
-  HIP_TRY(hipSetDevice(x->device));
-  for (int r = 0; r < x->p2p_world; ++r) {
-    if (r == x->p2p_rank || x->p2p_opened[r] || x->p2p_peer[r]) continue;  // itself, mapped already, or connected by pointer (same process)
-    hipIpcMemHandle_t h;
-    memcpy(&h, all_handles + (size_t)r * DQL_P2P_HANDLE_BYTES, sizeof(h));
-    void* ptr = nullptr;
-    const hipError_t e = hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess);
-    if (e != hipSuccess) return fail(DQL_EHIP, std::string("hipIpcOpenMemHandle(rank ") + std::to_string(r) + "): " + hipGetErrorString(e));
-    x->p2p_peer[r] = (unsigned long long*)ptr; x->p2p_opened[r] = true;
-  }
-  return DQL_OK;
-}
-int dql_p2p_connect_local(dql_ctx* x, dql_ctx* const* peers) {
-  POP_NEVER(x, "dql_p2p_connect_local");
-  CHECK_CTX(x);
-  if (!peers) return fail(DQL_EINVAL, "null pointer");
-  if (!x->p2p_buf) return fail(DQL_ESTATE, "dql_p2p_connect_local: call dql_p2p_create first");
-  HIP_TRY(hipSetDevice(x->device));
-  for (int r = 0; r < x->p2p_world; ++r) {
-    dql_ctx* pr = peers[r];
-    if (!pr || r == x->p2p_rank) continue;
-    if (!pr->p2p_buf || pr->p2p_rank != r || pr->p2p_world != x->p2p_world) return fail(DQL_EINVAL, "dql_p2p_connect_local: peers[r] must be the context that called dql_p2p_create(rank r, same world)");
-    if (pr->device != x->device) {
-      const hipError_t e = hipDeviceEnablePeerAccess(pr->device, 0);
-      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return fail(DQL_EHIP, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
-      (void)hipGetLastError();
-    }
-    x->p2p_peer[r] = pr->p2p_buf;
-  }
-  return DQL_OK;
-}
-static int p2p_ready(dql_ctx* x, const char* who) {
-  if (!x->p2p_buf) return fail(DQL_ESTATE, std::string(who) + ": no exchange buffer (dql_p2p_create / dql_p2p_connect)");
-  if (!x->windowed) return fail(DQL_ESTATE, std::string(who) + " needs windowed accumulation (dql_set_windowed)");
-  for (int r = 0; r < x->p2p_world; ++r) if (!x->p2p_peer[r]) return fail(DQL_ESTATE, std::string(who) + ": not connected to every peer (dql_p2p_connect / dql_p2p_connect_local)");
-  return DQL_OK;
-}
-static P2PPushArgs p2p_args(dql_ctx* x, unsigned long long seq) {
-  P2PPushArgs a;
-  a.window = x->window; a.rank = x->p2p_rank; a.world = x->p2p_world; a.parity = (int)(seq & 1);
-  for (int r = 0; r < DQL_P2P_MAX_RANKS; ++r) a.peer[r] = r < x->p2p_world ? x->p2p_peer[r] : nullptr;
-  return a;
-}
-int dql_p2p_push_window(dql_ctx* x) {
-  POP_NEVER(x, "dql_p2p_push_window");
-  CHECK_CTX(x);
-  { int rc = p2p_ready(x, "dql_p2p_push_window"); if (rc) return rc; }
-  if (x->p2p_pushed) return fail(DQL_ESTATE, "dql_p2p_push_window: the previous push has not been waited for (dql_p2p_wait_window)");
-  HIP_TRY(hipSetDevice(x->device));
-  { int rc = flush_pending(x); if (rc) return rc; }  // the last launch's accumulators enter the window here
-  if (x->kernel_timer) {
-    if (x->sev.size() & 1) { (void)hipEventDestroy(x->sev.back()); x->sev.pop_back(); }
-    hipEvent_t e0 = nullptr;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventRecord(e0, x->stream)); x->sev.push_back(e0);
-  }
-  const unsigned long long seq = ++x->p2p_seq;
-  const P2PPushArgs a = p2p_args(x, seq);
-  const int B = 256, G = (DQL_ACC_LEN + B - 1) / B;
-  hipLaunchKernelGGL(k_p2p_push, dim3(G), dim3(B), 0, x->stream, a);
-  hipLaunchKernelGGL(k_p2p_signal, dim3(1), dim3(64), 0, x->stream, a, seq);
-  HIP_TRY(hipGetLastError());
-  x->p2p_pushed = true;
-  return DQL_OK;
-}
-int dql_p2p_wait_window(dql_ctx* x) {
-  POP_NEVER(x, "dql_p2p_wait_window");
-  CHECK_CTX(x);
-  { int rc = p2p_ready(x, "dql_p2p_wait_window"); if (rc) return rc; }
-  if (!x->p2p_pushed) return fail(DQL_ESTATE, "dql_p2p_wait_window: nothing pushed (dql_p2p_push_window)");
-  HIP_TRY(hipSetDevice(x->device));
-  const unsigned long long seq = x->p2p_seq;
-  const int parity = (int)(seq & 1);
-  const int B = 256, G = (DQL_ACC_LEN + B - 1) / B;
-  hipLaunchKernelGGL(k_p2p_wait, dim3(1), dim3(64), 0, x->stream, (const unsigned long long*)x->p2p_buf, x->p2p_world, parity, seq, x->p2p_status, x->p2p_spin_limit);
-  hipLaunchKernelGGL(k_p2p_sum, dim3(G), dim3(B), 0, x->stream, x->p2p_buf, x->window, x->p2p_world, parity, seq, (const unsigned long long*)x->p2p_status);
-  HIP_TRY(hipGetLastError());
-  x->p2p_pushed = false;
-  return DQL_OK;
-}
-int dql_p2p_exchange_window(dql_ctx* x) {
-  POP_NEVER(x, "dql_p2p_exchange_window");
-  const int rc = dql_p2p_push_window(x);
-  return rc ? rc : dql_p2p_wait_window(x);
-}
-int dql_p2p_status(dql_ctx* x, int32_t* failed_seq) {
-  CHECK_CTX(x);
-  if (!failed_seq) return fail(DQL_EINVAL, "null pointer");
-  HIP_TRY(hipSetDevice(x->device));
-  unsigned long long v = 0;
-  { int rc = p2p_failed_seq(x, &v); if (rc) return rc; }
-  *failed_seq = (int32_t)(v > 0x7fffffffull ? 0x7fffffffull : v);
-  return DQL_OK;
-}
-
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
@@ -3826,22 +1923,6 @@ static int pop_agent(dql_ctx* x, int32_t k, dql_ctx** g) {
   if (k < 0 || k >= x->n_agents) return fail(DQL_EINVAL, "agent index out of range");
   HIP_TRY(hipSetDevice(x->device));
   *g = x->agents[k];
-  return DQL_OK;
-}
-template <typename T> static int launch_init_agent(dql_ctx* x, int k) {
-  // k_init over agent k's E envs alone: the state arrays keep the population's stride (n = K E), the base moves to the agent's first env, and the grid
-  // is exactly E threads (E is a multiple of 512), so that no thread reaches past the agent's slice
-  const dql_ctx* g = x->agents[k];
-  InitArgs<T> a;
-  a.c = make_simk<T>(x->cfg);
-  a.sr = (Quad<T>*)x->sr + k * x->pop_E; a.si = x->si + k * x->pop_E; a.n = x->n; a.seed = g->seed; a.env_id_offset = 0;
-  const dql_config& c = x->cfg;
-  a.hover = std::sqrt((T)(c.mass * c.gravity / (4.0 * c.k_f)));
-  a.vz_integ = (T)(c.mass * c.gravity / c.pid_vz[1]);
-  a.r_lo = (T)c.mp_r_lo; a.r_hi = (T)c.mp_r_hi; a.t_lo = (T)c.mp_t_lo; a.t_hi = (T)c.mp_t_hi;
-  const int B = 256;
-  hipLaunchKernelGGL(k_init<T>, dim3((unsigned)(x->pop_E / B)), dim3(B), 0, x->stream, a);
-  HIP_TRY(hipGetLastError());
   return DQL_OK;
 }
 static int pop_create_impl(dql_ctx* x, const uint64_t* seeds) {
@@ -3857,13 +1938,16 @@ static int pop_create_impl(dql_ctx* x, const uint64_t* seeds) {
     const double a0 = x->cfg.alpha_min;
     rc = dql_set_alpha_table(g, &a0, 1);
     if (rc) return rc;
-    rc = x->dtype == DQL_F32 ? launch_init_agent<float>(x, k) : launch_init_agent<double>(x, k);
+    // k_init over agent k's E envs alone: the state arrays keep the population's stride (n = K E), the base moves to the agent's first env, and the grid
+    // is exactly E threads (E is a multiple of 512), so that no thread reaches past the agent's slice
+    void* sr_k = (char*)x->sr + (size_t)k * (size_t)x->pop_E * 4 * x->real_size;
+    rc = by_dtype(x->dtype, [&](auto t) { return launch_init<decltype(t)>(x->cfg, sr_k, x->si + k * x->pop_E, x->n, x->pop_E, g->seed, 0, x->stream); });
     if (rc) return rc;
   }
   const size_t ring = (size_t)DQL_POP_RING * DQL_MAX_AGENTS * sizeof(PopAgentDesc);
   if (hipHostMalloc((void**)&x->pop_h, ring, hipHostMallocDefault) != hipSuccess) { x->pop_h = nullptr; return fail(DQL_ENOMEM, "hipHostMalloc(launch descriptors) failed"); }
-  if (hipMalloc((void**)&x->pop_d, ring) != hipSuccess) { x->pop_d = nullptr; return fail(DQL_ENOMEM, "hipMalloc(launch descriptors) failed"); }
-  if (hipMalloc((void**)&x->pop_faults, (size_t)x->n_agents * sizeof(unsigned long long)) != hipSuccess) { x->pop_faults = nullptr; return fail(DQL_ENOMEM, "hipMalloc(fault counters) failed"); }
+  if (x->dev.alloc((void**)&x->pop_d, ring) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc(launch descriptors) failed");
+  if (x->dev.alloc((void**)&x->pop_faults, (size_t)x->n_agents * sizeof(unsigned long long)) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc(fault counters) failed");
   HIP_TRY(hipMemsetAsync(x->pop_faults, 0, (size_t)x->n_agents * sizeof(unsigned long long), x->stream));
   for (int s = 0; s < DQL_POP_RING; ++s) HIP_TRY(hipEventCreateWithFlags(&x->pop_ev[s], hipEventDisableTiming));
   HIP_TRY(hipStreamSynchronize(x->stream));
@@ -3922,7 +2006,7 @@ int dql_pop_set_curriculum(dql_ctx* x, int32_t agent, int32_t level) {
   rc = flush_pending(g); if (rc) return rc;
   rc = publish_master(g); if (rc) return rc;
   g->cfg.working_curriculum_step = level;
-  rc = upload_mdpk(g); if (rc) return rc;
+  rc = upload_mdpk(g->cfg, g->mdpk, g->stream); if (rc) return rc;
   hipLaunchKernelGGL(k_mark_reset, dim3((unsigned)((x->pop_E + 255) / 256)), dim3(256), 0, x->stream, x->si + agent * x->pop_E, (const uint8_t*)nullptr, (long long)x->pop_E);
   HIP_TRY(hipGetLastError());
   return DQL_OK;
@@ -3946,3 +2030,9 @@ int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
 }
 
 }  // extern "C"
+
+#include "dql_ops.inc"
+#include "dql_greedy.inc"
+#include "dql_ensemble.inc"
+#include "dql_agent.inc"
+#include "dql_comm.inc"

@@ -1,7 +1,7 @@
 // dql_learner.hpp — one sequential Double-Q learner per lane: one env, its own three tables, the reference's update after every agent period
 // (DESIGN.md section 12).
 //
-// learner_periods is the per-lane body of k_learn (dql_hip.hip) and of its host emulation (tests/host_emu/learner_emu.cpp).  Learner l owns env l of a
+// learner_periods is the per-lane body of k_learn (dql_ensemble.inc) and of its host emulation (tests/host_emu/learner_emu.cpp).  Learner l owns env l of a
 // context made with dql_create(cfg, device, L, seed, 0) — the state arrays have that context's layout and are initialised by the same k_init — and the
 // slices [l][DQL_N_CELLS] of Q_table_a, Q_table_b and state_action_counter.  A launch loads the env once, flies n_periods agent periods with
 // agent_period<TICK, XMODE> in MODE_TRAIN (per-lane eps threshold) and applies DoubleQLearningAgent.update (pkg/double_q_learning.py:91-146) to the

@@ -1,6 +1,6 @@
 // dql_rollout.hpp — one env's first greedy episode, from reset to termination, in one lane.
 //
-// rollout_episode is the per-lane body of k_rollout (dql_hip.hip) and of its host emulation (tests/host_emu/rollout_emu.cpp): the env is
+// rollout_episode is the per-lane body of k_rollout (dql_greedy.inc) and of its host emulation (tests/host_emu/rollout_emu.cpp): the env is
 // built in registers as k_init builds it, flown with agent_period<TICK, XMODE> in MODE_EVAL for agent periods 0 .. max_steps (period 0 is the
 // reset period of a fresh context) and left at the first period that reports `done`.  What it writes is what a context driven one period at a
 // time shows through dql_get_sim_state / dql_get_sim_ints after that period, bit for bit.

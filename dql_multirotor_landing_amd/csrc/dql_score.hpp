@@ -1,6 +1,6 @@
 // dql_score.hpp — greedy scoring of a table set: one env per lane flies episode after episode, the wave counts how they end.
 //
-// score_episodes is the per-lane body of k_score (dql_hip.hip) and of its host emulation (tests/host_emu/score_emu.cpp).  The env is built in registers by
+// score_episodes is the per-lane body of k_score (dql_greedy.inc) and of its host emulation (tests/host_emu/score_emu.cpp).  The env is built in registers by
 // rollout_init_env and flown with agent_period<TICK, XMODE> in MODE_EVAL for agent periods 0 .. max_steps, as rollout_episode does; but a lane does not leave
 // at its first `done`: it notes the episode (terminal code, step_count & 0xffff), agent_period sends it through reset in the next period — exactly as a
 // context driven one period at a time does — and it stops after `episodes` finished episodes.  There are no records of state and no trace: what comes out

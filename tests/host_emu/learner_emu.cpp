@@ -1,7 +1,7 @@
 // learner_emu.cpp — launches of the sequential-learner kernel k_learn, emulated on the CPU from the real device source (dql_learner.hpp's
 // learner_periods on top of dql_device.hpp).
 //
-// For every learner the driver does what one lane of k_learn (dql_hip.hip) does: the launch's constants as the host side makes them (make_simk /
+// For every learner the driver does what one lane of k_learn (dql_ensemble.inc) does: the launch's constants as the host side makes them (make_simk /
 // make_mdpk / fill_schedule from the ensemble's period index), the env state arrays initialised as k_init initialises them, the learner's own table
 // slices, learner_periods<TICK_PLAIN, X_ONLY>.  A lane runs alone: __ballot(p) is p (host_shim.h).  The job lists the lengths of the consecutive runs
 // (launches); state, tables and counters live in arrays exactly as long as the ABI says, so the sanitized build sees any access beyond them.

@@ -1,7 +1,7 @@
 // rollout_emu.cpp — one launch of the roll-out kernel k_rollout, emulated on the CPU from the real device source (dql_rollout.hpp's
 // rollout_episode on top of dql_device.hpp).
 //
-// For every env of every table set the driver does what one lane of k_rollout (dql_hip.hip) does: the launch's constants as the host side
+// For every env of every table set the driver does what one lane of k_rollout (dql_greedy.inc) does: the launch's constants as the host side
 // makes them (make_simk / make_mdpk / make_rollout_init / fill_schedule over max_steps + 1 periods), the lane's table set, its env id within
 // the set, rollout_episode<TICK_PLAIN, X_ONLY | X_TWO>.  A lane runs alone: __ballot(p) is p (host_shim.h).  Every table read goes through
 // TabRef, which stops on an element outside [0, N_CELLS) with exit status 3; the schedule arrays are exactly max_steps + 1 long and the

@@ -1,7 +1,7 @@
 // score_emu.cpp — one launch of the scoring kernel k_score, emulated on the CPU from the real device source (dql_score.hpp's score_episodes on
 // top of dql_rollout.hpp and dql_device.hpp).
 //
-// For every env of every table set the driver does what one lane of k_score (dql_hip.hip) does: the launch's constants as the host side makes
+// For every env of every table set the driver does what one lane of k_score (dql_greedy.inc) does: the launch's constants as the host side makes
 // them (make_simk / make_mdpk / make_rollout_init / fill_schedule over max_steps + 1 periods), the lane's table set, its env id within the set,
 // score_episodes<TICK_PLAIN, X_ONLY | X_TWO>; then what the kernel does with the wave's tally: it is added to the table set's row.  A lane runs
 // alone: __ballot(p) is p (host_shim.h), so a "wave" is one lane and its tally that lane's own.  Every table read goes through TabRef, which stops

@@ -87,7 +87,9 @@ def test_kernel_sources_have_no_build_switches():
     never an alternative form of the shipped arithmetic or schedule.  Every macro an #if / #ifdef / #ifndef / #elif tests is listed here."""
     allowed = {"DQL_MARK", "DQL_WAVE_CLOCK", "DQL_PHASE_CLOCK", "DQL_H", "__cplusplus"}
     tested = set()
-    for f in ("dql_multirotor_landing_amd/csrc/dql_hip.hip", "dql_multirotor_landing_amd/csrc/dql_device.hpp", "include/dql.h"):
+    csrc = "dql_multirotor_landing_amd/csrc/"
+    fragments = [csrc + f"dql_{name}.inc" for name in ("ops", "greedy", "ensemble", "agent", "comm")]  # the subsystem files dql_hip.hip includes
+    for f in (csrc + "dql_hip.hip", csrc + "dql_device.hpp", "include/dql.h", *fragments):
         for kind, cond in re.findall(r"^\s*#\s*(ifdef|ifndef|if|elif)\b(.*)$", (ROOT / f).read_text(), re.M):
             cond = cond.split("//")[0].split("/*")[0]
             tested |= set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}

@@ -129,6 +129,31 @@ def test_mode_on_with_nobody_frozen_equals_the_plain_ensemble():
     ac.assert_equal(got, want, "curriculum mode off again")
 
 
+def test_replaced_schedules_leave_no_trace():
+    """`set_schedules` twice (tables of other lengths) and `set_level_schedules(0, ...)` twice (other tables), then eight periods in curriculum mode across an
+    advance point: tables, counters and levels are those of an ensemble that was only ever given the final schedules, bit for bit.  One wave, float32: what is
+    exercised is the host side — a replaced device table is freed when it is replaced, the last one when the ensemble is destroyed (`flown` closes it)."""
+    n, seed = 64, 5
+    first = dict(alpha_table=np.linspace(0.5, 0.05, 3), eps=np.full(2, 0.3), window=5, min_successes=2, max_episodes=9)
+    final = dict(alpha_table=np.linspace(0.9, 0.05, 11), eps=np.linspace(0.8, 0.1, 9), window=4, min_successes=3, max_episodes=6)
+    lv_first = dict(eps=np.full(3, 0.9), window=7, min_successes=2, max_episodes=4)
+    lv_final = dict(eps=np.linspace(0.7, 0.2, 6), window=4, min_successes=3, max_episodes=6)
+
+    def fly(ens):
+        ens.set_level_schedules(0, **lv_final)
+        ens.set_level_schedules(1, **lv_final)
+        ens.set_curriculum(1, 4)
+        return flown(ens, 8)
+
+    want, j, _ = fly(SequentialEnsemble(ac.level0(), n, seed=seed, log_capacity=4, **final))
+    assert j == 8 and want["decisions"].min() >= 1
+    ens = SequentialEnsemble(ac.level0(), n, seed=seed, log_capacity=4, **first)
+    ens.set_schedules(**final)
+    ens.set_level_schedules(0, **lv_first)
+    got, _, _ = fly(ens)
+    ac.assert_equal(got, want, "schedules replaced before the run against the final schedules alone")
+
+
 def test_last_level_2_is_never_exceeded(main):
     got, _, unfinished = flown(ac.case_ensemble(last_level=2), CASE["periods"])
     print("levels", np.bincount(got["level"], minlength=5).tolist(), "unfinished", unfinished)

@@ -20,6 +20,7 @@ def normalise(text):
     text = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", text)
     text = re.sub(r"\.Ltmp\d+", ".Ltmp", text)
     text = re.sub(r"(Header|header|Loop|Child Loop)( *=? *)BB\d+_", r"\1\2BB_", text)  # the same function number inside the assembler's loop comments
+    text = re.sub(r"^(\.LBB_\d+:) +;", r"\1 ;", text, flags=re.M)  # a label's comment is padded to a column: one space more or less when the function number changes width (.LBB8_3 / .LBB10_3)
     return text
 
 
