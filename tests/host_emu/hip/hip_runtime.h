@@ -1,5 +1,5 @@
-// Stand-in for the HIP runtime header when dql_device.hpp is compiled for the host (step_emu.cpp).  The device names the header uses
-// (__device__, int4, __ballot, the amdgcn builtins) come from host_shim.h, which step_emu.cpp includes first.  The header's inline-asm
+// Stand-in for the HIP runtime header when dql_device.hpp is compiled for the host (the drivers of this directory).  The device names the header
+// uses (__device__, int4, __ballot, the amdgcn builtins) come from host_shim.h, which every driver includes first.  The header's inline-asm
 // macros, defined just before it includes this file, are redefined here with their portable meaning: a register pin or a block marker
 // is nothing the host needs (a compiler barrier at most), the opaque SGPR -> VGPR copy is a copy, and each three-address fma is the fma
 // it spells (v_fmamk_f32 / v_fma_f32: d = x * k + y).

@@ -1,8 +1,9 @@
 // host_shim.h — the device names dql_device.hpp uses, defined for a plain host C++ build (x86-64, clang++) of that header.
 //
-// The emulator (step_emu.cpp) runs the step kernel's device code on the CPU, one env at a time, so that a sanitizer and explicit
-// index checks can watch it.  Every definition here either restates an instruction exactly or is licensed by a check that the
-// device code's own comments name:
+// The five emulators (step_emu, rollout_emu, score_emu, learner_emu, advance_emu) run the kernels' device code on the CPU, one lane at a
+// time, so that a sanitizer and explicit index checks can watch it; each includes this file first, then the device headers, then
+// emu_common.h (what the drivers share: job and result files, the launch prologue, the state packing, the checked table).  Every
+// definition here either restates an instruction exactly or is licensed by a check that the device code's own comments name:
 //   __ballot(p)                     one lane per wave: p ? 1 : 0.  Each ballot in the header guards a wave-uniform fast path that is
 //                                   documented as bit-identical to the per-lane path (det_atan2, kalman1d, the footprint tests), so
 //                                   running it for single lanes tests those claims.

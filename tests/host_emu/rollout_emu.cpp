@@ -5,7 +5,8 @@
 // makes them (make_simk / make_mdpk / make_rollout_init / fill_schedule over max_steps + 1 periods), the lane's table set, its env id within
 // the set, rollout_episode<TICK_PLAIN, X_ONLY | X_TWO>.  A lane runs alone: __ballot(p) is p (host_shim.h).  Every table read goes through
 // TabRef, which stops on an element outside [0, N_CELLS) with exit status 3; the schedule arrays are exactly max_steps + 1 long and the
-// output arrays exactly as long as the ABI says, so the sanitized build sees any access beyond them.
+// output arrays exactly as long as the ABI says, so the sanitized build sees any access beyond them.  The job and result files, the launch prologue
+// (emu::Launch) and TabRef are emu_common.h's, shared with the other four drivers.
 //
 //   rollout_emu JOB OUT   run the launch described by JOB (see read_job; tests/test_rollout_host_emulation.py writes it), write OUT
 #include "host_shim.h"
@@ -18,6 +19,7 @@
 #include "dql_device.hpp"
 #include "dql_host_consts.hpp"
 #include "dql_rollout.hpp"
+#include "emu_common.h"
 
 using namespace dql;
 
@@ -25,13 +27,7 @@ namespace {
 
 long long g_env = -1;
 
-struct TabRef {
-  const double* p;
-  double operator[](long long k) const {
-    if (k < 0 || k >= DQL_N_CELLS) { std::fprintf(stderr, "INDEX VIOLATION: acting-table element %lld outside [0, N_CELLS) at output column %lld\n", k, g_env); std::exit(3); }
-    return p[k];
-  }
-};
+void table_violation(long long k) { emu::index_violation(k, "output column", g_env); }
 
 struct Job {
   int dtype, xmode, n_tables, max_steps, trace_envs;
@@ -41,26 +37,19 @@ struct Job {
   std::vector<double> qa, qb;  // [n_tables][N_CELLS]
 };
 
-template <typename V> void read_into(FILE* f, V* p, size_t n) {
-  if (n && std::fread(p, sizeof(V), n, f) != n) { std::fprintf(stderr, "short job file\n"); std::exit(2); }
-}
-
 Job read_job(const char* path) {
-  FILE* f = std::fopen(path, "rb");
-  if (!f) { std::perror(path); std::exit(2); }
+  emu::JobFile f(path);
   Job j;
   int32_t hdr[8];  // cfg size, dtype, xmode, n_tables, max_steps, trace_envs, 0, 0
   int64_t ll[2];   // envs per table set, seed
-  read_into(f, hdr, 8); read_into(f, ll, 2);
-  if (hdr[0] != (int32_t)sizeof(dql_config)) { std::fprintf(stderr, "dql_config size %d != %d\n", hdr[0], (int)sizeof(dql_config)); std::exit(2); }
-  read_into(f, &j.cfg, 1);
+  f.read(hdr, 8); f.read(ll, 2);
+  f.read_config(j.cfg, hdr[0]);
   j.dtype = hdr[1]; j.xmode = hdr[2]; j.n_tables = hdr[3]; j.max_steps = hdr[4]; j.trace_envs = hdr[5];
   j.n = ll[0]; j.seed = (unsigned long long)ll[1];
   if (j.n < 1 || j.n_tables < 1 || j.n_tables > DQL_ROLLOUT_MAX_TABLES || j.max_steps < 1 || j.max_steps > DQL_ROLLOUT_MAX_STEPS || j.trace_envs < 0 || j.trace_envs > 64 ||
-      j.trace_envs > j.n) { std::fprintf(stderr, "bad job\n"); std::exit(2); }
+      j.trace_envs > j.n) emu::bad_job();
   j.qa.resize((size_t)j.n_tables * DQL_N_CELLS); j.qb.resize(j.qa.size());
-  read_into(f, j.qa.data(), j.qa.size()); read_into(f, j.qb.data(), j.qb.size());
-  std::fclose(f);
+  f.read(j.qa); f.read(j.qb);
   return j;
 }
 
@@ -83,23 +72,15 @@ template <typename T, int XMODE> void launch(const Job& j, Result& out) {
   // k_rollout, per launch: the x-axis kernels see two_axis as the constant 0; the run-time constants move to VGPRs; the Philox round keys in VGPRs
   SimK<T> cl = c;
   if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
-  SimK<T> cfgk = cl;
-  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
-  const TickConsts<TICK_PLAIN, T> tc(cfgk);
-  uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)j.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(j.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
+  const emu::Launch<T, TICK_PLAIN> lc(cl, j.seed);
   const MdpK<T> DQL_CONST_AS* mdp = (const MdpK<T> DQL_CONST_AS*)&mdpk;
   for (int k = 0; k < j.n_tables; ++k) {
-    const TabRef qa{j.qa.data() + (size_t)k * DQL_N_CELLS}, qb{j.qb.data() + (size_t)k * DQL_N_CELLS};
+    const emu::TabRef qa{j.qa.data() + (size_t)k * DQL_N_CELLS, table_violation}, qb{j.qb.data() + (size_t)k * DQL_N_CELLS, table_violation};
     for (long long i = 0; i < j.n; ++i) {
       const long long g = (long long)k * j.n + i;
       g_env = g;
       const bool first_wave = k == 0 && i < 64;
-      rollout_episode<TICK_PLAIN, XMODE>(cl, cfgk, tc, mdp, mdp_run, init, qa, qb, j.seed, (uint32_t)i, j.max_steps, mgr0.data(), sched.data(), kv, ro, g,
+      rollout_episode<TICK_PLAIN, XMODE>(cl, lc.cfgk, lc.tc, mdp, mdp_run, init, qa, qb, j.seed, (uint32_t)i, j.max_steps, mgr0.data(), sched.data(), lc.kv, ro, g,
                                          first_wave && j.trace_envs > 0, first_wave && i < j.trace_envs);
     }
   }
@@ -119,11 +100,7 @@ int main(int argc, char** argv) {
   const Job j = read_job(argv[1]);
   Result r;
   if (!dispatch(j, r)) { std::fprintf(stderr, "no such instance: dtype %d xmode %d for two_axis %d\n", j.dtype, j.xmode, j.cfg.two_axis); return 2; }
-  FILE* f = std::fopen(argv[2], "wb");
-  if (!f) { std::perror(argv[2]); return 2; }
-  std::fwrite(r.code.data(), sizeof(int32_t), r.code.size(), f);
-  std::fwrite(r.steps.data(), sizeof(int32_t), r.steps.size(), f);
-  std::fwrite(r.rec.data(), sizeof(double), r.rec.size(), f);
-  std::fwrite(r.trace.data(), sizeof(double), r.trace.size(), f);
-  return std::fclose(f) == 0 ? 0 : 2;
+  emu::ResultFile f(argv[2]);
+  f.put(r.code); f.put(r.steps); f.put(r.rec); f.put(r.trace);
+  return f.close();
 }

@@ -9,6 +9,8 @@
 // accumulator target is checked to lie in [0, 2 N_CELLS) AND to be the cell of the row the env left with the action it took, in the
 // table its coin picked.  A violation stops the run with exit status 3 and names the env, the period and the state.
 //
+// The job and result files, the launch prologue, the state packing and the checked table are emu_common.h's, shared with the other four drivers.
+//
 //   step_emu JOB OUT     run the launch described by JOB (see read_job; tests/test_step_host_emulation.py writes it), write OUT
 //   step_emu --admits JOB      print refm and lit_ok of JOB's config: may TICK_PACKED_LITM / TICK_LIT serve it (create_impl)
 //   step_emu --asan-selftest   read one element past a heap array (the sanitized build must report it)
@@ -21,6 +23,7 @@
 
 #include "dql_device.hpp"
 #include "dql_host_consts.hpp"
+#include "emu_common.h"
 
 using namespace dql;
 
@@ -38,14 +41,7 @@ Where g_where;
   std::exit(3);
 }
 
-// an acting table as agent_period's TabPtr: every element read is bounds-checked
-struct TabRef {
-  const double* p;
-  double operator[](long long k) const {
-    if (k < 0 || k >= DQL_N_CELLS) violation("acting-table element outside [0, N_CELLS)", k);
-    return p[k];
-  }
-};
+void table_violation(long long k) { violation("acting-table element outside [0, N_CELLS)", k); }
 
 struct Job {
   int dtype, tick, xmode, mode, n_periods;
@@ -59,27 +55,19 @@ struct Job {
   std::vector<uint8_t> actions;
 };
 
-template <typename V> void read_into(FILE* f, V* p, size_t n) {
-  if (n && std::fread(p, sizeof(V), n, f) != n) { std::fprintf(stderr, "short job file\n"); std::exit(2); }
-}
-
 Job read_job(const char* path) {
-  FILE* f = std::fopen(path, "rb");
-  if (!f) { std::perror(path); std::exit(2); }
+  emu::JobFile f(path);
   Job j;
   int32_t hdr[8];   // cfg size, dtype, tick, xmode, mode, n_periods, have_actions, 0
   int64_t ll[4];    // n, env_id_offset, step_index, seed
-  read_into(f, hdr, 8); read_into(f, ll, 4); read_into(f, &j.eps, 1);
-  if (hdr[0] != (int32_t)sizeof(dql_config)) { std::fprintf(stderr, "dql_config size %d != %d\n", hdr[0], (int)sizeof(dql_config)); std::exit(2); }
-  read_into(f, &j.cfg, 1);
+  f.read(hdr, 8); f.read(ll, 4); f.read(&j.eps, 1);
+  f.read_config(j.cfg, hdr[0]);
   j.dtype = hdr[1]; j.tick = hdr[2]; j.xmode = hdr[3]; j.mode = hdr[4]; j.n_periods = hdr[5];
   j.n = ll[0]; j.env_id_offset = ll[1]; j.step_index = ll[2]; j.seed = (unsigned long long)ll[3];
-  if (j.n < 1 || j.n_periods < 1 || j.n_periods > DQL_MAX_PERIODS) { std::fprintf(stderr, "bad job\n"); std::exit(2); }
+  if (j.n < 1 || j.n_periods < 1 || j.n_periods > DQL_MAX_PERIODS) emu::bad_job();
   j.reals.resize((size_t)NF_REAL * j.n); j.ints.resize((size_t)NF_INT * j.n); j.qa.resize(DQL_N_CELLS); j.qb.resize(DQL_N_CELLS);
-  read_into(f, j.reals.data(), j.reals.size()); read_into(f, j.ints.data(), j.ints.size());
-  read_into(f, j.qa.data(), j.qa.size()); read_into(f, j.qb.data(), j.qb.size());
-  if (hdr[6]) { j.actions.resize((size_t)j.n); read_into(f, j.actions.data(), j.actions.size()); }
-  std::fclose(f);
+  f.read(j.reals); f.read(j.ints); f.read(j.qa); f.read(j.qb);
+  if (hdr[6]) { j.actions.resize((size_t)j.n); f.read(j.actions); }
   return j;
 }
 
@@ -104,29 +92,14 @@ template <typename T, int TICK, int XMODE> void launch(const Job& j, Result& out
   fill_schedule(cfg, j.step_index, mgr0, sched);
   const unsigned eps_thr = eps_threshold(j.eps);
   // HBM images of the state (dql_set_sim_state / dql_set_sim_ints)
-  std::vector<Quad<T>> sr((size_t)NQ_REAL * n);
-  std::vector<int4> si((size_t)n);
-  for (int f = 0; f < NF_REAL; ++f) {
-    const int q = f / 4, k = f % 4;
-    for (long long i = 0; i < n; ++i) (&sr[(size_t)q * n + i].a)[k] = (T)j.reals[(size_t)f * n + i];
-  }
-  for (long long i = 0; i < n; ++i) {
-    const int32_t* g = j.ints.data();
-    si[i] = make_int4(g[0 * n + i], g[1 * n + i], (g[2 * n + i] & 0xffff) | (g[3 * n + i] << 16), (g[4 * n + i] & 0xff) | ((g[5 * n + i] & 0xff) << 8) | ((g[6 * n + i] & 0xff) << 16));
-  }
-  const TabRef qa{j.qa.data()}, qb{j.qb.data()};
+  std::vector<Quad<T>> sr;
+  std::vector<int4> si;
+  emu::pack_state(j.reals, j.ints, (size_t)n, sr, si);
+  const emu::TabRef qa{j.qa.data(), table_violation}, qb{j.qb.data(), table_violation};
   out.acc.assign(4 * (size_t)DQL_N_CELLS, 0ull);
-  // k_step, per launch: the x-axis kernels see two_axis as the constant 0; the run-time constants move to VGPRs; the tick constants in the layout's form
-  SimK<T> cfgk = c;
-  if constexpr (XMODE == X_ONLY) cfgk.two_axis = 0;
-  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);  // (BLOCK < 512: the instances this driver stands for)
-  const TickConsts<TICK, T> tc(cfgk);
-  uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4 && (TICK == TICK_LIT || TICK == TICK_PLAIN)) {
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)j.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(j.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
+  // k_step, per launch (emu::Launch): the x-axis kernels see two_axis as the constant 0; the run-time constants move to VGPRs (BLOCK < 512: the
+  // instances this driver stands for); the tick constants in the layout's form; the Philox round keys in VGPRs only for TICK_LIT / TICK_PLAIN
+  const emu::Launch<T, TICK> lc(XMODE == X_ONLY ? x_only_(c) : c, j.seed, sizeof(T) == 4 && (TICK == TICK_LIT || TICK == TICK_PLAIN));
   const MdpK<T> DQL_CONST_AS* mdp = (const MdpK<T> DQL_CONST_AS*)&mdpk;
   for (long long i = 0; i < n; ++i) {
     g_where = Where{i, -1, 0, 0, 0, 0};
@@ -142,8 +115,8 @@ template <typename T, int TICK, int XMODE> void launch(const Job& j, Result& out
         if (ax > 2 || ay > 2 || (ext >> 4) || (!c.two_axis && ay != 0 && ay != 2)) out.bad_actions += 1;
       }
       const int prev_idx = e.idx_x, prev_idy = e.idx_y;
-      const StepOut o = agent_period<TICK, XMODE>(cfgk, tc, mdp, mdp_run, e, qx, qa, qb, j.mode, eps_thr, ext, j.seed, (uint32_t)(j.env_id_offset + i),
-                                                  j.step_index + p, mgr0[p], sched[p], kv);
+      const StepOut o = agent_period<TICK, XMODE>(lc.cfgk, lc.tc, mdp, mdp_run, e, qx, qa, qb, j.mode, eps_thr, ext, j.seed, (uint32_t)(j.env_id_offset + i),
+                                                  j.step_index + p, mgr0[p], sched[p], lc.kv);
       // the accumulator targets: inside [0, 2 N_CELLS), and the cell of the row the env left with the action it took
       const int ax = e.action & 3, ay = (e.action >> 2) & 3;
       const struct { int cell; long long target; int prev, act; const char* what; } tgt[2] = {
@@ -165,16 +138,7 @@ template <typename T, int TICK, int XMODE> void launch(const Job& j, Result& out
     }
     store_env(e, sr.data(), si.data(), n, i, XMODE == X_ONLY ? x_only_(c) : c);
   }
-  out.reals.resize((size_t)NF_REAL * n); out.ints.resize((size_t)NF_INT * n);
-  for (int f = 0; f < NF_REAL; ++f) {
-    const int q = f / 4, k = f % 4;
-    for (long long i = 0; i < n; ++i) out.reals[(size_t)f * n + i] = (double)(&sr[(size_t)q * n + i].a)[k];
-  }
-  for (long long i = 0; i < n; ++i) {
-    const int4 h = si[i];
-    out.ints[0 * n + i] = h.x; out.ints[1 * n + i] = h.y; out.ints[2 * n + i] = h.z & 0xffff; out.ints[3 * n + i] = (h.z >> 16) & 0xffff;
-    out.ints[4 * n + i] = h.w & 0xff; out.ints[5 * n + i] = (h.w >> 8) & 0xff; out.ints[6 * n + i] = (h.w >> 16) & 0xff;
-  }
+  emu::unpack_state(sr.data(), si.data(), (size_t)n, out.reals, out.ints);
 }
 
 template <typename T, int TICK> bool dispatch_x(const Job& j, Result& r) {
@@ -220,12 +184,7 @@ int main(int argc, char** argv) {
   const Job j = read_job(argv[1]);
   Result r;
   if (!dispatch(j, r)) { std::fprintf(stderr, "no such instance: dtype %d tick %d xmode %d\n", j.dtype, j.tick, j.xmode); return 2; }
-  FILE* f = std::fopen(argv[2], "wb");
-  if (!f) { std::perror(argv[2]); return 2; }
-  std::fwrite(r.reals.data(), sizeof(double), r.reals.size(), f);
-  std::fwrite(r.ints.data(), sizeof(int32_t), r.ints.size(), f);
-  std::fwrite(r.acc.data(), sizeof(unsigned long long), r.acc.size(), f);
-  std::fwrite(r.stats, sizeof(unsigned long long), 12, f);
-  std::fwrite(&r.bad_actions, sizeof(unsigned long long), 1, f);
-  return std::fclose(f) == 0 ? 0 : 2;
+  emu::ResultFile f(argv[2]);
+  f.put(r.reals); f.put(r.ints); f.put(r.acc); f.put(r.stats, 12); f.put(&r.bad_actions, 1);
+  return f.close();
 }

@@ -2,13 +2,11 @@
 learner_periods, held `==` to the yardstick of tests/advance_checks.py (CPU only, no GPU).
 
 tests/host_emu/advance_emu.cpp compiles the real headers as host C++ and does what dql_ensemble_run does in curriculum mode: advance at the multiples of E,
-worklist, wave by wave.  It is a stand-alone program run as its own process, built twice: plain, and with ASan + UBSan (any report fails).  The cases are those
+worklist, wave by wave.  It is a stand-alone program run as its own process, built twice: plain, and with ASan + UBSan (any report fails); the builds, the
+child process and the reader of the learners' result are tests/host_emu_harness.py's, the level arrays and the period index are read here.  The cases are those
 of tests/test_gpu_ensemble_advance.py; the sanitized build flies the first 24 learners for 384 periods, and the 24 learners of the cases from trained tables
 (`advance_checks.TRAINED_CASE`, `TRAINED_CASE_PAPER`, `TRAINED_FROM_3`) whole."""
-import os
 import struct
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
@@ -18,29 +16,13 @@ from dql_multirotor_landing_amd.config import F32, F64, N_CELLS
 from dql_multirotor_landing_amd.ensemble import SequentialEnsemble
 
 import advance_checks as ac
-import ensemble_checks as ec
-from test_learner_host_emulation import CSRC, EMU, PLAIN_FLAGS, SAN_ENV, SAN_FLAGS, SAN_MARKERS, _clangxx
+import host_emu_harness as heh
 
 CASE = ac.CASE
 CELLS_PER_LEVEL = N_CELLS // 5
 SHORT = 384
 
-
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    out = tmp_path_factory.mktemp("advance_emu")
-    cxx = _clangxx()
-    common = ["-I", str(EMU), "-I", str(CSRC), "-Wno-pass-failed", str(EMU / "advance_emu.cpp")]
-    builds = {"plain": PLAIN_FLAGS, "san": SAN_FLAGS}
-
-    def build(kind):
-        exe = out / f"advance_emu_{kind}"
-        r = subprocess.run([cxx, *builds[kind], *common, "-o", str(exe)], capture_output=True, text=True)
-        assert r.returncode == 0, f"{kind} build of advance_emu failed:\n{r.stderr[-4000:]}"
-        return exe
-
-    with ThreadPoolExecutor(2) as ex:
-        return dict(zip(builds, ex.map(build, builds)))
+emu = heh.emu_fixture("advance_emu")
 
 
 def run_emu(exe, tmp, runs, n=None, dtype=F32, sanitized=False, **over):
@@ -57,38 +39,15 @@ def run_emu(exe, tmp, runs, n=None, dtype=F32, sanitized=False, **over):
         hdr += [len(s["eps"]), s["window"], s["min_successes"], s["max_episodes"]]
     hdr += [int(tables is not None)]
     hdr += [0] * (40 - len(hdr))
-    job, res = tmp / "advance_job.bin", tmp / "advance_res.bin"
-    job.write_bytes(struct.pack("<40i", *hdr) + struct.pack("<q", c["seed"]) + cb + np.asarray(ac.case_ratios(c), np.float64).tobytes() + alpha.tobytes()
-                    + b"".join(np.asarray(s["eps"], np.float64).tobytes() for s in sch)
-                    + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ())))
-    env = dict(os.environ, **SAN_ENV) if sanitized else None
-    r = subprocess.run([str(exe), str(job), str(res)], capture_output=True, text=True, env=env, timeout=1800)
-    assert r.returncode == 0, f"advance_emu ({'sanitized' if sanitized else 'plain'}) failed:\n{r.stderr[-6000:]}"
-    assert not any(m in r.stderr for m in SAN_MARKERS), f"sanitizer report:\n{r.stderr[-6000:]}"
-    b = res.read_bytes()
-    o = 0
-
-    def take(dt, shape):
-        nonlocal o
-        a = np.frombuffer(b, dt, int(np.prod(shape)), o).reshape(shape)
-        o += a.nbytes
-        return a
-
-    cap = c["log_capacity"]
-    out = {"qa": take(np.float64, (n, N_CELLS)), "qb": take(np.float64, (n, N_CELLS)), "count": take(np.float64, (n, N_CELLS)),
-           "decisions": take(np.int64, (n,)), "by_code": take(np.int64, (ec.N_CODES, n)), "episodes": take(np.int32, (n,)), "successes": take(np.int32, (n,)),
-           "level_episodes": take(np.int32, (n,)), "promotion_episode": take(np.int32, (n,)), "frozen": take(np.int32, (n,)), "log_n": take(np.int32, (n,)),
-           "log_code": take(np.uint8, (n, cap)), "log_len": take(np.uint16, (n, cap))}
-    reals, ints = take(np.float64, (64, n)), take(np.int32, (7, n))
-    faults = take(np.int64, (1,))
-    out.update({"level": take(np.int32, (n,)), "promoted_at": take(np.int32, (5, n)), "episodes_at": take(np.int32, (5, n)), "entered_period": take(np.int64, (5, n))})
-    j = int(take(np.int64, (1,))[0])
-    assert o == len(b)
-    assert faults[0] == 0, "a range check counted a fault"
+    job = (struct.pack("<40i", *hdr) + struct.pack("<q", c["seed"]) + cb + np.asarray(ac.case_ratios(c), np.float64).tobytes() + alpha.tobytes()
+           + b"".join(np.asarray(s["eps"], np.float64).tobytes() for s in sch)
+           + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ())))
+    r = heh.Reader(heh.run(exe, job, tmp, "advance", sanitized))
+    out = heh.learner_result(r, n, c["log_capacity"], cfg)
+    out.update({"level": r.take(np.int32, (n,)), "promoted_at": r.take(np.int32, (5, n)), "episodes_at": r.take(np.int32, (5, n)), "entered_period": r.take(np.int64, (5, n))})
+    j = int(r.take(np.int64, (1,))[0])
+    r.done()
     assert j == sum(runs)
-    ref = ec.Reference(cfg, 1, 0)
-    out.update({f: reals[k] for f, k in ref.ri.items()})
-    out.update({f: ints[k] for f, k in ref.ii.items()})
     return out
 
 

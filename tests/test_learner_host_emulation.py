@@ -2,57 +2,21 @@
 
 tests/host_emu/learner_emu.cpp compiles the real device headers as host C++ (the stand-in runtime header of step_emu.cpp) and flies every learner lane by
 lane, exactly as k_learn does, in two launches of 150 + 250 periods.  The yardstick is tests/ensemble_checks.py's `Reference`: the unchanged oracle stepped
-with external actions, `oracle.agent_predict` / `oracle.agent_update` on per-learner tables.  Built twice: plain, and with ASan + UBSan (any report fails)."""
-import os
-import shutil
+with external actions, `oracle.agent_predict` / `oracle.agent_update` on per-learner tables.  Built twice: plain, and with ASan + UBSan (any report fails); the builds, the child process
+and the reader of the learners' result (`learner_result`, shared with the advance module) are tests/host_emu_harness.py's."""
 import struct
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from dql_multirotor_landing_amd.config import F32, F64, N_CELLS, as_launched_config, training_config
+from dql_multirotor_landing_amd.config import F32, F64, as_launched_config, training_config
 
 import ensemble_checks as ec
+import host_emu_harness as heh
 
-ROOT = Path(__file__).resolve().parent.parent
-EMU = ROOT / "tests" / "host_emu"
-CSRC = ROOT / "dql_multirotor_landing_amd" / "csrc"
 L, SEED, RUNS, LOG_CAP = 3, 2024, (150, 250), 32
 
-PLAIN_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-mfma"]
-SAN_FLAGS = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off"]
-SAN_ENV = {"ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1"}
-SAN_MARKERS = ("runtime error:", "ERROR: AddressSanitizer", "ERROR: LeakSanitizer", "SUMMARY: ")
-
-
-def _clangxx():
-    rocm = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
-    for c in (rocm / "llvm" / "bin" / "clang++", rocm / "lib" / "llvm" / "bin" / "clang++"):
-        if c.exists():
-            return str(c)
-    c = shutil.which("clang++")
-    assert c, "the host emulation needs clang++ (ROCm's llvm/bin/clang++): dql_device.hpp uses clang vector extensions"
-    return c
-
-
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    out = tmp_path_factory.mktemp("learner_emu")
-    cxx = _clangxx()
-    common = ["-I", str(EMU), "-I", str(CSRC), "-Wno-pass-failed", str(EMU / "learner_emu.cpp")]
-    builds = {"plain": PLAIN_FLAGS, "san": SAN_FLAGS}
-
-    def build(kind):
-        exe = out / f"learner_emu_{kind}"
-        r = subprocess.run([cxx, *builds[kind], *common, "-o", str(exe)], capture_output=True, text=True)
-        assert r.returncode == 0, f"{kind} build of learner_emu failed:\n{r.stderr[-4000:]}"
-        return exe
-
-    with ThreadPoolExecutor(2) as ex:
-        return dict(zip(builds, ex.map(build, builds)))
+emu = heh.emu_fixture("learner_emu")
 
 
 def run_emu(exe, cfg, n, seed, runs, tmp, eps=ec.EPS_TABLE, window=100, min_successes=97, max_episodes=1 << 30, sanitized=False, log_capacity=LOG_CAP, alpha_tab=None, tables=None):
@@ -60,33 +24,10 @@ def run_emu(exe, cfg, n, seed, runs, tmp, eps=ec.EPS_TABLE, window=100, min_succ
     alpha = cfg.alpha_table() if alpha_tab is None else np.ascontiguousarray(alpha_tab, np.float64)
     r4 = list(runs) + [0] * (4 - len(runs))
     hdr = struct.pack("<16i", len(c), cfg.dtype, n, len(runs), *r4, len(alpha), len(eps), window, min_successes, max_episodes, log_capacity, int(tables is not None), 0) + struct.pack("<q", seed)
-    job, res = tmp / "learner_job.bin", tmp / "learner_res.bin"
-    job.write_bytes(hdr + c + alpha.tobytes() + np.asarray(eps, np.float64).tobytes() + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ())))
-    env = dict(os.environ, **SAN_ENV) if sanitized else None
-    r = subprocess.run([str(exe), str(job), str(res)], capture_output=True, text=True, env=env, timeout=1800)
-    assert r.returncode == 0, f"learner_emu ({'sanitized' if sanitized else 'plain'}) failed:\n{r.stderr[-6000:]}"
-    assert not any(m in r.stderr for m in SAN_MARKERS), f"sanitizer report:\n{r.stderr[-6000:]}"
-    b = res.read_bytes()
-    o = 0
-
-    def take(dtype, shape):
-        nonlocal o
-        cnt = int(np.prod(shape))
-        a = np.frombuffer(b, dtype, cnt, o).reshape(shape)
-        o += a.nbytes
-        return a
-
-    out = {"qa": take(np.float64, (n, N_CELLS)), "qb": take(np.float64, (n, N_CELLS)), "count": take(np.float64, (n, N_CELLS)),
-           "decisions": take(np.int64, (n,)), "by_code": take(np.int64, (ec.N_CODES, n)), "episodes": take(np.int32, (n,)), "successes": take(np.int32, (n,)),
-           "level_episodes": take(np.int32, (n,)), "promotion_episode": take(np.int32, (n,)), "frozen": take(np.int32, (n,)), "log_n": take(np.int32, (n,)),
-           "log_code": take(np.uint8, (n, log_capacity)), "log_len": take(np.uint16, (n, log_capacity))}
-    reals, ints = take(np.float64, (64, n)), take(np.int32, (7, n))
-    faults = take(np.int64, (1,))
-    assert o == len(b)
-    assert faults[0] == 0, "the bounds guard dropped an update"
-    ref = ec.Reference(cfg, 1, 0)
-    out.update({f: reals[k] for f, k in ref.ri.items()})
-    out.update({f: ints[k] for f, k in ref.ii.items()})
+    job = hdr + c + alpha.tobytes() + np.asarray(eps, np.float64).tobytes() + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ()))
+    r = heh.Reader(heh.run(exe, job, tmp, "learner", sanitized))
+    out = heh.learner_result(r, n, log_capacity, cfg)
+    r.done()
     return out
 
 

@@ -3,16 +3,12 @@
 tests/host_emu/rollout_emu.cpp compiles the real device headers as host C++ (the stand-in runtime header of step_emu.cpp) and flies every env's first
 greedy episode lane by lane, exactly as k_rollout does.  The yardstick is the unchanged oracle driven one period at a time — `Oracle.eval_steps(1)`
 repeated, the first FL_DONE of every env captured from `get_fields()` (tests/rollout_checks.py) —, which knows nothing of the roll-out: code, step count
-and every record field must agree in every bit.  Built twice: plain, and with ASan + UBSan (any report fails).
+and every record field must agree in every bit.  Built twice: plain, and with ASan + UBSan (any report fails); the builds, the child process and the
+result reader are tests/host_emu_harness.py's.
 
 Every case asserts on the ORACLE's result, before comparing, that it is not vacuous (several terminal codes, nothing unfinished — or, for the cut-off
 case, a real share of unfinished envs): a change of defaults cannot quietly turn these into one-code tests."""
-import os
-import shutil
 import struct
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -20,48 +16,14 @@ import pytest
 from dql_multirotor_landing_amd.config import F64
 from oracle.oracle import Oracle
 
+import host_emu_harness as heh
 import rollout_checks as rc
-
-ROOT = Path(__file__).resolve().parent.parent
-EMU = ROOT / "tests" / "host_emu"
-CSRC = ROOT / "dql_multirotor_landing_amd" / "csrc"
 
 X_TWO, X_ONLY = 0, 1  # dql_device.hpp
 N_REC, N_TRACE = len(rc.RECORD_FIELDS), len(rc.TRACE_FIELDS)
 N_ENVS, SEED, MAX_STEPS = 512, 123, 600
 
-PLAIN_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-mfma"]
-SAN_FLAGS = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off"]
-SAN_ENV = {"ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1"}
-SAN_MARKERS = ("runtime error:", "ERROR: AddressSanitizer", "ERROR: LeakSanitizer", "SUMMARY: ")
-
-
-def _clangxx():
-    rocm = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
-    for c in (rocm / "llvm" / "bin" / "clang++", rocm / "lib" / "llvm" / "bin" / "clang++"):
-        if c.exists():
-            return str(c)
-    c = shutil.which("clang++")
-    assert c, "the host emulation needs clang++ (ROCm's llvm/bin/clang++): dql_device.hpp uses clang vector extensions"
-    return c
-
-
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    """the two builds of tests/host_emu/rollout_emu.cpp: {"plain": path, "san": path}"""
-    out = tmp_path_factory.mktemp("rollout_emu")
-    cxx = _clangxx()
-    common = ["-I", str(EMU), "-I", str(CSRC), "-Wno-pass-failed", str(EMU / "rollout_emu.cpp")]
-    builds = {"plain": PLAIN_FLAGS, "san": SAN_FLAGS}
-
-    def build(kind):
-        exe = out / f"rollout_emu_{kind}"
-        r = subprocess.run([cxx, *builds[kind], *common, "-o", str(exe)], capture_output=True, text=True)
-        assert r.returncode == 0, f"{kind} build of rollout_emu failed:\n{r.stderr[-4000:]}"
-        return exe
-
-    with ThreadPoolExecutor(2) as ex:
-        return dict(zip(builds, ex.map(build, builds)))
+emu = heh.emu_fixture("rollout_emu")
 
 
 def run_emu(exe, cfg, tables, n, seed, max_steps, tmp, trace_envs=0, sanitized=False):
@@ -71,20 +33,10 @@ def run_emu(exe, cfg, tables, n, seed, max_steps, tmp, trace_envs=0, sanitized=F
     c = bytes(cfg.to_c())
     hdr = struct.pack("<8i", len(c), cfg.dtype, X_TWO if cfg.two_axis else X_ONLY, K, max_steps, trace_envs, 0, 0) + struct.pack("<2q", n, seed)
     qa = np.stack([np.ascontiguousarray(s[0], np.float64).ravel() for s in sets]); qb = np.stack([np.ascontiguousarray(s[1], np.float64).ravel() for s in sets])
-    job, res = tmp / "rollout_job.bin", tmp / "rollout_res.bin"
-    job.write_bytes(hdr + c + qa.tobytes() + qb.tobytes())
-    env = dict(os.environ, **SAN_ENV) if sanitized else None
-    r = subprocess.run([str(exe), str(job), str(res)], capture_output=True, text=True, env=env, timeout=1800)
-    assert r.returncode == 0, f"rollout_emu ({'sanitized' if sanitized else 'plain'}) failed:\n{r.stderr[-6000:]}"
-    assert not any(m in r.stderr for m in SAN_MARKERS), f"sanitizer report:\n{r.stderr[-6000:]}"
-    b = res.read_bytes()
-    nt = K * n
-    o = 0
-    code = np.frombuffer(b, np.int32, nt, o).reshape(K, n); o += 4 * nt
-    steps = np.frombuffer(b, np.int32, nt, o).reshape(K, n); o += 4 * nt
-    rec = np.frombuffer(b, np.float64, N_REC * nt, o).reshape(N_REC, K, n); o += 8 * N_REC * nt
-    trace = np.frombuffer(b, np.float64, (max_steps + 1) * N_TRACE * trace_envs, o).reshape(max_steps + 1, N_TRACE, trace_envs) if trace_envs else None
-    assert o + 8 * (max_steps + 1) * N_TRACE * trace_envs == len(b)
+    r = heh.Reader(heh.run(exe, hdr + c + qa.tobytes() + qb.tobytes(), tmp, "rollout", sanitized))
+    code, steps, rec = r.take(np.int32, (K, n)), r.take(np.int32, (K, n)), r.take(np.float64, (N_REC, K, n))
+    trace = r.take(np.float64, (max_steps + 1, N_TRACE, trace_envs)) if trace_envs else None
+    r.done()
     out = {"code": code, "steps": steps, "trace": trace}
     out.update({f: rec[k] for k, f in enumerate(rc.RECORD_FIELDS)})
     return out

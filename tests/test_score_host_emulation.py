@@ -3,27 +3,19 @@
 tests/host_emu/score_emu.cpp compiles the real device headers as host C++ and flies every env episode after episode, lane by lane, exactly as k_score
 does, adding each lane's tally to its table set's row.  The yardstick is the unchanged oracle driven one period at a time (tests/score_checks.py:
 `Oracle.eval_steps(1)` repeated, every FL_DONE of every env noted), which knows nothing of the scoring: the per-episode log, by_code and steps_sum must be
-equal.  Built twice: plain, and with ASan + UBSan (any report fails).
+equal.  Built twice: plain, and with ASan + UBSan (any report fails); the builds, the child process and the result reader are tests/host_emu_harness.py's.
 
 Every case asserts on the ORACLE's result, before comparing, that it is not vacuous."""
-import os
-import shutil
 import struct
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from oracle.oracle import Oracle
 
+import host_emu_harness as heh
 import rollout_checks as rc
 import score_checks as sc
-
-ROOT = Path(__file__).resolve().parent.parent
-EMU = ROOT / "tests" / "host_emu"
-CSRC = ROOT / "dql_multirotor_landing_amd" / "csrc"
 
 N_ENVS, SEED, EPISODES = 64, 123, 3
 MAX_STEPS = 900      # three episodes of every env of every case end before it (asserted on the oracle)
@@ -31,38 +23,7 @@ CASE_IDS = ("simulation-f64", "training4-f32")
 N_COLS = sc.N_CODES + 1
 X_TWO, X_ONLY = 0, 1  # dql_device.hpp
 
-PLAIN_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-mfma"]
-SAN_FLAGS = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off"]
-SAN_ENV = {"ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1"}
-SAN_MARKERS = ("runtime error:", "ERROR: AddressSanitizer", "ERROR: LeakSanitizer", "SUMMARY: ")
-
-
-def _clangxx():
-    rocm = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
-    for c in (rocm / "llvm" / "bin" / "clang++", rocm / "lib" / "llvm" / "bin" / "clang++"):
-        if c.exists():
-            return str(c)
-    c = shutil.which("clang++")
-    assert c, "the host emulation needs clang++ (ROCm's llvm/bin/clang++): dql_device.hpp uses clang vector extensions"
-    return c
-
-
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    """the two builds of tests/host_emu/score_emu.cpp: {"plain": path, "san": path}"""
-    out = tmp_path_factory.mktemp("score_emu")
-    cxx = _clangxx()
-    common = ["-I", str(EMU), "-I", str(CSRC), "-Wno-pass-failed", str(EMU / "score_emu.cpp")]
-    builds = {"plain": PLAIN_FLAGS, "san": SAN_FLAGS}
-
-    def build(kind):
-        exe = out / f"score_emu_{kind}"
-        r = subprocess.run([cxx, *builds[kind], *common, "-o", str(exe)], capture_output=True, text=True)
-        assert r.returncode == 0, f"{kind} build of score_emu failed:\n{r.stderr[-4000:]}"
-        return exe
-
-    with ThreadPoolExecutor(2) as ex:
-        return dict(zip(builds, ex.map(build, builds)))
+emu = heh.emu_fixture("score_emu")
 
 
 def run_emu(exe, cfg, sets, n, seed, max_steps, episodes, tmp, log=True, sanitized=False):
@@ -71,22 +32,11 @@ def run_emu(exe, cfg, sets, n, seed, max_steps, episodes, tmp, log=True, sanitiz
     c = bytes(cfg.to_c())
     hdr = struct.pack("<8i", len(c), cfg.dtype, X_TWO if cfg.two_axis else X_ONLY, K, max_steps, episodes, 1 if log else 0, 0) + struct.pack("<2q", n, seed)
     qa = np.stack([np.ascontiguousarray(s[0], np.float64).ravel() for s in sets]); qb = np.stack([np.ascontiguousarray(s[1], np.float64).ravel() for s in sets])
-    job, res = tmp / "score_job.bin", tmp / "score_res.bin"
-    job.write_bytes(hdr + c + qa.tobytes() + qb.tobytes())
-    env = dict(os.environ, **SAN_ENV) if sanitized else None
-    r = subprocess.run([str(exe), str(job), str(res)], capture_output=True, text=True, env=env, timeout=1800)
-    assert r.returncode == 0, f"score_emu ({'sanitized' if sanitized else 'plain'}) failed:\n{r.stderr[-6000:]}"
-    assert not any(m in r.stderr for m in SAN_MARKERS), f"sanitizer report:\n{r.stderr[-6000:]}"
-    b = res.read_bytes()
+    r = heh.Reader(heh.run(exe, hdr + c + qa.tobytes() + qb.tobytes(), tmp, "score", sanitized))
     nt = K * n
-    o = 0
-    by_code = np.frombuffer(b, np.int64, K * N_COLS, o).reshape(K, N_COLS); o += 8 * K * N_COLS
-    steps_sum = np.frombuffer(b, np.int64, K, o); o += 8 * K
-    ep_code = ep_steps = None
-    if log:
-        ep_code = np.frombuffer(b, np.uint8, episodes * nt, o).reshape(episodes, nt); o += episodes * nt
-        ep_steps = np.frombuffer(b, np.uint16, episodes * nt, o).reshape(episodes, nt); o += 2 * episodes * nt
-    assert o == len(b)
+    by_code, steps_sum = r.take(np.int64, (K, N_COLS)), r.take(np.int64, (K,))
+    ep_code, ep_steps = (r.take(np.uint8, (episodes, nt)), r.take(np.uint16, (episodes, nt))) if log else (None, None)
+    r.done()
     return {"by_code": by_code, "steps_sum": steps_sum, "ep_code": ep_code, "ep_steps": ep_steps}
 
 

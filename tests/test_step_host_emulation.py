@@ -4,17 +4,15 @@ tests/host_emu/step_emu.cpp compiles the real device header as host C++ (against
 inline-asm macros their portable meaning; the kernel source has no build switch for it) and
 emulates one launch of k_step lane by lane: the clamped acting-table row, load_env, P x agent_period<TICK, XMODE>, the un-staged
 accumulation, store_env.  Every table read and every accumulator target is index-checked.  It is built twice: plain (bit-exact runs)
-and with ASan + UBSan (the same kind of runs, smaller; any report fails).  The GPU tests run this source only on the device, where an
+and with ASan + UBSan (the same kind of runs, smaller; any report fails); building, running a job and reading the result file are
+tests/host_emu_harness.py's, shared with the other four emulation modules.  The GPU tests run this source only on the device, where an
 out-of-range index either faults the card or silently moves counts, and the oracle is a separate restatement that cannot see an
 addressing bug in the device header; this module closes that gap for every instance the source defines, the parked
 k_step<float, *, TICK_PACKED_LITM, X_TWO> included.
 """
 import os
-import shutil
 import struct
 import subprocess
-from concurrent.futures import ThreadPoolExecutor
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -22,49 +20,16 @@ import pytest
 from dql_multirotor_landing_amd.config import F32, F64, N_CELLS, Q_PAPER, TRAJ_EIGHT, DqlConfig
 from oracle.oracle import Oracle
 
-ROOT = Path(__file__).resolve().parent.parent
-EMU = ROOT / "tests" / "host_emu"
-CSRC = ROOT / "dql_multirotor_landing_amd" / "csrc"
+import host_emu_harness as heh
+from host_emu_harness import NF_INT, NF_REAL, ROOT, SAN_ENV
+
 GOLDEN = ROOT / "tests" / "golden" / "assets"
 
 TICK_PLAIN, TICK_PACKED, TICK_LIT, TICK_PACKED_LITM = 0, 2, 3, 4  # dql_device.hpp
 X_TWO, X_ONLY, X_RUNTIME = 0, 1, 2
 MODE_TRAIN, MODE_EVAL, MODE_EXTERNAL = 0, 1, 2
-NF_REAL, NF_INT = 64, 7
 
-PLAIN_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-mfma"]
-SAN_FLAGS = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off"]
-# the sanitizer settings live in the child's environment only; every report is fatal (halt_on_error) and printed with its stack
-SAN_ENV = {"ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1"}
-SAN_MARKERS = ("runtime error:", "ERROR: AddressSanitizer", "ERROR: LeakSanitizer", "SUMMARY: ")
-
-
-def _clangxx():
-    rocm = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
-    for c in (rocm / "llvm" / "bin" / "clang++", rocm / "lib" / "llvm" / "bin" / "clang++"):
-        if c.exists():
-            return str(c)
-    c = shutil.which("clang++")
-    assert c, "the host emulation needs clang++ (ROCm's llvm/bin/clang++): dql_device.hpp uses clang vector extensions"
-    return c
-
-
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    """the two builds of tests/host_emu/step_emu.cpp, compiled side by side: {"plain": path, "san": path}"""
-    out = tmp_path_factory.mktemp("step_emu")
-    cxx = _clangxx()
-    common = ["-I", str(EMU), "-I", str(CSRC), "-Wno-pass-failed", str(EMU / "step_emu.cpp")]
-    builds = {"plain": PLAIN_FLAGS, "san": SAN_FLAGS}
-
-    def build(kind):
-        exe = out / f"step_emu_{kind}"
-        r = subprocess.run([cxx, *builds[kind], *common, "-o", str(exe)], capture_output=True, text=True)
-        assert r.returncode == 0, f"{kind} build of step_emu failed:\n{r.stderr[-4000:]}"
-        return exe
-
-    with ThreadPoolExecutor(2) as ex:
-        return dict(zip(builds, ex.map(build, builds)))
+emu = heh.emu_fixture("step_emu")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -84,22 +49,13 @@ def _job_bytes(cfg, tick, xmode, snap):
 
 
 def run_emu(exe, cfg, tick, xmode, snap, tmp, sanitized=False):
-    """(reals, ints, acc [4 N_CELLS] int64, stats [12] int64): what one launch leaves behind"""
-    job, res = tmp / f"job_{tick}_{xmode}.bin", tmp / f"res_{tick}_{xmode}.bin"
-    job.write_bytes(_job_bytes(cfg, tick, xmode, snap))
-    env = dict(os.environ, **SAN_ENV) if sanitized else None
-    r = subprocess.run([str(exe), str(job), str(res)], capture_output=True, text=True, env=env, timeout=600)
+    """(reals, ints, acc [4 N_CELLS] int64, stats [12] int64, bad_actions): what one launch leaves behind"""
     what = f"tick {tick} xmode {xmode} mode {snap['mode']} P {snap['P']}"
-    assert r.returncode == 0, f"step_emu ({'sanitized' if sanitized else 'plain'}) failed, {what}:\n{r.stderr[-6000:]}"
-    assert not any(m in r.stderr for m in SAN_MARKERS), f"sanitizer report, {what}:\n{r.stderr[-6000:]}"
+    r = heh.Reader(heh.run(exe, _job_bytes(cfg, tick, xmode, snap), tmp, f"step_{tick}_{xmode}", sanitized, timeout=600, what=what))
     n = snap["ints"].shape[1]
-    b = res.read_bytes()
-    o = 0
-    reals = np.frombuffer(b, np.float64, NF_REAL * n, o).reshape(NF_REAL, n); o += 8 * NF_REAL * n
-    ints = np.frombuffer(b, np.int32, NF_INT * n, o).reshape(NF_INT, n); o += 4 * NF_INT * n
-    acc = np.frombuffer(b, np.int64, 4 * N_CELLS, o); o += 8 * 4 * N_CELLS
-    stats = np.frombuffer(b, np.int64, 12, o)
-    return reals, ints, acc, stats
+    got = r.take(np.float64, (NF_REAL, n)), r.take(np.int32, (NF_INT, n)), r.take(np.int64, (4 * N_CELLS,)), r.take(np.int64, (12,)), int(r.take(np.int64, (1,))[0])
+    r.done()
+    return got
 
 
 def admits(exe, cfg, tmp):
@@ -126,6 +82,18 @@ def instances(cfg, refm, lit_ok):
 # ---------------------------------------------------------------------------------------------------------------------
 # the oracle's launches, recorded
 # ---------------------------------------------------------------------------------------------------------------------
+def implied_bad_actions(cfg, mode, P, actions):
+    """the action codes k_step counts as bad (StatsDev::bad_actions), from the job's actions alone: once per env and period of an external-action launch"""
+    if mode != MODE_EXTERNAL:
+        return 0
+    a = np.asarray(actions, np.int64)
+    ax, ay = a & 3, (a >> 2) & 3
+    bad = (ax > 2) | (ay > 2) | ((a >> 4) != 0)
+    if not cfg.two_axis:
+        bad |= (ay != 0) & (ay != 2)
+    return P * int(bad.sum())
+
+
 def oracle_launch(orc, mode, eps=0.0, P=1, actions=None):
     """one launch of P periods on the oracle: its input (state, acting tables, step index) and what it computed"""
     reals, ints = orc.get_fields()
@@ -136,11 +104,13 @@ def oracle_launch(orc, mode, eps=0.0, P=1, actions=None):
     o_r, o_i = orc.get_fields()
     acc = orc.pending.copy() if mode == MODE_TRAIN else np.zeros(4 * N_CELLS, np.int64)
     snap["out"] = (o_r, o_i, acc, orc.stats - st0)
+    snap["bad_actions"] = implied_bad_actions(orc.cfg, mode, P, actions)
+    assert snap["bad_actions"] == 0, "ext_actions and the soak draws make valid action codes only"
     return snap
 
 
 def assert_launch_equal(got, snap, what):
-    g_r, g_i, g_acc, g_st = got
+    g_r, g_i, g_acc, g_st, g_bad = got
     o_r, o_i, o_acc, o_st = snap["out"]
     bad_i = [f for f in range(NF_INT) if not np.array_equal(g_i[f], o_i[f])]
     assert not bad_i, f"{what}: int fields {bad_i} differ from the oracle"
@@ -149,6 +119,7 @@ def assert_launch_equal(got, snap, what):
     assert not bad_r, f"{what}: real fields {bad_r} differ from the oracle"
     assert np.array_equal(g_acc, o_acc), f"{what}: accumulators differ in {np.count_nonzero(g_acc != o_acc)} entries"
     assert np.array_equal(g_st, o_st), f"{what}: statistics {g_st.tolist()} vs oracle {o_st.tolist()}"
+    assert g_bad == snap["bad_actions"], f"{what}: {g_bad} bad action codes counted, the job's actions imply {snap['bad_actions']}"
 
 
 def flown_oracle(cfg, n, seed, warm=40):
