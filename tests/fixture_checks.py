@@ -46,6 +46,14 @@ class OracleBackend:
     def manager_run(self, cfg, series, contact, seed=0):
         return self.o.manager_run(cfg, series, contact, seed=seed)
 
+    def discretise(self, cfg, p, v, a, ang):
+        return self.o.discretise(cfg, p, v, a, ang)
+
+    def mdp_transition(self, cfg, action, obs, ms, prev_idx, simulation=False):
+        # SimulationMdp.check is TrainingMdp.check without the goal branch: the library's DQL_MDP_SIMULATION stage feeds prev = -1 (csrc/dql_ops.inc), so does this
+        prev = np.full(len(action), -1, dtype=np.int32) if simulation else prev_idx
+        return self.o.mdp_transition(cfg, action, obs, ms, prev)
+
 
 class HipBackend:
     """the product's stateless operators (dql_*_run through ctypes: dql_multirotor_landing_amd/ops.py)"""
@@ -72,6 +80,12 @@ class HipBackend:
 
     def manager_run(self, cfg, series, contact, seed=0):
         return self.o.manager_run(cfg, np.asarray(series)[None], np.asarray(contact)[None], seed=seed)[0]
+
+    def discretise(self, cfg, p, v, a, ang):
+        return self.o.discretise(cfg, p, v, a, ang)
+
+    def mdp_transition(self, cfg, action, obs, ms, prev_idx, simulation=False):
+        return self.o.mdp_transition(cfg, action, obs, ms, prev_idx, stages=self.o.MDP_ALL | (self.o.MDP_SIMULATION if simulation else 0))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -277,3 +291,249 @@ def check_g12_manager_f32(be):
         assert (np.abs(got[:, 8] - ref[:, 8]) <= bsp).all() and (np.abs(got[:, 10] - ref[:, 10]) <= bsp).all()
         worst[tag] = (float(e_acc.max()), float(np.abs(got[:, 8] - ref[:, 8]).max()))
     return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# G1 / G2 / G2s: pkg/mdp.py:149-170, 257-569 (TrainingMdp), :572-886 (SimulationMdp) — discretise, check, reward, continuous_action
+# ---------------------------------------------------------------------------------------------------------------------------------
+# float32 forms (csrc/dql_device.hpp): x / x_max is fl(fl(x) * fl(1 / x_max)) (norm_by), a goal edge is fl(lim[k] * fl(lim[k+1] / lim[k])) or
+# fl(lim[k] * fl(beta)) from float32 casts of the limits, delta_theta / theta_max is a host quotient (dtheta_ratio).  A bin comparison v < edge can
+# therefore fall the other way when v is within rounding of the edge.  How far, relative, in units of eps = 2^-24:
+#   the input side:  cast of the input (1) + rounding of the reciprocal (1) + rounding of the product (1)                     = 3
+#   the edge side:   the cast limits (lim[k] cancels in lim[k] * (lim[k+1] / lim[k]): 1) + the quotient (1) + the product (1)  = 3
+#                    (lim * beta: two casts and a product, also 3; the angle grid: cast angle, cast grid points, two differences: < 3)
+# 6 eps to first order; EDGE_ULPS = 8 leaves 2 eps for the second-order terms and for the float64 side's own roundings (2^-53: nothing).
+EDGE_ULPS = 8
+EDGE_REL = EDGE_ULPS * EPS
+
+
+def unpack_state(idx):
+    idx = np.asarray(idx)
+    return np.stack([idx // 189, (idx // 63) % 3, (idx // 21) % 3, (idx // 7) % 3, idx % 7], axis=-1)
+
+
+def pack_state(s):
+    s = np.asarray(s).astype(np.int64)
+    return ((((s[..., 0] * 3 + s[..., 1]) * 3 + s[..., 2]) * 3 + s[..., 3]) * 7 + s[..., 4]).astype(np.int32)
+
+
+_ORACLE = []
+
+
+def _oracle():
+    """the float64 oracle: pinned bit for bit to G1 / G2 by tests/test_oracle_golden.py, so what it says about a perturbed input is what the reference says"""
+    if not _ORACLE:
+        _ORACLE.append(OracleBackend())
+    return _ORACLE[0]
+
+
+def edge_neighbours(cfg64, p, v, a, ang):
+    """float64 packed indices [8][n] of every input with ONE of its four arguments scaled by 1 +- EDGE_REL"""
+    args = [np.asarray(x, dtype=np.float64) for x in (p, v, a, ang)]
+    out = []
+    for j in range(4):
+        for s in (1.0 - EDGE_REL, 1.0 + EDGE_REL):
+            q = list(args); q[j] = args[j] * s
+            out.append(_oracle().discretise(cfg64, *q))
+    return np.stack(out)
+
+
+def _index_rules(idx32, golden_idx, nb, what):
+    """the three index assertions shared by G1 / G2 / G2s; returns the edge-near mask"""
+    near = (nb != golden_idx[None, :]).any(axis=0)
+    bad = ~near & (idx32 != golden_idx)
+    assert not bad.any(), f"{what}: {bad.sum()} inputs that are NOT within {EDGE_ULPS} eps of a bin edge differ from the golden state, first {np.flatnonzero(bad)[:5]}"
+    ok = (idx32 == golden_idx) | (idx32[None, :] == nb).any(axis=0)
+    assert ok.all(), f"{what}: {(~ok).sum()} edge-near inputs have neither the golden state nor a perturbed neighbour's, first {np.flatnonzero(~ok)[:5]}"
+    assert not ((idx32 < 0) & (golden_idx >= 0)).any(), f"{what}: float32 refuses an input float64 classifies"
+    return near
+
+
+def check_g1_discretise(be, dtype, level):
+    """TrainingMdp.discrete_state over the whole G1 fixture (1 500 random inputs, 500 near the origin, then the edge cases placed on / within 1e-12
+    of every bin edge).  float64: bit for bit.  float32: exact wherever the input is not edge-near; an edge-near input (its float64 class changes
+    when one argument is scaled by 1 +- 8 eps, derivation above) may take a neighbour's class.  Returns (differing, edge-near) counts.
+    Measured on the float32 oracle, levels 0-4: 7-43 inputs differ, all of them edge-near; edge-near 1.5 % (level 0) to 6.6 % (level 4)."""
+    g = np.load(GOLDEN / "g1_discretise.npz")
+    x = g[f"in_{level}"]
+    golden = pack_state(g[f"state_{level}"])
+    idx = be.discretise(DqlConfig(working_curriculum_step=level, dtype=dtype), x[:, 0], x[:, 1], x[:, 2], x[:, 3])
+    if dtype == F64:
+        assert (idx >= 0).all()
+        np.testing.assert_array_equal(unpack_state(idx), g[f"state_{level}"])
+        return 0, 0
+    nb = edge_neighbours(DqlConfig(working_curriculum_step=level, dtype=F64), x[:, 0], x[:, 1], x[:, 2], x[:, 3])
+    near = _index_rules(idx, golden, nb, f"G1 level {level}")
+    assert not near[:1500].any(), f"{near[:1500].sum()} of the 1 500 random inputs are edge-near: the allowance would hide a wrong form"
+    assert near.mean() <= 0.07, near.mean()
+    return int((idx != golden).sum()), int(near.sum())
+
+
+def _g2_replay(level):
+    """G2's trace replayed through the float64 oracle as tests/test_oracle_golden.py::test_g2_traces_bit_exact does (and asserted the same), keeping per
+    STEP row what a teacher-forced call needs: action, observation [7], MDP state before the step [8], previous index; and the golden row."""
+    t = np.load(GOLDEN / "g2_traces.npz")[f"trace_{level}"]
+    cfg = DqlConfig(working_curriculum_step=level, dtype=F64)
+    orc = _oracle()
+    ms = np.zeros((8, 1)); ms[7] = 8
+    prev = np.array([-1], dtype=np.int32)
+    acts, obss, mss, prevs, rows, after = [], [], [], [], [], []
+    for row in t:
+        obs = row[2:9].reshape(7, 1).copy()
+        if int(row[0]) == 0:
+            ms[0] = 0.0; ms[4] = 0.0; ms[5] = 0; ms[6] = 0; ms[7] = 8   # TrainingMdp.reset: everything but the shaping memory (B9)
+            prev = orc.discretise(cfg, obs[0], obs[2], obs[3], obs[4]).astype(np.int32)
+            np.testing.assert_array_equal(unpack_state(prev)[0], row[9:14].astype(int))
+            continue
+        acts.append(int(row[1])); obss.append(obs[:, 0]); mss.append(ms[:, 0].copy()); prevs.append(int(prev[0])); rows.append(row)
+        ms, idx, rew, done = orc.mdp_transition(cfg, [int(row[1])], obs, ms, prev)
+        assert (pack_state(row[9:14])) == idx[0] and int(ms[7, 0]) == int(row[14]) and rew[0] == row[15] and int(done[0]) == int(row[16])
+        assert ms[0, 0] == row[17] and ms[4, 0] == row[18] and int(ms[5, 0]) == int(row[19]) and int(ms[6, 0]) == int(row[20])
+        after.append(ms[:, 0].copy())
+        prev = idx.astype(np.int32)
+    return (np.array(acts, dtype=np.uint8), np.array(obss).T.copy(), np.array(mss).T.copy(), np.array(prevs, dtype=np.int32), np.array(rows),
+            np.array(after).T.copy())
+
+
+_G2_CACHE = {}
+
+
+def g2_replay(level):
+    if level not in _G2_CACHE:
+        _G2_CACHE[level] = _g2_replay(level)
+    return _G2_CACHE[level]
+
+
+def _limit_near(obs, cfg):
+    """a continuous input of check() within EDGE_REL of the limit it is compared with: |rel_p_x|, |rel_p_y| against p_max, z against minimum_altitude and p_max"""
+    px, py, z = np.abs(obs[0]), np.abs(obs[1]), obs[5]
+    nr = lambda x, lim: np.abs(x - lim) <= EDGE_REL * lim
+    return nr(px, cfg.p_max) | nr(py, cfg.p_max) | nr(z, cfg.minimum_altitude) | nr(z, cfg.p_max)
+
+
+def check_g2_traces(be, dtype, level):
+    """check / reward / continuous_action through G2's scripted episodes (quirks B7-B11, B18), every step row TEACHER-FORCED: the float64 replay supplies the
+    MDP state before the step, the previous index, the action and the observation, and ALL step rows go through one batched mdp_transition call of the backend.
+    No difference is carried into a later row.
+
+    float64: every output equals the golden row bit for bit (what test_g2_traces_bit_exact asserts of the sequential replay).
+    float32, per row:
+      index        as G1, edge-nearness from the row's observation
+      code, done, step and goal counters   == golden where the index is and no input of check() is within 8 eps of its limit (time-out 458.4 and f_ag 22.92
+                   are not integers: the integer counters cannot be near them)
+      set-point    continuous_action: fl(fl(sp) +- fl(delta_theta)) clipped at fl(theta_max): |err| <= 2 eps theta_max
+      reward       mdp_reward's float32 sequence, eps = 2^-24, relative roundings counted per term (rows with equal index and code):
+          shp_p = w_p |ncp|: ncp carries 3 eps (cast, reciprocal, product), w_p = -100 is exact, the product 1:           4 eps |shp_p|
+          r_p = clip(shp_p - prev_p, +-r_p_max): prev_p is the cast of the float64 memory (1 eps |prev_p|), the difference 1 eps (|r_p| <= |shp_p| + |prev_p|);
+                the clip is 1-Lipschitz; its bound r_p_max = |w_p| lim_v delta_t <= 4.37 carries 4 eps:                   5 eps (|shp_p| + |prev_p|) + 18 eps
+          r_v likewise with w_v = -10, r_v_max <= 0.44:                                                                     5 eps (|shp_v| + |prev_v|) + 2 eps
+          r_theta = fl(fl(w_theta (|shp_a| - |prev_a|)) inv_theta_max) lim_v: shp_a = w_theta npitch, npitch = sp inv_theta_max within 4 eps absolute (set-point
+                2 eps theta_max, reciprocal, product), shp_a within 1.55 * 6 eps, prev_a a cast (1.55 eps), the difference 1.55 eps: 1.55 * 8 eps; times w_theta
+                (+2): 1.55^2 * 10; times 1 / theta_max = 2.68 (+2): 1.55^2 * 2.68 * 12; times lim_v <= 1 (+2): 1.55^2 * 2.68 * 14                        =  91 eps
+          r_dur = w_dur lim_v delta_t <= 0.27, 5 roundings:                                                                                                  2 eps
+          r_term = w r_max, r_max = r_p_max + r_v_max + r_theta_max + r_dur_max <= 5.6 with <= 6 eps, times 2.6 (+2): 2.6 * 5.6 * 8                      = 117 eps
+          the four additions of terms that sum to <= 4.4 + 0.5 + 2 * 1.55^2 * 2.68 + 0.3 + 14.6 < 33 in magnitude: 4 * 33                                = 132 eps
+        |reward error| <= eps (5 (|shp_p| + |prev_p| + |shp_v| + |prev_v|) + 362)  — <= 8.8e-5 at |shp_p| = |prev_p| = 100; measured 1.3e-5 (float32 oracle, level 4)
+      shaping memory after the step (every row: it depends on neither index nor code): shp_p, shp_v within 4 eps relative, shp_a within 1.55 * 6 eps — the
+                   terms above.  This is where a normalising reciprocal that is off by more than its rounding shows: in the index it only moves the bin
+                   edges by a few eps, inside what G1 must allow, here it is a factor of every row's value (measured: <= 2.7 eps relative, shp_a 2.3 eps)
+      cumulative   cast of the float64 sum + one addition: reward bound + 2 eps |cum|; measured 4.7e-4 at |cum| ~ 4 000 (half an ulp of the sum)
+    and, because G2's own thresholds are not integers, the same rows once more with f_ag = 20 (time-out at exactly 400 steps, success at exactly 20 goal steps)
+    against the float64 oracle: code, done and counters equal under the same exclusions — `>=` against `>` shows only there.
+    Returns (excluded rows, edge-near rows, max reward error, max cumulative error)."""
+    act, obs, ms0, prev, rows, ms_after = g2_replay(level)
+    n = len(act)
+    assert n > 1000
+    cfg = DqlConfig(working_curriculum_step=level, dtype=dtype)
+    ms, idx, rew, done = be.mdp_transition(cfg, act, obs, ms0, prev)
+    golden = pack_state(rows[:, 9:14])
+    if dtype == F64:
+        np.testing.assert_array_equal(idx, golden)
+        np.testing.assert_array_equal(ms[7].astype(int), rows[:, 14].astype(int), err_msg="check code")
+        np.testing.assert_array_equal(rew, rows[:, 15], err_msg="reward")
+        np.testing.assert_array_equal(done, rows[:, 16].astype(np.uint8))
+        np.testing.assert_array_equal(ms[0], rows[:, 17], err_msg="pitch set-point (B11 float accumulator)")
+        np.testing.assert_array_equal(ms[4], rows[:, 18], err_msg="cumulative reward")
+        np.testing.assert_array_equal(ms[5].astype(int), rows[:, 19].astype(int)); np.testing.assert_array_equal(ms[6].astype(int), rows[:, 20].astype(int))
+        np.testing.assert_array_equal(ms[1:4], ms_after[1:4], err_msg="shaping memory")
+        return 0, 0, 0.0, 0.0
+    cfg64 = DqlConfig(working_curriculum_step=level, dtype=F64)
+    nb = edge_neighbours(cfg64, obs[0], obs[2], obs[3], obs[4])
+    near = _index_rules(idx, golden, nb, f"G2 level {level}")
+    same_idx = idx == golden
+    lim_near = _limit_near(obs, cfg)
+    held = same_idx & ~lim_near
+    excluded = int((~held).sum())
+    msg = f"level {level}: {excluded} of {n} rows excluded ({int((~same_idx).sum())} by index, {int(lim_near.sum())} by a limit), {int(near.sum())} edge-near"
+    assert near.mean() <= 0.07 and excluded <= 0.07 * n, msg
+    for j, col, name in ((7, 14, "check code"), (5, 19, "step counter"), (6, 20, "goal counter")):
+        bad = held & (ms[j].astype(int) != rows[:, col].astype(int))
+        assert not bad.any(), f"{name}: rows {np.flatnonzero(bad)[:5]}; {msg}"
+    assert not (held & (done != rows[:, 16].astype(np.uint8))).any(), f"done; {msg}"
+    e_sp = np.abs(ms[0] - rows[:, 17]).max()
+    assert e_sp <= 2 * EPS * cfg.theta_max, (e_sp, msg)
+    for j, name in ((1, "shp_p"), (2, "shp_v")):
+        rel = np.abs(ms[j] - ms_after[j]) / np.maximum(np.abs(ms_after[j]), 1e-30)
+        assert rel.max() <= 4 * EPS, f"{name} after the step: {rel.max() / EPS:.3g} eps relative, row {rel.argmax()}"
+    e_a = np.abs(ms[3] - ms_after[3]).max()
+    assert e_a <= abs(cfg.w_theta) * 6 * EPS, f"shp_a after the step: {e_a / EPS:.3g} eps"
+    ok = held & (ms[7].astype(int) == rows[:, 14].astype(int))
+    b_rew = EPS * (5 * (np.abs(ms_after[1]) + np.abs(ms0[1]) + np.abs(ms_after[2]) + np.abs(ms0[2])) + 362)
+    e_rew = np.abs(rew - rows[:, 15]); e_cum = np.abs(ms[4] - rows[:, 18])
+    b_cum = b_rew + 2 * EPS * np.abs(rows[:, 18])
+    assert (e_rew <= b_rew)[ok].all(), f"reward: worst {(e_rew / b_rew)[ok].max():.3g} of the bound; {msg}"
+    assert (e_cum <= b_cum)[ok].all(), f"cumulative reward: worst {(e_cum / b_cum)[ok].max():.3g} of the bound; {msg}"
+    # integer thresholds: f_ag = 20 -> time-out at 400 steps (B18's episode runs to 459), success at the 20th goal step (the goal sitters run to 23)
+    kw = dict(working_curriculum_step=level, f_ag=20.0)
+    ms_i, idx_i, _, done_i = be.mdp_transition(DqlConfig(dtype=dtype, **kw), act, obs, ms0, prev)
+    ms_r, idx_r, _, done_r = _oracle().mdp_transition(DqlConfig(dtype=F64, **kw), act, obs, ms0, prev)
+    held_i = (idx_i == idx_r) & ~lim_near
+    on_timeout = held_i & (ms0[5] == 399); on_success = held_i & (ms_r[6] == 20) & (ms0[6] == 19)
+    assert on_timeout.any() and (ms_r[7][on_timeout] == 6).any(), "no row sits on the time-out threshold"
+    assert on_success.any() and (ms_r[7][on_success] == 1).any(), "no row sits on the success threshold"
+    for j in (5, 6, 7):
+        bad = held_i & (ms_i[j].astype(int) != ms_r[j].astype(int))
+        assert not bad.any(), f"integer thresholds (f_ag = 20), state row {j}: rows {np.flatnonzero(bad)[:5]}"
+    assert not (held_i & (done_i != done_r)).any()
+    return excluded, int(near.sum()), float(e_rew[ok].max()), float(e_cum[ok].max())
+
+
+def check_g2s_simulation(be, dtype):
+    """SimulationMdp (level 4, no goal branch: the library's DQL_MDP_SIMULATION stage) over G2s, teacher-forced like G2.  The fixture's rows carry the set-point
+    and the check code after every step; the step counter before a row is the number of step rows since the episode's reset row; the goal counter is never
+    read without the goal branch and the rows carry no reward (SimulationMdp.reward is 0.0), so the shaping memory is not needed either.  x state from
+    (rel_p_x, rel_v_x, rel_a_x, pitch) through mdp_transition, y state from (rel_p_y, rel_v_y, rel_a_y, roll) through discretise.
+    float64: bit for bit.  float32: the index rules of G1, code / done where the index is equal and no limit is near, set-point within 2 eps theta_max."""
+    t = np.load(GOLDEN / "g2s_simulation.npz")["trace"]
+    step = t[:, 0] == 1
+    prev_row = np.flatnonzero(step) - 1
+    count = np.zeros(len(t))
+    for i in range(len(t)):
+        count[i] = 0 if t[i, 0] == 0 else count[i - 1] + 1
+    rows = t[step]
+    n = len(rows)
+    ms0 = np.zeros((8, n))
+    ms0[0] = t[prev_row, 25]; ms0[5] = count[prev_row]
+    ms0[7] = np.where(t[prev_row, 23] < 0, 8, t[prev_row, 23])
+    obs = np.stack([rows[:, 3], rows[:, 4], rows[:, 5], rows[:, 7], rows[:, 9], rows[:, 11], rows[:, 12]])
+    act = rows[:, 1].astype(np.uint8)
+    kw = dict(working_curriculum_step=4)
+    cfg = DqlConfig(dtype=dtype, **kw)
+    ms, idx, _, done = be.mdp_transition(cfg, act, obs, ms0, np.full(n, -1, dtype=np.int32), simulation=True)
+    idy = be.discretise(cfg, t[:, 4], t[:, 6], t[:, 8], t[:, 10])
+    gx, gy = pack_state(rows[:, 13:18]), pack_state(t[:, 18:23])
+    if dtype == F64:
+        np.testing.assert_array_equal(idx, gx); np.testing.assert_array_equal(idy, gy)
+        np.testing.assert_array_equal(ms[7].astype(int), rows[:, 23].astype(int)); np.testing.assert_array_equal(done, rows[:, 24].astype(np.uint8))
+        np.testing.assert_array_equal(ms[0], rows[:, 25]); np.testing.assert_array_equal(ms[5], count[step])
+        return 0
+    cfg64 = DqlConfig(dtype=F64, **kw)
+    near = _index_rules(idx, gx, edge_neighbours(cfg64, obs[0], obs[2], obs[3], obs[4]), "G2s x")
+    near_y = _index_rules(idy, gy, edge_neighbours(cfg64, t[:, 4], t[:, 6], t[:, 8], t[:, 10]), "G2s y")
+    held = (idx == gx) & ~_limit_near(obs, cfg)
+    assert near.mean() <= 0.07 and near_y.mean() <= 0.07 and (~held).sum() <= 0.07 * n, (near.sum(), near_y.sum(), (~held).sum(), n)
+    assert not (held & (ms[7].astype(int) != rows[:, 23].astype(int))).any() and not (held & (done != rows[:, 24].astype(np.uint8))).any()
+    assert not (held & (ms[5] != count[step])).any()
+    assert np.abs(ms[0] - rows[:, 25]).max() <= 2 * EPS * cfg.theta_max
+    assert (rows[:, 23] < 7).sum() >= 4, "the trace ends several episodes"
+    return int((~held).sum())

@@ -52,6 +52,28 @@ def test_g12_manager_tick_f32(be):
     fc.check_g12_manager_f32(be)
 
 
+# ---- the MDP itself (discretise / check / reward / continuous_action), both dtypes, against G1, G2 and G2s ----
+@pytest.mark.parametrize("level", range(5))
+@pytest.mark.parametrize("dtype", [F64, F32])
+def test_g1_discretise(be, dtype, level):
+    """pkg/mdp.py:257-333 over the whole fixture, placed edge cases included; float32: exact away from the bin edges, a neighbour's class within 8 eps of one"""
+    fc.check_g1_discretise(be, dtype, level)
+
+
+@pytest.mark.parametrize("level", range(5))
+@pytest.mark.parametrize("dtype", [F64, F32])
+def test_g2_traces(be, dtype, level):
+    """pkg/mdp.py:335-569 through G2's episodes, every step row teacher-forced in one batched call; float32: codes and counters exact, set-point and reward
+    within their rounding bounds; and the integer-threshold variant (f_ag = 20) against the float64 oracle"""
+    fc.check_g2_traces(be, dtype, level)
+
+
+@pytest.mark.parametrize("dtype", [F64, F32])
+def test_g2s_simulation(be, dtype):
+    """pkg/mdp.py:572-886: SimulationMdp's two discretisations and its check without the goal branch"""
+    fc.check_g2s_simulation(be, dtype)
+
+
 def test_angle_bin_from_tangent_equals_argmin_of_the_euler_angle():
     """Round 5: the float32 fused step picks the angle bin of the discrete state from three comparisons of tan^2 against the grid's bin boundaries
     (csrc/dql_device.hpp angle_bin_from_tangent) instead of atan2 + argmin |grid - clip(angle)| (pkg/mdp.py:318-324).  Held against the reference-shaped

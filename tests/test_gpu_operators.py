@@ -301,6 +301,39 @@ def test_g12_manager_tick_f32_on_hip(hip_be):
     fc.check_g12_manager_f32(hip)
 
 
+@pytest.mark.parametrize("level", range(5))
+@pytest.mark.parametrize("dtype", [F64, 0])
+def test_g1_discretise_on_hip(hip_be, dtype, level):
+    """pkg/mdp.py:257-333 (G1), the whole fixture in one launch: dql_discretise; float32: exact away from the bin edges, a neighbour's class within 8 eps of one"""
+    fc, hip, _ = hip_be
+    fc.check_g1_discretise(hip, dtype, level)
+
+
+@pytest.mark.parametrize("level", range(5))
+@pytest.mark.parametrize("dtype", [F64, 0])
+def test_g2_traces_on_hip(hip_be, dtype, level):
+    """pkg/mdp.py:335-569 (G2), every step row teacher-forced from the float64 replay, one launch of > 1 000 lanes: dql_mdp_transition"""
+    fc, hip, _ = hip_be
+    fc.check_g2_traces(hip, dtype, level)
+
+
+@pytest.mark.parametrize("dtype", [F64, 0])
+def test_g2s_simulation_on_hip(hip_be, dtype):
+    """pkg/mdp.py:572-886 (G2s): dql_mdp_transition with DQL_MDP_SIMULATION, the y state through dql_discretise"""
+    fc, hip, _ = hip_be
+    fc.check_g2s_simulation(hip, dtype)
+
+
+def test_mdp_operators_equal_the_oracle_bit_for_bit_in_float32(hip_be):
+    """what makes the oracle's float32 pins the kernel's: the batched G2 rows of every level through both, every output equal"""
+    fc, hip, orc = hip_be
+    for level in range(5):
+        act, obs, ms0, prev, _, _ = fc.g2_replay(level)
+        cfg = DqlConfig(working_curriculum_step=level, dtype=0)
+        for a, b in zip(hip.mdp_transition(cfg, act, obs, ms0, prev), orc.mdp_transition(cfg, act, obs, ms0, prev)):
+            np.testing.assert_array_equal(a, b)
+
+
 @pytest.mark.parametrize("dtype", [F64, 0])
 def test_tick_operators_equal_the_oracle_bit_for_bit(hip_be, golden_dir, dtype):
     """same dtype, same operation sequence: HIP == oracle exactly, for every replay operator (what makes the oracle's fixture pins the kernel's)"""

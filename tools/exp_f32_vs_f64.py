@@ -1,6 +1,11 @@
 """float32 HIP kernel vs float64 oracle from identical states, per field, over 1 period and over a 16-period launch, on the config
 flavours the throughput figures run on.  Prints one JSON line per (case, periods): max error per field group —
-the numbers tests/test_gpu_parity.py's tolerances are set from.  usage: python tools/exp_f32_vs_f64.py [n_envs]"""
+the numbers tests/test_gpu_parity.py's tolerances are set from.  usage: python tools/exp_f32_vs_f64.py [n_envs]
+
+`python tools/exp_f32_vs_f64.py flavours [oracle|hip]`: the flavours of tests/f32_step_checks.py instead (simulation / training at levels 2 and 4, paper
+mode, greedy on the stage-4 tables, handed over so that the 16 periods contain the episode ends), one period per call, with the float32 CPU oracle
+(default: needs no GPU; it is bit-identical to the kernel) or the HIP engine as the float32 side; then the G13 flights in float32 against the recording:
+max error per signal column, and the bound the tests assert (4 x the maximum, rounded up to one significant digit).  -> profiles/f32_step_vs_f64_flavours.jsonl"""
 import json
 import sys
 from pathlib import Path
@@ -27,7 +32,48 @@ GROUPS = {
 }
 
 
+def one_digit_up(x):
+    """x rounded up to one significant digit"""
+    import math
+    if x == 0.0:
+        return 0.0
+    e = math.floor(math.log10(x))
+    return float(f"{math.ceil(x / 10 ** e - 1e-12) * 10.0 ** e:.1g}")
+
+
+def flavours(side):
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tests"))
+    import f32_step_checks as sc
+    make = (lambda cfg, n, seed: Engine(cfg, n, seed=seed)) if side == "hip" else (lambda cfg, n, seed: Oracle(cfg, n, seed=seed, n_threads=16))
+    for name in sc.FLAVOURS:
+        res = sc.fly(make, name)
+        n = len(res["alive"][0])
+        for k, groups in sc.measured(res).items():
+            row = {"flavour": name, "f32_side": side, "periods": k, "n": n, "handover_period": sc.FLAVOURS[name][2],
+                   "envs_left_comparison": n - int(res["alive"][k - 1].sum()), "episode_ends_by_code_in_window": res["ended"].tolist(),
+                   "envs_touched_down_in_window": int(res["contact_envs"].sum())}
+            if sc.acc_is_difference_quotient(res["cfg"]):
+                r32, _, r64, _ = res["snap"][k]
+                row["acc_pair_worst_fraction_of_its_bound"] = max(
+                    float((np.abs(r32[res["names"].index(f)] - r64[res["names"].index(f)]) / sc.acc_bound(res["cfg"], r64, res["names"], sc.TOL[k][0], f))[res["alive"][k - 1]].max())
+                    for f in sc._ACC)
+            row.update(groups)
+            print(json.dumps(row), flush=True)
+    z = np.load(sc.GOLDEN / "g13_env.npz")
+    worst = np.zeros(len(sc.G13_SIGNALS))
+    big = {k: np.inf for k in sc.G13_SIGNALS}
+    for tag in sc.G13_CASES:
+        sig, out = sc.g13_fly(make, tag, z)
+        err, rew = sc.check_g13_flight(tag, z, sig, out, bounds=big)
+        worst = np.maximum(worst, err)
+        print(json.dumps({"g13": tag, "f32_side": side, "periods": len(sig), "max_abs_vs_recording": dict(zip(sc.G13_SIGNALS, err.tolist())), "reward_max_abs": rew}), flush=True)
+    print(json.dumps({"g13": "all", "f32_side": side, "max_abs_vs_recording": dict(zip(sc.G13_SIGNALS, worst.tolist())),
+                      "asserted_bound_4x_one_digit_up": {k: one_digit_up(4 * w) for k, w in zip(sc.G13_SIGNALS, worst.tolist())}}), flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "flavours":
+        return flavours(sys.argv[2] if len(sys.argv) > 2 else "oracle")
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
     for case, kw in CASES.items():
         for periods in (1, 16):
