@@ -170,6 +170,11 @@ SYMBOLS = {
     "dql_ensemble_set_level_schedules": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32]),
     "dql_ensemble_get_levels": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "dql_ensemble_n_unfinished": (C.c_int, [_vp, C.POINTER(_i64)]),
+    # per-learner recipes (include/dql.h)
+    "dql_ensemble_set_recipes": (C.c_int, [_vp, _i32, _vp]),
+    "dql_ensemble_set_recipe": (C.c_int, [_vp, _i32, C.c_uint32, _vp, _i32, _dbl, _vp, _i32, _i32, _i32]),
+    "dql_ensemble_set_recipe_level_schedules": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32]),
+    "dql_ensemble_get_recipes": (C.c_int, [_vp, _vp]),
 }
 MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS
 

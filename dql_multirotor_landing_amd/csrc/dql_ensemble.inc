@@ -1,7 +1,7 @@
 // dql_ensemble.inc: ensembles of sequential Double-Q learners (include/dql.h dql_ensemble_*, DESIGN.md sections 12 and 14): the lane kernels, struct dql_ensemble
 // and its C calls.  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype, OP_PROLOGUE, DevOwned, upload_mdpk,
 // upload_schedule, EvTimer, quads_to_fields / unpack_ints, check_config, InitArgs / k_init, k_mark_reset, TickLds; dql_learner.hpp, dql_advance.hpp; and
-// score_check / score_run of dql_greedy.inc (dql_ensemble_score).
+// score_check / score_run of dql_greedy.inc (dql_ensemble_score).  dql_recipes.inc, included after this file, holds the per-learner recipes (DESIGN.md section 16).
 // ---- sequential learners (dql_ensemble, DESIGN.md section 12) ----
 // One learner per lane (csrc/dql_learner.hpp: learner_periods), workgroups of one wave as in k_rollout; the env stays in registers for all periods of the launch,
 // the tables are the lane's own [DQL_N_CELLS] slices (per-lane global pointers, ordinary vector loads and stores, no atomics).
@@ -121,9 +121,16 @@ struct dql_ensemble {
   LevelSched* d_lv = nullptr; LevelSched h_lv[DQL_MAX_LEVELS]{}; bool have_lv[DQL_MAX_LEVELS]{};
   int* d_worklist = nullptr; int* d_wave_level = nullptr; long long wl_slots = 0;
   long long n_launches = 0, launched_periods = 0, launched_wave_periods = 0;  // since creation (dql_diag_ensemble_launches)
+  struct EnsRecipes* rcp = nullptr;  // per-learner recipes (DESIGN.md section 16, dql_recipes.inc); null: none are installed and every call is as it was
 };
+// of dql_recipes.inc: the installed recipes let go, the rule learner l advances by, the smallest last_level of the populated recipes, dql_ensemble_run's loop
+static void ens_recipes_release(dql_ensemble* x);
+static const AdvanceRule& ens_rule_of(const dql_ensemble* x, size_t l);
+static int ens_recipes_min_last_level(const dql_ensemble* x);
+static int ens_run_recipes(dql_ensemble* x, int64_t periods);
 #define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
 static void ens_free(dql_ensemble* x) {
+  ens_recipes_release(x);
   x->dev.free_all();
   delete x;
 }
@@ -301,7 +308,9 @@ int dql_ensemble_rearm(dql_ensemble* x) {
 int dql_ensemble_set_level(dql_ensemble* x, int32_t k) {
   CHECK_ENS(x);
   if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_level: curriculum step must be in 0..4");
-  if (x->advance_every && k > x->rule.last_level)
+  if (x->rcp && k > ens_recipes_min_last_level(x))
+    return fail(DQL_EINVAL, "dql_ensemble_set_level: with recipes installed the level must not exceed the smallest last_level of the recipes that have a member; nothing was changed");
+  if (!x->rcp && x->advance_every && k > x->rule.last_level)
     return fail(DQL_EINVAL, "dql_ensemble_set_level: in curriculum mode the level must not exceed last_level (raise it with dql_ensemble_set_curriculum first); nothing was changed");
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipDeviceSynchronize());
@@ -332,7 +341,7 @@ static int ens_fetch_levels(dql_ensemble* x, std::vector<int>& frozen, std::vect
   HIP_TRY(hipMemcpy(level.data(), x->adv.level, n * sizeof(int), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(promoted.data(), x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
   int64_t u = 0;
-  for (size_t l = 0; l < n; ++l) u += learner_finished(frozen[l], level[l], promoted[l], x->rule) ? 0 : 1;
+  for (size_t l = 0; l < n; ++l) u += learner_finished(frozen[l], level[l], promoted[l], ens_rule_of(x, l)) ? 0 : 1;
   *unfinished = u;
   return DQL_OK;
 }
@@ -384,6 +393,7 @@ int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
   CHECK_ENS(x);
   if (periods < 1 || periods > (1ll << 40)) return fail(DQL_EINVAL, "dql_ensemble_run: periods must be in 1..2^40; nothing was launched");
   HIP_TRY(hipSetDevice(x->device));
+  if (x->rcp) return ens_run_recipes(x, periods);
   if (x->advance_every) return ens_run_levels(x, periods);
   int rc = DQL_OK;
   EvTimer timer;
@@ -405,6 +415,8 @@ int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
 int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t advance_every, const double* ratios, int32_t advance_exhausted) {
   CHECK_ENS(x);
   if (advance_every < 0 || advance_every > ADV_MAX_EVERY) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_every must be in 0..4096 (0 turns the mode off); nothing was changed");
+  if (advance_every == 0 && x->rcp)
+    return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the mode cannot be switched off (advance_every = 0) while recipes are installed; uninstall them first (dql_ensemble_set_recipes with n_recipes = 0); nothing was changed");
   if (advance_every == 0) {
     // the plain launch flies everyone at the config's level: switching off is refused while a learner stands on another one (dql_ensemble_set_level first)
     if (x->advance_every) {

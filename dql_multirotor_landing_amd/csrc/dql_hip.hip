@@ -37,6 +37,7 @@
 #include "dql_rollout.hpp"
 #include "dql_learner.hpp"
 #include "dql_advance.hpp"
+#include "dql_recipes.hpp"
 #include "dql_score.hpp"
 #include "../../include/dql_diag.h"
 
@@ -2034,5 +2035,6 @@ int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
 #include "dql_ops.inc"
 #include "dql_greedy.inc"
 #include "dql_ensemble.inc"
+#include "dql_recipes.inc"
 #include "dql_agent.inc"
 #include "dql_comm.inc"

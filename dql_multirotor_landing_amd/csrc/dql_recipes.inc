@@ -1,0 +1,271 @@
+// dql_recipes.inc: per-learner recipes for the ensembles of sequential learners (include/dql.h dql_ensemble_set_recipes ..., DESIGN.md section 16): the two
+// kernels, struct EnsRecipes (what an ensemble holds while recipes are installed), dql_ensemble_run's launch loop for it, and the C calls.  A fragment of
+// dql_hip.hip's translation unit, included after dql_ensemble.inc, whose struct dql_ensemble, ens_fly's helpers (make_learn_args, upload_schedule),
+// ens_check_promotion and ens_upload_eps it uses; csrc/dql_recipes.hpp holds the recipe structs, the worklist and the advance step.
+
+// k_learn_levels with one more scalar load: wave w flies the learners worklist[64 w .. 64 w + 63] (-1: an inactive lane), all of them of recipe
+// wave_recipe[w] on level wave_level[w].  From the recipe follow SimK::quirks, the learning rates and the level's exploration table and freeze rules; from
+// (recipe, level) the MdpK (a.a.mdp is the array [R][5]).  After that the call to learner_periods is k_learn's.
+template <typename T> struct LearnRecipesArgs {
+  LearnArgs<T> a;                          // a.mdp: [n_recipes][DQL_MAX_LEVELS]; a.sched is not read (the recipe's RecipeSched replaces it)
+  const RecipeSched DQL_CONST_AS* rs;      // [n_recipes]
+  const int* worklist;                     // [64 n_waves]
+  const int DQL_CONST_AS* wave_recipe;     // [n_waves]
+  const int DQL_CONST_AS* wave_level;      // [n_waves]
+  int n_waves, n_recipes;
+};
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_learn_recipes(LearnRecipesArgs<T> g) {
+  const LearnArgs<T>& a = g.a;
+  const int tid = threadIdx.x;
+  const int w = (int)blockIdx.x;
+  if (w >= g.n_waves) return;
+  const int r = g.wave_recipe[w];
+  const int level = g.wave_level[w];
+  // never taken unless a bug (the host builds the worklist)
+  if ((unsigned)r >= (unsigned)g.n_recipes || (unsigned)level >= (unsigned)DQL_MAX_LEVELS) { if (tid == 0) a.mem.faults[0] += 1ull; return; }
+  const long long l = (long long)g.worklist[(long long)w * 64 + tid];
+  const RecipeSched DQL_CONST_AS* rs = g.rs + r;
+  SimK<T> cl = a.c;
+  cl.working = level;
+  cl.quirks = rs->quirks;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // as in k_learn
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int q = 0; q < 10; ++q) { kv_[q] = to_vgpr((uint32_t)a.seed + (uint32_t)q * 0x9E3779B9u); kv_[10 + q] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)q * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  const LevelSched DQL_CONST_AS* lv = rs->lv + level;
+  const LearnSched sc{rs->alpha_tab, rs->n_alpha, rs->alpha_min, lv->eps_tab, lv->n_eps, lv->window, lv->min_successes, lv->max_episodes};
+  learner_periods<TICK, XMODE>(cl, cfgk, tc, a.mdp + (r * DQL_MAX_LEVELS + level), a.mdp_run, sc, a.mem, a.sr, a.si, a.seed, l, l >= 0 && l < a.mem.n, a.j0, a.n_periods, a.mgr0,
+                               a.tick_sched, kv);
+}
+// an advance point: every learner takes advance_learner_recipe's step by itself, under its own recipe's rule (its own thread moves its own 2 x 567 cells;
+// ordinary vector stores, nothing shared but the `faults` word: see k_ens_advance)
+__global__ void k_ens_advance_recipes(LearnMem mem, AdvanceMem adv, const RecipeRule* rules, int n_recipes, const int* recipe_of, int4* si, long long j, int n_cells) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= mem.n) return;
+  (void)advance_learner_recipe(mem, adv, rules, n_recipes, recipe_of, si, l, j, n_cells);
+}
+
+// ---- what an ensemble holds while recipes are installed (dql_ensemble::rcp; null: none are) ----
+struct EnsRecipes {
+  int n = 0;
+  std::vector<int> recipe_of;                       // [L]
+  RecipeRule rule[RCP_MAX]{}; bool have_rule[RCP_MAX]{};
+  RecipeSched sched[RCP_MAX]{}; bool have_lv[RCP_MAX][DQL_MAX_LEVELS]{};   // (the tables its pointers name are the ensemble's device allocations)
+  int* d_recipe_of = nullptr; RecipeRule* d_rule = nullptr; RecipeSched* d_sched = nullptr; void* d_mdpk = nullptr;  // [L], [n], [n], [n][DQL_MAX_LEVELS] MdpK<T>
+  int* d_worklist = nullptr; int* d_wave_recipe = nullptr; int* d_wave_level = nullptr; long long wl_slots = 0;
+};
+static void ens_recipes_release(dql_ensemble* x) {
+  EnsRecipes* q = x->rcp;
+  if (!q) return;
+  for (int r = 0; r < q->n; ++r) {
+    (void)x->dev.release((void*)q->sched[r].alpha_tab);
+    for (int k = 0; k < DQL_MAX_LEVELS; ++k) (void)x->dev.release((void*)q->sched[r].lv[k].eps_tab);
+  }
+  void* own[] = {q->d_recipe_of, q->d_rule, q->d_sched, q->d_mdpk, q->d_worklist, q->d_wave_recipe, q->d_wave_level};
+  for (void* p : own) (void)x->dev.release(p);
+  delete q;
+  x->rcp = nullptr;
+}
+static const AdvanceRule& ens_rule_of(const dql_ensemble* x, size_t l) {
+  return x->rcp ? x->rcp->rule[x->rcp->recipe_of[l]].rule : x->rule;
+}
+static int ens_recipes_min_last_level(const dql_ensemble* x) {  // over the recipes that have a member and a rule; 4 where there is none
+  int lo = DQL_MAX_LEVELS - 1;
+  for (int r : x->rcp->recipe_of) if (x->rcp->have_rule[r] && x->rcp->rule[r].rule.last_level < lo) lo = x->rcp->rule[r].rule.last_level;
+  return lo;
+}
+// ens_fly's recipe launch: k periods from period x->j on n_waves waves of one (recipe, level) each
+static int ens_fly_recipes(dql_ensemble* x, int k, int n_waves) {
+  EnsRecipes* q = x->rcp;
+  int rc = upload_schedule(x->cfg, x->j, k, x->d_mgr0, x->d_sched); if (rc) return rc;
+  by_dtype(x->cfg.dtype, [&](auto t) {
+    using T = decltype(t);
+    LearnRecipesArgs<T> g;
+    g.a = make_learn_args<T>(x, q->d_mdpk, k);
+    g.rs = (const RecipeSched DQL_CONST_AS*)q->d_sched; g.worklist = q->d_worklist;
+    g.wave_recipe = (const int DQL_CONST_AS*)q->d_wave_recipe; g.wave_level = (const int DQL_CONST_AS*)q->d_wave_level;
+    g.n_waves = n_waves; g.n_recipes = q->n;
+    hipLaunchKernelGGL((k_learn_recipes<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
+  });
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += (long long)n_waves * k;
+  return DQL_OK;
+}
+// ens_run_levels with the recipe-aware learner_finished (ens_fetch_levels reads each learner's own rule), worklist and kernels
+static int ens_run_recipes(dql_ensemble* x, int64_t periods) {
+  EnsRecipes* q = x->rcp;
+  std::vector<int> frozen, level, promoted;
+  int64_t unfinished = 0;
+  int rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
+  // every recipe with a member is complete: its rule is set, and it has schedules for the level each member stands on and every level on its way up to last_level
+  for (size_t l = 0; l < (size_t)x->n; ++l) {
+    const int r = q->recipe_of[l];
+    bool ok = q->have_rule[r] && level[l] >= 0 && level[l] < DQL_MAX_LEVELS && q->have_lv[r][level[l]];
+    for (int k = level[l] + 1; ok && k <= q->rule[r].rule.last_level && k < DQL_MAX_LEVELS; ++k) ok = q->have_lv[r][k];
+    if (!ok)
+      return fail(DQL_EINVAL, "dql_ensemble_run: with recipes installed every recipe that has a member needs dql_ensemble_set_recipe and dql_ensemble_set_recipe_level_schedules for every "
+                              "level from its members' up to its last_level; nothing was launched");
+  }
+  EvTimer timer;
+  rc = timer.start(); if (rc) return rc;
+  std::vector<int> worklist((size_t)q->wl_slots), wave_recipe((size_t)(q->wl_slots / ADV_WAVE)), wave_level((size_t)(q->wl_slots / ADV_WAVE));
+  const long long E = x->advance_every;
+  long long left = periods;
+  while (left > 0) {
+    if (x->j % E == 0) {  // an advance point
+      hipLaunchKernelGGL(k_ens_advance_recipes, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->mem, x->adv, (const RecipeRule*)q->d_rule, q->n, (const int*)q->d_recipe_of, x->si,
+                         (long long)x->j, (int)DQL_CELLS_PER_LEVEL);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipDeviceSynchronize());
+    }
+    rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
+    if (unfinished == 0) { x->j += left; break; }  // nothing left to fly or to advance, now or later (the period index still advances by `periods`)
+    const long long to_point = E - x->j % E;
+    const int k = (int)(left < to_point ? left : to_point);  // <= advance_every <= LEARN_MAX_PERIODS
+    unsigned long long wl_faults = 0ull;
+    const int n_waves = build_worklist_recipes(frozen.data(), level.data(), q->recipe_of.data(), x->n, q->n, worklist.data(), wave_recipe.data(), wave_level.data(), q->wl_slots, &wl_faults);
+    if (wl_faults) {
+      unsigned long long v = 0;
+      HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
+      v += wl_faults;
+      HIP_TRY(hipMemcpy(x->mem.faults, &v, sizeof(v), hipMemcpyHostToDevice));
+    }
+    if (n_waves > 0) {  // (nobody live: everyone unfinished waits for the next advance point)
+      HIP_TRY(hipMemcpy(q->d_worklist, worklist.data(), (size_t)n_waves * ADV_WAVE * sizeof(int), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(q->d_wave_recipe, wave_recipe.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(q->d_wave_level, wave_level.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
+      rc = ens_fly_recipes(x, k, n_waves); if (rc) return rc;
+    }
+    x->j += k; left -= k;
+  }
+  return timer.stop_ms(&x->last_ms);
+}
+
+extern "C" {
+int dql_ensemble_set_recipes(dql_ensemble* x, int32_t n_recipes, const int32_t* recipe_of) {
+  CHECK_ENS(x);
+  if (n_recipes < 0 || n_recipes > RCP_MAX) return fail(DQL_EINVAL, "dql_ensemble_set_recipes: n_recipes must be in 0..64 (0 uninstalls); nothing was changed");
+  if (n_recipes == 0) {
+    HIP_TRY(hipSetDevice(x->device));
+    HIP_TRY(hipDeviceSynchronize());
+    ens_recipes_release(x);
+    return DQL_OK;
+  }
+  if (!x->advance_every) return fail(DQL_EINVAL, "dql_ensemble_set_recipes: recipes need curriculum mode (dql_ensemble_set_curriculum with advance_every > 0 first); nothing was changed");
+  if (!recipe_of) return fail(DQL_EINVAL, "dql_ensemble_set_recipes: null recipe_of; nothing was changed");
+  for (long long l = 0; l < x->n; ++l)
+    if (recipe_of[l] < 0 || recipe_of[l] >= n_recipes) return fail(DQL_EINVAL, "dql_ensemble_set_recipes: every recipe_of[l] must be in 0..n_recipes - 1; nothing was changed");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  // the new set is allocated in full before the installed one is let go
+  EnsRecipes* q = new EnsRecipes;
+  q->n = n_recipes;
+  q->recipe_of.assign(recipe_of, recipe_of + x->n);
+  q->wl_slots = worklist_capacity_recipes(x->n, n_recipes);
+  const size_t n = (size_t)x->n, R = (size_t)n_recipes, waves = (size_t)(q->wl_slots / ADV_WAVE);
+  struct { void** p; size_t bytes; } want[] = {{(void**)&q->d_recipe_of, n * sizeof(int)}, {(void**)&q->d_rule, R * sizeof(RecipeRule)}, {(void**)&q->d_sched, R * sizeof(RecipeSched)},
+                                               {&q->d_mdpk, R * DQL_MAX_LEVELS * mdpk_bytes(x->cfg.dtype)}, {(void**)&q->d_worklist, (size_t)q->wl_slots * sizeof(int)},
+                                               {(void**)&q->d_wave_recipe, waves * sizeof(int)}, {(void**)&q->d_wave_level, waves * sizeof(int)}};
+  bool ok = true;
+  for (auto& w : want) ok = ok && x->dev.alloc(w.p, w.bytes) == hipSuccess && hipMemset(*w.p, 0, w.bytes) == hipSuccess;
+  ok = ok && hipMemcpy(q->d_recipe_of, q->recipe_of.data(), n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    for (auto& w : want) (void)x->dev.release(*w.p);
+    delete q;
+    return fail(DQL_ENOMEM, "dql_ensemble_set_recipes: device memory for the recipes could not be set up; nothing was changed");
+  }
+  ens_recipes_release(x);
+  x->rcp = q;
+  return DQL_OK;
+}
+#define CHECK_RECIPE(who, x, r) do { CHECK_ENS(x); \
+    if (!(x)->rcp) return fail(DQL_EINVAL, std::string(who) + ": no recipes are installed (dql_ensemble_set_recipes first); nothing was changed"); \
+    if ((r) < 0 || (r) >= (x)->rcp->n) return fail(DQL_EINVAL, std::string(who) + ": the recipe must be in 0..n_recipes - 1; nothing was changed"); } while (0)
+int dql_ensemble_set_recipe(dql_ensemble* x, int32_t r, uint32_t quirks, const double* alpha, int32_t n_alpha, double alpha_min, const double* ratios, int32_t last_level,
+                            int32_t advance_exhausted, int32_t transfer_order) {
+  CHECK_RECIPE("dql_ensemble_set_recipe", x, r);
+  EnsRecipes* q = x->rcp;
+  dql_config c = x->cfg;
+  c.quirks = quirks;
+  int rc = check_config(&c); if (rc) return rc;
+  if (!alpha) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: null table; nothing was changed");
+  if (n_alpha < 1 || n_alpha > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: table lengths must be in 1..2^22; nothing was changed");
+  for (int i = 0; i < n_alpha; ++i) if (!(alpha[i] >= 0.0 && alpha[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: learning rates must be in [0, 1]; nothing was changed");
+  if (!(alpha_min >= 0.0 && alpha_min <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: learning rates must be in [0, 1] (alpha_min); nothing was changed");
+  if (!ratios) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: null ratios; nothing was changed");
+  for (int k = 0; k < DQL_MAX_LEVELS; ++k) if (!std::isfinite(ratios[k])) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: the five transfer ratios must be finite; nothing was changed");
+  if (advance_exhausted != 0 && advance_exhausted != 1) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: advance_exhausted must be 0 or 1; nothing was changed");
+  if (transfer_order != RCP_ORDER_REFERENCE && transfer_order != RCP_ORDER_PAPER)
+    return fail(DQL_EINVAL, "dql_ensemble_set_recipe: transfer_order must be 0 (the reference's) or 1 (the paper's); nothing was changed");
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<int> level((size_t)x->n);
+  HIP_TRY(hipMemcpy(level.data(), x->adv.level, level.size() * sizeof(int), hipMemcpyDeviceToHost));
+  int top = 0;
+  for (size_t l = 0; l < level.size(); ++l) if (q->recipe_of[l] == r && level[l] > top) top = level[l];
+  if (last_level < top || last_level >= DQL_MAX_LEVELS)
+    return fail(DQL_EINVAL, "dql_ensemble_set_recipe: last_level must lie between the current level of the recipe's learners and 4; nothing was changed");
+  // the device side is staged in full, then swapped in
+  const size_t mb = mdpk_bytes(x->cfg.dtype);
+  std::vector<char> staged(DQL_MAX_LEVELS * mb);
+  double* d_a = nullptr;
+  if (x->dev.alloc((void**)&d_a, (size_t)n_alpha * sizeof(double)) != hipSuccess) return fail(DQL_ENOMEM, "dql_ensemble_set_recipe: hipMalloc failed; nothing was changed");
+  RecipeRule rule{};
+  for (int k = 0; k < DQL_MAX_LEVELS; ++k) rule.rule.ratios[k] = ratios[k];
+  rule.rule.last_level = last_level; rule.rule.advance_exhausted = advance_exhausted; rule.transfer_order = transfer_order;
+  RecipeSched s = q->sched[r];
+  s.alpha_tab = d_a; s.n_alpha = n_alpha; s.alpha_min = alpha_min; s.quirks = quirks;
+  bool ok = hipMemcpy(d_a, alpha, (size_t)n_alpha * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  for (int k = 0; ok && k < DQL_MAX_LEVELS; ++k) {  // the recipe's MdpK per level: the config with the recipe's quirks and working = k
+    c.working_curriculum_step = k;
+    ok = upload_mdpk(c, (char*)q->d_mdpk + ((size_t)r * DQL_MAX_LEVELS + (size_t)k) * mb) == DQL_OK;
+  }
+  ok = ok && hipMemcpy(q->d_rule + r, &rule, sizeof(rule), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(q->d_sched + r, &s, sizeof(s), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {  // (the recipe is left without a rule: dql_ensemble_run refuses it until the call succeeds)
+    (void)x->dev.release(d_a);
+    q->have_rule[r] = false;
+    return fail(DQL_EHIP, "dql_ensemble_set_recipe: a copy to the device failed; the recipe has no rule now");
+  }
+  (void)x->dev.release((void*)q->sched[r].alpha_tab);  // the table it replaces
+  q->sched[r] = s; q->rule[r] = rule; q->have_rule[r] = true;
+  return DQL_OK;
+}
+int dql_ensemble_set_recipe_level_schedules(dql_ensemble* x, int32_t r, int32_t level, const double* eps, int32_t n_eps, int32_t window, int32_t min_successes, int32_t max_episodes) {
+  CHECK_RECIPE("dql_ensemble_set_recipe_level_schedules", x, r);
+  EnsRecipes* q = x->rcp;
+  if (level < 0 || level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: the level must be in 0..4; nothing was changed");
+  if (!eps) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: null table; nothing was changed");
+  if (n_eps < 1 || n_eps > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: the table length must be in 1..2^22; nothing was changed");
+  // (ens_check_promotion's and ens_upload_eps' checks, here with the whole sentence)
+  if (window < 1 || window > DQL_ENSEMBLE_MAX_WINDOW) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: the promotion window must be in 1..128 (DQL_ENSEMBLE_MAX_WINDOW); nothing was changed");
+  if (min_successes < 1 || max_episodes < 1) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: min_successes and max_episodes must be positive; nothing was changed");
+  for (int i = 0; i < n_eps; ++i) if (!(eps[i] >= 0.0 && eps[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: exploration rates must be in [0, 1]; nothing was changed");
+  uint32_t* d_e = nullptr;
+  int rc = ens_upload_eps(x, "dql_ensemble_set_recipe_level_schedules", eps, n_eps, &d_e); if (rc) return rc;
+  RecipeSched s = q->sched[r];
+  s.lv[level] = LevelSched{d_e, n_eps, window, min_successes, max_episodes};
+  if (hipMemcpy(q->d_sched + r, &s, sizeof(s), hipMemcpyHostToDevice) != hipSuccess) { (void)x->dev.release(d_e); return fail(DQL_EHIP, "hipMemcpy failed"); }
+  (void)x->dev.release((void*)q->sched[r].lv[level].eps_tab);  // the table it replaces
+  q->sched[r] = s; q->have_lv[r][level] = true;
+  return DQL_OK;
+}
+int dql_ensemble_get_recipes(dql_ensemble* x, int32_t* recipe_of) {
+  CHECK_ENS(x);
+  if (!recipe_of) return fail(DQL_EINVAL, "dql_ensemble_get_recipes: null array");
+  for (long long l = 0; l < x->n; ++l) recipe_of[l] = x->rcp ? x->rcp->recipe_of[(size_t)l] : -1;
+  return DQL_OK;
+}
+}  // extern "C"

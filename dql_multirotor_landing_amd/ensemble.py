@@ -10,8 +10,9 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from dataclasses import dataclass, field
 from types import SimpleNamespace
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -23,6 +24,8 @@ MAX_WINDOW = 128               # DQL_ENSEMBLE_MAX_WINDOW
 MAX_LEARNERS = 1 << 20         # DQL_ENSEMBLE_MAX_LEARNERS
 MAX_LEVELS = 5
 MAX_ADVANCE_EVERY = 4096       # csrc/dql_advance.hpp ADV_MAX_EVERY
+MAX_RECIPES = 64               # include/dql.h DQL_ENSEMBLE_MAX_RECIPES
+ORDER_REFERENCE, ORDER_PAPER = 0, 1  # Recipe.transfer_order
 REFERENCE_RATIOS = (1.0, 0.8172650252856599, 0.8211253690681617, 0.8257273369742982, 0.8311571820651724)  # Trainer.transfer_learning_ratio(k), k = 0 .. 4
 N_CODES = len(CHECK_NAMES)
 GOAL = CHECK_NAMES.index("TERMINAL_SUCCESS")
@@ -65,6 +68,62 @@ def min_successes_for(window: int = 100, success_rate: float = 0.96) -> int:
     while not k / window > success_rate:
         k += 1
     return k
+
+
+@dataclass
+class LevelSchedule:
+    """what one level of a recipe flies with (`SequentialEnsemble.set_level_schedules`' arguments); eps None: `exploration_rates(level)`; min_successes None:
+    the reference's 0.96 of the window"""
+    eps: Optional[Sequence[float]] = None
+    window: int = 100
+    min_successes: Optional[int] = None
+    max_episodes: int = 50000
+
+
+@dataclass
+class Recipe:
+    """What the learners of one recipe share (include/dql.h).  The defaults are the reference's recipe: its quirks, the config's
+    learning rates, its exploration and promotion rule per level, its ratios, `Q[k] = Q[k-1] ratio` after level k with the k = 0 wrap (transfer_order 0).
+    transfer_order 1 is the paper's: `Q[k+1] = Q[k] ratios[k+1]` on entering level k + 1, the level-k block kept, no wrap."""
+    quirks: int = 0x7F
+    alpha_table: Optional[Sequence[float]] = None   # None: the ensemble config's
+    alpha_min: Optional[float] = None               # None: the ensemble config's
+    ratios: Sequence[float] = REFERENCE_RATIOS
+    last_level: int = 4
+    advance_exhausted: bool = True
+    transfer_order: int = ORDER_REFERENCE
+    levels: Sequence[LevelSchedule] = field(default_factory=lambda: tuple(LevelSchedule() for _ in range(MAX_LEVELS)))
+
+    def checked(self, cfg: DqlConfig):
+        """-> (alpha float64[], alpha_min, ratios float64[5], per level (eps float64[], window, min_successes, max_episodes)); ValueError on what the library refuses"""
+        alpha = cfg.alpha_table() if self.alpha_table is None else np.ascontiguousarray(self.alpha_table, dtype=np.float64).ravel()
+        alpha_min = float(cfg.alpha_min if self.alpha_min is None else self.alpha_min)
+        if alpha.size < 1 or not ((alpha >= 0.0) & (alpha <= 1.0)).all() or not 0.0 <= alpha_min <= 1.0:
+            raise ValueError("the learning-rate table must not be empty and every learning rate (alpha_min included) must be in [0, 1]")
+        if not 0 <= int(self.quirks) < (1 << 32):
+            raise ValueError("quirks must be a 32-bit word")
+        r = np.ascontiguousarray(self.ratios, dtype=np.float64).ravel()
+        if r.size != MAX_LEVELS or not np.isfinite(r).all():
+            raise ValueError("ratios must be five finite numbers")
+        if not 0 <= int(self.last_level) < MAX_LEVELS:
+            raise ValueError("last_level must be in 0..4")
+        if self.transfer_order not in (ORDER_REFERENCE, ORDER_PAPER):
+            raise ValueError("transfer_order must be 0 (the reference's) or 1 (the paper's)")
+        if len(self.levels) != MAX_LEVELS:
+            raise ValueError("a recipe has five level schedules")
+        lv = []
+        for k, s in enumerate(self.levels):
+            e = exploration_rates(k) if s.eps is None else np.ascontiguousarray(s.eps, dtype=np.float64).ravel()
+            window = int(s.window)
+            if not 1 <= window <= MAX_WINDOW:
+                raise ValueError(f"window must be in 1..{MAX_WINDOW}")
+            ms = min_successes_for(window) if s.min_successes is None else int(s.min_successes)
+            if ms < 1 or int(s.max_episodes) < 1:
+                raise ValueError("min_successes and max_episodes must be positive")
+            if e.size < 1 or not ((e >= 0.0) & (e <= 1.0)).all():
+                raise ValueError("the eps table must not be empty and exploration rates must be in [0, 1]")
+            lv.append((e, window, ms, int(s.max_episodes)))
+        return alpha, alpha_min, r, lv
 
 
 class SequentialEnsemble:
@@ -170,6 +229,52 @@ class SequentialEnsemble:
         v = C.c_int64()
         _lib.check(self.lib.dql_ensemble_n_unfinished(self._h, C.byref(v)))
         return int(v.value)
+
+    # ---- per-learner recipes (include/dql.h) ----
+    def set_recipes(self, recipes, recipe_of):
+        """In curriculum mode: learner l flies by `recipes[recipe_of[l]]` (up to 64 `Recipe`s) instead of the ensemble's one quirk word, schedules and rule.
+        An empty list uninstalls them.  Every argument is checked before the library is touched."""
+        recipes = list(recipes)
+        if len(recipes) > MAX_RECIPES:
+            raise ValueError(f"at most {MAX_RECIPES} recipes")
+        if not recipes:
+            _lib.check(self.lib.dql_ensemble_set_recipes(self._h, 0, None))
+            self._recipes = []
+            return
+        of = np.ascontiguousarray(recipe_of, dtype=np.int32).ravel()
+        if of.size != self.n or of.min() < 0 or of.max() >= len(recipes):
+            raise ValueError("recipe_of needs one index in 0..len(recipes) - 1 per learner")
+        checked = [r.checked(self.cfg) for r in recipes]
+        _lib.check(self.lib.dql_ensemble_set_recipes(self._h, len(recipes), _p(of)))
+        self._recipes = []
+        for i, (r, (alpha, alpha_min, ratios, lv)) in enumerate(zip(recipes, checked)):
+            _lib.check(self.lib.dql_ensemble_set_recipe(self._h, i, int(r.quirks), _p(alpha), alpha.size, alpha_min, _p(ratios), int(r.last_level), 1 if r.advance_exhausted else 0,
+                                                        int(r.transfer_order)))
+            for k, (e, window, ms, me) in enumerate(lv):
+                _lib.check(self.lib.dql_ensemble_set_recipe_level_schedules(self._h, i, k, _p(e), e.size, window, ms, me))
+        self._recipes = recipes
+
+    def recipes(self):
+        """(the installed `Recipe`s, recipe_of int32 [L]); ([], all -1) while none are installed"""
+        of = np.zeros(self.n, dtype=np.int32)
+        _lib.check(self.lib.dql_ensemble_get_recipes(self._h, _p(of)))
+        return (list(getattr(self, "_recipes", [])) if (of >= 0).all() else []), of
+
+    def recipe_summary(self):
+        """per installed recipe: {"members", "learners_per_level" [5], "promoted_per_level" [5], "exhausted_per_level" [5] (learners that left level k — or
+        stand frozen on it — after promoting / out of episodes), "finished"}"""
+        recipes, of = self.recipes()
+        lv, c = self.levels(), self.counters()
+        level, frozen, promoted = lv["level"], c["frozen"], c["promotion_episode"]
+        out = []
+        for i, r in enumerate(recipes):
+            m = of == i
+            left = lambda k: m & ((level > k) | ((level == k) & frozen))
+            done = m & frozen & ((level >= r.last_level) | ((promoted < 0) & (not r.advance_exhausted)))
+            out.append({"members": int(m.sum()), "learners_per_level": np.bincount(level[m], minlength=MAX_LEVELS).tolist(),
+                        "promoted_per_level": [int((left(k) & (lv["promoted_at"][k] >= 0)).sum()) for k in range(MAX_LEVELS)],
+                        "exhausted_per_level": [int((left(k) & (lv["promoted_at"][k] < 0)).sum()) for k in range(MAX_LEVELS)], "finished": int(done.sum())})
+        return out
 
     def transfer(self, k: int, ratio: float):
         """`DoubleQLearningAgent.transfer_learning` on every learner's tables (k = 0 wraps to the last level, B6)"""
@@ -346,4 +451,24 @@ def curriculum_per_learner(ens: SequentialEnsemble, last_level: int = 4, advance
             on_chunk(ens, flown)
     out = ens.levels()
     out["periods"] = flown
+    return out
+
+
+def curriculum_recipes(ens: SequentialEnsemble, recipes, recipe_of, advance_every: int = MAX_ADVANCE_EVERY, chunk_periods: int = 16 * MAX_PERIODS_PER_LAUNCH,
+                       max_periods: Optional[int] = None, on_chunk=None):
+    """`curriculum_per_learner` with a recipe per learner (`SequentialEnsemble.set_recipes`): curriculum mode on with `advance_every`, the recipes installed,
+    then the ensemble runs until nobody is unfinished by its own recipe's rule or `max_periods` are flown.  -> `ens.levels()` plus "periods" and
+    "recipe_of"."""
+    ens.set_curriculum(MAX_LEVELS - 1, advance_every)
+    ens.set_recipes(recipes, recipe_of)
+    flown = 0
+    while ens.n_unfinished() > 0 and (max_periods is None or flown < max_periods):
+        k = int(chunk_periods) if max_periods is None else min(int(chunk_periods), int(max_periods) - flown)
+        ens.run(k)
+        flown += k
+        if on_chunk is not None:
+            on_chunk(ens, flown)
+    out = ens.levels()
+    out["periods"] = flown
+    out["recipe_of"] = ens.recipes()[1]
     return out

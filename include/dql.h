@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DQL_ABI_VERSION 6 /* 6: dql_agent_mirror_update_deferred / _complete (added since, without a new number: dql_ensemble_set_curriculum, _set_level_schedules, _get_levels, _n_unfinished); 5: tick replay operators (dql_*_run), measurement symbols moved to dql_diag.h as dql_diag_* */
+#define DQL_ABI_VERSION 6 /* 6: dql_agent_mirror_update_deferred / _complete (added since, without a new number: dql_ensemble_set_curriculum, _set_level_schedules, _get_levels, _n_unfinished; dql_ensemble_set_recipes, _set_recipe, _set_recipe_level_schedules, _get_recipes); 5: tick replay operators (dql_*_run), measurement symbols moved to dql_diag.h as dql_diag_* */
 
 typedef enum dql_status {
   DQL_OK = 0,
@@ -580,6 +580,36 @@ int dql_ensemble_set_level_schedules(dql_ensemble* ens, int32_t level, const dou
 int dql_ensemble_get_levels(dql_ensemble* ens, int32_t* level, int32_t* promoted_at, int32_t* episodes_at, int64_t* entered_period);
 /* learners that still have something to fly or a level to advance to; with the mode off: dql_ensemble_n_live */
 int dql_ensemble_n_unfinished(dql_ensemble* ens, int64_t* n);
+
+/* ---- per-learner recipes ----
+ * In curriculum mode an ensemble can hold up to DQL_ENSEMBLE_MAX_RECIPES recipes, and every learner belongs to one of them (recipe_of[l]).  A recipe holds
+ * what every learner of an ensemble otherwise shares: the quirk word (it replaces the config's for the recipe's learners, env side and update), the
+ * learning-rate table and alpha_min, per level 0..4 the exploration table, window, min_successes and max_episodes, and the rule of its advance points:
+ * ratios[5], last_level, advance_exhausted and transfer_order.  transfer_order 0 is the reference's order, exactly as described above.  transfer_order 1 is
+ * the paper's: a learner that leaves level k keeps its level-k block as learnt, and on entering level k + 1 gets Q[k+1] = Q[k] * ratios[k+1] in both tables;
+ * there is no wrap and ratios[0] is unused; everything else at an advance point is as above.  advance_every, the env-side config, gamma and dtype stay the
+ * ensemble's.  The RNG key stays (learner, seed) and advance points depend on the period index only, so learner l of a recipe ensemble equals, bit for bit
+ * in every output, learner l of an ensemble of the same size and seed in which EVERY learner has l's recipe; two runs of a and b periods equal one of a + b.
+ * While no recipes are installed every call behaves as described above.
+ * dql_ensemble_set_recipes installs n_recipes empty recipes and the assignment (replacing whatever was installed); n_recipes = 0 uninstalls.  Each recipe is
+ * then filled with dql_ensemble_set_recipe and, per level, dql_ensemble_set_recipe_level_schedules.  While recipes are installed the rule of
+ * dql_ensemble_set_curriculum and the schedules of dql_ensemble_set_schedules / _set_level_schedules are kept but not read; dql_ensemble_n_unfinished,
+ * dql_ensemble_get_levels and dql_ensemble_run go by each learner's own recipe.
+ * Refused with DQL_EINVAL, a message, nothing changed and nothing launched: dql_ensemble_set_recipes while curriculum mode is off, with n_recipes outside
+ * 0..64, with an index outside 0..n_recipes - 1, or with a null array and n_recipes > 0; dql_ensemble_set_recipe / _set_recipe_level_schedules for a recipe
+ * that is not installed, with what dql_ensemble_set_curriculum and dql_ensemble_set_schedules / _set_level_schedules refuse (last_level is held against the
+ * recipe's own learners; alpha_min is a learning rate), or with a transfer_order other than 0 or 1; dql_ensemble_run unless every recipe that has a member
+ * has its rule and its schedules for every level from each member's level up to its last_level; dql_ensemble_set_curriculum with advance_every = 0; and
+ * dql_ensemble_set_level above the smallest last_level of the recipes that have a member. */
+#define DQL_ENSEMBLE_MAX_RECIPES 64
+int dql_ensemble_set_recipes(dql_ensemble* ens, int32_t n_recipes, const int32_t* recipe_of); /* recipe_of int32[n_learners] */
+/* alpha double[n_alpha], ratios double[5] (transfer_order 0: ratios[k] when level k is finished; 1: ratios[k + 1] when level k + 1 is entered) */
+int dql_ensemble_set_recipe(dql_ensemble* ens, int32_t recipe, uint32_t quirks, const double* alpha, int32_t n_alpha, double alpha_min, const double* ratios,
+                            int32_t last_level, int32_t advance_exhausted, int32_t transfer_order);
+int dql_ensemble_set_recipe_level_schedules(dql_ensemble* ens, int32_t recipe, int32_t level, const double* eps, int32_t n_eps, int32_t window,
+                                            int32_t min_successes, int32_t max_episodes);
+/* recipe_of int32[n_learners]: every learner's recipe, or -1 everywhere while none are installed */
+int dql_ensemble_get_recipes(dql_ensemble* ens, int32_t* recipe_of);
 
 #ifdef __cplusplus
 }

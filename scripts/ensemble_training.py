@@ -3,7 +3,7 @@
 one learner per GPU lane (dql_multirotor_landing_amd/ensemble.py).
 
     python scripts/ensemble_training.py --learners 4096 --seed 42 [--launched] [--levels 5] [--episodes 50000] [--score ENVS] --out run.npz
-                                        [--per-learner [--advance-every E] [--drop-exhausted]]
+                                        [--per-learner [--advance-every E] [--drop-exhausted] [--max-periods N]] [--recipes FILE.json]
 
 --launched: the parameters the reference's manager node ran with under roslaunch (config.as_launched_config) instead of the launch file's.
 --score ENVS: after the curriculum, fly every learner's tables greedily where they live (SequentialEnsemble.landing_rates: ENVS envs per learner and flavour,
@@ -12,6 +12,11 @@ touchdowns), with the figures of the reference's published tables from the same 
 --per-learner: every learner walks the levels by itself (ensemble.curriculum_per_learner) instead of waiting at each level for the slowest
 learner of the ensemble; a learner advances at the next period index that is a multiple of E (--advance-every, default 4096); --drop-exhausted: a learner whose
 episode budget ran out stays where it is instead of advancing as the reference's loop does.
+--recipes FILE.json: several recipes in ONE ensemble (ensemble.curriculum_recipes; implies --per-learner).  The file is a list; an entry is
+a preset name — "reference" (quirks 0x7f, the reference's transfer order) or "paper" (evaluation.Q_PAPER, the paper's order) — or an object with any of "preset"
+(default "reference"), "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min" and "levels": {"K": {"eps": [...],
+"window", "min_successes", "max_episodes"}} for the levels that differ from the preset's.  Learners are dealt round-robin: recipe r gets the learners with
+l % R == r.  With --score the landing-rate quantiles are reported per recipe.
 Writes every learner's tables and, per level, its first-promotion episode (-1: the episode budget ran out first); with --per-learner also each learner's level,
 the episodes it spent at each level and the period index at which it entered it."""
 import argparse
@@ -25,7 +30,52 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from dql_multirotor_landing_amd.config import F32, F64, Q_REFERENCE, as_launched_config, training_config  # noqa: E402
 from dql_multirotor_landing_amd import evaluation  # noqa: E402
-from dql_multirotor_landing_amd.ensemble import SequentialEnsemble, curriculum, curriculum_per_learner  # noqa: E402
+from dql_multirotor_landing_amd.ensemble import (LevelSchedule, ORDER_PAPER, ORDER_REFERENCE, Recipe, SequentialEnsemble, curriculum, curriculum_per_learner,  # noqa: E402
+                                                 curriculum_recipes)
+
+RECIPE_KEYS = {"preset", "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min", "levels"}
+LEVEL_KEYS = {"eps", "window", "min_successes", "max_episodes"}
+
+
+def preset_recipe(name, episodes, last_level=4, advance_exhausted=True):
+    """"reference": 0x7f with the reference's order; "paper": evaluation.Q_PAPER with the paper's; both with the reference's schedules and `episodes` per level"""
+    if name not in ("reference", "paper"):
+        raise ValueError(f"unknown preset {name!r}: reference or paper")
+    levels = tuple(LevelSchedule(max_episodes=int(episodes)) for _ in range(5))
+    if name == "reference":
+        return Recipe(quirks=Q_REFERENCE, transfer_order=ORDER_REFERENCE, last_level=last_level, advance_exhausted=advance_exhausted, levels=levels)
+    return Recipe(quirks=evaluation.Q_PAPER, transfer_order=ORDER_PAPER, last_level=last_level, advance_exhausted=advance_exhausted, levels=levels)
+
+
+def load_recipes(path, episodes, last_level=4, advance_exhausted=True):
+    """-> (names, recipes) of a --recipes file"""
+    entries = json.loads(Path(path).read_text())
+    if not isinstance(entries, list) or not 1 <= len(entries) <= 64:
+        raise ValueError("a recipes file is a list of 1..64 recipes")
+    names, recipes = [], []
+    for i, e in enumerate(entries):
+        if isinstance(e, str):
+            e = {"preset": e, "name": e}
+        if not isinstance(e, dict) or set(e) - RECIPE_KEYS:
+            raise ValueError(f"recipe {i}: a preset name or an object with keys among {sorted(RECIPE_KEYS)}")
+        r = preset_recipe(e.get("preset", "reference"), episodes, last_level, advance_exhausted)
+        for k in ("quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min"):
+            if k in e:
+                setattr(r, k, e[k])
+        levels = list(r.levels)
+        for k, lv in e.get("levels", {}).items():
+            if not 0 <= int(k) < 5 or set(lv) - LEVEL_KEYS:
+                raise ValueError(f"recipe {i}: levels are 0..4 with keys among {sorted(LEVEL_KEYS)}")
+            levels[int(k)] = LevelSchedule(**{**vars(levels[int(k)]), **lv})
+        r.levels = tuple(levels)
+        names.append(e.get("name", f"recipe {i}"))
+        recipes.append(r)
+    return names, recipes
+
+
+def deal(n, n_recipes):
+    """round-robin: recipe r gets the learners with l % R == r"""
+    return (np.arange(int(n)) % int(n_recipes)).astype(np.int32)
 
 
 def rate_summary(x):
@@ -54,6 +104,12 @@ def score_report(ens, a):
     return rep, td, gh
 
 
+def per_recipe_report(names, recipe_of, td, gh, summary):
+    """the landing-rate quantiles and `SequentialEnsemble.recipe_summary` of every recipe's learners"""
+    return [{"recipe": r, "name": name, **summary[r], "learners_at_or_above_bar": int((td[recipe_of == r] >= evaluation.LANDING_BAR).sum()),
+             "touchdown_rate": rate_summary(td[recipe_of == r]), "goal_hold_rate": rate_summary(gh[recipe_of == r])} for r, name in enumerate(names)]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--learners", type=int, default=4096)
@@ -71,6 +127,8 @@ def main():
     ap.add_argument("--per-learner", action="store_true", help="every learner advances through the levels by itself")
     ap.add_argument("--advance-every", type=int, default=4096, metavar="E", help="with --per-learner: learners advance at the period indices that are multiples of E (1..4096)")
     ap.add_argument("--drop-exhausted", action="store_true", help="with --per-learner: a learner out of episodes stays frozen instead of advancing")
+    ap.add_argument("--max-periods", type=int, default=None, help="with --per-learner or --recipes: stop after this many periods whoever is unfinished")
+    ap.add_argument("--recipes", default=None, metavar="FILE.json", help="fly several recipes in one ensemble, dealt round-robin (implies --per-learner)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     dtype = F64 if a.f64 else F32
@@ -82,12 +140,20 @@ def main():
             print(json.dumps({"level": h["level"], "periods": h["periods"], "promoted": int((p >= 0).sum()), "of": int(p.size),
                               "median_promotion_episode": None if not (p >= 0).any() else int(np.median(p[p >= 0]))}), flush=True)
         extra = {}
-        if a.per_learner:
-            def progress(e, flown):
-                lv = e.levels()["level"]
-                print(json.dumps({"periods": flown, "unfinished": e.n_unfinished(), "learners_per_level": np.bincount(lv, minlength=5).tolist()}), flush=True)
+        names = recipe_of = None
+
+        def progress(e, flown):
+            lv = e.levels()["level"]
+            print(json.dumps({"periods": flown, "unfinished": e.n_unfinished(), "learners_per_level": np.bincount(lv, minlength=5).tolist()}), flush=True)
+        if a.recipes:
+            names, recipes = load_recipes(a.recipes, a.episodes, a.levels - 1, not a.drop_exhausted)
+            recipe_of = deal(a.learners, len(recipes))
+            h = curriculum_recipes(ens, recipes, recipe_of, advance_every=a.advance_every, max_periods=a.max_periods, on_chunk=progress)
+            hist = [{"promotion_episode": h["promoted_at"][k], "periods": h["periods"]} for k in range(a.levels)]
+            extra = {"level": h["level"], "episodes_at": h["episodes_at"], "entered_period": h["entered_period"], "recipe_of": recipe_of}
+        elif a.per_learner:
             h = curriculum_per_learner(ens, last_level=a.levels - 1, advance_every=a.advance_every, advance_exhausted=not a.drop_exhausted, max_episodes=a.episodes,
-                                       on_chunk=progress)
+                                       max_periods=a.max_periods, on_chunk=progress)
             hist = [{"promotion_episode": h["promoted_at"][k], "periods": h["periods"]} for k in range(a.levels)]
             extra = {"level": h["level"], "episodes_at": h["episodes_at"], "entered_period": h["entered_period"]}
         else:
@@ -95,6 +161,9 @@ def main():
         if a.score:
             rep, td, gh = score_report(ens, a)
             extra.update({"touchdown_rate": td, "goal_hold_rate": gh})
+            if names is not None:
+                rep["recipes"] = per_recipe_report(names, recipe_of, td, gh, ens.recipe_summary())
+                rep.update({"periods": int(h["periods"]), "unfinished": ens.n_unfinished()})
             print(json.dumps(rep), flush=True)
             ref = rep["reference_tables"]
             print(f"{rep['learners_at_or_above_bar']} of {rep['learners']} learners ({100.0 * rep['share_at_or_above_bar']:.1f} %) reach a touchdown rate of "
