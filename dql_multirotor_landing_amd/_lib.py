@@ -175,6 +175,9 @@ SYMBOLS = {
     "dql_ensemble_set_recipe": (C.c_int, [_vp, _i32, C.c_uint32, _vp, _i32, _dbl, _vp, _i32, _i32, _i32]),
     "dql_ensemble_set_recipe_level_schedules": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32]),
     "dql_ensemble_get_recipes": (C.c_int, [_vp, _vp]),
+    # teams of envs per learner
+    "dql_ensemble_create_teams": (C.c_int, [_cfgp, C.c_int, _i64, _i32, _u64, _i32, C.POINTER(_vp)]),
+    "dql_ensemble_envs_per_learner": (C.c_int, [_vp, C.POINTER(_i32)]),
 }
 MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS
 

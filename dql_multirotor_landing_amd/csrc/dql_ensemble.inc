@@ -122,12 +122,17 @@ struct dql_ensemble {
   int* d_worklist = nullptr; int* d_wave_level = nullptr; long long wl_slots = 0;
   long long n_launches = 0, launched_periods = 0, launched_wave_periods = 0;  // since creation (dql_diag_ensemble_launches)
   struct EnsRecipes* rcp = nullptr;  // per-learner recipes (DESIGN.md section 16, dql_recipes.inc); null: none are installed and every call is as it was
+  // teams (DESIGN.md section 17, dql_teams.inc): learner l owns envs l E .. l E + E - 1 of the n_envs = n E the state arrays hold; teams: dql_ensemble_run flies k_learn_team
+  int envs_per_learner = 1; long long n_envs = 0; bool teams = false;
 };
 // of dql_recipes.inc: the installed recipes let go, the rule learner l advances by, the smallest last_level of the populated recipes, dql_ensemble_run's loop
 static void ens_recipes_release(dql_ensemble* x);
 static const AdvanceRule& ens_rule_of(const dql_ensemble* x, size_t l);
 static int ens_recipes_min_last_level(const dql_ensemble* x);
 static int ens_run_recipes(dql_ensemble* x, int64_t periods);
+// of dql_teams.inc: one launch of k_learn_team (ens_fly's part for a team ensemble)
+static int ens_launch_teams(dql_ensemble* x, int k, int n_waves);
+#define ENS_TEAMS_REFUSED(who) "" who ": an ensemble with more than one env per learner flies the barrier mode only (teams have no per-learner curriculum and no recipes); nothing was changed and nothing was launched"
 #define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
 static void ens_free(dql_ensemble* x) {
   ens_recipes_release(x);
@@ -185,6 +190,7 @@ static int ens_fly(dql_ensemble* x, int k, int n_waves, bool by_level) {
   int rc = upload_schedule(x->cfg, x->j, k, x->d_mgr0, x->d_sched); if (rc) return rc;  // (synchronous: the previous launch has read its schedule)
   by_dtype(x->cfg.dtype, [&](auto t) {
     using T = decltype(t);
+    if (x->teams && !by_level) return;  // k_learn_team, below (with one env per learner a team ensemble in curriculum mode flies k_learn_levels: the same learner)
     if (by_level) {
       LearnLevelsArgs<T> g;
       g.a = make_learn_args<T>(x, x->mdpk5, k);
@@ -194,6 +200,7 @@ static int ens_fly(dql_ensemble* x, int k, int n_waves, bool by_level) {
       hipLaunchKernelGGL((k_learn<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, make_learn_args<T>(x, x->mdpk, k));
     }
   });
+  if (x->teams && !by_level) { rc = ens_launch_teams(x, k, n_waves); if (rc) return rc; }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += (long long)n_waves * k;
@@ -202,20 +209,17 @@ static int ens_fly(dql_ensemble* x, int k, int n_waves, bool by_level) {
 extern "C" {
 #define ENS_ALLOC(ptr, bytes) do { if (x->dev.alloc((void**)&(ptr), (bytes)) != hipSuccess) { ens_free(x); return fail(DQL_ENOMEM, "hipMalloc failed"); } \
                                    if (hipMemset((ptr), 0, (bytes)) != hipSuccess) { ens_free(x); return fail(DQL_EHIP, "hipMemset failed"); } } while (0)
-int dql_ensemble_create(const dql_config* cfg, int device, int64_t n_learners, uint64_t seed, int32_t log_capacity, dql_ensemble** out) {
-  int rc = check_config(cfg); if (rc) return rc;
-  if (!out) return fail(DQL_EINVAL, "dql_ensemble_create: null pointer; nothing was launched");
-  if (cfg->two_axis) return fail(DQL_EINVAL, "dql_ensemble_create: two-axis configs are refused (the reference's learner is x-only); nothing was launched");
-  if (cfg->trajectory == DQL_TRAJ_EIGHT) return fail(DQL_EINVAL, "dql_ensemble_create: the figure-eight trajectory is refused (the reference's learner is x-only); nothing was launched");
-  if (n_learners < 1 || n_learners > DQL_ENSEMBLE_MAX_LEARNERS) return fail(DQL_EINVAL, "dql_ensemble_create: n_learners must be in 1..2^20 (DQL_ENSEMBLE_MAX_LEARNERS); nothing was launched");
-  if (log_capacity < 0 || log_capacity > DQL_ENSEMBLE_MAX_LOG) return fail(DQL_EINVAL, "dql_ensemble_create: log_capacity must be in 0..2^20 (DQL_ENSEMBLE_MAX_LOG); nothing was launched");
+// what dql_ensemble_create and dql_ensemble_create_teams (dql_teams.inc) share once their arguments are checked: n_learners learners with envs_per_learner envs each
+static int ens_create(const dql_config* cfg, int device, int64_t n_learners, int envs_per_learner, bool teams, uint64_t seed, int32_t log_capacity, dql_ensemble** out) {
+  int rc = DQL_OK;
   OP_PROLOGUE(device)
   dql_ensemble* x = new dql_ensemble;
   x->cfg = *cfg; x->device = device; x->n = n_learners; x->seed = seed;
-  const size_t n = (size_t)n_learners, mdpk_size = mdpk_bytes(cfg->dtype), real = by_dtype(cfg->dtype, [](auto t) { return sizeof(t); });
+  x->envs_per_learner = envs_per_learner; x->n_envs = n_learners * envs_per_learner; x->teams = teams;
+  const size_t n = (size_t)n_learners, n_envs = (size_t)x->n_envs, mdpk_size = mdpk_bytes(cfg->dtype), real = by_dtype(cfg->dtype, [](auto t) { return sizeof(t); });
   const size_t TB = n * DQL_N_CELLS * sizeof(double);
-  ENS_ALLOC(x->sr, (size_t)NQ_REAL * n * 4 * real);
-  ENS_ALLOC(x->si, n * sizeof(int4));
+  ENS_ALLOC(x->sr, (size_t)NQ_REAL * n_envs * 4 * real);
+  ENS_ALLOC(x->si, n_envs * sizeof(int4));
   ENS_ALLOC(x->mdpk, mdpk_size);
   ENS_ALLOC(x->mem.qa, TB); ENS_ALLOC(x->mem.qb, TB); ENS_ALLOC(x->mem.count, TB);
   ENS_ALLOC(x->mem.decisions, n * sizeof(unsigned long long));
@@ -241,7 +245,7 @@ int dql_ensemble_create(const dql_config* cfg, int device, int64_t n_learners, u
   if (!rc) rc = ens_set_levels(x, 0);  // the whole history cleared ...
   if (!rc) rc = ens_set_levels(x, cfg->working_curriculum_step);  // ... and the config's level entered at period 0
   if (!rc) rc = ens_rearm(x);
-  if (!rc) rc = by_dtype(cfg->dtype, [&](auto t) { return launch_init<decltype(t)>(x->cfg, x->sr, x->si, x->n, x->n, x->seed, 0, nullptr); });
+  if (!rc) rc = by_dtype(cfg->dtype, [&](auto t) { return launch_init<decltype(t)>(x->cfg, x->sr, x->si, x->n_envs, x->n_envs, x->seed, 0, nullptr); });
   // default schedules: the plateau learning rate, no exploration, the reference's window (100 episodes, 97 successes) and no episode budget
   const double a0 = cfg->alpha_min; const double e0 = 0.0;
   if (!rc) rc = dql_ensemble_set_schedules(x, &a0, 1, &e0, 1, 100, 97, INT32_MAX);
@@ -249,6 +253,15 @@ int dql_ensemble_create(const dql_config* cfg, int device, int64_t n_learners, u
   if (rc) { ens_free(x); return rc; }
   *out = x;
   return DQL_OK;
+}
+int dql_ensemble_create(const dql_config* cfg, int device, int64_t n_learners, uint64_t seed, int32_t log_capacity, dql_ensemble** out) {
+  int rc = check_config(cfg); if (rc) return rc;
+  if (!out) return fail(DQL_EINVAL, "dql_ensemble_create: null pointer; nothing was launched");
+  if (cfg->two_axis) return fail(DQL_EINVAL, "dql_ensemble_create: two-axis configs are refused (the reference's learner is x-only); nothing was launched");
+  if (cfg->trajectory == DQL_TRAJ_EIGHT) return fail(DQL_EINVAL, "dql_ensemble_create: the figure-eight trajectory is refused (the reference's learner is x-only); nothing was launched");
+  if (n_learners < 1 || n_learners > DQL_ENSEMBLE_MAX_LEARNERS) return fail(DQL_EINVAL, "dql_ensemble_create: n_learners must be in 1..2^20 (DQL_ENSEMBLE_MAX_LEARNERS); nothing was launched");
+  if (log_capacity < 0 || log_capacity > DQL_ENSEMBLE_MAX_LOG) return fail(DQL_EINVAL, "dql_ensemble_create: log_capacity must be in 0..2^20 (DQL_ENSEMBLE_MAX_LOG); nothing was launched");
+  return ens_create(cfg, device, n_learners, 1, false, seed, log_capacity, out);
 }
 int dql_ensemble_destroy(dql_ensemble* x) {
   if (!x) return DQL_OK;
@@ -316,7 +329,7 @@ int dql_ensemble_set_level(dql_ensemble* x, int32_t k) {
   HIP_TRY(hipDeviceSynchronize());
   x->cfg.working_curriculum_step = k;
   int rc = upload_mdpk(x->cfg, x->mdpk); if (rc) return rc;
-  hipLaunchKernelGGL(k_mark_reset, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->si, (const uint8_t*)nullptr, (long long)x->n);  // every env re-enters through reset
+  hipLaunchKernelGGL(k_mark_reset, dim3((unsigned)((x->n_envs + 255) / 256)), dim3(256), 0, 0, x->si, (const uint8_t*)nullptr, (long long)x->n_envs);  // every env re-enters through reset
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   rc = ens_set_levels(x, k); if (rc) return rc;
@@ -406,7 +419,7 @@ int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
       rc = dql_ensemble_n_live(x, &live); if (rc) return rc;
       if (live == 0) { x->j += left; break; }
     }
-    rc = ens_fly(x, k, (int)((x->n + 63) / 64), false); if (rc) return rc;
+    rc = ens_fly(x, k, (int)((x->n_envs + 63) / 64), false); if (rc) return rc;
     x->j += k; left -= k;
   }
   return timer.stop_ms(&x->last_ms);
@@ -414,6 +427,7 @@ int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
 // ---- per-learner curriculum levels (DESIGN.md section 14) ----
 int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t advance_every, const double* ratios, int32_t advance_exhausted) {
   CHECK_ENS(x);
+  if (x->envs_per_learner > 1) return fail(DQL_EINVAL, ENS_TEAMS_REFUSED("dql_ensemble_set_curriculum"));
   if (advance_every < 0 || advance_every > ADV_MAX_EVERY) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_every must be in 0..4096 (0 turns the mode off); nothing was changed");
   if (advance_every == 0 && x->rcp)
     return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the mode cannot be switched off (advance_every = 0) while recipes are installed; uninstall them first (dql_ensemble_set_recipes with n_recipes = 0); nothing was changed");
@@ -566,7 +580,7 @@ int dql_ensemble_get_state(dql_ensemble* x, double* reals, int32_t* ints) {
   CHECK_ENS(x);
   if (!reals || !ints) return fail(DQL_EINVAL, "dql_ensemble_get_state: null array");
   HIP_TRY(hipSetDevice(x->device));
-  const long long n = x->n;
+  const long long n = x->n_envs;
   int rc = by_dtype(x->cfg.dtype, [&](auto t) -> int {
     std::vector<decltype(t)> h((size_t)NQ_REAL * n * 4);
     HIP_TRY(hipMemcpy(h.data(), x->sr, h.size() * sizeof(t), hipMemcpyDeviceToHost));

@@ -36,6 +36,7 @@
 #include "dql_host_consts.hpp"
 #include "dql_rollout.hpp"
 #include "dql_learner.hpp"
+#include "dql_team.hpp"
 #include "dql_advance.hpp"
 #include "dql_recipes.hpp"
 #include "dql_score.hpp"
@@ -2036,5 +2037,6 @@ int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
 #include "dql_greedy.inc"
 #include "dql_ensemble.inc"
 #include "dql_recipes.inc"
+#include "dql_teams.inc"
 #include "dql_agent.inc"
 #include "dql_comm.inc"

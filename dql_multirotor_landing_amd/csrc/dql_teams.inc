@@ -1,0 +1,97 @@
+// dql_teams.inc: sequential learners with teams of envs (include/dql.h dql_ensemble_create_teams, DESIGN.md section 17): k_learn_team and the C calls a team
+// ensemble adds.  A fragment of dql_hip.hip's translation unit, not a header; included after dql_ensemble.inc (struct dql_ensemble, LearnArgs, make_learn_args,
+// ens_create) and dql_recipes.inc.  The per-env and per-team bodies, and why two workgroup barriers per period order them, are csrc/dql_team.hpp's.
+template <typename T> struct TeamArgs {
+  LearnArgs<T> a;      // a.mem.n: the learners; a.sr / a.si: the n_envs envs
+  long long n_envs;    // a.mem.n * envs_per_learner: the stride of the state arrays
+  int envs_per_learner, team_shift;  // E = 1 << team_shift, a divisor of 64
+};
+// what the applying lane of a team tells its team-mates about the period to come
+struct TeamCtl { uint32_t eps_thr; int live; };
+// Workgroups of one wave; lane = env g; a team is E consecutive lanes, so no team straddles waves and the last wave may hold fewer teams.  Per period: every
+// live lane flies its env and leaves its record in LDS; barrier; the first lane of every live team applies the team's E records in order and publishes the next
+// period's threshold and whether the team flies on; barrier.  All teams of a wave run side by side.  The wave leaves when every team in it is frozen.
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_learn_team(TeamArgs<T> t) {
+  const LearnArgs<T>& a = t.a;
+  const int tid = threadIdx.x;
+  const long long g = (long long)blockIdx.x * 64 + tid;
+  const bool active = g < t.n_envs;
+  const long long l = active ? (g >> t.team_shift) : 0;  // < a.mem.n
+  const int lead = tid & ~(t.envs_per_learner - 1);      // the team's first lane: the one that applies
+  SimK<T> cl = a.c;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // as in k_learn
+  __shared__ TeamRecord sRec[64];
+  __shared__ TeamCtl sCtl[64];
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+    __syncthreads();
+  }
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  const double* qa = a.mem.qa + l * DQL_N_CELLS;
+  const double* qb = a.mem.qb + l * DQL_N_CELLS;
+  const bool applies = active && tid == lead;
+  TeamState ts = TeamState{};
+  if (applies) ts = team_load(a.sched, a.mem, l);
+  bool live = active && a.mem.frozen[l] == 0;
+  uint32_t eps_thr = live ? a.sched.eps_tab[a.mem.level_episodes[l] < a.sched.n_eps ? a.mem.level_episodes[l] : a.sched.n_eps - 1] : 0u;
+  const bool loaded = live;
+  Env<T> e = Env<T>{};
+  if (live) load_env(e, a.sr, a.si[g], t.n_envs, g, cl);
+  const int np = a.n_periods < LEARN_MAX_PERIODS ? a.n_periods : LEARN_MAX_PERIODS;
+  for (int p = 0; p < np; ++p) {
+    TeamRecord r{0.0, -1, 0, 0, 0};
+    if (live) r = team_env_period<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, e, qa, qb, eps_thr, a.seed, g, a.j0 + p, a.mgr0[p], a.tick_sched[p], kv);
+    sRec[tid] = r;
+    __syncthreads();  // the records are in LDS; every row load of this period lies before the first table write of it
+    if (applies && live) {
+      team_apply(a.sched, a.mem, cl.quirks, a.mdp_run.gamma, l, &sRec[tid], t.envs_per_learner, ts);
+      sCtl[tid] = TeamCtl{ts.eps_thr, ts.live ? 1 : 0};
+    }
+    __syncthreads();  // workgroup-scope release of the applying lanes' table stores, acquire in front of the next period's row loads (dql_team.hpp)
+    if (live) { const TeamCtl ctl = sCtl[lead]; eps_thr = ctl.eps_thr; live = ctl.live != 0; }
+    if (__ballot(live) == 0ull) break;
+  }
+  if (loaded) store_env(e, a.sr, a.si, t.n_envs, g, cl);
+  if (applies && loaded) team_store(ts, a.mem, l);
+}
+static int ens_launch_teams(dql_ensemble* x, int k, int n_waves) {
+  int shift = 0;
+  while ((1 << shift) < x->envs_per_learner) ++shift;
+  by_dtype(x->cfg.dtype, [&](auto t) {
+    using T = decltype(t);
+    TeamArgs<T> g;
+    g.a = make_learn_args<T>(x, x->mdpk, k);
+    g.n_envs = x->n_envs; g.envs_per_learner = x->envs_per_learner; g.team_shift = shift;
+    hipLaunchKernelGGL((k_learn_team<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
+  });
+  return DQL_OK;
+}
+extern "C" {
+int dql_ensemble_create_teams(const dql_config* cfg, int device, int64_t n_learners, int32_t envs_per_learner, uint64_t seed, int32_t log_capacity, dql_ensemble** out) {
+  int rc = check_config(cfg); if (rc) return rc;
+  if (!out) return fail(DQL_EINVAL, "dql_ensemble_create_teams: null pointer; nothing was launched");
+  if (cfg->two_axis) return fail(DQL_EINVAL, "dql_ensemble_create_teams: two-axis configs are refused (the reference's learner is x-only); nothing was launched");
+  if (cfg->trajectory == DQL_TRAJ_EIGHT) return fail(DQL_EINVAL, "dql_ensemble_create_teams: the figure-eight trajectory is refused (the reference's learner is x-only); nothing was launched");
+  if (!team_size_ok(envs_per_learner)) return fail(DQL_EINVAL, "dql_ensemble_create_teams: envs_per_learner must be one of 1, 2, 4, 8, 16, 32, 64 (a team is consecutive lanes of one wave); nothing was launched");
+  if (n_learners < 1 || n_learners > DQL_ENSEMBLE_MAX_LEARNERS / envs_per_learner)
+    return fail(DQL_EINVAL, "dql_ensemble_create_teams: n_learners must be positive and n_learners * envs_per_learner at most 2^20 (DQL_ENSEMBLE_MAX_LEARNERS); nothing was launched");
+  if (log_capacity < 0 || log_capacity > DQL_ENSEMBLE_MAX_LOG) return fail(DQL_EINVAL, "dql_ensemble_create_teams: log_capacity must be in 0..2^20 (DQL_ENSEMBLE_MAX_LOG); nothing was launched");
+  return ens_create(cfg, device, n_learners, envs_per_learner, true, seed, log_capacity, out);
+}
+int dql_ensemble_envs_per_learner(dql_ensemble* x, int32_t* envs_per_learner) {
+  CHECK_ENS(x);
+  if (!envs_per_learner) return fail(DQL_EINVAL, "null pointer");
+  *envs_per_learner = x->envs_per_learner;
+  return DQL_OK;
+}
+}  // extern "C"

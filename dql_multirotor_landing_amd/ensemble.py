@@ -25,6 +25,8 @@ MAX_LEARNERS = 1 << 20         # DQL_ENSEMBLE_MAX_LEARNERS
 MAX_LEVELS = 5
 MAX_ADVANCE_EVERY = 4096       # csrc/dql_advance.hpp ADV_MAX_EVERY
 MAX_RECIPES = 64               # include/dql.h DQL_ENSEMBLE_MAX_RECIPES
+TEAM_SIZES = (1, 2, 4, 8, 16, 32, 64)  # envs per learner (include/dql.h dql_ensemble_create_teams): a team is consecutive lanes of one wave
+TEAMS_BARRIER_ONLY = "an ensemble with more than one env per learner flies the barrier mode only (train_level / curriculum): teams have no per-learner curriculum and no recipes"
 ORDER_REFERENCE, ORDER_PAPER = 0, 1  # Recipe.transfer_order
 REFERENCE_RATIOS = (1.0, 0.8172650252856599, 0.8211253690681617, 0.8257273369742982, 0.8311571820651724)  # Trainer.transfer_learning_ratio(k), k = 0 .. 4
 N_CODES = len(CHECK_NAMES)
@@ -128,23 +130,35 @@ class Recipe:
 
 class SequentialEnsemble:
     def __init__(self, cfg: DqlConfig, n_learners: int, seed: int = 42, device: int = 0, log_capacity: int = 0, alpha_table=None, eps=None, window: int = 100,
-                 min_successes: Optional[int] = None, max_episodes: int = 50000):
-        n_learners, log_capacity = int(n_learners), int(log_capacity)
+                 min_successes: Optional[int] = None, max_episodes: int = 50000, envs_per_learner: int = 1, teams: Optional[bool] = None):
+        """envs_per_learner: E envs per learner (`TEAM_SIZES`), whose transitions the learner takes in env order every period; learner l
+        owns envs l E .. l E + E - 1 and `state()` returns [L E] arrays.  teams: create through dql_ensemble_create_teams (the team kernel) — default: when E > 1;
+        True with E = 1 flies the team kernel with teams of one, which equals the plain ensemble bit for bit."""
+        n_learners, log_capacity, envs_per_learner = int(n_learners), int(log_capacity), int(envs_per_learner)
+        if envs_per_learner not in TEAM_SIZES:
+            raise ValueError(f"envs_per_learner must be one of {TEAM_SIZES}")
+        teams = envs_per_learner > 1 if teams is None else bool(teams)
+        if envs_per_learner > 1 and not teams:
+            raise ValueError("more than one env per learner needs the team kernel (teams=False was asked for)")
         if cfg.two_axis:
             raise ValueError("two-axis configs are refused: the reference's learner is x-only")
         if cfg.trajectory != 0:
             raise ValueError("the figure-eight trajectory is refused: the reference's learner is x-only")
-        if not 1 <= n_learners <= MAX_LEARNERS:
-            raise ValueError(f"n_learners must be in 1..{MAX_LEARNERS}")
+        if not 1 <= n_learners <= MAX_LEARNERS // envs_per_learner:
+            raise ValueError(f"n_learners must be positive and n_learners * envs_per_learner at most {MAX_LEARNERS}")
         if log_capacity < 0:
             raise ValueError("log_capacity must not be negative")
         self.lib = _lib.load()
         self.cfg = cfg
         self.n = n_learners
+        self.envs_per_learner, self.n_envs, self.teams = envs_per_learner, n_learners * envs_per_learner, teams
         self.log_capacity = log_capacity
         self._c = cfg.to_c()
         h = C.c_void_p()
-        _lib.check(self.lib.dql_ensemble_create(C.byref(self._c), int(device), self.n, int(seed), log_capacity, C.byref(h)))
+        if teams:
+            _lib.check(self.lib.dql_ensemble_create_teams(C.byref(self._c), int(device), self.n, envs_per_learner, int(seed), log_capacity, C.byref(h)))
+        else:
+            _lib.check(self.lib.dql_ensemble_create(C.byref(self._c), int(device), self.n, int(seed), log_capacity, C.byref(h)))
         self._h = h
         self.set_schedules(alpha_table, eps, window, min_successes, max_episodes)
 
@@ -190,6 +204,8 @@ class SequentialEnsemble:
         episodes, with `advance_exhausted`) transfers ITS finished level with `ratios[level]`, moves up a level and flies on.  advance_every = 0: mode off.
         ratios: five transfer ratios, default the reference's."""
         last_level, advance_every = int(last_level), int(advance_every)
+        if getattr(self, "envs_per_learner", 1) > 1:
+            raise ValueError(TEAMS_BARRIER_ONLY)
         if not 0 <= advance_every <= MAX_ADVANCE_EVERY:
             raise ValueError(f"advance_every must be in 0..{MAX_ADVANCE_EVERY}")
         r = np.ascontiguousarray(REFERENCE_RATIOS if ratios is None else ratios, dtype=np.float64).ravel()
@@ -235,6 +251,8 @@ class SequentialEnsemble:
         """In curriculum mode: learner l flies by `recipes[recipe_of[l]]` (up to 64 `Recipe`s) instead of the ensemble's one quirk word, schedules and rule.
         An empty list uninstalls them.  Every argument is checked before the library is touched."""
         recipes = list(recipes)
+        if getattr(self, "envs_per_learner", 1) > 1:
+            raise ValueError(TEAMS_BARRIER_ONLY)
         if len(recipes) > MAX_RECIPES:
             raise ValueError(f"at most {MAX_RECIPES} recipes")
         if not recipes:
@@ -370,9 +388,10 @@ class SequentialEnsemble:
         return code, length, cnt
 
     def state(self):
-        """the env state after the last period: {field: float64 [L]} for STATE_REAL_FIELDS, {field: int32 [L]} for STATE_INT_FIELDS"""
-        reals = np.zeros((64, self.n), dtype=np.float64)
-        ints = np.zeros((7, self.n), dtype=np.int32)
+        """the env state after the last period: {field: float64 [L E]} for STATE_REAL_FIELDS, {field: int32 [L E]} for STATE_INT_FIELDS, in env order (learner
+        l's envs are l E .. l E + E - 1; E = 1 unless the ensemble was made with envs_per_learner)"""
+        reals = np.zeros((64, self.n_envs), dtype=np.float64)
+        ints = np.zeros((7, self.n_envs), dtype=np.int32)
         _lib.check(self.lib.dql_ensemble_get_state(self._h, _p(reals), _p(ints)))
         rn = [self.lib.dql_field_name(i, 0).decode() for i in range(64)]
         inn = [self.lib.dql_field_name(i, 1).decode() for i in range(7)]
@@ -437,6 +456,8 @@ def curriculum_per_learner(ens: SequentialEnsemble, last_level: int = 4, advance
     """`curriculum` without the ensemble-wide barrier: every learner walks the levels by itself (`SequentialEnsemble.set_curriculum`).  The five levels get
     the schedules `curriculum` gives them (`exploration_rates(k)`, `min_successes_for`, the reference's ratios), then the ensemble runs until nobody is
     unfinished or `max_periods` are flown.  -> `ens.levels()` plus "periods", the periods run."""
+    if getattr(ens, "envs_per_learner", 1) > 1:
+        raise ValueError(TEAMS_BARRIER_ONLY)
     ms = min_successes_for(window, success_rate)
     budget = ens.max_episodes if max_episodes is None else int(max_episodes)
     for k in range(MAX_LEVELS):
@@ -459,6 +480,8 @@ def curriculum_recipes(ens: SequentialEnsemble, recipes, recipe_of, advance_ever
     """`curriculum_per_learner` with a recipe per learner (`SequentialEnsemble.set_recipes`): curriculum mode on with `advance_every`, the recipes installed,
     then the ensemble runs until nobody is unfinished by its own recipe's rule or `max_periods` are flown.  -> `ens.levels()` plus "periods" and
     "recipe_of"."""
+    if getattr(ens, "envs_per_learner", 1) > 1:
+        raise ValueError(TEAMS_BARRIER_ONLY)
     ens.set_curriculum(MAX_LEVELS - 1, advance_every)
     ens.set_recipes(recipes, recipe_of)
     flown = 0

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DQL_ABI_VERSION 6 /* 6: dql_agent_mirror_update_deferred / _complete (added since, without a new number: dql_ensemble_set_curriculum, _set_level_schedules, _get_levels, _n_unfinished; dql_ensemble_set_recipes, _set_recipe, _set_recipe_level_schedules, _get_recipes); 5: tick replay operators (dql_*_run), measurement symbols moved to dql_diag.h as dql_diag_* */
+#define DQL_ABI_VERSION 6 /* 6: dql_agent_mirror_update_deferred / _complete (added since, without a new number: dql_ensemble_set_curriculum, _set_level_schedules, _get_levels, _n_unfinished; dql_ensemble_set_recipes, _set_recipe, _set_recipe_level_schedules, _get_recipes; dql_ensemble_create_teams, _envs_per_learner); 5: tick replay operators (dql_*_run), measurement symbols moved to dql_diag.h as dql_diag_* */
 
 typedef enum dql_status {
   DQL_OK = 0,
@@ -610,6 +610,25 @@ int dql_ensemble_set_recipe_level_schedules(dql_ensemble* ens, int32_t recipe, i
                                             int32_t min_successes, int32_t max_episodes);
 /* recipe_of int32[n_learners]: every learner's recipe, or -1 everywhere while none are installed */
 int dql_ensemble_get_recipes(dql_ensemble* ens, int32_t* recipe_of);
+
+/* ---- learners with teams of envs ----
+ * dql_ensemble_create_teams makes an ensemble whose learner l owns, besides its three tables, the envs g = l E .. l E + E - 1 (E = envs_per_learner, one of
+ * 1, 2, 4, 8, 16, 32, 64) of a context made with dql_create(cfg, device, n_learners * E, seed, 0): the Philox key of env g is (g, seed).  All envs share
+ * the period index.  In a period every env of a live learner that is not resetting acts on ONE exploration threshold (the eps table at the episodes the
+ * learner had finished at the level when the period began) and, where it does not explore, greedily on the learner's tables as they stood after all of the
+ * previous period's updates.  Then the learner applies DoubleQLearningAgent.update to the E transitions one after the other in env order — learning rate at
+ * the pre-increment count as it stands at that moment, the row of s' read from the tables as they stand at that moment, so after the updates of the envs
+ * before it in the same period — and books finished episodes in the same order (totals, by_code, episode log, the promotion ring).  Once the level is
+ * decided in a period (promotion or max_episodes), episodes that later envs finish in the SAME period count in the totals and the log only, so
+ * level_episodes and promoted never exceed max_episodes.  The learner freezes at the end of that period: all E updates applied, all E envs left as they
+ * are after it.  No fold, no delay: a literal sequence of update calls.  With E = 1 every output equals dql_ensemble_create's, bit for bit.
+ * Every dql_ensemble_* call works on such an ensemble; dql_ensemble_get_state returns n_learners * E envs in env order ([64][n_learners * E] and
+ * [7][n_learners * E]), dql_ensemble_set_level sends all of them through reset; tables, counters, log and score stay per learner.  With E > 1 the ensemble
+ * flies the barrier mode only: dql_ensemble_set_curriculum and dql_ensemble_set_recipes return DQL_EINVAL with nothing changed and nothing launched.
+ * Refused like dql_ensemble_create, and for an envs_per_learner outside the seven values or n_learners * envs_per_learner > DQL_ENSEMBLE_MAX_LEARNERS. */
+int dql_ensemble_create_teams(const dql_config* cfg, int device, int64_t n_learners, int32_t envs_per_learner, uint64_t seed, int32_t log_capacity,
+                              dql_ensemble** out);
+int dql_ensemble_envs_per_learner(dql_ensemble* ens, int32_t* envs_per_learner); /* 1 for dql_ensemble_create's */
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ one learner per GPU lane (dql_multirotor_landing_amd/ensemble.py).
 
     python scripts/ensemble_training.py --learners 4096 --seed 42 [--launched] [--levels 5] [--episodes 50000] [--score ENVS] --out run.npz
                                         [--per-learner [--advance-every E] [--drop-exhausted] [--max-periods N]] [--recipes FILE.json]
+                                        [--envs-per-learner E]
 
 --launched: the parameters the reference's manager node ran with under roslaunch (config.as_launched_config) instead of the launch file's.
 --score ENVS: after the curriculum, fly every learner's tables greedily where they live (SequentialEnsemble.landing_rates: ENVS envs per learner and flavour,
@@ -17,6 +18,9 @@ a preset name — "reference" (quirks 0x7f, the reference's transfer order) or "
 (default "reference"), "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min" and "levels": {"K": {"eps": [...],
 "window", "min_successes", "max_episodes"}} for the levels that differ from the preset's.  Learners are dealt round-robin: recipe r gets the learners with
 l % R == r.  With --score the landing-rate quantiles are reported per recipe.
+--envs-per-learner E: every learner owns a team of E envs (1, 2, 4, ..., 64) and applies the reference's update to their transitions in env order (DESIGN.md
+section 17), so it collects E episodes in the time of one; --learners times E is at most 2^20.  Teams fly the level-by-level driver only: the flag is refused
+together with --per-learner and --recipes.
 Writes every learner's tables and, per level, its first-promotion episode (-1: the episode budget ran out first); with --per-learner also each learner's level,
 the episodes it spent at each level and the period index at which it entered it."""
 import argparse
@@ -30,8 +34,8 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from dql_multirotor_landing_amd.config import F32, F64, Q_REFERENCE, as_launched_config, training_config  # noqa: E402
 from dql_multirotor_landing_amd import evaluation  # noqa: E402
-from dql_multirotor_landing_amd.ensemble import (LevelSchedule, ORDER_PAPER, ORDER_REFERENCE, Recipe, SequentialEnsemble, curriculum, curriculum_per_learner,  # noqa: E402
-                                                 curriculum_recipes)
+from dql_multirotor_landing_amd.ensemble import (LevelSchedule, ORDER_PAPER, ORDER_REFERENCE, Recipe, SequentialEnsemble, TEAM_SIZES, curriculum,  # noqa: E402
+                                                 curriculum_per_learner, curriculum_recipes)
 
 RECIPE_KEYS = {"preset", "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min", "levels"}
 LEVEL_KEYS = {"eps", "window", "min_successes", "max_episodes"}
@@ -129,11 +133,16 @@ def main():
     ap.add_argument("--drop-exhausted", action="store_true", help="with --per-learner: a learner out of episodes stays frozen instead of advancing")
     ap.add_argument("--max-periods", type=int, default=None, help="with --per-learner or --recipes: stop after this many periods whoever is unfinished")
     ap.add_argument("--recipes", default=None, metavar="FILE.json", help="fly several recipes in one ensemble, dealt round-robin (implies --per-learner)")
+    ap.add_argument("--envs-per-learner", type=int, default=1, metavar="E", help="envs per learner: 1, 2, 4, 8, 16, 32 or 64 (not with --per-learner / --recipes)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
+    if a.envs_per_learner not in TEAM_SIZES:
+        ap.error(f"--envs-per-learner must be one of {', '.join(map(str, TEAM_SIZES))}")
+    if a.envs_per_learner > 1 and (a.per_learner or a.recipes):
+        ap.error("--envs-per-learner above 1 cannot be combined with --per-learner or --recipes: teams fly the level-by-level (barrier) driver only")
     dtype = F64 if a.f64 else F32
     cfg = as_launched_config(dtype=dtype, quirks=Q_REFERENCE) if a.launched else training_config(0, dtype=dtype, quirks=Q_REFERENCE)
-    ens = SequentialEnsemble(cfg, a.learners, seed=a.seed, device=a.device, max_episodes=a.episodes)
+    ens = SequentialEnsemble(cfg, a.learners, seed=a.seed, device=a.device, max_episodes=a.episodes, envs_per_learner=a.envs_per_learner)
     try:
         def report(e, h):
             p = h["promotion_episode"]
