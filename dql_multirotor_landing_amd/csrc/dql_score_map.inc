@@ -1,0 +1,188 @@
+// dql_score_map.inc: greedy scoring with a map of where the greedy decisions were made (dql_score_map / dql_ensemble_score_map, DESIGN.md section 18).  A fragment
+// of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype_axes, DevBuf / OP_PROLOGUE / UP / OUT / DOWN, upload_mdpk,
+// upload_schedule, EvTimer, check_config, TickLds; fill_greedy_args / score_check / diag_last of dql_greedy.inc; struct dql_ensemble / CHECK_ENS of
+// dql_ensemble.inc; and dql_score_map.hpp.
+// k_score's shape — one env per lane, workgroups of one wave, table set k serves blocks [k B, (k + 1) B), env i of every set has RNG key (i, seed), the same
+// waves_per_eu — and on top of it the wave's histogram in LDS: unsigned [DQL_N_CELLS], 11 340 B per workgroup.  The wave clears it before the first period,
+// every lane adds its decisions with LDS atomics (many lanes hit one cell in the same period), and at the end the wave flushes the non-zero cells into the table
+// set's row of the global map — zeroed before the launch — with atomicAdd on unsigned long long: lanes sweep contiguous cells, c = it * 64 + lane, SCORE_MAP_SWEEPS
+// = 45 sweeps, the last one partial (cells 2 816 .. 2 834).  Integer sums: the result does not depend on the order the waves arrive in.
+// What orders clear, adds and flush: the workgroup is one wave, the LDS serves a wave's operations in the order they were issued, and the two __syncthreads()
+// keep the compiler from moving an LDS access across them (and make the order hold by the language's rules as well, whatever the workgroup size).
+template <typename T> struct ScoreMapArgs {
+  SimK<T> c;
+  const MdpK<T> DQL_CONST_AS* mdp;
+  MdpRun<T> mdp_run;
+  RolloutInit<T> init;
+  const double* qa; const double* qb;                                  // [n_tables][DQL_N_CELLS]
+  const long long DQL_CONST_AS* mgr0; const int DQL_CONST_AS* sched;   // [max_steps + 1] (fill_schedule)
+  unsigned long long* by_code;                                         // [n_tables][SCORE_N_COLS]
+  unsigned long long* steps_sum;                                       // [n_tables]
+  unsigned long long* visits;                                          // [n_tables][DQL_N_CELLS]
+  unsigned long long* faults;                                          // [1] writes the range checks dropped (0 unless a bug)
+  ScoreMapLog log;
+  unsigned long long seed;
+  int blocks_per_table, max_steps, episodes, n_tables;
+};
+struct LdsHist {  // the wave's histogram as score_map_episodes sees it; cell is range-checked by the caller
+  unsigned* h;
+  __device__ __forceinline__ void add(int cell) { atomicAdd(&h[cell], 1u); }
+};
+template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_score_map(ScoreMapArgs<T> a) {
+  const int tid = threadIdx.x;
+  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
+  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
+  const long long g = (long long)blockIdx.x * 64 + tid;                // log column: every lane of the grid is an env (envs_per_table is a multiple of 64)
+  if (k >= a.n_tables) {  // never taken unless a bug (the host sizes the grid): nothing is read or written for a table set that is not there
+    if (tid == 0) atomicAdd(a.faults, 1ull);
+    return;
+  }
+  SimK<T> cl = a.c;
+  if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
+  SimK<T> cfgk = cl;
+  if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
+  __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
+  __shared__ unsigned sHist[DQL_N_CELLS];
+#pragma unroll 1
+  for (int it = 0; it < SCORE_MAP_SWEEPS; ++it) {
+    const int c = it * 64 + tid;
+    if (c < DQL_N_CELLS) sHist[c] = 0u;
+  }
+  if constexpr (sizeof(T) == 8) {
+    if (tid == 0) sTickK.k = cfgk;
+  }
+  __syncthreads();  // the clear (and the tick constants) before the first period
+  const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
+  const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
+  LdsHist hist{sHist};
+  const ScoreMapTally r = score_map_episodes<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.episodes, a.mgr0, a.sched, kv,
+                                                          a.log, g, hist);
+  __syncthreads();  // the adds of every lane before the flush
+  unsigned long long* map = a.visits + (size_t)k * DQL_N_CELLS;
+#pragma unroll 1
+  for (int it = 0; it < SCORE_MAP_SWEEPS; ++it) {
+    const int c = it * 64 + tid;
+    const unsigned v = c < DQL_N_CELLS ? sHist[c] : 0u;
+    if (v) atomicAdd(&map[c], (unsigned long long)v);
+  }
+  if (r.faults) atomicAdd(a.faults, (unsigned long long)r.faults);
+  if (tid == 0) {
+    const ScoreTally& t = r.t;
+    unsigned long long* row = a.by_code + (size_t)k * SCORE_N_COLS;
+#pragma unroll
+    for (int col = 0; col < SCORE_N_COLS; ++col) if (t.by_code[col]) atomicAdd(&row[col], (unsigned long long)t.by_code[col]);
+    if (t.steps) atomicAdd(&a.steps_sum[k], t.steps);
+  }
+}
+
+extern "C" {
+static thread_local double g_score_map_ms = -1.0;
+static thread_local int g_score_map_inst[3] = {0, 0, 0};
+// score_check, and what the map adds to it: checked before the device is touched
+static int score_map_check(const char* who, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, int32_t max_steps, const int64_t* by_code, const int64_t* steps_sum,
+                           const int64_t* visits, const uint8_t* ep_code, const uint16_t* ep_steps, const uint16_t* ep_last_cell) {
+  const std::string w(who);
+  if (n_tables > DQL_SCORE_MAP_MAX_TABLES) return fail(DQL_EINVAL, w + ": the number of table sets must be in 1..2^14 (DQL_SCORE_MAP_MAX_TABLES: the map is 22 680 B per set); nothing was launched");
+  if ((ep_code == nullptr) != (ep_last_cell == nullptr) || (ep_steps == nullptr) != (ep_last_cell == nullptr))
+    return fail(DQL_EINVAL, w + ": the episode log needs all three arrays or none; nothing was launched");
+  int rc = score_check(who, n_tables, envs_per_table, episodes_per_env, max_steps, by_code, steps_sum, ep_code, ep_steps); if (rc) return rc;
+  if (!visits) return fail(DQL_EINVAL, w + ": null array; nothing was launched");
+  return DQL_OK;
+}
+// d_qa / d_qb: [n_tables][DQL_N_CELLS] on the current device
+static int score_map_run(const char* who, const dql_config* cfg, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, const double* d_qa,
+                         const double* d_qb, int64_t* by_code, int64_t* steps_sum, int64_t* visits, uint8_t* ep_code, uint16_t* ep_steps, uint16_t* ep_last_cell) {
+  const long long n_total = n_tables * envs_per_table;
+  const int n_per = max_steps + 1;
+  DevBuf d_mgr0, d_sched, d_mdp, d_sums, d_code, d_steps, d_cells;
+  OUT(d_mgr0, (size_t)n_per * sizeof(long long)); OUT(d_sched, (size_t)n_per * sizeof(int)); OUT(d_mdp, mdpk_bytes(cfg->dtype));
+  int rc = upload_schedule(*cfg, 0, n_per, d_mgr0.p, d_sched.p); if (rc) return rc;
+  rc = upload_mdpk(*cfg, d_mdp.p); if (rc) return rc;
+  // one buffer for all sums: [n_tables][SCORE_N_COLS] counts, [n_tables] step totals, [n_tables][DQL_N_CELLS] visits, [1] faults
+  const size_t n_sums = (size_t)n_tables * (SCORE_N_COLS + 1 + DQL_N_CELLS) + 1;
+  OUT(d_sums, n_sums * sizeof(unsigned long long));
+  HIP_TRY(hipMemset(d_sums.p, 0, n_sums * sizeof(unsigned long long)));
+  const size_t log_n = (size_t)episodes * (size_t)n_total;
+  if (ep_code) {
+    OUT(d_code, log_n); OUT(d_steps, log_n * sizeof(uint16_t)); OUT(d_cells, 2 * log_n * sizeof(uint16_t));
+    HIP_TRY(hipMemset(d_code.p, 0xff, log_n));  // not finished
+    HIP_TRY(hipMemset(d_steps.p, 0, log_n * sizeof(uint16_t)));
+    HIP_TRY(hipMemset(d_cells.p, 0xff, 2 * log_n * sizeof(uint16_t)));
+  }
+  unsigned long long* d_by_code = (unsigned long long*)d_sums.p;
+  unsigned long long* d_steps_sum = d_by_code + (size_t)n_tables * SCORE_N_COLS;
+  unsigned long long* d_visits = d_steps_sum + (size_t)n_tables;
+  unsigned long long* d_faults = d_visits + (size_t)n_tables * DQL_N_CELLS;
+  const ScoreMapLog log{(uint8_t*)d_code.p, (uint16_t*)d_steps.p, (uint16_t*)d_cells.p, n_total, episodes};
+  EvTimer timer;
+  rc = timer.start(); if (rc) return rc;
+  int inst[3] = {0, 0, 0};
+  by_dtype_axes(cfg->dtype, cfg->two_axis, [&](auto t, auto xmode) {
+    using T = decltype(t);
+    constexpr int XMODE = decltype(xmode)::value;
+    ScoreMapArgs<T> a;
+    fill_greedy_args<T>(a, *cfg, d_mdp.p, d_qa, d_qb, d_mgr0.p, d_sched.p, seed, envs_per_table, max_steps);
+    a.by_code = d_by_code; a.steps_sum = d_steps_sum; a.visits = d_visits; a.faults = d_faults; a.log = log; a.episodes = episodes; a.n_tables = (int)n_tables;
+    inst[0] = (int)sizeof(T); inst[1] = TICK_PLAIN; inst[2] = XMODE;
+    hipLaunchKernelGGL((k_score_map<T, TICK_PLAIN, XMODE>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
+  });
+  HIP_TRY(hipGetLastError());
+  double ms = 0.0;
+  rc = timer.stop_ms(&ms); if (rc) return rc;
+  unsigned long long faults = 0ull;
+  HIP_TRY(hipMemcpy(&faults, d_faults, sizeof(faults), hipMemcpyDeviceToHost));
+  if (faults) return fail(DQL_ESTATE, std::string(who) + ": the kernel's range checks dropped " + std::to_string(faults) + " writes (a bug); no result was returned");
+  HIP_TRY(hipMemcpy(by_code, d_by_code, (size_t)n_tables * SCORE_N_COLS * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(steps_sum, d_steps_sum, (size_t)n_tables * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(visits, d_visits, (size_t)n_tables * DQL_N_CELLS * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (ep_code) {
+    DOWN(ep_code, d_code, log_n);
+    DOWN(ep_steps, d_steps, log_n * sizeof(uint16_t));
+    DOWN(ep_last_cell, d_cells, 2 * log_n * sizeof(uint16_t));
+  }
+  g_score_map_ms = ms;
+  for (int q = 0; q < 3; ++q) g_score_map_inst[q] = inst[q];
+  return DQL_OK;
+}
+int dql_score_map(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
+                  const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, int64_t* visits, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null,
+                  uint16_t* ep_last_cell_or_null) {
+  int rc = check_config(cfg); if (rc) return rc;
+  rc = score_map_check("dql_score_map", n_tables, envs_per_table, episodes_per_env, max_steps, by_code, steps_sum, visits, ep_code_or_null, ep_steps_or_null, ep_last_cell_or_null);
+  if (rc) return rc;
+  if (!qa || !qb) return fail(DQL_EINVAL, "dql_score_map: null array; nothing was launched");
+  OP_PROLOGUE(device)
+  DevBuf d_qa, d_qb;
+  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
+  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
+  return score_map_run("dql_score_map", cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, (const double*)d_qa.p, (const double*)d_qb.p, by_code, steps_sum, visits,
+                       ep_code_or_null, ep_steps_or_null, ep_last_cell_or_null);
+}
+// the learners' tables are read where they live, as dql_ensemble_score reads them: k_score_map touches nothing else of the ensemble
+int dql_ensemble_score_map(dql_ensemble* x, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env, uint64_t seed,
+                           int32_t max_steps, int64_t* by_code, int64_t* steps_sum, int64_t* visits, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null,
+                           uint16_t* ep_last_cell_or_null) {
+  CHECK_ENS(x);
+  int rc = check_config(eval_cfg); if (rc) return rc;
+  rc = score_map_check("dql_ensemble_score_map", count, envs_per_learner, episodes_per_env, max_steps, by_code, steps_sum, visits, ep_code_or_null, ep_steps_or_null,
+                       ep_last_cell_or_null);
+  if (rc) return rc;
+  if (first < 0 || first > x->n || count > x->n - first)
+    return fail(DQL_EINVAL, "dql_ensemble_score_map: the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
+  HIP_TRY(hipSetDevice(x->device));
+  const size_t off = (size_t)first * DQL_N_CELLS;
+  return score_map_run("dql_ensemble_score_map", eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, x->mem.qa + off, x->mem.qb + off, by_code, steps_sum, visits,
+                       ep_code_or_null, ep_steps_or_null, ep_last_cell_or_null);
+}
+int dql_diag_score_map_last(double* kernel_ms, int32_t* inst3) {
+  return diag_last(g_score_map_ms, g_score_map_inst, kernel_ms, inst3, "no dql_score_map or dql_ensemble_score_map call has completed on this thread");
+}
+}  // extern "C"

@@ -358,6 +358,20 @@ class SequentialEnsemble:
         _lib.check(self.lib.dql_ensemble_score(self._h, C.byref(c), first, count, n, episodes, int(seed), max_steps, _p(by_code), _p(steps_sum), _p(ep_code), _p(ep_steps)))
         return ops.score_result(self.lib, by_code, steps_sum, ep_code, ep_steps, timing)
 
+    def score_map(self, eval_cfg: DqlConfig, envs_per_learner: int = 64, seed: int = 123, episodes: int = 1, max_steps: int = 600, log: bool = False, first: int = 0,
+                  count: Optional[int] = None, timing: dict = None):
+        """`ops.score_map` of learners first .. first + count - 1 on their tables where they live (no host copy): `score`'s result plus `visits` int64 [count,
+        2835] and, with `log`, `ep_last_cell`.  The ensemble is left as it was.  At most ops.SCORE_MAP_MAX_TABLES learners per call: slice with first / count."""
+        from . import ops
+        first, count = self._slice(first, count)
+        n, episodes, max_steps = int(envs_per_learner), int(episodes), int(max_steps)
+        ops.score_map_check_args(count, n, episodes, max_steps)
+        by_code, steps_sum, visits, ep_code, ep_steps, ep_last_cell = ops.score_map_buffers(count, n, episodes, log)
+        c = eval_cfg.to_c()
+        _lib.check(self.lib.dql_ensemble_score_map(self._h, C.byref(c), first, count, n, episodes, int(seed), max_steps, _p(by_code), _p(steps_sum), _p(visits), _p(ep_code),
+                                                   _p(ep_steps), _p(ep_last_cell)))
+        return ops.score_map_result(self.lib, by_code, steps_sum, visits, ep_code, ep_steps, ep_last_cell, timing)
+
     def landing_rates(self, n_envs: int = 4096, episodes: int = 1, level: int = 4, seed: int = 123, dtype=None, quirks=None, max_steps: int = 600, first: int = 0,
                       count: Optional[int] = None, timing: dict = None):
         """`evaluation.landing_rates` of the resident tables: `touchdown_rate` and `goal_hold_rate` per learner, two launches"""
@@ -365,6 +379,14 @@ class SequentialEnsemble:
         quirks = evaluation.Q_PAPER if quirks is None else quirks
         return evaluation.landing_rates_with(lambda cfg, n, sd, ep, ms, t: self.score(cfg, n, sd, ep, ms, first=first, count=count, timing=t),
                                              n_envs, episodes, level, seed, dtype, quirks, max_steps, timing)
+
+    def flight_maps(self, n_envs: int = 4096, episodes: int = 1, level: int = 4, seed: int = 123, dtype=None, quirks=None, max_steps: int = 600, log: bool = False,
+                    first: int = 0, count: Optional[int] = None, timing: dict = None):
+        """`evaluation.flight_maps` of the resident tables: `landing_rates`' figures and both flavours' maps per learner, two launches"""
+        from . import evaluation
+        quirks = evaluation.Q_PAPER if quirks is None else quirks
+        return evaluation.flight_maps_with(lambda cfg, n, sd, ep, ms, t: self.score_map(cfg, n, sd, ep, ms, log=log, first=first, count=count, timing=t),
+                                           n_envs, episodes, level, seed, dtype, quirks, max_steps, timing)
 
     # ---- outputs ----
     def counters(self):

@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import ops
-from .config import CHECK_NAMES, F32, Q_PAPER, simulation_config, training_config
+from .config import CHECK_NAMES, F32, N_CELLS, Q_PAPER, simulation_config, training_config
 from .engine import Engine
 
 METHODS = ("stepwise", "rollout")
@@ -124,6 +124,113 @@ def landing_rates(qa, qb, n_envs: int = 4096, episodes: int = 1, level: int = 4,
     TERMINAL_SUCCESS in the training flavour — and the two count tables.  With episodes = 1 these are `landing_scores`' numbers."""
     return landing_rates_with(lambda cfg, n, sd, ep, ms, t: ops.score(cfg, qa, qb, n, sd, episodes=ep, max_steps=ms, device=device, timing=t),
                               n_envs, episodes, level, seed, dtype, quirks, max_steps, timing)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# the mapping scorer (ops.score_map, include/dql.h dql_score_map): where the greedy policies fly, and what can be read from the maps (pure numpy below)
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+N_STATES = N_CELLS // 3
+
+
+def flight_maps_with(score_map_fn, n_envs: int = 4096, episodes: int = 1, level: int = 4, seed: int = 123, dtype=None, quirks: int = Q_PAPER, max_steps: int = 600,
+                     timing: dict = None):
+    """`landing_rates_with` through `score_map_fn(cfg, n_envs, seed, episodes, max_steps, timing)` -> a score-map result: its dict plus `simulation_visits` and
+    `training_visits` int64 [K, 2835], and `simulation_log` / `training_log` = (ep_code, ep_last_cell) of the flavour, or None where the function kept no log"""
+    kept = []
+
+    def fn(cfg, n, sd, ep, ms, t):
+        kept.append(score_map_fn(cfg, n, sd, ep, ms, t))
+        return kept[-1]
+
+    out = landing_rates_with(fn, n_envs, episodes, level, seed, dtype, quirks, max_steps, timing)
+    for flavour, r in zip(("simulation", "training"), kept):
+        out[f"{flavour}_visits"] = r["visits"]
+        out[f"{flavour}_log"] = None if r["ep_last_cell"] is None else (r["ep_code"], r["ep_last_cell"])
+    return out
+
+
+def flight_maps(qa, qb, n_envs: int = 4096, episodes: int = 1, level: int = 4, seed: int = 123, dtype=None, device=0, quirks: int = Q_PAPER, max_steps: int = 600,
+                log: bool = False, timing: dict = None):
+    """`landing_rates` of K table sets (K up to ops.SCORE_MAP_MAX_TABLES) with both flavours' maps, in two launches (see `flight_maps_with`)"""
+    return flight_maps_with(lambda cfg, n, sd, ep, ms, t: ops.score_map(cfg, qa, qb, n, sd, episodes=ep, max_steps=ms, log=log, device=device, timing=t),
+                            n_envs, episodes, level, seed, dtype, quirks, max_steps, timing)
+
+
+def greedy_actions(qa, qb):
+    """the greedy action of every state of K table sets (`qa`, `qb`: [K, 2835] or [2835]): int64 [K, 945].  `agent_predict`'s rule: the means of the two tables,
+    the first maximum wins (a later action needs a strictly greater mean)."""
+    qa, qb = np.atleast_2d(np.asarray(qa, dtype=np.float64)), np.atleast_2d(np.asarray(qb, dtype=np.float64))
+    if qa.ndim != 2 or qa.shape[1] != N_CELLS or qb.shape != qa.shape:
+        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    m = ((qa + qb) / 2).reshape(len(qa), N_STATES, 3)
+    k = np.zeros(m.shape[:2], np.int64)
+    v = m[..., 0]
+    b = m[..., 1] > v
+    k[b] = 1
+    v = np.where(b, m[..., 1], v)
+    k[m[..., 2] > v] = 2
+    return k
+
+
+def _state_shares(visits):
+    """(decisions [K], p [K, 945]): every state's share of its set's visits, the three actions summed; NaN rows where a set has no decision"""
+    per_state = np.asarray(visits, dtype=np.float64).reshape(-1, N_STATES, 3).sum(axis=2)
+    total = per_state.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return total, per_state / total[:, None]
+
+
+def map_report(visits, greedy, base_visits, base_greedy, trained_count=None):
+    """What K maps say against a baseline's (pure numpy).  `visits` [K, 2835] and `greedy` [K, 945] (`greedy_actions`) of the table sets, `base_visits` [2835] and
+    `base_greedy` [945] of the baseline.  Returns a dict of [K] arrays:
+      decisions, states_visited, cells_visited   totals of the map
+      occupancy_overlap          1 - 1/2 sum_s |p_k(s) - p_base(s)|, p = the state's share of the set's visits (actions summed)
+      disagreement_on_baseline   sum_s p_base(s) [greedy_k(s) != greedy_base(s)]: the share of the baseline's flight spent where set k would act otherwise
+      disagreement_on_own        the same sum weighted with p_k
+      untrained_share            only with `trained_count` [K, 2835]: the share of the set's decisions made at cells whose count is 0
+    A set (or a baseline) without a decision has NaN shares."""
+    visits = np.atleast_2d(np.asarray(visits, dtype=np.int64))
+    greedy = np.atleast_2d(np.asarray(greedy))
+    base_visits = np.asarray(base_visits, dtype=np.int64).reshape(-1)
+    base_greedy = np.asarray(base_greedy).reshape(-1)
+    K = len(visits)
+    if visits.shape[1] != N_CELLS or greedy.shape != (K, N_STATES) or base_visits.shape != (N_CELLS,) or base_greedy.shape != (N_STATES,):
+        raise ValueError("visits [K, 2835], greedy [K, 945], base_visits [2835], base_greedy [945]")
+    decisions, p = _state_shares(visits)
+    base_total, pb = _state_shares(base_visits[None])
+    differs = greedy != base_greedy[None]
+    nan_if_empty = lambda x, empty: np.where(empty, np.nan, x)
+    no_k, no_b = decisions == 0, bool(base_total[0] == 0)
+    with np.errstate(invalid="ignore"):
+        out = {"decisions": visits.sum(axis=1), "states_visited": (visits.reshape(K, N_STATES, 3).sum(axis=2) > 0).sum(axis=1), "cells_visited": (visits > 0).sum(axis=1),
+               "occupancy_overlap": nan_if_empty(1.0 - 0.5 * np.abs(np.nan_to_num(p) - np.nan_to_num(pb)).sum(axis=1), no_k | no_b),
+               "disagreement_on_baseline": nan_if_empty((np.nan_to_num(pb) * differs).sum(axis=1), no_b),
+               "disagreement_on_own": nan_if_empty((np.nan_to_num(p) * differs).sum(axis=1), no_k)}
+    if trained_count is not None:
+        trained_count = np.atleast_2d(np.asarray(trained_count))
+        if trained_count.shape != (K, N_CELLS):
+            raise ValueError("trained_count must be [K, 2835]")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["untrained_share"] = nan_if_empty((visits * (trained_count == 0)).sum(axis=1) / decisions, no_k)
+    return out
+
+
+def failure_origins(ep_code, ep_last_cell, codes, n_tables: int):
+    """int64 [n_tables, 2835]: the histogram of the last x cells (`ep_last_cell[0]`) of the finished episodes whose terminal code is among `codes` (numbers or
+    CHECK_NAMES).  `ep_code` [episodes, n_tables * envs], `ep_last_cell` [2, episodes, n_tables * envs] as `ops.score_map(log=True)` returns them."""
+    ep_code, cells = np.asarray(ep_code), np.asarray(ep_last_cell)
+    if ep_code.ndim != 2 or cells.shape != (2,) + ep_code.shape or n_tables < 1 or ep_code.shape[1] % n_tables:
+        raise ValueError("ep_code [episodes, n_tables * envs] and ep_last_cell [2, episodes, n_tables * envs]")
+    codes = [CHECK_NAMES.index(c) if isinstance(c, str) else int(c) for c in codes]
+    n = ep_code.shape[1] // n_tables
+    x = cells[0].astype(np.int64)
+    pick = np.isin(ep_code, codes) & (x != ops.NO_CELL)
+    if (x[pick] >= N_CELLS).any():
+        raise ValueError("a last cell lies outside the table")
+    out = np.zeros((n_tables, N_CELLS), np.int64)
+    _, col = np.nonzero(pick)
+    np.add.at(out, (col // n, x[pick]), 1)
+    return out
 
 
 QUANTILES = (0.05, 0.5, 0.95)

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .config import CHECK_NAMES, DqlConfig, Q_REFERENCE
+from .config import CHECK_NAMES, DqlConfig, N_CELLS, Q_REFERENCE
 
 
 def _p(a):
@@ -303,3 +303,51 @@ def score(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, episodes: int 
     _lib.check(lib.dql_score(C.byref(c), device, K, n, episodes, int(seed), max_steps, _p(qa), _p(qb), _p(by_code), _p(steps_sum),
                              None if ep_code is None else _p(ep_code), None if ep_steps is None else _p(ep_steps)))
     return score_result(lib, by_code, steps_sum, ep_code, ep_steps, timing)
+
+
+SCORE_MAP_MAX_TABLES = 1 << 14  # include/dql.h DQL_SCORE_MAP_MAX_TABLES: the map is 22 680 B per table set
+NO_CELL = 0xFFFF                # `ep_last_cell` of an episode that did not finish, and of the y plane without a y axis
+
+
+def score_map_check_args(n_tables: int, envs_per_table: int, episodes: int, max_steps: int):
+    """the argument checks of dql_score_map / dql_ensemble_score_map, made before the library is touched"""
+    if not 1 <= n_tables <= SCORE_MAP_MAX_TABLES:
+        raise ValueError(f"between 1 and {SCORE_MAP_MAX_TABLES} table sets per mapping call, not {n_tables}: slice the sets")
+    score_check_args(n_tables, envs_per_table, episodes, max_steps)
+
+
+def score_map_buffers(n_tables: int, envs_per_table: int, episodes: int, log: bool):
+    """(by_code, steps_sum, visits, ep_code or None, ep_steps or None, ep_last_cell or None) as the C calls fill them"""
+    by_code, steps_sum, ep_code, ep_steps = score_buffers(n_tables, envs_per_table, episodes, log)
+    visits = np.zeros((n_tables, N_CELLS), np.int64)
+    ep_last_cell = np.zeros((2, episodes, n_tables * envs_per_table), np.uint16) if log else None
+    return by_code, steps_sum, visits, ep_code, ep_steps, ep_last_cell
+
+
+def score_map_result(lib, by_code, steps_sum, visits, ep_code, ep_steps, ep_last_cell, timing):
+    if timing is not None:
+        ms, inst = C.c_double(), (C.c_int32 * 3)()
+        _lib.check(lib.dql_diag_score_map_last(C.byref(ms), inst))
+        timing["kernel_ms"] = ms.value
+        timing["instance"] = f"k_score_map<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    return {"by_code": by_code, "steps_sum": steps_sum, "ep_code": ep_code, "ep_steps": ep_steps, "columns": SCORE_COLUMNS, "visits": visits, "ep_last_cell": ep_last_cell}
+
+
+def score_map(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, episodes: int = 1, max_steps: int = 600, log: bool = False, device: int = 0, timing: dict = None):
+    """`score`, and where the greedy policy of every table set flew (include/dql.h dql_score_map): the same arguments fly the same episodes and give the same
+    `by_code`, `steps_sum`, `ep_code` and `ep_steps`.  On top of them `visits` int64 [K, 2835]: how many greedy decisions set k made at each cell (state the
+    action was decided from, times 3, plus the action; with two axes both axes' decisions), and with `log` `ep_last_cell` uint16 [2, episodes, K *
+    envs_per_table]: the x and y cell of the decision in whose period the episode ended (0xffff: not finished, or no y axis), else None.  At most
+    SCORE_MAP_MAX_TABLES sets per call.  `timing`: receives `kernel_ms` and `instance`."""
+    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
+    if qa.ndim != 2 or qa.shape[1] != N_CELLS or qb.shape != qa.shape:
+        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    K, n, episodes, max_steps = len(qa), int(envs_per_table), int(episodes), int(max_steps)
+    score_map_check_args(K, n, episodes, max_steps)
+    lib = _lib.load()
+    by_code, steps_sum, visits, ep_code, ep_steps, ep_last_cell = score_map_buffers(K, n, episodes, log)
+    c = cfg.to_c()
+    opt = lambda a: None if a is None else _p(a)
+    _lib.check(lib.dql_score_map(C.byref(c), device, K, n, episodes, int(seed), max_steps, _p(qa), _p(qb), _p(by_code), _p(steps_sum), _p(visits), opt(ep_code), opt(ep_steps),
+                                 opt(ep_last_cell)))
+    return score_map_result(lib, by_code, steps_sum, visits, ep_code, ep_steps, ep_last_cell, timing)

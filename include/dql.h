@@ -419,6 +419,25 @@ int dql_rollout(const dql_config* cfg, int device, int32_t n_tables, int64_t env
 #define DQL_SCORE_MAX_STEPS 4096
 int dql_score(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
               const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null);
+/* ---- greedy scoring with a map: where the greedy policy of each table set flies, counted on the device in the same launch ----
+ * dql_score_map flies exactly what dql_score flies: the table sets, the envs, the key (i, seed), max_steps, episodes_per_env and the schedules are the same, and
+ * for equal arguments by_code, steps_sum, ep_code and ep_steps are equal to dql_score's.  It returns two more things.
+ *   visits  int64 [n_tables][DQL_N_CELLS].  Take the stepwise context of dql_score's contract: dql_create(cfg, device, envs_per_table, seed, 0) with the tables
+ *           of set k, then dql_eval_steps(ctx, 1) for periods 0 .. max_steps.  An env counts in a period if it has finished fewer than episodes_per_env
+ *           episodes before that period and the period is not a reset period of that env (FL_WAS_RESET clear).  Each such period adds 1 at cell
+ *           idx_x_before * 3 + (action & 3), where idx_x_before is the env's idx_x as it stood after the previous period; with two_axis it also adds 1 at
+ *           idx_y_before * 3 + ((action >> 2) & 3) — the tables are shared between the axes, so the y decision lands in the same map.  A lane that has
+ *           finished its episodes counts nothing more; decisions of episodes that max_steps cuts off are counted.  Integer sums: bit-reproducible.
+ *   ep_last_cell  uint16 [2][episodes_per_env][n_tables * envs_per_table], optional (all three log arrays are given, or none).  Plane 0 holds the x cell of the
+ *           decision made in the period in which the episode ended, plane 1 the y cell.  0xffff marks an episode that did not finish; plane 1 holds 0xffff
+ *           everywhere under an x-only config.
+ * dql_ensemble_score_map (below, with the ensembles) does the same on the tables of an ensemble's learners where they live.
+ * DQL_EINVAL (and no launch) for whatever dql_score refuses, for a null visits, for a log of which only some arrays are given, and for n_tables >
+ * DQL_SCORE_MAP_MAX_TABLES: the map is 22 680 B per set, so 2^14 sets are 372 MB on the device and on the host; the caller slices beyond that. */
+#define DQL_SCORE_MAP_MAX_TABLES (1 << 14)
+int dql_score_map(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
+                  const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, int64_t* visits, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null,
+                  uint16_t* ep_last_cell_or_null);
 /* ---- a DoubleQLearningAgent's tables RESIDENT on the device (pkg/double_q_learning.py:32-146) ----
  * The stateless dql_agent_predict / dql_agent_update below ship all three tables (3 x 22 680 B) both ways per call — fine for a batch,
  * 6x slower than the reference's own Python for a caller that steps ONE env (BASELINE configs[0]).  A dql_agent keeps them in device
@@ -551,6 +570,11 @@ int dql_ensemble_index_faults(dql_ensemble* ens, int64_t* n); /* updates dropped
  * windows and period index. */
 int dql_ensemble_score(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
                        uint64_t seed, int32_t max_steps, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null);
+/* dql_score_map on the tables of learners [first, first + count), as dql_ensemble_score is dql_score on them: outputs and refusals as for dql_score_map (count
+ * in place of n_tables; the slice must lie inside the ensemble).  The ensemble is left exactly as it was. */
+int dql_ensemble_score_map(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
+                           uint64_t seed, int32_t max_steps, int64_t* by_code, int64_t* steps_sum, int64_t* visits, uint8_t* ep_code_or_null,
+                           uint16_t* ep_steps_or_null, uint16_t* ep_last_cell_or_null);
 
 /* ---- per-learner curriculum levels ----
  * Every learner has its own working level (it starts at the config's working_curriculum_step; dql_ensemble_set_level sets everybody's and clears the history

@@ -4,12 +4,18 @@ one learner per GPU lane (dql_multirotor_landing_amd/ensemble.py).
 
     python scripts/ensemble_training.py --learners 4096 --seed 42 [--launched] [--levels 5] [--episodes 50000] [--score ENVS] --out run.npz
                                         [--per-learner [--advance-every E] [--drop-exhausted] [--max-periods N]] [--recipes FILE.json]
-                                        [--envs-per-learner E]
+                                        [--envs-per-learner E] [--score-map] [--preset reference|paper]
 
 --launched: the parameters the reference's manager node ran with under roslaunch (config.as_launched_config) instead of the launch file's.
 --score ENVS: after the curriculum, fly every learner's tables greedily where they live (SequentialEnsemble.landing_rates: ENVS envs per learner and flavour,
 two launches), store `touchdown_rate` and `goal_hold_rate` in the .npz and print the share of learners at or above the acceptance bar of attempts.py (0.875
 touchdowns), with the figures of the reference's published tables from the same call of `evaluation.landing_rates` (same envs, seed and episodes) beside it.
+--score-map (with --score): the scoring launches also count where every learner's greedy policy flies (SequentialEnsemble.flight_maps).
+The report gains, per flavour, the quantiles over learners of `evaluation.map_report`'s columns — baseline: the reference's tables from --reference-tables flown
+by the same call, `trained_count`: the ensemble's own state_action_counter — per recipe too with --recipes, and the .npz gains `greedy_visits_simulation` and
+`greedy_visits_training` (uint32 [learners, 2835]).
+--preset paper (level-by-level driver only; default reference): train under evaluation.Q_PAPER with the paper's transfer order — on leaving level k, level k + 1
+takes level k's tables times the reference's ratio of k + 1, nothing after the last level — the "paper" preset of DESIGN.md section 17(b).
 --per-learner: every learner walks the levels by itself (ensemble.curriculum_per_learner) instead of waiting at each level for the slowest
 learner of the ensemble; a learner advances at the next period index that is a multiple of E (--advance-every, default 4096); --drop-exhausted: a learner whose
 episode budget ran out stays where it is instead of advancing as the reference's loop does.
@@ -34,8 +40,8 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from dql_multirotor_landing_amd.config import F32, F64, Q_REFERENCE, as_launched_config, training_config  # noqa: E402
 from dql_multirotor_landing_amd import evaluation  # noqa: E402
-from dql_multirotor_landing_amd.ensemble import (LevelSchedule, ORDER_PAPER, ORDER_REFERENCE, Recipe, SequentialEnsemble, TEAM_SIZES, curriculum,  # noqa: E402
-                                                 curriculum_per_learner, curriculum_recipes)
+from dql_multirotor_landing_amd.ensemble import (LevelSchedule, ORDER_PAPER, ORDER_REFERENCE, REFERENCE_RATIOS, Recipe, SequentialEnsemble, TEAM_SIZES, curriculum,  # noqa: E402
+                                                 curriculum_per_learner, curriculum_recipes, exploration_rates, min_successes_for, train_level)
 
 RECIPE_KEYS = {"preset", "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min", "levels"}
 LEVEL_KEYS = {"eps", "window", "min_successes", "max_episodes"}
@@ -82,18 +88,79 @@ def deal(n, n_recipes):
     return (np.arange(int(n)) % int(n_recipes)).astype(np.int32)
 
 
+def curriculum_paper(ens, levels, max_episodes, on_level=None):
+    """`ensemble.curriculum` with the paper's transfer order (tools/exp_teams.py's "paper" preset): -> per level, the counters at its end"""
+    history = []
+    for k in range(int(levels)):
+        if k:
+            ens.set_level(k)
+        ens.set_schedules(eps=exploration_rates(k), window=100, min_successes=min_successes_for(100), max_episodes=max_episodes)
+        flown = train_level(ens)
+        c = ens.counters()
+        history.append({"level": k, "periods": flown, "promotion_episode": c["promotion_episode"].copy(), "level_episodes": c["level_episodes"].copy()})
+        if on_level is not None:
+            on_level(ens, history[-1])
+        if k < 4:
+            ens.transfer(k + 1, REFERENCE_RATIOS[k + 1])
+    return history
+
+
 def rate_summary(x):
     x = np.asarray(x, dtype=np.float64)
     q = np.quantile(x, (0.0, 0.05, 0.25, 0.5, 0.75, 0.95, 1.0))
     return {"mean": float(x.mean()), **{k: float(v) for k, v in zip(("min", "q05", "q25", "q50", "q75", "q95", "max"), q)}}
 
 
+MAP_COLUMNS = ("decisions", "states_visited", "cells_visited", "occupancy_overlap", "disagreement_on_baseline", "disagreement_on_own", "untrained_share")
+FLAVOURS = ("simulation", "training")
+
+
+def flight_maps_sliced(ens, timing, **kw):
+    """`ens.flight_maps` of all learners, at most ops.SCORE_MAP_MAX_TABLES per call: the slices' arrays joined, the kernel times summed"""
+    from dql_multirotor_landing_amd.ops import SCORE_MAP_MAX_TABLES
+    parts, ms, inst = [], 0.0, None
+    for first in range(0, ens.n, SCORE_MAP_MAX_TABLES):
+        t = {}
+        parts.append(ens.flight_maps(first=first, count=min(SCORE_MAP_MAX_TABLES, ens.n - first), timing=t, **kw))
+        ms, inst = ms + t["kernel_ms"], t["instance"]
+    timing.update({"kernel_ms": ms, "instance": inst})
+    out = {k: np.concatenate([p[k] for p in parts]) for k in ("touchdown_rate", "goal_hold_rate", "simulation_by_code", "training_by_code", "simulation_visits", "training_visits")}
+    out["columns"] = parts[0]["columns"]
+    return out
+
+
+def map_summary(rep, pick=None):
+    """quantiles over (the picked) learners of every map_report column; a learner without a decision has NaN shares and is left out of them"""
+    out = {}
+    for col in MAP_COLUMNS:
+        x = np.asarray(rep[col], dtype=np.float64)
+        x = x if pick is None else x[pick]
+        x = x[np.isfinite(x)]
+        out[col] = None if x.size == 0 else rate_summary(x)
+    return out
+
+
+def maps_report(r, ens, a, kw):
+    """-> ({flavour: map_report of every learner}, {flavour: map_report of the reference's tables against themselves}): baseline the reference's tables flown by
+    the same call, trained_count the ensemble's own state_action_counter"""
+    ref = Path(a.reference_tables)
+    qa, qb = (np.load(ref / f).ravel().astype(np.float64) for f in ("Q_table_a.npy", "Q_table_b.npy"))
+    base = evaluation.flight_maps(qa, qb, device=a.device, **kw)
+    base_greedy = evaluation.greedy_actions(qa, qb)[0]
+    tqa, tqb, count = ens.get_tables()
+    greedy = evaluation.greedy_actions(tqa, tqb)
+    mine = {f: evaluation.map_report(r[f"{f}_visits"], greedy, base[f"{f}_visits"][0], base_greedy, trained_count=count) for f in FLAVOURS}
+    theirs = {f: evaluation.map_report(base[f"{f}_visits"], base_greedy[None], base[f"{f}_visits"][0], base_greedy) for f in FLAVOURS}
+    return mine, theirs
+
+
 def score_report(ens, a):
-    """both landing rates of every learner (resident tables, two launches) and of the reference's tables, as one JSON-able dict + the two arrays"""
+    """both landing rates of every learner (resident tables, two launches) and of the reference's tables, as one JSON-able dict + the two arrays + with
+    --score-map the maps ({"report": {flavour: map_report}, "visits": {flavour: [learners, 2835]}}), else None"""
     level = a.levels - 1
     kw = dict(n_envs=a.score, episodes=a.score_episodes, level=level, seed=a.score_seed)
     t = {}
-    r = ens.landing_rates(timing=t, **kw)
+    r = flight_maps_sliced(ens, t, **kw) if a.score_map else ens.landing_rates(timing=t, **kw)
     td, gh = r["touchdown_rate"], r["goal_hold_rate"]
     rep = {"what": "ensemble_landing_rates", "learners": int(td.size), "envs_per_learner": a.score, "episodes_per_env": a.score_episodes, "level": level,
            "levels_trained": a.levels, "episode_budget_per_level": a.episodes, "launched": bool(a.launched), "seed": a.score_seed, "bar": evaluation.LANDING_BAR, "learners_at_or_above_bar": int((td >= evaluation.LANDING_BAR).sum()),
@@ -105,7 +172,13 @@ def score_report(ens, a):
         qa, qb = (np.load(ref / f).ravel().astype(np.float64) for f in ("Q_table_a.npy", "Q_table_b.npy"))
         rr = evaluation.landing_rates(qa, qb, device=a.device, **kw)
         rep["reference_tables"] = {"touchdown_rate": float(rr["touchdown_rate"][0]), "goal_hold_rate": float(rr["goal_hold_rate"][0])}
-    return rep, td, gh
+    maps = None
+    if a.score_map:
+        mine, theirs = maps_report(r, ens, a, kw)
+        rep["maps"] = {f: map_summary(mine[f]) for f in FLAVOURS}
+        rep["reference_tables"]["maps"] = {f: {c: float(v[0]) for c, v in theirs[f].items()} for f in FLAVOURS}
+        maps = {"report": mine, "visits": {f: r[f"{f}_visits"] for f in FLAVOURS}}
+    return rep, td, gh, maps
 
 
 def per_recipe_report(names, recipe_of, td, gh, summary):
@@ -134,14 +207,23 @@ def main():
     ap.add_argument("--max-periods", type=int, default=None, help="with --per-learner or --recipes: stop after this many periods whoever is unfinished")
     ap.add_argument("--recipes", default=None, metavar="FILE.json", help="fly several recipes in one ensemble, dealt round-robin (implies --per-learner)")
     ap.add_argument("--envs-per-learner", type=int, default=1, metavar="E", help="envs per learner: 1, 2, 4, 8, 16, 32 or 64 (not with --per-learner / --recipes)")
+    ap.add_argument("--score-map", action="store_true", help="with --score: also count where every learner's greedy policy flies, and report it against the reference's tables")
+    ap.add_argument("--preset", default="reference", choices=["reference", "paper"], help="quirks and transfer order of the level-by-level driver (not with --per-learner / --recipes)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
+    if a.preset != "reference" and (a.per_learner or a.recipes):
+        ap.error("--preset belongs to the level-by-level driver: with --recipes name the preset in the recipes file")
+    if a.score_map and not a.score:
+        ap.error("--score-map needs --score ENVS: the maps are counted by the scoring launches")
+    if a.score_map and not all((Path(a.reference_tables) / f).exists() for f in ("Q_table_a.npy", "Q_table_b.npy")):
+        ap.error("--score-map needs the baseline's tables: --reference-tables has no Q_table_a.npy / Q_table_b.npy")
     if a.envs_per_learner not in TEAM_SIZES:
         ap.error(f"--envs-per-learner must be one of {', '.join(map(str, TEAM_SIZES))}")
     if a.envs_per_learner > 1 and (a.per_learner or a.recipes):
         ap.error("--envs-per-learner above 1 cannot be combined with --per-learner or --recipes: teams fly the level-by-level (barrier) driver only")
     dtype = F64 if a.f64 else F32
-    cfg = as_launched_config(dtype=dtype, quirks=Q_REFERENCE) if a.launched else training_config(0, dtype=dtype, quirks=Q_REFERENCE)
+    quirks = evaluation.Q_PAPER if a.preset == "paper" else Q_REFERENCE
+    cfg = as_launched_config(dtype=dtype, quirks=quirks) if a.launched else training_config(0, dtype=dtype, quirks=quirks)
     ens = SequentialEnsemble(cfg, a.learners, seed=a.seed, device=a.device, max_episodes=a.episodes, envs_per_learner=a.envs_per_learner)
     try:
         def report(e, h):
@@ -166,13 +248,19 @@ def main():
             hist = [{"promotion_episode": h["promoted_at"][k], "periods": h["periods"]} for k in range(a.levels)]
             extra = {"level": h["level"], "episodes_at": h["episodes_at"], "entered_period": h["entered_period"]}
         else:
-            hist = curriculum(ens, levels=a.levels, max_episodes=a.episodes, on_level=report)
+            hist = (curriculum_paper(ens, a.levels, a.episodes, on_level=report) if a.preset == "paper" else
+                    curriculum(ens, levels=a.levels, max_episodes=a.episodes, on_level=report))
         if a.score:
-            rep, td, gh = score_report(ens, a)
+            rep, td, gh, maps = score_report(ens, a)
             extra.update({"touchdown_rate": td, "goal_hold_rate": gh})
             if names is not None:
                 rep["recipes"] = per_recipe_report(names, recipe_of, td, gh, ens.recipe_summary())
                 rep.update({"periods": int(h["periods"]), "unfinished": ens.n_unfinished()})
+                if maps is not None:
+                    for r, entry in enumerate(rep["recipes"]):
+                        entry["maps"] = {f: map_summary(maps["report"][f], recipe_of == r) for f in FLAVOURS}
+            if maps is not None:
+                extra.update({f"greedy_visits_{f}": maps["visits"][f].astype(np.uint32) for f in FLAVOURS})
             print(json.dumps(rep), flush=True)
             ref = rep["reference_tables"]
             print(f"{rep['learners_at_or_above_bar']} of {rep['learners']} learners ({100.0 * rep['share_at_or_above_bar']:.1f} %) reach a touchdown rate of "

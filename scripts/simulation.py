@@ -3,11 +3,13 @@
 pair of Q tables in the vectorised simulator and reports how the episodes end.
 
     python scripts/simulation.py [--tables DIR] [--envs 4096] [--level 4] [--flavour simulation|training] [--mode paper|reference]
-                                 [--rollout] [--report] [--trace-out FILE.npz [--trace-envs 8]]
+                                 [--rollout] [--report] [--trace-out FILE.npz [--trace-envs 8]] [--map-out FILE.npz [--map-episodes 1]]
 Default tables: tests/golden/assets (a data copy of the reference's stage-4 policy).
 --rollout flies all first episodes in one launch (dql_rollout) instead of one launch per agent period; --report prints what the episodes looked like at
 their end (the counterpart of the `info` dictionary the reference prints per episode, scripts/simulation.py:52-56) and --trace-out saves the per-period
 flight record of the first envs; both imply --rollout.
+--map-out writes where the tables' greedy policy flies (dql_score_map): `visits` [2835], the decisions counted by cell, and
+`last_cell_by_code` [codes, 2835], the histogram of the x cell of each finished episode's last decision by terminal code, with `by_code` and `columns`.
 """
 import argparse
 import json
@@ -33,6 +35,19 @@ def evaluate_records(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, 
     return rollout_records([agent._padded()], n_envs, level, max_steps, seed, dtype, flavour, device, trace_envs=trace_envs, **cfg_kw)
 
 
+def evaluate_map(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, episodes=1, **cfg_kw):
+    """The map of the same greedy flights and the last-cell histogram by terminal code, from one launch of the mapping scorer."""
+    import numpy as np
+    from dql_multirotor_landing_amd import evaluation, ops
+    from dql_multirotor_landing_amd.config import CHECK_NAMES
+    from dql_multirotor_landing_amd.double_q_learning import DoubleQLearningAgent
+    qa, qb, _ = DoubleQLearningAgent.load(Path(tables_dir))._padded()
+    cfg = evaluation._flavour_config(flavour, level, dtype, cfg_kw)
+    r = ops.score_map(cfg, qa, qb, n_envs, seed, episodes=episodes, max_steps=max_steps, log=True, device=device)
+    by_code = np.stack([evaluation.failure_origins(r["ep_code"], r["ep_last_cell"], [k], 1)[0] for k in range(len(CHECK_NAMES))])
+    return {"visits": r["visits"][0], "last_cell_by_code": by_code, "by_code": r["by_code"][0], "columns": np.array(r["columns"]), "steps_sum": r["steps_sum"][0]}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--tables", default=str(Path(__file__).resolve().parent.parent / "tests" / "golden" / "assets"))
@@ -46,6 +61,8 @@ if __name__ == "__main__":
     ap.add_argument("--report", action="store_true", help="print episode_report: length, return and touchdown quantiles of the first episodes (implies --rollout)")
     ap.add_argument("--trace-out", default=None, metavar="FILE.npz", help="save the per-period trace of the first --trace-envs envs with its field names (implies --rollout)")
     ap.add_argument("--trace-envs", type=int, default=8)
+    ap.add_argument("--map-out", default=None, metavar="FILE.npz", help="save the map of the greedy flights and the last-cell histogram by terminal code (dql_score_map)")
+    ap.add_argument("--map-episodes", type=int, default=1, help="episodes per env of the --map-out launch")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build_hip()
@@ -68,5 +85,11 @@ if __name__ == "__main__":
     else:
         h = evaluate(a.tables, n, a.level, flavour=a.flavour, method="rollout" if a.rollout else "stepwise", quirks=quirks)
         out["method"] = "rollout" if a.rollout else "stepwise"
+    if a.map_out:
+        import numpy as np
+        m = evaluate_map(a.tables, n, a.level, flavour=a.flavour, episodes=a.map_episodes, quirks=quirks)
+        np.savez_compressed(a.map_out, **m)
+        out["map"] = {"file": a.map_out, "episodes_per_env": a.map_episodes, "decisions": int(m["visits"].sum()), "cells_visited": int((m["visits"] > 0).sum()),
+                      "busiest_cell": int(m["visits"].argmax()), "busiest_cell_visits": int(m["visits"].max())}
     out.update({"first_episode_outcomes": h, "touchdown_rate": h["TERMINAL_CONTACT"] / n, "goal_rate": h["TERMINAL_SUCCESS"] / n})
     print(json.dumps(out, indent=1))
