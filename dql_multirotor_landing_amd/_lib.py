@@ -119,6 +119,10 @@ SYMBOLS = {
     "dql_score_map": (C.c_int, [_cfgp, C.c_int, _i64, _i64, _i32, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dql_diag_score_map_last": (C.c_int, [C.POINTER(_dbl), _vp]),
     "dql_diag_selftest_sqrt": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_i64)]),
+    "dql_diag_selftest_sqrt_ieee": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_i64)]),
+    "dql_diag_det_math_run": (C.c_int, [C.c_int, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "dql_diag_box_muller_run": (C.c_int, [C.c_int, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "dql_diag_philox_run": (C.c_int, [C.c_int, _vp, C.c_uint32, C.c_uint32, _i32, _i64, _vp]),
     "dql_place": (C.c_int, [_cfgp, C.c_int, _vp, _vp, _i64, _vp]),
     "dql_agent_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "dql_agent_destroy": (C.c_int, [_vp]),

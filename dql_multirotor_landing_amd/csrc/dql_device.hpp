@@ -102,9 +102,12 @@ namespace dql {
 // ---------------------------------------------------------------------------------------------
 DQL_DEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 DQL_DEV double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
-// Correctly rounded sqrt for x = 0 or normal x (the only inputs this kernel produces): hardware v_sqrt_f32 (<= 1 ulp) plus the
+// Correctly rounded sqrt for x = 0 or x >= 2^-102: hardware v_sqrt_f32 (<= 1 ulp) plus the
 // neighbour test LLVM's own expansion uses, without its denormal rescaling and inf/nan class test (9 instead of 18
 // instructions; x = 0 falls through: the lower neighbour is NaN and the upper one gives fma(-tiny, 0, 0) = -0, both compares false).
+// EXHAUSTIVELY verified on gfx950 against (float)sqrt((double)x) (dql_diag_selftest_sqrt_ieee, tests/test_gpu_det_math.py): 0 misrounded from 2^-104 to FLT_MAX
+// and at 0; below 2^-104 the neighbour residuals go subnormal and 3 954 656 normal inputs misround (largest 0x0b6e9372) — the same floor as sqrt_pos.  Its one
+// float32 call site is Box-Muller's radius, whose argument -2 log(u24p) is 0 or lies in [1.19e-7, 33.3] (every one of the 2^24 is run by the same test).
 DQL_DEV float sqrt_(float x) {
   float y = __builtin_amdgcn_sqrtf(x);
   const float ym = __uint_as_float(__float_as_uint(y) - 1u), yp = __uint_as_float(__float_as_uint(y) + 1u);
@@ -170,6 +173,9 @@ template <typename T> struct Pio2;
 template <> struct Pio2<float> { static constexpr float hi = 1.5703125f, lo = 4.8382679489661923e-4f; };
 template <> struct Pio2<double> { static constexpr double hi = 1.57079632673412561417e+00, lo = 6.07710050650619224932e-11; };
 
+// Verified domain (tests/det_math_checks.py through dql_diag_det_math_run, device == oracle bit for bit and both against numpy): float32 on ALL 2^24 Box-Muller
+// angles float32(2 pi) k 2^-24, float64 on 2^20 of them, the set-point range [-0.6, 0.6] and |x| <= 50 (the platform's phase step is the one argument not
+// bounded by 2 pi): absolute error <= 2e-7 / 3e-16 against the function of the same-dtype argument.  Two-constant Cody-Waite reduction: not for |x| >> 50.
 template <typename T> DQL_DEV void det_sincos(T x, T& s, T& c) {
   const T fn = rint_(x * T(6.36619772367581382433e-01));
   const int n = (int)fn;
@@ -212,6 +218,10 @@ template <typename T> DQL_DEV T det_atan(T x) {
   else r = hi - ((x * (s1 + s2) - lo) - x);
   return neg ? -r : r;
 }
+// Contract: x == 0 (either sign) gives 0 for y == +-0 — NOT pi for (+0, -0) — and +-pi/2 otherwise; a zero y is read as +0 (+0 in front of the axis, +pi
+// behind it).  Verified domain (tests/det_math_checks.py): 2^20 normal pairs, absolute error <= 5e-7 / 5e-16, and constructed waves of 64 in which 0, 1, 2, 32,
+// 63 or 64 lanes fail the float32 fast-path predicate below (x < 0, x = +-0, |y / x| on and beside each range bound of det_atan, 1e-30, 1e30, y = -0), placed
+// first or last: every lane equals the oracle and its own value in any other wave.
 template <typename T> DQL_DEV T det_atan2(T y, T x) {
   const T pi = T(3.14159265358979311600e+00), pio2 = T(1.57079632679489655800e+00);
   if constexpr (sizeof(T) == 4) {
@@ -245,6 +255,8 @@ DQL_DEV void split_exp(double x, int& k, double& m) {
   k = (int)(b >> 52) - 1023;
   m = __longlong_as_double((long long)((b & 0x000fffffffffffffull) | 0x3ff0000000000000ull));
 }
+// Verified domain (tests/det_math_checks.py): float32 on ALL 2^24 values u24p can take (k 2^-24, k = 1 .. 2^24), float64 on 2^20 of them: relative error
+// <= 2e-7 / 4e-16, never positive, never non-finite, 0 only at x = 1 — so Box-Muller's radius sqrt_(-2 log u) is finite and real for every draw.
 template <typename T> DQL_DEV T det_log(T x) {  // x in (0, 1], normal
   int k; T m;
   split_exp(x, k, m);

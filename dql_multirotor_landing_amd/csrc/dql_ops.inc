@@ -1,4 +1,5 @@
-// dql_ops.inc: the stateless drop-in operators (include/dql.h dql_discretise .. dql_place, dql_diag_selftest_sqrt): their kernels and their C calls.
+// dql_ops.inc: the stateless drop-in operators (include/dql.h dql_discretise .. dql_place; include/dql_diag.h dql_diag_selftest_sqrt[_ieee], dql_diag_det_math_run,
+// dql_diag_box_muller_run, dql_diag_philox_run): their kernels and their C calls.
 // A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype, DevBuf / OP_PROLOGUE / UP / OUT / DOWN, check_config; and
 // dql_device.hpp, dql_host_consts.hpp.  Every call: argument checks (before the device is touched), uploads, one launch, downloads.
 template <typename T> __global__ void k_discretise(MdpK<T> c, const double* p, const double* v, const double* acc, const double* ang, long long n, int* out) {
@@ -143,19 +144,81 @@ template <typename T> __global__ void k_platform_run(SimK<T> s, long long n, int
     out[i * 4] = (double)e.mp_x; out[i * 4 + 1] = (double)e.mp_y; out[i * 4 + 2] = (double)e.mp_u; out[i * 4 + 3] = (double)e.mp_v;
   }
 }
-// exhaustive self-test of sqrt_pos (dql_diag_selftest_sqrt): inputs with bit patterns lo .. hi against (float)sqrt((double)x)
-__global__ void k_selftest_sqrt(unsigned lo, unsigned hi, unsigned long long* bad) {
+// exhaustive self-test of sqrt_pos (dql_diag_selftest_sqrt) or, IEEE, of sqrt_(float) (dql_diag_selftest_sqrt_ieee): inputs with bit patterns lo .. hi
+// against (float)sqrt((double)x)
+template <bool IEEE> __global__ void k_selftest_sqrt(unsigned lo, unsigned hi, unsigned long long* bad) {
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
   unsigned long long n = 0;
   for (unsigned long long b = lo + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; b <= hi; b += stride) {
     const float x = __uint_as_float((unsigned)b);
-    if (__float_as_uint(sqrt_pos(x)) != __float_as_uint((float)__builtin_sqrt((double)x))) ++n;
+    const float y = IEEE ? sqrt_(x) : sqrt_pos(x);
+    if (__float_as_uint(y) != __float_as_uint((float)__builtin_sqrt((double)x))) ++n;
   }
   if (n) atomicAdd(bad, n);
+}
+// ---- the elementary functions and random draws of dql_device.hpp on the caller's inputs (dql_diag_det_math_run, dql_diag_box_muller_run, dql_diag_philox_run):
+// thread i computes element i in blocks of DIAG_BLOCK (a multiple of 64), so elements 64 w .. 64 w + 63 share a wave — the float32 det_atan2 branches on a
+// ballot over it.  Lanes past n leave before the first call ----
+constexpr int DIAG_BLOCK = 256;
+template <typename T> __global__ void k_det_math(const double* x, const double* y, long long n, double* s, double* c, double* at2, double* lg) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const T xv = (T)x[i], yv = (T)y[i];
+  T ss, cc;
+  det_sincos(xv, ss, cc);
+  s[i] = (double)ss; c[i] = (double)cc;
+  at2[i] = (double)det_atan2(yv, xv);
+  const T ax = abs_(xv);
+  lg[i] = (double)det_log(ax > T(1e-30) ? ax : T(1.0));
+}
+template <typename T> __global__ void k_box_muller(const uint32_t* ra, const uint32_t* rb, long long n, double* n0, double* n1) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  T a, b;
+  box_muller<T>(ra[i], rb[i], a, b);
+  n0[i] = (double)a; n1[i] = (double)b;
+}
+// KEYS: the 20 round keys in VGPRs, filled as k_step fills them from its seed
+template <bool KEYS> __global__ void k_philox(const uint4* ctr, uint32_t k0, uint32_t k1, long long n, uint4* out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t kv_[20];
+  const uint32_t* kv = nullptr;
+  if constexpr (KEYS) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr(k0 + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr(k1 + (uint32_t)r * 0xBB67AE85u); }
+    kv = kv_;
+  }
+  if (i >= n) return;
+  const uint4 c = ctr[i];
+  uint32_t r[4];
+  philox4x32(c.x, c.y, c.z, c.w, k0, k1, r, kv);
+  out[i] = make_uint4(r[0], r[1], r[2], r[3]);
 }
 template <typename T> __global__ void k_place(int init_mode, T p_max, const double* x0, const double* mp, long long n, double* out) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = (double)place_axis(init_mode, (T)x0[i], (T)mp[i], p_max);
+}
+
+// shared by the C calls below (templates cannot live inside extern "C")
+template <bool IEEE> static int selftest_sqrt(int device, uint32_t lo_bits, uint32_t hi_bits, int64_t* not_correctly_rounded) {
+  if (!not_correctly_rounded) return fail(DQL_EINVAL, "null pointer");
+  if (lo_bits > hi_bits || hi_bits > 0x7f7fffffu) return fail(DQL_EINVAL, "bit patterns must satisfy lo <= hi <= 0x7f7fffff (largest finite float32)");
+  OP_PROLOGUE(device)
+  DevBuf b;
+  OUT(b, sizeof(unsigned long long));
+  HIP_TRY(hipMemset(b.p, 0, sizeof(unsigned long long)));
+  hipLaunchKernelGGL(k_selftest_sqrt<IEEE>, dim3(256 * 32), dim3(256), 0, 0, (unsigned)lo_bits, (unsigned)hi_bits, (unsigned long long*)b.p);
+  HIP_TRY(hipGetLastError());
+  unsigned long long n = 0;
+  DOWN(&n, b, sizeof(n));
+  *not_correctly_rounded = (int64_t)n;
+  return DQL_OK;
+}
+static int diag_check_n(int32_t dtype, int64_t n, bool any_null) {
+  if (dtype != DQL_F32 && dtype != DQL_F64) return fail(DQL_EINVAL, "dtype must be DQL_F32 or DQL_F64");
+  if (n < 0 || n > DQL_DIAG_MAX_N) return fail(DQL_EINVAL, "n must be in 0 .. DQL_DIAG_MAX_N (2^24) per call");
+  if (n > 0 && any_null) return fail(DQL_EINVAL, "null array");
+  return DQL_OK;
 }
 
 extern "C" {
@@ -314,17 +377,52 @@ int dql_platform_run(const dql_config* cfg, int device, int64_t n, int32_t carry
 }
 
 int dql_diag_selftest_sqrt(int device, uint32_t lo_bits, uint32_t hi_bits, int64_t* not_correctly_rounded) {
-  if (!not_correctly_rounded) return fail(DQL_EINVAL, "null pointer");
-  if (lo_bits > hi_bits || hi_bits > 0x7f7fffffu) return fail(DQL_EINVAL, "bit patterns must satisfy lo <= hi <= 0x7f7fffff (largest finite float32)");
+  return selftest_sqrt<false>(device, lo_bits, hi_bits, not_correctly_rounded);
+}
+int dql_diag_selftest_sqrt_ieee(int device, uint32_t lo_bits, uint32_t hi_bits, int64_t* not_correctly_rounded) {
+  return selftest_sqrt<true>(device, lo_bits, hi_bits, not_correctly_rounded);
+}
+
+int dql_diag_det_math_run(int device, int32_t dtype, const double* x, const double* y, int64_t n, double* sin_out, double* cos_out, double* atan2_out, double* log_out) {
+  int rc = diag_check_n(dtype, n, !x || !y || !sin_out || !cos_out || !atan2_out || !log_out); if (rc) return rc;
   OP_PROLOGUE(device)
-  DevBuf b;
-  OUT(b, sizeof(unsigned long long));
-  HIP_TRY(hipMemset(b.p, 0, sizeof(unsigned long long)));
-  hipLaunchKernelGGL(k_selftest_sqrt, dim3(256 * 32), dim3(256), 0, 0, (unsigned)lo_bits, (unsigned)hi_bits, (unsigned long long*)b.p);
+  if (n == 0) return DQL_OK;
+  DevBuf a, b, s, c, t, l;
+  const size_t B = (size_t)n * sizeof(double);
+  UP(a, x, B); UP(b, y, B);
+  OUT(s, B); OUT(c, B); OUT(t, B); OUT(l, B);
+  const unsigned grid = (unsigned)((n + DIAG_BLOCK - 1) / DIAG_BLOCK);
+  by_dtype(dtype, [&](auto ty) { using T = decltype(ty); hipLaunchKernelGGL(k_det_math<T>, dim3(grid), dim3(DIAG_BLOCK), 0, 0, (const double*)a.p, (const double*)b.p, (long long)n, (double*)s.p, (double*)c.p, (double*)t.p, (double*)l.p); });
   HIP_TRY(hipGetLastError());
-  unsigned long long n = 0;
-  DOWN(&n, b, sizeof(n));
-  *not_correctly_rounded = (int64_t)n;
+  DOWN(sin_out, s, B); DOWN(cos_out, c, B); DOWN(atan2_out, t, B); DOWN(log_out, l, B);
+  return DQL_OK;
+}
+int dql_diag_box_muller_run(int device, int32_t dtype, const uint32_t* ra, const uint32_t* rb, int64_t n, double* n0_out, double* n1_out) {
+  int rc = diag_check_n(dtype, n, !ra || !rb || !n0_out || !n1_out); if (rc) return rc;
+  OP_PROLOGUE(device)
+  if (n == 0) return DQL_OK;
+  DevBuf a, b, o0, o1;
+  UP(a, ra, (size_t)n * sizeof(uint32_t)); UP(b, rb, (size_t)n * sizeof(uint32_t));
+  OUT(o0, (size_t)n * sizeof(double)); OUT(o1, (size_t)n * sizeof(double));
+  const unsigned grid = (unsigned)((n + DIAG_BLOCK - 1) / DIAG_BLOCK);
+  by_dtype(dtype, [&](auto ty) { using T = decltype(ty); hipLaunchKernelGGL(k_box_muller<T>, dim3(grid), dim3(DIAG_BLOCK), 0, 0, (const uint32_t*)a.p, (const uint32_t*)b.p, (long long)n, (double*)o0.p, (double*)o1.p); });
+  HIP_TRY(hipGetLastError());
+  DOWN(n0_out, o0, (size_t)n * sizeof(double)); DOWN(n1_out, o1, (size_t)n * sizeof(double));
+  return DQL_OK;
+}
+int dql_diag_philox_run(int device, const uint32_t* counters, uint32_t k0, uint32_t k1, int32_t round_keys, int64_t n, uint32_t* out) {
+  int rc = diag_check_n(DQL_F32, n, !counters || !out); if (rc) return rc;
+  if (round_keys != 0 && round_keys != 1) return fail(DQL_EINVAL, "round_keys must be 0 (inline key schedule) or 1 (round keys in registers)");
+  OP_PROLOGUE(device)
+  if (n == 0) return DQL_OK;
+  DevBuf a, o;
+  UP(a, counters, (size_t)n * 4 * sizeof(uint32_t));
+  OUT(o, (size_t)n * 4 * sizeof(uint32_t));
+  const unsigned grid = (unsigned)((n + DIAG_BLOCK - 1) / DIAG_BLOCK);
+  if (round_keys) hipLaunchKernelGGL(k_philox<true>, dim3(grid), dim3(DIAG_BLOCK), 0, 0, (const uint4*)a.p, k0, k1, (long long)n, (uint4*)o.p);
+  else hipLaunchKernelGGL(k_philox<false>, dim3(grid), dim3(DIAG_BLOCK), 0, 0, (const uint4*)a.p, k0, k1, (long long)n, (uint4*)o.p);
+  HIP_TRY(hipGetLastError());
+  DOWN(out, o, (size_t)n * 4 * sizeof(uint32_t));
   return DQL_OK;
 }
 

@@ -135,6 +135,48 @@ def selftest_sqrt(lo: float = 1e-30, hi: float = 3.4028234663852886e38, device: 
     return n.value
 
 
+def selftest_sqrt_ieee(lo: float = 2.0 ** -102, hi: float = 3.4028234663852886e38, device: int = 0) -> int:
+    """the same count for sqrt_(float), the square root of Box-Muller's radius: 0 at x = 0 and on its domain [2^-102, FLT_MAX]"""
+    lo_b = int(np.float32(lo).view(np.uint32)); hi_b = int(np.float32(hi).view(np.uint32))
+    n = C.c_int64(-1)
+    _lib.check(_lib.load().dql_diag_selftest_sqrt_ieee(device, lo_b, hi_b, C.byref(n)))
+    return n.value
+
+
+DIAG_MAX_N = 1 << 24  # include/dql_diag.h DQL_DIAG_MAX_N
+
+
+def det_math_run(x, y, dtype: int, device: int = 0):
+    """The device's det_sincos / det_atan2 / det_log on chosen inputs in float32 (dtype 0) or float64 (1) arithmetic -> (sin x, cos x, atan2(y, x),
+    log |x| or log 1 where |x| <= 1e-30) as float64.  Element i runs on thread i: elements 64 w .. 64 w + 63 share a wave (include/dql_diag.h)."""
+    x, y = _f64(x), _f64(y)
+    if x.ndim != 1 or x.shape != y.shape:
+        raise ValueError("x and y must be 1-D arrays of equal length")
+    s = np.zeros_like(x); c = np.zeros_like(x); a = np.zeros_like(x); lg = np.zeros_like(x)
+    _lib.check(_lib.load().dql_diag_det_math_run(device, int(dtype), _p(x), _p(y), len(x), _p(s), _p(c), _p(a), _p(lg)))
+    return s, c, a, lg
+
+
+def box_muller_run(ra, rb, dtype: int, device: int = 0):
+    """The device's box_muller on raw 32-bit words -> the two normal deviates (n0, n1) as float64."""
+    ra = np.ascontiguousarray(ra, dtype=np.uint32); rb = np.ascontiguousarray(rb, dtype=np.uint32)
+    if ra.ndim != 1 or ra.shape != rb.shape:
+        raise ValueError("ra and rb must be 1-D arrays of equal length")
+    n0 = np.zeros(len(ra)); n1 = np.zeros(len(ra))
+    _lib.check(_lib.load().dql_diag_box_muller_run(device, int(dtype), _p(ra), _p(rb), len(ra), _p(n0), _p(n1)))
+    return n0, n1
+
+
+def philox_run(counters, k0: int, k1: int, round_keys: int = 0, device: int = 0) -> np.ndarray:
+    """The device's philox4x32 of counters [n][4] under the key (k0, k1) -> uint32 [n][4]; round_keys = 1: the form with the 20 round keys in registers."""
+    ctr = np.ascontiguousarray(counters, dtype=np.uint32)
+    if ctr.ndim != 2 or ctr.shape[1] != 4:
+        raise ValueError("counters must be [n][4]")
+    out = np.zeros_like(ctr)
+    _lib.check(_lib.load().dql_diag_philox_run(device, _p(ctr), int(k0), int(k1), int(round_keys), len(ctr), _p(out)))
+    return out
+
+
 def place(cfg: DqlConfig, x0, mp, device: int = 0) -> np.ndarray:
     """Drone start coordinate for (random offset, platform coordinate) pairs: the reset placement selected by cfg.init_uniform."""
     x0, mp = _f64(x0), _f64(mp)

@@ -53,6 +53,26 @@ int dql_diag_ensemble_launches(dql_ensemble* ens, int64_t* launches, int64_t* pe
  * patterns lo_bits .. hi_bits whose result is NOT the correctly rounded sqrt.  The CPU oracle computes sqrtf(); parity is bit for bit only while
  * this count is 0 on the tick's domain [1e-30, FLT_MAX] — all 2.1e9 inputs take under a second. */
 int dql_diag_selftest_sqrt(int device, uint32_t lo_bits, uint32_t hi_bits, int64_t* not_correctly_rounded);
+/* The same count for sqrt_(float) (v_sqrt_f32 + a neighbour test: Box-Muller's radius, the float64-form attitude law), against (float)sqrt((double)x).
+ * The CPU oracle's sqrtf() is the definition: the count is 0 at x = 0 and on sqrt_'s domain [2^-102, FLT_MAX]; the normal inputs below 2^-104 are outside it
+ * (3 954 656 of them misround) and Box-Muller never produces one. */
+int dql_diag_selftest_sqrt_ieee(int device, uint32_t lo_bits, uint32_t hi_bits, int64_t* not_correctly_rounded);
+
+/* ---- the elementary functions and random draws at the top of csrc/dql_device.hpp, evaluated on inputs of the caller's choosing ----
+ * The kernels call det_sincos / det_atan2 / det_log / box_muller / philox4x32 themselves and restate nothing.  dtype: DQL_F32 (0) or DQL_F64 (1), the
+ * arithmetic the function runs in; values travel as float64 (every float32 is one) and 32-bit words.  1 <= n <= DQL_DIAG_MAX_N per call (n = 0: nothing to do).
+ *
+ * WAVE LAYOUT: element i is computed by thread i of a one-dimensional grid of 256-thread blocks, so elements 64 w .. 64 w + 63 share wave w and the caller
+ * decides which inputs meet in a wave (lanes past n have left before the first function is called).  The float32 det_atan2 branches on a ballot over the wave;
+ * the tests construct waves in which some lanes pass its fast-path predicate and others do not. */
+#define DQL_DIAG_MAX_N (1ll << 24)
+/* element i: sin and cos of x[i], atan2(y[i], x[i]), and log of |x[i]| where |x[i]| > 1e-30, else of 1 */
+int dql_diag_det_math_run(int device, int32_t dtype, const double* x, const double* y, int64_t n, double* sin_out, double* cos_out, double* atan2_out, double* log_out);
+/* element i: the two normal deviates box_muller makes of the raw words ra[i], rb[i] (radius from ra's upper 24 bits, angle from rb's) */
+int dql_diag_box_muller_run(int device, int32_t dtype, const uint32_t* ra, const uint32_t* rb, int64_t n, double* n0_out, double* n1_out);
+/* philox4x32-10 of counters [n][4] under the key (k0, k1) -> out [n][4].  round_keys = 0: the key schedule computed inline; 1: the 20 round keys preloaded
+ * into registers and passed as philox4x32's kv, filled the way the step kernel fills them */
+int dql_diag_philox_run(int device, const uint32_t* counters, uint32_t k0, uint32_t k1, int32_t round_keys, int64_t n, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -1279,10 +1279,18 @@ EXPORT void ORC(det_math)(const double* x, const double* y, int64_t n, double* s
     lg[i] = det_log((REAL)(FABS((REAL)x[i]) > R_(1e-30) ? FABS((REAL)x[i]) : R_(1.0)));
   }
 }
+/* box_muller on raw 32-bit words (only their upper 24 bits count): the two normal deviates of every (ra, rb) pair */
+EXPORT void ORC(box_muller)(const uint32_t* ra, const uint32_t* rb, int64_t n, double* n0, double* n1) {
+  for (int64_t i = 0; i < n; ++i) { REAL a, b; box_muller(ra[i], rb[i], &a, &b); n0[i] = a; n1[i] = b; }
+}
 
 #if !ORACLE_F32
 /* ---- precision-independent pieces, emitted once ---- */
 EXPORT void orc_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) { philox4x32(c0, c1, c2, c3, k0, k1, out); }
+/* the array form: n counters [n][4], one key per counter [n][2] -> [n][4] */
+EXPORT void orc_philox_n(const uint32_t* ctr, const uint32_t* key, int64_t n, uint32_t* out) {
+  for (int64_t i = 0; i < n; ++i) philox4x32(ctr[i * 4], ctr[i * 4 + 1], ctr[i * 4 + 2], ctr[i * 4 + 3], key[i * 2], key[i * 2 + 1], out + i * 4);
+}
 EXPORT void orc_agent_predict(const double* qa, const double* qb, const int32_t* idx, int64_t n, uint8_t* out) {
   for (int64_t i = 0; i < n; ++i) out[i] = (uint8_t)agent_predict(qa, qb, idx[i]);
 }

@@ -380,6 +380,23 @@ def det_math(x, y, dtype=1):
     return s, c, a, lg
 
 
+def box_muller(ra, rb, dtype=1):
+    """the two normal deviates box_muller makes of every pair of raw 32-bit words -> (n0, n1) as float64"""
+    ra = np.ascontiguousarray(ra, dtype=np.uint32); rb = np.ascontiguousarray(rb, dtype=np.uint32)
+    n0 = np.zeros(len(ra)); n1 = np.zeros(len(ra))
+    _run("box_muller", dtype, _p(ra), _p(rb), C.c_int64(len(ra)), _p(n0), _p(n1))
+    return n0, n1
+
+
+def philox_n(counters, keys):
+    """philox4x32-10 of counters [n][4] under keys [n][2] (or one key for all) -> uint32 [n][4]"""
+    ctr = np.ascontiguousarray(counters, dtype=np.uint32)
+    key = np.ascontiguousarray(np.broadcast_to(np.asarray(keys, dtype=np.uint32), (len(ctr), 2)))
+    out = np.zeros((len(ctr), 4), dtype=np.uint32)
+    lib().orc_philox_n(_p(ctr), _p(key), C.c_int64(len(ctr)), _p(out))
+    return out
+
+
 def manager_run(cfg: DqlConfig, series, contact, seed=0, dtype=None):
     """one series [n_ticks][14] -> [n_ticks][12] (see dql_oracle.c manager_run)"""
     a = _f64(series); c = np.ascontiguousarray(contact, dtype=np.uint8)

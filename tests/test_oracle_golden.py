@@ -165,25 +165,6 @@ def test_g11_platform(golden_dir):
     np.testing.assert_allclose(out, g["eight"][:, 1:], rtol=0, atol=2e-11)
 
 
-def test_det_math_accuracy():
-    rng = np.random.default_rng(1)
-    x = np.concatenate([rng.uniform(-7, 7, 4000), [0.0, 1e-9, np.pi / 2, np.pi, 2 * np.pi - 1e-12]])
-    y = rng.uniform(-3, 3, len(x))
-    s, c, a, lg = orc.det_math(x, y, dtype=1)
-    np.testing.assert_allclose(s, np.sin(x), rtol=0, atol=3e-16)
-    np.testing.assert_allclose(c, np.cos(x), rtol=0, atol=3e-16)
-    np.testing.assert_allclose(a, np.arctan2(y, x), rtol=0, atol=5e-16)
-    m = np.abs(x) > 1e-30
-    np.testing.assert_allclose(lg[m], np.log(np.abs(x[m])), rtol=4e-16, atol=5e-16)
-    s, c, a, lg = orc.det_math(x, y, dtype=0)
-    x32 = x.astype(np.float32).astype(np.float64); y32 = y.astype(np.float32).astype(np.float64)
-    np.testing.assert_allclose(s, np.sin(x32), rtol=0, atol=2e-7)
-    np.testing.assert_allclose(c, np.cos(x32), rtol=0, atol=2e-7)
-    np.testing.assert_allclose(a, np.arctan2(y32, x32), rtol=0, atol=5e-7)
-    m = np.abs(x32) > 1e-30
-    np.testing.assert_allclose(lg[m], np.log(np.abs(x32[m])), rtol=2e-7, atol=1e-6)
-
-
 def test_philox_known_answer():
     """Random123 known-answer vectors for philox4x32-10."""
     np.testing.assert_array_equal(orc.philox((0, 0, 0, 0), (0, 0)), [0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8])
