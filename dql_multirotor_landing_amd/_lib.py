@@ -63,6 +63,7 @@ SYMBOLS = {
     "dql_set_windowed": (C.c_int, [_vp, _i32]),
     "dql_diag_accum_dev_ptr": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "dql_diag_step_instance": (C.c_int, [_vp, _vp]),
+    "dql_diag_step_level0": (C.c_int, [_vp, _vp]),
     "dql_set_window_buffer": (C.c_int, [_vp, _vp]),
     "dql_stream_handle": (C.c_int, [_vp, C.POINTER(_vp)]),
     "dql_flush": (C.c_int, [_vp]),

@@ -1512,7 +1512,11 @@ template <int TICK, typename T> struct TickConsts {
 // (roll set-point exactly 0: attitude()'s xonly form, and the y-axis state is dead code — the caller passes a SimK whose two_axis is the
 // constant 0); X_RUNTIME: decided by s.two_axis (wave-uniform), both forms in the code — the layouts the host does not pick by itself.
 enum { X_TWO = 0, X_ONLY = 1, X_RUNTIME = 2 };
-template <int TICK, int XMODE, typename T, typename TabPtr>
+// LEVEL0: the launch runs at curriculum level 0 and the kernel knows it at compile time (k_step's level-0 instances; the host picks them per launch from the
+// engine's current level, never when working != 0).  `working` is then the constant 0 wherever the period's begin and end read it — the reset placement's
+// level test, discretise_impl's three level searches (n = 1: the answer is 0) and the select chains on the level that follow them, mdp_check, mdp_reward —
+// instead of a scalar the pin below hides from the optimiser.  The same values by construction; every other instance keeps the generic body.
+template <int TICK, int XMODE, bool LEVEL0 = false, typename T, typename TabPtr>
 DQL_DEV StepOut agent_period(const SimK<T>& s_in, const TickConsts<TICK, T>& tc, const MdpK<T> DQL_CONST_AS* mp, const MdpRun<T>& mr, Env<T>& e, const QRow& qx, TabPtr qa, TabPtr qb, int mode, uint32_t eps_thr,
                              int ext_action, uint64_t seed, uint32_t env_id, long long step_index, long long mgr0, int sched, const uint32_t* kv = nullptr) {
   SimK<T> s = s_in;
@@ -1520,8 +1524,11 @@ DQL_DEV StepOut agent_period(const SimK<T>& s_in, const TickConsts<TICK, T>& tc,
   // the period loop and keeps it as a 64-bit lane mask — a dozen SGPR pairs the kernel does not have: they were spilled into VGPR lanes and read back at every use
   // (two v_readlane + a hazard wait each).  Made opaque here, once per period, the conditions are re-derived where they are used: a scalar compare each.
   // (the packed layout — batches of at most one wave per SIMD — is indifferent: 4 096 envs +0.3 %, 32 768 / 65 536 -0.3 %: left alone)
-  if constexpr (sizeof(T) == 4 && (TICK == TICK_LIT || TICK == TICK_PLAIN))
-    DQL_ASM_PIN("+s"(s.quirks), "+s"(s.working), "+s"(s.init_uniform), "+s"(mode));
+  if constexpr (sizeof(T) == 4 && (TICK == TICK_LIT || TICK == TICK_PLAIN)) {
+    if constexpr (LEVEL0) DQL_ASM_PIN("+s"(s.quirks), "+s"(s.init_uniform), "+s"(mode));
+    else DQL_ASM_PIN("+s"(s.quirks), "+s"(s.working), "+s"(s.init_uniform), "+s"(mode));
+  }
+  if constexpr (LEVEL0) s.working = 0;  // behind the pin: the level stays a compile-time constant for period_begin and period_end
   DQL_SECTION("period_begin");
   const PeriodCtx c = period_begin(s, e, qx, qa, qb, mode, eps_thr, ext_action, seed, env_id, step_index, kv);
   T B[9];

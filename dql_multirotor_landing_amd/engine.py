@@ -300,6 +300,12 @@ class Engine:
         tick = {0: "PLAIN", 2: "PACKED", 3: "LIT", 4: "PACKED_LITM"}[v[2]]
         return f"{'k_step_pop' if v[4] else 'k_step'}<{'float' if v[0] == 4 else 'double'},{v[1]},{tick},{('X_TWO', 'X_ONLY', 'X_RUNTIME')[v[3]]}>"
 
+    def step_level0(self) -> bool:
+        """did the latest launch run its layout's level-0 instance (the working level compiled in as 0)?  Chosen by the library at every launch."""
+        v = C.c_int32()
+        _lib.check(self.lib.dql_diag_step_level0(self._h, C.byref(v)))
+        return bool(v.value)
+
     def delay(self, microseconds: float):
         _lib.check(self.lib.dql_diag_delay(self._h, float(microseconds)))
 

@@ -25,6 +25,9 @@ int dql_diag_sync_time_ms(dql_ctx* ctx, double* avg_ms, int64_t* syncs);
 /* the step kernel the context's latest launch ran: out5 = {sizeof(real) in bytes, BLOCK, TICK (csrc/dql_device.hpp TICK_*), XMODE (X_TWO 0, X_ONLY 1,
  * X_RUNTIME 2), 1 for the population kernel k_step_pop}: the template arguments of its name; all 0 before the first launch */
 int dql_diag_step_instance(dql_ctx* ctx, int32_t* out5);
+/* 1 when that launch ran the layout's level-0 instance (working level 0 compiled in: TICK_LIT and TICK_PACKED_LITM launches of x-axis configs at level 0, chosen per launch),
+ * 0 for the generic instance; the five numbers above are the same for both */
+int dql_diag_step_level0(dql_ctx* ctx, int32_t* level0);
 /* holds the context's stream for this long (a one-wave timer kernel): phase offset between contexts that share a GPU (tools/exp_cohorts.py) */
 int dql_diag_delay(dql_ctx* ctx, double microseconds);
 /* the window accumulators' device buffer (4 * 2835 int64), for a caller that wants to reduce it with a collective of its own; the product path
