@@ -41,6 +41,7 @@
 #include "dql_recipes.hpp"
 #include "dql_score.hpp"
 #include "dql_score_map.hpp"
+#include "dql_model.hpp"
 #include "../../include/dql_diag.h"
 
 using namespace dql;
@@ -2075,5 +2076,6 @@ int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
 #include "dql_recipes.inc"
 #include "dql_teams.inc"
 #include "dql_score_map.inc"
+#include "dql_model.inc"
 #include "dql_agent.inc"
 #include "dql_comm.inc"

@@ -372,6 +372,20 @@ class SequentialEnsemble:
                                                    _p(ep_steps), _p(ep_last_cell)))
         return ops.score_map_result(self.lib, by_code, steps_sum, visits, ep_code, ep_steps, ep_last_cell, timing)
 
+    def model(self, eval_cfg: DqlConfig, envs_per_learner: int = 64, seed: int = 123, eps: float = 0.1, episodes: int = 1, max_steps: int = 600, first: int = 0,
+              count: Optional[int] = None, timing: dict = None):
+        """`ops.transition_model` of learners first .. first + count - 1 on their tables where they live (no host copy).  The ensemble is left as it was.  At
+        most ops.MODEL_MAX_TABLES learners per call (the pair table is 10.7 MB per learner): slice with first / count."""
+        from . import ops
+        first, count = self._slice(first, count)
+        n, episodes, max_steps, eps = int(envs_per_learner), int(episodes), int(max_steps), float(eps)
+        ops.model_check_args(eval_cfg, count, n, episodes, max_steps, eps)
+        pairs, reward_fx, terminal, by_code, steps_sum = ops.model_buffers(count)
+        c = eval_cfg.to_c()
+        _lib.check(self.lib.dql_ensemble_model(self._h, C.byref(c), first, count, n, episodes, int(seed), max_steps, eps, _p(pairs), _p(reward_fx), _p(terminal), _p(by_code),
+                                               _p(steps_sum)))
+        return ops.model_result(self.lib, pairs, reward_fx, terminal, by_code, steps_sum, timing)
+
     def landing_rates(self, n_envs: int = 4096, episodes: int = 1, level: int = 4, seed: int = 123, dtype=None, quirks=None, max_steps: int = 600, first: int = 0,
                       count: Optional[int] = None, timing: dict = None):
         """`evaluation.landing_rates` of the resident tables: `touchdown_rate` and `goal_hold_rate` per learner, two launches"""

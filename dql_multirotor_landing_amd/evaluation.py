@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import ops
-from .config import CHECK_NAMES, F32, N_CELLS, Q_PAPER, simulation_config, training_config
+from .config import CHECK_NAMES, F32, N_CELLS, Q_PAPER, TARGET_FRAC_BITS, simulation_config, training_config
 from .engine import Engine
 
 METHODS = ("stepwise", "rollout")
@@ -260,3 +260,56 @@ def episode_report(records):
                                 "sink_rate": _quantiles(-get("vz")[k][td])}
         out.append(rep)
     return out
+
+
+# the empirical transition model (ops.transition_model, include/dql.h dql_model): what can be read from its tables (pure numpy below)
+def _model_arrays(pairs, terminal):
+    pairs, terminal = np.asarray(pairs), np.asarray(terminal)
+    if pairs.shape != (N_CELLS, N_STATES) or terminal.ndim != 2 or terminal.shape[0] != N_CELLS:
+        raise ValueError("pairs [2835, 945] and terminal [2835, codes] of ONE table set")
+    return pairs.astype(np.float64), terminal.astype(np.float64)
+
+
+def solve_model(pairs, reward_fx, terminal, gamma: float, min_visits: int = 1, tol: float = 1e-9, max_iter: int = 100000):
+    """Value iteration on the empirical model of one table set: `pairs` [2835, 945], `reward_fx` [2835], `terminal` [2835, codes] as `ops.transition_model`
+    returns them.  A cell is SOLVED if it was visited at least `min_visits` (>= 1) times; for those
+        Q(c) = mean reward(c) + gamma * sum_s' P(s' | c) * max over the solved actions a' of Q(s', a'),
+    P(s' | c) = pairs[c, s'] / visits[c]: a transition that ended the episode bootstraps nothing (the paper's mask: bootstrap unless done), and a state none
+    of whose actions is solved has value 0.  Iterated from 0 until no Q moves by more than `tol`, `max_iter` sweeps at most.  Unsolved cells get min(solved Q) - 1,
+    so that a greedy flight never prefers them.  Returns (Q float64 [2835], solved bool [2835])."""
+    p, t = _model_arrays(pairs, terminal)
+    reward_fx = np.asarray(reward_fx, dtype=np.float64).reshape(-1)
+    if reward_fx.shape != (N_CELLS,) or min_visits < 1 or not 0.0 <= gamma <= 1.0:
+        raise ValueError("reward_fx [2835], min_visits >= 1, gamma in [0, 1]")
+    visits = p.sum(axis=1) + t.sum(axis=1)
+    solved = visits >= min_visits
+    safe = np.where(solved, visits, 1.0)
+    r = np.where(solved, reward_fx / float(1 << TARGET_FRAC_BITS) / safe, 0.0)
+    P = np.where(solved[:, None], p / safe[:, None], 0.0)
+    by_state = solved.reshape(N_STATES, 3)
+    q = np.zeros(N_CELLS)
+    for _ in range(int(max_iter)):
+        v = np.where(by_state, q.reshape(N_STATES, 3), -np.inf).max(axis=1)
+        v = np.where(by_state.any(axis=1), v, 0.0)
+        new = np.where(solved, r + gamma * (P @ v), 0.0)
+        moved = float(np.abs(new - q).max())
+        q = new
+        if moved <= tol:
+            break
+    floor = (q[solved].min() if solved.any() else 0.0) - 1.0
+    return np.where(solved, q, floor), solved
+
+
+def model_divergence(pairs_a, terminal_a, pairs_b, terminal_b, min_visits: int = 1):
+    """float64 [2835]: per cell the total-variation distance 1/2 sum |P_a - P_b| between the next-outcome distributions of two models of one table shape, the
+    945 next states and the terminal codes taken as one alphabet.  NaN where either side has fewer than `min_visits` (>= 1) visits.  0: the two behaviour
+    policies saw the same thing happen after that (state, action); 1: disjoint outcomes."""
+    pa, ta = _model_arrays(pairs_a, terminal_a)
+    pb, tb = _model_arrays(pairs_b, terminal_b)
+    if ta.shape != tb.shape or min_visits < 1:
+        raise ValueError("both terminal tables [2835, codes] with the same codes, min_visits >= 1")
+    a, b = np.concatenate([pa, ta], axis=1), np.concatenate([pb, tb], axis=1)
+    va, vb = a.sum(axis=1), b.sum(axis=1)
+    ok = (va >= min_visits) & (vb >= min_visits)
+    tv = 0.5 * np.abs(a / np.where(ok, va, 1.0)[:, None] - b / np.where(ok, vb, 1.0)[:, None]).sum(axis=1)
+    return np.where(ok, tv, np.nan)

@@ -393,3 +393,57 @@ def score_map(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, episodes: 
     _lib.check(lib.dql_score_map(C.byref(c), device, K, n, episodes, int(seed), max_steps, _p(qa), _p(qb), _p(by_code), _p(steps_sum), _p(visits), opt(ep_code), opt(ep_steps),
                                  opt(ep_last_cell)))
     return score_map_result(lib, by_code, steps_sum, visits, ep_code, ep_steps, ep_last_cell, timing)
+
+
+MODEL_MAX_TABLES = 16  # include/dql.h DQL_MODEL_MAX_TABLES: the pair table is 10.7 MB per table set
+N_STATES = N_CELLS // 3
+
+
+def model_check_args(cfg: DqlConfig, n_tables: int, envs_per_table: int, episodes: int, max_steps: int, eps: float):
+    """the argument checks of dql_model / dql_ensemble_model, made before the library is touched"""
+    if cfg.two_axis:
+        raise ValueError("the transition model is the x MDP's (the reward is not kept per axis): a two-axis config is refused")
+    if not 1 <= n_tables <= MODEL_MAX_TABLES:
+        raise ValueError(f"between 1 and {MODEL_MAX_TABLES} table sets per model call, not {n_tables}: slice the sets")
+    score_check_args(n_tables, envs_per_table, episodes, max_steps)
+    if envs_per_table * (max_steps + 1) >= 1 << 32:
+        raise ValueError(f"envs_per_table * (max_steps + 1) must be below 2^32 (a 32-bit pair count), not {envs_per_table * (max_steps + 1)}")
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"eps must be in [0, 1], not {eps}")
+
+
+def model_buffers(n_tables: int):
+    """(pairs, reward_fx, terminal, by_code, steps_sum) as the C calls fill them"""
+    return (np.zeros((n_tables, N_CELLS, N_STATES), np.uint32), np.zeros((n_tables, N_CELLS), np.int64), np.zeros((n_tables, N_CELLS, len(CHECK_NAMES)), np.int64),
+            np.zeros((n_tables, len(SCORE_COLUMNS)), np.int64), np.zeros(n_tables, np.int64))
+
+
+def model_result(lib, pairs, reward_fx, terminal, by_code, steps_sum, timing):
+    if timing is not None:
+        ms, inst = C.c_double(), (C.c_int32 * 3)()
+        _lib.check(lib.dql_diag_model_last(C.byref(ms), inst))
+        timing["kernel_ms"] = ms.value
+        timing["instance"] = f"k_model<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    return {"pairs": pairs, "reward_fx": reward_fx, "terminal": terminal, "by_code": by_code, "steps_sum": steps_sum, "columns": SCORE_COLUMNS,
+            "visits": pairs.sum(axis=-1, dtype=np.int64) + terminal.sum(axis=-1)}
+
+
+def transition_model(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, eps: float, episodes: int = 1, max_steps: int = 600, device: int = 0, timing: dict = None):
+    """The empirical transition model of the discretised x MDP under the eps-greedy policy of K table sets, counted on the device in one launch (include/dql.h
+    dql_model).
+
+    `qa`, `qb`: float64 [K, 2835] (one set: [2835]), K up to MODEL_MAX_TABLES.  The envs and periods are `score`'s; an env explores with probability `eps` (the
+    action stream's draw, as in training) and takes its tables' greedy action otherwise; nothing is learnt.  With cell = state before the period * 3 + action,
+    every decision adds to `pairs` uint32 [K, 2835, 945] at (cell, state after) if the episode went on, to `terminal` int64 [K, 2835, len(CHECK_NAMES)] at
+    (cell, code) if it ended, and its reward times 2^26 (rounded to nearest even) to `reward_fx` int64 [K, 2835].  `by_code` and `steps_sum` are `score`'s;
+    `visits` int64 [K, 2835] = pairs.sum(-1) + terminal.sum(-1).  Integer sums: bit-reproducible.  `timing`: receives `kernel_ms` and `instance`."""
+    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
+    if qa.ndim != 2 or qa.shape[1] != N_CELLS or qb.shape != qa.shape:
+        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    K, n, episodes, max_steps, eps = len(qa), int(envs_per_table), int(episodes), int(max_steps), float(eps)
+    model_check_args(cfg, K, n, episodes, max_steps, eps)
+    lib = _lib.load()
+    pairs, reward_fx, terminal, by_code, steps_sum = model_buffers(K)
+    c = cfg.to_c()
+    _lib.check(lib.dql_model(C.byref(c), device, K, n, episodes, int(seed), max_steps, eps, _p(qa), _p(qb), _p(pairs), _p(reward_fx), _p(terminal), _p(by_code), _p(steps_sum)))
+    return model_result(lib, pairs, reward_fx, terminal, by_code, steps_sum, timing)

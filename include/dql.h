@@ -438,6 +438,26 @@ int dql_score(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_
 int dql_score_map(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
                   const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, int64_t* visits, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null,
                   uint16_t* ep_last_cell_or_null);
+/* ---- the empirical transition model of the discretised x MDP, counted on the device in one launch ----
+ * dql_model flies what dql_score flies — table set k, envs i with the RNG key (i, seed), periods 0 .. max_steps, every env until it has finished
+ * episodes_per_env episodes — but the behaviour policy is eps-greedy on the fixed tables, and nothing is learnt.
+ * The equality contract: take a context from dql_create(cfg, device, envs_per_table, seed, 0) and drive it with EXTERNAL actions through dql_step.  For env i
+ * in period j, not a reset period of that env: w = philox((j_lo, j_hi, i, 0), (seed_lo, seed_hi)) (the action stream); the env explores iff (w[0] >> 8) <
+ * ceil(eps 2^24), and its action is then (w[1] * 3) >> 32; otherwise its action is dql_agent_predict on the tables of set k at the env's idx_x.  An env counts
+ * in a period exactly as in dql_score_map: it has finished fewer than episodes_per_env episodes before that period, and FL_WAS_RESET is clear after it.  With
+ * cell = idx_x before the period * 3 + action, each counted period adds
+ *   pairs      uint32 [n_tables][DQL_N_CELLS][DQL_N_STATES]: 1 at (cell, idx_x after the period) when the period did not end the episode
+ *   terminal   int64 [n_tables][DQL_N_CELLS][DQL_N_CHECK_CODES]: 1 at (cell, code) when it did
+ *   reward_fx  int64 [n_tables][DQL_N_CELLS]: the period's reward times 2^DQL_TARGET_FRAC_BITS, rounded to nearest even, at the cell (terminal periods included)
+ *   by_code / steps_sum: as dql_score's
+ * Everything is an integer sum: bit-reproducible, whatever order the lanes arrive in.  dql_ensemble_model (below, with the ensembles) does the same on the
+ * tables of an ensemble's learners where they live.
+ * DQL_EINVAL (and no launch) for a two_axis config (the model is the x MDP's; the reward is not kept per axis), n_tables outside 1..DQL_MODEL_MAX_TABLES (the
+ * pair table is 10.7 MB per set), envs_per_table not a positive multiple of 64, envs_per_table * (max_steps + 1) >= 2^32 (below that no pair count can
+ * overflow), episodes_per_env or max_steps outside dql_score's ranges, eps outside [0, 1], or a null pointer. */
+#define DQL_MODEL_MAX_TABLES 16
+int dql_model(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps, double eps,
+              const double* qa, const double* qb, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code, int64_t* steps_sum);
 /* ---- a DoubleQLearningAgent's tables RESIDENT on the device (pkg/double_q_learning.py:32-146) ----
  * The stateless dql_agent_predict / dql_agent_update below ship all three tables (3 x 22 680 B) both ways per call — fine for a batch,
  * 6x slower than the reference's own Python for a caller that steps ONE env (BASELINE configs[0]).  A dql_agent keeps them in device
@@ -575,6 +595,11 @@ int dql_ensemble_score(dql_ensemble* ens, const dql_config* eval_cfg, int64_t fi
 int dql_ensemble_score_map(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
                            uint64_t seed, int32_t max_steps, int64_t* by_code, int64_t* steps_sum, int64_t* visits, uint8_t* ep_code_or_null,
                            uint16_t* ep_steps_or_null, uint16_t* ep_last_cell_or_null);
+/* dql_model on the tables of learners [first, first + count), as dql_ensemble_score_map is dql_score_map on them: outputs and refusals as for dql_model (count
+ * in place of n_tables, so count <= DQL_MODEL_MAX_TABLES; the slice must lie inside the ensemble).  The ensemble is left exactly as it was. */
+int dql_ensemble_model(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
+                       uint64_t seed, int32_t max_steps, double eps, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code,
+                       int64_t* steps_sum);
 
 /* ---- per-learner curriculum levels ----
  * Every learner has its own working level (it starts at the config's working_curriculum_step; dql_ensemble_set_level sets everybody's and clears the history

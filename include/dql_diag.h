@@ -44,6 +44,8 @@ int dql_diag_score_last(double* kernel_ms, int32_t* inst3);
 /* the same for the calling thread's latest completed dql_score_map or dql_ensemble_score_map: the template arguments of k_score_map's name.
  * dql_diag_score_last keeps its meaning: a map call does not change what it reports */
 int dql_diag_score_map_last(double* kernel_ms, int32_t* inst3);
+/* the same for the calling thread's latest completed dql_model or dql_ensemble_model: the template arguments of k_model's name */
+int dql_diag_model_last(double* kernel_ms, int32_t* inst3);
 
 /* wall duration on the device (HIP events around all launches) of the ensemble's latest completed dql_ensemble_run */
 int dql_diag_ensemble_last(dql_ensemble* ens, double* run_ms);

@@ -4,12 +4,16 @@ pair of Q tables in the vectorised simulator and reports how the episodes end.
 
     python scripts/simulation.py [--tables DIR] [--envs 4096] [--level 4] [--flavour simulation|training] [--mode paper|reference]
                                  [--rollout] [--report] [--trace-out FILE.npz [--trace-envs 8]] [--map-out FILE.npz [--map-episodes 1]]
+                                 [--model-out FILE.npz [--model-eps 0.1]]
 Default tables: tests/golden/assets (a data copy of the reference's stage-4 policy).
 --rollout flies all first episodes in one launch (dql_rollout) instead of one launch per agent period; --report prints what the episodes looked like at
 their end (the counterpart of the `info` dictionary the reference prints per episode, scripts/simulation.py:52-56) and --trace-out saves the per-period
 flight record of the first envs; both imply --rollout.
 --map-out writes where the tables' greedy policy flies (dql_score_map): `visits` [2835], the decisions counted by cell, and
 `last_cell_by_code` [codes, 2835], the histogram of the x cell of each finished episode's last decision by terminal code, with `by_code` and `columns`.
+--model-out writes the empirical transition model of the discretised MDP under the tables' eps-greedy policy (dql_model): `pairs`
+[2835, 945], `reward_fx` [2835], `terminal` [2835, codes] and `visits` [2835], with `by_code`, `columns`, `steps_sum` and `eps` (--model-eps; --map-episodes
+episodes per env).
 """
 import argparse
 import json
@@ -48,6 +52,19 @@ def evaluate_map(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dtyp
     return {"visits": r["visits"][0], "last_cell_by_code": by_code, "by_code": r["by_code"][0], "columns": np.array(r["columns"]), "steps_sum": r["steps_sum"][0]}
 
 
+def evaluate_model(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, episodes=1, eps=0.1, **cfg_kw):
+    """The empirical transition model of the same flights under the tables' eps-greedy policy, from one launch of the model operator."""
+    import numpy as np
+    from dql_multirotor_landing_amd import evaluation, ops
+    from dql_multirotor_landing_amd.double_q_learning import DoubleQLearningAgent
+    qa, qb, _ = DoubleQLearningAgent.load(Path(tables_dir))._padded()
+    cfg = evaluation._flavour_config(flavour, level, dtype, cfg_kw)
+    r = ops.transition_model(cfg, qa, qb, n_envs, seed, eps, episodes=episodes, max_steps=max_steps, device=device)
+    out = {f: r[f][0] for f in ("pairs", "reward_fx", "terminal", "visits", "by_code", "steps_sum")}
+    out.update({"columns": np.array(r["columns"]), "eps": np.float64(eps)})
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--tables", default=str(Path(__file__).resolve().parent.parent / "tests" / "golden" / "assets"))
@@ -63,6 +80,8 @@ if __name__ == "__main__":
     ap.add_argument("--trace-envs", type=int, default=8)
     ap.add_argument("--map-out", default=None, metavar="FILE.npz", help="save the map of the greedy flights and the last-cell histogram by terminal code (dql_score_map)")
     ap.add_argument("--map-episodes", type=int, default=1, help="episodes per env of the --map-out launch")
+    ap.add_argument("--model-out", default=None, metavar="FILE.npz", help="save the empirical transition model of the tables' eps-greedy policy (dql_model)")
+    ap.add_argument("--model-eps", type=float, default=0.1, help="exploration rate of the --model-out launch, in [0, 1]")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build_hip()
@@ -91,5 +110,11 @@ if __name__ == "__main__":
         np.savez_compressed(a.map_out, **m)
         out["map"] = {"file": a.map_out, "episodes_per_env": a.map_episodes, "decisions": int(m["visits"].sum()), "cells_visited": int((m["visits"] > 0).sum()),
                       "busiest_cell": int(m["visits"].argmax()), "busiest_cell_visits": int(m["visits"].max())}
+    if a.model_out:
+        import numpy as np
+        m = evaluate_model(a.tables, n, a.level, flavour=a.flavour, episodes=a.map_episodes, eps=a.model_eps, quirks=quirks)
+        np.savez_compressed(a.model_out, **m)
+        out["model"] = {"file": a.model_out, "eps": a.model_eps, "episodes_per_env": a.map_episodes, "decisions": int(m["visits"].sum()), "cells_visited": int((m["visits"] > 0).sum()),
+                        "distinct_pairs": int((m["pairs"] > 0).sum()), "terminal_decisions": int(m["terminal"].sum())}
     out.update({"first_episode_outcomes": h, "touchdown_rate": h["TERMINAL_CONTACT"] / n, "goal_rate": h["TERMINAL_SUCCESS"] / n})
     print(json.dumps(out, indent=1))
