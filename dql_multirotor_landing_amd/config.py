@@ -269,3 +269,39 @@ def simulation_config(**kw) -> DqlConfig:
     base = dict(working_curriculum_step=4, vz_setpoint=-0.4, init_uniform=2, z_init=4.0, goal_logic=0)
     base.update(kw)
     return DqlConfig(**base)
+
+
+def scenario_grid(base: DqlConfig, **axes):
+    """The Cartesian product of `DqlConfig` fields given as lists, for `ops.score_grid`: `scenario_grid(cfg, mp_t_x=[0.8, 1.6], trajectory=[TRAJ_RPM,
+    TRAJ_EIGHT])` -> (cfgs, labels), four configs that differ from `base` in those fields only, the first keyword varying slowest; `labels[s]` is the dict of
+    the varied fields of `cfgs[s]`.  No axes: ([base], [{}]).  An unknown field name, or an axis without values, raises ValueError."""
+    import dataclasses
+    import itertools
+    names = {f.name for f in dataclasses.fields(DqlConfig)}
+    for name, values in axes.items():
+        if name not in names:
+            raise ValueError(f"scenario_grid: DqlConfig has no field {name!r}")
+        if isinstance(values, (str, bytes)) or not hasattr(values, "__len__") or len(values) == 0:
+            raise ValueError(f"scenario_grid: the axis {name!r} needs a non-empty list of values")
+    labels = [dict(zip(axes, combo)) for combo in itertools.product(*axes.values())]
+    return [dataclasses.replace(base, **lab) for lab in labels], labels
+
+
+def parse_grid_axes(specs):
+    """The command-line form of `scenario_grid`'s axes: each of `specs` is "FIELD=v1,v2,..." (scripts/simulation.py --grid, scripts/ensemble_training.py
+    --score-grid); the values take the type of the field's default (int or float; the list-valued fields are not offered).  Returns {field: [values]} in the
+    order given; a malformed item, an unknown or list-valued field or a repeated field raises ValueError."""
+    import dataclasses
+    defaults = {f.name: f.default for f in dataclasses.fields(DqlConfig) if f.default is not dataclasses.MISSING}
+    axes = {}
+    for spec in specs:
+        name, eq, values = spec.partition("=")
+        if not eq or not values:
+            raise ValueError(f"a grid axis is FIELD=v1,v2,..., not {spec!r}")
+        if name not in defaults:
+            raise ValueError(f"DqlConfig has no scalar field {name!r}")
+        if name in axes:
+            raise ValueError(f"the grid axis {name!r} is given twice")
+        kind = int if isinstance(defaults[name], int) else float
+        axes[name] = [kind(v) for v in values.split(",")]
+    return axes

@@ -386,6 +386,21 @@ class SequentialEnsemble:
                                                _p(steps_sum)))
         return ops.model_result(self.lib, pairs, reward_fx, terminal, by_code, steps_sum, timing)
 
+    def score_grid(self, eval_cfgs, envs_per_learner: int = 64, seed: int = 123, episodes: int = 1, max_steps: int = 600, log: bool = False, touch: bool = True,
+                   first: int = 0, count: Optional[int] = None, timing: dict = None):
+        """`ops.score_grid` of learners first .. first + count - 1 on their tables where they live (no host copy), under every config of `eval_cfgs` in one
+        launch.  The ensemble is left as it was.  Returns what `ops.score_grid` returns, table set k = learner first + k."""
+        from . import ops
+        eval_cfgs = list(eval_cfgs)
+        first, count = self._slice(first, count)
+        n, episodes, max_steps = int(envs_per_learner), int(episodes), int(max_steps)
+        ops.grid_check_args(eval_cfgs, count, n, episodes, max_steps)
+        by_code, steps_sum, touch_hist, ep_code, ep_steps = ops.grid_buffers(len(eval_cfgs), count, n, episodes, log, touch)
+        c = ops.grid_configs_to_c(eval_cfgs)
+        _lib.check(self.lib.dql_ensemble_score_grid(self._h, c, len(eval_cfgs), first, count, n, episodes, int(seed), max_steps, _p(by_code), _p(steps_sum), _p(touch_hist),
+                                                    _p(ep_code), _p(ep_steps)))
+        return ops.grid_result(self.lib, eval_cfgs, by_code, steps_sum, touch_hist, ep_code, ep_steps, timing)
+
     def landing_rates(self, n_envs: int = 4096, episodes: int = 1, level: int = 4, seed: int = 123, dtype=None, quirks=None, max_steps: int = 600, first: int = 0,
                       count: Optional[int] = None, timing: dict = None):
         """`evaluation.landing_rates` of the resident tables: `touchdown_rate` and `goal_hold_rate` per learner, two launches"""

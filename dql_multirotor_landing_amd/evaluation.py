@@ -313,3 +313,40 @@ def model_divergence(pairs_a, terminal_a, pairs_b, terminal_b, min_visits: int =
     ok = (va >= min_visits) & (vb >= min_visits)
     tv = 0.5 * np.abs(a / np.where(ok, va, 1.0)[:, None] - b / np.where(ok, vb, 1.0)[:, None]).sum(axis=1)
     return np.where(ok, tv, np.nan)
+
+
+def robustness_table(result, labels, column: str = "TERMINAL_CONTACT"):
+    """What an `ops.score_grid` result says per (scenario, table set), pure numpy.  `result`: a dict with `by_code` [S, K, len(ops.SCORE_COLUMNS)], `steps_sum`
+    [S, K] and, optionally, `touch_hist` [S, K, 8]; `labels`: one label per scenario (`config.scenario_grid`'s dicts).  Returns a dict of float64 [S, K] arrays:
+      rate        the share of all episodes asked for that ended with `column`
+      mean_steps  the mean length of the finished episodes (NaN where none finished)
+      unfinished  the share of episodes that did not finish
+      touch_centre / touch_outside  the share of touchdowns in bins 0 - 1 (within a quarter of the platform's width of its centre) and in bins >= 4 (beyond the
+                  half extent); NaN where nothing touched down, None without `touch_hist`
+    and per table set `worst_scenario` int64 [K] (the first scenario with the smallest rate), `worst_rate` [K] and `worst_label` (a list of K labels)."""
+    by_code = np.asarray(result["by_code"], dtype=np.int64); steps_sum = np.asarray(result["steps_sum"], dtype=np.int64)
+    if by_code.ndim != 3 or by_code.shape[2] != len(ops.SCORE_COLUMNS) or steps_sum.shape != by_code.shape[:2]:
+        raise ValueError(f"by_code must be [S, K, {len(ops.SCORE_COLUMNS)}] and steps_sum [S, K]")
+    S, K = steps_sum.shape
+    if len(labels) != S:
+        raise ValueError(f"{len(labels)} labels for {S} scenarios")
+    total = by_code.sum(axis=2)
+    if (total <= 0).any():
+        raise ValueError("a row of by_code counts no episode")
+    unfinished = by_code[:, :, -1]
+    finished = total - unfinished
+    rate = by_code[:, :, ops.SCORE_COLUMNS.index(column)] / total
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = {"rate": rate, "mean_steps": np.where(finished > 0, steps_sum / np.where(finished > 0, finished, 1), np.nan), "unfinished": unfinished / total,
+               "touch_centre": None, "touch_outside": None}
+        if result.get("touch_hist") is not None:
+            touch = np.asarray(result["touch_hist"], dtype=np.int64)
+            if touch.shape != (S, K, ops.GRID_TOUCH_BINS):
+                raise ValueError(f"touch_hist must be [S, K, {ops.GRID_TOUCH_BINS}]")
+            n = touch.sum(axis=2)
+            den = np.where(n > 0, n, 1)
+            out["touch_centre"] = np.where(n > 0, touch[:, :, :2].sum(axis=2) / den, np.nan)
+            out["touch_outside"] = np.where(n > 0, touch[:, :, 4:].sum(axis=2) / den, np.nan)
+    worst = rate.argmin(axis=0)
+    out.update(worst_scenario=worst.astype(np.int64), worst_rate=rate[worst, np.arange(K)], worst_label=[labels[int(s)] for s in worst], column=column)
+    return out

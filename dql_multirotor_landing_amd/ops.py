@@ -447,3 +447,82 @@ def transition_model(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, eps
     c = cfg.to_c()
     _lib.check(lib.dql_model(C.byref(c), device, K, n, episodes, int(seed), max_steps, eps, _p(qa), _p(qb), _p(pairs), _p(reward_fx), _p(terminal), _p(by_code), _p(steps_sum)))
     return model_result(lib, pairs, reward_fx, terminal, by_code, steps_sum, timing)
+
+
+GRID_MAX_SCENARIOS, GRID_TOUCH_BINS = 1024, 8  # include/dql.h DQL_GRID_MAX_SCENARIOS, DQL_GRID_TOUCH_BINS
+GRID_SHARED_FIELDS = ("dtype", "two_axis", "f_ag", "dt", "manager_div")  # what one launch must share: the kernel instance and the tick schedule
+
+
+def grid_check_args(cfgs, n_tables: int, envs_per_table: int, episodes: int, max_steps: int):
+    """the argument checks of dql_score_grid / dql_ensemble_score_grid, made before the library is touched"""
+    if not 1 <= len(cfgs) <= GRID_MAX_SCENARIOS:
+        raise ValueError(f"between 1 and {GRID_MAX_SCENARIOS} scenarios per call, not {len(cfgs)}")
+    for s, c in enumerate(cfgs):
+        if not isinstance(c, DqlConfig):
+            raise ValueError(f"scenario {s} is not a DqlConfig")
+        for f in GRID_SHARED_FIELDS:
+            if getattr(c, f) != getattr(cfgs[0], f):
+                raise ValueError(f"scenario {s} differs from scenario 0 in {f} ({getattr(c, f)!r} vs {getattr(cfgs[0], f)!r}), which one launch must share")
+    score_check_args(n_tables, envs_per_table, episodes, max_steps)
+    if len(cfgs) * n_tables * envs_per_table > SCORE_MAX_LANES:
+        raise ValueError(f"scenarios x table sets x envs must be at most 2^30, not {len(cfgs) * n_tables * envs_per_table}")
+
+
+def grid_configs_to_c(cfgs):
+    """the scenarios as one contiguous dql_config array"""
+    from .config import DqlConfigC
+    arr = (DqlConfigC * len(cfgs))()
+    for s, c in enumerate(cfgs):
+        arr[s] = c.to_c()
+    return arr
+
+
+def grid_touch_edges(cfgs) -> np.ndarray:
+    """float64 [S, 7]: the bin edges j * mp_half_x / 4, j = 1 .. 7, rounded to the scenarios' real type as the library rounds them (include/dql.h)"""
+    t = np.float32 if cfgs[0].dtype == 0 else np.float64
+    return np.array([[float(t(float(j) * c.mp_half_x * 0.25)) for j in range(1, GRID_TOUCH_BINS)] for c in cfgs], np.float64)
+
+
+def grid_buffers(n_scenarios: int, n_tables: int, envs_per_table: int, episodes: int, log: bool, touch: bool):
+    """(by_code, steps_sum, touch_hist or None, ep_code or None, ep_steps or None) as the C calls fill them"""
+    S, K = n_scenarios, n_tables
+    by_code = np.zeros((S, K, len(SCORE_COLUMNS)), np.int64); steps_sum = np.zeros((S, K), np.int64)
+    touch_hist = np.zeros((S, K, GRID_TOUCH_BINS), np.int64) if touch else None
+    ep_code = np.zeros((S, episodes, K * envs_per_table), np.uint8) if log else None
+    ep_steps = np.zeros((S, episodes, K * envs_per_table), np.uint16) if log else None
+    return by_code, steps_sum, touch_hist, ep_code, ep_steps
+
+
+def grid_result(lib, cfgs, by_code, steps_sum, touch_hist, ep_code, ep_steps, timing):
+    if timing is not None:
+        ms, inst = C.c_double(), (C.c_int32 * 3)()
+        _lib.check(lib.dql_diag_score_grid_last(C.byref(ms), inst))
+        timing["kernel_ms"] = ms.value
+        timing["instance"] = f"k_score_grid<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    return {"by_code": by_code, "steps_sum": steps_sum, "touch_hist": touch_hist, "touch_edges": grid_touch_edges(cfgs), "ep_code": ep_code, "ep_steps": ep_steps,
+            "columns": SCORE_COLUMNS}
+
+
+def score_grid(cfgs, qa, qb, envs_per_table: int, seed: int, episodes: int = 1, max_steps: int = 600, log: bool = False, touch: bool = True, device: int = 0,
+               timing: dict = None):
+    """`score` of K table sets under each of S scenarios in ONE launch, plus where on the platform the touchdowns land (include/dql.h dql_score_grid, DESIGN.md
+    section 20).
+
+    `cfgs`: a list of DqlConfig (`config.scenario_grid` builds one) that share dtype, two_axis, f_ag, dt and manager_div and may differ in anything else.
+    Slice s of every output is what `score(cfgs[s], ...)` returns: `by_code` int64 [S, K, len(SCORE_COLUMNS)], `steps_sum` int64 [S, K], and with `log` `ep_code`
+    uint8 / `ep_steps` uint16 [S, episodes, K * envs_per_table].  Env i of every (scenario, set) has the key (i, seed): first episodes are paired across both axes.
+    With `touch`, `touch_hist` int64 [S, K, 8] counts the episodes that ended in TERMINAL_CONTACT by the drone's horizontal offset from the platform centre
+    after the terminal period (two axes: the larger of the two offsets): bin = the number of `touch_edges[s]` (float64 [S, 7], j * mp_half_x / 4) the offset
+    reaches, so bins 0 - 3 lie inside the half extent and 4 - 7 beyond it.  `timing`: receives `kernel_ms` and `instance`."""
+    cfgs = list(cfgs)
+    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
+    if qa.ndim != 2 or qa.shape[1] != N_CELLS or qb.shape != qa.shape:
+        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    K, n, episodes, max_steps = len(qa), int(envs_per_table), int(episodes), int(max_steps)
+    grid_check_args(cfgs, K, n, episodes, max_steps)
+    lib = _lib.load()
+    by_code, steps_sum, touch_hist, ep_code, ep_steps = grid_buffers(len(cfgs), K, n, episodes, log, touch)
+    c = grid_configs_to_c(cfgs)
+    _lib.check(lib.dql_score_grid(c, len(cfgs), device, K, n, episodes, int(seed), max_steps, _p(qa), _p(qb), _p(by_code), _p(steps_sum),
+                                  None if touch_hist is None else _p(touch_hist), None if ep_code is None else _p(ep_code), None if ep_steps is None else _p(ep_steps)))
+    return grid_result(lib, cfgs, by_code, steps_sum, touch_hist, ep_code, ep_steps, timing)

@@ -458,6 +458,28 @@ int dql_score_map(const dql_config* cfg, int device, int64_t n_tables, int64_t e
 #define DQL_MODEL_MAX_TABLES 16
 int dql_model(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps, double eps,
               const double* qa, const double* qb, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code, int64_t* steps_sum);
+/* ---- greedy scoring over a grid of scenarios: S configs x K table sets in one launch, with the landing precision of the touchdowns ----
+ * The equality contract: slice s of every output is what dql_score(&cfgs[s], ...) returns for the same remaining arguments — in turn the stepwise context of
+ * dql_score's own contract: dql_create(&cfgs[s], device, envs_per_table, seed, 0) with the tables of set k, then dql_eval_steps(ctx, 1) for periods 0 ..
+ * max_steps.  Env i of every (scenario, set) has the key (i, seed): first episodes are paired across table sets and across scenarios.
+ *   by_code    int64 [n_scenarios][n_tables][DQL_N_CHECK_CODES + 1];  steps_sum  int64 [n_scenarios][n_tables]
+ *   ep_code    uint8 [n_scenarios][episodes_per_env][n_tables * envs_per_table];  ep_steps uint16, same shape (both or neither)
+ *   touch_hist int64 [n_scenarios][n_tables][DQL_GRID_TOUCH_BINS], optional, the only output dql_score has no counterpart for.  It counts, among the first
+ *              episodes_per_env episodes of an env, those that end with DQL_TERMINAL_CONTACT, binned by d, the drone's horizontal offset from the platform
+ *              centre after the terminal period: d = |px - mp_x| in the config's real type T, on the values dql_rollout's record shows as px and mp_x at that
+ *              period; with two_axis d = max(|px - mp_x|, |py - mp_y|) (the platform is a square).  bin = the number of j in 1..7 with d >= edge_j, edge_j =
+ *              (T)((double)j * cfgs[s].mp_half_x * 0.25): bins 0 - 3 lie inside the half extent, bins 4 - 7 beyond it (they do occur: the contact latch is set
+ *              at a physics tick, the offset is read at the period's end).  A NaN offset falls into bin 0.  Integer sums: bit-reproducible.
+ * The scenarios may differ in anything except what one launch must share: dtype and two_axis (they fix the kernel instance) and f_ag, dt and manager_div (they
+ * fix the tick schedule, which is uploaded once).  dql_ensemble_score_grid (below, with the ensembles) does the same on an ensemble's resident tables.
+ * DQL_EINVAL (and no launch, outputs untouched), in a sentence that names the scenario where there is one: n_scenarios outside 1..DQL_GRID_MAX_SCENARIOS, a
+ * scenario that is not a valid config, a scenario that differs from scenario 0 in one of the five shared fields, n_scenarios * n_tables * envs_per_table >
+ * 2^30, whatever dql_score refuses, a log of which only one array is given, a null cfgs, qa, qb, by_code or steps_sum. */
+#define DQL_GRID_MAX_SCENARIOS 1024
+#define DQL_GRID_TOUCH_BINS 8
+int dql_score_grid(const dql_config* cfgs /* [n_scenarios] */, int32_t n_scenarios, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env,
+                   uint64_t seed, int32_t max_steps, const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, int64_t* touch_hist_or_null,
+                   uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null);
 /* ---- a DoubleQLearningAgent's tables RESIDENT on the device (pkg/double_q_learning.py:32-146) ----
  * The stateless dql_agent_predict / dql_agent_update below ship all three tables (3 x 22 680 B) both ways per call — fine for a batch,
  * 6x slower than the reference's own Python for a caller that steps ONE env (BASELINE configs[0]).  A dql_agent keeps them in device
@@ -600,6 +622,11 @@ int dql_ensemble_score_map(dql_ensemble* ens, const dql_config* eval_cfg, int64_
 int dql_ensemble_model(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
                        uint64_t seed, int32_t max_steps, double eps, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code,
                        int64_t* steps_sum);
+/* dql_score_grid on the tables of learners [first, first + count): outputs and refusals as for dql_score_grid (count in place of n_tables; the slice must lie
+ * inside the ensemble).  The ensemble is left exactly as it was. */
+int dql_ensemble_score_grid(dql_ensemble* ens, const dql_config* eval_cfgs /* [n_scenarios] */, int32_t n_scenarios, int64_t first, int64_t count,
+                            int64_t envs_per_learner, int32_t episodes_per_env, uint64_t seed, int32_t max_steps, int64_t* by_code, int64_t* steps_sum,
+                            int64_t* touch_hist_or_null, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null);
 
 /* ---- per-learner curriculum levels ----
  * Every learner has its own working level (it starts at the config's working_curriculum_step; dql_ensemble_set_level sets everybody's and clears the history

@@ -46,6 +46,9 @@ int dql_diag_score_last(double* kernel_ms, int32_t* inst3);
 int dql_diag_score_map_last(double* kernel_ms, int32_t* inst3);
 /* the same for the calling thread's latest completed dql_model or dql_ensemble_model: the template arguments of k_model's name */
 int dql_diag_model_last(double* kernel_ms, int32_t* inst3);
+/* the same for the calling thread's latest completed dql_score_grid or dql_ensemble_score_grid: the template arguments of k_score_grid's name.  A refused
+ * call leaves the record as it was */
+int dql_diag_score_grid_last(double* kernel_ms, int32_t* inst3);
 
 /* wall duration on the device (HIP events around all launches) of the ensemble's latest completed dql_ensemble_run */
 int dql_diag_ensemble_last(dql_ensemble* ens, double* run_ms);

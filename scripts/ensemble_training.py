@@ -5,6 +5,7 @@ one learner per GPU lane (dql_multirotor_landing_amd/ensemble.py).
     python scripts/ensemble_training.py --learners 4096 --seed 42 [--launched] [--levels 5] [--episodes 50000] [--score ENVS] --out run.npz
                                         [--per-learner [--advance-every E] [--drop-exhausted] [--max-periods N]] [--recipes FILE.json]
                                         [--envs-per-learner E] [--score-map] [--preset reference|paper]
+                                        [--score-grid FIELD=v1,v2,... [--score-grid ...]]
 
 --launched: the parameters the reference's manager node ran with under roslaunch (config.as_launched_config) instead of the launch file's.
 --score ENVS: after the curriculum, fly every learner's tables greedily where they live (SequentialEnsemble.landing_rates: ENVS envs per learner and flavour,
@@ -24,6 +25,10 @@ a preset name — "reference" (quirks 0x7f, the reference's transfer order) or "
 (default "reference"), "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min" and "levels": {"K": {"eps": [...],
 "window", "min_successes", "max_episodes"}} for the levels that differ from the preset's.  Learners are dealt round-robin: recipe r gets the learners with
 l % R == r.  With --score the landing-rate quantiles are reported per recipe.
+--score-grid FIELD=v1,v2,... (repeatable, with --score): after the curriculum, every learner's tables are also scored where they live over the Cartesian product
+of the given DqlConfig fields around the simulation flavour's config, all scenarios in one launch per slice of learners (SequentialEnsemble.score_grid, DESIGN.md
+section 20).  The report gains `grid`: per scenario its label and the quantiles over learners of the touchdown rate, and the share of learners whose worst
+scenario it is; the .npz gains `grid_touchdown_rate` [scenarios, learners] and `grid_touch_hist` [scenarios, learners, 8].
 --envs-per-learner E: every learner owns a team of E envs (1, 2, 4, ..., 64) and applies the reference's update to their transitions in env order (DESIGN.md
 section 17), so it collects E episodes in the time of one; --learners times E is at most 2^20.  Teams fly the level-by-level driver only: the flag is refused
 together with --per-learner and --recipes.
@@ -187,6 +192,22 @@ def per_recipe_report(names, recipe_of, td, gh, summary):
              "touchdown_rate": rate_summary(td[recipe_of == r]), "goal_hold_rate": rate_summary(gh[recipe_of == r])} for r, name in enumerate(names)]
 
 
+def grid_report(ens, a, quirks):
+    """--score-grid: ({"labels", "touchdown_rate": [quantiles per scenario], "worst_share"}, rate [S, learners], touch_hist [S, learners, 8])"""
+    from dql_multirotor_landing_amd.config import parse_grid_axes, scenario_grid, simulation_config
+    from dql_multirotor_landing_amd.ops import SCORE_MAX_LANES
+    base = simulation_config(working_curriculum_step=a.levels - 1, quirks=quirks, dtype=ens.cfg.dtype)
+    cfgs, labels = scenario_grid(base, **parse_grid_axes(a.score_grid))
+    per_call = max(1, SCORE_MAX_LANES // (len(cfgs) * a.score))  # learners per launch: scenarios x learners x envs <= 2^30
+    parts = [ens.score_grid(cfgs, a.score, a.score_seed, episodes=a.score_episodes, first=first, count=min(per_call, ens.n - first)) for first in range(0, ens.n, per_call)]
+    r = {f: np.concatenate([p[f] for p in parts], axis=1) for f in ("by_code", "steps_sum", "touch_hist")}
+    t = evaluation.robustness_table(r, labels)
+    q = lambda x: {f"q{int(100 * p):02d}": float(np.quantile(x, p)) for p in (0.05, 0.25, 0.5, 0.75, 0.95)}
+    rep = {"labels": labels, "touchdown_rate": [q(t["rate"][s]) for s in range(len(cfgs))],
+           "worst_share": (np.bincount(t["worst_scenario"], minlength=len(cfgs)) / ens.n).tolist()}
+    return rep, t["rate"], r["touch_hist"]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--learners", type=int, default=4096)
@@ -208,6 +229,7 @@ def main():
     ap.add_argument("--recipes", default=None, metavar="FILE.json", help="fly several recipes in one ensemble, dealt round-robin (implies --per-learner)")
     ap.add_argument("--envs-per-learner", type=int, default=1, metavar="E", help="envs per learner: 1, 2, 4, 8, 16, 32 or 64 (not with --per-learner / --recipes)")
     ap.add_argument("--score-map", action="store_true", help="with --score: also count where every learner's greedy policy flies, and report it against the reference's tables")
+    ap.add_argument("--score-grid", action="append", default=[], metavar="FIELD=v1,v2,...", help="with --score: also score every learner over this grid of scenarios in one launch (repeatable)")
     ap.add_argument("--preset", default="reference", choices=["reference", "paper"], help="quirks and transfer order of the level-by-level driver (not with --per-learner / --recipes)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
@@ -215,6 +237,8 @@ def main():
         ap.error("--preset belongs to the level-by-level driver: with --recipes name the preset in the recipes file")
     if a.score_map and not a.score:
         ap.error("--score-map needs --score ENVS: the maps are counted by the scoring launches")
+    if a.score_grid and not a.score:
+        ap.error("--score-grid needs --score ENVS: the grid flies ENVS envs per learner and scenario")
     if a.score_map and not all((Path(a.reference_tables) / f).exists() for f in ("Q_table_a.npy", "Q_table_b.npy")):
         ap.error("--score-map needs the baseline's tables: --reference-tables has no Q_table_a.npy / Q_table_b.npy")
     if a.envs_per_learner not in TEAM_SIZES:
@@ -261,6 +285,9 @@ def main():
                         entry["maps"] = {f: map_summary(maps["report"][f], recipe_of == r) for f in FLAVOURS}
             if maps is not None:
                 extra.update({f"greedy_visits_{f}": maps["visits"][f].astype(np.uint32) for f in FLAVOURS})
+            if a.score_grid:
+                rep["grid"], grid_rate, grid_touch = grid_report(ens, a, evaluation.Q_PAPER)
+                extra.update({"grid_touchdown_rate": grid_rate, "grid_touch_hist": grid_touch})
             print(json.dumps(rep), flush=True)
             ref = rep["reference_tables"]
             print(f"{rep['learners_at_or_above_bar']} of {rep['learners']} learners ({100.0 * rep['share_at_or_above_bar']:.1f} %) reach a touchdown rate of "

@@ -4,7 +4,7 @@ pair of Q tables in the vectorised simulator and reports how the episodes end.
 
     python scripts/simulation.py [--tables DIR] [--envs 4096] [--level 4] [--flavour simulation|training] [--mode paper|reference]
                                  [--rollout] [--report] [--trace-out FILE.npz [--trace-envs 8]] [--map-out FILE.npz [--map-episodes 1]]
-                                 [--model-out FILE.npz [--model-eps 0.1]]
+                                 [--model-out FILE.npz [--model-eps 0.1]] [--grid-out FILE.npz --grid FIELD=v1,v2,... [--grid ...]]
 Default tables: tests/golden/assets (a data copy of the reference's stage-4 policy).
 --rollout flies all first episodes in one launch (dql_rollout) instead of one launch per agent period; --report prints what the episodes looked like at
 their end (the counterpart of the `info` dictionary the reference prints per episode, scripts/simulation.py:52-56) and --trace-out saves the per-period
@@ -14,6 +14,10 @@ flight record of the first envs; both imply --rollout.
 --model-out writes the empirical transition model of the discretised MDP under the tables' eps-greedy policy (dql_model): `pairs`
 [2835, 945], `reward_fx` [2835], `terminal` [2835, codes] and `visits` [2835], with `by_code`, `columns`, `steps_sum` and `eps` (--model-eps; --map-episodes
 episodes per env).
+--grid-out scores the tables over the Cartesian product of the --grid axes in ONE launch (dql_score_grid): `--grid mp_t_x=0.8,1.2,1.6 --grid
+trajectory=0,1` flies six scenarios that differ from the flavour's config in those fields only (the first axis varies slowest).  The file holds `by_code`
+[S, codes + 1], `steps_sum` [S], `touch_hist` [S, 8] (touchdowns by their offset from the platform centre), `touch_edges` [S, 7], `columns`, one array per
+axis with its value per scenario, and `evaluation.robustness_table`'s columns; the report names the worst scenario (--map-episodes episodes per env).
 """
 import argparse
 import json
@@ -65,6 +69,22 @@ def evaluate_model(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dt
     return out
 
 
+def evaluate_grid(tables_dir, axes, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, episodes=1, **cfg_kw):
+    """The same tables scored under every scenario of the grid `axes` ({field: [values]}) in one launch; returns (arrays for the .npz, labels, table)."""
+    import numpy as np
+    from dql_multirotor_landing_amd import evaluation, ops
+    from dql_multirotor_landing_amd.config import scenario_grid
+    from dql_multirotor_landing_amd.double_q_learning import DoubleQLearningAgent
+    qa, qb, _ = DoubleQLearningAgent.load(Path(tables_dir))._padded()
+    cfgs, labels = scenario_grid(evaluation._flavour_config(flavour, level, dtype, cfg_kw), **axes)
+    r = ops.score_grid(cfgs, qa, qb, n_envs, seed, episodes=episodes, max_steps=max_steps, device=device)
+    t = evaluation.robustness_table(r, labels)
+    out = {"by_code": r["by_code"][:, 0], "steps_sum": r["steps_sum"][:, 0], "touch_hist": r["touch_hist"][:, 0], "touch_edges": r["touch_edges"], "columns": np.array(r["columns"])}
+    out.update({f"axis_{f}": np.array([lab[f] for lab in labels]) for f in axes})
+    out.update({f: t[f][:, 0] for f in ("rate", "mean_steps", "unfinished", "touch_centre", "touch_outside")})
+    return out, labels, t
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--tables", default=str(Path(__file__).resolve().parent.parent / "tests" / "golden" / "assets"))
@@ -82,7 +102,11 @@ if __name__ == "__main__":
     ap.add_argument("--map-episodes", type=int, default=1, help="episodes per env of the --map-out launch")
     ap.add_argument("--model-out", default=None, metavar="FILE.npz", help="save the empirical transition model of the tables' eps-greedy policy (dql_model)")
     ap.add_argument("--model-eps", type=float, default=0.1, help="exploration rate of the --model-out launch, in [0, 1]")
+    ap.add_argument("--grid-out", default=None, metavar="FILE.npz", help="save the tables' score over the grid of --grid scenarios, flown in one launch (dql_score_grid)")
+    ap.add_argument("--grid", action="append", default=[], metavar="FIELD=v1,v2,...", help="one axis of the --grid-out scenarios: a DqlConfig field and its values (repeatable)")
     a = ap.parse_args()
+    if bool(a.grid_out) != bool(a.grid):
+        ap.error("--grid-out FILE.npz and at least one --grid FIELD=v1,v2,... belong together")
     import __graft_entry__ as g
     g.build_hip()
     from dql_multirotor_landing_amd.config import Q_PAPER, Q_REFERENCE
@@ -116,5 +140,12 @@ if __name__ == "__main__":
         np.savez_compressed(a.model_out, **m)
         out["model"] = {"file": a.model_out, "eps": a.model_eps, "episodes_per_env": a.map_episodes, "decisions": int(m["visits"].sum()), "cells_visited": int((m["visits"] > 0).sum()),
                         "distinct_pairs": int((m["pairs"] > 0).sum()), "terminal_decisions": int(m["terminal"].sum())}
+    if a.grid_out:
+        import numpy as np
+        from dql_multirotor_landing_amd.config import parse_grid_axes
+        m, labels, t = evaluate_grid(a.tables, parse_grid_axes(a.grid), n, a.level, flavour=a.flavour, episodes=a.map_episodes, quirks=quirks)
+        np.savez_compressed(a.grid_out, **m)
+        out["grid"] = {"file": a.grid_out, "scenarios": len(labels), "episodes_per_env": a.map_episodes, "touchdown_rate": [round(float(x), 4) for x in m["rate"]],
+                       "labels": labels, "worst_scenario": labels[int(t["worst_scenario"][0])], "worst_touchdown_rate": float(t["worst_rate"][0])}
     out.update({"first_episode_outcomes": h, "touchdown_rate": h["TERMINAL_CONTACT"] / n, "goal_rate": h["TERMINAL_SUCCESS"] / n})
     print(json.dumps(out, indent=1))
