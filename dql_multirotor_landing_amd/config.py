@@ -215,6 +215,10 @@ class DqlConfig:
         With |r| <= R and tables that start within R / (1 - gamma) (zero, or the reference's stage-4 tables), every target and every
         fold (a convex combination of the cell and its mean target) stays within Q* = R / (1 - gamma).  2^-10 relative margin for the
         float32 reward's rounding.  inf for gamma >= 1."""
+        return math.inf if self.gamma >= 1.0 else self.max_abs_reward() / (1.0 - self.gamma) * (1.0 + 2.0 ** -10)
+
+    def max_abs_reward(self) -> float:
+        """R, the per-step bound on |reward| that max_abs_td_target is built on (its docstring has the terms): 26.0 for the default config"""
         dt = 1.0 / self.f_ag
         r = 0.0
         for k in range(MAX_LEVELS):
@@ -223,7 +227,7 @@ class DqlConfig:
             rd = abs(self.w_dur) * self.lim_v[k] * dt
             rth = abs(self.w_theta) * abs(self.w_theta) / self.theta_max * self.lim_v[k]
             r = max(r, rp + rv + rth + rd + max(abs(self.w_succ), abs(self.w_fail)) * (rp + rv + rth_max + rd))
-        return math.inf if self.gamma >= 1.0 else r / (1.0 - self.gamma) * (1.0 + 2.0 ** -10)
+        return r
 
     def accum_visit_limit(self) -> int:
         """Most targets one int64 accumulator cell may sum (fixed point, TARGET_FRAC_BITS fraction bits) without leaving int64:

@@ -42,6 +42,7 @@
 #include "dql_score.hpp"
 #include "dql_score_map.hpp"
 #include "dql_model.hpp"
+#include "dql_returns.hpp"
 #include "dql_score_grid.hpp"
 #include "../../include/dql_diag.h"
 
@@ -2078,6 +2079,7 @@ int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
 #include "dql_teams.inc"
 #include "dql_score_map.inc"
 #include "dql_model.inc"
+#include "dql_returns.inc"
 #include "dql_score_grid.inc"
 #include "dql_agent.inc"
 #include "dql_comm.inc"

@@ -386,6 +386,20 @@ class SequentialEnsemble:
                                                _p(steps_sum)))
         return ops.model_result(self.lib, pairs, reward_fx, terminal, by_code, steps_sum, timing)
 
+    def returns_map(self, eval_cfg: DqlConfig, envs_per_learner: int = 64, seed: int = 123, eps: float = 0.1, gamma: float = 0.99, episodes: int = 1, max_steps: int = 600,
+                    first: int = 0, count: Optional[int] = None, timing: dict = None):
+        """`ops.returns_map` of learners first .. first + count - 1 on their tables where they live (no host copy).  The ensemble is left as it was.  At most
+        ops.SCORE_MAP_MAX_TABLES learners per call, and count * envs_per_learner * (max_steps + 1) <= 2^29: slice with first / count."""
+        from . import ops
+        first, count = self._slice(first, count)
+        n, episodes, max_steps, eps, gamma = int(envs_per_learner), int(episodes), int(max_steps), float(eps), float(gamma)
+        ops.returns_check_args(eval_cfg, count, n, episodes, max_steps, eps, gamma)
+        visits, return_fx, cut, by_code, steps_sum = ops.returns_buffers(count)
+        c = eval_cfg.to_c()
+        _lib.check(self.lib.dql_ensemble_returns(self._h, C.byref(c), first, count, n, episodes, int(seed), max_steps, eps, gamma, _p(visits), _p(return_fx), _p(cut),
+                                                 _p(by_code), _p(steps_sum)))
+        return ops.returns_result(self.lib, visits, return_fx, cut, by_code, steps_sum, timing)
+
     def score_grid(self, eval_cfgs, envs_per_learner: int = 64, seed: int = 123, episodes: int = 1, max_steps: int = 600, log: bool = False, touch: bool = True,
                    first: int = 0, count: Optional[int] = None, timing: dict = None):
         """`ops.score_grid` of learners first .. first + count - 1 on their tables where they live (no host copy), under every config of `eval_cfgs` in one

@@ -315,6 +315,57 @@ def model_divergence(pairs_a, terminal_a, pairs_b, terminal_b, min_visits: int =
     return np.where(ok, tv, np.nan)
 
 
+def value_calibration(qa, qb, visits, return_fx, greedy=None, min_visits: int = 30):
+    """The tables' values held against the realised returns of `ops.returns_map` (one table set), pure numpy.  `qa`, `qb`: float64 [2835]; `visits`, `return_fx`:
+    int64 [2835]; `greedy`: the tables' greedy action per state, [945] (ops' predict), or None.  Returns a dict.  Per cell, float64 [2835]:
+      mean_return                  return_fx / visits / 2^26, NaN below `min_visits` (>= 1) visits
+      bias_a, bias_b, bias_mean    Q - mean_return for `qa`, `qb` and (qa + qb) / 2: positive = the table overestimates
+    and under `summary`, for each of "a", "b" and "mean", over the cells that have `min_visits`, weighted by their visits:
+      mean_bias, rms_bias                    floats (NaN if no cell qualifies)
+      mean_bias_by_level, rms_bias_by_level  float64 [5], by curriculum level cell // 567 (NaN for a level without such a cell)
+      overestimated_share                    the visit share of the cells whose bias is positive
+    plus `cells` (how many qualify) and `visits` (their visits).  With `greedy`: `agreement_states`, the states in which the greedy action and at least one
+    other action have `min_visits`, and `agreement_share`, the share of those in which the arg-max of the mean returns over the actions that qualify is the
+    greedy action (NaN if no state qualifies)."""
+    qa, qb = (np.asarray(t, dtype=np.float64).ravel() for t in (qa, qb))
+    visits, return_fx = (np.asarray(t, dtype=np.int64).ravel() for t in (visits, return_fx))
+    if not (qa.shape == qb.shape == visits.shape == return_fx.shape == (N_CELLS,)) or min_visits < 1 or (visits < 0).any():
+        raise ValueError("qa, qb, visits and return_fx must be [2835] (one table set), visits >= 0, min_visits >= 1")
+    ok = visits >= min_visits
+    mean_return = np.where(ok, return_fx / np.where(ok, visits, 1) / float(1 << TARGET_FRAC_BITS), np.nan)
+    out = {"mean_return": mean_return, "bias_a": qa - mean_return, "bias_b": qb - mean_return, "bias_mean": 0.5 * (qa + qb) - mean_return}
+    level = np.arange(N_CELLS) // 567
+    w = np.where(ok, visits, 0).astype(np.float64)
+
+    def weighted(bias, sel):
+        tot = w[sel].sum()
+        if tot <= 0.0:
+            return float("nan"), float("nan")
+        b = np.where(ok, bias, 0.0)[sel]
+        return float((w[sel] * b).sum() / tot), float(np.sqrt((w[sel] * b * b).sum() / tot))
+
+    summary = {"cells": int(ok.sum()), "visits": int(visits[ok].sum())}
+    everything = np.ones(N_CELLS, bool)
+    for name in ("a", "b", "mean"):
+        bias = out[f"bias_{name}"]
+        mean_bias, rms_bias = weighted(bias, everything)
+        per_level = [weighted(bias, level == k) for k in range(N_CELLS // 567)]
+        over = float(w[ok & (np.where(ok, bias, 0.0) > 0.0)].sum() / w.sum()) if w.sum() > 0.0 else float("nan")
+        summary[name] = {"mean_bias": mean_bias, "rms_bias": rms_bias, "mean_bias_by_level": np.array([p[0] for p in per_level]),
+                         "rms_bias_by_level": np.array([p[1] for p in per_level]), "overestimated_share": over}
+    if greedy is not None:
+        greedy = np.asarray(greedy, dtype=np.int64).ravel()
+        if greedy.shape != (N_CELLS // 3,) or (greedy < 0).any() or (greedy > 2).any():
+            raise ValueError("greedy must be [945] actions in 0..2")
+        ok3, m3 = ok.reshape(-1, 3), np.where(ok, mean_return, -np.inf).reshape(-1, 3)
+        states = np.arange(N_CELLS // 3)
+        compared = ok3[states, greedy] & (ok3.sum(axis=1) >= 2)
+        summary["agreement_states"] = int(compared.sum())
+        summary["agreement_share"] = float((m3.argmax(axis=1) == greedy)[compared].mean()) if compared.any() else float("nan")
+    out["summary"] = summary
+    return out
+
+
 def robustness_table(result, labels, column: str = "TERMINAL_CONTACT"):
     """What an `ops.score_grid` result says per (scenario, table set), pure numpy.  `result`: a dict with `by_code` [S, K, len(ops.SCORE_COLUMNS)], `steps_sum`
     [S, K] and, optionally, `touch_hist` [S, K, 8]; `labels`: one label per scenario (`config.scenario_grid`'s dicts).  Returns a dict of float64 [S, K] arrays:

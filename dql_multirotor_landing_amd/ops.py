@@ -3,11 +3,12 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
 from . import _lib
-from .config import CHECK_NAMES, DqlConfig, N_CELLS, Q_REFERENCE
+from .config import CHECK_NAMES, DqlConfig, N_CELLS, Q_REFERENCE, TARGET_FRAC_BITS
 
 
 def _p(a):
@@ -526,3 +527,68 @@ def score_grid(cfgs, qa, qb, envs_per_table: int, seed: int, episodes: int = 1, 
     _lib.check(lib.dql_score_grid(c, len(cfgs), device, K, n, episodes, int(seed), max_steps, _p(qa), _p(qb), _p(by_code), _p(steps_sum),
                                   None if touch_hist is None else _p(touch_hist), None if ep_code is None else _p(ep_code), None if ep_steps is None else _p(ep_steps)))
     return grid_result(lib, cfgs, by_code, steps_sum, touch_hist, ep_code, ep_steps, timing)
+
+
+RETURNS_MAX_LOG_WORDS = 1 << 29  # include/dql.h: the decision log is one 64-bit word per possible decision, 4 GiB there
+
+
+def returns_bound_fx(cfg: DqlConfig, gamma: float, max_steps: int) -> int:
+    """ceil(B 2^26), B = R min(1 / (1 - gamma), max_steps + 1) (1 + 2^-10) with R = cfg.max_abs_reward(): no |return-to-go| in fixed point exceeds it"""
+    horizon = float(max_steps + 1) if gamma >= 1.0 else min(1.0 / (1.0 - gamma), float(max_steps + 1))
+    return math.ceil(cfg.max_abs_reward() * horizon * (1.0 + 2.0 ** -10) * float(1 << TARGET_FRAC_BITS))
+
+
+def returns_check_args(cfg: DqlConfig, n_tables: int, envs_per_table: int, episodes: int, max_steps: int, eps: float, gamma: float):
+    """the argument checks of dql_returns / dql_ensemble_returns, made before the library is touched"""
+    if cfg.two_axis:
+        raise ValueError("the returns are the x MDP's (the reward is not kept per axis): a two-axis config is refused")
+    if not 1 <= n_tables <= SCORE_MAP_MAX_TABLES:
+        raise ValueError(f"between 1 and {SCORE_MAP_MAX_TABLES} table sets per returns call, not {n_tables}: slice the sets")
+    score_check_args(n_tables, envs_per_table, episodes, max_steps)
+    if n_tables * envs_per_table * (max_steps + 1) > RETURNS_MAX_LOG_WORDS:
+        raise ValueError(f"table sets x envs x (max_steps + 1) must be at most 2^29 (the decision log: one 64-bit word each), not {n_tables * envs_per_table * (max_steps + 1)}")
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"eps must be in [0, 1], not {eps}")
+    if not 0.0 <= gamma <= 1.0:
+        raise ValueError(f"gamma must be in [0, 1], not {gamma}")
+    bound = returns_bound_fx(cfg, gamma, max_steps)
+    if (bound + 1) * envs_per_table * (max_steps + 1) > (1 << 63) - 1:
+        raise ValueError(f"{envs_per_table * (max_steps + 1)} returns of up to {bound} * 2^-26 could overflow one int64 cell of return_fx (at most "
+                         f"{((1 << 63) - 1) // (bound + 1)} decisions per table set): fly fewer envs per call and add the results of several seeds")
+
+
+def returns_buffers(n_tables: int):
+    """(visits, return_fx, cut_decisions, by_code, steps_sum) as the C calls fill them"""
+    return (np.zeros((n_tables, N_CELLS), np.int64), np.zeros((n_tables, N_CELLS), np.int64), np.zeros(n_tables, np.int64),
+            np.zeros((n_tables, len(SCORE_COLUMNS)), np.int64), np.zeros(n_tables, np.int64))
+
+
+def returns_result(lib, visits, return_fx, cut_decisions, by_code, steps_sum, timing):
+    if timing is not None:
+        fly, sweep, inst = C.c_double(), C.c_double(), (C.c_int32 * 3)()
+        _lib.check(lib.dql_diag_returns_last(C.byref(fly), C.byref(sweep), inst))
+        timing["fly_ms"], timing["sweep_ms"] = fly.value, sweep.value
+        timing["instance"] = f"k_returns_fly<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    return {"visits": visits, "return_fx": return_fx, "cut_decisions": cut_decisions, "by_code": by_code, "steps_sum": steps_sum, "columns": SCORE_COLUMNS}
+
+
+def returns_map(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, eps: float, gamma: float, episodes: int = 1, max_steps: int = 600, device: int = 0,
+                timing: dict = None):
+    """The realised discounted return of every decision, summed per (state, action) cell, under the eps-greedy policy of K table sets (include/dql.h dql_returns,
+    DESIGN.md section 21): what `evaluation.value_calibration` holds against the tables' own values.
+
+    `qa`, `qb`: float64 [K, 2835] (one set: [2835]).  The flights are `transition_model`'s.  For every decision of an episode that finished, with cell = state
+    before the period * 3 + action, `visits` int64 [K, 2835] gains 1 and `return_fx` int64 [K, 2835] the return-to-go g_t = r_t + gamma g_{t+1} (float64, in
+    units of 2^-26, g = 0 after the terminal period) rounded to nearest even.  Decisions of episodes that `max_steps` cut off are counted in `cut_decisions`
+    int64 [K] and nowhere else.  `by_code` and `steps_sum` are `score`'s.  Integer sums: bit-reproducible.  `timing`: receives `fly_ms`, `sweep_ms`, `instance`."""
+    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
+    if qa.ndim != 2 or qa.shape[1] != N_CELLS or qb.shape != qa.shape:
+        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    K, n, episodes, max_steps, eps, gamma = len(qa), int(envs_per_table), int(episodes), int(max_steps), float(eps), float(gamma)
+    returns_check_args(cfg, K, n, episodes, max_steps, eps, gamma)
+    lib = _lib.load()
+    visits, return_fx, cut, by_code, steps_sum = returns_buffers(K)
+    c = cfg.to_c()
+    _lib.check(lib.dql_returns(C.byref(c), device, K, n, episodes, int(seed), max_steps, eps, gamma, _p(qa), _p(qb), _p(visits), _p(return_fx), _p(cut), _p(by_code),
+                               _p(steps_sum)))
+    return returns_result(lib, visits, return_fx, cut, by_code, steps_sum, timing)

@@ -458,6 +458,27 @@ int dql_score_map(const dql_config* cfg, int device, int64_t n_tables, int64_t e
 #define DQL_MODEL_MAX_TABLES 16
 int dql_model(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps, double eps,
               const double* qa, const double* qb, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code, int64_t* steps_sum);
+/* ---- realised discounted returns per (state, action) cell, to be held against the Q tables ----
+ * dql_returns flies exactly what dql_model flies, counted the same way: table set k, env i with the RNG key (i, seed), periods 0 .. max_steps, the eps-greedy
+ * rule of dql_model's contract on the fixed tables (eps = 0: the greedy policy), and an env counts in a period as in dql_score_map.  Take the counted decisions
+ * of env i in period order; each carries a cell c_t = idx_x before the period * 3 + action, the period's reward_fx r_t (int64: reward * 2^26 rounded to nearest
+ * even, as dql_model has it) and the flag "this period ended the episode".  For every episode of the env that FINISHED, with decisions t = 0 .. L - 1, the
+ * return-to-go in units of 2^-26 is defined backwards in IEEE double: g_L = 0.0, g_t = (double)r_t + (gamma * g_{t+1}) — two operations, each rounded to
+ * nearest, never fused.  Decision t then adds
+ *   visits         int64 [n_tables][DQL_N_CELLS]: 1 at c_t
+ *   return_fx      int64 [n_tables][DQL_N_CELLS]: llrint(g_t) at c_t (round to nearest even)
+ * Decisions of an episode that max_steps cuts off contribute to neither (their return is not known); they are counted in
+ *   cut_decisions  int64 [n_tables]
+ * by_code / steps_sum are dql_score's and, for equal arguments, dql_model's; visits.sum() + cut_decisions equals dql_model's visits.sum().  Integer sums of
+ * per-lane deterministic values: bit-reproducible in any arrival order.  gamma is an argument, not cfg->gamma.
+ * DQL_EINVAL (and no launch) for a two_axis config, n_tables outside 1..DQL_SCORE_MAP_MAX_TABLES, envs_per_table not a positive multiple of 64,
+ * episodes_per_env or max_steps outside dql_score's ranges, eps or gamma outside [0, 1] (NaN included), a null pointer, n_tables * envs_per_table *
+ * (max_steps + 1) > 2^29 (the decision log is one 64-bit word per possible decision: 4 GiB there), and when one int64 cell of return_fx could overflow: with R
+ * the per-step reward bound of the config (26.0 by default) and B = R min(1 / (1 - gamma), max_steps + 1) (1 + 2^-10), when (ceil(B 2^26) + 1) *
+ * envs_per_table * (max_steps + 1) > 2^63 - 1.  Sums of several calls with different seeds add: the caller slices.  DQL_ESTATE (no result) if a range check
+ * in the kernels dropped a contribution. */
+int dql_returns(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps, double eps,
+                double gamma, const double* qa, const double* qb, int64_t* visits, int64_t* return_fx, int64_t* cut_decisions, int64_t* by_code, int64_t* steps_sum);
 /* ---- greedy scoring over a grid of scenarios: S configs x K table sets in one launch, with the landing precision of the touchdowns ----
  * The equality contract: slice s of every output is what dql_score(&cfgs[s], ...) returns for the same remaining arguments — in turn the stepwise context of
  * dql_score's own contract: dql_create(&cfgs[s], device, envs_per_table, seed, 0) with the tables of set k, then dql_eval_steps(ctx, 1) for periods 0 ..
@@ -622,6 +643,11 @@ int dql_ensemble_score_map(dql_ensemble* ens, const dql_config* eval_cfg, int64_
 int dql_ensemble_model(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
                        uint64_t seed, int32_t max_steps, double eps, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code,
                        int64_t* steps_sum);
+/* dql_returns on the tables of learners [first, first + count): outputs and refusals as for dql_returns (count in place of n_tables; the slice must lie
+ * inside the ensemble).  The ensemble is left exactly as it was. */
+int dql_ensemble_returns(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
+                         uint64_t seed, int32_t max_steps, double eps, double gamma, int64_t* visits, int64_t* return_fx, int64_t* cut_decisions,
+                         int64_t* by_code, int64_t* steps_sum);
 /* dql_score_grid on the tables of learners [first, first + count): outputs and refusals as for dql_score_grid (count in place of n_tables; the slice must lie
  * inside the ensemble).  The ensemble is left exactly as it was. */
 int dql_ensemble_score_grid(dql_ensemble* ens, const dql_config* eval_cfgs /* [n_scenarios] */, int32_t n_scenarios, int64_t first, int64_t count,

@@ -5,6 +5,7 @@ pair of Q tables in the vectorised simulator and reports how the episodes end.
     python scripts/simulation.py [--tables DIR] [--envs 4096] [--level 4] [--flavour simulation|training] [--mode paper|reference]
                                  [--rollout] [--report] [--trace-out FILE.npz [--trace-envs 8]] [--map-out FILE.npz [--map-episodes 1]]
                                  [--model-out FILE.npz [--model-eps 0.1]] [--grid-out FILE.npz --grid FIELD=v1,v2,... [--grid ...]]
+                                 [--returns-out FILE.npz [--returns-eps 0.1] [--returns-gamma 0.99]]
 Default tables: tests/golden/assets (a data copy of the reference's stage-4 policy).
 --rollout flies all first episodes in one launch (dql_rollout) instead of one launch per agent period; --report prints what the episodes looked like at
 their end (the counterpart of the `info` dictionary the reference prints per episode, scripts/simulation.py:52-56) and --trace-out saves the per-period
@@ -14,6 +15,10 @@ flight record of the first envs; both imply --rollout.
 --model-out writes the empirical transition model of the discretised MDP under the tables' eps-greedy policy (dql_model): `pairs`
 [2835, 945], `reward_fx` [2835], `terminal` [2835, codes] and `visits` [2835], with `by_code`, `columns`, `steps_sum` and `eps` (--model-eps; --map-episodes
 episodes per env).
+--returns-out writes the realised discounted returns of the tables' eps-greedy policy per (state, action) cell and what they say about the tables' values
+(dql_returns): `visits` [2835] and `return_fx` [2835] (the returns-to-go of the finished episodes' decisions, summed, in units of 2^-26),
+`cut_decisions`, `by_code`, `columns`, `steps_sum`, `eps`, `gamma`, and `evaluation.value_calibration`'s per-cell arrays `mean_return`, `bias_a`, `bias_b`,
+`bias_mean` (Q minus mean return; NaN below 30 visits); the report carries its summary (--map-episodes episodes per env).
 --grid-out scores the tables over the Cartesian product of the --grid axes in ONE launch (dql_score_grid): `--grid mp_t_x=0.8,1.2,1.6 --grid
 trajectory=0,1` flies six scenarios that differ from the flavour's config in those fields only (the first axis varies slowest).  The file holds `by_code`
 [S, codes + 1], `steps_sum` [S], `touch_hist` [S, 8] (touchdowns by their offset from the platform centre), `touch_edges` [S, 7], `columns`, one array per
@@ -69,6 +74,21 @@ def evaluate_model(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dt
     return out
 
 
+def evaluate_returns(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, episodes=1, eps=0.1, gamma=0.99, **cfg_kw):
+    """The realised returns of the same flights under the tables' eps-greedy policy and the calibration of the tables against them; returns (arrays, summary)."""
+    import numpy as np
+    from dql_multirotor_landing_amd import evaluation, ops
+    from dql_multirotor_landing_amd.double_q_learning import DoubleQLearningAgent
+    qa, qb, _ = DoubleQLearningAgent.load(Path(tables_dir))._padded()
+    cfg = evaluation._flavour_config(flavour, level, dtype, cfg_kw)
+    r = ops.returns_map(cfg, qa, qb, n_envs, seed, eps, gamma, episodes=episodes, max_steps=max_steps, device=device)
+    cal = evaluation.value_calibration(qa, qb, r["visits"][0], r["return_fx"][0], greedy=evaluation.greedy_actions(qa, qb)[0])
+    out = {f: r[f][0] for f in ("visits", "return_fx", "cut_decisions", "by_code", "steps_sum")}
+    out.update({"columns": np.array(r["columns"]), "eps": np.float64(eps), "gamma": np.float64(gamma)})
+    out.update({f: cal[f] for f in ("mean_return", "bias_a", "bias_b", "bias_mean")})
+    return out, cal["summary"]
+
+
 def evaluate_grid(tables_dir, axes, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, episodes=1, **cfg_kw):
     """The same tables scored under every scenario of the grid `axes` ({field: [values]}) in one launch; returns (arrays for the .npz, labels, table)."""
     import numpy as np
@@ -102,6 +122,9 @@ if __name__ == "__main__":
     ap.add_argument("--map-episodes", type=int, default=1, help="episodes per env of the --map-out launch")
     ap.add_argument("--model-out", default=None, metavar="FILE.npz", help="save the empirical transition model of the tables' eps-greedy policy (dql_model)")
     ap.add_argument("--model-eps", type=float, default=0.1, help="exploration rate of the --model-out launch, in [0, 1]")
+    ap.add_argument("--returns-out", default=None, metavar="FILE.npz", help="save the realised returns per cell of the tables' eps-greedy policy and the tables' calibration (dql_returns)")
+    ap.add_argument("--returns-eps", type=float, default=0.1, help="exploration rate of the --returns-out launch, in [0, 1]")
+    ap.add_argument("--returns-gamma", type=float, default=0.99, help="discount of the --returns-out returns, in [0, 1]")
     ap.add_argument("--grid-out", default=None, metavar="FILE.npz", help="save the tables' score over the grid of --grid scenarios, flown in one launch (dql_score_grid)")
     ap.add_argument("--grid", action="append", default=[], metavar="FIELD=v1,v2,...", help="one axis of the --grid-out scenarios: a DqlConfig field and its values (repeatable)")
     a = ap.parse_args()
@@ -140,6 +163,13 @@ if __name__ == "__main__":
         np.savez_compressed(a.model_out, **m)
         out["model"] = {"file": a.model_out, "eps": a.model_eps, "episodes_per_env": a.map_episodes, "decisions": int(m["visits"].sum()), "cells_visited": int((m["visits"] > 0).sum()),
                         "distinct_pairs": int((m["pairs"] > 0).sum()), "terminal_decisions": int(m["terminal"].sum())}
+    if a.returns_out:
+        import numpy as np
+        m, summary = evaluate_returns(a.tables, n, a.level, flavour=a.flavour, episodes=a.map_episodes, eps=a.returns_eps, gamma=a.returns_gamma, quirks=quirks)
+        np.savez_compressed(a.returns_out, **m)
+        as_json = lambda v: {k: as_json(x) for k, x in v.items()} if isinstance(v, dict) else ([round(float(x), 4) for x in v] if isinstance(v, np.ndarray) else v)
+        out["returns"] = {"file": a.returns_out, "eps": a.returns_eps, "gamma": a.returns_gamma, "episodes_per_env": a.map_episodes, "decisions_kept": int(m["visits"].sum()),
+                          "decisions_cut": int(m["cut_decisions"]), "cells_visited": int((m["visits"] > 0).sum()), "calibration": as_json(summary)}
     if a.grid_out:
         import numpy as np
         from dql_multirotor_landing_amd.config import parse_grid_axes
