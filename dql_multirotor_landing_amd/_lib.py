@@ -195,6 +195,9 @@ SYMBOLS = {
     # teams of envs per learner
     "dql_ensemble_create_teams": (C.c_int, [_cfgp, C.c_int, _i64, _i32, _u64, _i32, C.POINTER(_vp)]),
     "dql_ensemble_envs_per_learner": (C.c_int, [_vp, C.POINTER(_i32)]),
+    # n-step targets
+    "dql_ensemble_set_nstep": (C.c_int, [_vp, _i32]),
+    "dql_ensemble_get_nstep": (C.c_int, [_vp, C.POINTER(_i32), _vp]),
 }
 MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS
 

@@ -124,6 +124,10 @@ struct dql_ensemble {
   struct EnsRecipes* rcp = nullptr;  // per-learner recipes (DESIGN.md section 16, dql_recipes.inc); null: none are installed and every call is as it was
   // teams (DESIGN.md section 17, dql_teams.inc): learner l owns envs l E .. l E + E - 1 of the n_envs = n E the state arrays hold; teams: dql_ensemble_run flies k_learn_team
   int envs_per_learner = 1; long long n_envs = 0; bool teams = false;
+  // n-step targets (DESIGN.md section 22, dql_nstep.inc); nstep = 0: dql_ensemble_run flies k_learn and the arrays below are never read.  The learners' pending
+  // windows between launches: key / val [DQL_NSTEP_MAX][n], len [n], allocated by the first dql_ensemble_set_nstep with n >= 1
+  int nstep = 0;
+  uint16_t* ns_key = nullptr; double* ns_val = nullptr; int* ns_len = nullptr;
 };
 // of dql_recipes.inc: the installed recipes let go, the rule learner l advances by, the smallest last_level of the populated recipes, dql_ensemble_run's loop
 static void ens_recipes_release(dql_ensemble* x);
@@ -132,6 +136,9 @@ static int ens_recipes_min_last_level(const dql_ensemble* x);
 static int ens_run_recipes(dql_ensemble* x, int64_t periods);
 // of dql_teams.inc: one launch of k_learn_team (ens_fly's part for a team ensemble)
 static int ens_launch_teams(dql_ensemble* x, int k, int n_waves);
+// of dql_nstep.inc: one launch of k_learn_nstep (ens_fly's part while nstep >= 1)
+static int ens_launch_nstep(dql_ensemble* x, int k, int n_waves);
+#define ENS_NSTEP_REFUSED(who) "" who ": n-step targets (dql_ensemble_set_nstep with n >= 1) are for the plain mode, where every learner flies the config's level; set n = 0 first; nothing was changed and nothing was launched"
 #define ENS_TEAMS_REFUSED(who) "" who ": an ensemble with more than one env per learner flies the barrier mode only (teams have no per-learner curriculum and no recipes); nothing was changed and nothing was launched"
 #define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
 static void ens_free(dql_ensemble* x) {
@@ -191,6 +198,7 @@ static int ens_fly(dql_ensemble* x, int k, int n_waves, bool by_level) {
   by_dtype(x->cfg.dtype, [&](auto t) {
     using T = decltype(t);
     if (x->teams && !by_level) return;  // k_learn_team, below (with one env per learner a team ensemble in curriculum mode flies k_learn_levels: the same learner)
+    if (x->nstep && !by_level) return;  // k_learn_nstep, below (n >= 1 is refused on team ensembles and in curriculum mode)
     if (by_level) {
       LearnLevelsArgs<T> g;
       g.a = make_learn_args<T>(x, x->mdpk5, k);
@@ -201,6 +209,7 @@ static int ens_fly(dql_ensemble* x, int k, int n_waves, bool by_level) {
     }
   });
   if (x->teams && !by_level) { rc = ens_launch_teams(x, k, n_waves); if (rc) return rc; }
+  else if (x->nstep && !by_level) { rc = ens_launch_nstep(x, k, n_waves); if (rc) return rc; }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += (long long)n_waves * k;
@@ -333,6 +342,7 @@ int dql_ensemble_set_level(dql_ensemble* x, int32_t k) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   rc = ens_set_levels(x, k); if (rc) return rc;
+  if (x->ns_len) HIP_TRY(hipMemset(x->ns_len, 0, (size_t)x->n * sizeof(int)));  // every env re-enters through reset: the pending windows belong to episodes that are gone
   return ens_rearm(x);
 }
 int dql_ensemble_n_live(dql_ensemble* x, int64_t* n_live) {
@@ -445,6 +455,7 @@ int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t adv
     x->advance_every = 0;
     return DQL_OK;
   }
+  if (x->nstep) return fail(DQL_EINVAL, ENS_NSTEP_REFUSED("dql_ensemble_set_curriculum"));
   if (!ratios) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: null ratios; nothing was changed");
   for (int k = 0; k < DQL_MAX_LEVELS; ++k) if (!std::isfinite(ratios[k])) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the five transfer ratios must be finite; nothing was changed");
   if (advance_exhausted != 0 && advance_exhausted != 1) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_exhausted must be 0 or 1; nothing was changed");

@@ -44,6 +44,7 @@
 #include "dql_model.hpp"
 #include "dql_returns.hpp"
 #include "dql_score_grid.hpp"
+#include "dql_nstep.hpp"
 #include "../../include/dql_diag.h"
 
 using namespace dql;
@@ -2077,6 +2078,7 @@ int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
 #include "dql_ensemble.inc"
 #include "dql_recipes.inc"
 #include "dql_teams.inc"
+#include "dql_nstep.inc"
 #include "dql_score_map.inc"
 #include "dql_model.inc"
 #include "dql_returns.inc"

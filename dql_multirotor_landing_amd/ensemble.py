@@ -25,6 +25,8 @@ MAX_LEARNERS = 1 << 20         # DQL_ENSEMBLE_MAX_LEARNERS
 MAX_LEVELS = 5
 MAX_ADVANCE_EVERY = 4096       # csrc/dql_advance.hpp ADV_MAX_EVERY
 MAX_RECIPES = 64               # include/dql.h DQL_ENSEMBLE_MAX_RECIPES
+NSTEP_MAX = 16                 # include/dql.h DQL_NSTEP_MAX
+NSTEP_PLAIN_ONLY = "n-step targets (nstep >= 1) are for the plain mode, where every learner flies the config's level: no teams, no per-learner curriculum, no recipes"
 TEAM_SIZES = (1, 2, 4, 8, 16, 32, 64)  # envs per learner (include/dql.h dql_ensemble_create_teams): a team is consecutive lanes of one wave
 TEAMS_BARRIER_ONLY = "an ensemble with more than one env per learner flies the barrier mode only (train_level / curriculum): teams have no per-learner curriculum and no recipes"
 ORDER_REFERENCE, ORDER_PAPER = 0, 1  # Recipe.transfer_order
@@ -130,8 +132,9 @@ class Recipe:
 
 class SequentialEnsemble:
     def __init__(self, cfg: DqlConfig, n_learners: int, seed: int = 42, device: int = 0, log_capacity: int = 0, alpha_table=None, eps=None, window: int = 100,
-                 min_successes: Optional[int] = None, max_episodes: int = 50000, envs_per_learner: int = 1, teams: Optional[bool] = None):
-        """envs_per_learner: E envs per learner (`TEAM_SIZES`), whose transitions the learner takes in env order every period; learner l
+                 min_successes: Optional[int] = None, max_episodes: int = 50000, envs_per_learner: int = 1, teams: Optional[bool] = None, nstep: int = 0):
+        """nstep: 0 for the reference's one-step update, 1..NSTEP_MAX for the n-step return as the target (`set_nstep`).
+        envs_per_learner: E envs per learner (`TEAM_SIZES`), whose transitions the learner takes in env order every period; learner l
         owns envs l E .. l E + E - 1 and `state()` returns [L E] arrays.  teams: create through dql_ensemble_create_teams (the team kernel) — default: when E > 1;
         True with E = 1 flies the team kernel with teams of one, which equals the plain ensemble bit for bit."""
         n_learners, log_capacity, envs_per_learner = int(n_learners), int(log_capacity), int(envs_per_learner)
@@ -148,6 +151,7 @@ class SequentialEnsemble:
             raise ValueError(f"n_learners must be positive and n_learners * envs_per_learner at most {MAX_LEARNERS}")
         if log_capacity < 0:
             raise ValueError("log_capacity must not be negative")
+        self._check_nstep(int(nstep), teams)
         self.lib = _lib.load()
         self.cfg = cfg
         self.n = n_learners
@@ -160,7 +164,10 @@ class SequentialEnsemble:
         else:
             _lib.check(self.lib.dql_ensemble_create(C.byref(self._c), int(device), self.n, int(seed), log_capacity, C.byref(h)))
         self._h = h
+        self._nstep, self._advance_every = 0, 0
         self.set_schedules(alpha_table, eps, window, min_successes, max_episodes)
+        if int(nstep):
+            self.set_nstep(nstep)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -198,6 +205,35 @@ class SequentialEnsemble:
     def rearm(self):
         _lib.check(self.lib.dql_ensemble_rearm(self._h))
 
+    # ---- n-step targets (include/dql.h) ----
+    @staticmethod
+    def _check_nstep(n: int, teams: bool, curriculum: bool = False):
+        if not 0 <= n <= NSTEP_MAX:
+            raise ValueError(f"nstep must be in 0..{NSTEP_MAX} (0: the one-step update)")
+        if n >= 1 and (teams or curriculum):
+            raise ValueError(NSTEP_PLAIN_ONLY)
+
+    def set_nstep(self, n: int):
+        """n = 0: `run` flies the one-step kernel, as after creation.  1 <= n <= NSTEP_MAX: every learner updates with the uncorrected n-step Double-Q return of
+        its pending window (include/dql.h); n = 1 equals n = 0 bit for bit.  Refused on a team ensemble, in per-learner curriculum or recipe mode, and
+        (by the library) while a learner's window holds entries: change n after creation, after `set_level`, or when every learner is frozen."""
+        n = int(n)
+        self._check_nstep(n, getattr(self, "teams", False) or getattr(self, "envs_per_learner", 1) > 1, bool(getattr(self, "_advance_every", 0)) or bool(getattr(self, "_recipes", [])))
+        _lib.check(self.lib.dql_ensemble_set_nstep(self._h, n))
+        self._nstep = n
+
+    @property
+    def nstep(self) -> int:
+        v = C.c_int32()
+        _lib.check(self.lib.dql_ensemble_get_nstep(self._h, C.byref(v), None))
+        return int(v.value)
+
+    def pending_lengths(self) -> np.ndarray:
+        """int32 [L]: the entries in each learner's pending window (0 with nstep = 0, for a frozen learner, and right after `set_level`)"""
+        v, out = C.c_int32(), np.zeros(self.n, dtype=np.int32)
+        _lib.check(self.lib.dql_ensemble_get_nstep(self._h, C.byref(v), _p(out)))
+        return out
+
     # ---- per-learner curriculum levels (include/dql.h, DESIGN.md section 14) ----
     def set_curriculum(self, last_level: int = 4, advance_every: int = MAX_ADVANCE_EVERY, ratios=None, advance_exhausted: bool = True):
         """Curriculum mode: at every period index that is a multiple of `advance_every`, a frozen learner below `last_level` that promoted (or ran out of
@@ -208,6 +244,8 @@ class SequentialEnsemble:
             raise ValueError(TEAMS_BARRIER_ONLY)
         if not 0 <= advance_every <= MAX_ADVANCE_EVERY:
             raise ValueError(f"advance_every must be in 0..{MAX_ADVANCE_EVERY}")
+        if advance_every and getattr(self, "_nstep", 0):
+            raise ValueError(NSTEP_PLAIN_ONLY)
         r = np.ascontiguousarray(REFERENCE_RATIOS if ratios is None else ratios, dtype=np.float64).ravel()
         if advance_every:
             if not 0 <= last_level < MAX_LEVELS:
@@ -215,6 +253,7 @@ class SequentialEnsemble:
             if r.size != MAX_LEVELS or not np.isfinite(r).all():
                 raise ValueError("ratios must be five finite numbers")
         _lib.check(self.lib.dql_ensemble_set_curriculum(self._h, last_level, advance_every, _p(r), 1 if advance_exhausted else 0))
+        self._advance_every = advance_every
 
     def set_level_schedules(self, level: int, eps=None, window: int = 100, min_successes: Optional[int] = None, max_episodes: int = 50000):
         """`set_schedules` without the learning rates, for the learners that stand on `level` in curriculum mode (eps default: the reference's for it)"""
@@ -255,6 +294,8 @@ class SequentialEnsemble:
             raise ValueError(TEAMS_BARRIER_ONLY)
         if len(recipes) > MAX_RECIPES:
             raise ValueError(f"at most {MAX_RECIPES} recipes")
+        if recipes and getattr(self, "_nstep", 0):
+            raise ValueError(NSTEP_PLAIN_ONLY)
         if not recipes:
             _lib.check(self.lib.dql_ensemble_set_recipes(self._h, 0, None))
             self._recipes = []
@@ -494,10 +535,13 @@ def train_level(ens: SequentialEnsemble, chunk_periods: int = 16 * MAX_PERIODS_P
 
 
 def curriculum(ens: SequentialEnsemble, levels: int = 5, first_level: int = 0, ratios=None, max_episodes: Optional[int] = None, max_periods_per_level: Optional[int] = None,
-               window: int = 100, success_rate: float = 0.96, on_level=None):
+               window: int = 100, success_rate: float = 0.96, on_level=None, nstep: Optional[int] = None):
     """`Trainer.curriculum_training` for the ensemble: per level, run until all learners are frozen, `transfer_learning` of the finished level with the
-    reference's ratio, next level.  -> per level, the counters at its end."""
+    reference's ratio, next level.  -> per level, the counters at its end.  nstep: `ens.set_nstep(nstep)` before the first level (the windows must be
+    empty: a fresh ensemble, or one whose learners are all frozen); None leaves the ensemble's setting."""
     from .trainer import Trainer
+    if nstep is not None:
+        ens.set_nstep(nstep)
     me = SimpleNamespace(_scale_modification_value=(0.8172650252856599, 0.8211253690681617, 0.8257273369742982, 0.8311571820651724))
     history = []
     for k in range(int(first_level), int(levels)):

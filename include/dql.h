@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DQL_ABI_VERSION 6 /* 6: dql_agent_mirror_update_deferred / _complete (added since, without a new number: dql_ensemble_set_curriculum, _set_level_schedules, _get_levels, _n_unfinished; dql_ensemble_set_recipes, _set_recipe, _set_recipe_level_schedules, _get_recipes; dql_ensemble_create_teams, _envs_per_learner); 5: tick replay operators (dql_*_run), measurement symbols moved to dql_diag.h as dql_diag_* */
+#define DQL_ABI_VERSION 6 /* 6: dql_agent_mirror_update_deferred / _complete (added since, without a new number: dql_ensemble_set_curriculum, _set_level_schedules, _get_levels, _n_unfinished; dql_ensemble_set_recipes, _set_recipe, _set_recipe_level_schedules, _get_recipes; dql_ensemble_create_teams, _envs_per_learner; dql_ensemble_set_nstep, _get_nstep); 5: tick replay operators (dql_*_run), measurement symbols moved to dql_diag.h as dql_diag_* */
 
 typedef enum dql_status {
   DQL_OK = 0,
@@ -731,6 +731,34 @@ int dql_ensemble_get_recipes(dql_ensemble* ens, int32_t* recipe_of);
 int dql_ensemble_create_teams(const dql_config* cfg, int device, int64_t n_learners, int32_t envs_per_learner, uint64_t seed, int32_t log_capacity,
                               dql_ensemble** out);
 int dql_ensemble_envs_per_learner(dql_ensemble* ens, int32_t* envs_per_learner); /* 1 for dql_ensemble_create's */
+
+/* ---- n-step Double-Q targets for the plain sequential ensemble ----
+ * dql_ensemble_set_nstep(ens, n): n = 0, the state at creation, lets dql_ensemble_run fly the one-step kernel exactly as before; 1 <= n <= DQL_NSTEP_MAX
+ * makes it fly the n-step kernel (n = 1 included, which equals n = 0 bit for bit).  The period schedule, the action rule (STREAM_ACTION word, per-learner
+ * eps threshold, greedy choice on the learner's current tables), reset periods, counters, the episode log, the promotion ring and the freeze rules do not
+ * change; only the update does.
+ * Each learner keeps a PENDING WINDOW of at most n entries (cell, reward, coin), one per decision of the current episode, oldest first: cell = idx_x before
+ * the period * 3 + action, reward = the env's reward field as a double, coin = bit 31 of the third word of that decision's action draw.  After a decision
+ * that ended in state s': (1) its entry is appended; (2) both tables' row of s' is read once, before this period's first write; (3) mask = "the position
+ * bin of the newest entry's state differs from that of s'" under DQL_Q_BOOTSTRAP_ON_POS_CHANGE, !done otherwise; (4) if the period ended the episode every
+ * entry is updated, oldest first, and the window emptied; else if the window holds n entries the oldest is updated and removed; else nothing is updated.
+ * The update of the entry at position k of a window of m entries (0 = oldest): sel_b = Double Q-learning and the ENTRY's coin (never under
+ * DQL_Q_UPDATE_TABLE_A_ONLY); best = the valuing table's element of the row of s' at the arg-max of the selecting table's row, tables assigned as in the
+ * one-step update; g = best * mask, then for i = m - 1 down to k: g = r_i + (gamma * g), IEEE double, two roundings per step, never contracted; alpha at
+ * the cell's pre-increment count, which is then incremented; q_new = q + alpha * (g - q) on the selected table.  A cell outside [0, 2835) is counted in
+ * dql_ensemble_index_faults and dropped.  A write to the row of the state the env is in now also reaches the next period's greedy choice, whichever entry
+ * made it.
+ * A learner freezes only at an episode's end, after the flush: a frozen learner's window is empty.  A window that is open at a launch's end persists, so
+ * runs of a and b periods equal one run of a + b.  dql_ensemble_set_level discards every window (every env re-enters through reset); dql_ensemble_rearm,
+ * _transfer and _set_tables leave them alone.
+ * Refused with a message, nothing launched and nothing changed: DQL_EINVAL for n outside 0..DQL_NSTEP_MAX, for n >= 1 on a team ensemble
+ * (dql_ensemble_create_teams), and for n >= 1 in per-learner curriculum mode or with recipes installed (and dql_ensemble_set_curriculum with
+ * advance_every > 0 and dql_ensemble_set_recipes with n_recipes > 0 while n >= 1); DQL_ESTATE for any change of n while some learner's window holds
+ * entries (allowed after creation, after dql_ensemble_set_level, or when every learner is frozen); a null pointer.
+ * dql_ensemble_get_nstep returns the setting and, where asked for, the windows' lengths (int32 [n_learners]). */
+#define DQL_NSTEP_MAX 16
+int dql_ensemble_set_nstep(dql_ensemble* ens, int32_t n);
+int dql_ensemble_get_nstep(dql_ensemble* ens, int32_t* n, int32_t* pending_len_or_null);
 
 #ifdef __cplusplus
 }

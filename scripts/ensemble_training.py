@@ -45,7 +45,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from dql_multirotor_landing_amd.config import F32, F64, Q_REFERENCE, as_launched_config, training_config  # noqa: E402
 from dql_multirotor_landing_amd import evaluation  # noqa: E402
-from dql_multirotor_landing_amd.ensemble import (LevelSchedule, ORDER_PAPER, ORDER_REFERENCE, REFERENCE_RATIOS, Recipe, SequentialEnsemble, TEAM_SIZES, curriculum,  # noqa: E402
+from dql_multirotor_landing_amd.ensemble import (LevelSchedule, NSTEP_MAX, ORDER_PAPER, ORDER_REFERENCE, REFERENCE_RATIOS, Recipe, SequentialEnsemble, TEAM_SIZES, curriculum,  # noqa: E402
                                                  curriculum_per_learner, curriculum_recipes, exploration_rates, min_successes_for, train_level)
 
 RECIPE_KEYS = {"preset", "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min", "levels"}
@@ -231,6 +231,7 @@ def main():
     ap.add_argument("--score-map", action="store_true", help="with --score: also count where every learner's greedy policy flies, and report it against the reference's tables")
     ap.add_argument("--score-grid", action="append", default=[], metavar="FIELD=v1,v2,...", help="with --score: also score every learner over this grid of scenarios in one launch (repeatable)")
     ap.add_argument("--preset", default="reference", choices=["reference", "paper"], help="quirks and transfer order of the level-by-level driver (not with --per-learner / --recipes)")
+    ap.add_argument("--nstep", type=int, default=0, metavar="N", help="n-step Double-Q targets, 1..16 (0: the reference's one-step update; not with --per-learner / --recipes / --envs-per-learner above 1)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     if a.preset != "reference" and (a.per_learner or a.recipes):
@@ -245,10 +246,14 @@ def main():
         ap.error(f"--envs-per-learner must be one of {', '.join(map(str, TEAM_SIZES))}")
     if a.envs_per_learner > 1 and (a.per_learner or a.recipes):
         ap.error("--envs-per-learner above 1 cannot be combined with --per-learner or --recipes: teams fly the level-by-level (barrier) driver only")
+    if not 0 <= a.nstep <= NSTEP_MAX:
+        ap.error(f"--nstep must be in 0..{NSTEP_MAX}")
+    if a.nstep and (a.per_learner or a.recipes or a.envs_per_learner > 1):
+        ap.error("--nstep cannot be combined with --per-learner, --recipes or --envs-per-learner above 1: n-step targets fly the level-by-level (barrier) driver with one env per learner only")
     dtype = F64 if a.f64 else F32
     quirks = evaluation.Q_PAPER if a.preset == "paper" else Q_REFERENCE
     cfg = as_launched_config(dtype=dtype, quirks=quirks) if a.launched else training_config(0, dtype=dtype, quirks=quirks)
-    ens = SequentialEnsemble(cfg, a.learners, seed=a.seed, device=a.device, max_episodes=a.episodes, envs_per_learner=a.envs_per_learner)
+    ens = SequentialEnsemble(cfg, a.learners, seed=a.seed, device=a.device, max_episodes=a.episodes, envs_per_learner=a.envs_per_learner, nstep=a.nstep)
     try:
         def report(e, h):
             p = h["promotion_episode"]
@@ -296,7 +301,7 @@ def main():
             if a.score_json:
                 Path(a.score_json).write_text(json.dumps(rep) + "\n")
         qa, qb, cnt = ens.get_tables()
-        np.savez_compressed(a.out, Q_table_a=qa, Q_table_b=qb, state_action_counter=cnt, **extra,
+        np.savez_compressed(a.out, Q_table_a=qa, Q_table_b=qb, state_action_counter=cnt, nstep=np.int32(a.nstep), **extra,
                             promotion_episode=np.stack([h["promotion_episode"] for h in hist]), periods=np.array([h["periods"] for h in hist]))
     finally:
         ens.close()
