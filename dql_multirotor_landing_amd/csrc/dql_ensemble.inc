@@ -1,7 +1,7 @@
 // dql_ensemble.inc: ensembles of sequential Double-Q learners (include/dql.h dql_ensemble_*, DESIGN.md sections 12 and 14): the lane kernels, struct dql_ensemble
 // and its C calls.  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype, OP_PROLOGUE, DevOwned, upload_mdpk,
 // upload_schedule, EvTimer, quads_to_fields / unpack_ints, check_config, InitArgs / k_init, k_mark_reset, TickLds; dql_learner.hpp, dql_advance.hpp; and
-// score_check / score_run of dql_greedy.inc (dql_ensemble_score).  dql_recipes.inc, included after this file, holds the per-learner recipes (DESIGN.md section 16).
+// score_check / score_run / TableSets of dql_greedy.inc (dql_ensemble_score, tables_of_slice).  dql_recipes.inc, included after this file, holds the per-learner recipes (DESIGN.md section 16).
 // ---- sequential learners (dql_ensemble, DESIGN.md section 12) ----
 // One learner per lane (csrc/dql_learner.hpp: learner_periods), workgroups of one wave as in k_rollout; the env stays in registers for all periods of the launch,
 // the tables are the lane's own [DQL_N_CELLS] slices (per-lane global pointers, ordinary vector loads and stores, no atomics).
@@ -141,6 +141,15 @@ static int ens_launch_nstep(dql_ensemble* x, int k, int n_waves);
 #define ENS_NSTEP_REFUSED(who) "" who ": n-step targets (dql_ensemble_set_nstep with n >= 1) are for the plain mode, where every learner flies the config's level; set n = 0 first; nothing was changed and nothing was launched"
 #define ENS_TEAMS_REFUSED(who) "" who ": an ensemble with more than one env per learner flies the barrier mode only (teams have no per-learner curriculum and no recipes); nothing was changed and nothing was launched"
 #define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
+// the tables of learners [first, first + count) where they live, for the dql_ensemble_* twins of the greedy family (TableSets of dql_greedy.inc; count >= 1 is the
+// twin's own check): the ensemble's device becomes the current one, nothing is copied
+static int tables_of_slice(const char* who, dql_ensemble* x, int64_t first, int64_t count, TableSets& q) {
+  if (first < 0 || first > x->n || count > x->n - first)
+    return fail(DQL_EINVAL, std::string(who) + ": the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
+  HIP_TRY(hipSetDevice(x->device));
+  q.qa = x->mem.qa + (size_t)first * DQL_N_CELLS; q.qb = x->mem.qb + (size_t)first * DQL_N_CELLS;
+  return DQL_OK;
+}
 static void ens_free(dql_ensemble* x) {
   ens_recipes_release(x);
   x->dev.free_all();
@@ -619,10 +628,9 @@ int dql_ensemble_score(dql_ensemble* x, const dql_config* eval_cfg, int64_t firs
   CHECK_ENS(x);
   int rc = check_config(eval_cfg); if (rc) return rc;
   rc = score_check("dql_ensemble_score", count, envs_per_learner, episodes_per_env, max_steps, by_code, steps_sum, ep_code_or_null, ep_steps_or_null); if (rc) return rc;
-  if (first < 0 || first > x->n || count > x->n - first) return fail(DQL_EINVAL, "dql_ensemble_score: the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t off = (size_t)first * DQL_N_CELLS;
-  return score_run(eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, x->mem.qa + off, x->mem.qb + off, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
+  TableSets q;
+  rc = tables_of_slice("dql_ensemble_score", x, first, count, q); if (rc) return rc;
+  return score_run(eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, q, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
 }
 int dql_diag_ensemble_launches(dql_ensemble* x, int64_t* launches, int64_t* periods, int64_t* wave_periods) {
   CHECK_ENS(x);

@@ -1,6 +1,8 @@
 // dql_greedy.inc: greedy flight of given tables in one launch: the roll-outs with flight records (dql_rollout, DESIGN.md section 11) and the scorer (dql_score,
-// DESIGN.md section 13; score_check / score_run also serve dql_ensemble_score).  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail /
-// HIP_TRY, by_dtype_axes, DevBuf / OP_PROLOGUE / UP / OUT / DOWN, upload_mdpk, upload_schedule, EvTimer, check_config, TickLds; and dql_rollout.hpp, dql_score.hpp.
+// DESIGN.md section 13; score_check / score_run also serve dql_ensemble_score), and the host helpers every greedy-flight operator shares (DESIGN.md section 15:
+// TableSets, Flight, Sums, EpisodeLog, RangeFaults, LastCall / diag_last, timed_launch, fill_flight_args / fill_greedy_args).  A fragment of dql_hip.hip's translation
+// unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype_axes, DevBuf / OP_PROLOGUE / UP / OUT / DOWN, mdpk_bytes, upload_mdpk, upload_schedule, EvTimer,
+// check_config, TickLds; and dql_rollout.hpp, dql_score.hpp.
 // ---- greedy roll-outs (dql_rollout, DESIGN.md section 11) ----
 // One env per lane flies its FIRST episode from reset to termination (csrc/dql_rollout.hpp: rollout_episode); workgroups of one wave: evaluation batches are
 // small, a lone wave per SIMD needs no LDS staging, no barrier, and there are no accumulators, table-writer blocks or statistics here.  Table set k serves
@@ -97,22 +99,123 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   }
 }
 
-// what RolloutArgs<T> and ScoreArgs<T> have in common (mgr0 / sched: device arrays of upload_schedule, mdpk: of upload_mdpk)
-template <typename T, typename A> static void fill_greedy_args(A& a, const dql_config& cfg, const void* mdpk, const double* qa, const double* qb, const void* mgr0, const void* sched,
-                                                               unsigned long long seed, long long envs_per_table, int max_steps) {
+// ---- shared host helpers of the greedy family (DESIGN.md section 15): what the host side of dql_rollout, dql_score, dql_score_map, dql_model, dql_returns and
+// dql_score_grid, and of their dql_ensemble_* twins, does in the same way ----
+// the tables a call flies, [n_tables][DQL_N_CELLS] on the current device: uploaded from the host (from_host owns the copies), or a slice of an ensemble's own
+// arrays (tables_of_slice, next to struct dql_ensemble)
+struct TableSets {
+  DevBuf a, b;
+  const double* qa = nullptr; const double* qb = nullptr;
+  int from_host(const char* who, int device, long long n_tables, const double* h_qa, const double* h_qb) {
+    if (!h_qa || !h_qb) return fail(DQL_EINVAL, std::string(who) + ": null array; nothing was launched");
+    OP_PROLOGUE(device)
+    const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
+    UP(a, h_qa, TB); UP(b, h_qb, TB);
+    qa = (const double*)a.p; qb = (const double*)b.p;
+    return DQL_OK;
+  }
+};
+// the tick schedule of periods 0 .. max_steps and the config's MdpK (score_grid: the schedule only, it uploads one MdpK per scenario into `mdp` itself)
+struct Flight {
+  DevBuf mgr0, sched, mdp;
+  int setup(const dql_config& cfg, int max_steps, bool with_mdp = true) {
+    const int n_per = max_steps + 1;
+    OUT(mgr0, (size_t)n_per * sizeof(long long)); OUT(sched, (size_t)n_per * sizeof(int));
+    if (with_mdp) OUT(mdp, mdpk_bytes(cfg.dtype));
+    const int rc = upload_schedule(cfg, 0, n_per, mgr0.p, sched.p); if (rc) return rc;
+    return with_mdp ? upload_mdpk(cfg, mdp.p) : DQL_OK;
+  }
+};
+// one zeroed buffer of 64-bit sums, declared slice by slice; a slice is handed to the kernel and downloaded with the size it was declared with
+struct Sums {
+  struct Slice { size_t at, n; };
+  DevBuf buf;
+  size_t n_words = 0;
+  Slice add(size_t n) { const Slice s{n_words, n}; n_words += n; return s; }
+  int alloc_zeroed() {
+    OUT(buf, n_words * sizeof(unsigned long long));
+    HIP_TRY(hipMemset(buf.p, 0, n_words * sizeof(unsigned long long)));
+    return DQL_OK;
+  }
+  unsigned long long* dev(Slice s) const { return (unsigned long long*)buf.p + s.at; }
+  struct To { int64_t* host; Slice s; };
+  int down(std::initializer_list<To> parts) const {  // a null host array (an optional output) is skipped
+    for (const To& t : parts) if (t.host) HIP_TRY(hipMemcpy(t.host, dev(t.s), t.s.n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return DQL_OK;
+  }
+};
+// the optional episode log, `entries` each of ep_code (0xff: not finished) and ep_steps (0); without one the device pointers are null
+struct EpisodeLog {
+  DevBuf code, steps;
+  size_t entries = 0;
+  bool on = false;
+  int setup(bool wanted, size_t n) {
+    on = wanted; entries = n;
+    if (!on) return DQL_OK;
+    OUT(code, entries); OUT(steps, entries * sizeof(uint16_t));
+    HIP_TRY(hipMemset(code.p, 0xff, entries));  // not finished
+    HIP_TRY(hipMemset(steps.p, 0, entries * sizeof(uint16_t)));
+    return DQL_OK;
+  }
+  int down(uint8_t* ep_code, uint16_t* ep_steps) const {
+    if (!on) return DQL_OK;
+    DOWN(ep_code, code, entries);
+    DOWN(ep_steps, steps, entries * sizeof(uint16_t));
+    return DQL_OK;
+  }
+};
+// the word a kernel counts in what its range checks dropped (0 unless a bug): read back after the launch, non-zero refuses the result
+struct RangeFaults {
+  const unsigned long long* d = nullptr; const char* who = ""; const char* whose = "kernel's"; const char* what = "contributions";
+  int refuse_if_any() const {
+    if (!d) return DQL_OK;
+    unsigned long long faults = 0ull;
+    HIP_TRY(hipMemcpy(&faults, d, sizeof(faults), hipMemcpyDeviceToHost));
+    if (faults) return fail(DQL_ESTATE, std::string(who) + ": the " + whose + " range checks dropped " + std::to_string(faults) + " " + what + " (a bug); no result was returned");
+    return DQL_OK;
+  }
+};
+// kernel time(s) and instance (sizeof(T), TICK, XMODE) of a thread's latest completed call of one operator: a *_run fills a local one and stores it on DQL_OK only
+struct LastCall {
+  double ms = -1.0, ms2 = 0.0;  // ms2: the second stretch of the returns
+  int inst[3] = {0, 0, 0};
+  template <typename T> void instance(int tick, int xmode) { inst[0] = (int)sizeof(T); inst[1] = tick; inst[2] = xmode; }
+};
+static int diag_last(const LastCall& c, double* ms, double* ms2, int32_t* out3, const char* none_yet) {
+  if (!ms || !ms2 || !out3) return fail(DQL_EINVAL, "null pointer");
+  if (c.ms < 0.0) return fail(DQL_ESTATE, none_yet);
+  *ms = c.ms; *ms2 = c.ms2;
+  for (int k = 0; k < 3; ++k) out3[k] = c.inst[k];
+  return DQL_OK;
+}
+static int diag_last(const LastCall& c, double* kernel_ms, int32_t* out3, const char* none_yet) { double unused = 0.0; return diag_last(c, kernel_ms, &unused, out3, none_yet); }
+// the launch bracket: timer start, launch() (the typed hipLaunchKernelGGL and nothing else), hipGetLastError, timer stop, then the range-check word if there is one
+template <typename L> static int timed_launch(L&& launch, double* ms, const RangeFaults& faults = RangeFaults{}) {
+  EvTimer timer;
+  int rc = timer.start(); if (rc) return rc;
+  launch();
+  HIP_TRY(hipGetLastError());
+  rc = timer.stop_ms(ms); if (rc) return rc;
+  return faults.refuse_if_any();
+}
+// the kernel arguments every greedy-flight kernel has, and (fill_greedy_args) the ones made from the call's one config
+template <typename A> static void fill_flight_args(A& a, const TableSets& q, const Flight& fl, unsigned long long seed, long long envs_per_table, int max_steps) {
+  a.qa = q.qa; a.qb = q.qb;
+  a.mgr0 = (const long long DQL_CONST_AS*)fl.mgr0.p; a.sched = (const int DQL_CONST_AS*)fl.sched.p;
+  a.seed = seed; a.blocks_per_table = (int)(envs_per_table / 64); a.max_steps = max_steps;
+}
+template <typename T, typename A> static void fill_greedy_args(A& a, const dql_config& cfg, const TableSets& q, const Flight& fl, unsigned long long seed, long long envs_per_table,
+                                                               int max_steps) {
   a.c = make_simk<T>(cfg);
-  a.mdp = (const MdpK<T> DQL_CONST_AS*)mdpk;
+  a.mdp = (const MdpK<T> DQL_CONST_AS*)fl.mdp.p;
   a.mdp_run = MdpRun<T>{cfg.gamma, (T)(cfg.t_max * cfg.f_ag), cfg.goal_logic};
   a.init = make_rollout_init<T>(cfg);
-  a.qa = qa; a.qb = qb;
-  a.mgr0 = (const long long DQL_CONST_AS*)mgr0; a.sched = (const int DQL_CONST_AS*)sched;
-  a.seed = seed; a.blocks_per_table = (int)(envs_per_table / 64); a.max_steps = max_steps;
+  fill_flight_args(a, q, fl, seed, envs_per_table, max_steps);
 }
 
 extern "C" {
 // ---- greedy roll-outs ----
-static thread_local double g_rollout_ms = -1.0;
-static thread_local int g_rollout_inst[3] = {0, 0, 0};
+static thread_local LastCall g_rollout_last;
 int dql_rollout_n_fields(int32_t* n_record, int32_t* n_trace) { if (n_record) *n_record = RO_N_RECORD; if (n_trace) *n_trace = RO_N_TRACE; return DQL_OK; }
 const char* dql_rollout_field_name(int32_t i, int32_t is_trace) { return (i >= 0 && i < (is_trace ? RO_N_TRACE : RO_N_RECORD)) ? k_rollout_field_names[i] : nullptr; }
 int dql_rollout(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, uint64_t seed, int32_t max_steps, const double* qa, const double* qb,
@@ -125,57 +228,44 @@ int dql_rollout(const dql_config* cfg, int device, int32_t n_tables, int64_t env
   if (max_steps < 1 || max_steps > DQL_ROLLOUT_MAX_STEPS) return fail(DQL_EINVAL, "dql_rollout: max_steps must be in 1..4096 (DQL_ROLLOUT_MAX_STEPS); nothing was launched");
   if (trace_envs < 0 || trace_envs > 64) return fail(DQL_EINVAL, "dql_rollout: trace_envs must be in 0..64 (the trace stays inside one wave); nothing was launched");
   if (trace_envs > 0 && !trace_or_null) return fail(DQL_EINVAL, "dql_rollout: trace_envs > 0 needs a trace buffer; nothing was launched");
-  if (!qa || !qb || !code || !steps || !rec) return fail(DQL_EINVAL, "dql_rollout: null array; nothing was launched");
-  OP_PROLOGUE(device)
+  if (!code || !steps || !rec) return fail(DQL_EINVAL, "dql_rollout: null array; nothing was launched");
+  TableSets q;
+  rc = q.from_host("dql_rollout", device, n_tables, qa, qb); if (rc) return rc;
   const long long n_total = (long long)n_tables * envs_per_table;
-  const int n_per = max_steps + 1;
-  DevBuf d_qa, d_qb, d_mgr0, d_sched, d_mdp, d_code, d_steps, d_rec, d_trace;
-  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
-  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
-  OUT(d_mgr0, (size_t)n_per * sizeof(long long)); OUT(d_sched, (size_t)n_per * sizeof(int)); OUT(d_mdp, mdpk_bytes(cfg->dtype));
-  rc = upload_schedule(*cfg, 0, n_per, d_mgr0.p, d_sched.p); if (rc) return rc;
-  rc = upload_mdpk(*cfg, d_mdp.p); if (rc) return rc;
+  Flight fl;
+  rc = fl.setup(*cfg, max_steps); if (rc) return rc;
+  DevBuf d_code, d_steps, d_rec, d_trace;
   OUT(d_code, (size_t)n_total * sizeof(int)); OUT(d_steps, (size_t)n_total * sizeof(int)); OUT(d_rec, (size_t)RO_N_RECORD * n_total * sizeof(double));
-  const size_t trace_bytes = (size_t)n_per * RO_N_TRACE * (size_t)trace_envs * sizeof(double);
+  const size_t trace_bytes = (size_t)(max_steps + 1) * RO_N_TRACE * (size_t)trace_envs * sizeof(double);
   if (trace_envs > 0) {
     OUT(d_trace, trace_bytes);
     HIP_TRY(hipMemset(d_trace.p, 0xff, trace_bytes));  // all ones = NaN: what a row keeps after its env's last period
   }
   const RolloutOut out{(int*)d_code.p, (int*)d_steps.p, (double*)d_rec.p, trace_envs > 0 ? (double*)d_trace.p : nullptr, n_total, trace_envs};
-  EvTimer timer;
-  rc = timer.start(); if (rc) return rc;
-  by_dtype_axes(cfg->dtype, cfg->two_axis, [&](auto t, auto xmode) {
-    using T = decltype(t);
-    constexpr int XMODE = decltype(xmode)::value;
-    RolloutArgs<T> a;
-    fill_greedy_args<T>(a, *cfg, d_mdp.p, (const double*)d_qa.p, (const double*)d_qb.p, d_mgr0.p, d_sched.p, seed, envs_per_table, max_steps);
-    a.out = out;
-    g_rollout_inst[0] = (int)sizeof(T); g_rollout_inst[1] = TICK_PLAIN; g_rollout_inst[2] = XMODE;
-    hipLaunchKernelGGL((k_rollout<T, TICK_PLAIN, XMODE>), dim3((unsigned)((long long)n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
-  });
-  HIP_TRY(hipGetLastError());
-  double ms = 0.0;
-  rc = timer.stop_ms(&ms); if (rc) return rc;
+  LastCall call;
+  rc = timed_launch([&] {
+    by_dtype_axes(cfg->dtype, cfg->two_axis, [&](auto t, auto xmode) {
+      using T = decltype(t);
+      constexpr int XMODE = decltype(xmode)::value;
+      RolloutArgs<T> a;
+      fill_greedy_args<T>(a, *cfg, q, fl, seed, envs_per_table, max_steps);
+      a.out = out;
+      call.instance<T>(TICK_PLAIN, XMODE);
+      hipLaunchKernelGGL((k_rollout<T, TICK_PLAIN, XMODE>), dim3((unsigned)((long long)n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
+    });
+  }, &call.ms);
+  if (rc) return rc;
   DOWN(code, d_code, (size_t)n_total * sizeof(int));
   DOWN(steps, d_steps, (size_t)n_total * sizeof(int));
   DOWN(rec, d_rec, (size_t)RO_N_RECORD * n_total * sizeof(double));
   if (trace_envs > 0) DOWN(trace_or_null, d_trace, trace_bytes);
-  g_rollout_ms = ms;
+  g_rollout_last = call;
   return DQL_OK;
 }
-// kernel time and instance (sizeof(T), TICK, XMODE) of this thread's latest completed call
-static int diag_last(double ms, const int* inst, double* kernel_ms, int32_t* out3, const char* none_yet) {
-  if (!kernel_ms || !out3) return fail(DQL_EINVAL, "null pointer");
-  if (ms < 0.0) return fail(DQL_ESTATE, none_yet);
-  *kernel_ms = ms;
-  for (int k = 0; k < 3; ++k) out3[k] = inst[k];
-  return DQL_OK;
-}
-int dql_diag_rollout_last(double* kernel_ms, int32_t* out3) { return diag_last(g_rollout_ms, g_rollout_inst, kernel_ms, out3, "no dql_rollout call has completed on this thread"); }
+int dql_diag_rollout_last(double* kernel_ms, int32_t* out3) { return diag_last(g_rollout_last, kernel_ms, out3, "no dql_rollout call has completed on this thread"); }
 
 // ---- greedy scoring ----
-static thread_local double g_score_ms = -1.0;
-static thread_local int g_score_inst[3] = {0, 0, 0};
+static thread_local LastCall g_score_last;
 // every argument both entry points share, checked before the device is touched: a refused call starts no kernel
 static int score_check(const char* who, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, int32_t max_steps, const int64_t* by_code, const int64_t* steps_sum,
                        const uint8_t* ep_code, const uint16_t* ep_steps) {
@@ -189,61 +279,42 @@ static int score_check(const char* who, int64_t n_tables, int64_t envs_per_table
   if (!by_code || !steps_sum) return fail(DQL_EINVAL, w + ": null array; nothing was launched");
   return DQL_OK;
 }
-// d_qa / d_qb: [n_tables][DQL_N_CELLS] on the current device
-static int score_run(const dql_config* cfg, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, const double* d_qa, const double* d_qb,
-                     int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code, uint16_t* ep_steps) {
+static int score_run(const dql_config* cfg, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, const TableSets& q, int64_t* by_code,
+                     int64_t* steps_sum, uint8_t* ep_code, uint16_t* ep_steps) {
   const long long n_total = n_tables * envs_per_table;
-  const int n_per = max_steps + 1;
-  DevBuf d_mgr0, d_sched, d_mdp, d_sums, d_code, d_steps;
-  OUT(d_mgr0, (size_t)n_per * sizeof(long long)); OUT(d_sched, (size_t)n_per * sizeof(int)); OUT(d_mdp, mdpk_bytes(cfg->dtype));
-  int rc = upload_schedule(*cfg, 0, n_per, d_mgr0.p, d_sched.p); if (rc) return rc;
-  rc = upload_mdpk(*cfg, d_mdp.p); if (rc) return rc;
-  // one buffer for both sums: [n_tables][SCORE_N_COLS] counts, then [n_tables] step totals
-  const size_t sums_bytes = (size_t)n_tables * (SCORE_N_COLS + 1) * sizeof(unsigned long long);
-  OUT(d_sums, sums_bytes);
-  HIP_TRY(hipMemset(d_sums.p, 0, sums_bytes));
-  const size_t log_n = (size_t)episodes * (size_t)n_total;
-  if (ep_code) {
-    OUT(d_code, log_n); OUT(d_steps, log_n * sizeof(uint16_t));
-    HIP_TRY(hipMemset(d_code.p, 0xff, log_n));  // not finished
-    HIP_TRY(hipMemset(d_steps.p, 0, log_n * sizeof(uint16_t)));
-  }
-  unsigned long long* d_by_code = (unsigned long long*)d_sums.p;
-  unsigned long long* d_steps_sum = d_by_code + (size_t)n_tables * SCORE_N_COLS;
-  const ScoreLog log{(uint8_t*)d_code.p, (uint16_t*)d_steps.p, n_total};
-  EvTimer timer;
-  rc = timer.start(); if (rc) return rc;
-  by_dtype_axes(cfg->dtype, cfg->two_axis, [&](auto t, auto xmode) {
-    using T = decltype(t);
-    constexpr int XMODE = decltype(xmode)::value;
-    ScoreArgs<T> a;
-    fill_greedy_args<T>(a, *cfg, d_mdp.p, d_qa, d_qb, d_mgr0.p, d_sched.p, seed, envs_per_table, max_steps);
-    a.by_code = d_by_code; a.steps_sum = d_steps_sum; a.log = log; a.episodes = episodes;
-    g_score_inst[0] = (int)sizeof(T); g_score_inst[1] = TICK_PLAIN; g_score_inst[2] = XMODE;
-    hipLaunchKernelGGL((k_score<T, TICK_PLAIN, XMODE>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
-  });
-  HIP_TRY(hipGetLastError());
-  double ms = 0.0;
-  rc = timer.stop_ms(&ms); if (rc) return rc;
-  HIP_TRY(hipMemcpy(by_code, d_by_code, (size_t)n_tables * SCORE_N_COLS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(steps_sum, d_steps_sum, (size_t)n_tables * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (ep_code) {
-    DOWN(ep_code, d_code, log_n);
-    DOWN(ep_steps, d_steps, log_n * sizeof(uint16_t));
-  }
-  g_score_ms = ms;
+  Flight fl;
+  int rc = fl.setup(*cfg, max_steps); if (rc) return rc;
+  Sums sums;
+  const Sums::Slice s_by_code = sums.add((size_t)n_tables * SCORE_N_COLS), s_steps = sums.add((size_t)n_tables);
+  rc = sums.alloc_zeroed(); if (rc) return rc;
+  EpisodeLog elog;
+  rc = elog.setup(ep_code != nullptr, (size_t)episodes * (size_t)n_total); if (rc) return rc;
+  const ScoreLog log{(uint8_t*)elog.code.p, (uint16_t*)elog.steps.p, n_total};
+  LastCall call;
+  rc = timed_launch([&] {
+    by_dtype_axes(cfg->dtype, cfg->two_axis, [&](auto t, auto xmode) {
+      using T = decltype(t);
+      constexpr int XMODE = decltype(xmode)::value;
+      ScoreArgs<T> a;
+      fill_greedy_args<T>(a, *cfg, q, fl, seed, envs_per_table, max_steps);
+      a.by_code = sums.dev(s_by_code); a.steps_sum = sums.dev(s_steps); a.log = log; a.episodes = episodes;
+      call.instance<T>(TICK_PLAIN, XMODE);
+      hipLaunchKernelGGL((k_score<T, TICK_PLAIN, XMODE>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
+    });
+  }, &call.ms);
+  if (rc) return rc;
+  rc = sums.down({{by_code, s_by_code}, {steps_sum, s_steps}}); if (rc) return rc;
+  rc = elog.down(ep_code, ep_steps); if (rc) return rc;
+  g_score_last = call;
   return DQL_OK;
 }
 int dql_score(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
               const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null) {
   int rc = check_config(cfg); if (rc) return rc;
   rc = score_check("dql_score", n_tables, envs_per_table, episodes_per_env, max_steps, by_code, steps_sum, ep_code_or_null, ep_steps_or_null); if (rc) return rc;
-  if (!qa || !qb) return fail(DQL_EINVAL, "dql_score: null array; nothing was launched");
-  OP_PROLOGUE(device)
-  DevBuf d_qa, d_qb;
-  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
-  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
-  return score_run(cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, (const double*)d_qa.p, (const double*)d_qb.p, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
+  TableSets q;
+  rc = q.from_host("dql_score", device, n_tables, qa, qb); if (rc) return rc;
+  return score_run(cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, q, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
 }
-int dql_diag_score_last(double* kernel_ms, int32_t* inst3) { return diag_last(g_score_ms, g_score_inst, kernel_ms, inst3, "no dql_score or dql_ensemble_score call has completed on this thread"); }
+int dql_diag_score_last(double* kernel_ms, int32_t* inst3) { return diag_last(g_score_last, kernel_ms, inst3, "no dql_score or dql_ensemble_score call has completed on this thread"); }
 }  // extern "C"

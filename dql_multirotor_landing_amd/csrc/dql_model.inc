@@ -1,7 +1,7 @@
 // dql_model.inc: the empirical transition model of the discretised x MDP under an eps-greedy policy on fixed tables (dql_model / dql_ensemble_model, DESIGN.md
-// section 19).  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype, DevBuf / OP_PROLOGUE / UP / OUT,
-// upload_mdpk, upload_schedule, EvTimer, check_config, TickLds, eps_threshold; fill_greedy_args / score_check / diag_last of dql_greedy.inc; struct dql_ensemble /
-// CHECK_ENS of dql_ensemble.inc; and dql_model.hpp.
+// section 19).  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype, DevBuf / OUT / DOWN, check_config, TickLds,
+// eps_threshold; score_check and the family's host helpers of dql_greedy.inc (TableSets, Flight, Sums, RangeFaults, LastCall / diag_last, timed_launch,
+// fill_greedy_args); struct dql_ensemble / CHECK_ENS / tables_of_slice of dql_ensemble.inc; and dql_model.hpp.
 // k_score_map's shape — one env per lane, workgroups of one wave, table set k serves blocks [k B, (k + 1) B), env i of every set has RNG key (i, seed), the same
 // waves_per_eu.  Where the counts go:
 //   pairs     the pair table of a set (uint32 [DQL_N_CELLS][DQL_N_STATES], 10.7 MB) does not fit LDS: returnless 32-bit atomic adds into global memory.  Lanes
@@ -105,8 +105,7 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
 }
 
 extern "C" {
-static thread_local double g_model_ms = -1.0;
-static thread_local int g_model_inst[3] = {0, 0, 0};
+static thread_local LastCall g_model_last;
 // everything both entry points share, checked before the device is touched: a refused call starts no kernel
 static int model_check(const char* who, const dql_config* cfg, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, int32_t max_steps, double eps,
                        const uint32_t* pairs, const int64_t* reward_fx, const int64_t* terminal, const int64_t* by_code, const int64_t* steps_sum) {
@@ -121,64 +120,43 @@ static int model_check(const char* who, const dql_config* cfg, int64_t n_tables,
   if (!(eps >= 0.0 && eps <= 1.0)) return fail(DQL_EINVAL, w + ": eps must be in [0, 1]; nothing was launched");
   return DQL_OK;
 }
-// d_qa / d_qb: [n_tables][DQL_N_CELLS] on the current device
 static int model_run(const char* who, const dql_config* cfg, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, double eps,
-                     const double* d_qa, const double* d_qb, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code, int64_t* steps_sum) {
-  const int n_per = max_steps + 1;
-  DevBuf d_mgr0, d_sched, d_mdp, d_sums, d_pairs;
-  OUT(d_mgr0, (size_t)n_per * sizeof(long long)); OUT(d_sched, (size_t)n_per * sizeof(int)); OUT(d_mdp, mdpk_bytes(cfg->dtype));
-  int rc = upload_schedule(*cfg, 0, n_per, d_mgr0.p, d_sched.p); if (rc) return rc;
-  rc = upload_mdpk(*cfg, d_mdp.p); if (rc) return rc;
-  // one buffer for all 64-bit sums: [n_tables][SCORE_N_COLS] counts, [n_tables] step totals, [n_tables][DQL_N_CELLS] rewards, [n_tables][DQL_N_CELLS]
-  // [DQL_N_CHECK_CODES] terminals, [1] faults; the pair tables in one of their own
-  const size_t n_sums = (size_t)n_tables * (SCORE_N_COLS + 1 + DQL_N_CELLS + (size_t)DQL_N_CELLS * DQL_N_CHECK_CODES) + 1;
-  const size_t n_pairs = (size_t)n_tables * DQL_N_CELLS * DQL_N_STATES;
-  OUT(d_sums, n_sums * sizeof(unsigned long long)); OUT(d_pairs, n_pairs * sizeof(unsigned));
-  HIP_TRY(hipMemset(d_sums.p, 0, n_sums * sizeof(unsigned long long)));
-  HIP_TRY(hipMemset(d_pairs.p, 0, n_pairs * sizeof(unsigned)));
-  unsigned long long* d_by_code = (unsigned long long*)d_sums.p;
-  unsigned long long* d_steps_sum = d_by_code + (size_t)n_tables * SCORE_N_COLS;
-  unsigned long long* d_reward = d_steps_sum + (size_t)n_tables;
-  unsigned long long* d_terminal = d_reward + (size_t)n_tables * DQL_N_CELLS;
-  unsigned long long* d_faults = d_terminal + (size_t)n_tables * DQL_N_CELLS * DQL_N_CHECK_CODES;
-  EvTimer timer;
-  rc = timer.start(); if (rc) return rc;
-  int inst[3] = {0, 0, 0};
-  by_dtype(cfg->dtype, [&](auto t) {
-    using T = decltype(t);
-    ModelArgs<T> a;
-    fill_greedy_args<T>(a, *cfg, d_mdp.p, d_qa, d_qb, d_mgr0.p, d_sched.p, seed, envs_per_table, max_steps);
-    a.pairs = (unsigned*)d_pairs.p; a.reward_fx = d_reward; a.terminal = d_terminal; a.by_code = d_by_code; a.steps_sum = d_steps_sum; a.faults = d_faults;
-    a.eps_thr = eps_threshold(eps); a.episodes = episodes; a.n_tables = (int)n_tables;
-    inst[0] = (int)sizeof(T); inst[1] = TICK_PLAIN; inst[2] = X_ONLY;
-    hipLaunchKernelGGL((k_model<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
-  });
-  HIP_TRY(hipGetLastError());
-  double ms = 0.0;
-  rc = timer.stop_ms(&ms); if (rc) return rc;
-  unsigned long long faults = 0ull;
-  HIP_TRY(hipMemcpy(&faults, d_faults, sizeof(faults), hipMemcpyDeviceToHost));
-  if (faults) return fail(DQL_ESTATE, std::string(who) + ": the kernel's range checks dropped " + std::to_string(faults) + " contributions (a bug); no result was returned");
-  HIP_TRY(hipMemcpy(by_code, d_by_code, (size_t)n_tables * SCORE_N_COLS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(steps_sum, d_steps_sum, (size_t)n_tables * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(reward_fx, d_reward, (size_t)n_tables * DQL_N_CELLS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(terminal, d_terminal, (size_t)n_tables * DQL_N_CELLS * DQL_N_CHECK_CODES * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(pairs, d_pairs.p, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  g_model_ms = ms;
-  for (int q = 0; q < 3; ++q) g_model_inst[q] = inst[q];
+                     const TableSets& q, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code, int64_t* steps_sum) {
+  Flight fl;
+  int rc = fl.setup(*cfg, max_steps); if (rc) return rc;
+  Sums sums;
+  const Sums::Slice s_by_code = sums.add((size_t)n_tables * SCORE_N_COLS), s_steps = sums.add((size_t)n_tables), s_reward = sums.add((size_t)n_tables * DQL_N_CELLS),
+                    s_terminal = sums.add((size_t)n_tables * DQL_N_CELLS * DQL_N_CHECK_CODES), s_faults = sums.add(1);
+  rc = sums.alloc_zeroed(); if (rc) return rc;
+  DevBuf d_pairs;  // the 32-bit pair tables in a buffer of their own
+  const size_t pairs_bytes = (size_t)n_tables * DQL_N_CELLS * DQL_N_STATES * sizeof(uint32_t);
+  OUT(d_pairs, pairs_bytes);
+  HIP_TRY(hipMemset(d_pairs.p, 0, pairs_bytes));
+  LastCall call;
+  rc = timed_launch([&] {
+    by_dtype(cfg->dtype, [&](auto t) {
+      using T = decltype(t);
+      ModelArgs<T> a;
+      fill_greedy_args<T>(a, *cfg, q, fl, seed, envs_per_table, max_steps);
+      a.pairs = (unsigned*)d_pairs.p; a.reward_fx = sums.dev(s_reward); a.terminal = sums.dev(s_terminal); a.by_code = sums.dev(s_by_code); a.steps_sum = sums.dev(s_steps);
+      a.faults = sums.dev(s_faults); a.eps_thr = eps_threshold(eps); a.episodes = episodes; a.n_tables = (int)n_tables;
+      call.instance<T>(TICK_PLAIN, X_ONLY);
+      hipLaunchKernelGGL((k_model<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
+    });
+  }, &call.ms, RangeFaults{sums.dev(s_faults), who, "kernel's", "contributions"});
+  if (rc) return rc;
+  rc = sums.down({{by_code, s_by_code}, {steps_sum, s_steps}, {reward_fx, s_reward}, {terminal, s_terminal}}); if (rc) return rc;
+  DOWN(pairs, d_pairs, pairs_bytes);
+  g_model_last = call;
   return DQL_OK;
 }
 int dql_model(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps, double eps,
               const double* qa, const double* qb, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code, int64_t* steps_sum) {
   int rc = check_config(cfg); if (rc) return rc;
   rc = model_check("dql_model", cfg, n_tables, envs_per_table, episodes_per_env, max_steps, eps, pairs, reward_fx, terminal, by_code, steps_sum); if (rc) return rc;
-  if (!qa || !qb) return fail(DQL_EINVAL, "dql_model: null array; nothing was launched");
-  OP_PROLOGUE(device)
-  DevBuf d_qa, d_qb;
-  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
-  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
-  return model_run("dql_model", cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, eps, (const double*)d_qa.p, (const double*)d_qb.p, pairs, reward_fx, terminal, by_code,
-                   steps_sum);
+  TableSets q;
+  rc = q.from_host("dql_model", device, n_tables, qa, qb); if (rc) return rc;
+  return model_run("dql_model", cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, eps, q, pairs, reward_fx, terminal, by_code, steps_sum);
 }
 // the learners' tables are read where they live, as dql_ensemble_score_map reads them: k_model touches nothing else of the ensemble
 int dql_ensemble_model(dql_ensemble* x, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env, uint64_t seed,
@@ -186,14 +164,11 @@ int dql_ensemble_model(dql_ensemble* x, const dql_config* eval_cfg, int64_t firs
   CHECK_ENS(x);
   int rc = check_config(eval_cfg); if (rc) return rc;
   rc = model_check("dql_ensemble_model", eval_cfg, count, envs_per_learner, episodes_per_env, max_steps, eps, pairs, reward_fx, terminal, by_code, steps_sum); if (rc) return rc;
-  if (first < 0 || first > x->n || count > x->n - first)
-    return fail(DQL_EINVAL, "dql_ensemble_model: the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t off = (size_t)first * DQL_N_CELLS;
-  return model_run("dql_ensemble_model", eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, eps, x->mem.qa + off, x->mem.qb + off, pairs, reward_fx, terminal, by_code,
-                   steps_sum);
+  TableSets q;
+  rc = tables_of_slice("dql_ensemble_model", x, first, count, q); if (rc) return rc;
+  return model_run("dql_ensemble_model", eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, eps, q, pairs, reward_fx, terminal, by_code, steps_sum);
 }
 int dql_diag_model_last(double* kernel_ms, int32_t* inst3) {
-  return diag_last(g_model_ms, g_model_inst, kernel_ms, inst3, "no dql_model or dql_ensemble_model call has completed on this thread");
+  return diag_last(g_model_last, kernel_ms, inst3, "no dql_model or dql_ensemble_model call has completed on this thread");
 }
 }  // extern "C"

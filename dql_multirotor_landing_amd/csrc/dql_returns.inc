@@ -1,7 +1,7 @@
 // dql_returns.inc: realised discounted returns per (state, action) cell under an eps-greedy policy on fixed tables (dql_returns / dql_ensemble_returns, DESIGN.md
-// section 21).  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype, DevBuf / OP_PROLOGUE / UP / OUT,
-// upload_mdpk, upload_schedule, EvTimer, check_config, TickLds, eps_threshold; fill_greedy_args / score_check of dql_greedy.inc; struct dql_ensemble / CHECK_ENS of
-// dql_ensemble.inc; and dql_returns.hpp.
+// section 21).  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype, DevBuf / OUT, EvTimer, check_config, TickLds,
+// eps_threshold; score_check and the family's host helpers of dql_greedy.inc (TableSets, Flight, Sums, RangeFaults, LastCall / diag_last, fill_greedy_args); struct
+// dql_ensemble / CHECK_ENS / tables_of_slice of dql_ensemble.inc; and dql_returns.hpp.
 // A decision's return is known only when its episode ends, so it cannot be summed forward.  Two kernels, launched back to back by one call:
 //   k_returns_fly    k_model's shape (one env per lane, workgroups of one wave, table set k serves blocks [k B, (k + 1) B), env i of every set has RNG key
 //                    (i, seed), the same waves_per_eu) and k_model's flights (model_episodes, unchanged), with ReturnsLogSink: one 64-bit store per lane and
@@ -154,8 +154,7 @@ static double returns_g_bound(const dql_config& c, double gamma, int max_steps) 
 }
 
 extern "C" {
-static thread_local double g_returns_ms[2] = {-1.0, -1.0};  // fly, sweep
-static thread_local int g_returns_inst[3] = {0, 0, 0};
+static thread_local LastCall g_returns_last;  // ms: fly, ms2: sweep
 // everything both entry points share, checked before the device is touched: a refused call starts no kernel
 static int returns_check(const char* who, const dql_config* cfg, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, int32_t max_steps, double eps, double gamma,
                          const int64_t* visits, const int64_t* return_fx, const int64_t* cut_decisions, const int64_t* by_code, const int64_t* steps_sum) {
@@ -176,75 +175,55 @@ static int returns_check(const char* who, const dql_config* cfg, int64_t n_table
                             "fewer envs per call and add the results of several seeds; nothing was launched");
   return DQL_OK;
 }
-// d_qa / d_qb: [n_tables][DQL_N_CELLS] on the current device
 static int returns_run(const char* who, const dql_config* cfg, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, double eps, double gamma,
-                       const double* d_qa, const double* d_qb, int64_t* visits, int64_t* return_fx, int64_t* cut_decisions, int64_t* by_code, int64_t* steps_sum) {
-  const int n_per = max_steps + 1;
+                       const TableSets& q, int64_t* visits, int64_t* return_fx, int64_t* cut_decisions, int64_t* by_code, int64_t* steps_sum) {
   const long long n_columns = n_tables * envs_per_table;
-  DevBuf d_mgr0, d_sched, d_mdp, d_sums, d_traj, d_ndec;
-  OUT(d_mgr0, (size_t)n_per * sizeof(long long)); OUT(d_sched, (size_t)n_per * sizeof(int)); OUT(d_mdp, mdpk_bytes(cfg->dtype));
-  int rc = upload_schedule(*cfg, 0, n_per, d_mgr0.p, d_sched.p); if (rc) return rc;
-  rc = upload_mdpk(*cfg, d_mdp.p); if (rc) return rc;
-  // one buffer for all 64-bit sums: [n_tables][SCORE_N_COLS] counts, [n_tables] step totals, [n_tables] cut decisions, [n_tables][DQL_N_CELLS] visits,
-  // [n_tables][DQL_N_CELLS] returns, [1] faults; the log (not zeroed) in one of its own, the decision counts beside it
-  const size_t n_sums = (size_t)n_tables * (SCORE_N_COLS + 2 + 2 * (size_t)DQL_N_CELLS) + 1;
-  OUT(d_sums, n_sums * sizeof(unsigned long long));
-  OUT(d_traj, (size_t)n_per * (size_t)n_columns * sizeof(unsigned long long));
+  Flight fl;
+  int rc = fl.setup(*cfg, max_steps); if (rc) return rc;
+  Sums sums;
+  const Sums::Slice s_by_code = sums.add((size_t)n_tables * SCORE_N_COLS), s_steps = sums.add((size_t)n_tables), s_cut = sums.add((size_t)n_tables),
+                    s_visits = sums.add((size_t)n_tables * DQL_N_CELLS), s_return = sums.add((size_t)n_tables * DQL_N_CELLS), s_faults = sums.add(1);
+  rc = sums.alloc_zeroed(); if (rc) return rc;
+  DevBuf d_traj, d_ndec;  // the decision log (not zeroed: n_dec says what is valid) in a buffer of its own, the decision counts beside it
+  OUT(d_traj, (size_t)(max_steps + 1) * (size_t)n_columns * sizeof(unsigned long long));
   OUT(d_ndec, (size_t)n_columns * sizeof(unsigned));
-  HIP_TRY(hipMemset(d_sums.p, 0, n_sums * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(d_ndec.p, 0, (size_t)n_columns * sizeof(unsigned)));
-  unsigned long long* d_by_code = (unsigned long long*)d_sums.p;
-  unsigned long long* d_steps_sum = d_by_code + (size_t)n_tables * SCORE_N_COLS;
-  unsigned long long* d_cut = d_steps_sum + (size_t)n_tables;
-  unsigned long long* d_visits = d_cut + (size_t)n_tables;
-  unsigned long long* d_return = d_visits + (size_t)n_tables * DQL_N_CELLS;
-  unsigned long long* d_faults = d_return + (size_t)n_tables * DQL_N_CELLS;
+  // two stretches: the flight from t_fly's first event to t_sweep's first, the sweep between t_sweep's two
   EvTimer t_fly, t_sweep;
   rc = t_fly.start(); if (rc) return rc;
-  int inst[3] = {0, 0, 0};
+  LastCall call;
   by_dtype(cfg->dtype, [&](auto t) {
     using T = decltype(t);
     ReturnsFlyArgs<T> a;
-    fill_greedy_args<T>(a, *cfg, d_mdp.p, d_qa, d_qb, d_mgr0.p, d_sched.p, seed, envs_per_table, max_steps);
-    a.traj = (unsigned long long*)d_traj.p; a.n_dec = (unsigned*)d_ndec.p; a.by_code = d_by_code; a.steps_sum = d_steps_sum; a.faults = d_faults;
+    fill_greedy_args<T>(a, *cfg, q, fl, seed, envs_per_table, max_steps);
+    a.traj = (unsigned long long*)d_traj.p; a.n_dec = (unsigned*)d_ndec.p; a.by_code = sums.dev(s_by_code); a.steps_sum = sums.dev(s_steps); a.faults = sums.dev(s_faults);
     a.n_columns = n_columns; a.eps_thr = eps_threshold(eps); a.episodes = episodes; a.n_tables = (int)n_tables;
-    inst[0] = (int)sizeof(T); inst[1] = TICK_PLAIN; inst[2] = X_ONLY;
+    call.instance<T>(TICK_PLAIN, X_ONLY);
     hipLaunchKernelGGL((k_returns_fly<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
   });
   HIP_TRY(hipGetLastError());
   rc = t_sweep.start(); if (rc) return rc;  // its first event closes the flight's stretch
-  const ReturnsSweepArgs s{(const unsigned long long*)d_traj.p, (const unsigned*)d_ndec.p, d_visits, d_return, d_cut, d_faults, gamma, returns_g_bound(*cfg, gamma, max_steps),
-                           n_columns, envs_per_table, max_steps, (int)n_tables};
+  const ReturnsSweepArgs s{(const unsigned long long*)d_traj.p, (const unsigned*)d_ndec.p, sums.dev(s_visits), sums.dev(s_return), sums.dev(s_cut), sums.dev(s_faults), gamma,
+                           returns_g_bound(*cfg, gamma, max_steps), n_columns, envs_per_table, max_steps, (int)n_tables};
   if (envs_per_table % RETURNS_BLOCK == 0) hipLaunchKernelGGL((k_returns_sweep<RETURNS_BLOCK>), dim3((unsigned)(n_columns / RETURNS_BLOCK)), dim3(RETURNS_BLOCK), 0, 0, s);
   else hipLaunchKernelGGL((k_returns_sweep<64>), dim3((unsigned)(n_columns / 64)), dim3(64), 0, 0, s);
   HIP_TRY(hipGetLastError());
-  double sweep_ms = 0.0;
-  rc = t_sweep.stop_ms(&sweep_ms); if (rc) return rc;
+  rc = t_sweep.stop_ms(&call.ms2); if (rc) return rc;
   float fly_ms = 0.0f;
   HIP_TRY(hipEventElapsedTime(&fly_ms, t_fly.e0, t_sweep.e0));
-  unsigned long long faults = 0ull;
-  HIP_TRY(hipMemcpy(&faults, d_faults, sizeof(faults), hipMemcpyDeviceToHost));
-  if (faults) return fail(DQL_ESTATE, std::string(who) + ": the kernels' range checks dropped " + std::to_string(faults) + " contributions (a bug); no result was returned");
-  HIP_TRY(hipMemcpy(by_code, d_by_code, (size_t)n_tables * SCORE_N_COLS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(steps_sum, d_steps_sum, (size_t)n_tables * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(cut_decisions, d_cut, (size_t)n_tables * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(visits, d_visits, (size_t)n_tables * DQL_N_CELLS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(return_fx, d_return, (size_t)n_tables * DQL_N_CELLS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  g_returns_ms[0] = (double)fly_ms; g_returns_ms[1] = sweep_ms;
-  for (int q = 0; q < 3; ++q) g_returns_inst[q] = inst[q];
+  call.ms = (double)fly_ms;
+  rc = RangeFaults{sums.dev(s_faults), who, "kernels'", "contributions"}.refuse_if_any(); if (rc) return rc;
+  rc = sums.down({{by_code, s_by_code}, {steps_sum, s_steps}, {cut_decisions, s_cut}, {visits, s_visits}, {return_fx, s_return}}); if (rc) return rc;
+  g_returns_last = call;
   return DQL_OK;
 }
 int dql_returns(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps, double eps, double gamma,
                 const double* qa, const double* qb, int64_t* visits, int64_t* return_fx, int64_t* cut_decisions, int64_t* by_code, int64_t* steps_sum) {
   int rc = check_config(cfg); if (rc) return rc;
   rc = returns_check("dql_returns", cfg, n_tables, envs_per_table, episodes_per_env, max_steps, eps, gamma, visits, return_fx, cut_decisions, by_code, steps_sum); if (rc) return rc;
-  if (!qa || !qb) return fail(DQL_EINVAL, "dql_returns: null array; nothing was launched");
-  OP_PROLOGUE(device)
-  DevBuf d_qa, d_qb;
-  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
-  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
-  return returns_run("dql_returns", cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, eps, gamma, (const double*)d_qa.p, (const double*)d_qb.p, visits, return_fx,
-                     cut_decisions, by_code, steps_sum);
+  TableSets q;
+  rc = q.from_host("dql_returns", device, n_tables, qa, qb); if (rc) return rc;
+  return returns_run("dql_returns", cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, eps, gamma, q, visits, return_fx, cut_decisions, by_code, steps_sum);
 }
 // the learners' tables are read where they live, as dql_ensemble_model reads them: the kernels touch nothing else of the ensemble
 int dql_ensemble_returns(dql_ensemble* x, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env, uint64_t seed,
@@ -253,18 +232,11 @@ int dql_ensemble_returns(dql_ensemble* x, const dql_config* eval_cfg, int64_t fi
   int rc = check_config(eval_cfg); if (rc) return rc;
   rc = returns_check("dql_ensemble_returns", eval_cfg, count, envs_per_learner, episodes_per_env, max_steps, eps, gamma, visits, return_fx, cut_decisions, by_code, steps_sum);
   if (rc) return rc;
-  if (first < 0 || first > x->n || count > x->n - first)
-    return fail(DQL_EINVAL, "dql_ensemble_returns: the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t off = (size_t)first * DQL_N_CELLS;
-  return returns_run("dql_ensemble_returns", eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, eps, gamma, x->mem.qa + off, x->mem.qb + off, visits, return_fx,
-                     cut_decisions, by_code, steps_sum);
+  TableSets q;
+  rc = tables_of_slice("dql_ensemble_returns", x, first, count, q); if (rc) return rc;
+  return returns_run("dql_ensemble_returns", eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, eps, gamma, q, visits, return_fx, cut_decisions, by_code, steps_sum);
 }
 int dql_diag_returns_last(double* fly_ms, double* sweep_ms, int32_t* inst3) {
-  if (!fly_ms || !sweep_ms || !inst3) return fail(DQL_EINVAL, "null pointer");
-  if (g_returns_ms[0] < 0.0) return fail(DQL_ESTATE, "no dql_returns or dql_ensemble_returns call has completed on this thread");
-  *fly_ms = g_returns_ms[0]; *sweep_ms = g_returns_ms[1];
-  for (int k = 0; k < 3; ++k) inst3[k] = g_returns_inst[k];
-  return DQL_OK;
+  return diag_last(g_returns_last, fly_ms, sweep_ms, inst3, "no dql_returns or dql_ensemble_returns call has completed on this thread");
 }
 }  // extern "C"

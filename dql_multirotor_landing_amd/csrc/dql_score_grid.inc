@@ -1,7 +1,7 @@
 // dql_score_grid.inc: greedy scoring of K table sets over S scenarios in one launch, with the touchdowns binned by their offset from the platform centre
 // (dql_score_grid / dql_ensemble_score_grid, DESIGN.md section 20).  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY,
-// by_dtype_axes, DevBuf / OP_PROLOGUE / UP / OUT / DOWN, upload_schedule, EvTimer, check_config, TickLds; score_check / diag_last of dql_greedy.inc; struct
-// dql_ensemble / CHECK_ENS of dql_ensemble.inc; and dql_score_grid.hpp.
+// by_dtype / by_dtype_axes, DevBuf / UP, check_config, TickLds; score_check and the family's host helpers of dql_greedy.inc (TableSets, Flight for the schedule, Sums,
+// EpisodeLog, LastCall / diag_last, timed_launch, fill_flight_args); struct dql_ensemble / CHECK_ENS / tables_of_slice of dql_ensemble.inc; and dql_score_grid.hpp.
 // k_score's shape — one env per lane, workgroups of one wave, env i of every (scenario, set) has RNG key (i, seed), the same waves_per_eu — with one more
 // coordinate: the blocks are scenario-major (grid_coords), so that the scenario s and the table set k of a wave are both wave-uniform.  What k_score receives
 // by value in its kernel argument (SimK, MdpRun, RolloutInit) a wave of k_score_grid reads from record s of a device array, and its MdpK from element s of
@@ -66,8 +66,7 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
 }
 
 extern "C" {
-static thread_local double g_grid_ms = -1.0;
-static thread_local int g_grid_inst[3] = {0, 0, 0};
+static thread_local LastCall g_grid_last;
 // everything both entry points share, checked before the device is touched: a refused call starts no kernel
 static int score_grid_check(const char* who, const dql_config* cfgs, int32_t n_scenarios, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, int32_t max_steps,
                             const int64_t* by_code, const int64_t* steps_sum, const uint8_t* ep_code, const uint16_t* ep_steps) {
@@ -89,15 +88,13 @@ static int score_grid_check(const char* who, const dql_config* cfgs, int32_t n_s
   if ((int64_t)n_scenarios * n_tables * envs_per_table > (1ll << 30)) return fail(DQL_EINVAL, w + ": scenarios x table sets x envs must be at most 2^30; nothing was launched");
   return DQL_OK;
 }
-// d_qa / d_qb: [n_tables][DQL_N_CELLS] on the current device
-static int score_grid_run(const dql_config* cfgs, int S, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, const double* d_qa,
-                          const double* d_qb, int64_t* by_code, int64_t* steps_sum, int64_t* touch_hist, uint8_t* ep_code, uint16_t* ep_steps) {
+static int score_grid_run(const dql_config* cfgs, int S, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, const TableSets& q,
+                          int64_t* by_code, int64_t* steps_sum, int64_t* touch_hist, uint8_t* ep_code, uint16_t* ep_steps) {
   const long long n_total = n_tables * envs_per_table;  // per scenario
-  const int n_per = max_steps + 1;
   const size_t rows = (size_t)S * (size_t)n_tables;
-  DevBuf d_mgr0, d_sched, d_sc, d_mdp, d_sums, d_code, d_steps;
-  OUT(d_mgr0, (size_t)n_per * sizeof(long long)); OUT(d_sched, (size_t)n_per * sizeof(int));
-  int rc = upload_schedule(cfgs[0], 0, n_per, d_mgr0.p, d_sched.p); if (rc) return rc;
+  Flight fl;  // the schedule the scenarios share; fl.mdp: one MdpK per scenario, uploaded below
+  int rc = fl.setup(cfgs[0], max_steps, false); if (rc) return rc;
+  DevBuf d_sc;
   // the per-scenario constants: make_simk per scenario, the Kalman fixed point (up to 200 000 iterations) once per distinct (kal_q, kal_r) in T
   rc = by_dtype(cfgs[0].dtype, [&](auto t) -> int {
     using T = decltype(t);
@@ -124,64 +121,43 @@ static int score_grid_run(const dql_config* cfgs, int S, long long n_tables, lon
       mk[(size_t)s] = make_mdpk<T>(c);
     }
     UP(d_sc, sc.data(), sc.size() * sizeof(GridScenario<T>));
-    UP(d_mdp, mk.data(), mk.size() * sizeof(MdpK<T>));
+    UP(fl.mdp, mk.data(), mk.size() * sizeof(MdpK<T>));
     return DQL_OK;
   });
   if (rc) return rc;
-  // one buffer for all sums: [S][K][SCORE_N_COLS] counts, [S][K] step totals, [S][K][GRID_TOUCH_BINS] touch bins
-  const size_t sums_bytes = rows * (SCORE_N_COLS + 1 + GRID_TOUCH_BINS) * sizeof(unsigned long long);
-  OUT(d_sums, sums_bytes);
-  HIP_TRY(hipMemset(d_sums.p, 0, sums_bytes));
-  const size_t log_n = (size_t)S * (size_t)episodes * (size_t)n_total;
-  if (ep_code) {
-    OUT(d_code, log_n); OUT(d_steps, log_n * sizeof(uint16_t));
-    HIP_TRY(hipMemset(d_code.p, 0xff, log_n));  // not finished
-    HIP_TRY(hipMemset(d_steps.p, 0, log_n * sizeof(uint16_t)));
-  }
-  unsigned long long* d_by_code = (unsigned long long*)d_sums.p;
-  unsigned long long* d_steps_sum = d_by_code + rows * SCORE_N_COLS;
-  unsigned long long* d_touch = d_steps_sum + rows;
-  EvTimer timer;
-  rc = timer.start(); if (rc) return rc;
-  int inst[3] = {0, 0, 0};
-  by_dtype_axes(cfgs[0].dtype, cfgs[0].two_axis, [&](auto t, auto xmode) {
-    using T = decltype(t);
-    constexpr int XMODE = decltype(xmode)::value;
-    ScoreGridArgs<T> a;
-    a.sc = (const GridScenario<T> DQL_CONST_AS*)d_sc.p; a.mdp = (const MdpK<T> DQL_CONST_AS*)d_mdp.p;
-    a.qa = d_qa; a.qb = d_qb;
-    a.mgr0 = (const long long DQL_CONST_AS*)d_mgr0.p; a.sched = (const int DQL_CONST_AS*)d_sched.p;
-    a.by_code = d_by_code; a.steps_sum = d_steps_sum; a.touch = d_touch;
-    a.ep_code = (uint8_t*)d_code.p; a.ep_steps = (uint16_t*)d_steps.p;
-    a.seed = seed; a.n_tables = (int)n_tables; a.blocks_per_table = (int)(envs_per_table / 64); a.max_steps = max_steps; a.episodes = episodes; a.n_scenarios = S;
-    inst[0] = (int)sizeof(T); inst[1] = TICK_PLAIN; inst[2] = XMODE;
-    hipLaunchKernelGGL((k_score_grid<T, TICK_PLAIN, XMODE>), dim3((unsigned)((long long)S * n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
-  });
-  HIP_TRY(hipGetLastError());
-  double ms = 0.0;
-  rc = timer.stop_ms(&ms); if (rc) return rc;
-  HIP_TRY(hipMemcpy(by_code, d_by_code, rows * SCORE_N_COLS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(steps_sum, d_steps_sum, rows * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (touch_hist) HIP_TRY(hipMemcpy(touch_hist, d_touch, rows * GRID_TOUCH_BINS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (ep_code) {
-    DOWN(ep_code, d_code, log_n);
-    DOWN(ep_steps, d_steps, log_n * sizeof(uint16_t));
-  }
-  g_grid_ms = ms;
-  for (int q = 0; q < 3; ++q) g_grid_inst[q] = inst[q];
+  Sums sums;  // rows are (scenario, table set)
+  const Sums::Slice s_by_code = sums.add(rows * SCORE_N_COLS), s_steps = sums.add(rows), s_touch = sums.add(rows * GRID_TOUCH_BINS);
+  rc = sums.alloc_zeroed(); if (rc) return rc;
+  EpisodeLog elog;
+  rc = elog.setup(ep_code != nullptr, (size_t)S * (size_t)episodes * (size_t)n_total); if (rc) return rc;
+  LastCall call;
+  rc = timed_launch([&] {
+    by_dtype_axes(cfgs[0].dtype, cfgs[0].two_axis, [&](auto t, auto xmode) {
+      using T = decltype(t);
+      constexpr int XMODE = decltype(xmode)::value;
+      ScoreGridArgs<T> a;
+      fill_flight_args(a, q, fl, seed, envs_per_table, max_steps);
+      a.sc = (const GridScenario<T> DQL_CONST_AS*)d_sc.p; a.mdp = (const MdpK<T> DQL_CONST_AS*)fl.mdp.p;
+      a.by_code = sums.dev(s_by_code); a.steps_sum = sums.dev(s_steps); a.touch = sums.dev(s_touch);
+      a.ep_code = (uint8_t*)elog.code.p; a.ep_steps = (uint16_t*)elog.steps.p;
+      a.n_tables = (int)n_tables; a.episodes = episodes; a.n_scenarios = S;
+      call.instance<T>(TICK_PLAIN, XMODE);
+      hipLaunchKernelGGL((k_score_grid<T, TICK_PLAIN, XMODE>), dim3((unsigned)((long long)S * n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
+    });
+  }, &call.ms);
+  if (rc) return rc;
+  rc = sums.down({{by_code, s_by_code}, {steps_sum, s_steps}, {touch_hist, s_touch}}); if (rc) return rc;  // touch_hist: optional
+  rc = elog.down(ep_code, ep_steps); if (rc) return rc;
+  g_grid_last = call;
   return DQL_OK;
 }
 int dql_score_grid(const dql_config* cfgs, int32_t n_scenarios, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
                    const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum, int64_t* touch_hist_or_null, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null) {
   int rc = score_grid_check("dql_score_grid", cfgs, n_scenarios, n_tables, envs_per_table, episodes_per_env, max_steps, by_code, steps_sum, ep_code_or_null, ep_steps_or_null);
   if (rc) return rc;
-  if (!qa || !qb) return fail(DQL_EINVAL, "dql_score_grid: null array; nothing was launched");
-  OP_PROLOGUE(device)
-  DevBuf d_qa, d_qb;
-  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
-  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
-  return score_grid_run(cfgs, n_scenarios, n_tables, envs_per_table, episodes_per_env, seed, max_steps, (const double*)d_qa.p, (const double*)d_qb.p, by_code, steps_sum,
-                        touch_hist_or_null, ep_code_or_null, ep_steps_or_null);
+  TableSets q;
+  rc = q.from_host("dql_score_grid", device, n_tables, qa, qb); if (rc) return rc;
+  return score_grid_run(cfgs, n_scenarios, n_tables, envs_per_table, episodes_per_env, seed, max_steps, q, by_code, steps_sum, touch_hist_or_null, ep_code_or_null, ep_steps_or_null);
 }
 // the learners' tables are read where they live, as dql_ensemble_score reads them: k_score_grid touches nothing else of the ensemble
 int dql_ensemble_score_grid(dql_ensemble* x, const dql_config* eval_cfgs, int32_t n_scenarios, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
@@ -191,14 +167,12 @@ int dql_ensemble_score_grid(dql_ensemble* x, const dql_config* eval_cfgs, int32_
   int rc = score_grid_check("dql_ensemble_score_grid", eval_cfgs, n_scenarios, count, envs_per_learner, episodes_per_env, max_steps, by_code, steps_sum, ep_code_or_null,
                             ep_steps_or_null);
   if (rc) return rc;
-  if (first < 0 || first > x->n || count > x->n - first)
-    return fail(DQL_EINVAL, "dql_ensemble_score_grid: the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t off = (size_t)first * DQL_N_CELLS;
-  return score_grid_run(eval_cfgs, n_scenarios, count, envs_per_learner, episodes_per_env, seed, max_steps, x->mem.qa + off, x->mem.qb + off, by_code, steps_sum, touch_hist_or_null,
-                        ep_code_or_null, ep_steps_or_null);
+  TableSets q;
+  rc = tables_of_slice("dql_ensemble_score_grid", x, first, count, q); if (rc) return rc;
+  return score_grid_run(eval_cfgs, n_scenarios, count, envs_per_learner, episodes_per_env, seed, max_steps, q, by_code, steps_sum, touch_hist_or_null, ep_code_or_null,
+                        ep_steps_or_null);
 }
 int dql_diag_score_grid_last(double* kernel_ms, int32_t* inst3) {
-  return diag_last(g_grid_ms, g_grid_inst, kernel_ms, inst3, "no dql_score_grid or dql_ensemble_score_grid call has completed on this thread");
+  return diag_last(g_grid_last, kernel_ms, inst3, "no dql_score_grid or dql_ensemble_score_grid call has completed on this thread");
 }
 }  // extern "C"

@@ -1,7 +1,7 @@
 // dql_score_map.inc: greedy scoring with a map of where the greedy decisions were made (dql_score_map / dql_ensemble_score_map, DESIGN.md section 18).  A fragment
-// of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype_axes, DevBuf / OP_PROLOGUE / UP / OUT / DOWN, upload_mdpk,
-// upload_schedule, EvTimer, check_config, TickLds; fill_greedy_args / score_check / diag_last of dql_greedy.inc; struct dql_ensemble / CHECK_ENS of
-// dql_ensemble.inc; and dql_score_map.hpp.
+// of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype_axes, DevBuf / OUT / DOWN, check_config, TickLds; score_check and the
+// family's host helpers of dql_greedy.inc (TableSets, Flight, Sums, EpisodeLog, RangeFaults, LastCall / diag_last, timed_launch, fill_greedy_args); struct
+// dql_ensemble / CHECK_ENS / tables_of_slice of dql_ensemble.inc; and dql_score_map.hpp.
 // k_score's shape — one env per lane, workgroups of one wave, table set k serves blocks [k B, (k + 1) B), env i of every set has RNG key (i, seed), the same
 // waves_per_eu — and on top of it the wave's histogram in LDS: unsigned [DQL_N_CELLS], 11 340 B per workgroup.  The wave clears it before the first period,
 // every lane adds its decisions with LDS atomics (many lanes hit one cell in the same period), and at the end the wave flushes the non-zero cells into the table
@@ -84,8 +84,7 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
 }
 
 extern "C" {
-static thread_local double g_score_map_ms = -1.0;
-static thread_local int g_score_map_inst[3] = {0, 0, 0};
+static thread_local LastCall g_score_map_last;
 // score_check, and what the map adds to it: checked before the device is touched
 static int score_map_check(const char* who, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, int32_t max_steps, const int64_t* by_code, const int64_t* steps_sum,
                            const int64_t* visits, const uint8_t* ep_code, const uint16_t* ep_steps, const uint16_t* ep_last_cell) {
@@ -97,59 +96,42 @@ static int score_map_check(const char* who, int64_t n_tables, int64_t envs_per_t
   if (!visits) return fail(DQL_EINVAL, w + ": null array; nothing was launched");
   return DQL_OK;
 }
-// d_qa / d_qb: [n_tables][DQL_N_CELLS] on the current device
-static int score_map_run(const char* who, const dql_config* cfg, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, const double* d_qa,
-                         const double* d_qb, int64_t* by_code, int64_t* steps_sum, int64_t* visits, uint8_t* ep_code, uint16_t* ep_steps, uint16_t* ep_last_cell) {
+static int score_map_run(const char* who, const dql_config* cfg, long long n_tables, long long envs_per_table, int episodes, uint64_t seed, int max_steps, const TableSets& q,
+                         int64_t* by_code, int64_t* steps_sum, int64_t* visits, uint8_t* ep_code, uint16_t* ep_steps, uint16_t* ep_last_cell) {
   const long long n_total = n_tables * envs_per_table;
-  const int n_per = max_steps + 1;
-  DevBuf d_mgr0, d_sched, d_mdp, d_sums, d_code, d_steps, d_cells;
-  OUT(d_mgr0, (size_t)n_per * sizeof(long long)); OUT(d_sched, (size_t)n_per * sizeof(int)); OUT(d_mdp, mdpk_bytes(cfg->dtype));
-  int rc = upload_schedule(*cfg, 0, n_per, d_mgr0.p, d_sched.p); if (rc) return rc;
-  rc = upload_mdpk(*cfg, d_mdp.p); if (rc) return rc;
-  // one buffer for all sums: [n_tables][SCORE_N_COLS] counts, [n_tables] step totals, [n_tables][DQL_N_CELLS] visits, [1] faults
-  const size_t n_sums = (size_t)n_tables * (SCORE_N_COLS + 1 + DQL_N_CELLS) + 1;
-  OUT(d_sums, n_sums * sizeof(unsigned long long));
-  HIP_TRY(hipMemset(d_sums.p, 0, n_sums * sizeof(unsigned long long)));
-  const size_t log_n = (size_t)episodes * (size_t)n_total;
-  if (ep_code) {
-    OUT(d_code, log_n); OUT(d_steps, log_n * sizeof(uint16_t)); OUT(d_cells, 2 * log_n * sizeof(uint16_t));
-    HIP_TRY(hipMemset(d_code.p, 0xff, log_n));  // not finished
-    HIP_TRY(hipMemset(d_steps.p, 0, log_n * sizeof(uint16_t)));
-    HIP_TRY(hipMemset(d_cells.p, 0xff, 2 * log_n * sizeof(uint16_t)));
+  Flight fl;
+  int rc = fl.setup(*cfg, max_steps); if (rc) return rc;
+  Sums sums;
+  const Sums::Slice s_by_code = sums.add((size_t)n_tables * SCORE_N_COLS), s_steps = sums.add((size_t)n_tables), s_visits = sums.add((size_t)n_tables * DQL_N_CELLS),
+                    s_faults = sums.add(1);
+  rc = sums.alloc_zeroed(); if (rc) return rc;
+  EpisodeLog elog;
+  rc = elog.setup(ep_code != nullptr, (size_t)episodes * (size_t)n_total); if (rc) return rc;
+  DevBuf d_cells;  // ep_last_cell beside the log: [2] planes of its entries
+  const size_t cells_bytes = 2 * elog.entries * sizeof(uint16_t);
+  if (elog.on) {
+    OUT(d_cells, cells_bytes);
+    HIP_TRY(hipMemset(d_cells.p, 0xff, cells_bytes));
   }
-  unsigned long long* d_by_code = (unsigned long long*)d_sums.p;
-  unsigned long long* d_steps_sum = d_by_code + (size_t)n_tables * SCORE_N_COLS;
-  unsigned long long* d_visits = d_steps_sum + (size_t)n_tables;
-  unsigned long long* d_faults = d_visits + (size_t)n_tables * DQL_N_CELLS;
-  const ScoreMapLog log{(uint8_t*)d_code.p, (uint16_t*)d_steps.p, (uint16_t*)d_cells.p, n_total, episodes};
-  EvTimer timer;
-  rc = timer.start(); if (rc) return rc;
-  int inst[3] = {0, 0, 0};
-  by_dtype_axes(cfg->dtype, cfg->two_axis, [&](auto t, auto xmode) {
-    using T = decltype(t);
-    constexpr int XMODE = decltype(xmode)::value;
-    ScoreMapArgs<T> a;
-    fill_greedy_args<T>(a, *cfg, d_mdp.p, d_qa, d_qb, d_mgr0.p, d_sched.p, seed, envs_per_table, max_steps);
-    a.by_code = d_by_code; a.steps_sum = d_steps_sum; a.visits = d_visits; a.faults = d_faults; a.log = log; a.episodes = episodes; a.n_tables = (int)n_tables;
-    inst[0] = (int)sizeof(T); inst[1] = TICK_PLAIN; inst[2] = XMODE;
-    hipLaunchKernelGGL((k_score_map<T, TICK_PLAIN, XMODE>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
-  });
-  HIP_TRY(hipGetLastError());
-  double ms = 0.0;
-  rc = timer.stop_ms(&ms); if (rc) return rc;
-  unsigned long long faults = 0ull;
-  HIP_TRY(hipMemcpy(&faults, d_faults, sizeof(faults), hipMemcpyDeviceToHost));
-  if (faults) return fail(DQL_ESTATE, std::string(who) + ": the kernel's range checks dropped " + std::to_string(faults) + " writes (a bug); no result was returned");
-  HIP_TRY(hipMemcpy(by_code, d_by_code, (size_t)n_tables * SCORE_N_COLS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(steps_sum, d_steps_sum, (size_t)n_tables * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(visits, d_visits, (size_t)n_tables * DQL_N_CELLS * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (ep_code) {
-    DOWN(ep_code, d_code, log_n);
-    DOWN(ep_steps, d_steps, log_n * sizeof(uint16_t));
-    DOWN(ep_last_cell, d_cells, 2 * log_n * sizeof(uint16_t));
-  }
-  g_score_map_ms = ms;
-  for (int q = 0; q < 3; ++q) g_score_map_inst[q] = inst[q];
+  const ScoreMapLog log{(uint8_t*)elog.code.p, (uint16_t*)elog.steps.p, (uint16_t*)d_cells.p, n_total, episodes};
+  LastCall call;
+  rc = timed_launch([&] {
+    by_dtype_axes(cfg->dtype, cfg->two_axis, [&](auto t, auto xmode) {
+      using T = decltype(t);
+      constexpr int XMODE = decltype(xmode)::value;
+      ScoreMapArgs<T> a;
+      fill_greedy_args<T>(a, *cfg, q, fl, seed, envs_per_table, max_steps);
+      a.by_code = sums.dev(s_by_code); a.steps_sum = sums.dev(s_steps); a.visits = sums.dev(s_visits); a.faults = sums.dev(s_faults);
+      a.log = log; a.episodes = episodes; a.n_tables = (int)n_tables;
+      call.instance<T>(TICK_PLAIN, XMODE);
+      hipLaunchKernelGGL((k_score_map<T, TICK_PLAIN, XMODE>), dim3((unsigned)(n_tables * a.blocks_per_table)), dim3(64), 0, 0, a);
+    });
+  }, &call.ms, RangeFaults{sums.dev(s_faults), who, "kernel's", "writes"});
+  if (rc) return rc;
+  rc = sums.down({{by_code, s_by_code}, {steps_sum, s_steps}, {visits, s_visits}}); if (rc) return rc;
+  rc = elog.down(ep_code, ep_steps); if (rc) return rc;
+  if (elog.on) DOWN(ep_last_cell, d_cells, cells_bytes);
+  g_score_map_last = call;
   return DQL_OK;
 }
 int dql_score_map(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
@@ -158,13 +140,10 @@ int dql_score_map(const dql_config* cfg, int device, int64_t n_tables, int64_t e
   int rc = check_config(cfg); if (rc) return rc;
   rc = score_map_check("dql_score_map", n_tables, envs_per_table, episodes_per_env, max_steps, by_code, steps_sum, visits, ep_code_or_null, ep_steps_or_null, ep_last_cell_or_null);
   if (rc) return rc;
-  if (!qa || !qb) return fail(DQL_EINVAL, "dql_score_map: null array; nothing was launched");
-  OP_PROLOGUE(device)
-  DevBuf d_qa, d_qb;
-  const size_t TB = (size_t)n_tables * DQL_N_CELLS * sizeof(double);
-  UP(d_qa, qa, TB); UP(d_qb, qb, TB);
-  return score_map_run("dql_score_map", cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, (const double*)d_qa.p, (const double*)d_qb.p, by_code, steps_sum, visits,
-                       ep_code_or_null, ep_steps_or_null, ep_last_cell_or_null);
+  TableSets q;
+  rc = q.from_host("dql_score_map", device, n_tables, qa, qb); if (rc) return rc;
+  return score_map_run("dql_score_map", cfg, n_tables, envs_per_table, episodes_per_env, seed, max_steps, q, by_code, steps_sum, visits, ep_code_or_null, ep_steps_or_null,
+                       ep_last_cell_or_null);
 }
 // the learners' tables are read where they live, as dql_ensemble_score reads them: k_score_map touches nothing else of the ensemble
 int dql_ensemble_score_map(dql_ensemble* x, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env, uint64_t seed,
@@ -175,14 +154,12 @@ int dql_ensemble_score_map(dql_ensemble* x, const dql_config* eval_cfg, int64_t 
   rc = score_map_check("dql_ensemble_score_map", count, envs_per_learner, episodes_per_env, max_steps, by_code, steps_sum, visits, ep_code_or_null, ep_steps_or_null,
                        ep_last_cell_or_null);
   if (rc) return rc;
-  if (first < 0 || first > x->n || count > x->n - first)
-    return fail(DQL_EINVAL, "dql_ensemble_score_map: the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
-  HIP_TRY(hipSetDevice(x->device));
-  const size_t off = (size_t)first * DQL_N_CELLS;
-  return score_map_run("dql_ensemble_score_map", eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, x->mem.qa + off, x->mem.qb + off, by_code, steps_sum, visits,
-                       ep_code_or_null, ep_steps_or_null, ep_last_cell_or_null);
+  TableSets q;
+  rc = tables_of_slice("dql_ensemble_score_map", x, first, count, q); if (rc) return rc;
+  return score_map_run("dql_ensemble_score_map", eval_cfg, count, envs_per_learner, episodes_per_env, seed, max_steps, q, by_code, steps_sum, visits, ep_code_or_null,
+                       ep_steps_or_null, ep_last_cell_or_null);
 }
 int dql_diag_score_map_last(double* kernel_ms, int32_t* inst3) {
-  return diag_last(g_score_map_ms, g_score_map_inst, kernel_ms, inst3, "no dql_score_map or dql_ensemble_score_map call has completed on this thread");
+  return diag_last(g_score_map_last, kernel_ms, inst3, "no dql_score_map or dql_ensemble_score_map call has completed on this thread");
 }
 }  // extern "C"

@@ -245,6 +245,24 @@ def _table_sets(tables):
     return np.ascontiguousarray(np.stack(qa)), np.ascontiguousarray(np.stack(qb))
 
 
+def _table_pair(qa, qb):
+    """`qa`, `qb` as float64 [K, 2835] arrays of the same K (one set: [2835]), checked: what every greedy-flight operator but the roll-outs takes"""
+    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
+    if qa.ndim != 2 or qa.shape[1] != N_CELLS or qb.shape != qa.shape:
+        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    return qa, qb
+
+
+def _last_call(lib, op: str, kernel: str, timing, times=("kernel_ms",)):
+    """`timing`, if given, receives the kernel time(s) and the `instance` of this thread's latest completed call of the operator (include/dql_diag.h dql_diag_<op>_last)"""
+    if timing is None:
+        return
+    ms, inst = [C.c_double() for _ in times], (C.c_int32 * 3)()
+    _lib.check(getattr(lib, f"dql_diag_{op}_last")(*[C.byref(m) for m in ms], inst))
+    timing.update({k: m.value for k, m in zip(times, ms)})
+    timing["instance"] = f"{kernel}<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+
+
 def rollout(cfg: DqlConfig, tables, envs_per_table: int, seed: int, max_steps: int = 600, trace_envs: int = 0, device: int = 0, timing: dict = None):
     """Every env's FIRST greedy episode from reset to termination in one launch, for up to 16 table sets at once (include/dql.h dql_rollout).
 
@@ -271,11 +289,7 @@ def rollout(cfg: DqlConfig, tables, envs_per_table: int, seed: int, max_steps: i
     trace = np.zeros((max_steps + 1, nt.value, trace_envs)) if trace_envs else None
     c = cfg.to_c()
     _lib.check(lib.dql_rollout(C.byref(c), device, K, n, int(seed), max_steps, _p(qa), _p(qb), _p(code), _p(steps), _p(rec), trace_envs, None if trace is None else _p(trace)))
-    if timing is not None:
-        ms, inst = C.c_double(), (C.c_int32 * 3)()
-        _lib.check(lib.dql_diag_rollout_last(C.byref(ms), inst))
-        timing["kernel_ms"] = ms.value
-        timing["instance"] = f"k_rollout<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    _last_call(lib, "rollout", "k_rollout", timing)
     out = {"code": code, "steps": steps, "trace": trace, "trace_fields": ROLLOUT_TRACE_FIELDS}
     out.update({f: rec[k] for k, f in enumerate(ROLLOUT_RECORD_FIELDS)})
     return out
@@ -309,11 +323,7 @@ def score_buffers(n_tables: int, envs_per_table: int, episodes: int, log: bool):
 
 
 def score_result(lib, by_code, steps_sum, ep_code, ep_steps, timing):
-    if timing is not None:
-        ms, inst = C.c_double(), (C.c_int32 * 3)()
-        _lib.check(lib.dql_diag_score_last(C.byref(ms), inst))
-        timing["kernel_ms"] = ms.value
-        timing["instance"] = f"k_score<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    _last_call(lib, "score", "k_score", timing)
     return {"by_code": by_code, "steps_sum": steps_sum, "ep_code": ep_code, "ep_steps": ep_steps, "columns": SCORE_COLUMNS}
 
 
@@ -335,9 +345,7 @@ def score(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, episodes: int 
     `Engine(cfg, envs_per_table, seed)`), each until it has finished `episodes` episodes or `max_steps` periods are over.  Returns a dict: `by_code` int64
     [K, len(SCORE_COLUMNS)] (finished episodes by terminal code, last column the episodes not finished), `steps_sum` int64 [K], `columns`, and with `log`
     `ep_code` uint8 / `ep_steps` uint16 [episodes, K * envs_per_table] (0xff / 0: not finished), else None.  `timing`: receives `kernel_ms` and `instance`."""
-    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
-    if qa.ndim != 2 or qa.shape[1] != 2835 or qb.shape != qa.shape:
-        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    qa, qb = _table_pair(qa, qb)
     K, n, episodes, max_steps = len(qa), int(envs_per_table), int(episodes), int(max_steps)
     score_check_args(K, n, episodes, max_steps)
     lib = _lib.load()
@@ -368,11 +376,7 @@ def score_map_buffers(n_tables: int, envs_per_table: int, episodes: int, log: bo
 
 
 def score_map_result(lib, by_code, steps_sum, visits, ep_code, ep_steps, ep_last_cell, timing):
-    if timing is not None:
-        ms, inst = C.c_double(), (C.c_int32 * 3)()
-        _lib.check(lib.dql_diag_score_map_last(C.byref(ms), inst))
-        timing["kernel_ms"] = ms.value
-        timing["instance"] = f"k_score_map<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    _last_call(lib, "score_map", "k_score_map", timing)
     return {"by_code": by_code, "steps_sum": steps_sum, "ep_code": ep_code, "ep_steps": ep_steps, "columns": SCORE_COLUMNS, "visits": visits, "ep_last_cell": ep_last_cell}
 
 
@@ -382,9 +386,7 @@ def score_map(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, episodes: 
     action was decided from, times 3, plus the action; with two axes both axes' decisions), and with `log` `ep_last_cell` uint16 [2, episodes, K *
     envs_per_table]: the x and y cell of the decision in whose period the episode ended (0xffff: not finished, or no y axis), else None.  At most
     SCORE_MAP_MAX_TABLES sets per call.  `timing`: receives `kernel_ms` and `instance`."""
-    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
-    if qa.ndim != 2 or qa.shape[1] != N_CELLS or qb.shape != qa.shape:
-        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    qa, qb = _table_pair(qa, qb)
     K, n, episodes, max_steps = len(qa), int(envs_per_table), int(episodes), int(max_steps)
     score_map_check_args(K, n, episodes, max_steps)
     lib = _lib.load()
@@ -420,11 +422,7 @@ def model_buffers(n_tables: int):
 
 
 def model_result(lib, pairs, reward_fx, terminal, by_code, steps_sum, timing):
-    if timing is not None:
-        ms, inst = C.c_double(), (C.c_int32 * 3)()
-        _lib.check(lib.dql_diag_model_last(C.byref(ms), inst))
-        timing["kernel_ms"] = ms.value
-        timing["instance"] = f"k_model<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    _last_call(lib, "model", "k_model", timing)
     return {"pairs": pairs, "reward_fx": reward_fx, "terminal": terminal, "by_code": by_code, "steps_sum": steps_sum, "columns": SCORE_COLUMNS,
             "visits": pairs.sum(axis=-1, dtype=np.int64) + terminal.sum(axis=-1)}
 
@@ -438,9 +436,7 @@ def transition_model(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, eps
     every decision adds to `pairs` uint32 [K, 2835, 945] at (cell, state after) if the episode went on, to `terminal` int64 [K, 2835, len(CHECK_NAMES)] at
     (cell, code) if it ended, and its reward times 2^26 (rounded to nearest even) to `reward_fx` int64 [K, 2835].  `by_code` and `steps_sum` are `score`'s;
     `visits` int64 [K, 2835] = pairs.sum(-1) + terminal.sum(-1).  Integer sums: bit-reproducible.  `timing`: receives `kernel_ms` and `instance`."""
-    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
-    if qa.ndim != 2 or qa.shape[1] != N_CELLS or qb.shape != qa.shape:
-        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    qa, qb = _table_pair(qa, qb)
     K, n, episodes, max_steps, eps = len(qa), int(envs_per_table), int(episodes), int(max_steps), float(eps)
     model_check_args(cfg, K, n, episodes, max_steps, eps)
     lib = _lib.load()
@@ -495,11 +491,7 @@ def grid_buffers(n_scenarios: int, n_tables: int, envs_per_table: int, episodes:
 
 
 def grid_result(lib, cfgs, by_code, steps_sum, touch_hist, ep_code, ep_steps, timing):
-    if timing is not None:
-        ms, inst = C.c_double(), (C.c_int32 * 3)()
-        _lib.check(lib.dql_diag_score_grid_last(C.byref(ms), inst))
-        timing["kernel_ms"] = ms.value
-        timing["instance"] = f"k_score_grid<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    _last_call(lib, "score_grid", "k_score_grid", timing)
     return {"by_code": by_code, "steps_sum": steps_sum, "touch_hist": touch_hist, "touch_edges": grid_touch_edges(cfgs), "ep_code": ep_code, "ep_steps": ep_steps,
             "columns": SCORE_COLUMNS}
 
@@ -516,9 +508,7 @@ def score_grid(cfgs, qa, qb, envs_per_table: int, seed: int, episodes: int = 1, 
     after the terminal period (two axes: the larger of the two offsets): bin = the number of `touch_edges[s]` (float64 [S, 7], j * mp_half_x / 4) the offset
     reaches, so bins 0 - 3 lie inside the half extent and 4 - 7 beyond it.  `timing`: receives `kernel_ms` and `instance`."""
     cfgs = list(cfgs)
-    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
-    if qa.ndim != 2 or qa.shape[1] != N_CELLS or qb.shape != qa.shape:
-        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    qa, qb = _table_pair(qa, qb)
     K, n, episodes, max_steps = len(qa), int(envs_per_table), int(episodes), int(max_steps)
     grid_check_args(cfgs, K, n, episodes, max_steps)
     lib = _lib.load()
@@ -564,11 +554,7 @@ def returns_buffers(n_tables: int):
 
 
 def returns_result(lib, visits, return_fx, cut_decisions, by_code, steps_sum, timing):
-    if timing is not None:
-        fly, sweep, inst = C.c_double(), C.c_double(), (C.c_int32 * 3)()
-        _lib.check(lib.dql_diag_returns_last(C.byref(fly), C.byref(sweep), inst))
-        timing["fly_ms"], timing["sweep_ms"] = fly.value, sweep.value
-        timing["instance"] = f"k_returns_fly<{'float' if inst[0] == 4 else 'double'}, {inst[1]}, {inst[2]}>"
+    _last_call(lib, "returns", "k_returns_fly", timing, times=("fly_ms", "sweep_ms"))
     return {"visits": visits, "return_fx": return_fx, "cut_decisions": cut_decisions, "by_code": by_code, "steps_sum": steps_sum, "columns": SCORE_COLUMNS}
 
 
@@ -581,9 +567,7 @@ def returns_map(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, eps: flo
     before the period * 3 + action, `visits` int64 [K, 2835] gains 1 and `return_fx` int64 [K, 2835] the return-to-go g_t = r_t + gamma g_{t+1} (float64, in
     units of 2^-26, g = 0 after the terminal period) rounded to nearest even.  Decisions of episodes that `max_steps` cut off are counted in `cut_decisions`
     int64 [K] and nowhere else.  `by_code` and `steps_sum` are `score`'s.  Integer sums: bit-reproducible.  `timing`: receives `fly_ms`, `sweep_ms`, `instance`."""
-    qa, qb = np.atleast_2d(_f64(qa)), np.atleast_2d(_f64(qb))
-    if qa.ndim != 2 or qa.shape[1] != N_CELLS or qb.shape != qa.shape:
-        raise ValueError("qa and qb must be [K, 2835] arrays of the same K")
+    qa, qb = _table_pair(qa, qb)
     K, n, episodes, max_steps, eps, gamma = len(qa), int(envs_per_table), int(episodes), int(max_steps), float(eps), float(gamma)
     returns_check_args(cfg, K, n, episodes, max_steps, eps, gamma)
     lib = _lib.load()
