@@ -125,7 +125,8 @@ struct dql_ensemble {
   // teams (DESIGN.md section 17, dql_teams.inc): learner l owns envs l E .. l E + E - 1 of the n_envs = n E the state arrays hold; teams: dql_ensemble_run flies k_learn_team
   int envs_per_learner = 1; long long n_envs = 0; bool teams = false;
   // n-step targets (DESIGN.md section 22, dql_nstep.inc); nstep = 0: dql_ensemble_run flies k_learn and the arrays below are never read.  The learners' pending
-  // windows between launches: key / val [DQL_NSTEP_MAX][n], len [n], allocated by the first dql_ensemble_set_nstep with n >= 1
+  // windows between launches: key / val [DQL_NSTEP_MAX][n], len [n], allocated by the first dql_ensemble_set_nstep with n >= 1 — or, with recipes installed, by the
+  // first dql_ensemble_set_recipe_nstep with n >= 1 (section 23, dql_nstep_recipes.inc: n is then a recipe's, EnsRecipes::nstep, and `nstep` here stays 0)
   int nstep = 0;
   uint16_t* ns_key = nullptr; double* ns_val = nullptr; int* ns_len = nullptr;
 };

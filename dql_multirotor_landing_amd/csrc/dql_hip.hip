@@ -2079,6 +2079,7 @@ int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
 #include "dql_recipes.inc"
 #include "dql_teams.inc"
 #include "dql_nstep.inc"
+#include "dql_nstep_recipes.inc"
 #include "dql_score_map.inc"
 #include "dql_model.inc"
 #include "dql_returns.inc"

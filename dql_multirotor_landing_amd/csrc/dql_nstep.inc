@@ -55,6 +55,21 @@ static int ens_launch_nstep(dql_ensemble* x, int k, int n_waves) {
   return DQL_OK;
 }
 
+// the persistent windows, zeroed, on the first call (dql_ensemble_set_nstep and dql_ensemble_set_recipe_nstep with n >= 1); later calls change nothing
+static int ens_alloc_windows(dql_ensemble* x) {
+  if (x->ns_len) return DQL_OK;
+  const size_t L = (size_t)x->n;
+  uint16_t* key = nullptr; double* val = nullptr; int* len = nullptr;
+  bool ok = x->dev.alloc((void**)&key, (size_t)DQL_NSTEP_MAX * L * sizeof(uint16_t)) == hipSuccess && x->dev.alloc((void**)&val, (size_t)DQL_NSTEP_MAX * L * sizeof(double)) == hipSuccess &&
+            x->dev.alloc((void**)&len, L * sizeof(int)) == hipSuccess;
+  if (!ok) { (void)x->dev.release(key); (void)x->dev.release(val); (void)x->dev.release(len); return fail(DQL_ENOMEM, "hipMalloc failed"); }
+  ok = hipMemset(key, 0, (size_t)DQL_NSTEP_MAX * L * sizeof(uint16_t)) == hipSuccess && hipMemset(val, 0, (size_t)DQL_NSTEP_MAX * L * sizeof(double)) == hipSuccess &&
+       hipMemset(len, 0, L * sizeof(int)) == hipSuccess;
+  if (!ok) { (void)x->dev.release(key); (void)x->dev.release(val); (void)x->dev.release(len); return fail(DQL_EHIP, "hipMemset failed"); }
+  x->ns_key = key; x->ns_val = val; x->ns_len = len;
+  return DQL_OK;
+}
+
 extern "C" {
 int dql_ensemble_set_nstep(dql_ensemble* x, int32_t n) {
   CHECK_ENS(x);
@@ -74,16 +89,7 @@ int dql_ensemble_set_nstep(dql_ensemble* x, int32_t n) {
       if (v != 0)
         return fail(DQL_ESTATE, "dql_ensemble_set_nstep: n cannot change while a learner's pending window holds entries (change it after creation, after dql_ensemble_set_level, or when every learner is frozen); nothing was changed");
   }
-  if (n >= 1 && !x->ns_len) {
-    uint16_t* key = nullptr; double* val = nullptr; int* len = nullptr;
-    bool ok = x->dev.alloc((void**)&key, (size_t)DQL_NSTEP_MAX * L * sizeof(uint16_t)) == hipSuccess && x->dev.alloc((void**)&val, (size_t)DQL_NSTEP_MAX * L * sizeof(double)) == hipSuccess &&
-              x->dev.alloc((void**)&len, L * sizeof(int)) == hipSuccess;
-    if (!ok) { (void)x->dev.release(key); (void)x->dev.release(val); (void)x->dev.release(len); return fail(DQL_ENOMEM, "hipMalloc failed"); }
-    ok = hipMemset(key, 0, (size_t)DQL_NSTEP_MAX * L * sizeof(uint16_t)) == hipSuccess && hipMemset(val, 0, (size_t)DQL_NSTEP_MAX * L * sizeof(double)) == hipSuccess &&
-         hipMemset(len, 0, L * sizeof(int)) == hipSuccess;
-    if (!ok) { (void)x->dev.release(key); (void)x->dev.release(val); (void)x->dev.release(len); return fail(DQL_EHIP, "hipMemset failed"); }
-    x->ns_key = key; x->ns_val = val; x->ns_len = len;
-  }
+  if (n >= 1) { const int rc = ens_alloc_windows(x); if (rc) return rc; }
   x->nstep = n;
   return DQL_OK;
 }

@@ -65,7 +65,12 @@ struct EnsRecipes {
   RecipeSched sched[RCP_MAX]{}; bool have_lv[RCP_MAX][DQL_MAX_LEVELS]{};   // (the tables its pointers name are the ensemble's device allocations)
   int* d_recipe_of = nullptr; RecipeRule* d_rule = nullptr; RecipeSched* d_sched = nullptr; void* d_mdpk = nullptr;  // [L], [n], [n], [n][DQL_MAX_LEVELS] MdpK<T>
   int* d_worklist = nullptr; int* d_wave_recipe = nullptr; int* d_wave_level = nullptr; long long wl_slots = 0;
+  // per-recipe n-step targets (DESIGN.md section 23, dql_nstep_recipes.inc): the capacity of the members' pending windows, 0: the one-step update; the device
+  // copy [n] is made by the first dql_ensemble_set_recipe_nstep that changes an n and read by k_learn_recipes_nstep alone
+  int nstep[RCP_MAX]{}; int* d_nstep = nullptr;
 };
+// of dql_nstep_recipes.inc: ens_fly_recipes with k_learn_recipes_nstep (flown while a recipe that has a member has n >= 1)
+static int ens_fly_recipes_nstep(dql_ensemble* x, int k, int n_waves);
 static void ens_recipes_release(dql_ensemble* x) {
   EnsRecipes* q = x->rcp;
   if (!q) return;
@@ -73,7 +78,7 @@ static void ens_recipes_release(dql_ensemble* x) {
     (void)x->dev.release((void*)q->sched[r].alpha_tab);
     for (int k = 0; k < DQL_MAX_LEVELS; ++k) (void)x->dev.release((void*)q->sched[r].lv[k].eps_tab);
   }
-  void* own[] = {q->d_recipe_of, q->d_rule, q->d_sched, q->d_mdpk, q->d_worklist, q->d_wave_recipe, q->d_wave_level};
+  void* own[] = {q->d_recipe_of, q->d_rule, q->d_sched, q->d_mdpk, q->d_worklist, q->d_wave_recipe, q->d_wave_level, q->d_nstep};
   for (void* p : own) (void)x->dev.release(p);
   delete q;
   x->rcp = nullptr;
@@ -86,18 +91,22 @@ static int ens_recipes_min_last_level(const dql_ensemble* x) {  // over the reci
   for (int r : x->rcp->recipe_of) if (x->rcp->have_rule[r] && x->rcp->rule[r].rule.last_level < lo) lo = x->rcp->rule[r].rule.last_level;
   return lo;
 }
+// what k_learn_recipes and k_learn_recipes_nstep (dql_nstep_recipes.inc) share
+template <typename T> static LearnRecipesArgs<T> make_learn_recipes_args(dql_ensemble* x, int k, int n_waves) {
+  EnsRecipes* q = x->rcp;
+  LearnRecipesArgs<T> g;
+  g.a = make_learn_args<T>(x, q->d_mdpk, k);
+  g.rs = (const RecipeSched DQL_CONST_AS*)q->d_sched; g.worklist = q->d_worklist;
+  g.wave_recipe = (const int DQL_CONST_AS*)q->d_wave_recipe; g.wave_level = (const int DQL_CONST_AS*)q->d_wave_level;
+  g.n_waves = n_waves; g.n_recipes = q->n;
+  return g;
+}
 // ens_fly's recipe launch: k periods from period x->j on n_waves waves of one (recipe, level) each
 static int ens_fly_recipes(dql_ensemble* x, int k, int n_waves) {
-  EnsRecipes* q = x->rcp;
   int rc = upload_schedule(x->cfg, x->j, k, x->d_mgr0, x->d_sched); if (rc) return rc;
   by_dtype(x->cfg.dtype, [&](auto t) {
     using T = decltype(t);
-    LearnRecipesArgs<T> g;
-    g.a = make_learn_args<T>(x, q->d_mdpk, k);
-    g.rs = (const RecipeSched DQL_CONST_AS*)q->d_sched; g.worklist = q->d_worklist;
-    g.wave_recipe = (const int DQL_CONST_AS*)q->d_wave_recipe; g.wave_level = (const int DQL_CONST_AS*)q->d_wave_level;
-    g.n_waves = n_waves; g.n_recipes = q->n;
-    hipLaunchKernelGGL((k_learn_recipes<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
+    hipLaunchKernelGGL((k_learn_recipes<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, make_learn_recipes_args<T>(x, k, n_waves));
   });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
@@ -119,6 +128,8 @@ static int ens_run_recipes(dql_ensemble* x, int64_t periods) {
       return fail(DQL_EINVAL, "dql_ensemble_run: with recipes installed every recipe that has a member needs dql_ensemble_set_recipe and dql_ensemble_set_recipe_level_schedules for every "
                               "level from its members' up to its last_level; nothing was launched");
   }
+  bool nstep_kernel = false;  // a recipe that has a member has n >= 1: every launch of this call is k_learn_recipes_nstep's
+  for (int r : q->recipe_of) nstep_kernel = nstep_kernel || q->nstep[r] >= 1;
   EvTimer timer;
   rc = timer.start(); if (rc) return rc;
   std::vector<int> worklist((size_t)q->wl_slots), wave_recipe((size_t)(q->wl_slots / ADV_WAVE)), wave_level((size_t)(q->wl_slots / ADV_WAVE));
@@ -147,11 +158,23 @@ static int ens_run_recipes(dql_ensemble* x, int64_t periods) {
       HIP_TRY(hipMemcpy(q->d_worklist, worklist.data(), (size_t)n_waves * ADV_WAVE * sizeof(int), hipMemcpyHostToDevice));
       HIP_TRY(hipMemcpy(q->d_wave_recipe, wave_recipe.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
       HIP_TRY(hipMemcpy(q->d_wave_level, wave_level.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
-      rc = ens_fly_recipes(x, k, n_waves); if (rc) return rc;
+      rc = nstep_kernel ? ens_fly_recipes_nstep(x, k, n_waves) : ens_fly_recipes(x, k, n_waves); if (rc) return rc;
     }
     x->j += k; left -= k;
   }
   return timer.stop_ms(&x->last_ms);
+}
+
+// an install or an uninstall would orphan pending entries of the recipes' n-step targets (only an ensemble that called dql_ensemble_set_recipe_nstep with
+// n >= 1 has window arrays while recipes can be installed); DQL_OK: every window is empty
+static int ens_recipes_windows_empty(dql_ensemble* x) {
+  if (!x->ns_len) return DQL_OK;
+  std::vector<int> len((size_t)x->n);
+  HIP_TRY(hipMemcpy(len.data(), x->ns_len, len.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int v : len)
+    if (v != 0)
+      return fail(DQL_ESTATE, "dql_ensemble_set_recipes: recipes cannot be installed or uninstalled while a learner's pending window holds entries (after dql_ensemble_set_level, or when every learner is frozen); nothing was changed");
+  return DQL_OK;
 }
 
 extern "C" {
@@ -162,6 +185,7 @@ int dql_ensemble_set_recipes(dql_ensemble* x, int32_t n_recipes, const int32_t* 
   if (n_recipes == 0) {
     HIP_TRY(hipSetDevice(x->device));
     HIP_TRY(hipDeviceSynchronize());
+    if (x->rcp) { int rc = ens_recipes_windows_empty(x); if (rc) return rc; }
     ens_recipes_release(x);
     return DQL_OK;
   }
@@ -172,6 +196,7 @@ int dql_ensemble_set_recipes(dql_ensemble* x, int32_t n_recipes, const int32_t* 
     if (recipe_of[l] < 0 || recipe_of[l] >= n_recipes) return fail(DQL_EINVAL, "dql_ensemble_set_recipes: every recipe_of[l] must be in 0..n_recipes - 1; nothing was changed");
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipDeviceSynchronize());
+  { int rc = ens_recipes_windows_empty(x); if (rc) return rc; }
   // the new set is allocated in full before the installed one is let go
   EnsRecipes* q = new EnsRecipes;
   q->n = n_recipes;

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from types import SimpleNamespace
 from typing import Optional, Sequence
 
@@ -88,7 +88,9 @@ class LevelSchedule:
 class Recipe:
     """What the learners of one recipe share (include/dql.h).  The defaults are the reference's recipe: its quirks, the config's
     learning rates, its exploration and promotion rule per level, its ratios, `Q[k] = Q[k-1] ratio` after level k with the k = 0 wrap (transfer_order 0).
-    transfer_order 1 is the paper's: `Q[k+1] = Q[k] ratios[k+1]` on entering level k + 1, the level-k block kept, no wrap."""
+    transfer_order 1 is the paper's: `Q[k+1] = Q[k] ratios[k+1]` on entering level k + 1, the level-k block kept, no wrap.
+    nstep: the recipe's learners update with the uncorrected n-step Double-Q return of their pending windows (`SequentialEnsemble.set_nstep`'s update, DESIGN.md
+    section 23); 0, the default, is the one-step update."""
     quirks: int = 0x7F
     alpha_table: Optional[Sequence[float]] = None   # None: the ensemble config's
     alpha_min: Optional[float] = None               # None: the ensemble config's
@@ -97,9 +99,12 @@ class Recipe:
     advance_exhausted: bool = True
     transfer_order: int = ORDER_REFERENCE
     levels: Sequence[LevelSchedule] = field(default_factory=lambda: tuple(LevelSchedule() for _ in range(MAX_LEVELS)))
+    nstep: int = 0                                  # 0: the one-step update; 1..NSTEP_MAX: the n-step return as this recipe's target
 
     def checked(self, cfg: DqlConfig):
         """-> (alpha float64[], alpha_min, ratios float64[5], per level (eps float64[], window, min_successes, max_episodes)); ValueError on what the library refuses"""
+        if not 0 <= int(self.nstep) <= NSTEP_MAX:
+            raise ValueError(f"a recipe's nstep must be in 0..{NSTEP_MAX} (0: the one-step update)")
         alpha = cfg.alpha_table() if self.alpha_table is None else np.ascontiguousarray(self.alpha_table, dtype=np.float64).ravel()
         alpha_min = float(cfg.alpha_min if self.alpha_min is None else self.alpha_min)
         if alpha.size < 1 or not ((alpha >= 0.0) & (alpha <= 1.0)).all() or not 0.0 <= alpha_min <= 1.0:
@@ -311,13 +316,22 @@ class SequentialEnsemble:
                                                         int(r.transfer_order)))
             for k, (e, window, ms, me) in enumerate(lv):
                 _lib.check(self.lib.dql_ensemble_set_recipe_level_schedules(self._h, i, k, _p(e), e.size, window, ms, me))
+            if int(r.nstep):  # (fresh recipes have n = 0)
+                _lib.check(self.lib.dql_ensemble_set_recipe_nstep(self._h, i, int(r.nstep)))
         self._recipes = recipes
 
     def recipes(self):
-        """(the installed `Recipe`s, recipe_of int32 [L]); ([], all -1) while none are installed"""
+        """(the installed `Recipe`s, each with the n-step setting the library holds for it, recipe_of int32 [L]); ([], all -1) while none are installed"""
         of = np.zeros(self.n, dtype=np.int32)
         _lib.check(self.lib.dql_ensemble_get_recipes(self._h, _p(of)))
-        return (list(getattr(self, "_recipes", [])) if (of >= 0).all() else []), of
+        if not (of >= 0).all():
+            return [], of
+        out = []
+        for i, r in enumerate(getattr(self, "_recipes", [])):
+            v = C.c_int32()
+            _lib.check(self.lib.dql_ensemble_get_recipe_nstep(self._h, i, C.byref(v)))
+            out.append(replace(r, nstep=int(v.value)))
+        return out, of
 
     def recipe_summary(self):
         """per installed recipe: {"members", "learners_per_level" [5], "promoted_per_level" [5], "exhausted_per_level" [5] (learners that left level k — or

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DQL_ABI_VERSION 6 /* 6: dql_agent_mirror_update_deferred / _complete (added since, without a new number: dql_ensemble_set_curriculum, _set_level_schedules, _get_levels, _n_unfinished; dql_ensemble_set_recipes, _set_recipe, _set_recipe_level_schedules, _get_recipes; dql_ensemble_create_teams, _envs_per_learner; dql_ensemble_set_nstep, _get_nstep); 5: tick replay operators (dql_*_run), measurement symbols moved to dql_diag.h as dql_diag_* */
+#define DQL_ABI_VERSION 6 /* 6: dql_agent_mirror_update_deferred / _complete (added since, without a new number: dql_ensemble_set_curriculum, _set_level_schedules, _get_levels, _n_unfinished; dql_ensemble_set_recipes, _set_recipe, _set_recipe_level_schedules, _get_recipes; dql_ensemble_create_teams, _envs_per_learner; dql_ensemble_set_nstep, _get_nstep; dql_ensemble_set_recipe_nstep, _get_recipe_nstep); 5: tick replay operators (dql_*_run), measurement symbols moved to dql_diag.h as dql_diag_* */
 
 typedef enum dql_status {
   DQL_OK = 0,
@@ -759,6 +759,22 @@ int dql_ensemble_envs_per_learner(dql_ensemble* ens, int32_t* envs_per_learner);
 #define DQL_NSTEP_MAX 16
 int dql_ensemble_set_nstep(dql_ensemble* ens, int32_t n);
 int dql_ensemble_get_nstep(dql_ensemble* ens, int32_t* n, int32_t* pending_len_or_null);
+
+/* ---- n-step targets per recipe ----
+ * With recipes installed (curriculum mode), n is a property of a recipe: dql_ensemble_set_recipe_nstep(ens, recipe, n) with 0 <= n <= DQL_NSTEP_MAX.  The
+ * learners of a recipe with n = 0, the state after dql_ensemble_set_recipes, fly the one-step update exactly as before; those of a recipe with n >= 1 walk
+ * the levels under their recipe's rule and update with the n-step return described above (append, one early read of the row of s', mask, flush at an
+ * episode's end, oldest-entry update from a full window, the entry's own coin), with the recipe's quirks, learning rates and per-level schedules.  Launches
+ * are cut at the multiples of advance_every as before; a window that is open at a cut persists, so runs of a and b periods equal one run of a + b.  A
+ * learner freezes only after its flush, so a learner that advances has an empty window.  Learner l of a mixed ensemble equals, bit for bit in every output,
+ * learner l of an ensemble of the same size and seed in which every learner has l's recipe, n included.  dql_ensemble_set_level empties every window;
+ * dql_ensemble_transfer, _set_tables and _rearm leave them alone.  The ensemble-wide dql_ensemble_set_nstep stays the plain mode's switch with its refusals
+ * unchanged, and dql_ensemble_get_nstep keeps returning it (0 in a recipe ensemble) and the windows' lengths.
+ * Refused with a message and nothing changed: DQL_EINVAL while no recipes are installed, for a recipe outside 0..n_recipes - 1 and for n outside
+ * 0..DQL_NSTEP_MAX; DQL_ESTATE for a change of n while a member of that recipe has a pending window with entries (the value the recipe already has is
+ * accepted).  dql_ensemble_set_recipes, install or uninstall, returns DQL_ESTATE with nothing changed while any window holds entries. */
+int dql_ensemble_set_recipe_nstep(dql_ensemble* ens, int32_t recipe, int32_t n);
+int dql_ensemble_get_recipe_nstep(dql_ensemble* ens, int32_t recipe, int32_t* n);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,8 @@ learner of the ensemble; a learner advances at the next period index that is a m
 episode budget ran out stays where it is instead of advancing as the reference's loop does.
 --recipes FILE.json: several recipes in ONE ensemble (ensemble.curriculum_recipes; implies --per-learner).  The file is a list; an entry is
 a preset name — "reference" (quirks 0x7f, the reference's transfer order) or "paper" (evaluation.Q_PAPER, the paper's order) — or an object with any of "preset"
-(default "reference"), "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min" and "levels": {"K": {"eps": [...],
+(default "reference"), "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min", "nstep" (0..16: the recipe's
+n-step target; default 0, the one-step update) and "levels": {"K": {"eps": [...],
 "window", "min_successes", "max_episodes"}} for the levels that differ from the preset's.  Learners are dealt round-robin: recipe r gets the learners with
 l % R == r.  With --score the landing-rate quantiles are reported per recipe.
 --score-grid FIELD=v1,v2,... (repeatable, with --score): after the curriculum, every learner's tables are also scored where they live over the Cartesian product
@@ -48,7 +49,7 @@ from dql_multirotor_landing_amd import evaluation  # noqa: E402
 from dql_multirotor_landing_amd.ensemble import (LevelSchedule, NSTEP_MAX, ORDER_PAPER, ORDER_REFERENCE, REFERENCE_RATIOS, Recipe, SequentialEnsemble, TEAM_SIZES, curriculum,  # noqa: E402
                                                  curriculum_per_learner, curriculum_recipes, exploration_rates, min_successes_for, train_level)
 
-RECIPE_KEYS = {"preset", "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min", "levels"}
+RECIPE_KEYS = {"preset", "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min", "levels", "nstep"}
 LEVEL_KEYS = {"eps", "window", "min_successes", "max_episodes"}
 
 
@@ -74,7 +75,7 @@ def load_recipes(path, episodes, last_level=4, advance_exhausted=True):
         if not isinstance(e, dict) or set(e) - RECIPE_KEYS:
             raise ValueError(f"recipe {i}: a preset name or an object with keys among {sorted(RECIPE_KEYS)}")
         r = preset_recipe(e.get("preset", "reference"), episodes, last_level, advance_exhausted)
-        for k in ("quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min"):
+        for k in ("quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min", "nstep"):
             if k in e:
                 setattr(r, k, e[k])
         levels = list(r.levels)
@@ -231,7 +232,7 @@ def main():
     ap.add_argument("--score-map", action="store_true", help="with --score: also count where every learner's greedy policy flies, and report it against the reference's tables")
     ap.add_argument("--score-grid", action="append", default=[], metavar="FIELD=v1,v2,...", help="with --score: also score every learner over this grid of scenarios in one launch (repeatable)")
     ap.add_argument("--preset", default="reference", choices=["reference", "paper"], help="quirks and transfer order of the level-by-level driver (not with --per-learner / --recipes)")
-    ap.add_argument("--nstep", type=int, default=0, metavar="N", help="n-step Double-Q targets, 1..16 (0: the reference's one-step update; not with --per-learner / --recipes / --envs-per-learner above 1)")
+    ap.add_argument("--nstep", type=int, default=0, metavar="N", help="n-step Double-Q targets, 1..16 (0: the reference's one-step update; not with --per-learner / --recipes / --envs-per-learner above 1; with --recipes give each recipe its own \"nstep\" in the file)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     if a.preset != "reference" and (a.per_learner or a.recipes):
@@ -270,7 +271,9 @@ def main():
             recipe_of = deal(a.learners, len(recipes))
             h = curriculum_recipes(ens, recipes, recipe_of, advance_every=a.advance_every, max_periods=a.max_periods, on_chunk=progress)
             hist = [{"promotion_episode": h["promoted_at"][k], "periods": h["periods"]} for k in range(a.levels)]
-            extra = {"level": h["level"], "episodes_at": h["episodes_at"], "entered_period": h["entered_period"], "recipe_of": recipe_of}
+            recipe_nstep = [int(r.nstep) for r in ens.recipes()[0]]  # as the library holds them
+            extra = {"level": h["level"], "episodes_at": h["episodes_at"], "entered_period": h["entered_period"], "recipe_of": recipe_of,
+                     "recipe_nstep": np.asarray(recipe_nstep, np.int32)}
         elif a.per_learner:
             h = curriculum_per_learner(ens, last_level=a.levels - 1, advance_every=a.advance_every, advance_exhausted=not a.drop_exhausted, max_episodes=a.episodes,
                                        max_periods=a.max_periods, on_chunk=progress)
@@ -284,6 +287,8 @@ def main():
             extra.update({"touchdown_rate": td, "goal_hold_rate": gh})
             if names is not None:
                 rep["recipes"] = per_recipe_report(names, recipe_of, td, gh, ens.recipe_summary())
+                for entry, n in zip(rep["recipes"], recipe_nstep):
+                    entry["nstep"] = n
                 rep.update({"periods": int(h["periods"]), "unfinished": ens.n_unfinished()})
                 if maps is not None:
                     for r, entry in enumerate(rep["recipes"]):
