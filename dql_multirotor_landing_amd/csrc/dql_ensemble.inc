@@ -99,6 +99,30 @@ __global__ void k_ens_advance(LearnMem mem, AdvanceMem adv, AdvanceRule rule, in
   (void)advance_learner(mem, adv, rule, si, l, j, n_cells);
 }
 
+// a launch's worklist on the host and on the device: build() regroups the live learners by level (build_worklist) or, where recipe_of is set, by (recipe,
+// level) (build_worklist_recipes: then the wave_recipe column exists); upload() copies the waves build() made.  dql_ensemble and EnsRecipes (dql_recipes.inc)
+// each hold one: the capacities differ.
+struct EnsWorklist {
+  long long slots = 0;                                   // 64 per wave
+  const int* recipe_of = nullptr; int n_recipes = 0;     // host [L]; null: by level alone
+  std::vector<int> list, wave_recipe, wave_level;        // host [slots], [slots / 64], [slots / 64]
+  int* d_list = nullptr; int* d_wave_recipe = nullptr; int* d_wave_level = nullptr;
+  void resize(long long n_slots, const int* of = nullptr, int n_of = 0) {
+    slots = n_slots; recipe_of = of; n_recipes = n_of;
+    list.assign((size_t)slots, 0); wave_level.assign((size_t)(slots / ADV_WAVE), 0); wave_recipe.assign(of ? (size_t)(slots / ADV_WAVE) : 0, 0);
+  }
+  int build(const int* frozen, const int* level, long long n, unsigned long long* faults) {  // -> the waves to fly
+    return recipe_of ? build_worklist_recipes(frozen, level, recipe_of, n, n_recipes, list.data(), wave_recipe.data(), wave_level.data(), slots, faults)
+                     : build_worklist(frozen, level, n, list.data(), wave_level.data(), slots, faults);
+  }
+  int upload(int n_waves) const {
+    HIP_TRY(hipMemcpy(d_list, list.data(), (size_t)n_waves * ADV_WAVE * sizeof(int), hipMemcpyHostToDevice));
+    if (recipe_of) HIP_TRY(hipMemcpy(d_wave_recipe, wave_recipe.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_wave_level, wave_level.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
+    return DQL_OK;
+  }
+};
+
 // ---- ensembles of sequential learners (DESIGN.md section 12) ----
 struct dql_ensemble {
   dql_config cfg;
@@ -119,7 +143,7 @@ struct dql_ensemble {
   int advance_every = 0;
   void* mdpk5 = nullptr;                                      // [DQL_MAX_LEVELS] MdpK<T>, entry k with working = k
   LevelSched* d_lv = nullptr; LevelSched h_lv[DQL_MAX_LEVELS]{}; bool have_lv[DQL_MAX_LEVELS]{};
-  int* d_worklist = nullptr; int* d_wave_level = nullptr; long long wl_slots = 0;
+  EnsWorklist wl;                                             // by level (capacity: worklist_capacity)
   long long n_launches = 0, launched_periods = 0, launched_wave_periods = 0;  // since creation (dql_diag_ensemble_launches)
   struct EnsRecipes* rcp = nullptr;  // per-learner recipes (DESIGN.md section 16, dql_recipes.inc); null: none are installed and every call is as it was
   // teams (DESIGN.md section 17, dql_teams.inc): learner l owns envs l E .. l E + E - 1 of the n_envs = n E the state arrays hold; teams: dql_ensemble_run flies k_learn_team
@@ -130,15 +154,21 @@ struct dql_ensemble {
   int nstep = 0;
   uint16_t* ns_key = nullptr; double* ns_val = nullptr; int* ns_len = nullptr;
 };
-// of dql_recipes.inc: the installed recipes let go, the rule learner l advances by, the smallest last_level of the populated recipes, dql_ensemble_run's loop
+// which of the six learner kernels a launch flies (ens_kernel_of decides, ens_fly switches)
+enum EnsKernel { ENS_K_LEARN, ENS_K_TEAM, ENS_K_NSTEP, ENS_K_LEVELS, ENS_K_RECIPES, ENS_K_RECIPES_NSTEP };
+// of dql_recipes.inc: the installed recipes let go, the rule learner l advances by, the smallest last_level of the populated recipes, whether a recipe that has
+// a member has n >= 1, the device copy of the recipes' n (null until one was set), dql_ensemble_run's part with recipes installed
 static void ens_recipes_release(dql_ensemble* x);
 static const AdvanceRule& ens_rule_of(const dql_ensemble* x, size_t l);
 static int ens_recipes_min_last_level(const dql_ensemble* x);
-static int ens_run_recipes(dql_ensemble* x, int64_t periods);
-// of dql_teams.inc: one launch of k_learn_team (ens_fly's part for a team ensemble)
-static int ens_launch_teams(dql_ensemble* x, int k, int n_waves);
-// of dql_nstep.inc: one launch of k_learn_nstep (ens_fly's part while nstep >= 1)
-static int ens_launch_nstep(dql_ensemble* x, int k, int n_waves);
+static bool ens_recipes_any_nstep(const dql_ensemble* x);
+static const int* ens_recipes_nstep_table(const dql_ensemble* x);
+static int ens_run_recipes(dql_ensemble* x, int64_t periods, EnsKernel kern);
+// each later fragment's argument filler, next to its kernel: the kernel's arguments from the ensemble, and the launch of k periods on n_waves waves
+template <typename T> static void launch_learn_recipes(dql_ensemble* x, int k, int n_waves);        // dql_recipes.inc
+template <typename T> static void launch_learn_team(dql_ensemble* x, int k, int n_waves);           // dql_teams.inc
+template <typename T> static void launch_learn_nstep(dql_ensemble* x, int k, int n_waves);          // dql_nstep.inc
+template <typename T> static void launch_learn_recipes_nstep(dql_ensemble* x, int k, int n_waves);  // dql_nstep_recipes.inc
 #define ENS_NSTEP_REFUSED(who) "" who ": n-step targets (dql_ensemble_set_nstep with n >= 1) are for the plain mode, where every learner flies the config's level; set n = 0 first; nothing was changed and nothing was launched"
 #define ENS_TEAMS_REFUSED(who) "" who ": an ensemble with more than one env per learner flies the barrier mode only (teams have no per-learner curriculum and no recipes); nothing was changed and nothing was launched"
 #define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
@@ -156,6 +186,44 @@ static void ens_free(dql_ensemble* x) {
   x->dev.free_all();
   delete x;
 }
+// ---- shared host helpers of the learner family (DESIGN.md section 15) ----
+// `count` elements of one device array -> host
+template <typename T> static int ens_fetch(const T* d, size_t count, std::vector<T>& h) {
+  h.resize(count);
+  HIP_TRY(hipMemcpy(h.data(), d, count * sizeof(T), hipMemcpyDeviceToHost));
+  return DQL_OK;
+}
+// all of these device arrays, zeroed, or none of them: DQL_OK; DQL_ENOMEM (a hipMalloc failed) or DQL_EHIP (a hipMemset did) with every pointer null again.
+// The caller says the sentence.
+struct DevWant { void** p; size_t bytes; };
+static int ens_alloc_zeroed(DevOwned& dev, std::initializer_list<DevWant> want) {
+  int rc = DQL_OK;
+  for (const DevWant& w : want) {
+    if (rc) break;
+    if (dev.alloc(w.p, w.bytes) != hipSuccess) rc = DQL_ENOMEM;
+    else if (hipMemset(*w.p, 0, w.bytes) != hipSuccess) rc = DQL_EHIP;
+  }
+  if (rc) for (const DevWant& w : want) { (void)dev.release(*w.p); *w.p = nullptr; }
+  return rc;
+}
+// DQL_ESTATE with the sentence while a learner l with member(l) has entries in its pending window (no window arrays: nobody has)
+template <typename F> static int ens_windows_empty(dql_ensemble* x, F member, const char* sentence) {
+  if (!x->ns_len) return DQL_OK;
+  std::vector<int> len;
+  const int rc = ens_fetch(x->ns_len, (size_t)x->n, len); if (rc) return rc;
+  for (size_t l = 0; l < len.size(); ++l) if (len[l] != 0 && member(l)) return fail(DQL_ESTATE, sentence);
+  return DQL_OK;
+}
+// what the host found wrong while it built a worklist, added to the device's `faults` word
+static int ens_add_faults(dql_ensemble* x, unsigned long long more) {
+  if (!more) return DQL_OK;
+  unsigned long long v = 0;
+  HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
+  v += more;
+  HIP_TRY(hipMemcpy(x->mem.faults, &v, sizeof(v), hipMemcpyHostToDevice));
+  return DQL_OK;
+}
+
 // every learner to level k: the per-level history from level k on is cleared, level k is entered at the present period index
 static int ens_set_levels(dql_ensemble* x, int k) {
   const size_t n = (size_t)x->n;
@@ -201,33 +269,131 @@ template <typename T> static LearnArgs<T> make_learn_args(dql_ensemble* x, const
   a.seed = x->seed; a.j0 = x->j; a.n_periods = n_periods;
   return a;
 }
-// one launch of k periods from period x->j on n_waves waves: the tick schedule, the kernel (by level through the worklist, or every learner at the config's level),
-// its completion, the launch accounting
-static int ens_fly(dql_ensemble* x, int k, int n_waves, bool by_level) {
-  int rc = upload_schedule(x->cfg, x->j, k, x->d_mgr0, x->d_sched); if (rc) return rc;  // (synchronous: the previous launch has read its schedule)
+template <typename T> static void launch_learn(dql_ensemble* x, int k, int n_waves) {
+  hipLaunchKernelGGL((k_learn<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, make_learn_args<T>(x, x->mdpk, k));
+}
+template <typename T> static void launch_learn_levels(dql_ensemble* x, int k, int n_waves) {
+  LearnLevelsArgs<T> g;
+  g.a = make_learn_args<T>(x, x->mdpk5, k);
+  g.lv = (const LevelSched DQL_CONST_AS*)x->d_lv; g.worklist = x->wl.d_list; g.wave_level = (const int DQL_CONST_AS*)x->wl.d_wave_level; g.n_waves = n_waves;
+  hipLaunchKernelGGL((k_learn_levels<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
+}
+// The one place that says which kernel flies.  by_level: the launch goes through a worklist (curriculum mode, with or without recipes); with one env per learner
+// a team ensemble in curriculum mode flies k_learn_levels, the same learner; n >= 1 is refused on team ensembles and in curriculum mode, and with recipes
+// installed n is a recipe's: one recipe that has a member and n >= 1 makes every launch k_learn_recipes_nstep's.
+static EnsKernel ens_kernel_of(const dql_ensemble* x, bool by_level) {
+  if (by_level) return !x->rcp ? ENS_K_LEVELS : ens_recipes_any_nstep(x) ? ENS_K_RECIPES_NSTEP : ENS_K_RECIPES;
+  return x->teams ? ENS_K_TEAM : x->nstep ? ENS_K_NSTEP : ENS_K_LEARN;
+}
+// The one launch path of the learners: k periods from period x->j on n_waves waves.  The tick schedule, the kernel, its completion, the launch accounting
+// (dql_diag_ensemble_launches).
+static int ens_fly(dql_ensemble* x, EnsKernel kern, int k, int n_waves) {
+  const bool windows = kern == ENS_K_NSTEP || kern == ENS_K_RECIPES_NSTEP;
+  if (windows && (!x->ns_key || !x->ns_val || !x->ns_len || (kern == ENS_K_RECIPES_NSTEP && !ens_recipes_nstep_table(x))))  // (never taken unless a bug)
+    return fail(DQL_ESTATE, kern == ENS_K_NSTEP ? "dql_ensemble_run: n-step targets are on but the pending windows were never allocated; nothing was launched"
+                                                : "dql_ensemble_run: a recipe has n-step targets but the pending windows were never allocated; nothing was launched");
+  const int rc = upload_schedule(x->cfg, x->j, k, x->d_mgr0, x->d_sched); if (rc) return rc;  // (synchronous: the previous launch has read its schedule)
   by_dtype(x->cfg.dtype, [&](auto t) {
     using T = decltype(t);
-    if (x->teams && !by_level) return;  // k_learn_team, below (with one env per learner a team ensemble in curriculum mode flies k_learn_levels: the same learner)
-    if (x->nstep && !by_level) return;  // k_learn_nstep, below (n >= 1 is refused on team ensembles and in curriculum mode)
-    if (by_level) {
-      LearnLevelsArgs<T> g;
-      g.a = make_learn_args<T>(x, x->mdpk5, k);
-      g.lv = (const LevelSched DQL_CONST_AS*)x->d_lv; g.worklist = x->d_worklist; g.wave_level = (const int DQL_CONST_AS*)x->d_wave_level; g.n_waves = n_waves;
-      hipLaunchKernelGGL((k_learn_levels<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
-    } else {
-      hipLaunchKernelGGL((k_learn<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, make_learn_args<T>(x, x->mdpk, k));
+    switch (kern) {
+      case ENS_K_LEARN: launch_learn<T>(x, k, n_waves); break;
+      case ENS_K_TEAM: launch_learn_team<T>(x, k, n_waves); break;
+      case ENS_K_NSTEP: launch_learn_nstep<T>(x, k, n_waves); break;
+      case ENS_K_LEVELS: launch_learn_levels<T>(x, k, n_waves); break;
+      case ENS_K_RECIPES: launch_learn_recipes<T>(x, k, n_waves); break;
+      case ENS_K_RECIPES_NSTEP: launch_learn_recipes_nstep<T>(x, k, n_waves); break;
     }
   });
-  if (x->teams && !by_level) { rc = ens_launch_teams(x, k, n_waves); if (rc) return rc; }
-  else if (x->nstep && !by_level) { rc = ens_launch_nstep(x, k, n_waves); if (rc) return rc; }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += (long long)n_waves * k;
   return DQL_OK;
 }
+// every rate of a table in [0, 1], or the sentence
+static int ens_check_rates(const double* tab, int32_t n, const std::string& sentence) {
+  for (int i = 0; i < n; ++i) if (!(tab[i] >= 0.0 && tab[i] <= 1.0)) return fail(DQL_EINVAL, sentence);
+  return DQL_OK;
+}
+// host words in a new device table the ensemble owns
+template <typename D> static int ens_upload_table(dql_ensemble* x, const D* h, size_t n, D** d_out) {
+  if (x->dev.alloc((void**)d_out, n * sizeof(D)) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc failed");
+  if (hipMemcpy(*d_out, h, n * sizeof(D), hipMemcpyHostToDevice) != hipSuccess) { (void)x->dev.release(*d_out); *d_out = nullptr; return fail(DQL_EHIP, "hipMemcpy failed"); }
+  return DQL_OK;
+}
+// What the three schedule calls share: the promotion rule and the rate tables checked in the order dql_ensemble_set_schedules always had (it alone passes
+// learning rates), then (the device idle) the exploration rates as eps_threshold words in a new device table.  who: the call's name, the prefix of its
+// sentences; tail: their ending ("" or "; nothing was changed").
+static int ens_check_upload_rule(dql_ensemble* x, const std::string& who, const char* tail, const double* alpha, int32_t n_alpha, const double* eps, int32_t n_eps, int32_t window,
+                                 int32_t min_successes, int32_t max_episodes, uint32_t** d_eps) {
+  if (window < 1 || window > DQL_ENSEMBLE_MAX_WINDOW) return fail(DQL_EINVAL, who + ": the promotion window must be in 1..128 (DQL_ENSEMBLE_MAX_WINDOW)" + tail);
+  if (min_successes < 1 || max_episodes < 1) return fail(DQL_EINVAL, who + ": min_successes and max_episodes must be positive" + tail);
+  int rc = ens_check_rates(alpha, n_alpha, who + ": learning rates must be in [0, 1]" + tail); if (rc) return rc;
+  rc = ens_check_rates(eps, n_eps, who + ": exploration rates must be in [0, 1]" + tail); if (rc) return rc;
+  HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<uint32_t> thr((size_t)n_eps);
+  for (int i = 0; i < n_eps; ++i) thr[(size_t)i] = eps_threshold(eps[i]);
+  return ens_upload_table(x, thr.data(), thr.size(), d_eps);
+}
+// frozen, level and promoted of every learner -> host; the learners that are not finished for good
+static int ens_fetch_levels(dql_ensemble* x, std::vector<int>& frozen, std::vector<int>& level, std::vector<int>& promoted, int64_t* unfinished) {
+  const size_t n = (size_t)x->n;
+  int rc = ens_fetch(x->mem.frozen, n, frozen);
+  if (!rc) rc = ens_fetch(x->adv.level, n, level);
+  if (!rc) rc = ens_fetch(x->mem.promoted, n, promoted);
+  if (rc) return rc;
+  int64_t u = 0;
+  for (size_t l = 0; l < n; ++l) u += learner_finished(frozen[l], level[l], promoted[l], ens_rule_of(x, l)) ? 0 : 1;
+  *unfinished = u;
+  return DQL_OK;
+}
+// a learner on `level` has the schedules it will fly by: the level it stands on is flown whatever last_level says, then every level on its way up to last_level
+static bool ens_way_up_scheduled(const bool* have_lv, int level, int last_level) {
+  bool ok = level >= 0 && level < DQL_MAX_LEVELS && have_lv[level];
+  for (int k = level + 1; ok && k <= last_level && k < DQL_MAX_LEVELS; ++k) ok = have_lv[k];
+  return ok;
+}
+// The one advancing run loop: dql_ensemble_run in curriculum mode, with and without recipes.  The launches are cut at the multiples of advance_every; at such a
+// period index j, before period j is flown, every learner takes its advance step; each launch flies the live learners regrouped by the worklist.  What the two
+// modes differ in is passed in: complete(l, level) with the sentence that refuses the call where it fails, the advance kernel's launch, the worklist, the kernel.
+template <typename Complete, typename Advance>
+static int ens_run_advancing(dql_ensemble* x, int64_t periods, EnsKernel kern, EnsWorklist& wl, Complete complete, const char* incomplete, Advance launch_advance) {
+  std::vector<int> frozen, level, promoted;
+  int64_t unfinished = 0;
+  int rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
+  for (size_t l = 0; l < (size_t)x->n; ++l) if (!complete(l, level[l])) return fail(DQL_EINVAL, incomplete);
+  EvTimer timer;
+  rc = timer.start(); if (rc) return rc;
+  const long long E = x->advance_every;
+  long long left = periods;
+  while (left > 0) {
+    if (x->j % E == 0) {  // an advance point
+      launch_advance();
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipDeviceSynchronize());
+    }
+    rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
+    if (unfinished == 0) { x->j += left; break; }  // nothing left to fly or to advance, now or later (the period index still advances by `periods`)
+    const long long to_point = E - x->j % E;
+    const int k = (int)(left < to_point ? left : to_point);  // <= advance_every <= LEARN_MAX_PERIODS
+    unsigned long long wl_faults = 0ull;
+    const int n_waves = wl.build(frozen.data(), level.data(), x->n, &wl_faults);
+    rc = ens_add_faults(x, wl_faults); if (rc) return rc;
+    if (n_waves > 0) {  // (nobody live: everyone unfinished waits for the next advance point)
+      rc = wl.upload(n_waves); if (rc) return rc;
+      rc = ens_fly(x, kern, k, n_waves); if (rc) return rc;
+    }
+    x->j += k; left -= k;
+  }
+  return timer.stop_ms(&x->last_ms);
+}
+static int ens_run_levels(dql_ensemble* x, int64_t periods, EnsKernel kern) {
+  return ens_run_advancing(x, periods, kern, x->wl, [&](size_t, int level) { return ens_way_up_scheduled(x->have_lv, level, x->rule.last_level); },
+                           "dql_ensemble_run: curriculum mode needs dql_ensemble_set_level_schedules for every level from the learners' up to last_level; nothing was launched", [&] {
+                             hipLaunchKernelGGL(k_ens_advance, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->mem, x->adv, x->rule, x->si, (long long)x->j, (int)DQL_CELLS_PER_LEVEL);
+                           });
+}
 extern "C" {
-#define ENS_ALLOC(ptr, bytes) do { if (x->dev.alloc((void**)&(ptr), (bytes)) != hipSuccess) { ens_free(x); return fail(DQL_ENOMEM, "hipMalloc failed"); } \
-                                   if (hipMemset((ptr), 0, (bytes)) != hipSuccess) { ens_free(x); return fail(DQL_EHIP, "hipMemset failed"); } } while (0)
 // what dql_ensemble_create and dql_ensemble_create_teams (dql_teams.inc) share once their arguments are checked: n_learners learners with envs_per_learner envs each
 static int ens_create(const dql_config* cfg, int device, int64_t n_learners, int envs_per_learner, bool teams, uint64_t seed, int32_t log_capacity, dql_ensemble** out) {
   int rc = DQL_OK;
@@ -236,28 +402,22 @@ static int ens_create(const dql_config* cfg, int device, int64_t n_learners, int
   x->cfg = *cfg; x->device = device; x->n = n_learners; x->seed = seed;
   x->envs_per_learner = envs_per_learner; x->n_envs = n_learners * envs_per_learner; x->teams = teams;
   const size_t n = (size_t)n_learners, n_envs = (size_t)x->n_envs, mdpk_size = mdpk_bytes(cfg->dtype), real = by_dtype(cfg->dtype, [](auto t) { return sizeof(t); });
-  const size_t TB = n * DQL_N_CELLS * sizeof(double);
-  ENS_ALLOC(x->sr, (size_t)NQ_REAL * n_envs * 4 * real);
-  ENS_ALLOC(x->si, n_envs * sizeof(int4));
-  ENS_ALLOC(x->mdpk, mdpk_size);
-  ENS_ALLOC(x->mem.qa, TB); ENS_ALLOC(x->mem.qb, TB); ENS_ALLOC(x->mem.count, TB);
-  ENS_ALLOC(x->mem.decisions, n * sizeof(unsigned long long));
-  ENS_ALLOC(x->mem.by_code, (size_t)DQL_N_CHECK_CODES * n * sizeof(unsigned long long));
-  ENS_ALLOC(x->mem.episodes, n * sizeof(int)); ENS_ALLOC(x->mem.successes, n * sizeof(int));
-  ENS_ALLOC(x->mem.level_episodes, n * sizeof(int)); ENS_ALLOC(x->mem.win_count, n * sizeof(int));
-  ENS_ALLOC(x->mem.win_bits, 2 * n * sizeof(unsigned long long));
-  ENS_ALLOC(x->mem.promoted, n * sizeof(int)); ENS_ALLOC(x->mem.frozen, n * sizeof(int));
-  ENS_ALLOC(x->mem.log_code, n * (size_t)(log_capacity ? log_capacity : 1)); ENS_ALLOC(x->mem.log_len, n * (size_t)(log_capacity ? log_capacity : 1) * sizeof(uint16_t));
-  ENS_ALLOC(x->mem.log_n, n * sizeof(int));
-  ENS_ALLOC(x->mem.faults, sizeof(unsigned long long));
-  ENS_ALLOC(x->d_mgr0, (size_t)LEARN_MAX_PERIODS * sizeof(long long)); ENS_ALLOC(x->d_sched, (size_t)LEARN_MAX_PERIODS * sizeof(int));
-  ENS_ALLOC(x->adv.level, n * sizeof(int));
-  ENS_ALLOC(x->adv.promoted_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int)); ENS_ALLOC(x->adv.episodes_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int));
-  ENS_ALLOC(x->adv.entered_period, (size_t)DQL_MAX_LEVELS * n * sizeof(long long));
-  ENS_ALLOC(x->mdpk5, (size_t)DQL_MAX_LEVELS * mdpk_size);
-  ENS_ALLOC(x->d_lv, (size_t)DQL_MAX_LEVELS * sizeof(LevelSched));
-  x->wl_slots = worklist_capacity(n_learners);
-  ENS_ALLOC(x->d_worklist, (size_t)x->wl_slots * sizeof(int)); ENS_ALLOC(x->d_wave_level, (size_t)(x->wl_slots / ADV_WAVE) * sizeof(int));
+  const size_t TB = n * DQL_N_CELLS * sizeof(double), I = n * sizeof(int), U = n * sizeof(unsigned long long), LOG = n * (size_t)(log_capacity ? log_capacity : 1);
+  const size_t H = (size_t)DQL_MAX_LEVELS * n;  // the per-level history
+  LearnMem& m = x->mem; AdvanceMem& a = x->adv;
+  x->wl.resize(worklist_capacity(n_learners));
+  const size_t waves = (size_t)(x->wl.slots / ADV_WAVE);
+  rc = ens_alloc_zeroed(x->dev, {
+      {&x->sr, (size_t)NQ_REAL * n_envs * 4 * real}, {(void**)&x->si, n_envs * sizeof(int4)}, {&x->mdpk, mdpk_size},
+      {(void**)&m.qa, TB}, {(void**)&m.qb, TB}, {(void**)&m.count, TB}, {(void**)&m.decisions, U}, {(void**)&m.by_code, (size_t)DQL_N_CHECK_CODES * U},
+      {(void**)&m.episodes, I}, {(void**)&m.successes, I}, {(void**)&m.level_episodes, I}, {(void**)&m.win_count, I}, {(void**)&m.win_bits, 2 * U},
+      {(void**)&m.promoted, I}, {(void**)&m.frozen, I}, {(void**)&m.log_code, LOG}, {(void**)&m.log_len, LOG * sizeof(uint16_t)}, {(void**)&m.log_n, I},
+      {(void**)&m.faults, sizeof(unsigned long long)},
+      {(void**)&x->d_mgr0, (size_t)LEARN_MAX_PERIODS * sizeof(long long)}, {(void**)&x->d_sched, (size_t)LEARN_MAX_PERIODS * sizeof(int)},
+      {(void**)&a.level, I}, {(void**)&a.promoted_at, H * sizeof(int)}, {(void**)&a.episodes_at, H * sizeof(int)}, {(void**)&a.entered_period, H * sizeof(long long)},
+      {&x->mdpk5, (size_t)DQL_MAX_LEVELS * mdpk_size}, {(void**)&x->d_lv, (size_t)DQL_MAX_LEVELS * sizeof(LevelSched)},
+      {(void**)&x->wl.d_list, (size_t)x->wl.slots * sizeof(int)}, {(void**)&x->wl.d_wave_level, waves * sizeof(int)}});
+  if (rc) { ens_free(x); return fail(rc, rc == DQL_ENOMEM ? "hipMalloc failed" : "hipMemset failed"); }
   x->mem.n = n_learners; x->mem.log_cap = log_capacity;
   rc = upload_mdpk(x->cfg, x->mdpk);
   if (!rc) rc = ens_upload_mdpk5(x);
@@ -295,37 +455,14 @@ int dql_ensemble_n_learners(dql_ensemble* x, int64_t* n) {
   *n = x->n;
   return DQL_OK;
 }
-// the checks and the exploration-table upload dql_ensemble_set_schedules and dql_ensemble_set_level_schedules share (who: the call's name, the prefix of its error texts)
-static int ens_check_promotion(const std::string& who, int32_t window, int32_t min_successes, int32_t max_episodes) {
-  if (window < 1 || window > DQL_ENSEMBLE_MAX_WINDOW) return fail(DQL_EINVAL, who + ": the promotion window must be in 1..128 (DQL_ENSEMBLE_MAX_WINDOW)");
-  if (min_successes < 1 || max_episodes < 1) return fail(DQL_EINVAL, who + ": min_successes and max_episodes must be positive");
-  return DQL_OK;
-}
-// range check, then (the device idle) the rates as eps_threshold words in a new device table the ensemble owns
-static int ens_upload_eps(dql_ensemble* x, const std::string& who, const double* eps, int32_t n_eps, uint32_t** d_out) {
-  for (int i = 0; i < n_eps; ++i) if (!(eps[i] >= 0.0 && eps[i] <= 1.0)) return fail(DQL_EINVAL, who + ": exploration rates must be in [0, 1]");
-  HIP_TRY(hipSetDevice(x->device));
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<uint32_t> thr((size_t)n_eps);
-  for (int i = 0; i < n_eps; ++i) thr[(size_t)i] = eps_threshold(eps[i]);
-  if (x->dev.alloc((void**)d_out, (size_t)n_eps * sizeof(uint32_t)) != hipSuccess) return fail(DQL_ENOMEM, "hipMalloc failed");
-  if (hipMemcpy(*d_out, thr.data(), (size_t)n_eps * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) { (void)x->dev.release(*d_out); return fail(DQL_EHIP, "hipMemcpy failed"); }
-  return DQL_OK;
-}
 int dql_ensemble_set_schedules(dql_ensemble* x, const double* alpha, int32_t n_alpha, const double* eps, int32_t n_eps, int32_t window, int32_t min_successes,
                                int32_t max_episodes) {
   CHECK_ENS(x);
   if (!alpha || !eps) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: null table");
   if (n_alpha < 1 || n_alpha > (1 << 22) || n_eps < 1 || n_eps > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: table lengths must be in 1..2^22");
-  int rc = ens_check_promotion("dql_ensemble_set_schedules", window, min_successes, max_episodes); if (rc) return rc;
-  for (int i = 0; i < n_alpha; ++i) if (!(alpha[i] >= 0.0 && alpha[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_schedules: learning rates must be in [0, 1]");
   double* d_a = nullptr; uint32_t* d_e = nullptr;
-  rc = ens_upload_eps(x, "dql_ensemble_set_schedules", eps, n_eps, &d_e); if (rc) return rc;
-  if (x->dev.alloc((void**)&d_a, (size_t)n_alpha * sizeof(double)) != hipSuccess) { (void)x->dev.release(d_e); return fail(DQL_ENOMEM, "hipMalloc failed"); }
-  if (hipMemcpy(d_a, alpha, (size_t)n_alpha * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)x->dev.release(d_a); (void)x->dev.release(d_e);
-    return fail(DQL_EHIP, "hipMemcpy failed");
-  }
+  int rc = ens_check_upload_rule(x, "dql_ensemble_set_schedules", "", alpha, n_alpha, eps, n_eps, window, min_successes, max_episodes, &d_e); if (rc) return rc;
+  rc = ens_upload_table(x, alpha, (size_t)n_alpha, &d_a); if (rc) { (void)x->dev.release(d_e); return rc; }
   (void)x->dev.release(x->alpha_tab); (void)x->dev.release(x->eps_tab);  // the tables they replace
   x->alpha_tab = d_a; x->eps_tab = d_e;
   x->sched = LearnSched{d_a, n_alpha, x->cfg.alpha_min, d_e, n_eps, window, min_successes, max_episodes};
@@ -359,75 +496,20 @@ int dql_ensemble_n_live(dql_ensemble* x, int64_t* n_live) {
   CHECK_ENS(x);
   if (!n_live) return fail(DQL_EINVAL, "null pointer");
   HIP_TRY(hipSetDevice(x->device));
-  std::vector<int> h((size_t)x->n);
-  HIP_TRY(hipMemcpy(h.data(), x->mem.frozen, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> h;
+  const int rc = ens_fetch(x->mem.frozen, (size_t)x->n, h); if (rc) return rc;
   int64_t live = 0;
   for (int v : h) live += v ? 0 : 1;
   *n_live = live;
   return DQL_OK;
 }
-// frozen, level and promoted of every learner -> host; the learners that are not finished for good
-static int ens_fetch_levels(dql_ensemble* x, std::vector<int>& frozen, std::vector<int>& level, std::vector<int>& promoted, int64_t* unfinished) {
-  const size_t n = (size_t)x->n;
-  frozen.resize(n); level.resize(n); promoted.resize(n);
-  HIP_TRY(hipMemcpy(frozen.data(), x->mem.frozen, n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(level.data(), x->adv.level, n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(promoted.data(), x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
-  int64_t u = 0;
-  for (size_t l = 0; l < n; ++l) u += learner_finished(frozen[l], level[l], promoted[l], ens_rule_of(x, l)) ? 0 : 1;
-  *unfinished = u;
-  return DQL_OK;
-}
-// dql_ensemble_run in curriculum mode: the launches are cut at the multiples of advance_every; at such a period index j, before period j is flown, every
-// learner takes advance_learner's step; each launch flies the live learners regrouped by level (build_worklist)
-static int ens_run_levels(dql_ensemble* x, int64_t periods) {
-  std::vector<int> frozen, level, promoted;
-  int64_t unfinished = 0;
-  int rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
-  // the level a learner stands on is flown whatever last_level says, so its schedule is asked for first; then every level on its way up to last_level
-  for (size_t l = 0; l < (size_t)x->n; ++l) {
-    bool ok = level[l] >= 0 && level[l] < DQL_MAX_LEVELS && x->have_lv[level[l]];
-    for (int k = level[l] + 1; ok && k <= x->rule.last_level && k < DQL_MAX_LEVELS; ++k) ok = x->have_lv[k];
-    if (!ok) return fail(DQL_EINVAL, "dql_ensemble_run: curriculum mode needs dql_ensemble_set_level_schedules for every level from the learners' up to last_level; nothing was launched");
-  }
-  EvTimer timer;
-  rc = timer.start(); if (rc) return rc;
-  std::vector<int> worklist((size_t)x->wl_slots), wave_level((size_t)(x->wl_slots / ADV_WAVE));
-  const long long E = x->advance_every;
-  long long left = periods;
-  while (left > 0) {
-    if (x->j % E == 0) {  // an advance point
-      hipLaunchKernelGGL(k_ens_advance, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->mem, x->adv, x->rule, x->si, (long long)x->j, (int)DQL_CELLS_PER_LEVEL);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipDeviceSynchronize());
-    }
-    rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
-    if (unfinished == 0) { x->j += left; break; }  // nothing left to fly or to advance, now or later (the period index still advances by `periods`)
-    const long long to_point = E - x->j % E;
-    const int k = (int)(left < to_point ? left : to_point);  // <= advance_every <= LEARN_MAX_PERIODS
-    unsigned long long wl_faults = 0ull;
-    const int n_waves = build_worklist(frozen.data(), level.data(), x->n, worklist.data(), wave_level.data(), x->wl_slots, &wl_faults);
-    if (wl_faults) {
-      unsigned long long v = 0;
-      HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
-      v += wl_faults;
-      HIP_TRY(hipMemcpy(x->mem.faults, &v, sizeof(v), hipMemcpyHostToDevice));
-    }
-    if (n_waves > 0) {  // (nobody live: everyone unfinished waits for the next advance point)
-      HIP_TRY(hipMemcpy(x->d_worklist, worklist.data(), (size_t)n_waves * ADV_WAVE * sizeof(int), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(x->d_wave_level, wave_level.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
-      rc = ens_fly(x, k, n_waves, true); if (rc) return rc;
-    }
-    x->j += k; left -= k;
-  }
-  return timer.stop_ms(&x->last_ms);
-}
 int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
   CHECK_ENS(x);
   if (periods < 1 || periods > (1ll << 40)) return fail(DQL_EINVAL, "dql_ensemble_run: periods must be in 1..2^40; nothing was launched");
   HIP_TRY(hipSetDevice(x->device));
-  if (x->rcp) return ens_run_recipes(x, periods);
-  if (x->advance_every) return ens_run_levels(x, periods);
+  const EnsKernel kern = ens_kernel_of(x, x->rcp || x->advance_every);
+  if (x->rcp) return ens_run_recipes(x, periods, kern);
+  if (x->advance_every) return ens_run_levels(x, periods, kern);
   int rc = DQL_OK;
   EvTimer timer;
   rc = timer.start(); if (rc) return rc;
@@ -439,7 +521,7 @@ int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
       rc = dql_ensemble_n_live(x, &live); if (rc) return rc;
       if (live == 0) { x->j += left; break; }
     }
-    rc = ens_fly(x, k, (int)((x->n_envs + 63) / 64), false); if (rc) return rc;
+    rc = ens_fly(x, kern, k, (int)((x->n_envs + 63) / 64)); if (rc) return rc;
     x->j += k; left -= k;
   }
   return timer.stop_ms(&x->last_ms);
@@ -456,8 +538,8 @@ int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t adv
     if (x->advance_every) {
       HIP_TRY(hipSetDevice(x->device));
       HIP_TRY(hipDeviceSynchronize());
-      std::vector<int> lv((size_t)x->n);
-      HIP_TRY(hipMemcpy(lv.data(), x->adv.level, lv.size() * sizeof(int), hipMemcpyDeviceToHost));
+      std::vector<int> lv;
+      const int rc = ens_fetch(x->adv.level, (size_t)x->n, lv); if (rc) return rc;
       for (int v : lv)
         if (v != x->cfg.working_curriculum_step)
           return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the mode cannot be switched off (advance_every = 0) while learners stand on different levels; call dql_ensemble_set_level first; nothing was changed");
@@ -471,12 +553,12 @@ int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t adv
   if (advance_exhausted != 0 && advance_exhausted != 1) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_exhausted must be 0 or 1; nothing was changed");
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipDeviceSynchronize());
-  std::vector<int> level((size_t)x->n);
-  HIP_TRY(hipMemcpy(level.data(), x->adv.level, level.size() * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> level;
+  int rc = ens_fetch(x->adv.level, (size_t)x->n, level); if (rc) return rc;
   int top = 0;
   for (int v : level) top = v > top ? v : top;
   if (last_level < top || last_level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: last_level must lie between the learners' current level and 4; nothing was changed");
-  int rc = ens_upload_mdpk5(x); if (rc) return rc;
+  rc = ens_upload_mdpk5(x); if (rc) return rc;
   for (int k = 0; k < DQL_MAX_LEVELS; ++k) x->rule.ratios[k] = ratios[k];
   x->rule.last_level = last_level; x->rule.advance_exhausted = advance_exhausted;
   x->advance_every = advance_every;
@@ -487,9 +569,8 @@ int dql_ensemble_set_level_schedules(dql_ensemble* x, int32_t level, const doubl
   if (level < 0 || level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: the level must be in 0..4");
   if (!eps) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: null table");
   if (n_eps < 1 || n_eps > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_level_schedules: the table length must be in 1..2^22");
-  int rc = ens_check_promotion("dql_ensemble_set_level_schedules", window, min_successes, max_episodes); if (rc) return rc;
   uint32_t* d_e = nullptr;
-  rc = ens_upload_eps(x, "dql_ensemble_set_level_schedules", eps, n_eps, &d_e); if (rc) return rc;
+  const int rc = ens_check_upload_rule(x, "dql_ensemble_set_level_schedules", "", nullptr, 0, eps, n_eps, window, min_successes, max_episodes, &d_e); if (rc) return rc;
   LevelSched lv[DQL_MAX_LEVELS];
   for (int k = 0; k < DQL_MAX_LEVELS; ++k) lv[k] = x->h_lv[k];
   lv[level] = LevelSched{d_e, n_eps, window, min_successes, max_episodes};
@@ -508,9 +589,10 @@ int dql_ensemble_get_levels(dql_ensemble* x, int32_t* level, int32_t* promoted_a
   HIP_TRY(hipMemcpy(episodes_at, x->adv.episodes_at, (size_t)DQL_MAX_LEVELS * n * sizeof(int), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(entered_period, x->adv.entered_period, (size_t)DQL_MAX_LEVELS * n * sizeof(long long), hipMemcpyDeviceToHost));
   // the level a learner stands on has no history entry yet: its row shows the counters as they are
-  std::vector<int> promoted(n), lvl_eps(n);
-  HIP_TRY(hipMemcpy(promoted.data(), x->mem.promoted, n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(lvl_eps.data(), x->mem.level_episodes, n * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> promoted, lvl_eps;
+  int rc = ens_fetch(x->mem.promoted, n, promoted);
+  if (!rc) rc = ens_fetch(x->mem.level_episodes, n, lvl_eps);
+  if (rc) return rc;
   for (size_t l = 0; l < n; ++l) {
     const int k = level[l];
     if (k < 0 || k >= DQL_MAX_LEVELS) continue;

@@ -1,6 +1,6 @@
 // dql_nstep.inc: sequential learners with n-step Double-Q targets (include/dql.h dql_ensemble_set_nstep / _get_nstep, DESIGN.md section 22): the lane kernel
 // and the two C calls.  A fragment of dql_hip.hip's translation unit, not a header, included after dql_ensemble.inc, whose struct dql_ensemble, LearnArgs,
-// make_learn_args and ens_fly it works with; dql_nstep.hpp holds the per-lane body.
+// make_learn_args and shared host helpers it works with (ens_fly launches the kernel through launch_learn_nstep below); dql_nstep.hpp holds the per-lane body.
 // k_learn's shape: one learner per lane, workgroups of one wave, the env in registers for all periods of the launch, the tables the lane's own slices.  The
 // pending windows live in LDS for the launch, [slot][lane]: 16 x 64 x (2 + 8) B = 10 KB per wave whatever n is; a lane reads and writes its own column only,
 // so no barrier is needed.  learner_periods_nstep loads them from the ensemble's arrays at its start and stores them back beside store_env.
@@ -42,17 +42,12 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
                                      g.nstep, LdsWindow{sKey + tid, sVal + tid}, g.nm);
 }
 
-static int ens_launch_nstep(dql_ensemble* x, int k, int n_waves) {
-  if (!x->ns_key || !x->ns_val || !x->ns_len) return fail(DQL_ESTATE, "dql_ensemble_run: n-step targets are on but the pending windows were never allocated; nothing was launched");
-  by_dtype(x->cfg.dtype, [&](auto t) {
-    using T = decltype(t);
-    NstepArgs<T> g;
-    g.a = make_learn_args<T>(x, x->mdpk, k);
-    g.nm = NstepDev{x->ns_key, x->ns_val, x->ns_len};
-    g.nstep = x->nstep;
-    hipLaunchKernelGGL((k_learn_nstep<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
-  });
-  return DQL_OK;
+template <typename T> static void launch_learn_nstep(dql_ensemble* x, int k, int n_waves) {
+  NstepArgs<T> g;
+  g.a = make_learn_args<T>(x, x->mdpk, k);
+  g.nm = NstepDev{x->ns_key, x->ns_val, x->ns_len};
+  g.nstep = x->nstep;
+  hipLaunchKernelGGL((k_learn_nstep<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
 }
 
 // the persistent windows, zeroed, on the first call (dql_ensemble_set_nstep and dql_ensemble_set_recipe_nstep with n >= 1); later calls change nothing
@@ -60,12 +55,8 @@ static int ens_alloc_windows(dql_ensemble* x) {
   if (x->ns_len) return DQL_OK;
   const size_t L = (size_t)x->n;
   uint16_t* key = nullptr; double* val = nullptr; int* len = nullptr;
-  bool ok = x->dev.alloc((void**)&key, (size_t)DQL_NSTEP_MAX * L * sizeof(uint16_t)) == hipSuccess && x->dev.alloc((void**)&val, (size_t)DQL_NSTEP_MAX * L * sizeof(double)) == hipSuccess &&
-            x->dev.alloc((void**)&len, L * sizeof(int)) == hipSuccess;
-  if (!ok) { (void)x->dev.release(key); (void)x->dev.release(val); (void)x->dev.release(len); return fail(DQL_ENOMEM, "hipMalloc failed"); }
-  ok = hipMemset(key, 0, (size_t)DQL_NSTEP_MAX * L * sizeof(uint16_t)) == hipSuccess && hipMemset(val, 0, (size_t)DQL_NSTEP_MAX * L * sizeof(double)) == hipSuccess &&
-       hipMemset(len, 0, L * sizeof(int)) == hipSuccess;
-  if (!ok) { (void)x->dev.release(key); (void)x->dev.release(val); (void)x->dev.release(len); return fail(DQL_EHIP, "hipMemset failed"); }
+  const int rc = ens_alloc_zeroed(x->dev, {{(void**)&key, (size_t)DQL_NSTEP_MAX * L * sizeof(uint16_t)}, {(void**)&val, (size_t)DQL_NSTEP_MAX * L * sizeof(double)}, {(void**)&len, L * sizeof(int)}});
+  if (rc) return fail(rc, rc == DQL_ENOMEM ? "hipMalloc failed" : "hipMemset failed");
   x->ns_key = key; x->ns_val = val; x->ns_len = len;
   return DQL_OK;
 }
@@ -81,15 +72,9 @@ int dql_ensemble_set_nstep(dql_ensemble* x, int32_t n) {
   if (n == x->nstep) return DQL_OK;
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipDeviceSynchronize());
-  const size_t L = (size_t)x->n;
-  if (x->ns_len) {
-    std::vector<int> len(L);
-    HIP_TRY(hipMemcpy(len.data(), x->ns_len, L * sizeof(int), hipMemcpyDeviceToHost));
-    for (int v : len)
-      if (v != 0)
-        return fail(DQL_ESTATE, "dql_ensemble_set_nstep: n cannot change while a learner's pending window holds entries (change it after creation, after dql_ensemble_set_level, or when every learner is frozen); nothing was changed");
-  }
-  if (n >= 1) { const int rc = ens_alloc_windows(x); if (rc) return rc; }
+  int rc = ens_windows_empty(x, [](size_t) { return true; }, "dql_ensemble_set_nstep: n cannot change while a learner's pending window holds entries (change it after creation, after dql_ensemble_set_level, or when every learner is frozen); nothing was changed");
+  if (rc) return rc;
+  if (n >= 1) { rc = ens_alloc_windows(x); if (rc) return rc; }
   x->nstep = n;
   return DQL_OK;
 }

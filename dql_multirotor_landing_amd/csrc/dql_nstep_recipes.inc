@@ -1,5 +1,5 @@
 // dql_nstep_recipes.inc: n-step Double-Q targets as a property of a recipe (include/dql.h dql_ensemble_set_recipe_nstep / _get_recipe_nstep, DESIGN.md
-// section 23): the kernel that flies a (recipe, level) worklist with either lane body, its launch, and the two C calls.  A fragment of dql_hip.hip's
+// section 23): the kernel that flies a (recipe, level) worklist with either lane body, its argument filler, and the two C calls.  A fragment of dql_hip.hip's
 // translation unit, included after dql_recipes.inc (EnsRecipes, LearnRecipesArgs, CHECK_RECIPE) and dql_nstep.inc (LdsWindow, NstepDev, ens_alloc_windows).
 
 // k_learn_recipes' shape and prologue with k_learn_nstep's LDS windows: wave w flies worklist[64 w .. 64 w + 63] of recipe wave_recipe[w] on level
@@ -64,24 +64,13 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   }
 }
 
-// ens_fly_recipes' sibling: the same launch with the windows and the recipes' n
-static int ens_fly_recipes_nstep(dql_ensemble* x, int k, int n_waves) {
-  EnsRecipes* q = x->rcp;
-  if (!x->ns_key || !x->ns_val || !x->ns_len || !q->d_nstep)
-    return fail(DQL_ESTATE, "dql_ensemble_run: a recipe has n-step targets but the pending windows were never allocated; nothing was launched");
-  int rc = upload_schedule(x->cfg, x->j, k, x->d_mgr0, x->d_sched); if (rc) return rc;
-  by_dtype(x->cfg.dtype, [&](auto t) {
-    using T = decltype(t);
-    LearnRecipesNstepArgs<T> h;
-    h.g = make_learn_recipes_args<T>(x, k, n_waves);
-    h.nm = NstepDev{x->ns_key, x->ns_val, x->ns_len};
-    h.recipe_nstep = (const int DQL_CONST_AS*)q->d_nstep;
-    hipLaunchKernelGGL((k_learn_recipes_nstep<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, h);
-  });
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += (long long)n_waves * k;
-  return DQL_OK;
+// launch_learn_recipes' sibling: the same arguments with the windows and the recipes' n
+template <typename T> static void launch_learn_recipes_nstep(dql_ensemble* x, int k, int n_waves) {
+  LearnRecipesNstepArgs<T> h;
+  h.g = make_learn_recipes_args<T>(x, k, n_waves);
+  h.nm = NstepDev{x->ns_key, x->ns_val, x->ns_len};
+  h.recipe_nstep = (const int DQL_CONST_AS*)x->rcp->d_nstep;
+  hipLaunchKernelGGL((k_learn_recipes_nstep<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, h);
 }
 
 extern "C" {
@@ -92,15 +81,9 @@ int dql_ensemble_set_recipe_nstep(dql_ensemble* x, int32_t r, int32_t n) {
   if (n == q->nstep[r]) return DQL_OK;
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipDeviceSynchronize());
-  const size_t L = (size_t)x->n;
-  if (x->ns_len) {
-    std::vector<int> len(L);
-    HIP_TRY(hipMemcpy(len.data(), x->ns_len, L * sizeof(int), hipMemcpyDeviceToHost));
-    for (size_t l = 0; l < L; ++l)
-      if (q->recipe_of[l] == r && len[l] != 0)
-        return fail(DQL_ESTATE, "dql_ensemble_set_recipe_nstep: a recipe's n cannot change while a member's pending window holds entries (change it after dql_ensemble_set_recipes, after dql_ensemble_set_level, or when every member is frozen); nothing was changed");
-  }
-  if (n >= 1) { const int rc = ens_alloc_windows(x); if (rc) return rc; }
+  int rc = ens_windows_empty(x, [&](size_t l) { return q->recipe_of[l] == r; }, "dql_ensemble_set_recipe_nstep: a recipe's n cannot change while a member's pending window holds entries (change it after dql_ensemble_set_recipes, after dql_ensemble_set_level, or when every member is frozen); nothing was changed");
+  if (rc) return rc;
+  if (n >= 1) { rc = ens_alloc_windows(x); if (rc) return rc; }
   int* d = q->d_nstep;
   if (!d) {  // [n_recipes], zeros until set
     if (x->dev.alloc((void**)&d, (size_t)q->n * sizeof(int)) != hipSuccess) return fail(DQL_ENOMEM, "dql_ensemble_set_recipe_nstep: hipMalloc failed; nothing was changed");

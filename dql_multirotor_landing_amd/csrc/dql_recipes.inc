@@ -1,7 +1,7 @@
 // dql_recipes.inc: per-learner recipes for the ensembles of sequential learners (include/dql.h dql_ensemble_set_recipes ..., DESIGN.md section 16): the two
-// kernels, struct EnsRecipes (what an ensemble holds while recipes are installed), dql_ensemble_run's launch loop for it, and the C calls.  A fragment of
-// dql_hip.hip's translation unit, included after dql_ensemble.inc, whose struct dql_ensemble, ens_fly's helpers (make_learn_args, upload_schedule),
-// ens_check_promotion and ens_upload_eps it uses; csrc/dql_recipes.hpp holds the recipe structs, the worklist and the advance step.
+// kernels, struct EnsRecipes (what an ensemble holds while recipes are installed), what dql_ensemble_run passes to the advancing run loop for it, and the C calls.
+// A fragment of dql_hip.hip's translation unit, included after dql_ensemble.inc, whose struct dql_ensemble, EnsWorklist, make_learn_args, ens_run_advancing and
+// shared host helpers (ens_alloc_zeroed, ens_windows_empty, ens_check_upload_rule ...) it uses; csrc/dql_recipes.hpp holds the recipe structs, the worklist and the advance step.
 
 // k_learn_levels with one more scalar load: wave w flies the learners worklist[64 w .. 64 w + 63] (-1: an inactive lane), all of them of recipe
 // wave_recipe[w] on level wave_level[w].  From the recipe follow SimK::quirks, the learning rates and the level's exploration table and freeze rules; from
@@ -64,13 +64,11 @@ struct EnsRecipes {
   RecipeRule rule[RCP_MAX]{}; bool have_rule[RCP_MAX]{};
   RecipeSched sched[RCP_MAX]{}; bool have_lv[RCP_MAX][DQL_MAX_LEVELS]{};   // (the tables its pointers name are the ensemble's device allocations)
   int* d_recipe_of = nullptr; RecipeRule* d_rule = nullptr; RecipeSched* d_sched = nullptr; void* d_mdpk = nullptr;  // [L], [n], [n], [n][DQL_MAX_LEVELS] MdpK<T>
-  int* d_worklist = nullptr; int* d_wave_recipe = nullptr; int* d_wave_level = nullptr; long long wl_slots = 0;
+  EnsWorklist wl;                                   // by (recipe, level) (capacity: worklist_capacity_recipes)
   // per-recipe n-step targets (DESIGN.md section 23, dql_nstep_recipes.inc): the capacity of the members' pending windows, 0: the one-step update; the device
   // copy [n] is made by the first dql_ensemble_set_recipe_nstep that changes an n and read by k_learn_recipes_nstep alone
   int nstep[RCP_MAX]{}; int* d_nstep = nullptr;
 };
-// of dql_nstep_recipes.inc: ens_fly_recipes with k_learn_recipes_nstep (flown while a recipe that has a member has n >= 1)
-static int ens_fly_recipes_nstep(dql_ensemble* x, int k, int n_waves);
 static void ens_recipes_release(dql_ensemble* x) {
   EnsRecipes* q = x->rcp;
   if (!q) return;
@@ -78,7 +76,7 @@ static void ens_recipes_release(dql_ensemble* x) {
     (void)x->dev.release((void*)q->sched[r].alpha_tab);
     for (int k = 0; k < DQL_MAX_LEVELS; ++k) (void)x->dev.release((void*)q->sched[r].lv[k].eps_tab);
   }
-  void* own[] = {q->d_recipe_of, q->d_rule, q->d_sched, q->d_mdpk, q->d_worklist, q->d_wave_recipe, q->d_wave_level, q->d_nstep};
+  void* own[] = {q->d_recipe_of, q->d_rule, q->d_sched, q->d_mdpk, q->wl.d_list, q->wl.d_wave_recipe, q->wl.d_wave_level, q->d_nstep};
   for (void* p : own) (void)x->dev.release(p);
   delete q;
   x->rcp = nullptr;
@@ -96,85 +94,35 @@ template <typename T> static LearnRecipesArgs<T> make_learn_recipes_args(dql_ens
   EnsRecipes* q = x->rcp;
   LearnRecipesArgs<T> g;
   g.a = make_learn_args<T>(x, q->d_mdpk, k);
-  g.rs = (const RecipeSched DQL_CONST_AS*)q->d_sched; g.worklist = q->d_worklist;
-  g.wave_recipe = (const int DQL_CONST_AS*)q->d_wave_recipe; g.wave_level = (const int DQL_CONST_AS*)q->d_wave_level;
+  g.rs = (const RecipeSched DQL_CONST_AS*)q->d_sched; g.worklist = q->wl.d_list;
+  g.wave_recipe = (const int DQL_CONST_AS*)q->wl.d_wave_recipe; g.wave_level = (const int DQL_CONST_AS*)q->wl.d_wave_level;
   g.n_waves = n_waves; g.n_recipes = q->n;
   return g;
 }
-// ens_fly's recipe launch: k periods from period x->j on n_waves waves of one (recipe, level) each
-static int ens_fly_recipes(dql_ensemble* x, int k, int n_waves) {
-  int rc = upload_schedule(x->cfg, x->j, k, x->d_mgr0, x->d_sched); if (rc) return rc;
-  by_dtype(x->cfg.dtype, [&](auto t) {
-    using T = decltype(t);
-    hipLaunchKernelGGL((k_learn_recipes<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, make_learn_recipes_args<T>(x, k, n_waves));
-  });
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  x->n_launches += 1; x->launched_periods += k; x->launched_wave_periods += (long long)n_waves * k;
-  return DQL_OK;
+template <typename T> static void launch_learn_recipes(dql_ensemble* x, int k, int n_waves) {
+  hipLaunchKernelGGL((k_learn_recipes<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, make_learn_recipes_args<T>(x, k, n_waves));
 }
-// ens_run_levels with the recipe-aware learner_finished (ens_fetch_levels reads each learner's own rule), worklist and kernels
-static int ens_run_recipes(dql_ensemble* x, int64_t periods) {
+static bool ens_recipes_any_nstep(const dql_ensemble* x) {  // a recipe that has a member has n >= 1
+  for (int r : x->rcp->recipe_of) if (x->rcp->nstep[r] >= 1) return true;
+  return false;
+}
+static const int* ens_recipes_nstep_table(const dql_ensemble* x) { return x->rcp->d_nstep; }
+// the advancing run loop with the recipe-aware learner_finished (ens_fetch_levels reads each learner's own rule), worklist and kernels.  Complete: every recipe
+// with a member has its rule, and schedules for the level each member stands on and every level on its way up to last_level
+static int ens_run_recipes(dql_ensemble* x, int64_t periods, EnsKernel kern) {
   EnsRecipes* q = x->rcp;
-  std::vector<int> frozen, level, promoted;
-  int64_t unfinished = 0;
-  int rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
-  // every recipe with a member is complete: its rule is set, and it has schedules for the level each member stands on and every level on its way up to last_level
-  for (size_t l = 0; l < (size_t)x->n; ++l) {
-    const int r = q->recipe_of[l];
-    bool ok = q->have_rule[r] && level[l] >= 0 && level[l] < DQL_MAX_LEVELS && q->have_lv[r][level[l]];
-    for (int k = level[l] + 1; ok && k <= q->rule[r].rule.last_level && k < DQL_MAX_LEVELS; ++k) ok = q->have_lv[r][k];
-    if (!ok)
-      return fail(DQL_EINVAL, "dql_ensemble_run: with recipes installed every recipe that has a member needs dql_ensemble_set_recipe and dql_ensemble_set_recipe_level_schedules for every "
-                              "level from its members' up to its last_level; nothing was launched");
-  }
-  bool nstep_kernel = false;  // a recipe that has a member has n >= 1: every launch of this call is k_learn_recipes_nstep's
-  for (int r : q->recipe_of) nstep_kernel = nstep_kernel || q->nstep[r] >= 1;
-  EvTimer timer;
-  rc = timer.start(); if (rc) return rc;
-  std::vector<int> worklist((size_t)q->wl_slots), wave_recipe((size_t)(q->wl_slots / ADV_WAVE)), wave_level((size_t)(q->wl_slots / ADV_WAVE));
-  const long long E = x->advance_every;
-  long long left = periods;
-  while (left > 0) {
-    if (x->j % E == 0) {  // an advance point
-      hipLaunchKernelGGL(k_ens_advance_recipes, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->mem, x->adv, (const RecipeRule*)q->d_rule, q->n, (const int*)q->d_recipe_of, x->si,
-                         (long long)x->j, (int)DQL_CELLS_PER_LEVEL);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipDeviceSynchronize());
-    }
-    rc = ens_fetch_levels(x, frozen, level, promoted, &unfinished); if (rc) return rc;
-    if (unfinished == 0) { x->j += left; break; }  // nothing left to fly or to advance, now or later (the period index still advances by `periods`)
-    const long long to_point = E - x->j % E;
-    const int k = (int)(left < to_point ? left : to_point);  // <= advance_every <= LEARN_MAX_PERIODS
-    unsigned long long wl_faults = 0ull;
-    const int n_waves = build_worklist_recipes(frozen.data(), level.data(), q->recipe_of.data(), x->n, q->n, worklist.data(), wave_recipe.data(), wave_level.data(), q->wl_slots, &wl_faults);
-    if (wl_faults) {
-      unsigned long long v = 0;
-      HIP_TRY(hipMemcpy(&v, x->mem.faults, sizeof(v), hipMemcpyDeviceToHost));
-      v += wl_faults;
-      HIP_TRY(hipMemcpy(x->mem.faults, &v, sizeof(v), hipMemcpyHostToDevice));
-    }
-    if (n_waves > 0) {  // (nobody live: everyone unfinished waits for the next advance point)
-      HIP_TRY(hipMemcpy(q->d_worklist, worklist.data(), (size_t)n_waves * ADV_WAVE * sizeof(int), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(q->d_wave_recipe, wave_recipe.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(q->d_wave_level, wave_level.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
-      rc = nstep_kernel ? ens_fly_recipes_nstep(x, k, n_waves) : ens_fly_recipes(x, k, n_waves); if (rc) return rc;
-    }
-    x->j += k; left -= k;
-  }
-  return timer.stop_ms(&x->last_ms);
+  return ens_run_advancing(x, periods, kern, q->wl,
+                           [&](size_t l, int level) { const int r = q->recipe_of[l]; return q->have_rule[r] && ens_way_up_scheduled(q->have_lv[r], level, q->rule[r].rule.last_level); },
+                           "dql_ensemble_run: with recipes installed every recipe that has a member needs dql_ensemble_set_recipe and dql_ensemble_set_recipe_level_schedules for every "
+                           "level from its members' up to its last_level; nothing was launched", [&] {
+                             hipLaunchKernelGGL(k_ens_advance_recipes, dim3((unsigned)((x->n + 255) / 256)), dim3(256), 0, 0, x->mem, x->adv, (const RecipeRule*)q->d_rule, q->n,
+                                                (const int*)q->d_recipe_of, x->si, (long long)x->j, (int)DQL_CELLS_PER_LEVEL);
+                           });
 }
-
 // an install or an uninstall would orphan pending entries of the recipes' n-step targets (only an ensemble that called dql_ensemble_set_recipe_nstep with
 // n >= 1 has window arrays while recipes can be installed); DQL_OK: every window is empty
 static int ens_recipes_windows_empty(dql_ensemble* x) {
-  if (!x->ns_len) return DQL_OK;
-  std::vector<int> len((size_t)x->n);
-  HIP_TRY(hipMemcpy(len.data(), x->ns_len, len.size() * sizeof(int), hipMemcpyDeviceToHost));
-  for (int v : len)
-    if (v != 0)
-      return fail(DQL_ESTATE, "dql_ensemble_set_recipes: recipes cannot be installed or uninstalled while a learner's pending window holds entries (after dql_ensemble_set_level, or when every learner is frozen); nothing was changed");
-  return DQL_OK;
+  return ens_windows_empty(x, [](size_t) { return true; }, "dql_ensemble_set_recipes: recipes cannot be installed or uninstalled while a learner's pending window holds entries (after dql_ensemble_set_level, or when every learner is frozen); nothing was changed");
 }
 
 extern "C" {
@@ -201,16 +149,15 @@ int dql_ensemble_set_recipes(dql_ensemble* x, int32_t n_recipes, const int32_t* 
   EnsRecipes* q = new EnsRecipes;
   q->n = n_recipes;
   q->recipe_of.assign(recipe_of, recipe_of + x->n);
-  q->wl_slots = worklist_capacity_recipes(x->n, n_recipes);
-  const size_t n = (size_t)x->n, R = (size_t)n_recipes, waves = (size_t)(q->wl_slots / ADV_WAVE);
-  struct { void** p; size_t bytes; } want[] = {{(void**)&q->d_recipe_of, n * sizeof(int)}, {(void**)&q->d_rule, R * sizeof(RecipeRule)}, {(void**)&q->d_sched, R * sizeof(RecipeSched)},
-                                               {&q->d_mdpk, R * DQL_MAX_LEVELS * mdpk_bytes(x->cfg.dtype)}, {(void**)&q->d_worklist, (size_t)q->wl_slots * sizeof(int)},
-                                               {(void**)&q->d_wave_recipe, waves * sizeof(int)}, {(void**)&q->d_wave_level, waves * sizeof(int)}};
-  bool ok = true;
-  for (auto& w : want) ok = ok && x->dev.alloc(w.p, w.bytes) == hipSuccess && hipMemset(*w.p, 0, w.bytes) == hipSuccess;
+  q->wl.resize(worklist_capacity_recipes(x->n, n_recipes), q->recipe_of.data(), n_recipes);
+  const size_t n = (size_t)x->n, R = (size_t)n_recipes, waves = (size_t)(q->wl.slots / ADV_WAVE);
+  bool ok = ens_alloc_zeroed(x->dev, {{(void**)&q->d_recipe_of, n * sizeof(int)}, {(void**)&q->d_rule, R * sizeof(RecipeRule)}, {(void**)&q->d_sched, R * sizeof(RecipeSched)},
+                                      {&q->d_mdpk, R * DQL_MAX_LEVELS * mdpk_bytes(x->cfg.dtype)}, {(void**)&q->wl.d_list, (size_t)q->wl.slots * sizeof(int)},
+                                      {(void**)&q->wl.d_wave_recipe, waves * sizeof(int)}, {(void**)&q->wl.d_wave_level, waves * sizeof(int)}}) == DQL_OK;
   ok = ok && hipMemcpy(q->d_recipe_of, q->recipe_of.data(), n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
-    for (auto& w : want) (void)x->dev.release(*w.p);
+    void* own[] = {q->d_recipe_of, q->d_rule, q->d_sched, q->d_mdpk, q->wl.d_list, q->wl.d_wave_recipe, q->wl.d_wave_level};
+    for (void* p : own) (void)x->dev.release(p);
     delete q;
     return fail(DQL_ENOMEM, "dql_ensemble_set_recipes: device memory for the recipes could not be set up; nothing was changed");
   }
@@ -230,7 +177,7 @@ int dql_ensemble_set_recipe(dql_ensemble* x, int32_t r, uint32_t quirks, const d
   int rc = check_config(&c); if (rc) return rc;
   if (!alpha) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: null table; nothing was changed");
   if (n_alpha < 1 || n_alpha > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: table lengths must be in 1..2^22; nothing was changed");
-  for (int i = 0; i < n_alpha; ++i) if (!(alpha[i] >= 0.0 && alpha[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: learning rates must be in [0, 1]; nothing was changed");
+  rc = ens_check_rates(alpha, n_alpha, "dql_ensemble_set_recipe: learning rates must be in [0, 1]; nothing was changed"); if (rc) return rc;
   if (!(alpha_min >= 0.0 && alpha_min <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: learning rates must be in [0, 1] (alpha_min); nothing was changed");
   if (!ratios) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: null ratios; nothing was changed");
   for (int k = 0; k < DQL_MAX_LEVELS; ++k) if (!std::isfinite(ratios[k])) return fail(DQL_EINVAL, "dql_ensemble_set_recipe: the five transfer ratios must be finite; nothing was changed");
@@ -239,8 +186,8 @@ int dql_ensemble_set_recipe(dql_ensemble* x, int32_t r, uint32_t quirks, const d
     return fail(DQL_EINVAL, "dql_ensemble_set_recipe: transfer_order must be 0 (the reference's) or 1 (the paper's); nothing was changed");
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipDeviceSynchronize());
-  std::vector<int> level((size_t)x->n);
-  HIP_TRY(hipMemcpy(level.data(), x->adv.level, level.size() * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> level;
+  rc = ens_fetch(x->adv.level, (size_t)x->n, level); if (rc) return rc;
   int top = 0;
   for (size_t l = 0; l < level.size(); ++l) if (q->recipe_of[l] == r && level[l] > top) top = level[l];
   if (last_level < top || last_level >= DQL_MAX_LEVELS)
@@ -276,12 +223,8 @@ int dql_ensemble_set_recipe_level_schedules(dql_ensemble* x, int32_t r, int32_t 
   if (level < 0 || level >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: the level must be in 0..4; nothing was changed");
   if (!eps) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: null table; nothing was changed");
   if (n_eps < 1 || n_eps > (1 << 22)) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: the table length must be in 1..2^22; nothing was changed");
-  // (ens_check_promotion's and ens_upload_eps' checks, here with the whole sentence)
-  if (window < 1 || window > DQL_ENSEMBLE_MAX_WINDOW) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: the promotion window must be in 1..128 (DQL_ENSEMBLE_MAX_WINDOW); nothing was changed");
-  if (min_successes < 1 || max_episodes < 1) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: min_successes and max_episodes must be positive; nothing was changed");
-  for (int i = 0; i < n_eps; ++i) if (!(eps[i] >= 0.0 && eps[i] <= 1.0)) return fail(DQL_EINVAL, "dql_ensemble_set_recipe_level_schedules: exploration rates must be in [0, 1]; nothing was changed");
   uint32_t* d_e = nullptr;
-  int rc = ens_upload_eps(x, "dql_ensemble_set_recipe_level_schedules", eps, n_eps, &d_e); if (rc) return rc;
+  const int rc = ens_check_upload_rule(x, "dql_ensemble_set_recipe_level_schedules", "; nothing was changed", nullptr, 0, eps, n_eps, window, min_successes, max_episodes, &d_e); if (rc) return rc;
   RecipeSched s = q->sched[r];
   s.lv[level] = LevelSched{d_e, n_eps, window, min_successes, max_episodes};
   if (hipMemcpy(q->d_sched + r, &s, sizeof(s), hipMemcpyHostToDevice) != hipSuccess) { (void)x->dev.release(d_e); return fail(DQL_EHIP, "hipMemcpy failed"); }

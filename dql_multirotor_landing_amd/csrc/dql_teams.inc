@@ -64,17 +64,12 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   if (loaded) store_env(e, a.sr, a.si, t.n_envs, g, cl);
   if (applies && loaded) team_store(ts, a.mem, l);
 }
-static int ens_launch_teams(dql_ensemble* x, int k, int n_waves) {
-  int shift = 0;
-  while ((1 << shift) < x->envs_per_learner) ++shift;
-  by_dtype(x->cfg.dtype, [&](auto t) {
-    using T = decltype(t);
-    TeamArgs<T> g;
-    g.a = make_learn_args<T>(x, x->mdpk, k);
-    g.n_envs = x->n_envs; g.envs_per_learner = x->envs_per_learner; g.team_shift = shift;
-    hipLaunchKernelGGL((k_learn_team<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
-  });
-  return DQL_OK;
+template <typename T> static void launch_learn_team(dql_ensemble* x, int k, int n_waves) {
+  TeamArgs<T> g;
+  g.a = make_learn_args<T>(x, x->mdpk, k);
+  g.n_envs = x->n_envs; g.envs_per_learner = x->envs_per_learner; g.team_shift = 0;
+  while ((1 << g.team_shift) < x->envs_per_learner) ++g.team_shift;
+  hipLaunchKernelGGL((k_learn_team<T, TICK_PLAIN, X_ONLY>), dim3((unsigned)n_waves), dim3(64), 0, 0, g);
 }
 extern "C" {
 int dql_ensemble_create_teams(const dql_config* cfg, int device, int64_t n_learners, int32_t envs_per_learner, uint64_t seed, int32_t log_capacity, dql_ensemble** out) {

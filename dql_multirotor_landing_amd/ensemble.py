@@ -74,6 +74,21 @@ def min_successes_for(window: int = 100, success_rate: float = 0.96) -> int:
     return k
 
 
+def _checked_rule(eps, level: int, window, min_successes, max_episodes, bad_eps: str, ranged: bool = False):
+    """-> (eps float64[], window, min_successes, max_episodes) as the library takes them.  eps None: `exploration_rates(level)`; min_successes None: the
+    reference's 0.96 of the window.  ValueError on what the library refuses; `bad_eps` is the caller's sentence for an empty (`ranged`: or out-of-range) table."""
+    e = exploration_rates(level) if eps is None else np.ascontiguousarray(eps, dtype=np.float64).ravel()
+    window = int(window)
+    if not 1 <= window <= MAX_WINDOW:
+        raise ValueError(f"window must be in 1..{MAX_WINDOW}")
+    ms = min_successes_for(window) if min_successes is None else int(min_successes)
+    if ms < 1 or int(max_episodes) < 1:
+        raise ValueError("min_successes and max_episodes must be positive")
+    if e.size < 1 or (ranged and not ((e >= 0.0) & (e <= 1.0)).all()):
+        raise ValueError(bad_eps)
+    return e, window, ms, int(max_episodes)
+
+
 @dataclass
 class LevelSchedule:
     """what one level of a recipe flies with (`SequentialEnsemble.set_level_schedules`' arguments); eps None: `exploration_rates(level)`; min_successes None:
@@ -120,18 +135,8 @@ class Recipe:
             raise ValueError("transfer_order must be 0 (the reference's) or 1 (the paper's)")
         if len(self.levels) != MAX_LEVELS:
             raise ValueError("a recipe has five level schedules")
-        lv = []
-        for k, s in enumerate(self.levels):
-            e = exploration_rates(k) if s.eps is None else np.ascontiguousarray(s.eps, dtype=np.float64).ravel()
-            window = int(s.window)
-            if not 1 <= window <= MAX_WINDOW:
-                raise ValueError(f"window must be in 1..{MAX_WINDOW}")
-            ms = min_successes_for(window) if s.min_successes is None else int(s.min_successes)
-            if ms < 1 or int(s.max_episodes) < 1:
-                raise ValueError("min_successes and max_episodes must be positive")
-            if e.size < 1 or not ((e >= 0.0) & (e <= 1.0)).all():
-                raise ValueError("the eps table must not be empty and exploration rates must be in [0, 1]")
-            lv.append((e, window, ms, int(s.max_episodes)))
+        lv = [_checked_rule(s.eps, k, s.window, s.min_successes, s.max_episodes, "the eps table must not be empty and exploration rates must be in [0, 1]", ranged=True)
+              for k, s in enumerate(self.levels)]
         return alpha, alpha_min, r, lv
 
 
@@ -190,17 +195,11 @@ class SequentialEnsemble:
         """alpha_table: alpha(count), default the config's; eps: exploration rate per episode index within the level, default the reference's for the
         config's level; window / min_successes: the promotion rule (default: the reference's 0.96 of the window); max_episodes: budget per level"""
         alpha = self.cfg.alpha_table() if alpha_table is None else np.ascontiguousarray(alpha_table, dtype=np.float64).ravel()
-        e = exploration_rates(self.cfg.working_curriculum_step) if eps is None else np.ascontiguousarray(eps, dtype=np.float64).ravel()
-        window = int(window)
-        if not 1 <= window <= MAX_WINDOW:
-            raise ValueError(f"window must be in 1..{MAX_WINDOW}")
-        ms = min_successes_for(window) if min_successes is None else int(min_successes)
-        if ms < 1 or int(max_episodes) < 1:
-            raise ValueError("min_successes and max_episodes must be positive")
-        if alpha.size < 1 or e.size < 1:
+        e, window, ms, max_episodes = _checked_rule(eps, self.cfg.working_curriculum_step, window, min_successes, max_episodes, "the alpha and eps tables must not be empty")
+        if alpha.size < 1:
             raise ValueError("the alpha and eps tables must not be empty")
-        _lib.check(self.lib.dql_ensemble_set_schedules(self._h, _p(alpha), alpha.size, _p(e), e.size, window, ms, int(max_episodes)))
-        self.window, self.min_successes, self.max_episodes = window, ms, int(max_episodes)
+        _lib.check(self.lib.dql_ensemble_set_schedules(self._h, _p(alpha), alpha.size, _p(e), e.size, window, ms, max_episodes))
+        self.window, self.min_successes, self.max_episodes = window, ms, max_episodes
 
     def set_level(self, level: int):
         """new working level: every env re-enters through reset, per-level episode counts and windows are cleared, all learners re-armed"""
@@ -262,18 +261,11 @@ class SequentialEnsemble:
 
     def set_level_schedules(self, level: int, eps=None, window: int = 100, min_successes: Optional[int] = None, max_episodes: int = 50000):
         """`set_schedules` without the learning rates, for the learners that stand on `level` in curriculum mode (eps default: the reference's for it)"""
-        level, window = int(level), int(window)
+        level = int(level)
         if not 0 <= level < MAX_LEVELS:
             raise ValueError("level must be in 0..4")
-        e = exploration_rates(level) if eps is None else np.ascontiguousarray(eps, dtype=np.float64).ravel()
-        if not 1 <= window <= MAX_WINDOW:
-            raise ValueError(f"window must be in 1..{MAX_WINDOW}")
-        ms = min_successes_for(window) if min_successes is None else int(min_successes)
-        if ms < 1 or int(max_episodes) < 1:
-            raise ValueError("min_successes and max_episodes must be positive")
-        if e.size < 1:
-            raise ValueError("the eps table must not be empty")
-        _lib.check(self.lib.dql_ensemble_set_level_schedules(self._h, level, _p(e), e.size, window, ms, int(max_episodes)))
+        e, window, ms, max_episodes = _checked_rule(eps, level, window, min_successes, max_episodes, "the eps table must not be empty")
+        _lib.check(self.lib.dql_ensemble_set_level_schedules(self._h, level, _p(e), e.size, window, ms, max_episodes))
 
     def levels(self):
         """{"level": int32 [L], "promoted_at": int32 [5][L] (episode at level k at which the learner promoted, or -1), "episodes_at": int32 [5][L],
@@ -368,6 +360,12 @@ class SequentialEnsemble:
         v = C.c_int64()
         _lib.check(self.lib.dql_ensemble_get_period_index(self._h, C.byref(v)))
         return int(v.value)
+
+    def launches(self):
+        """(launches, periods, wave_periods) of the learner kernels since creation (dql_diag_ensemble_launches): the periods summed over the launches, and waves x periods"""
+        n, p, wp = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(self.lib.dql_diag_ensemble_launches(self._h, C.byref(n), C.byref(p), C.byref(wp)))
+        return int(n.value), int(p.value), int(wp.value)
 
     def index_faults(self) -> int:
         v = C.c_int64()
@@ -536,16 +534,21 @@ class SequentialEnsemble:
         return out
 
 
-def train_level(ens: SequentialEnsemble, chunk_periods: int = 16 * MAX_PERIODS_PER_LAUNCH, max_periods: Optional[int] = None, on_chunk=None) -> int:
-    """Run the current level until every learner is frozen (promoted, or out of episodes) or `max_periods` are flown; -> periods flown."""
+def _run_until(ens: SequentialEnsemble, still_running, chunk_periods: int, max_periods: Optional[int], on_chunk) -> int:
+    """`ens.run` in chunks while `still_running()` counts a learner and fewer than `max_periods` are flown; -> periods flown"""
     flown = 0
-    while ens.n_live() > 0 and (max_periods is None or flown < max_periods):
+    while still_running() > 0 and (max_periods is None or flown < max_periods):
         k = int(chunk_periods) if max_periods is None else min(int(chunk_periods), int(max_periods) - flown)
         ens.run(k)
         flown += k
         if on_chunk is not None:
             on_chunk(ens, flown)
     return flown
+
+
+def train_level(ens: SequentialEnsemble, chunk_periods: int = 16 * MAX_PERIODS_PER_LAUNCH, max_periods: Optional[int] = None, on_chunk=None) -> int:
+    """Run the current level until every learner is frozen (promoted, or out of episodes) or `max_periods` are flown; -> periods flown."""
+    return _run_until(ens, ens.n_live, chunk_periods, max_periods, on_chunk)
 
 
 def curriculum(ens: SequentialEnsemble, levels: int = 5, first_level: int = 0, ratios=None, max_episodes: Optional[int] = None, max_periods_per_level: Optional[int] = None,
@@ -586,13 +589,7 @@ def curriculum_per_learner(ens: SequentialEnsemble, last_level: int = 4, advance
     for k in range(MAX_LEVELS):
         ens.set_level_schedules(k, exploration_rates(k), window, ms, budget)
     ens.set_curriculum(last_level, advance_every, ratios, advance_exhausted)
-    flown = 0
-    while ens.n_unfinished() > 0 and (max_periods is None or flown < max_periods):
-        k = int(chunk_periods) if max_periods is None else min(int(chunk_periods), int(max_periods) - flown)
-        ens.run(k)
-        flown += k
-        if on_chunk is not None:
-            on_chunk(ens, flown)
+    flown = _run_until(ens, ens.n_unfinished, chunk_periods, max_periods, on_chunk)
     out = ens.levels()
     out["periods"] = flown
     return out
@@ -607,13 +604,7 @@ def curriculum_recipes(ens: SequentialEnsemble, recipes, recipe_of, advance_ever
         raise ValueError(TEAMS_BARRIER_ONLY)
     ens.set_curriculum(MAX_LEVELS - 1, advance_every)
     ens.set_recipes(recipes, recipe_of)
-    flown = 0
-    while ens.n_unfinished() > 0 and (max_periods is None or flown < max_periods):
-        k = int(chunk_periods) if max_periods is None else min(int(chunk_periods), int(max_periods) - flown)
-        ens.run(k)
-        flown += k
-        if on_chunk is not None:
-            on_chunk(ens, flown)
+    flown = _run_until(ens, ens.n_unfinished, chunk_periods, max_periods, on_chunk)
     out = ens.levels()
     out["periods"] = flown
     out["recipe_of"] = ens.recipes()[1]

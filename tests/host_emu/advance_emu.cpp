@@ -1,7 +1,7 @@
 // advance_emu.cpp — dql_ensemble_run in curriculum mode, emulated on the CPU from the real device source: dql_advance.hpp's
 // build_worklist and advance_learner on top of dql_learner.hpp's learner_periods.
 //
-// The driver does what ens_run_levels (dql_ensemble.inc) does: launches cut at the multiples of advance_every; at such a period index every learner takes
+// The driver does what ens_run_advancing does for ens_run_levels (dql_ensemble.inc): launches cut at the multiples of advance_every; at such a period index every learner takes
 // advance_learner's step (k_ens_advance: one thread per learner); then the live learners are regrouped by level (build_worklist) and flown wave by wave, lane
 // by lane, as k_learn_levels flies them — the wave's level from wave_level[w], the lane's learner from the worklist (-1: an inactive lane), SimK::working, the
 // level's MdpK and the level's schedules from that level.  A lane runs alone: __ballot(p) is p (host_shim.h).  Every array is exactly as long as the library

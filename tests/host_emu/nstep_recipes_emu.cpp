@@ -2,7 +2,7 @@
 // device source: dql_recipes.hpp's build_worklist_recipes and advance_learner_recipe on top of dql_nstep.hpp's learner_periods_nstep and dql_learner.hpp's
 // learner_periods.
 //
-// recipes_emu.cpp's driver with nstep_emu.cpp's windows.  It does what ens_run_recipes (dql_recipes.inc) does: launches cut at the multiples of
+// recipes_emu.cpp's driver with nstep_emu.cpp's windows.  It does what ens_run_advancing (dql_ensemble.inc) does for ens_run_recipes (dql_recipes.inc): launches cut at the multiples of
 // advance_every; at such a period index every learner takes advance_learner_recipe's step; then the live learners are regrouped by (recipe, level) and flown
 // wave by wave, lane by lane, as k_learn_recipes_nstep (dql_nstep_recipes.inc) flies them — the wave's recipe and level from wave_recipe[w] and wave_level[w],
 // its n from recipe_nstep[recipe], the lane's learner from the worklist (-1: an inactive lane); a wave with n = 0 flies learner_periods, the others

@@ -1,7 +1,7 @@
 // recipes_emu.cpp — dql_ensemble_run with recipes installed, emulated on the CPU from the real device source: dql_recipes.hpp's
 // build_worklist_recipes and advance_learner_recipe on top of dql_learner.hpp's learner_periods.
 //
-// The driver does what ens_run_recipes (dql_recipes.inc) does: launches cut at the multiples of advance_every; at such a period index every learner takes
+// The driver does what ens_run_advancing (dql_ensemble.inc) does for ens_run_recipes (dql_recipes.inc): launches cut at the multiples of advance_every; at such a period index every learner takes
 // advance_learner_recipe's step (k_ens_advance_recipes: one thread per learner); then the live learners are regrouped by (recipe, level) and flown wave by
 // wave, lane by lane, as k_learn_recipes flies them — the wave's recipe and level from wave_recipe[w] and wave_level[w], the lane's learner from the worklist
 // (-1: an inactive lane), SimK::working and SimK::quirks, the MdpK of (recipe, level), the recipe's learning rates and the level's schedules from those.  A

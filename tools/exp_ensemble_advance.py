@@ -14,7 +14,6 @@ tests/advance_checks.py, counting live learners period by period, gives the same
 set of lines is measured with `--second-window` / `--second-success-rate` (default: 10 episodes, 0.5), a setting chosen beforehand, not tuned.  `--max-periods` caps a path (per level for `curriculum`, divided by the levels); a capped
 run says so.  One JSON line per path is appended to `--out`."""
 import argparse
-import ctypes as C
 import json
 import statistics
 import sys
@@ -25,15 +24,8 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-from dql_multirotor_landing_amd import _lib  # noqa: E402
 from dql_multirotor_landing_amd.config import F32, as_launched_config  # noqa: E402
 from dql_multirotor_landing_amd.ensemble import SequentialEnsemble, curriculum, curriculum_per_learner  # noqa: E402
-
-
-def launches(ens):
-    n, p, wp = C.c_int64(), C.c_int64(), C.c_int64()
-    _lib.check(ens.lib.dql_diag_ensemble_launches(ens._h, C.byref(n), C.byref(p), C.byref(wp)))
-    return int(n.value), int(p.value), int(wp.value)
 
 
 def one(path, a):
@@ -54,7 +46,7 @@ def one(path, a):
             beyond = int((h["promoted_at"][1:] >= 0).any(axis=0).sum())
         wall = time.perf_counter() - t0
         c = ens.counters()
-        n, p, wp = launches(ens)
+        n, p, wp = ens.launches()
         return {"wall_s": wall, "launches": n, "periods_launched": p, "wave_periods_launched": wp,
                 "learner_periods_flown": int(c["decisions"].sum() + c["episodes"].sum() + a.learners - c["frozen"].astype(bool).sum()), "period_index": ens.period_index(),
                 "learners_per_level_at_the_end": np.bincount(level, minlength=5).tolist(), "promoted_at_current_level": int((c["promotion_episode"] >= 0).sum()),

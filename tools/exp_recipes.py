@@ -42,12 +42,6 @@ LANDING_RECIPES = ["reference",
                    {"name": "paper, eps 0.1 for 64 episodes above level 0", "preset": "paper", "levels": {str(k): {"eps": [0.1] * 64 + [0.0]} for k in (1, 2, 3, 4)}}]
 
 
-def launches(ens):
-    n, p, wp = C.c_int64(), C.c_int64(), C.c_int64()
-    _lib.check(ens.lib.dql_diag_ensemble_launches(ens._h, C.byref(n), C.byref(p), C.byref(wp)))
-    return int(n.value), int(p.value), int(wp.value)
-
-
 def last_ms(ens):
     v = C.c_double()
     _lib.check(ens.lib.dql_diag_ensemble_last(ens._h, C.byref(v)))
@@ -81,7 +75,7 @@ def one_timing(way, a):
             ens.set_curriculum(4, a.advance_every)
             ens.set_recipes([timing_recipe(r, eps_budget) for r in range(R)], np.arange(R * n) % R)
             wall, ms = fly(ens, a.periods, a.chunk)
-            n_l, n_p, n_wp = launches(ens)
+            n_l, n_p, n_wp = ens.launches()
             decisions = int(ens.counters()["decisions"].sum())
             assert ens.index_faults() == 0
         finally:
@@ -96,7 +90,7 @@ def one_timing(way, a):
                 ens.set_curriculum(4, a.advance_every, rec.ratios)
                 w, m = fly(ens, a.periods, a.chunk)
                 wall += w; ms += m
-                l, p, wp = launches(ens)
+                l, p, wp = ens.launches()
                 n_l += l; n_p += p; n_wp += wp
                 decisions += int(ens.counters()["decisions"].sum())
                 assert ens.index_faults() == 0
