@@ -200,6 +200,8 @@ SYMBOLS = {
     "dql_ensemble_get_nstep": (C.c_int, [_vp, C.POINTER(_i32), _vp]),
     "dql_ensemble_set_recipe_nstep": (C.c_int, [_vp, _i32, _i32]),
     "dql_ensemble_get_recipe_nstep": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "dql_ensemble_set_team_nstep": (C.c_int, [_vp, _i32]),
+    "dql_ensemble_get_team_nstep": (C.c_int, [_vp, C.POINTER(_i32), _vp]),
 }
 MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS
 

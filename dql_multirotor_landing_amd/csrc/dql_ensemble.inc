@@ -153,9 +153,14 @@ struct dql_ensemble {
   // first dql_ensemble_set_recipe_nstep with n >= 1 (section 23, dql_nstep_recipes.inc: n is then a recipe's, EnsRecipes::nstep, and `nstep` here stays 0)
   int nstep = 0;
   uint16_t* ns_key = nullptr; double* ns_val = nullptr; int* ns_len = nullptr;
+  // a team ensemble's n-step targets (DESIGN.md section 24, dql_team_nstep.inc); team_nstep = 0: dql_ensemble_run flies k_learn_team and the arrays below are never
+  // read.  One pending window PER ENV between launches: key / val [DQL_NSTEP_MAX][n_envs], len [n_envs], allocated by the first dql_ensemble_set_team_nstep with
+  // n >= 1.  Members of their own: nstep and ns_* above stay 0 / null on a team ensemble, so dql_ensemble_get_nstep answers as it always did
+  int team_nstep = 0;
+  uint16_t* tn_key = nullptr; double* tn_val = nullptr; int* tn_len = nullptr;
 };
-// which of the six learner kernels a launch flies (ens_kernel_of decides, ens_fly switches)
-enum EnsKernel { ENS_K_LEARN, ENS_K_TEAM, ENS_K_NSTEP, ENS_K_LEVELS, ENS_K_RECIPES, ENS_K_RECIPES_NSTEP };
+// which of the seven learner kernels a launch flies (ens_kernel_of decides, ens_fly switches)
+enum EnsKernel { ENS_K_LEARN, ENS_K_TEAM, ENS_K_TEAM_NSTEP, ENS_K_NSTEP, ENS_K_LEVELS, ENS_K_RECIPES, ENS_K_RECIPES_NSTEP };
 // of dql_recipes.inc: the installed recipes let go, the rule learner l advances by, the smallest last_level of the populated recipes, whether a recipe that has
 // a member has n >= 1, the device copy of the recipes' n (null until one was set), dql_ensemble_run's part with recipes installed
 static void ens_recipes_release(dql_ensemble* x);
@@ -168,8 +173,10 @@ static int ens_run_recipes(dql_ensemble* x, int64_t periods, EnsKernel kern);
 template <typename T> static void launch_learn_recipes(dql_ensemble* x, int k, int n_waves);        // dql_recipes.inc
 template <typename T> static void launch_learn_team(dql_ensemble* x, int k, int n_waves);           // dql_teams.inc
 template <typename T> static void launch_learn_nstep(dql_ensemble* x, int k, int n_waves);          // dql_nstep.inc
+template <typename T> static void launch_learn_team_nstep(dql_ensemble* x, int k, int n_waves);     // dql_team_nstep.inc
 template <typename T> static void launch_learn_recipes_nstep(dql_ensemble* x, int k, int n_waves);  // dql_nstep_recipes.inc
 #define ENS_NSTEP_REFUSED(who) "" who ": n-step targets (dql_ensemble_set_nstep with n >= 1) are for the plain mode, where every learner flies the config's level; set n = 0 first; nothing was changed and nothing was launched"
+#define ENS_TEAM_NSTEP_REFUSED(who) "" who ": team n-step targets (dql_ensemble_set_team_nstep with n >= 1) are for the barrier mode, where every learner flies the config's level: a team ensemble of one env per learner has no per-learner curriculum and no recipes while they are on; set n = 0 first; nothing was changed and nothing was launched"
 #define ENS_TEAMS_REFUSED(who) "" who ": an ensemble with more than one env per learner flies the barrier mode only (teams have no per-learner curriculum and no recipes); nothing was changed and nothing was launched"
 #define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
 // the tables of learners [first, first + count) where they live, for the dql_ensemble_* twins of the greedy family (TableSets of dql_greedy.inc; count >= 1 is the
@@ -280,10 +287,12 @@ template <typename T> static void launch_learn_levels(dql_ensemble* x, int k, in
 }
 // The one place that says which kernel flies.  by_level: the launch goes through a worklist (curriculum mode, with or without recipes); with one env per learner
 // a team ensemble in curriculum mode flies k_learn_levels, the same learner; n >= 1 is refused on team ensembles and in curriculum mode, and with recipes
-// installed n is a recipe's: one recipe that has a member and n >= 1 makes every launch k_learn_recipes_nstep's.
+// installed n is a recipe's: one recipe that has a member and n >= 1 makes every launch k_learn_recipes_nstep's.  A team ensemble with team_nstep >= 1 flies
+// k_learn_team_nstep in the barrier mode; team_nstep >= 1 and curriculum mode (possible with one env per learner only) refuse each other, so by_level never
+// meets it.
 static EnsKernel ens_kernel_of(const dql_ensemble* x, bool by_level) {
   if (by_level) return !x->rcp ? ENS_K_LEVELS : ens_recipes_any_nstep(x) ? ENS_K_RECIPES_NSTEP : ENS_K_RECIPES;
-  return x->teams ? ENS_K_TEAM : x->nstep ? ENS_K_NSTEP : ENS_K_LEARN;
+  return x->teams ? (x->team_nstep ? ENS_K_TEAM_NSTEP : ENS_K_TEAM) : x->nstep ? ENS_K_NSTEP : ENS_K_LEARN;
 }
 // The one launch path of the learners: k periods from period x->j on n_waves waves.  The tick schedule, the kernel, its completion, the launch accounting
 // (dql_diag_ensemble_launches).
@@ -292,12 +301,15 @@ static int ens_fly(dql_ensemble* x, EnsKernel kern, int k, int n_waves) {
   if (windows && (!x->ns_key || !x->ns_val || !x->ns_len || (kern == ENS_K_RECIPES_NSTEP && !ens_recipes_nstep_table(x))))  // (never taken unless a bug)
     return fail(DQL_ESTATE, kern == ENS_K_NSTEP ? "dql_ensemble_run: n-step targets are on but the pending windows were never allocated; nothing was launched"
                                                 : "dql_ensemble_run: a recipe has n-step targets but the pending windows were never allocated; nothing was launched");
+  if (kern == ENS_K_TEAM_NSTEP && (!x->tn_key || !x->tn_val || !x->tn_len))  // (never taken unless a bug)
+    return fail(DQL_ESTATE, "dql_ensemble_run: team n-step targets are on but the envs' pending windows were never allocated; nothing was launched");
   const int rc = upload_schedule(x->cfg, x->j, k, x->d_mgr0, x->d_sched); if (rc) return rc;  // (synchronous: the previous launch has read its schedule)
   by_dtype(x->cfg.dtype, [&](auto t) {
     using T = decltype(t);
     switch (kern) {
       case ENS_K_LEARN: launch_learn<T>(x, k, n_waves); break;
       case ENS_K_TEAM: launch_learn_team<T>(x, k, n_waves); break;
+      case ENS_K_TEAM_NSTEP: launch_learn_team_nstep<T>(x, k, n_waves); break;
       case ENS_K_NSTEP: launch_learn_nstep<T>(x, k, n_waves); break;
       case ENS_K_LEVELS: launch_learn_levels<T>(x, k, n_waves); break;
       case ENS_K_RECIPES: launch_learn_recipes<T>(x, k, n_waves); break;
@@ -490,6 +502,7 @@ int dql_ensemble_set_level(dql_ensemble* x, int32_t k) {
   HIP_TRY(hipDeviceSynchronize());
   rc = ens_set_levels(x, k); if (rc) return rc;
   if (x->ns_len) HIP_TRY(hipMemset(x->ns_len, 0, (size_t)x->n * sizeof(int)));  // every env re-enters through reset: the pending windows belong to episodes that are gone
+  if (x->tn_len) HIP_TRY(hipMemset(x->tn_len, 0, (size_t)x->n_envs * sizeof(int)));  // ... and so do the team envs' (section 24)
   return ens_rearm(x);
 }
 int dql_ensemble_n_live(dql_ensemble* x, int64_t* n_live) {
@@ -548,6 +561,7 @@ int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t adv
     return DQL_OK;
   }
   if (x->nstep) return fail(DQL_EINVAL, ENS_NSTEP_REFUSED("dql_ensemble_set_curriculum"));
+  if (x->team_nstep) return fail(DQL_EINVAL, ENS_TEAM_NSTEP_REFUSED("dql_ensemble_set_curriculum"));
   if (!ratios) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: null ratios; nothing was changed");
   for (int k = 0; k < DQL_MAX_LEVELS; ++k) if (!std::isfinite(ratios[k])) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the five transfer ratios must be finite; nothing was changed");
   if (advance_exhausted != 0 && advance_exhausted != 1) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_exhausted must be 0 or 1; nothing was changed");

@@ -138,6 +138,7 @@ int dql_ensemble_set_recipes(dql_ensemble* x, int32_t n_recipes, const int32_t* 
     return DQL_OK;
   }
   if (x->nstep) return fail(DQL_EINVAL, ENS_NSTEP_REFUSED("dql_ensemble_set_recipes"));
+  if (x->team_nstep) return fail(DQL_EINVAL, ENS_TEAM_NSTEP_REFUSED("dql_ensemble_set_recipes"));
   if (!x->advance_every) return fail(DQL_EINVAL, "dql_ensemble_set_recipes: recipes need curriculum mode (dql_ensemble_set_curriculum with advance_every > 0 first); nothing was changed");
   if (!recipe_of) return fail(DQL_EINVAL, "dql_ensemble_set_recipes: null recipe_of; nothing was changed");
   for (long long l = 0; l < x->n; ++l)

@@ -27,6 +27,8 @@ MAX_ADVANCE_EVERY = 4096       # csrc/dql_advance.hpp ADV_MAX_EVERY
 MAX_RECIPES = 64               # include/dql.h DQL_ENSEMBLE_MAX_RECIPES
 NSTEP_MAX = 16                 # include/dql.h DQL_NSTEP_MAX
 NSTEP_PLAIN_ONLY = "n-step targets (nstep >= 1) are for the plain mode, where every learner flies the config's level: no teams, no per-learner curriculum, no recipes"
+TEAM_NSTEP_TEAMS_ONLY = "team_nstep is for an ensemble made through the team kernel (envs_per_learner > 1 or teams=True); a plain ensemble takes nstep"
+TEAM_NSTEP_BARRIER_ONLY = "team n-step targets (team_nstep >= 1) are for the barrier mode, where every learner flies the config's level: no per-learner curriculum, no recipes"
 TEAM_SIZES = (1, 2, 4, 8, 16, 32, 64)  # envs per learner (include/dql.h dql_ensemble_create_teams): a team is consecutive lanes of one wave
 TEAMS_BARRIER_ONLY = "an ensemble with more than one env per learner flies the barrier mode only (train_level / curriculum): teams have no per-learner curriculum and no recipes"
 ORDER_REFERENCE, ORDER_PAPER = 0, 1  # Recipe.transfer_order
@@ -142,8 +144,10 @@ class Recipe:
 
 class SequentialEnsemble:
     def __init__(self, cfg: DqlConfig, n_learners: int, seed: int = 42, device: int = 0, log_capacity: int = 0, alpha_table=None, eps=None, window: int = 100,
-                 min_successes: Optional[int] = None, max_episodes: int = 50000, envs_per_learner: int = 1, teams: Optional[bool] = None, nstep: int = 0):
+                 min_successes: Optional[int] = None, max_episodes: int = 50000, envs_per_learner: int = 1, teams: Optional[bool] = None, nstep: int = 0,
+                 team_nstep: int = 0):
         """nstep: 0 for the reference's one-step update, 1..NSTEP_MAX for the n-step return as the target (`set_nstep`).
+        team_nstep: the same for a team ensemble, one pending window per env (`set_team_nstep`).
         envs_per_learner: E envs per learner (`TEAM_SIZES`), whose transitions the learner takes in env order every period; learner l
         owns envs l E .. l E + E - 1 and `state()` returns [L E] arrays.  teams: create through dql_ensemble_create_teams (the team kernel) — default: when E > 1;
         True with E = 1 flies the team kernel with teams of one, which equals the plain ensemble bit for bit."""
@@ -162,6 +166,7 @@ class SequentialEnsemble:
         if log_capacity < 0:
             raise ValueError("log_capacity must not be negative")
         self._check_nstep(int(nstep), teams)
+        self._check_team_nstep(int(team_nstep), teams)
         self.lib = _lib.load()
         self.cfg = cfg
         self.n = n_learners
@@ -174,10 +179,12 @@ class SequentialEnsemble:
         else:
             _lib.check(self.lib.dql_ensemble_create(C.byref(self._c), int(device), self.n, int(seed), log_capacity, C.byref(h)))
         self._h = h
-        self._nstep, self._advance_every = 0, 0
+        self._nstep, self._advance_every, self._team_nstep = 0, 0, 0
         self.set_schedules(alpha_table, eps, window, min_successes, max_episodes)
         if int(nstep):
             self.set_nstep(nstep)
+        if int(team_nstep):
+            self.set_team_nstep(team_nstep)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -238,6 +245,42 @@ class SequentialEnsemble:
         _lib.check(self.lib.dql_ensemble_get_nstep(self._h, C.byref(v), _p(out)))
         return out
 
+    # ---- n-step targets for team ensembles: one pending window per env (include/dql.h) ----
+    @staticmethod
+    def _check_team_nstep(n: int, teams: bool, curriculum: bool = False):
+        if not 0 <= n <= NSTEP_MAX:
+            raise ValueError(f"team_nstep must be in 0..{NSTEP_MAX} (0: the one-step team update)")
+        if not teams and n >= 1:
+            raise ValueError(TEAM_NSTEP_TEAMS_ONLY)
+        if n >= 1 and curriculum:
+            raise ValueError(TEAM_NSTEP_BARRIER_ONLY)
+
+    def set_team_nstep(self, n: int):
+        """n = 0: `run` flies the one-step team kernel, as after creation.  1 <= n <= NSTEP_MAX: every ENV keeps a pending window of its own and the learner
+        updates with the uncorrected n-step Double-Q return, the E records of a period still in env order (include/dql.h); n = 1 equals n = 0 bit for bit, E = 1
+        equals a plain ensemble's `set_nstep(n)`.  A frozen team's windows are generally NOT empty: the library refuses a change of n while any env's window
+        holds entries, so change it after creation or after `set_level` (n = 0 and n = 1 leave every window empty after every period, so a change from them
+        is accepted at any time).  Refused in per-learner curriculum mode and with recipes installed, which a team ensemble of one env per learner can enter."""
+        n = int(n)
+        teams = bool(getattr(self, "teams", False))
+        if not teams:
+            raise ValueError(TEAM_NSTEP_TEAMS_ONLY)
+        self._check_team_nstep(n, teams, bool(self.__dict__.get("_advance_every", 0)) or bool(self.__dict__.get("_recipes", [])))
+        _lib.check(self.lib.dql_ensemble_set_team_nstep(self._h, n))
+        self._team_nstep = n
+
+    @property
+    def team_nstep(self) -> int:
+        v = C.c_int32()
+        _lib.check(self.lib.dql_ensemble_get_team_nstep(self._h, C.byref(v), None))
+        return int(v.value)
+
+    def team_pending_lengths(self) -> np.ndarray:
+        """int32 [L E]: the entries in each env's pending window, in env order (0 with team_nstep = 0 and right after `set_level`; a frozen team's stay open)"""
+        v, out = C.c_int32(), np.zeros(self.n_envs, dtype=np.int32)
+        _lib.check(self.lib.dql_ensemble_get_team_nstep(self._h, C.byref(v), _p(out)))
+        return out
+
     # ---- per-learner curriculum levels (include/dql.h, DESIGN.md section 14) ----
     def set_curriculum(self, last_level: int = 4, advance_every: int = MAX_ADVANCE_EVERY, ratios=None, advance_exhausted: bool = True):
         """Curriculum mode: at every period index that is a multiple of `advance_every`, a frozen learner below `last_level` that promoted (or ran out of
@@ -250,6 +293,8 @@ class SequentialEnsemble:
             raise ValueError(f"advance_every must be in 0..{MAX_ADVANCE_EVERY}")
         if advance_every and getattr(self, "_nstep", 0):
             raise ValueError(NSTEP_PLAIN_ONLY)
+        if advance_every and self.__dict__.get("_team_nstep", 0):
+            raise ValueError(TEAM_NSTEP_BARRIER_ONLY)
         r = np.ascontiguousarray(REFERENCE_RATIOS if ratios is None else ratios, dtype=np.float64).ravel()
         if advance_every:
             if not 0 <= last_level < MAX_LEVELS:
@@ -293,6 +338,8 @@ class SequentialEnsemble:
             raise ValueError(f"at most {MAX_RECIPES} recipes")
         if recipes and getattr(self, "_nstep", 0):
             raise ValueError(NSTEP_PLAIN_ONLY)
+        if recipes and self.__dict__.get("_team_nstep", 0):
+            raise ValueError(TEAM_NSTEP_BARRIER_ONLY)
         if not recipes:
             _lib.check(self.lib.dql_ensemble_set_recipes(self._h, 0, None))
             self._recipes = []
@@ -552,13 +599,16 @@ def train_level(ens: SequentialEnsemble, chunk_periods: int = 16 * MAX_PERIODS_P
 
 
 def curriculum(ens: SequentialEnsemble, levels: int = 5, first_level: int = 0, ratios=None, max_episodes: Optional[int] = None, max_periods_per_level: Optional[int] = None,
-               window: int = 100, success_rate: float = 0.96, on_level=None, nstep: Optional[int] = None):
+               window: int = 100, success_rate: float = 0.96, on_level=None, nstep: Optional[int] = None, team_nstep: Optional[int] = None):
     """`Trainer.curriculum_training` for the ensemble: per level, run until all learners are frozen, `transfer_learning` of the finished level with the
     reference's ratio, next level.  -> per level, the counters at its end.  nstep: `ens.set_nstep(nstep)` before the first level (the windows must be
-    empty: a fresh ensemble, or one whose learners are all frozen); None leaves the ensemble's setting."""
+    empty: a fresh ensemble, or one whose learners are all frozen); None leaves the ensemble's setting.  team_nstep: `ens.set_team_nstep(team_nstep)` before
+    the first level, for a team ensemble (every env's window must be empty: a fresh ensemble, or right after `set_level`)."""
     from .trainer import Trainer
     if nstep is not None:
         ens.set_nstep(nstep)
+    if team_nstep is not None:
+        ens.set_team_nstep(team_nstep)
     me = SimpleNamespace(_scale_modification_value=(0.8172650252856599, 0.8211253690681617, 0.8257273369742982, 0.8311571820651724))
     history = []
     for k in range(int(first_level), int(levels)):

@@ -776,6 +776,37 @@ int dql_ensemble_get_nstep(dql_ensemble* ens, int32_t* n, int32_t* pending_len_o
 int dql_ensemble_set_recipe_nstep(dql_ensemble* ens, int32_t recipe, int32_t n);
 int dql_ensemble_get_recipe_nstep(dql_ensemble* ens, int32_t recipe, int32_t* n);
 
+/* ---- n-step targets for team ensembles: one pending window per env ----
+ * A team ensemble (dql_ensemble_create_teams, any E, E = 1 included) has an ensemble-wide team_nstep.  At 0, the state at creation, dql_ensemble_run flies
+ * the one-step team kernel exactly as before.  At 1 <= n <= DQL_NSTEP_MAX every ENV g keeps a pending window of its own: at most n entries (cell, reward as
+ * a double, coin), one per decision of env g's running episode, oldest first.  A period of a live learner is the team period described above — one
+ * threshold per team, the greedy row read from the tables as they stand after all of the previous period's updates, the flight, the bookkeeping, the
+ * decision rule, the freeze at the period's end — with the update replaced.  For e = 0 .. E - 1 in env order, for an env that made a decision: (1) the
+ * decision's entry is appended to env g's window; (2) both tables' row of s' is read ONCE, AT THIS ENV'S TURN: after every write that envs < e made in this
+ * period and before this env's own; (3) mask as in the team period; (4) if the period ended the env's episode every entry is updated, oldest first, and the
+ * window emptied; else if the window holds n entries the oldest is updated and removed; else nothing is updated.  One update is dql_ensemble_set_nstep's,
+ * operation for operation: the ENTRY's own coin, best on the row of step 2, g = best * mask, g = r_i + (gamma * g) for i = m - 1 down to k, alpha at the
+ * cell's count as it stands at that moment (pre-increment), q_new = q + alpha * (g - q) on the value that stands at that moment: team-mates may have
+ * written the entry's cell since it was appended.  A cell outside [0, 2835), or an s' outside the tables, is counted in dql_ensemble_index_faults; nothing
+ * is updated for it and the window keeps its shape (at most n - 1 entries after the record, none after a done).
+ * With E = 1 every output equals a plain ensemble's under dql_ensemble_set_nstep(n); with n = 1 every output equals team_nstep = 0, bit for bit.
+ * A team freezes at the end of the deciding period, when its envs are mostly in the middle of an episode: A FROZEN TEAM'S WINDOWS ARE GENERALLY NOT EMPTY,
+ * unlike a plain n-step learner's.  The windows persist in device memory per env across launches and across a freeze: runs of a and b periods equal one
+ * run of a + b; dql_ensemble_rearm, _transfer and _set_tables leave them alone, and after a rearm the envs fly on with the windows they had;
+ * dql_ensemble_set_level empties all of them.  The first call with n >= 1 allocates them (160 B per env); creation is untouched.  They are not the plain
+ * mode's: dql_ensemble_get_nstep keeps answering 0 and zeros [n_learners] on a team ensemble, and dql_ensemble_set_nstep, _set_curriculum and
+ * _set_recipes keep their refusals.
+ * dql_ensemble_set_team_nstep: DQL_EINVAL with nothing changed for n outside 0..DQL_NSTEP_MAX, for an ensemble not made by dql_ensemble_create_teams and
+ * for a null pointer; DQL_ESTATE for a change of n while any env's window holds entries — allowed after creation and after dql_ensemble_set_level; that
+ * every team is frozen is NOT enough.  The value it already has is accepted.  (At n = 0 and n = 1 every window is empty after every period, so a change
+ * from those values is accepted at any time, in the middle of episodes included: the first windows then begin with the next decision.)
+ * A team ensemble of one env per learner may enter per-learner curriculum mode and take recipes; those modes fly the one-step learners, so they and
+ * team_nstep >= 1 refuse each other with DQL_EINVAL and nothing changed: dql_ensemble_set_curriculum with advance_every > 0 and dql_ensemble_set_recipes with
+ * n_recipes > 0 while team_nstep >= 1, and dql_ensemble_set_team_nstep with n >= 1 while curriculum mode is on or recipes are installed.
+ * dql_ensemble_get_team_nstep returns n and, where asked for, the windows' lengths, int32 [n_learners * E] in env order. */
+int dql_ensemble_set_team_nstep(dql_ensemble* ens, int32_t n);
+int dql_ensemble_get_team_nstep(dql_ensemble* ens, int32_t* n, int32_t* pending_len_or_null);
+
 #ifdef __cplusplus
 }
 #endif

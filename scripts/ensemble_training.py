@@ -4,7 +4,7 @@ one learner per GPU lane (dql_multirotor_landing_amd/ensemble.py).
 
     python scripts/ensemble_training.py --learners 4096 --seed 42 [--launched] [--levels 5] [--episodes 50000] [--score ENVS] --out run.npz
                                         [--per-learner [--advance-every E] [--drop-exhausted] [--max-periods N]] [--recipes FILE.json]
-                                        [--envs-per-learner E] [--score-map] [--preset reference|paper]
+                                        [--envs-per-learner E [--team-nstep N]] [--score-map] [--preset reference|paper]
                                         [--score-grid FIELD=v1,v2,... [--score-grid ...]]
 
 --launched: the parameters the reference's manager node ran with under roslaunch (config.as_launched_config) instead of the launch file's.
@@ -33,6 +33,9 @@ scenario it is; the .npz gains `grid_touchdown_rate` [scenarios, learners] and `
 --envs-per-learner E: every learner owns a team of E envs (1, 2, 4, ..., 64) and applies the reference's update to their transitions in env order (DESIGN.md
 section 17), so it collects E episodes in the time of one; --learners times E is at most 2^20.  Teams fly the level-by-level driver only: the flag is refused
 together with --per-learner and --recipes.
+--team-nstep N (with --envs-per-learner above 1): the team learners update with the uncorrected N-step Double-Q return, 1..16, one pending window per env, the
+E transitions of a period still taken in env order (SequentialEnsemble.set_team_nstep); 0, the default, is the one-step team update.
+Refused together with --nstep, --per-learner and --recipes; N is recorded in the .npz as `team_nstep`.
 Writes every learner's tables and, per level, its first-promotion episode (-1: the episode budget ran out first); with --per-learner also each learner's level,
 the episodes it spent at each level and the period index at which it entered it."""
 import argparse
@@ -233,6 +236,7 @@ def main():
     ap.add_argument("--score-grid", action="append", default=[], metavar="FIELD=v1,v2,...", help="with --score: also score every learner over this grid of scenarios in one launch (repeatable)")
     ap.add_argument("--preset", default="reference", choices=["reference", "paper"], help="quirks and transfer order of the level-by-level driver (not with --per-learner / --recipes)")
     ap.add_argument("--nstep", type=int, default=0, metavar="N", help="n-step Double-Q targets, 1..16 (0: the reference's one-step update; not with --per-learner / --recipes / --envs-per-learner above 1; with --recipes give each recipe its own \"nstep\" in the file)")
+    ap.add_argument("--team-nstep", type=int, default=0, metavar="N", help="with --envs-per-learner above 1: n-step Double-Q targets for the team learners, 1..16, one pending window per env (0: the one-step team update; not with --nstep / --per-learner / --recipes)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     if a.preset != "reference" and (a.per_learner or a.recipes):
@@ -249,12 +253,23 @@ def main():
         ap.error("--envs-per-learner above 1 cannot be combined with --per-learner or --recipes: teams fly the level-by-level (barrier) driver only")
     if not 0 <= a.nstep <= NSTEP_MAX:
         ap.error(f"--nstep must be in 0..{NSTEP_MAX}")
+    if a.team_nstep and a.nstep:
+        ap.error("--team-nstep cannot be combined with --nstep: --nstep is the plain ensemble's switch (one env per learner), --team-nstep the team ensemble's")
     if a.nstep and (a.per_learner or a.recipes or a.envs_per_learner > 1):
         ap.error("--nstep cannot be combined with --per-learner, --recipes or --envs-per-learner above 1: n-step targets fly the level-by-level (barrier) driver with one env per learner only")
+    if not 0 <= a.team_nstep <= NSTEP_MAX:
+        ap.error(f"--team-nstep must be in 0..{NSTEP_MAX}")
+    if a.team_nstep and a.per_learner:
+        ap.error("--team-nstep cannot be combined with --per-learner: teams fly the level-by-level (barrier) driver only")
+    if a.team_nstep and a.recipes:
+        ap.error("--team-nstep cannot be combined with --recipes: teams fly the level-by-level (barrier) driver only; give each recipe its own \"nstep\" in the file instead")
+    if a.team_nstep and a.envs_per_learner < 2:
+        ap.error("--team-nstep needs a team ensemble: give --envs-per-learner above 1 (with one env per learner use --nstep)")
     dtype = F64 if a.f64 else F32
     quirks = evaluation.Q_PAPER if a.preset == "paper" else Q_REFERENCE
     cfg = as_launched_config(dtype=dtype, quirks=quirks) if a.launched else training_config(0, dtype=dtype, quirks=quirks)
-    ens = SequentialEnsemble(cfg, a.learners, seed=a.seed, device=a.device, max_episodes=a.episodes, envs_per_learner=a.envs_per_learner, nstep=a.nstep)
+    ens = SequentialEnsemble(cfg, a.learners, seed=a.seed, device=a.device, max_episodes=a.episodes, envs_per_learner=a.envs_per_learner, nstep=a.nstep,
+                             team_nstep=a.team_nstep)
     try:
         def report(e, h):
             p = h["promotion_episode"]
@@ -306,7 +321,7 @@ def main():
             if a.score_json:
                 Path(a.score_json).write_text(json.dumps(rep) + "\n")
         qa, qb, cnt = ens.get_tables()
-        np.savez_compressed(a.out, Q_table_a=qa, Q_table_b=qb, state_action_counter=cnt, nstep=np.int32(a.nstep), **extra,
+        np.savez_compressed(a.out, Q_table_a=qa, Q_table_b=qb, state_action_counter=cnt, nstep=np.int32(a.nstep), team_nstep=np.int32(a.team_nstep), **extra,
                             promotion_episode=np.stack([h["promotion_episode"] for h in hist]), periods=np.array([h["periods"] for h in hist]))
     finally:
         ens.close()
