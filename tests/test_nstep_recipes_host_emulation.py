@@ -25,8 +25,9 @@ N = rc.N_SMALL
 emu = heh.emu_fixture("nstep_recipes_emu")
 
 
-def run_emu(exe, tmp, runs, nsteps, n=N, dtype=F32, sanitized=False, recipes=None, recipe_of=None):
-    cfg = rc.case_config(dtype)
+def run_emu(exe, tmp, runs, nsteps, n=N, dtype=F32, sanitized=False, recipes=None, recipe_of=None, cfg=None):
+    """cfg: the config of the starting level (default: the case's)"""
+    cfg = rc.case_config(dtype) if cfg is None else cfg
     recipes = nr.case_recipes(nsteps, dtype) if recipes is None else recipes
     of = rc.case_recipe_of(n) if recipe_of is None else np.asarray(recipe_of, np.int32)
     cb = bytes(cfg.to_c())
