@@ -21,6 +21,10 @@ struct LevelSched {
   const uint32_t* eps_tab; int n_eps;
   int window, min_successes, max_episodes;
 };
+// what a wave on one level flies by: the learning rates (the ensemble's, or a recipe's) with the level's exploration table and freeze rules
+DQL_DEV LearnSched learn_sched(const double* alpha_tab, int n_alpha, double alpha_min, const LevelSched DQL_CONST_AS* lv) {
+  return LearnSched{alpha_tab, n_alpha, alpha_min, lv->eps_tab, lv->n_eps, lv->window, lv->min_successes, lv->max_episodes};
+}
 
 // per-learner curriculum state, indexed by the learner l in [0, n); the history by [level][l]
 struct AdvanceMem {

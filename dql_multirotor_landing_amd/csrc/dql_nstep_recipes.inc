@@ -39,26 +39,16 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
     __syncthreads();
   }
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
-  const LevelSched DQL_CONST_AS* lv = rs->lv + level;
-  const LearnSched sc{rs->alpha_tab, rs->n_alpha, rs->alpha_min, lv->eps_tab, lv->n_eps, lv->window, lv->min_successes, lv->max_episodes};
+  const LearnSched sc = learn_sched(rs->alpha_tab, rs->n_alpha, rs->alpha_min, rs->lv + level);
   const bool active = l >= 0 && l < a.mem.n;
   // the Philox key schedule (float32: in VGPRs, as in k_learn) is made once per body: one array read by both bodies stays in private memory
-  const auto key_schedule = [&](uint32_t (&kv_)[20]) -> const uint32_t* {
-    if constexpr (sizeof(T) == 4) {
-#pragma unroll
-      for (int q = 0; q < 10; ++q) { kv_[q] = to_vgpr((uint32_t)a.seed + (uint32_t)q * 0x9E3779B9u); kv_[10 + q] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)q * 0xBB67AE85u); }
-      return kv_;
-    } else {
-      return nullptr;
-    }
-  };
   if (nstep == 0) {
     uint32_t kv_[20];
-    const uint32_t* kv = key_schedule(kv_);
+    const uint32_t* kv = learner_round_keys<T>(a.seed, kv_);
     learner_periods<TICK, XMODE>(cl, cfgk, tc, a.mdp + (r * DQL_MAX_LEVELS + level), a.mdp_run, sc, a.mem, a.sr, a.si, a.seed, l, active, a.j0, a.n_periods, a.mgr0, a.tick_sched, kv);
   } else {
     uint32_t kv_[20];
-    const uint32_t* kv = key_schedule(kv_);
+    const uint32_t* kv = learner_round_keys<T>(a.seed, kv_);
     learner_periods_nstep<TICK, XMODE>(cl, cfgk, tc, a.mdp + (r * DQL_MAX_LEVELS + level), a.mdp_run, sc, a.mem, a.sr, a.si, a.seed, l, active, a.j0, a.n_periods, a.mgr0,
                                        a.tick_sched, kv, nstep, LdsWindow{sKey + tid, sVal + tid}, h.nm);
   }

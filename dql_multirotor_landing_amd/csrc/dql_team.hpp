@@ -8,21 +8,22 @@
 //                     a row carried in registers would miss what a team-mate wrote —, then agent_period<TICK, XMODE> in MODE_TRAIN, then the transition
 //                     as a TeamRecord.  The tables are only read here.
 //   team_apply        per team (one lane): the E records in env order through learner_update (dql_learner.hpp, unchanged).  The row of s' is read from the
-//                     tables as they stand at that moment, so after the updates of envs < e of this period; then the episode bookkeeping of learner_periods,
-//                     except that a level once decided in a period takes no further outcome into its ring in that period (totals and log only).
+//                     tables as they stand at that moment, so after the updates of envs < e of this period; then the episode's end in the learner's books
+//                     (LearnerBooks of dql_learner.hpp, which this file only uses: team_episode), except that a level once decided in a period takes no
+//                     further outcome into its ring in that period (totals and log only).
 //
 // With E = 1 the two parts are learner_periods operation for operation: its carried row patched with q_new is the row of the updated tables.
 //
 // Between the two parts the records cross lanes, and the tables written by the applying lane are read by its team-mates in the next period.  That exchange
-// and the ordering live in the kernel (dql_teams.inc: k_learn_team), not here: the host emulation (tests/host_emu/team_emu.cpp) calls the two parts for one
-// lane after the other, where program order does both.  On the device a team is E consecutive lanes of a one-wave workgroup, and k_learn_team puts a
-// __syncthreads() between the parts and another after team_apply.  __syncthreads() is a workgroup-scope release fence, the barrier, and a workgroup-scope
+// and the ordering live in team_wave (dql_team_nstep.hpp: what k_learn_team and k_learn_team_nstep run below their declarations), not here: the host
+// emulation (tests/host_emu/team_emu.cpp) calls the two parts for one lane after the other, where program order does both.  On the device a team is E
+// consecutive lanes of a one-wave workgroup, and team_wave puts a __syncthreads() between the parts and another after team_apply.  __syncthreads() is a workgroup-scope release fence, the barrier, and a workgroup-scope
 // acquire fence.  The release makes the applying lane's wave wait for its stores (s_waitcnt vmcnt(0): they have reached the CU's write-through vector L1 and
 // the L2 behind it), the acquire keeps every later load behind it; writer and readers are lanes of ONE wave, hence of one CU and one vector L1, which is the
 // situation workgroup scope is defined for.  No other workgroup ever touches a learner's slices during a launch, so no wider scope is needed.  The records
 // travel through LDS under the same two barriers.
 //
-// The loop of k_learn_team runs n_periods <= LEARN_MAX_PERIODS times at most on every path.  Include after dql_learner.hpp.
+// The loop of team_wave runs n_periods <= LEARN_MAX_PERIODS times at most on every path.  Include after dql_learner.hpp.
 #pragma once
 #include "dql_learner.hpp"
 
@@ -41,26 +42,13 @@ struct TeamRecord {
   int step_count;   // the episode's length so far (logged when it ended)
 };
 
-// a learner's counters while a launch holds them in the applying lane's registers
-struct TeamState {
-  unsigned long long decisions, w0, w1;
-  int episodes, successes, lvl_eps, win_count, promoted, log_n;
-  uint32_t eps_thr;  // of the period to come: eps_tab[min(lvl_eps, n_eps - 1)], the same for all E envs
-  bool live;
-};
-DQL_DEV TeamState team_load(const LearnSched& sc, const LearnMem& mem, long long l) {
-  TeamState t;
-  t.decisions = mem.decisions[l]; t.episodes = mem.episodes[l]; t.successes = mem.successes[l]; t.lvl_eps = mem.level_episodes[l]; t.win_count = mem.win_count[l];
-  t.w0 = mem.win_bits[l]; t.w1 = mem.win_bits[mem.n + l]; t.promoted = mem.promoted[l]; t.log_n = mem.log_n[l];
-  t.eps_thr = sc.eps_tab[t.lvl_eps < sc.n_eps ? t.lvl_eps : sc.n_eps - 1];
-  t.live = mem.frozen[l] == 0;
-  return t;
-}
-DQL_DEV void team_store(const TeamState& t, const LearnMem& mem, long long l) {
-  mem.decisions[l] = t.decisions; mem.episodes[l] = t.episodes; mem.successes[l] = t.successes; mem.level_episodes[l] = t.lvl_eps; mem.win_count[l] = t.win_count;
-  mem.win_bits[l] = t.w0; mem.win_bits[mem.n + l] = t.w1; mem.promoted[l] = t.promoted; mem.log_n[l] = t.log_n;
-  mem.frozen[l] = t.live ? 0 : 1;
-}
+// A team's name for its learner's books (dql_learner.hpp) while the applying lane holds them in registers: the wave body and the host emulations of the team
+// kernels load and store them under these names.  Nothing of the books is stated here.
+using TeamState = LearnerBooks;
+DQL_DEV TeamState team_load(const LearnSched& sc, const LearnMem& mem, long long l) { return books_load(sc, mem, l); }
+DQL_DEV void team_store(const TeamState& t, const LearnMem& mem, long long l) { books_store(t, mem, l); }
+// what the applying lane of a team tells its team-mates about the period to come
+struct TeamCtl { uint32_t eps_thr; int live; };
 
 // One agent period of env g (the arguments are learner_periods').  qa / qb: the learner's slices, read only.  j: the period's index; mgr0 / sched: its tick schedule.
 template <int TICK, int XMODE, typename T>
@@ -79,10 +67,17 @@ DQL_DEV TeamRecord team_env_period(const SimK<T>& c, const SimK<T>& cfgk, const 
   return r;
 }
 
+// The end of the episode record r reports, in the learner's books (dql_learner.hpp): the totals and the log always, the outcome into the ring only while the
+// level is undecided in this period — an episode a team-mate finishes after the decision counts in the totals and the log only.
+DQL_DEV void team_episode(const LearnSched& sc, const LearnMem& mem, long long l, const TeamRecord& r, LearnerBooks& t, bool& decided) {
+  const int won = books_episode(t, mem, l, (r.what >> 8) & 0xff, r.step_count);
+  if (!decided) decided = books_ring_push(t, sc, won);
+}
+
 // The serial section: the E records of learner l's period in env order, on the learner's own pointers (one thread's program order).  t.eps_thr leaves as the
 // next period's threshold; t.live leaves false when the level was decided in this period — after ALL E updates.
 template <typename RecPtr>
-DQL_DEV void team_apply(const LearnSched& sc, const LearnMem& mem, uint32_t quirks, double gamma, long long l, RecPtr rec, int n_envs, TeamState& t) {
+DQL_DEV void team_apply(const LearnSched& sc, const LearnMem& mem, uint32_t quirks, double gamma, long long l, RecPtr rec, int n_envs, LearnerBooks& t) {
   double* qa = mem.qa + l * DQL_N_CELLS;
   double* qb = mem.qb + l * DQL_N_CELLS;
   double* count = mem.count + l * DQL_N_CELLS;
@@ -101,28 +96,10 @@ DQL_DEV void team_apply(const LearnSched& sc, const LearnMem& mem, uint32_t quir
       ok = learner_update(qa, qb, count, sc, quirks, gamma, sa, coin, next, r.reward, (r.what & TEAM_MASK) ? 1 : 0, q_new, sel_b);
     }
     if (!ok) mem.faults[0] += 1ull;  // never taken unless a bug: a plain (racy) count is enough to make the tests fail
-    if (r.what & TEAM_DONE) {
-      const int code = (r.what >> 8) & 0xff;
-      const int won = code == DQL_TERMINAL_SUCCESS ? 1 : 0;
-      ++t.episodes; t.successes += won;
-      if ((unsigned)code < (unsigned)DQL_N_CHECK_CODES) mem.by_code[(long long)code * mem.n + l] += 1ull;
-      if (t.log_n < mem.log_cap) { mem.log_code[l * mem.log_cap + t.log_n] = (uint8_t)code; mem.log_len[l * mem.log_cap + t.log_n] = (uint16_t)r.step_count; }
-      ++t.log_n;
-      if (!decided) {  // the ring of learner_periods; an episode a team-mate finishes after the decision counts in the totals and the log only
-        const int pos = t.lvl_eps % sc.window;
-        const unsigned long long bit = 1ull << (pos & 63);
-        unsigned long long w = pos >= 64 ? t.w1 : t.w0;
-        t.win_count += won - ((w & bit) ? 1 : 0);
-        w = won ? (w | bit) : (w & ~bit);
-        if (pos >= 64) t.w1 = w; else t.w0 = w;
-        ++t.lvl_eps;
-        if (t.win_count >= sc.min_successes) { t.promoted = t.lvl_eps; decided = true; }
-        else if (t.lvl_eps >= sc.max_episodes) decided = true;
-      }
-    }
+    if (r.what & TEAM_DONE) team_episode(sc, mem, l, r, t, decided);
   }
   if (decided) t.live = false;
-  t.eps_thr = sc.eps_tab[t.lvl_eps < sc.n_eps ? t.lvl_eps : sc.n_eps - 1];
+  t.eps_thr = eps_of_episode(sc, t.lvl_eps);
 }
 
 }  // namespace dql

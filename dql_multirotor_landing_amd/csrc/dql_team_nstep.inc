@@ -1,18 +1,11 @@
 // dql_team_nstep.inc: team learners with n-step Double-Q targets, one pending window per env (include/dql.h dql_ensemble_set_team_nstep / _get_team_nstep,
-// DESIGN.md section 24): the kernel and the two C calls.  A fragment of dql_hip.hip's translation unit, not a header, included after dql_teams.inc (TeamArgs,
-// TeamCtl) and dql_nstep.inc (NstepDev).  The per-team body is csrc/dql_team_nstep.hpp's team_apply_nstep; the per-env body is dql_team.hpp's, unchanged.
+// DESIGN.md section 24): the kernel and the two C calls.  A fragment of dql_hip.hip's translation unit, not a header, included after dql_teams.inc (TeamArgs)
+// and dql_nstep.inc (NstepDev).  The per-team body is csrc/dql_team_nstep.hpp's team_apply_nstep; the per-env body is dql_team.hpp's, unchanged.
 // k_learn_team's shape: workgroups of one wave, lane = env g, a team is E consecutive lanes, two __syncthreads() per period.  Added: the windows of the wave's
 // 64 envs in LDS for the launch, [slot][lane] as in k_learn_nstep (16 x 64 x 10 B), and their heads and lengths [lane] — the applying lane cannot hold those of
 // 64 envs in registers.  A lane loads its env's window before the first barrier of the launch and stores it beside store_env, after the last; in between only
 // the team's applying lane touches the team's columns, between the two barriers of a period.  The windows of a team frozen at the launch's start are neither
-// loaded nor stored.
-struct LdsTeamWindow {
-  uint16_t* k; double* v; int* h; int* n;  // column 0 of the team (its first lane): env e of the team is column e
-  DQL_DEV uint16_t& key(int e, int slot) const { return k[slot * 64 + e]; }
-  DQL_DEV double& val(int e, int slot) const { return v[slot * 64 + e]; }
-  DQL_DEV int& head(int e) const { return h[e]; }
-  DQL_DEV int& len(int e) const { return n[e]; }
-};
+// loaded nor stored.  All of that is team_wave's (csrc/dql_team_nstep.hpp, with its LdsTeamWindow); the kernel is the wave prologue and the LDS.
 template <typename T> struct TeamNstepArgs {
   TeamArgs<T> t;
   NstepDev tm;  // the persistent windows: key / val [DQL_NSTEP_MAX][n_envs], len [n_envs]
@@ -22,10 +15,6 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   const TeamArgs<T>& t = ga.t;
   const LearnArgs<T>& a = t.a;
   const int tid = threadIdx.x;
-  const long long g = (long long)blockIdx.x * 64 + tid;
-  const bool active = g < t.n_envs;
-  const long long l = active ? (g >> t.team_shift) : 0;  // < a.mem.n
-  const int lead = tid & ~(t.envs_per_learner - 1);      // the team's first lane: the one that applies
   SimK<T> cl = a.c;
   if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
   SimK<T> cfgk = cl;
@@ -43,46 +32,9 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   }
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
   uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
-  const double* qa = a.mem.qa + l * DQL_N_CELLS;
-  const double* qb = a.mem.qb + l * DQL_N_CELLS;
-  const bool applies = active && tid == lead;
-  TeamState ts = TeamState{};
-  if (applies) ts = team_load(a.sched, a.mem, l);
-  bool live = active && a.mem.frozen[l] == 0;
-  uint32_t eps_thr = live ? a.sched.eps_tab[a.mem.level_episodes[l] < a.sched.n_eps ? a.mem.level_episodes[l] : a.sched.n_eps - 1] : 0u;
-  const bool loaded = live;
-  Env<T> e = Env<T>{};
+  const uint32_t* kv = learner_round_keys<T>(a.seed, kv_);
   const LdsTeamWindow mine{sKey + tid, sVal + tid, sHead + tid, sLen + tid};  // this lane's own column: env 0 of it
-  sHead[tid] = 0; sLen[tid] = 0;
-  if (live) {
-    load_env(e, a.sr, a.si[g], t.n_envs, g, cl);
-    team_window_load(ga.tm, t.n_envs, g, 0, ga.nstep, mine);  // read by the applying lane behind the period's first barrier
-  }
-  const int np = a.n_periods < LEARN_MAX_PERIODS ? a.n_periods : LEARN_MAX_PERIODS;
-  for (int p = 0; p < np; ++p) {
-    TeamRecord r{0.0, -1, 0, 0, 0};
-    if (live) r = team_env_period<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, e, qa, qb, eps_thr, a.seed, g, a.j0 + p, a.mgr0[p], a.tick_sched[p], kv);
-    sRec[tid] = r;
-    __syncthreads();  // the records (and, in the first period, the windows) are in LDS; every row load of this period lies before the first table write of it
-    if (applies && live) {
-      team_apply_nstep(a.sched, a.mem, cl.quirks, a.mdp_run.gamma, l, &sRec[tid], t.envs_per_learner, ga.nstep, mine, ts);  // `mine` of the first lane: the team's columns
-      sCtl[tid] = TeamCtl{ts.eps_thr, ts.live ? 1 : 0};
-    }
-    __syncthreads();  // workgroup-scope release of the applying lanes' table stores and window writes, acquire in front of the next period's row loads (dql_team.hpp)
-    if (live) { const TeamCtl ctl = sCtl[lead]; eps_thr = ctl.eps_thr; live = ctl.live != 0; }
-    if (__ballot(live) == 0ull) break;
-  }
-  if (loaded) {
-    store_env(e, a.sr, a.si, t.n_envs, g, cl);
-    team_window_store(ga.tm, t.n_envs, g, 0, ga.nstep, mine);  // behind the last period's second barrier
-  }
-  if (applies && loaded) team_store(ts, a.mem, l);
+  team_wave<XMODE>(t, cl, cfgk, tc, kv, tid, sRec, sCtl, TeamWindows<NstepDev>{mine, ga.tm, ga.nstep});
 }
 template <typename T> static void launch_learn_team_nstep(dql_ensemble* x, int k, int n_waves) {
   TeamNstepArgs<T> g;

@@ -6,18 +6,10 @@ template <typename T> struct TeamArgs {
   long long n_envs;    // a.mem.n * envs_per_learner: the stride of the state arrays
   int envs_per_learner, team_shift;  // E = 1 << team_shift, a divisor of 64
 };
-// what the applying lane of a team tells its team-mates about the period to come
-struct TeamCtl { uint32_t eps_thr; int live; };
-// Workgroups of one wave; lane = env g; a team is E consecutive lanes, so no team straddles waves and the last wave may hold fewer teams.  Per period: every
-// live lane flies its env and leaves its record in LDS; barrier; the first lane of every live team applies the team's E records in order and publishes the next
-// period's threshold and whether the team flies on; barrier.  All teams of a wave run side by side.  The wave leaves when every team in it is frozen.
+// The wave prologue and the LDS of a team wave; what the wave does is team_wave's (csrc/dql_team_nstep.hpp), here without windows.
 template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_learn_team(TeamArgs<T> t) {
   const LearnArgs<T>& a = t.a;
   const int tid = threadIdx.x;
-  const long long g = (long long)blockIdx.x * 64 + tid;
-  const bool active = g < t.n_envs;
-  const long long l = active ? (g >> t.team_shift) : 0;  // < a.mem.n
-  const int lead = tid & ~(t.envs_per_learner - 1);      // the team's first lane: the one that applies
   SimK<T> cl = a.c;
   if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
   SimK<T> cfgk = cl;
@@ -31,38 +23,8 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   }
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
   uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
-  const double* qa = a.mem.qa + l * DQL_N_CELLS;
-  const double* qb = a.mem.qb + l * DQL_N_CELLS;
-  const bool applies = active && tid == lead;
-  TeamState ts = TeamState{};
-  if (applies) ts = team_load(a.sched, a.mem, l);
-  bool live = active && a.mem.frozen[l] == 0;
-  uint32_t eps_thr = live ? a.sched.eps_tab[a.mem.level_episodes[l] < a.sched.n_eps ? a.mem.level_episodes[l] : a.sched.n_eps - 1] : 0u;
-  const bool loaded = live;
-  Env<T> e = Env<T>{};
-  if (live) load_env(e, a.sr, a.si[g], t.n_envs, g, cl);
-  const int np = a.n_periods < LEARN_MAX_PERIODS ? a.n_periods : LEARN_MAX_PERIODS;
-  for (int p = 0; p < np; ++p) {
-    TeamRecord r{0.0, -1, 0, 0, 0};
-    if (live) r = team_env_period<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, e, qa, qb, eps_thr, a.seed, g, a.j0 + p, a.mgr0[p], a.tick_sched[p], kv);
-    sRec[tid] = r;
-    __syncthreads();  // the records are in LDS; every row load of this period lies before the first table write of it
-    if (applies && live) {
-      team_apply(a.sched, a.mem, cl.quirks, a.mdp_run.gamma, l, &sRec[tid], t.envs_per_learner, ts);
-      sCtl[tid] = TeamCtl{ts.eps_thr, ts.live ? 1 : 0};
-    }
-    __syncthreads();  // workgroup-scope release of the applying lanes' table stores, acquire in front of the next period's row loads (dql_team.hpp)
-    if (live) { const TeamCtl ctl = sCtl[lead]; eps_thr = ctl.eps_thr; live = ctl.live != 0; }
-    if (__ballot(live) == 0ull) break;
-  }
-  if (loaded) store_env(e, a.sr, a.si, t.n_envs, g, cl);
-  if (applies && loaded) team_store(ts, a.mem, l);
+  const uint32_t* kv = learner_round_keys<T>(a.seed, kv_);
+  team_wave<XMODE>(t, cl, cfgk, tc, kv, tid, sRec, sCtl, NoTeamWindows{});
 }
 template <typename T> static void launch_learn_team(dql_ensemble* x, int k, int n_waves) {
   TeamArgs<T> g;

@@ -115,7 +115,7 @@ template <typename T> int launch(Job& j, const char* out_path) {
         cl.working = k;
         cl.two_axis = 0;
         const emu::Launch<T, TICK_PLAIN> lc(cl, j.seed);
-        const LearnSched sc{j.alpha.data(), j.n_alpha, cfg.alpha_min, lv[k].eps_tab, lv[k].n_eps, lv[k].window, lv[k].min_successes, lv[k].max_episodes};
+        const LearnSched sc = learn_sched(j.alpha.data(), j.n_alpha, cfg.alpha_min, (const LevelSched DQL_CONST_AS*)&lv[k]);
         const MdpK<T> DQL_CONST_AS* mdp = (const MdpK<T> DQL_CONST_AS*)&mdpk5[k];
         for (int lane = 0; lane < ADV_WAVE; ++lane) {
           const long long l = worklist[(size_t)w * ADV_WAVE + (size_t)lane];

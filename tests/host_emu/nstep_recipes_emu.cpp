@@ -177,8 +177,7 @@ template <typename T> int launch(Job& j, const char* out_path) {
         cl.quirks = rs[(size_t)r].quirks;
         cl.two_axis = 0;
         const emu::Launch<T, TICK_PLAIN> lc(cl, j.seed);
-        const LevelSched& lv = rs[(size_t)r].lv[k];
-        const LearnSched sc{rs[(size_t)r].alpha_tab, rs[(size_t)r].n_alpha, rs[(size_t)r].alpha_min, lv.eps_tab, lv.n_eps, lv.window, lv.min_successes, lv.max_episodes};
+        const LearnSched sc = learn_sched(rs[(size_t)r].alpha_tab, rs[(size_t)r].n_alpha, rs[(size_t)r].alpha_min, (const LevelSched DQL_CONST_AS*)&rs[(size_t)r].lv[k]);
         const MdpK<T> DQL_CONST_AS* mdp = (const MdpK<T> DQL_CONST_AS*)&mdpk[(size_t)r * ADV_MAX_LEVELS + (size_t)k];
         lds_key.assign(lds_key.size(), (uint16_t)0xffffu); lds_val.assign(lds_val.size(), std::nan(""));
         for (int lane = 0; lane < ADV_WAVE; ++lane) {
