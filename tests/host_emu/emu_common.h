@@ -1,6 +1,6 @@
-// emu_common.h — what the five drivers (step_emu, rollout_emu, score_emu, learner_emu, advance_emu) share, included after host_shim.h and the device
-// headers: the job and result files, the per-launch prologue every kernel begins with, the packed state arrays, the checked acting table, and (for the two
-// learner drivers, which define DQL_EMU_LEARNERS first) the learners' state.  A driver keeps its Job and its launch loop: the part that restates one kernel.
+// emu_common.h — what every driver under tests/host_emu/ shares, included after host_shim.h and the device headers: the job and result files, the per-launch
+// prologue every kernel begins with, the packed state arrays and the checked acting table.  What only the drivers of the sequential-learner family share
+// (their jobs, state, windows and run loops) is emu_learners.h, which includes this file.  A driver keeps the part that restates one kernel.
 // The Python side of the same plumbing is tests/host_emu_harness.py.  Exit status 2 is a bad job or a file that cannot be written, 3 an index violation.
 #pragma once
 #include <cstdio>
@@ -91,47 +91,5 @@ struct TabRef {
     return p[k];
   }
 };
-
-#ifdef DQL_EMU_LEARNERS
-// ---- the learners of an ensemble, in arrays exactly as long as the library allocates them: the env state as k_init leaves it (c: the context's SimK, whose
-// level is the config's), the counters zeroed; mem() is the kernels' view of them with the job's tables, put() the head of both drivers' result files
-template <typename T> struct LearnerState {
-  const size_t n;
-  const int log_cap;
-  std::vector<dql::Quad<T>> sr;
-  std::vector<int4> si;
-  std::vector<unsigned long long> decisions, by_code, win_bits, faults;
-  std::vector<int> episodes, successes, lvl, win_count, promoted, frozen, log_n;
-  std::vector<uint8_t> log_code;
-  std::vector<uint16_t> log_len;
-
-  LearnerState(const dql::SimK<T>& c, const dql::RolloutInit<T>& init, size_t n_, unsigned long long seed, int log_cap_)
-      : n(n_), log_cap(log_cap_), sr((size_t)dql::NQ_REAL * n, dql::Quad<T>{T(0.0), T(0.0), T(0.0), T(0.0)}), si(n), decisions(n, 0ull),
-        by_code((size_t)DQL_N_CHECK_CODES * n, 0ull), win_bits(2 * n, 0ull), faults(1, 0ull), episodes(n, 0), successes(n, 0), lvl(n, 0), win_count(n, 0),
-        promoted(n, -1), frozen(n, 0), log_n(n, 0), log_code(n * (size_t)log_cap, 0), log_len(n * (size_t)log_cap, 0) {
-    dql::SimK<T> cl = c;
-    cl.two_axis = 0;
-    for (size_t l = 0; l < n; ++l) {
-      dql::Env<T> e; T mp_v_hbm;
-      dql::rollout_init_env(cl, init, e, (uint32_t)l, seed, mp_v_hbm);
-      sr[11 * n + l] = dql::Quad<T>{mp_v_hbm, T(0.0), T(0.0), T(1.0)};
-      sr[13 * n + l] = dql::Quad<T>{e.mp_r, e.mp_w, T(0.0), T(0.0)};
-      dql::store_env(e, sr.data(), si.data(), (long long)n, (long long)l, c);
-    }
-  }
-  dql::LearnMem mem(std::vector<double>& qa, std::vector<double>& qb, std::vector<double>& count) {
-    return dql::LearnMem{qa.data(), qb.data(), count.data(), decisions.data(), by_code.data(), episodes.data(), successes.data(), lvl.data(), win_count.data(),
-                         win_bits.data(), promoted.data(), frozen.data(), log_code.data(), log_len.data(), log_n.data(), faults.data(), (long long)n, log_cap};
-  }
-  void put(ResultFile& out, const std::vector<double>& qa, const std::vector<double>& qb, const std::vector<double>& count) const {
-    std::vector<double> reals;
-    std::vector<int32_t> ints;
-    unpack_state(sr.data(), si.data(), n, reals, ints);
-    out.put(qa); out.put(qb); out.put(count); out.put(decisions); out.put(by_code);
-    out.put(episodes); out.put(successes); out.put(lvl); out.put(promoted); out.put(frozen); out.put(log_n);
-    out.put(log_code); out.put(log_len); out.put(reals); out.put(ints); out.put(faults);
-  }
-};
-#endif
 
 }  // namespace emu

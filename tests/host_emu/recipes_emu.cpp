@@ -1,100 +1,25 @@
 // recipes_emu.cpp — dql_ensemble_run with recipes installed, emulated on the CPU from the real device source: dql_recipes.hpp's
 // build_worklist_recipes and advance_learner_recipe on top of dql_learner.hpp's learner_periods.
 //
-// The driver does what ens_run_advancing (dql_ensemble.inc) does for ens_run_recipes (dql_recipes.inc): launches cut at the multiples of advance_every; at such a period index every learner takes
-// advance_learner_recipe's step (k_ens_advance_recipes: one thread per learner); then the live learners are regrouped by (recipe, level) and flown wave by
-// wave, lane by lane, as k_learn_recipes flies them — the wave's recipe and level from wave_recipe[w] and wave_level[w], the lane's learner from the worklist
-// (-1: an inactive lane), SimK::working and SimK::quirks, the MdpK of (recipe, level), the recipe's learning rates and the level's schedules from those.  A
-// lane runs alone: __ballot(p) is p (host_shim.h).  Every array is exactly as long as the library allocates it, so the sanitized build sees any access
-// beyond them.  The learners' arrays, the per-wave prologue and the job and result files are emu_common.h's, as for advance_emu.cpp.
+// The driver does what ens_run_advancing (dql_ensemble.inc) does for ens_run_recipes (dql_recipes.inc), through emu_learners.h's RecipeRun: at an advance point
+// every learner takes advance_learner_recipe's step (k_ens_advance_recipes: one thread per learner); then the live learners are regrouped by (recipe, level)
+// and flown wave by wave, lane by lane, as k_learn_recipes flies them — the wave's recipe and level from wave_recipe[w] and wave_level[w], the lane's learner
+// from the worklist (-1: an inactive lane), SimK::working and SimK::quirks, the MdpK of (recipe, level), the recipe's learning rates and the level's schedules
+// from those.  A lane runs alone: __ballot(p) is p (host_shim.h).  Every array is exactly as long as the library allocates it, so the sanitized build sees any
+// access beyond them.  What stands here is the wave, and mode 1.
 //
-//   recipes_emu JOB OUT   run the job (see read_job; tests/test_recipes_host_emulation.py writes it), write OUT.  A job is either a run of the ensemble or one
+//   recipes_emu JOB OUT   run the job (emu::RecipeJob; tests/test_recipes_host_emulation.py writes it), write OUT.  A job is either a run of the ensemble or one
 //                         call of build_worklist_recipes on given arrays (mode 1), whose outputs are written as they are.
 #include "host_shim.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "dql_device.hpp"
-#include "dql_host_consts.hpp"
-#include "dql_rollout.hpp"
-#include "dql_learner.hpp"
-#include "dql_advance.hpp"
-#include "dql_recipes.hpp"
-#define DQL_EMU_LEARNERS
-#include "emu_common.h"
+#include "emu_learners.h"
 
 using namespace dql;
 
 namespace {
 
-struct JobRecipe {
-  uint32_t quirks;
-  int n_alpha, last_level, advance_exhausted, transfer_order;
-  int n_eps[ADV_MAX_LEVELS], window[ADV_MAX_LEVELS], min_successes[ADV_MAX_LEVELS], max_episodes[ADV_MAX_LEVELS];
-  double alpha_min, ratios[ADV_MAX_LEVELS];
-  std::vector<double> alpha, eps[ADV_MAX_LEVELS];
-};
-struct Job {
-  int mode, dtype, n_runs, runs[8], every, log_cap, n_recipes, has_tables;
-  long long n, cap_slots;
-  unsigned long long seed;
-  dql_config cfg;
-  std::vector<int> recipe_of, frozen, level;  // frozen, level: mode 1 only
-  std::vector<JobRecipe> recipes;
-  std::vector<double> qa, qb, count;  // the tables: zeros, or the job's initial ones ([L][DQL_N_CELLS] each, at the end of the job)
-};
-
-Job read_job(const char* path) {
-  emu::JobFile f(path);
-  Job j;
-  int32_t hdr[24];  // cfg size, dtype, L, n_runs, runs[8], every, log_cap, n_recipes, has_tables, mode, worklist capacity (mode 1), 0 ...
-  int64_t seed;
-  f.read(hdr, 24); f.read(&seed, 1);
-  f.read_config(j.cfg, hdr[0]);
-  j.dtype = hdr[1]; j.n = hdr[2]; j.n_runs = hdr[3];
-  for (int k = 0; k < 8; ++k) j.runs[k] = hdr[4 + k];
-  j.seed = (unsigned long long)seed;
-  j.every = hdr[12]; j.log_cap = hdr[13]; j.n_recipes = hdr[14]; j.has_tables = hdr[15]; j.mode = hdr[16]; j.cap_slots = hdr[17];
-  if (j.n < 1 || (j.mode != 0 && j.mode != 1)) emu::bad_job();
-  j.recipe_of.resize((size_t)j.n);
-  f.read(j.recipe_of);
-  if (j.mode == 1) {  // (any n_recipes and any indices: the faults are what is looked at)
-    if (j.cap_slots < 0) emu::bad_job();
-    j.frozen.resize((size_t)j.n); j.level.resize((size_t)j.n);
-    f.read(j.frozen); f.read(j.level);
-    return j;
-  }
-  bool ok = j.n_runs >= 1 && j.n_runs <= 8 && j.every >= 1 && j.every <= ADV_MAX_EVERY && j.log_cap >= 1 && j.n_recipes >= 1 && j.n_recipes <= RCP_MAX && !j.cfg.two_axis &&
-            j.cfg.trajectory != DQL_TRAJ_EIGHT;
-  for (int k = 0; ok && k < j.n_runs; ++k) ok = j.runs[k] >= 1;
-  for (size_t l = 0; ok && l < (size_t)j.n; ++l) ok = j.recipe_of[l] >= 0 && j.recipe_of[l] < j.n_recipes;
-  if (!ok) emu::bad_job();
-  j.recipes.resize((size_t)j.n_recipes);
-  for (JobRecipe& r : j.recipes) {
-    int32_t h[28];  // quirks, n_alpha, last_level, advance_exhausted, transfer_order, 0, 0, 0, then per level {n_eps, window, min_successes, max_episodes}
-    f.read(h, 28);
-    r.quirks = (uint32_t)h[0]; r.n_alpha = h[1]; r.last_level = h[2]; r.advance_exhausted = h[3]; r.transfer_order = h[4];
-    ok = r.n_alpha >= 1 && r.last_level >= j.cfg.working_curriculum_step && r.last_level < ADV_MAX_LEVELS && (r.transfer_order == 0 || r.transfer_order == 1);
-    for (int k = 0; k < ADV_MAX_LEVELS; ++k) {
-      r.n_eps[k] = h[8 + 4 * k]; r.window[k] = h[9 + 4 * k]; r.min_successes[k] = h[10 + 4 * k]; r.max_episodes[k] = h[11 + 4 * k];
-      ok = ok && r.n_eps[k] >= 1 && r.window[k] >= 1 && r.window[k] <= LEARN_MAX_WINDOW && r.min_successes[k] >= 1 && r.max_episodes[k] >= 1;
-    }
-    if (!ok) emu::bad_job();
-    f.read(&r.alpha_min, 1); f.read(r.ratios, ADV_MAX_LEVELS);
-    r.alpha.resize((size_t)r.n_alpha);
-    f.read(r.alpha);
-    for (int k = 0; k < ADV_MAX_LEVELS; ++k) { r.eps[k].resize((size_t)r.n_eps[k]); f.read(r.eps[k]); }
-  }
-  const size_t TB = (size_t)j.n * DQL_N_CELLS;
-  j.qa.assign(TB, 0.0); j.qb.assign(TB, 0.0); j.count.assign(TB, 0.0);
-  if (j.has_tables) { f.read(j.qa); f.read(j.qb); f.read(j.count); }
-  return j;
-}
-
 // one call of build_worklist_recipes: the arrays as long as the capacity says, written whole (slots beyond the returned waves stay at the fill value -2)
-int worklist_only(Job& j, const char* out_path) {
+int worklist_only(emu::RecipeJob& j, const char* out_path) {
   const size_t slots = (size_t)j.cap_slots, waves = slots / ADV_WAVE;
   std::vector<int> worklist(slots, -2), wave_recipe(waves, -2), wave_level(waves, -2);
   unsigned long long faults = 0ull;
@@ -106,86 +31,30 @@ int worklist_only(Job& j, const char* out_path) {
   return f.close();
 }
 
-template <typename T> int launch(Job& j, const char* out_path) {
-  const dql_config& cfg = j.cfg;
-  const size_t n = (size_t)j.n, R = (size_t)j.n_recipes;
-  const SimK<T> c = make_simk<T>(cfg);
-  std::vector<MdpK<T>> mdpk(R * ADV_MAX_LEVELS);  // [R][5]: the config with the recipe's quirks and working = k (dql_ensemble_set_recipe)
-  std::vector<std::vector<uint32_t>> thr(R * ADV_MAX_LEVELS);
-  std::vector<RecipeSched> rs(R);
-  std::vector<RecipeRule> rules(R);
-  for (size_t r = 0; r < R; ++r) {
-    const JobRecipe& q = j.recipes[r];
-    rs[r].alpha_tab = q.alpha.data(); rs[r].n_alpha = q.n_alpha; rs[r].quirks = q.quirks; rs[r].alpha_min = q.alpha_min;
-    for (int k = 0; k < ADV_MAX_LEVELS; ++k) {
-      dql_config ck = cfg; ck.quirks = q.quirks; ck.working_curriculum_step = k;
-      mdpk[r * ADV_MAX_LEVELS + (size_t)k] = make_mdpk<T>(ck);
-      std::vector<uint32_t>& t = thr[r * ADV_MAX_LEVELS + (size_t)k];
-      t.resize((size_t)q.n_eps[k]);
-      for (int i = 0; i < q.n_eps[k]; ++i) t[(size_t)i] = eps_threshold(q.eps[k][(size_t)i]);
-      rs[r].lv[k] = LevelSched{t.data(), q.n_eps[k], q.window[k], q.min_successes[k], q.max_episodes[k]};
-      rules[r].rule.ratios[k] = q.ratios[k];
+template <typename T> int launch(emu::RecipeJob& j, const char* out_path) {
+  emu::RecipeRun<T> run(j);
+  emu::LearnerState<T>& st = run.st;
+  run.fly([&](int w, long long j0, int np, const long long* mgr0, const int* sched) {
+    const int r = run.wave_recipe[(size_t)w], lvl = run.wave_level[(size_t)w];
+    if ((unsigned)r >= (unsigned)j.n_recipes || (unsigned)lvl >= (unsigned)ADV_MAX_LEVELS) { st.faults[0] += 1ull; return; }
+    const RecipeSched& rs = run.tab.rs[(size_t)r];
+    const SimK<T> cl = run.k.simk(lvl, rs.quirks);
+    const emu::Launch<T, TICK_PLAIN> lc(cl, j.seed);
+    const LearnSched sc = learn_sched(rs.alpha_tab, rs.n_alpha, rs.alpha_min, (const LevelSched DQL_CONST_AS*)&rs.lv[lvl]);
+    const MdpK<T> DQL_CONST_AS* mdp = (const MdpK<T> DQL_CONST_AS*)&run.tab.mdpk[(size_t)r * ADV_MAX_LEVELS + (size_t)lvl];
+    for (int lane = 0; lane < ADV_WAVE; ++lane) {
+      const long long l = run.worklist[(size_t)w * ADV_WAVE + (size_t)lane];
+      learner_periods<TICK_PLAIN, X_ONLY>(cl, lc.cfgk, lc.tc, mdp, run.k.mdp_run, sc, run.mem, st.sr.data(), st.si.data(), j.seed, l, l >= 0 && l < j.n, j0, np, mgr0, sched, lc.kv);
     }
-    rules[r].rule.last_level = q.last_level; rules[r].rule.advance_exhausted = q.advance_exhausted; rules[r].transfer_order = q.transfer_order; rules[r].pad_ = 0;
-  }
-  const MdpRun<T> mdp_run{cfg.gamma, (T)(cfg.t_max * cfg.f_ag), cfg.goal_logic};
-  const RolloutInit<T> init = make_rollout_init<T>(cfg);
-  emu::LearnerState<T> st(c, init, n, j.seed, j.log_cap);  // (at the config's level, with the config's quirks: k_init reads neither a recipe nor a level)
-  const LearnMem mem = st.mem(j.qa, j.qb, j.count);
-  std::vector<int> level(n, cfg.working_curriculum_step), promoted_at((size_t)ADV_MAX_LEVELS * n, -1), episodes_at((size_t)ADV_MAX_LEVELS * n, 0);
-  std::vector<long long> entered((size_t)ADV_MAX_LEVELS * n, -1);
-  for (size_t l = 0; l < n; ++l) entered[(size_t)cfg.working_curriculum_step * n + l] = 0;
-  const AdvanceMem adv{level.data(), promoted_at.data(), episodes_at.data(), entered.data()};
-  const long long slots = worklist_capacity_recipes((long long)n, j.n_recipes);
-  std::vector<int> worklist((size_t)slots), wave_recipe((size_t)(slots / ADV_WAVE)), wave_level((size_t)(slots / ADV_WAVE));
-
-  long long j0 = 0;
-  for (int run = 0; run < j.n_runs; ++run) {
-    long long left = j.runs[run];
-    while (left > 0) {
-      if (j0 % j.every == 0)
-        for (size_t l = 0; l < n; ++l) (void)advance_learner_recipe(mem, adv, rules.data(), j.n_recipes, j.recipe_of.data(), st.si.data(), (long long)l, j0, DQL_CELLS_PER_LEVEL);
-      long long unfinished = 0;
-      for (size_t l = 0; l < n; ++l) unfinished += learner_finished(st.frozen[l], level[l], st.promoted[l], rules[(size_t)j.recipe_of[l]].rule) ? 0 : 1;
-      if (unfinished == 0) { j0 += left; break; }
-      const long long to_point = j.every - j0 % j.every;
-      const int np = (int)(left < to_point ? left : to_point);
-      const int n_waves = build_worklist_recipes(st.frozen.data(), level.data(), j.recipe_of.data(), (long long)n, j.n_recipes, worklist.data(), wave_recipe.data(), wave_level.data(),
-                                                 slots, st.faults.data());
-      std::vector<long long> mgr0((size_t)np);
-      std::vector<int> sched((size_t)np);
-      fill_schedule(cfg, j0, mgr0.data(), sched.data(), np);
-      for (int w = 0; w < n_waves; ++w) {
-        const int r = wave_recipe[(size_t)w], k = wave_level[(size_t)w];
-        if ((unsigned)r >= (unsigned)j.n_recipes || (unsigned)k >= (unsigned)ADV_MAX_LEVELS) { st.faults[0] += 1ull; continue; }
-        SimK<T> cl = c;
-        cl.working = k;
-        cl.quirks = rs[(size_t)r].quirks;
-        cl.two_axis = 0;
-        const emu::Launch<T, TICK_PLAIN> lc(cl, j.seed);
-        const LearnSched sc = learn_sched(rs[(size_t)r].alpha_tab, rs[(size_t)r].n_alpha, rs[(size_t)r].alpha_min, (const LevelSched DQL_CONST_AS*)&rs[(size_t)r].lv[k]);
-        const MdpK<T> DQL_CONST_AS* mdp = (const MdpK<T> DQL_CONST_AS*)&mdpk[(size_t)r * ADV_MAX_LEVELS + (size_t)k];
-        for (int lane = 0; lane < ADV_WAVE; ++lane) {
-          const long long l = worklist[(size_t)w * ADV_WAVE + (size_t)lane];
-          learner_periods<TICK_PLAIN, X_ONLY>(cl, lc.cfgk, lc.tc, mdp, mdp_run, sc, mem, st.sr.data(), st.si.data(), j.seed, l, l >= 0 && l < (long long)n, j0, np, mgr0.data(), sched.data(), lc.kv);
-        }
-      }
-      j0 += np; left -= np;
-    }
-  }
-  // dql_ensemble_get_levels: the row of a learner's current level shows its counters as they stand
-  for (size_t l = 0; l < n; ++l) { promoted_at[(size_t)level[l] * n + l] = st.promoted[l]; episodes_at[(size_t)level[l] * n + l] = st.lvl[l]; }
-  emu::ResultFile f(out_path);
-  st.put(f, j.qa, j.qb, j.count);
-  f.put(level); f.put(promoted_at); f.put(episodes_at); f.put(entered); f.put(&j0, 1);
-  return f.close();
+  });
+  return run.write(out_path);
 }
 
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc != 3) { std::fprintf(stderr, "usage: recipes_emu JOB OUT\n"); return 2; }
-  Job j = read_job(argv[1]);
+  emu::RecipeJob j(argv[1], true);
   if (j.mode == 1) return worklist_only(j, argv[2]);
   return j.dtype == DQL_F64 ? launch<double>(j, argv[2]) : launch<float>(j, argv[2]);
 }

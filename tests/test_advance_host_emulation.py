@@ -3,7 +3,7 @@ learner_periods, held `==` to the yardstick of tests/advance_checks.py (CPU only
 
 tests/host_emu/advance_emu.cpp compiles the real headers as host C++ and does what dql_ensemble_run does in curriculum mode: advance at the multiples of E,
 worklist, wave by wave.  It is a stand-alone program run as its own process, built twice: plain, and with ASan + UBSan (any report fails); the builds, the
-child process and the reader of the learners' result are tests/host_emu_harness.py's, the level arrays and the period index are read here.  The cases are those
+child process and the reader of the result (the learners, the level arrays, the period index) are tests/host_emu_harness.py's; the job's layout is this module's.  The cases are those
 of tests/test_gpu_ensemble_advance.py; the sanitized build flies the first 24 learners for 384 periods, and the 24 learners of the cases from trained tables
 (`advance_checks.TRAINED_CASE`, `TRAINED_CASE_PAPER`, `TRAINED_FROM_3`) whole."""
 import struct
@@ -42,13 +42,7 @@ def run_emu(exe, tmp, runs, n=None, dtype=F32, sanitized=False, **over):
     job = (struct.pack("<40i", *hdr) + struct.pack("<q", c["seed"]) + cb + np.asarray(ac.case_ratios(c), np.float64).tobytes() + alpha.tobytes()
            + b"".join(np.asarray(s["eps"], np.float64).tobytes() for s in sch)
            + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ())))
-    r = heh.Reader(heh.run(exe, job, tmp, "advance", sanitized))
-    out = heh.learner_result(r, n, c["log_capacity"], cfg)
-    out.update({"level": r.take(np.int32, (n,)), "promoted_at": r.take(np.int32, (5, n)), "episodes_at": r.take(np.int32, (5, n)), "entered_period": r.take(np.int64, (5, n))})
-    j = int(r.take(np.int64, (1,))[0])
-    r.done()
-    assert j == sum(runs)
-    return out
+    return heh.learner_result(heh.run(exe, job, tmp, "advance", sanitized), n, c["log_capacity"], cfg, tail=("levels",), periods=sum(runs))
 
 
 @pytest.fixture(scope="module")

@@ -3,10 +3,7 @@
 tests/host_emu/learner_emu.cpp compiles the real device headers as host C++ (the stand-in runtime header of step_emu.cpp) and flies every learner lane by
 lane, exactly as k_learn does, in two launches of 150 + 250 periods.  The yardstick is tests/ensemble_checks.py's `Reference`: the unchanged oracle stepped
 with external actions, `oracle.agent_predict` / `oracle.agent_update` on per-learner tables.  Built twice: plain, and with ASan + UBSan (any report fails); the builds, the child process
-and the reader of the learners' result (`learner_result`, shared with the advance module) are tests/host_emu_harness.py's."""
-import struct
-
-import numpy as np
+and the job's layout and the reader of the learners' result (`learner_job`, `learner_result`, shared with the whole learner family) are tests/host_emu_harness.py's."""
 import pytest
 
 from dql_multirotor_landing_amd.config import F32, F64, as_launched_config, training_config
@@ -20,15 +17,9 @@ emu = heh.emu_fixture("learner_emu")
 
 
 def run_emu(exe, cfg, n, seed, runs, tmp, eps=ec.EPS_TABLE, window=100, min_successes=97, max_episodes=1 << 30, sanitized=False, log_capacity=LOG_CAP, alpha_tab=None, tables=None):
-    c = bytes(cfg.to_c())
-    alpha = cfg.alpha_table() if alpha_tab is None else np.ascontiguousarray(alpha_tab, np.float64)
-    r4 = list(runs) + [0] * (4 - len(runs))
-    hdr = struct.pack("<16i", len(c), cfg.dtype, n, len(runs), *r4, len(alpha), len(eps), window, min_successes, max_episodes, log_capacity, int(tables is not None), 0) + struct.pack("<q", seed)
-    job = hdr + c + alpha.tobytes() + np.asarray(eps, np.float64).tobytes() + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ()))
-    r = heh.Reader(heh.run(exe, job, tmp, "learner", sanitized))
-    out = heh.learner_result(r, n, log_capacity, cfg)
-    r.done()
-    return out
+    alpha = cfg.alpha_table() if alpha_tab is None else alpha_tab
+    job = heh.learner_job(cfg, n, seed, runs, alpha, eps, window, min_successes, max_episodes, log_capacity, tables)
+    return heh.learner_result(heh.run(exe, job, tmp, "learner", sanitized), n, log_capacity, cfg)
 
 
 @pytest.fixture(scope="module")

@@ -3,9 +3,6 @@
 tests/host_emu/nstep_emu.cpp compiles the real device headers as host C++ and flies every learner lane by lane, exactly as k_learn_nstep does; the pending
 windows are reached through checked references onto poisoned storage exactly as long as the library's.  Built twice through tests/host_emu_harness.py: plain,
 and as a stand-alone ASan + UBSan program (any report fails)."""
-import struct
-
-import numpy as np
 import pytest
 
 from dql_multirotor_landing_amd.config import F32, F64, training_config
@@ -20,16 +17,8 @@ emu = heh.emu_fixture("nstep_emu")
 
 
 def run_emu(exe, cfg, n, seed, runs, nstep, tmp, eps=ec.EPS_TABLE, window=100, min_successes=97, max_episodes=1 << 30, sanitized=False, log_capacity=nc.MAIN_LOG, tables=None):
-    c = bytes(cfg.to_c())
-    alpha = cfg.alpha_table()
-    r4 = list(runs) + [0] * (4 - len(runs))
-    hdr = struct.pack("<16i", len(c), cfg.dtype, n, len(runs), *r4, len(alpha), len(eps), window, min_successes, max_episodes, log_capacity, int(tables is not None), nstep) + struct.pack("<q", seed)
-    job = hdr + c + alpha.tobytes() + np.asarray(eps, np.float64).tobytes() + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ()))
-    r = heh.Reader(heh.run(exe, job, tmp, "nstep", sanitized))
-    out = heh.learner_result(r, n, log_capacity, cfg)
-    out["pending_len"] = r.take(np.int32, (n,))
-    r.done()
-    return out
+    job = heh.learner_job(cfg, n, seed, runs, cfg.alpha_table(), eps, window, min_successes, max_episodes, log_capacity, tables, extra=(nstep,))
+    return heh.learner_result(heh.run(exe, job, tmp, "nstep", sanitized), n, log_capacity, cfg, tail=("pending_len",))
 
 
 def test_the_yardstick_at_n_1_equals_the_one_step_reference_loop():

@@ -5,8 +5,6 @@ tests/host_emu/nstep_recipes_emu.cpp compiles the real headers as host C++ and d
 lane, the wave's n from its recipe, the working windows poisoned before every wave, the persistent ones exactly as long as the library's, both behind checked
 references.  It is a stand-alone program run as its own process, built twice through tests/host_emu_harness.py: plain, and with ASan + UBSan (any report
 fails).  The case is `recipe_checks.CASE` with 28 learners (20 / 4 / 4 members)."""
-import struct
-
 import numpy as np
 import pytest
 
@@ -30,24 +28,8 @@ def run_emu(exe, tmp, runs, nsteps, n=N, dtype=F32, sanitized=False, recipes=Non
     cfg = rc.case_config(dtype) if cfg is None else cfg
     recipes = nr.case_recipes(nsteps, dtype) if recipes is None else recipes
     of = rc.case_recipe_of(n) if recipe_of is None else np.asarray(recipe_of, np.int32)
-    cb = bytes(cfg.to_c())
-    hdr = [len(cb), cfg.dtype, n, len(runs), *(list(runs) + [0] * (8 - len(runs))), CASE["E"], CASE["log_capacity"], len(recipes), 1]
-    job = struct.pack("<24i", *(hdr + [0] * (24 - len(hdr)))) + struct.pack("<q", CASE["seed"]) + cb + np.ascontiguousarray(of, np.int32).tobytes()
-    for r in recipes:
-        alpha, alpha_min, ratios, lv = r.checked(cfg)
-        h = [int(r.quirks), alpha.size, int(r.last_level), int(bool(r.advance_exhausted)), int(r.transfer_order), int(r.nstep), 0, 0]
-        for e, w, ms, me in lv:
-            h += [e.size, w, ms, me]
-        job += struct.pack("<28i", *h) + struct.pack("<d", alpha_min) + ratios.tobytes() + alpha.tobytes() + b"".join(e.tobytes() for e, _, _, _ in lv)
-    job += b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in ec.trained_tables(n))
-    r = heh.Reader(heh.run(exe, job, tmp, "nstep_recipes", sanitized))
-    out = heh.learner_result(r, n, CASE["log_capacity"], cfg)
-    out.update({"level": r.take(np.int32, (n,)), "promoted_at": r.take(np.int32, (5, n)), "episodes_at": r.take(np.int32, (5, n)), "entered_period": r.take(np.int64, (5, n))})
-    j = int(r.take(np.int64, (1,))[0])
-    out["pending_len"] = r.take(np.int32, (n,))
-    r.done()
-    assert j == sum(runs)
-    return out
+    job = heh.recipes_job(cfg, n, CASE["seed"], runs, CASE["E"], CASE["log_capacity"], recipes, of, ec.trained_tables(n))
+    return heh.learner_result(heh.run(exe, job, tmp, "nstep_recipes", sanitized), n, CASE["log_capacity"], cfg, tail=("levels", "pending_len"), periods=sum(runs))
 
 
 # ---- the yardstick's anchors ----

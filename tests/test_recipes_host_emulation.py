@@ -4,8 +4,6 @@ with csrc/dql_learner.hpp's learner_periods, held `==` to the yardsticks of test
 tests/host_emu/recipes_emu.cpp compiles the real headers as host C++ and does what dql_ensemble_run does with recipes installed.  It is a stand-alone program
 run as its own process, built twice: plain, and with ASan + UBSan (any report fails); the builds, the child process and the reader of the learners' result are
 tests/host_emu_harness.py's.  The case is that of tests/test_gpu_ensemble_recipes.py with 28 learners (20 / 4 / 4 members)."""
-import struct
-
 import numpy as np
 import pytest
 
@@ -25,38 +23,17 @@ emu = heh.emu_fixture("recipes_emu")
 advance_emu = heh.emu_fixture("advance_emu")
 
 
-def header(cfg, n, runs=(), n_recipes=0, has_tables=0, mode=0, cap=0):
-    cb = bytes(cfg.to_c())
-    r8 = list(runs) + [0] * (8 - len(runs))
-    hdr = [len(cb), cfg.dtype, n, len(runs), *r8, CASE["E"], CASE["log_capacity"], n_recipes, has_tables, mode, cap]
-    return struct.pack("<24i", *(hdr + [0] * (24 - len(hdr)))) + struct.pack("<q", CASE["seed"]) + cb
-
-
 def run_emu(exe, tmp, runs, n=N, dtype=F32, sanitized=False, recipes=None, recipe_of=None, tables=True):
     cfg = rc.case_config(dtype)
     recipes = rc.case_recipes(dtype) if recipes is None else recipes
     of = rc.case_recipe_of(n) if recipe_of is None else np.asarray(recipe_of, np.int32)
-    job = header(cfg, n, runs, len(recipes), int(tables)) + np.ascontiguousarray(of, np.int32).tobytes()
-    for r in recipes:
-        alpha, alpha_min, ratios, lv = r.checked(cfg)
-        h = [int(r.quirks), alpha.size, int(r.last_level), int(bool(r.advance_exhausted)), int(r.transfer_order), 0, 0, 0]
-        for e, w, ms, me in lv:
-            h += [e.size, w, ms, me]
-        job += struct.pack("<28i", *h) + struct.pack("<d", alpha_min) + ratios.tobytes() + alpha.tobytes() + b"".join(e.tobytes() for e, _, _, _ in lv)
-    if tables:
-        job += b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in rc.ec.trained_tables(n))
-    r = heh.Reader(heh.run(exe, job, tmp, "recipes", sanitized))
-    out = heh.learner_result(r, n, CASE["log_capacity"], cfg)
-    out.update({"level": r.take(np.int32, (n,)), "promoted_at": r.take(np.int32, (5, n)), "episodes_at": r.take(np.int32, (5, n)), "entered_period": r.take(np.int64, (5, n))})
-    j = int(r.take(np.int64, (1,))[0])
-    r.done()
-    assert j == sum(runs)
-    return out
+    job = heh.recipes_job(cfg, n, CASE["seed"], runs, CASE["E"], CASE["log_capacity"], recipes, of, rc.ec.trained_tables(n) if tables else None)
+    return heh.learner_result(heh.run(exe, job, tmp, "recipes", sanitized), n, CASE["log_capacity"], cfg, tail=("levels",), periods=sum(runs))
 
 
 def run_worklist(exe, tmp, frozen, level, recipe_of, n_recipes, cap, sanitized=False):
     n = len(frozen)
-    job = header(rc.case_config(), n, n_recipes=n_recipes, mode=1, cap=cap) + b"".join(np.ascontiguousarray(a, np.int32).tobytes() for a in (recipe_of, frozen, level))
+    job = heh.recipes_header(rc.case_config(), n, CASE["seed"], (), CASE["E"], CASE["log_capacity"], n_recipes, 0, mode=1, cap=cap) + b"".join(np.ascontiguousarray(a, np.int32).tobytes() for a in (recipe_of, frozen, level))
     r = heh.Reader(heh.run(exe, job, tmp, "worklist", sanitized))
     n_waves, faults, capacity = (int(v) for v in r.take(np.int64, (3,)))
     out = r.take(np.int32, (cap,)), r.take(np.int32, (cap // WAVE,)), r.take(np.int32, (cap // WAVE,))

@@ -5,12 +5,9 @@ tests/host_emu/team_emu.cpp compiles the real device headers as host C++ and fli
 records and then the real team_apply on it.  The yardstick is tests/team_checks.py's `TeamReference`: the unchanged oracle stepped with external actions,
 `oracle.agent_predict` before the step and `oracle.agent_update` for the envs in ascending order after it, on the learner's shared tables.  Every case first
 asserts on the reference that the events it is there for occurred (team_checks.case_reference).  Built twice: plain, and with ASan + UBSan."""
-import struct
-
-import numpy as np
 import pytest
 
-from dql_multirotor_landing_amd.config import F32, F64, N_CELLS, training_config
+from dql_multirotor_landing_amd.config import F32, F64, training_config
 
 import ensemble_checks as ec
 import host_emu_harness as heh
@@ -22,26 +19,8 @@ learner_emu = heh.emu_fixture("learner_emu")
 
 
 def run_emu(exe, cfg, n, envs_per_learner, seed, runs, tmp, eps, window, min_successes, max_episodes, log_capacity, sanitized=False, tables=None):
-    c = bytes(cfg.to_c())
-    alpha = cfg.alpha_table()
-    r4 = list(runs) + [0] * (4 - len(runs))
-    hdr = struct.pack("<16i", len(c), cfg.dtype, n, len(runs), *r4, len(alpha), len(eps), window, min_successes, max_episodes, log_capacity, int(tables is not None),
-                      envs_per_learner) + struct.pack("<q", seed)
-    job = hdr + c + alpha.tobytes() + np.asarray(eps, np.float64).tobytes() + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ()))
-    r = heh.Reader(heh.run(exe, job, tmp, "team", sanitized))
-    take, m = r.take, n * envs_per_learner
-    out = {"qa": take(np.float64, (n, N_CELLS)), "qb": take(np.float64, (n, N_CELLS)), "count": take(np.float64, (n, N_CELLS)),
-           "decisions": take(np.int64, (n,)), "by_code": take(np.int64, (ec.N_CODES, n)), "episodes": take(np.int32, (n,)), "successes": take(np.int32, (n,)),
-           "level_episodes": take(np.int32, (n,)), "promotion_episode": take(np.int32, (n,)), "frozen": take(np.int32, (n,)), "log_n": take(np.int32, (n,)),
-           "log_code": take(np.uint8, (n, log_capacity)), "log_len": take(np.uint16, (n, log_capacity))}
-    reals, ints = take(np.float64, (heh.NF_REAL, m)), take(np.int32, (heh.NF_INT, m))
-    faults = take(np.int64, (1,))
-    r.done()
-    assert faults[0] == 0, "a range check counted a fault: the bounds guard dropped an update"
-    ref = ec.Reference(cfg, 1, 0)
-    out.update({f: reals[k] for f, k in ref.ri.items()})
-    out.update({f: ints[k] for f, k in ref.ii.items()})
-    return out
+    job = heh.learner_job(cfg, n, seed, runs, cfg.alpha_table(), eps, window, min_successes, max_episodes, log_capacity, tables, extra=(envs_per_learner,))
+    return heh.learner_result(heh.run(exe, job, tmp, "team", sanitized), n, log_capacity, cfg, n_envs=n * envs_per_learner)
 
 
 def run_case(exe, name, dtype, runs, tmp, sanitized=False, learners=None):

@@ -5,12 +5,9 @@ tests/host_emu/team_nstep_emu.cpp compiles the real device headers as host C++ a
 through checked references onto poisoned storage exactly as long as stated: the team's working copy [16][E] plus head and len [E], the persistent arrays
 [16][L E] and [L E].  Built twice through tests/host_emu_harness.py: plain, and as a stand-alone ASan + UBSan program (any report fails).  The yardstick
 itself is held to its two parents first: at n = 1 to `team_checks.TeamReference`, at E = 1 to `nstep_checks.NstepReference`."""
-import struct
-
-import numpy as np
 import pytest
 
-from dql_multirotor_landing_amd.config import F32, F64, N_CELLS, training_config
+from dql_multirotor_landing_amd.config import F32, F64, training_config
 
 import ensemble_checks as ec
 import host_emu_harness as heh
@@ -26,26 +23,9 @@ nstep_emu = heh.emu_fixture("nstep_emu")
 
 
 def run_emu(exe, cfg, n, envs_per_learner, seed, runs, nstep, tmp, eps, window, min_successes, max_episodes, log_capacity, sanitized=False, tables=None, rearm_after=-1):
-    c = bytes(cfg.to_c())
-    alpha = cfg.alpha_table()
-    r4 = list(runs) + [0] * (4 - len(runs))
-    hdr = struct.pack("<18i", len(c), cfg.dtype, n, len(runs), *r4, len(alpha), len(eps), window, min_successes, max_episodes, log_capacity, int(tables is not None),
-                      envs_per_learner, nstep, rearm_after) + struct.pack("<q", seed)
-    job = hdr + c + alpha.tobytes() + np.asarray(eps, np.float64).tobytes() + b"".join(np.ascontiguousarray(t, np.float64).tobytes() for t in (tables or ()))
-    r = heh.Reader(heh.run(exe, job, tmp, "team_nstep", sanitized))
-    take, m = r.take, n * envs_per_learner
-    out = {"qa": take(np.float64, (n, N_CELLS)), "qb": take(np.float64, (n, N_CELLS)), "count": take(np.float64, (n, N_CELLS)),
-           "decisions": take(np.int64, (n,)), "by_code": take(np.int64, (ec.N_CODES, n)), "episodes": take(np.int32, (n,)), "successes": take(np.int32, (n,)),
-           "level_episodes": take(np.int32, (n,)), "promotion_episode": take(np.int32, (n,)), "frozen": take(np.int32, (n,)), "log_n": take(np.int32, (n,)),
-           "log_code": take(np.uint8, (n, log_capacity)), "log_len": take(np.uint16, (n, log_capacity))}
-    reals, ints = take(np.float64, (heh.NF_REAL, m)), take(np.int32, (heh.NF_INT, m))
-    faults = take(np.int64, (1,))
-    out["team_pending_len"] = take(np.int32, (m,))
-    r.done()
-    assert faults[0] == 0, "a range check counted a fault: the bounds guard dropped an update"
-    ref = ec.Reference(cfg, 1, 0)
-    out.update({f: reals[k] for f, k in ref.ri.items()})
-    out.update({f: ints[k] for f, k in ref.ii.items()})
+    job = heh.learner_job(cfg, n, seed, runs, cfg.alpha_table(), eps, window, min_successes, max_episodes, log_capacity, tables, extra=(envs_per_learner, nstep, rearm_after))
+    out = heh.learner_result(heh.run(exe, job, tmp, "team_nstep", sanitized), n, log_capacity, cfg, n_envs=n * envs_per_learner, tail=("pending_len",))
+    out["team_pending_len"] = out.pop("pending_len")
     return out
 
 
