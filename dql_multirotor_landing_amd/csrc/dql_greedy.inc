@@ -1,8 +1,47 @@
 // dql_greedy.inc: greedy flight of given tables in one launch: the roll-outs with flight records (dql_rollout, DESIGN.md section 11) and the scorer (dql_score,
 // DESIGN.md section 13; score_check / score_run also serve dql_ensemble_score), and the host helpers every greedy-flight operator shares (DESIGN.md section 15:
-// TableSets, Flight, Sums, EpisodeLog, RangeFaults, LastCall / diag_last, timed_launch, fill_flight_args / fill_greedy_args).  A fragment of dql_hip.hip's translation
+// TableSets, Flight, Sums, EpisodeLog, RangeFaults, LastCall / diag_last, timed_launch, fill_flight_args / fill_greedy_args) and what its kernels share on the
+// device (DESIGN.md section 28: set_coords, flush_tally, cells_clear / cells_flush).  A fragment of dql_hip.hip's translation
 // unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype_axes, DevBuf / OP_PROLOGUE / UP / OUT / DOWN, mdpk_bytes, upload_mdpk, upload_schedule, EvTimer,
 // check_config, TickLds; and dql_rollout.hpp, dql_score.hpp.
+// ---- what the family's kernels share on the device (DESIGN.md section 28) ----
+// A launch of n_tables * B one-wave workgroups, B = blocks_per_table = envs_per_table / 64: table set k serves blocks [k B, (k + 1) B), so that the set's tables
+// are a wave-uniform pointer; env i of every set has env id i = its RNG key (paired episodes); g: the lane's column of the outputs (every lane of the grid is an
+// env: envs_per_table is a multiple of 64)
+struct SetCoords { int k, i; long long g; };
+__device__ __forceinline__ SetCoords set_coords(int blocks_per_table) {
+  const int k = (int)blockIdx.x / blocks_per_table;
+  return SetCoords{k, ((int)blockIdx.x - k * blocks_per_table) * 64 + (int)threadIdx.x, (long long)blockIdx.x * 64 + (int)threadIdx.x};
+}
+// what leaves a wave that flew fly_episodes: one atomicAdd per non-zero column of its tally into row `row_i` of buffers zeroed before the launch
+__device__ __forceinline__ void flush_tally(const ScoreTally& t, unsigned long long* by_code, unsigned long long* steps_sum, size_t row_i) {
+  if (threadIdx.x == 0) {
+    unsigned long long* row = by_code + row_i * SCORE_N_COLS;
+#pragma unroll
+    for (int col = 0; col < SCORE_N_COLS; ++col) if (t.by_code[col]) atomicAdd(&row[col], (unsigned long long)t.by_code[col]);
+    if (t.steps) atomicAdd(&steps_sum[row_i], t.steps);
+  }
+}
+// a one-wave workgroup's LDS table of DQL_N_CELLS cells (k_score_map's histogram, k_model's rewards): the lanes sweep contiguous cells, c = it * 64 + lane,
+// CELL_SWEEPS = 45 sweeps, the last one partial (cells 2 816 .. 2 834); the flush adds the non-zero cells to a row of 64-bit sums.  The caller's two
+// __syncthreads() order clear, adds and flush (dql_score_map.inc)
+constexpr int CELL_SWEEPS = (DQL_N_CELLS + 63) / 64;
+template <typename Cell> __device__ __forceinline__ void cells_clear(Cell* cells) {
+#pragma unroll 1
+  for (int it = 0; it < CELL_SWEEPS; ++it) {
+    const int c = it * 64 + (int)threadIdx.x;
+    if (c < DQL_N_CELLS) cells[c] = Cell(0);
+  }
+}
+template <typename Cell> __device__ __forceinline__ void cells_flush(const Cell* cells, unsigned long long* row) {
+#pragma unroll 1
+  for (int it = 0; it < CELL_SWEEPS; ++it) {
+    const int c = it * 64 + (int)threadIdx.x;
+    const Cell v = c < DQL_N_CELLS ? cells[c] : Cell(0);
+    if (v) atomicAdd(&row[c], (unsigned long long)v);
+  }
+}
+
 // ---- greedy roll-outs (dql_rollout, DESIGN.md section 11) ----
 // One env per lane flies its FIRST episode from reset to termination (csrc/dql_rollout.hpp: rollout_episode); workgroups of one wave: evaluation batches are
 // small, a lone wave per SIMD needs no LDS staging, no barrier, and there are no accumulators, table-writer blocks or statistics here.  Table set k serves
@@ -37,7 +76,7 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
   uint32_t kv_[20];
   const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
+  if constexpr (sizeof(T) == 4) {  // lane_round_keys' text, kept here: through the function this kernel's float32 code is allocated differently (DESIGN.md section 28)
 #pragma unroll
     for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
     kv = kv_;
@@ -68,9 +107,7 @@ template <typename T> struct ScoreArgs {
 };
 template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_score(ScoreArgs<T> a) {
   const int tid = threadIdx.x;
-  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
-  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
-  const long long g = (long long)blockIdx.x * 64 + tid;                // log column: every lane of the grid is an env (envs_per_table is a multiple of 64)
+  const auto [k, i, g] = set_coords(a.blocks_per_table);
   SimK<T> cl = a.c;
   if constexpr (XMODE == X_ONLY) cl.two_axis = 0;
   SimK<T> cfgk = cl;
@@ -83,7 +120,7 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
   uint32_t kv_[20];
   const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
+  if constexpr (sizeof(T) == 4) {  // lane_round_keys' text, kept here: through the function this kernel's float32 code is allocated differently (DESIGN.md section 28)
 #pragma unroll
     for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
     kv = kv_;
@@ -91,12 +128,7 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
   const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
   const ScoreTally t = score_episodes<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.episodes, a.mgr0, a.sched, kv, a.log, g);
-  if (tid == 0) {
-    unsigned long long* row = a.by_code + (size_t)k * SCORE_N_COLS;
-#pragma unroll
-    for (int col = 0; col < SCORE_N_COLS; ++col) if (t.by_code[col]) atomicAdd(&row[col], (unsigned long long)t.by_code[col]);
-    if (t.steps) atomicAdd(&a.steps_sum[k], t.steps);
-  }
+  flush_tally(t, a.by_code, a.steps_sum, (size_t)k);
 }
 
 // ---- shared host helpers of the greedy family (DESIGN.md section 15): what the host side of dql_rollout, dql_score, dql_score_map, dql_model, dql_returns and

@@ -5,7 +5,7 @@
 //                halves of an episode's end.  The solo bodies call both halves, the team bodies (dql_team.hpp) the second only while the level is undecided.
 //   the update   learner_best and learner_alpha, of which learner_update is written and which the n-step update (dql_nstep.hpp) shares; qrow_patch, the
 //                carried row after a write to the row of the state the env is in.
-//   the keys     learner_round_keys, the float32 Philox round keys in VGPRs, for the seven learner kernels.
+// The float32 Philox round keys the seven learner kernels put in VGPRs are lane_round_keys (dql_rollout.hpp), shared with the greedy-flight family.
 // The pending windows of the n-step learners are dql_nstep.hpp's.
 //
 // learner_periods is the per-lane body of k_learn (dql_ensemble.inc) and of its host emulation (tests/host_emu/learner_emu.cpp).  Learner l owns env l of a
@@ -44,17 +44,6 @@ struct LearnMem {
   unsigned long long* faults;              // [1] updates dropped by the bounds guard (0 unless a bug)
   long long n; int log_cap;
 };
-
-// the float32 Philox round keys of `seed` in VGPRs (float64 reads them from SGPRs: null)
-template <typename T> DQL_DEV const uint32_t* learner_round_keys(uint64_t seed, uint32_t (&kv_)[20]) {
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    return kv_;
-  } else {
-    return nullptr;
-  }
-}
 
 // ---- the books ----
 // a learner's counters while a launch holds them in registers (a team's: in its applying lane's)

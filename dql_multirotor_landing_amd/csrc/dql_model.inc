@@ -31,7 +31,6 @@ template <typename T> struct ModelArgs {
   unsigned eps_thr;
   int blocks_per_table, max_steps, episodes, n_tables;
 };
-constexpr int MODEL_SWEEPS = (DQL_N_CELLS + 63) / 64;
 struct WaveModelSink {  // the table set's tables as model_episodes sees them; cell, next and code are range-checked by the caller
   unsigned* p; unsigned long long* t; unsigned long long* r_lds; int lane;
   __device__ __forceinline__ void pair(int cell, int next) {
@@ -53,8 +52,7 @@ struct WaveModelSink {  // the table set's tables as model_episodes sees them; c
 };
 template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_model(ModelArgs<T> a) {
   const int tid = threadIdx.x;
-  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
-  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
+  const auto [k, i, g] = set_coords(a.blocks_per_table);  // g: not used, the model has no per-lane output
   if (k >= a.n_tables) {  // never taken unless a bug (the host sizes the grid): nothing is read or written for a table set that is not there
     if (tid == 0) atomicAdd(a.faults, 1ull);
     return;
@@ -65,43 +63,22 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
   __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
   __shared__ unsigned long long sReward[DQL_N_CELLS];
-#pragma unroll 1
-  for (int it = 0; it < MODEL_SWEEPS; ++it) {
-    const int c = it * 64 + tid;
-    if (c < DQL_N_CELLS) sReward[c] = 0ull;
-  }
+  cells_clear(sReward);
   if constexpr (sizeof(T) == 8) {
     if (tid == 0) sTickK.k = cfgk;
   }
   __syncthreads();  // the clear (and the tick constants) before the first period
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
   uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
+  const uint32_t* kv = lane_round_keys<T>(a.seed, kv_);
   const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
   const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
   WaveModelSink sink{a.pairs + (size_t)k * DQL_N_CELLS * DQL_N_STATES, a.terminal + (size_t)k * DQL_N_CELLS * DQL_N_CHECK_CODES, sReward, tid};
   const ModelTally r = model_episodes<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.episodes, a.eps_thr, a.mgr0, a.sched, kv, sink);
   __syncthreads();  // the adds of every lane before the flush
-  unsigned long long* row_r = a.reward_fx + (size_t)k * DQL_N_CELLS;
-#pragma unroll 1
-  for (int it = 0; it < MODEL_SWEEPS; ++it) {
-    const int c = it * 64 + tid;
-    const unsigned long long v = c < DQL_N_CELLS ? sReward[c] : 0ull;
-    if (v) atomicAdd(&row_r[c], v);
-  }
+  cells_flush(sReward, a.reward_fx + (size_t)k * DQL_N_CELLS);
   if (r.faults) atomicAdd(a.faults, (unsigned long long)r.faults);
-  if (tid == 0) {
-    const ScoreTally& t = r.t;
-    unsigned long long* row = a.by_code + (size_t)k * SCORE_N_COLS;
-#pragma unroll
-    for (int col = 0; col < SCORE_N_COLS; ++col) if (t.by_code[col]) atomicAdd(&row[col], (unsigned long long)t.by_code[col]);
-    if (t.steps) atomicAdd(&a.steps_sum[k], t.steps);
-  }
+  flush_tally(r.t, a.by_code, a.steps_sum, (size_t)k);
 }
 
 extern "C" {

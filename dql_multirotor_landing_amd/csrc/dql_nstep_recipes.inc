@@ -44,11 +44,11 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   // the Philox key schedule (float32: in VGPRs, as in k_learn) is made once per body: one array read by both bodies stays in private memory
   if (nstep == 0) {
     uint32_t kv_[20];
-    const uint32_t* kv = learner_round_keys<T>(a.seed, kv_);
+    const uint32_t* kv = lane_round_keys<T>(a.seed, kv_);
     learner_periods<TICK, XMODE>(cl, cfgk, tc, a.mdp + (r * DQL_MAX_LEVELS + level), a.mdp_run, sc, a.mem, a.sr, a.si, a.seed, l, active, a.j0, a.n_periods, a.mgr0, a.tick_sched, kv);
   } else {
     uint32_t kv_[20];
-    const uint32_t* kv = learner_round_keys<T>(a.seed, kv_);
+    const uint32_t* kv = lane_round_keys<T>(a.seed, kv_);
     learner_periods_nstep<TICK, XMODE>(cl, cfgk, tc, a.mdp + (r * DQL_MAX_LEVELS + level), a.mdp_run, sc, a.mem, a.sr, a.si, a.seed, l, active, a.j0, a.n_periods, a.mgr0,
                                        a.tick_sched, kv, nstep, LdsWindow{sKey + tid, sVal + tid}, h.nm);
   }

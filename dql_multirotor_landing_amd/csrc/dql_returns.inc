@@ -33,9 +33,8 @@ template <typename T> struct ReturnsFlyArgs {
 };
 template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_returns_fly(ReturnsFlyArgs<T> a) {
   const int tid = threadIdx.x;
-  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
-  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
-  const size_t column = (size_t)blockIdx.x * 64 + (size_t)tid;         // = k * envs_per_table + i
+  const auto [k, i, g] = set_coords(a.blocks_per_table);
+  const size_t column = (size_t)g;                                     // = k * envs_per_table + i
   if (k >= a.n_tables || (size_t)blockIdx.x * 64 + 64 > (size_t)a.n_columns) {  // never taken unless a bug (the host sizes the grid): nothing is read or written
     if (tid == 0) atomicAdd(a.faults, 1ull);
     return;
@@ -51,25 +50,14 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   }
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
   uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
+  const uint32_t* kv = lane_round_keys<T>(a.seed, kv_);
   const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
   const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
   ReturnsLogSink<unsigned long long*> sink{a.traj, (size_t)a.n_columns, column, (unsigned)(a.max_steps + 1)};
   const ModelTally r = model_episodes<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.episodes, a.eps_thr, a.mgr0, a.sched, kv, sink);
   a.n_dec[column] = sink.n_dec;
   if (r.faults + sink.faults) atomicAdd(a.faults, (unsigned long long)(r.faults + sink.faults));
-  if (tid == 0) {
-    const ScoreTally& t = r.t;
-    unsigned long long* row = a.by_code + (size_t)k * SCORE_N_COLS;
-#pragma unroll
-    for (int col = 0; col < SCORE_N_COLS; ++col) if (t.by_code[col]) atomicAdd(&row[col], (unsigned long long)t.by_code[col]);
-    if (t.steps) atomicAdd(&a.steps_sum[k], t.steps);
-  }
+  flush_tally(r.t, a.by_code, a.steps_sum, (size_t)k);
 }
 
 struct ReturnsSweepArgs {

@@ -36,6 +36,18 @@ template <typename T> static RolloutInit<T> make_rollout_init(const dql_config& 
   return a;
 }
 
+// the float32 Philox round keys of `seed` in VGPRs (float64 reads them from SGPRs: null), for every kernel that flies agent_period one env per lane: the
+// greedy-flight family and the learners
+template <typename T> DQL_DEV const uint32_t* lane_round_keys(uint64_t seed, uint32_t (&kv_)[20]) {
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
+    return kv_;
+  } else {
+    return nullptr;
+  }
+}
+
 // [n_total] codes and step counts, [RO_N_RECORD][n_total] record fields, [max_steps + 1][RO_N_TRACE][trace_envs] trace rows (or null)
 struct RolloutOut { int* code; int* steps; double* rec; double* trace; long long n_total; int trace_envs; };
 

@@ -1,14 +1,13 @@
-// dql_score_grid.hpp — greedy scoring of K table sets over S scenarios in one launch, with the landing precision of the touchdowns.
+// dql_score_grid.hpp — greedy scoring of K table sets over S scenarios in one launch, with the landing precision of the touchdowns (DESIGN.md sections 20 and 28).
 //
 // Three things in plain C++, shared by k_score_grid (dql_score_grid.inc) and its host emulation (tests/host_emu/grid_emu.cpp):
 //   grid_coords          which scenario, table set and envs a block of the launch serves (scenario-major)
 //   touch_bin            the bin of a touchdown's horizontal offset from the platform centre
-//   score_grid_episodes  the per-lane body: score_episodes' loop (dql_score.hpp) — one env flies episode after episode under ITS scenario's constants — plus,
-//                        in the wave-uniform bookkeeping branch, eight ballots for the touch bins beside the nine for the terminal codes
+//   score_grid_episodes  the per-lane body: fly_episodes (dql_score.hpp) with score's log — one env flies episode after episode under ITS scenario's constants —
+//                        and one hook more: in the wave-uniform bookkeeping branch, eight ballots for the touch bins beside the nine for the terminal codes
 // Nothing here knows where the scenario's constants come from: the caller hands them over as score_episodes' caller does.  Every output of a (scenario, set)
 // is what score_episodes gives for that scenario's config alone; the touch bins are the only output it has no counterpart for.
 //
-// The loop runs max_steps + 1 <= SCORE_MAX_STEPS + 1 times at most on every path: the data can only shorten it (a wave leaves when none of its lanes flies).
 // Include after dql_device.hpp, dql_rollout.hpp and dql_score.hpp.
 #pragma once
 #include "dql_device.hpp"
@@ -59,58 +58,26 @@ template <int XMODE, typename T> DQL_DEV T touch_offset(const Env<T>& e) {
 
 struct GridTally { ScoreTally t; unsigned touch[GRID_TOUCH_BINS]; };
 
+template <int XMODE, typename T> struct GridHooks : ScoreLogHooks {
+  const T (&edges)[GRID_N_EDGES]; unsigned (&touch_hist)[GRID_TOUCH_BINS];
+  DQL_DEV GridHooks(const ScoreLog& log_, long long g_, const T (&edges_)[GRID_N_EDGES], unsigned (&touch_)[GRID_TOUCH_BINS]) : ScoreLogHooks(log_, g_), edges(edges_), touch_hist(touch_) {}
+  DQL_DEV void wave_end(bool done, int code, const Env<T>& e) {
+    // a lane that is `done` here is within its first n_eps episodes (it stops flying after them): its touchdown counts, by the offset after this period
+    const bool touch = done && code == DQL_TERMINAL_CONTACT;
+    const int bin = touch_bin(touch_offset<XMODE>(e), edges);
+#pragma unroll
+    for (int b = 0; b < GRID_TOUCH_BINS; ++b) touch_hist[b] += (unsigned)__builtin_popcountll(__ballot(touch && bin == b));
+  }
+};
+
 // score_episodes' arguments, plus the scenario's touch edges.  g: the lane's column of ITS SCENARIO's log (log.code / log.steps point at that scenario's slice).
 template <int TICK, int XMODE, typename T, typename TabPtr, typename MgrPtr, typename SchedPtr>
 DQL_DEV GridTally score_grid_episodes(const SimK<T>& c, const SimK<T>& cfgk, const TickConsts<TICK, T>& tc, const MdpK<T> DQL_CONST_AS* mdp, const MdpRun<T>& mr,
                                       const RolloutInit<T>& init, const T (&edges)[GRID_N_EDGES], TabPtr qa, TabPtr qb, uint64_t seed, uint32_t env_id, int max_steps,
                                       int episodes, MgrPtr mgr0, SchedPtr sched, const uint32_t* kv, const ScoreLog& log, long long g) {
-  Env<T> e;
-  T mp_v_hbm;
-  rollout_init_env(c, init, e, env_id, seed, mp_v_hbm);
-  QRow qx = load_qrow(qa, qb, 0);  // a fresh env has no previous state: its row is never used
   GridTally r{};
-  ScoreTally& t = r.t;
-  const int n_eps = episodes < SCORE_MAX_EPISODES ? episodes : SCORE_MAX_EPISODES;
-  const int last = max_steps < SCORE_MAX_STEPS ? max_steps : SCORE_MAX_STEPS;
-  int finished = 0;
-  unsigned lane_steps = 0u;  // at most SCORE_MAX_STEPS + 1 periods: fits
-  bool flying = n_eps > 0;
-  for (int j = 0; j <= last; ++j) {
-    bool done = false;
-    if (flying) {
-      const StepOut o = agent_period<TICK, XMODE>(cfgk, tc, mdp, mr, e, qx, qa, qb, MODE_EVAL, 0u, 2, seed, env_id, (long long)j, mgr0[j], sched[j], kv);
-      qx = o.next;
-      done = o.done != 0;
-    }
-    if (__ballot(done) != 0ull) {  // wave-uniform: the bookkeeping runs in the few periods in which an episode of this wave ends
-      const int code = e.code;
-#pragma unroll
-      for (int k = 0; k < DQL_N_CHECK_CODES; ++k) t.by_code[k] += (unsigned)__builtin_popcountll(__ballot(done && code == k));
-      // a lane that is `done` here is within its first n_eps episodes (it stops flying after them): its touchdown counts, by the offset after this period
-      const bool touch = done && code == DQL_TERMINAL_CONTACT;
-      const int bin = touch_bin(touch_offset<XMODE>(e), edges);
-#pragma unroll
-      for (int b = 0; b < GRID_TOUCH_BINS; ++b) r.touch[b] += (unsigned)__builtin_popcountll(__ballot(touch && bin == b));
-      if (done) {
-        const int len = e.step_count & 0xffff;
-        lane_steps += (unsigned)len;
-        if (log.code) {
-          log.code[(long long)finished * log.n_total + g] = (uint8_t)code;
-          log.steps[(long long)finished * log.n_total + g] = (uint16_t)len;
-        }
-        ++finished;
-        flying = finished < n_eps;
-      }
-    }
-    if (__ballot(flying) == 0ull) break;
-  }
-  // the lanes' sums as sums over bit planes: ballots and scalar counts only, once per launch
-  unsigned unfinished = 0u;
-#pragma unroll
-  for (int b = 0; b < 7; ++b) unfinished += (unsigned)__builtin_popcountll(__ballot((((unsigned)(n_eps - finished) >> b) & 1u) != 0u)) << b;
-  t.by_code[DQL_N_CHECK_CODES] = unfinished;
-#pragma unroll
-  for (int b = 0; b < 13; ++b) t.steps += (unsigned long long)__builtin_popcountll(__ballot(((lane_steps >> b) & 1u) != 0u)) << b;
+  GridHooks<XMODE, T> h(log, g, edges, r.touch);
+  fly_episodes<TICK, XMODE>(r.t, c, cfgk, tc, mdp, mr, init, qa, qb, seed, env_id, max_steps, episodes, MODE_EVAL, 0u, mgr0, sched, kv, h);
   return r;
 }
 

@@ -41,24 +41,16 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   }
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
   uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
+  const uint32_t* kv = lane_round_keys<T>(a.seed, kv_);
   const double* qa = a.qa + (size_t)gc.k * DQL_N_CELLS;
   const double* qb = a.qb + (size_t)gc.k * DQL_N_CELLS;
   const size_t log_off = (size_t)gc.s * (size_t)a.episodes * (size_t)n_total;
   const ScoreLog log{a.ep_code ? a.ep_code + log_off : nullptr, a.ep_code ? a.ep_steps + log_off : nullptr, n_total};
   const GridTally r = score_grid_episodes<TICK, XMODE>(cl, cfgk, tc, a.mdp + gc.s, rec.mr, rec.init, rec.touch_edges, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.episodes,
                                                        a.mgr0, a.sched, kv, log, g);
+  const size_t row_i = (size_t)gc.s * (size_t)a.n_tables + (size_t)gc.k;
+  flush_tally(r.t, a.by_code, a.steps_sum, row_i);
   if (tid == 0) {
-    const size_t row_i = (size_t)gc.s * (size_t)a.n_tables + (size_t)gc.k;
-    unsigned long long* row = a.by_code + row_i * SCORE_N_COLS;
-#pragma unroll
-    for (int col = 0; col < SCORE_N_COLS; ++col) if (r.t.by_code[col]) atomicAdd(&row[col], (unsigned long long)r.t.by_code[col]);
-    if (r.t.steps) atomicAdd(&a.steps_sum[row_i], r.t.steps);
     unsigned long long* trow = a.touch + row_i * GRID_TOUCH_BINS;
 #pragma unroll
     for (int b = 0; b < GRID_TOUCH_BINS; ++b) if (r.touch[b]) atomicAdd(&trow[b], (unsigned long long)r.touch[b]);

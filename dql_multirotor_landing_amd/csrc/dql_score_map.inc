@@ -5,7 +5,7 @@
 // k_score's shape — one env per lane, workgroups of one wave, table set k serves blocks [k B, (k + 1) B), env i of every set has RNG key (i, seed), the same
 // waves_per_eu — and on top of it the wave's histogram in LDS: unsigned [DQL_N_CELLS], 11 340 B per workgroup.  The wave clears it before the first period,
 // every lane adds its decisions with LDS atomics (many lanes hit one cell in the same period), and at the end the wave flushes the non-zero cells into the table
-// set's row of the global map — zeroed before the launch — with atomicAdd on unsigned long long: lanes sweep contiguous cells, c = it * 64 + lane, SCORE_MAP_SWEEPS
+// set's row of the global map — zeroed before the launch — with atomicAdd on unsigned long long: lanes sweep contiguous cells, c = it * 64 + lane, CELL_SWEEPS
 // = 45 sweeps, the last one partial (cells 2 816 .. 2 834).  Integer sums: the result does not depend on the order the waves arrive in.
 // What orders clear, adds and flush: the workgroup is one wave, the LDS serves a wave's operations in the order they were issued, and the two __syncthreads()
 // keep the compiler from moving an LDS access across them (and make the order hold by the language's rules as well, whatever the workgroup size).
@@ -30,9 +30,7 @@ struct LdsHist {  // the wave's histogram as score_map_episodes sees it; cell is
 };
 template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_score_map(ScoreMapArgs<T> a) {
   const int tid = threadIdx.x;
-  const int k = (int)blockIdx.x / a.blocks_per_table;                  // table set (wave-uniform)
-  const int i = ((int)blockIdx.x - k * a.blocks_per_table) * 64 + tid;  // env within its table set = its RNG key
-  const long long g = (long long)blockIdx.x * 64 + tid;                // log column: every lane of the grid is an env (envs_per_table is a multiple of 64)
+  const auto [k, i, g] = set_coords(a.blocks_per_table);
   if (k >= a.n_tables) {  // never taken unless a bug (the host sizes the grid): nothing is read or written for a table set that is not there
     if (tid == 0) atomicAdd(a.faults, 1ull);
     return;
@@ -43,44 +41,23 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   if constexpr (sizeof(T) == 4) cfgk = period_consts_in_vgprs(cfgk);
   __shared__ TickLds<T> sTickK;  // float64: the tick's constants are read from LDS (k_step); float32: an unused byte
   __shared__ unsigned sHist[DQL_N_CELLS];
-#pragma unroll 1
-  for (int it = 0; it < SCORE_MAP_SWEEPS; ++it) {
-    const int c = it * 64 + tid;
-    if (c < DQL_N_CELLS) sHist[c] = 0u;
-  }
+  cells_clear(sHist);
   if constexpr (sizeof(T) == 8) {
     if (tid == 0) sTickK.k = cfgk;
   }
   __syncthreads();  // the clear (and the tick constants) before the first period
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
   uint32_t kv_[20];
-  const uint32_t* kv = nullptr;
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { kv_[r] = to_vgpr((uint32_t)a.seed + (uint32_t)r * 0x9E3779B9u); kv_[10 + r] = to_vgpr((uint32_t)(a.seed >> 32) + (uint32_t)r * 0xBB67AE85u); }
-    kv = kv_;
-  }
+  const uint32_t* kv = lane_round_keys<T>(a.seed, kv_);
   const double* qa = a.qa + (size_t)k * DQL_N_CELLS;
   const double* qb = a.qb + (size_t)k * DQL_N_CELLS;
   LdsHist hist{sHist};
   const ScoreMapTally r = score_map_episodes<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, a.init, qa, qb, a.seed, (uint32_t)i, a.max_steps, a.episodes, a.mgr0, a.sched, kv,
                                                           a.log, g, hist);
   __syncthreads();  // the adds of every lane before the flush
-  unsigned long long* map = a.visits + (size_t)k * DQL_N_CELLS;
-#pragma unroll 1
-  for (int it = 0; it < SCORE_MAP_SWEEPS; ++it) {
-    const int c = it * 64 + tid;
-    const unsigned v = c < DQL_N_CELLS ? sHist[c] : 0u;
-    if (v) atomicAdd(&map[c], (unsigned long long)v);
-  }
+  cells_flush(sHist, a.visits + (size_t)k * DQL_N_CELLS);
   if (r.faults) atomicAdd(a.faults, (unsigned long long)r.faults);
-  if (tid == 0) {
-    const ScoreTally& t = r.t;
-    unsigned long long* row = a.by_code + (size_t)k * SCORE_N_COLS;
-#pragma unroll
-    for (int col = 0; col < SCORE_N_COLS; ++col) if (t.by_code[col]) atomicAdd(&row[col], (unsigned long long)t.by_code[col]);
-    if (t.steps) atomicAdd(&a.steps_sum[k], t.steps);
-  }
+  flush_tally(r.t, a.by_code, a.steps_sum, (size_t)k);
 }
 
 extern "C" {

@@ -23,7 +23,7 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   }
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
   uint32_t kv_[20];
-  const uint32_t* kv = learner_round_keys<T>(a.seed, kv_);
+  const uint32_t* kv = lane_round_keys<T>(a.seed, kv_);
   team_wave<XMODE>(t, cl, cfgk, tc, kv, tid, sRec, sCtl, NoTeamWindows{});
 }
 template <typename T> static void launch_learn_team(dql_ensemble* x, int k, int n_waves) {
