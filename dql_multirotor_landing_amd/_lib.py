@@ -202,6 +202,8 @@ SYMBOLS = {
     "dql_ensemble_get_recipe_nstep": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
     "dql_ensemble_set_team_nstep": (C.c_int, [_vp, _i32]),
     "dql_ensemble_get_team_nstep": (C.c_int, [_vp, C.POINTER(_i32), _vp]),
+    # team curriculum mode (include/dql.h)
+    "dql_ensemble_set_team_curriculum": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32]),
 }
 MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS
 

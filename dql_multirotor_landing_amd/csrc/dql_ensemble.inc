@@ -1,6 +1,6 @@
 // dql_ensemble.inc: ensembles of sequential Double-Q learners (include/dql.h dql_ensemble_*, DESIGN.md sections 12 and 14): the lane kernels, struct dql_ensemble
 // and its C calls.  A fragment of dql_hip.hip's translation unit, not a header.  Needs from it: fail / HIP_TRY, by_dtype, OP_PROLOGUE, DevOwned, upload_mdpk,
-// upload_schedule, EvTimer, quads_to_fields / unpack_ints, check_config, InitArgs / k_init, k_mark_reset, TickLds; dql_learner.hpp, dql_advance.hpp; and
+// upload_schedule, EvTimer, quads_to_fields / unpack_ints, check_config, InitArgs / k_init, k_mark_reset, TickLds; dql_learner.hpp, dql_advance.hpp, dql_team_levels.hpp; and
 // score_check / score_run / TableSets of dql_greedy.inc (dql_ensemble_score, tables_of_slice).  dql_recipes.inc, included after this file, holds the per-learner recipes (DESIGN.md section 16).
 // ---- sequential learners (dql_ensemble, DESIGN.md section 12) ----
 // One learner per lane (csrc/dql_learner.hpp: learner_periods), workgroups of one wave as in k_rollout; the env stays in registers for all periods of the launch,
@@ -89,23 +89,26 @@ __global__ void k_ens_advance(LearnMem mem, AdvanceMem adv, AdvanceRule rule, in
 }
 
 // a launch's worklist on the host and on the device: build() regroups the live learners by level (build_worklist) or, where recipe_of is set, by (recipe,
-// level) (build_worklist_recipes: then the wave_recipe column exists); upload() copies the waves build() made.  dql_ensemble and EnsRecipes (dql_recipes.inc)
-// each hold one: the capacities differ.
+// level) (build_worklist_recipes: then the wave_recipe column exists), or, where a slot is a team (team_slots: per_wave = 64 / E slots make a wave), the live
+// teams by level (build_team_worklist); upload() copies the waves build() made.  dql_ensemble holds two (learners, and teams once team curriculum mode was
+// switched on) and EnsRecipes (dql_recipes.inc) one: the capacities differ.
 struct EnsWorklist {
-  long long slots = 0;                                   // 64 per wave
+  long long slots = 0;                                   // per_wave per wave
+  int per_wave = ADV_WAVE; bool team_slots = false;
   const int* recipe_of = nullptr; int n_recipes = 0;     // host [L]; null: by level alone
-  std::vector<int> list, wave_recipe, wave_level;        // host [slots], [slots / 64], [slots / 64]
+  std::vector<int> list, wave_recipe, wave_level;        // host [slots], [slots / per_wave], [slots / per_wave]
   int* d_list = nullptr; int* d_wave_recipe = nullptr; int* d_wave_level = nullptr;
-  void resize(long long n_slots, const int* of = nullptr, int n_of = 0) {
-    slots = n_slots; recipe_of = of; n_recipes = n_of;
-    list.assign((size_t)slots, 0); wave_level.assign((size_t)(slots / ADV_WAVE), 0); wave_recipe.assign(of ? (size_t)(slots / ADV_WAVE) : 0, 0);
+  void resize(long long n_slots, const int* of = nullptr, int n_of = 0, int teams_per_wave = 0) {
+    slots = n_slots; recipe_of = of; n_recipes = n_of; team_slots = teams_per_wave > 0; per_wave = team_slots ? teams_per_wave : ADV_WAVE;
+    list.assign((size_t)slots, 0); wave_level.assign((size_t)(slots / per_wave), 0); wave_recipe.assign(of ? (size_t)(slots / per_wave) : 0, 0);
   }
   int build(const int* frozen, const int* level, long long n, unsigned long long* faults) {  // -> the waves to fly
+    if (team_slots) return build_team_worklist(frozen, level, n, per_wave, list.data(), wave_level.data(), slots, faults);
     return recipe_of ? build_worklist_recipes(frozen, level, recipe_of, n, n_recipes, list.data(), wave_recipe.data(), wave_level.data(), slots, faults)
                      : build_worklist(frozen, level, n, list.data(), wave_level.data(), slots, faults);
   }
   int upload(int n_waves) const {
-    HIP_TRY(hipMemcpy(d_list, list.data(), (size_t)n_waves * ADV_WAVE * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_list, list.data(), (size_t)n_waves * per_wave * sizeof(int), hipMemcpyHostToDevice));
     if (recipe_of) HIP_TRY(hipMemcpy(d_wave_recipe, wave_recipe.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_wave_level, wave_level.data(), (size_t)n_waves * sizeof(int), hipMemcpyHostToDevice));
     return DQL_OK;
@@ -147,9 +150,14 @@ struct dql_ensemble {
   // n >= 1.  Members of their own: nstep and ns_* above stay 0 / null on a team ensemble, so dql_ensemble_get_nstep answers as it always did
   int team_nstep = 0;
   uint16_t* tn_key = nullptr; double* tn_val = nullptr; int* tn_len = nullptr;
+  // team curriculum mode (DESIGN.md section 29, dql_team_levels.inc); team_every = 0: the mode is off.  A member of its own: advance_every above stays 0 on an
+  // ensemble in this mode, so every condition on it answers as it always did.  The rule is `rule` above (the two modes refuse each other), the order of
+  // transfer and level change is RecipeRule's; the worklist of teams is allocated by the first dql_ensemble_set_team_curriculum that switches the mode on
+  int team_every = 0, team_order = RCP_ORDER_REFERENCE;
+  EnsWorklist twl;                                            // by level, 64 / E team slots per wave (capacity: team_worklist_capacity)
 };
-// which of the seven learner kernels a launch flies (ens_kernel_of decides, ens_fly switches)
-enum EnsKernel { ENS_K_LEARN, ENS_K_TEAM, ENS_K_TEAM_NSTEP, ENS_K_NSTEP, ENS_K_LEVELS, ENS_K_RECIPES, ENS_K_RECIPES_NSTEP };
+// which of the nine learner kernels a launch flies (ens_kernel_of decides, ens_fly switches)
+enum EnsKernel { ENS_K_LEARN, ENS_K_TEAM, ENS_K_TEAM_NSTEP, ENS_K_NSTEP, ENS_K_LEVELS, ENS_K_RECIPES, ENS_K_RECIPES_NSTEP, ENS_K_TEAM_LEVELS, ENS_K_TEAM_LEVELS_NSTEP };
 // of dql_recipes.inc: the installed recipes let go, the rule learner l advances by, the smallest last_level of the populated recipes, whether a recipe that has
 // a member has n >= 1, the device copy of the recipes' n (null until one was set), dql_ensemble_run's part with recipes installed
 static void ens_recipes_release(dql_ensemble* x);
@@ -158,15 +166,19 @@ static int ens_recipes_min_last_level(const dql_ensemble* x);
 static bool ens_recipes_any_nstep(const dql_ensemble* x);
 static const int* ens_recipes_nstep_table(const dql_ensemble* x);
 static int ens_run_recipes(dql_ensemble* x, int64_t periods, EnsKernel kern);
+static int ens_run_team_levels(dql_ensemble* x, int64_t periods, EnsKernel kern);  // of dql_team_levels.inc: dql_ensemble_run's part in team curriculum mode
 // each later fragment's argument filler, next to its kernel: the kernel's arguments from the ensemble, and the launch of k periods on n_waves waves
 template <typename T> static void launch_learn_recipes(dql_ensemble* x, int k, int n_waves);        // dql_recipes.inc
 template <typename T> static void launch_learn_team(dql_ensemble* x, int k, int n_waves);           // dql_teams.inc
 template <typename T> static void launch_learn_nstep(dql_ensemble* x, int k, int n_waves);          // dql_nstep.inc
 template <typename T> static void launch_learn_team_nstep(dql_ensemble* x, int k, int n_waves);     // dql_team_nstep.inc
 template <typename T> static void launch_learn_recipes_nstep(dql_ensemble* x, int k, int n_waves);  // dql_nstep_recipes.inc
+template <typename T> static void launch_learn_team_levels(dql_ensemble* x, int k, int n_waves);        // dql_team_levels.inc
+template <typename T> static void launch_learn_team_levels_nstep(dql_ensemble* x, int k, int n_waves);  // dql_team_levels.inc
 #define ENS_NSTEP_REFUSED(who) "" who ": n-step targets (dql_ensemble_set_nstep with n >= 1) are for the plain mode, where every learner flies the config's level; set n = 0 first; nothing was changed and nothing was launched"
 #define ENS_TEAM_NSTEP_REFUSED(who) "" who ": team n-step targets (dql_ensemble_set_team_nstep with n >= 1) are for the barrier mode, where every learner flies the config's level: a team ensemble of one env per learner has no per-learner curriculum and no recipes while they are on; set n = 0 first; nothing was changed and nothing was launched"
 #define ENS_TEAMS_REFUSED(who) "" who ": an ensemble with more than one env per learner flies the barrier mode only (teams have no per-learner curriculum and no recipes); nothing was changed and nothing was launched"
+#define ENS_TEAM_LEVELS_REFUSED(who) "" who ": team curriculum mode (dql_ensemble_set_team_curriculum) is on: a team ensemble of one env per learner flies one of the two curriculum modes at a time; switch it off first (advance_every = 0); nothing was changed and nothing was launched"
 #define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
 // the tables of learners [first, first + count) where they live, for the dql_ensemble_* twins of the greedy family (TableSets of dql_greedy.inc; count >= 1 is the
 // twin's own check): the ensemble's device becomes the current one, nothing is copied
@@ -278,8 +290,9 @@ template <typename T> static void launch_learn_levels(dql_ensemble* x, int k, in
 // a team ensemble in curriculum mode flies k_learn_levels, the same learner; n >= 1 is refused on team ensembles and in curriculum mode, and with recipes
 // installed n is a recipe's: one recipe that has a member and n >= 1 makes every launch k_learn_recipes_nstep's.  A team ensemble with team_nstep >= 1 flies
 // k_learn_team_nstep in the barrier mode; team_nstep >= 1 and curriculum mode (possible with one env per learner only) refuse each other, so by_level never
-// meets it.
+// meets it.  Team curriculum mode (team_every, which refuses that curriculum mode and recipes) flies the two team kernels over the worklist of teams.
 static EnsKernel ens_kernel_of(const dql_ensemble* x, bool by_level) {
+  if (x->team_every) return x->team_nstep ? ENS_K_TEAM_LEVELS_NSTEP : ENS_K_TEAM_LEVELS;
   if (by_level) return !x->rcp ? ENS_K_LEVELS : ens_recipes_any_nstep(x) ? ENS_K_RECIPES_NSTEP : ENS_K_RECIPES;
   return x->teams ? (x->team_nstep ? ENS_K_TEAM_NSTEP : ENS_K_TEAM) : x->nstep ? ENS_K_NSTEP : ENS_K_LEARN;
 }
@@ -290,7 +303,7 @@ static int ens_fly(dql_ensemble* x, EnsKernel kern, int k, int n_waves) {
   if (windows && (!x->ns_key || !x->ns_val || !x->ns_len || (kern == ENS_K_RECIPES_NSTEP && !ens_recipes_nstep_table(x))))  // (never taken unless a bug)
     return fail(DQL_ESTATE, kern == ENS_K_NSTEP ? "dql_ensemble_run: n-step targets are on but the pending windows were never allocated; nothing was launched"
                                                 : "dql_ensemble_run: a recipe has n-step targets but the pending windows were never allocated; nothing was launched");
-  if (kern == ENS_K_TEAM_NSTEP && (!x->tn_key || !x->tn_val || !x->tn_len))  // (never taken unless a bug)
+  if ((kern == ENS_K_TEAM_NSTEP || kern == ENS_K_TEAM_LEVELS_NSTEP) && (!x->tn_key || !x->tn_val || !x->tn_len))  // (never taken unless a bug)
     return fail(DQL_ESTATE, "dql_ensemble_run: team n-step targets are on but the envs' pending windows were never allocated; nothing was launched");
   const int rc = upload_schedule(x->cfg, x->j, k, x->d_mgr0, x->d_sched); if (rc) return rc;  // (synchronous: the previous launch has read its schedule)
   by_dtype(x->cfg.dtype, [&](auto t) {
@@ -303,6 +316,8 @@ static int ens_fly(dql_ensemble* x, EnsKernel kern, int k, int n_waves) {
       case ENS_K_LEVELS: launch_learn_levels<T>(x, k, n_waves); break;
       case ENS_K_RECIPES: launch_learn_recipes<T>(x, k, n_waves); break;
       case ENS_K_RECIPES_NSTEP: launch_learn_recipes_nstep<T>(x, k, n_waves); break;
+      case ENS_K_TEAM_LEVELS: launch_learn_team_levels<T>(x, k, n_waves); break;
+      case ENS_K_TEAM_LEVELS_NSTEP: launch_learn_team_levels_nstep<T>(x, k, n_waves); break;
     }
   });
   HIP_TRY(hipGetLastError());
@@ -354,8 +369,8 @@ static bool ens_way_up_scheduled(const bool* have_lv, int level, int last_level)
   for (int k = level + 1; ok && k <= last_level && k < DQL_MAX_LEVELS; ++k) ok = have_lv[k];
   return ok;
 }
-// The one advancing run loop: dql_ensemble_run in curriculum mode, with and without recipes.  The launches are cut at the multiples of advance_every; at such a
-// period index j, before period j is flown, every learner takes its advance step; each launch flies the live learners regrouped by the worklist.  What the two
+// The one advancing run loop: dql_ensemble_run in curriculum mode, with and without recipes, and in team curriculum mode.  The launches are cut at the multiples of advance_every; at such a
+// period index j, before period j is flown, every learner takes its advance step; each launch flies the live learners regrouped by the worklist.  What the
 // modes differ in is passed in: complete(l, level) with the sentence that refuses the call where it fails, the advance kernel's launch, the worklist, the kernel.
 template <typename Complete, typename Advance>
 static int ens_run_advancing(dql_ensemble* x, int64_t periods, EnsKernel kern, EnsWorklist& wl, Complete complete, const char* incomplete, Advance launch_advance) {
@@ -365,7 +380,7 @@ static int ens_run_advancing(dql_ensemble* x, int64_t periods, EnsKernel kern, E
   for (size_t l = 0; l < (size_t)x->n; ++l) if (!complete(l, level[l])) return fail(DQL_EINVAL, incomplete);
   EvTimer timer;
   rc = timer.start(); if (rc) return rc;
-  const long long E = x->advance_every;
+  const long long E = x->team_every ? x->team_every : x->advance_every;
   long long left = periods;
   while (left > 0) {
     if (x->j % E == 0) {  // an advance point
@@ -482,6 +497,8 @@ int dql_ensemble_set_level(dql_ensemble* x, int32_t k) {
     return fail(DQL_EINVAL, "dql_ensemble_set_level: with recipes installed the level must not exceed the smallest last_level of the recipes that have a member; nothing was changed");
   if (!x->rcp && x->advance_every && k > x->rule.last_level)
     return fail(DQL_EINVAL, "dql_ensemble_set_level: in curriculum mode the level must not exceed last_level (raise it with dql_ensemble_set_curriculum first); nothing was changed");
+  if (x->team_every && k > x->rule.last_level)
+    return fail(DQL_EINVAL, "dql_ensemble_set_level: in team curriculum mode the level must not exceed last_level (raise it with dql_ensemble_set_team_curriculum first); nothing was changed");
   HIP_TRY(hipSetDevice(x->device));
   HIP_TRY(hipDeviceSynchronize());
   x->cfg.working_curriculum_step = k;
@@ -510,6 +527,7 @@ int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
   if (periods < 1 || periods > (1ll << 40)) return fail(DQL_EINVAL, "dql_ensemble_run: periods must be in 1..2^40; nothing was launched");
   HIP_TRY(hipSetDevice(x->device));
   const EnsKernel kern = ens_kernel_of(x, x->rcp || x->advance_every);
+  if (x->team_every) return ens_run_team_levels(x, periods, kern);
   if (x->rcp) return ens_run_recipes(x, periods, kern);
   if (x->advance_every) return ens_run_levels(x, periods, kern);
   int rc = DQL_OK;
@@ -532,6 +550,7 @@ int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
 int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t advance_every, const double* ratios, int32_t advance_exhausted) {
   CHECK_ENS(x);
   if (x->envs_per_learner > 1) return fail(DQL_EINVAL, ENS_TEAMS_REFUSED("dql_ensemble_set_curriculum"));
+  if (x->team_every) return fail(DQL_EINVAL, ENS_TEAM_LEVELS_REFUSED("dql_ensemble_set_curriculum"));
   if (advance_every < 0 || advance_every > ADV_MAX_EVERY) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_every must be in 0..4096 (0 turns the mode off); nothing was changed");
   if (advance_every == 0 && x->rcp)
     return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: the mode cannot be switched off (advance_every = 0) while recipes are installed; uninstall them first (dql_ensemble_set_recipes with n_recipes = 0); nothing was changed");
@@ -606,7 +625,7 @@ int dql_ensemble_get_levels(dql_ensemble* x, int32_t* level, int32_t* promoted_a
 int dql_ensemble_n_unfinished(dql_ensemble* x, int64_t* n) {
   CHECK_ENS(x);
   if (!n) return fail(DQL_EINVAL, "null pointer");
-  if (!x->advance_every) return dql_ensemble_n_live(x, n);
+  if (!x->advance_every && !x->team_every) return dql_ensemble_n_live(x, n);
   HIP_TRY(hipSetDevice(x->device));
   std::vector<int> frozen, level, promoted;
   return ens_fetch_levels(x, frozen, level, promoted, n);

@@ -46,6 +46,7 @@
 #include "dql_score_grid.hpp"
 #include "dql_nstep.hpp"
 #include "dql_team_nstep.hpp"
+#include "dql_team_levels.hpp"
 #include "../../include/dql_diag.h"
 
 using namespace dql;
@@ -2082,6 +2083,7 @@ int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
 #include "dql_nstep.inc"
 #include "dql_nstep_recipes.inc"
 #include "dql_team_nstep.inc"
+#include "dql_team_levels.inc"
 #include "dql_score_map.inc"
 #include "dql_model.inc"
 #include "dql_returns.inc"

@@ -123,6 +123,7 @@ extern "C" {
 int dql_ensemble_set_recipes(dql_ensemble* x, int32_t n_recipes, const int32_t* recipe_of) {
   CHECK_ENS(x);
   if (x->envs_per_learner > 1) return fail(DQL_EINVAL, ENS_TEAMS_REFUSED("dql_ensemble_set_recipes"));
+  if (x->team_every) return fail(DQL_EINVAL, ENS_TEAM_LEVELS_REFUSED("dql_ensemble_set_recipes"));
   if (n_recipes < 0 || n_recipes > RCP_MAX) return fail(DQL_EINVAL, "dql_ensemble_set_recipes: n_recipes must be in 0..64 (0 uninstalls); nothing was changed");
   if (n_recipes == 0) {
     HIP_TRY(hipSetDevice(x->device));

@@ -129,29 +129,35 @@ struct LdsTeamWindow {
 struct NoTeamWindows {};
 template <typename TMem> struct TeamWindows { LdsTeamWindow mine; TMem tm; int nstep; };
 
+// which env and which team a lane of a team wave flies (active: one at all), as the kernel's lane map says
+struct TeamLane { long long g, l; bool active; };
+
 #ifdef __HIPCC__  // the barriers have no host restatement: the emulations call the two parts for one lane after the other (dql_team.hpp)
-// Workgroups of one wave; lane = env g; a team is E consecutive lanes, so no team straddles waves and the last wave may hold fewer teams.  Per period: every
+// Workgroups of one wave; a team is E consecutive lanes, so no team straddles waves.  Which env g and team l a lane flies, and whether it flies one at all
+// (active), is the caller's: the identity map g = 64 blockIdx.x + tid of k_learn_team and k_learn_team_nstep, whose last wave may hold fewer teams, or the
+// worklist's of k_learn_team_levels and k_learn_team_levels_nstep (dql_team_levels.inc), in whose waves a slot of E lanes may be empty.  So are the schedules sc
+// and the MdpK the wave flies by (the ensemble's, or its level's).  Lane tid is env tid & (E - 1) of its team under every map.  Per period: every
 // live lane flies its env and leaves its record in LDS; barrier; the first lane of every live team applies the team's E records in order and publishes the next
 // period's threshold and whether the team flies on; barrier.  All teams of a wave run side by side.  The wave leaves when every team in it is frozen.
 // With windows a lane loads its env's window before the first barrier of the launch and stores it beside store_env, after the last; in between only the team's
 // applying lane touches the team's columns, between the two barriers of a period.  The windows of a team frozen at the launch's start are neither loaded nor stored.
-// t: the kernel's TeamArgs; cl / cfgk / tc / kv: its wave prologue's; sRec / sCtl: [64] in LDS.
+// t: the kernel's TeamArgs; cl / cfgk / tc / kv: its wave prologue's; sRec / sCtl: [64] in LDS; lane / sc / mdp: the kernel's lane map, schedules and MdpK.
 template <int XMODE, int TICK, typename T, typename TArgs, typename Wins>
 DQL_DEV void team_wave(const TArgs& t, const SimK<T>& cl, const SimK<T>& cfgk, const TickConsts<TICK, T>& tc, const uint32_t* kv, int tid, TeamRecord* sRec,
-                       TeamCtl* sCtl, const Wins& w) {
+                       TeamCtl* sCtl, const Wins& w, const TeamLane& lane, const LearnSched& sc, const MdpK<T> DQL_CONST_AS* mdp) {
   constexpr bool windows = !std::is_same_v<Wins, NoTeamWindows>;
   const auto& a = t.a;
-  const long long g = (long long)blockIdx.x * 64 + tid;
-  const bool active = g < t.n_envs;
-  const long long l = active ? (g >> t.team_shift) : 0;  // < a.mem.n
+  const bool active = lane.active;
+  const long long g = active ? lane.g : 0;  // < t.n_envs
+  const long long l = active ? lane.l : 0;  // < a.mem.n
   const int lead = tid & ~(t.envs_per_learner - 1);      // the team's first lane: the one that applies
   const double* qa = a.mem.qa + l * DQL_N_CELLS;
   const double* qb = a.mem.qb + l * DQL_N_CELLS;
   const bool applies = active && tid == lead;
   TeamState ts = TeamState{};
-  if (applies) ts = team_load(a.sched, a.mem, l);
+  if (applies) ts = team_load(sc, a.mem, l);
   bool live = active && a.mem.frozen[l] == 0;
-  uint32_t eps_thr = live ? eps_of_episode(a.sched, a.mem.level_episodes[l]) : 0u;
+  uint32_t eps_thr = live ? eps_of_episode(sc, a.mem.level_episodes[l]) : 0u;
   const bool loaded = live;
   Env<T> e = Env<T>{};
   if constexpr (windows) { w.mine.head(0) = 0; w.mine.len(0) = 0; }
@@ -162,12 +168,12 @@ DQL_DEV void team_wave(const TArgs& t, const SimK<T>& cl, const SimK<T>& cfgk, c
   const int np = a.n_periods < LEARN_MAX_PERIODS ? a.n_periods : LEARN_MAX_PERIODS;
   for (int p = 0; p < np; ++p) {
     TeamRecord r{0.0, -1, 0, 0, 0};
-    if (live) r = team_env_period<TICK, XMODE>(cl, cfgk, tc, a.mdp, a.mdp_run, e, qa, qb, eps_thr, a.seed, g, a.j0 + p, a.mgr0[p], a.tick_sched[p], kv);
+    if (live) r = team_env_period<TICK, XMODE>(cl, cfgk, tc, mdp, a.mdp_run, e, qa, qb, eps_thr, a.seed, g, a.j0 + p, a.mgr0[p], a.tick_sched[p], kv);
     sRec[tid] = r;
     __syncthreads();  // the records (and, in the first period, the windows) are in LDS; every row load of this period lies before the first table write of it
     if (applies && live) {
-      if constexpr (windows) team_apply_nstep(a.sched, a.mem, cl.quirks, a.mdp_run.gamma, l, &sRec[tid], t.envs_per_learner, w.nstep, w.mine, ts);  // `mine` of the first lane: the team's columns
-      else team_apply(a.sched, a.mem, cl.quirks, a.mdp_run.gamma, l, &sRec[tid], t.envs_per_learner, ts);
+      if constexpr (windows) team_apply_nstep(sc, a.mem, cl.quirks, a.mdp_run.gamma, l, &sRec[tid], t.envs_per_learner, w.nstep, w.mine, ts);  // `mine` of the first lane: the team's columns
+      else team_apply(sc, a.mem, cl.quirks, a.mdp_run.gamma, l, &sRec[tid], t.envs_per_learner, ts);
       sCtl[tid] = TeamCtl{ts.eps_thr, ts.live ? 1 : 0};
     }
     __syncthreads();  // workgroup-scope release of the applying lanes' table stores and window writes, acquire in front of the next period's row loads (dql_team.hpp)

@@ -34,7 +34,7 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   uint32_t kv_[20];
   const uint32_t* kv = lane_round_keys<T>(a.seed, kv_);
   const LdsTeamWindow mine{sKey + tid, sVal + tid, sHead + tid, sLen + tid};  // this lane's own column: env 0 of it
-  team_wave<XMODE>(t, cl, cfgk, tc, kv, tid, sRec, sCtl, TeamWindows<NstepDev>{mine, ga.tm, ga.nstep});
+  team_wave<XMODE>(t, cl, cfgk, tc, kv, tid, sRec, sCtl, TeamWindows<NstepDev>{mine, ga.tm, ga.nstep}, team_lane_identity(t, tid), a.sched, a.mdp);
 }
 template <typename T> static void launch_learn_team_nstep(dql_ensemble* x, int k, int n_waves) {
   TeamNstepArgs<T> g;

@@ -6,6 +6,11 @@ template <typename T> struct TeamArgs {
   long long n_envs;    // a.mem.n * envs_per_learner: the stride of the state arrays
   int envs_per_learner, team_shift;  // E = 1 << team_shift, a divisor of 64
 };
+// the identity lane map of k_learn_team and k_learn_team_nstep: lane = env g = 64 blockIdx.x + tid, team g >> team_shift; the last wave may hold fewer teams
+template <typename T> DQL_DEV TeamLane team_lane_identity(const TeamArgs<T>& t, int tid) {
+  const long long g = (long long)blockIdx.x * 64 + tid;
+  return TeamLane{g, g >> t.team_shift, g < t.n_envs};
+}
 // The wave prologue and the LDS of a team wave; what the wave does is team_wave's (csrc/dql_team_nstep.hpp), here without windows.
 template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_learn_team(TeamArgs<T> t) {
   const LearnArgs<T>& a = t.a;
@@ -24,7 +29,7 @@ template <typename T, int TICK, int XMODE> __global__ __launch_bounds__(64) __at
   const TickConsts<TICK, T> tc([&]() -> const SimK<T>& { if constexpr (sizeof(T) == 8) return sTickK.k; else return cfgk; }());
   uint32_t kv_[20];
   const uint32_t* kv = lane_round_keys<T>(a.seed, kv_);
-  team_wave<XMODE>(t, cl, cfgk, tc, kv, tid, sRec, sCtl, NoTeamWindows{});
+  team_wave<XMODE>(t, cl, cfgk, tc, kv, tid, sRec, sCtl, NoTeamWindows{}, team_lane_identity(t, tid), a.sched, a.mdp);
 }
 template <typename T> static void launch_learn_team(dql_ensemble* x, int k, int n_waves) {
   TeamArgs<T> g;

@@ -29,6 +29,8 @@ NSTEP_MAX = 16                 # include/dql.h DQL_NSTEP_MAX
 NSTEP_PLAIN_ONLY = "n-step targets (nstep >= 1) are for the plain mode, where every learner flies the config's level: no teams, no per-learner curriculum, no recipes"
 TEAM_NSTEP_TEAMS_ONLY = "team_nstep is for an ensemble made through the team kernel (envs_per_learner > 1 or teams=True); a plain ensemble takes nstep"
 TEAM_NSTEP_BARRIER_ONLY = "team n-step targets (team_nstep >= 1) are for the barrier mode, where every learner flies the config's level: no per-learner curriculum, no recipes"
+TEAM_CURRICULUM_TEAMS_ONLY = "team curriculum mode is for an ensemble made through the team kernel (envs_per_learner > 1 or teams=True); a plain ensemble takes set_curriculum"
+TEAM_CURRICULUM_ONE_MODE = "team curriculum mode and per-learner curriculum mode (set_curriculum, recipes) refuse each other: a team ensemble of one env per learner flies one of them at a time"
 TEAM_SIZES = (1, 2, 4, 8, 16, 32, 64)  # envs per learner (include/dql.h dql_ensemble_create_teams): a team is consecutive lanes of one wave
 TEAMS_BARRIER_ONLY = "an ensemble with more than one env per learner flies the barrier mode only (train_level / curriculum): teams have no per-learner curriculum and no recipes"
 ORDER_REFERENCE, ORDER_PAPER = 0, 1  # Recipe.transfer_order
@@ -179,7 +181,7 @@ class SequentialEnsemble:
         else:
             _lib.check(self.lib.dql_ensemble_create(C.byref(self._c), int(device), self.n, int(seed), log_capacity, C.byref(h)))
         self._h = h
-        self._nstep, self._advance_every, self._team_nstep = 0, 0, 0
+        self._nstep, self._advance_every, self._team_nstep, self._team_every = 0, 0, 0, 0
         self.set_schedules(alpha_table, eps, window, min_successes, max_episodes)
         if int(nstep):
             self.set_nstep(nstep)
@@ -295,6 +297,8 @@ class SequentialEnsemble:
             raise ValueError(NSTEP_PLAIN_ONLY)
         if advance_every and self.__dict__.get("_team_nstep", 0):
             raise ValueError(TEAM_NSTEP_BARRIER_ONLY)
+        if self.__dict__.get("_team_every", 0):
+            raise ValueError(TEAM_CURRICULUM_ONE_MODE)
         r = np.ascontiguousarray(REFERENCE_RATIOS if ratios is None else ratios, dtype=np.float64).ravel()
         if advance_every:
             if not 0 <= last_level < MAX_LEVELS:
@@ -303,6 +307,37 @@ class SequentialEnsemble:
                 raise ValueError("ratios must be five finite numbers")
         _lib.check(self.lib.dql_ensemble_set_curriculum(self._h, last_level, advance_every, _p(r), 1 if advance_exhausted else 0))
         self._advance_every = advance_every
+
+    # ---- team curriculum mode: every team walks the levels by itself (include/dql.h) ----
+    def set_team_curriculum(self, last_level: int = 4, advance_every: int = MAX_ADVANCE_EVERY, ratios=None, advance_exhausted: bool = True,
+                            transfer_order: int = ORDER_REFERENCE):
+        """`set_curriculum` for a team ensemble: at every period index that is a multiple of `advance_every`, a frozen team below `last_level` that promoted
+        (or ran out of episodes, with `advance_exhausted`) transfers ITS finished level, moves up a level with all E of its envs re-entering through reset
+        and their pending windows emptied, and flies on; each launch flies the live teams regrouped by level.  transfer_order: `ORDER_REFERENCE`
+        (`Q[k] = Q[k-1] ratios[k]`, the k = 0 wrap) or `ORDER_PAPER` (`Q[k+1] = Q[k] ratios[k+1]`).  advance_every = 0: mode off.  The levels' schedules are
+        `set_level_schedules`'; `set_team_nstep` may be called before or after.  Every argument is checked before the library is touched."""
+        last_level, advance_every, r, transfer_order = self._checked_team_curriculum(last_level, advance_every, ratios, transfer_order)
+        _lib.check(self.lib.dql_ensemble_set_team_curriculum(self._h, last_level, advance_every, _p(r), 1 if advance_exhausted else 0, transfer_order))
+        self._team_every = advance_every
+
+    def _checked_team_curriculum(self, last_level, advance_every, ratios, transfer_order):
+        """-> (last_level, advance_every, ratios float64[5], transfer_order) as the library takes them; ValueError on what it refuses"""
+        last_level, advance_every, transfer_order = int(last_level), int(advance_every), int(transfer_order)
+        if not self.__dict__.get("teams", False):
+            raise ValueError(TEAM_CURRICULUM_TEAMS_ONLY)
+        if not 0 <= advance_every <= MAX_ADVANCE_EVERY:
+            raise ValueError(f"advance_every must be in 0..{MAX_ADVANCE_EVERY}")
+        if self.__dict__.get("_advance_every", 0) or self.__dict__.get("_recipes", []):
+            raise ValueError(TEAM_CURRICULUM_ONE_MODE)
+        r = np.ascontiguousarray(REFERENCE_RATIOS if ratios is None else ratios, dtype=np.float64).ravel()
+        if advance_every:
+            if not 0 <= last_level < MAX_LEVELS:
+                raise ValueError("last_level must be in 0..4")
+            if r.size != MAX_LEVELS or not np.isfinite(r).all():
+                raise ValueError("ratios must be five finite numbers")
+            if transfer_order not in (ORDER_REFERENCE, ORDER_PAPER):
+                raise ValueError("transfer_order must be 0 (the reference's) or 1 (the paper's)")
+        return last_level, advance_every, r, transfer_order
 
     def set_level_schedules(self, level: int, eps=None, window: int = 100, min_successes: Optional[int] = None, max_episodes: int = 50000):
         """`set_schedules` without the learning rates, for the learners that stand on `level` in curriculum mode (eps default: the reference's for it)"""
@@ -340,6 +375,8 @@ class SequentialEnsemble:
             raise ValueError(NSTEP_PLAIN_ONLY)
         if recipes and self.__dict__.get("_team_nstep", 0):
             raise ValueError(TEAM_NSTEP_BARRIER_ONLY)
+        if self.__dict__.get("_team_every", 0):
+            raise ValueError(TEAM_CURRICULUM_ONE_MODE)
         if not recipes:
             _lib.check(self.lib.dql_ensemble_set_recipes(self._h, 0, None))
             self._recipes = []
@@ -639,6 +676,36 @@ def curriculum_per_learner(ens: SequentialEnsemble, last_level: int = 4, advance
     for k in range(MAX_LEVELS):
         ens.set_level_schedules(k, exploration_rates(k), window, ms, budget)
     ens.set_curriculum(last_level, advance_every, ratios, advance_exhausted)
+    flown = _run_until(ens, ens.n_unfinished, chunk_periods, max_periods, on_chunk)
+    out = ens.levels()
+    out["periods"] = flown
+    return out
+
+
+def curriculum_per_team(ens: SequentialEnsemble, last_level: int = 4, advance_every: int = MAX_ADVANCE_EVERY, ratios=None, advance_exhausted: bool = True,
+                        transfer_order: int = ORDER_REFERENCE, max_episodes: Optional[int] = None, window: int = 100, success_rate: float = 0.96,
+                        chunk_periods: int = 16 * MAX_PERIODS_PER_LAUNCH, max_periods: Optional[int] = None, on_chunk=None, team_nstep: Optional[int] = None):
+    """`curriculum_per_learner` for a team ensemble: every team walks the levels by itself (`SequentialEnsemble.set_team_curriculum`), with the one-step update
+    or, with `team_nstep`, the per-env pending windows (`ens.set_team_nstep(team_nstep)` first: every env's window must be empty; None leaves the ensemble's
+    setting).  The five levels get the schedules `curriculum` gives them, then the ensemble runs until no team is unfinished or `max_periods` are flown.
+    -> `ens.levels()` plus "periods", the periods run."""
+    if not getattr(ens, "teams", False):
+        raise ValueError(TEAM_CURRICULUM_TEAMS_ONLY)
+    ens._checked_team_curriculum(last_level, advance_every, ratios, transfer_order)
+    if int(advance_every) < 1:
+        raise ValueError("advance_every must be positive: curriculum_per_team switches the mode on")
+    ms = min_successes_for(window, success_rate)
+    budget = ens.max_episodes if max_episodes is None else int(max_episodes)
+    for k in range(MAX_LEVELS):
+        _checked_rule(None, k, window, ms, budget, "the eps table must not be empty")
+    if int(chunk_periods) < 1 or (max_periods is not None and int(max_periods) < 0):
+        raise ValueError("chunk_periods must be positive and max_periods not negative")
+    if team_nstep is not None:
+        ens._check_team_nstep(int(team_nstep), True)
+        ens.set_team_nstep(team_nstep)
+    for k in range(MAX_LEVELS):
+        ens.set_level_schedules(k, exploration_rates(k), window, ms, budget)
+    ens.set_team_curriculum(last_level, advance_every, ratios, advance_exhausted, transfer_order)
     flown = _run_until(ens, ens.n_unfinished, chunk_periods, max_periods, on_chunk)
     out = ens.levels()
     out["periods"] = flown

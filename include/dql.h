@@ -726,7 +726,8 @@ int dql_ensemble_get_recipes(dql_ensemble* ens, int32_t* recipe_of);
  * are after it.  No fold, no delay: a literal sequence of update calls.  With E = 1 every output equals dql_ensemble_create's, bit for bit.
  * Every dql_ensemble_* call works on such an ensemble; dql_ensemble_get_state returns n_learners * E envs in env order ([64][n_learners * E] and
  * [7][n_learners * E]), dql_ensemble_set_level sends all of them through reset; tables, counters, log and score stay per learner.  With E > 1 the ensemble
- * flies the barrier mode only: dql_ensemble_set_curriculum and dql_ensemble_set_recipes return DQL_EINVAL with nothing changed and nothing launched.
+ * flies the barrier mode or team curriculum mode (dql_ensemble_set_team_curriculum, below); it has no per-learner curriculum and no recipes:
+ * dql_ensemble_set_curriculum and dql_ensemble_set_recipes return DQL_EINVAL with nothing changed and nothing launched.
  * Refused like dql_ensemble_create, and for an envs_per_learner outside the seven values or n_learners * envs_per_learner > DQL_ENSEMBLE_MAX_LEARNERS. */
 int dql_ensemble_create_teams(const dql_config* cfg, int device, int64_t n_learners, int32_t envs_per_learner, uint64_t seed, int32_t log_capacity,
                               dql_ensemble** out);
@@ -806,6 +807,30 @@ int dql_ensemble_get_recipe_nstep(dql_ensemble* ens, int32_t recipe, int32_t* n)
  * dql_ensemble_get_team_nstep returns n and, where asked for, the windows' lengths, int32 [n_learners * E] in env order. */
 int dql_ensemble_set_team_nstep(dql_ensemble* ens, int32_t n);
 int dql_ensemble_get_team_nstep(dql_ensemble* ens, int32_t* n, int32_t* pending_len_or_null);
+
+/* ---- team curriculum mode: every team walks the levels by itself, n-step targets included ----
+ * A team ensemble (dql_ensemble_create_teams, any E, E = 1 included) with advance_every >= 1: every team stands on a level of its own, starting at the
+ * config's, and dql_ensemble_run is per-learner curriculum mode's for teams.  Its launches are cut at the period indices that are multiples of
+ * advance_every.  At such an index j, before period j is flown, a frozen team below last_level that promoted — or ran out of episodes, with
+ * advance_exhausted = 1 — takes the step a learner takes there: its history entry (promoted_at, episodes_at of the level it leaves) is recorded; the
+ * transfer is applied to ITS OWN two tables, with transfer_order 0 the reference's Q[k] = Q[k-1] * ratios[k] for the finished level k (k = 0 wraps to level
+ * 4), with transfer_order 1 the paper's Q[k+1] = Q[k] * ratios[k+1] (the level-k block kept, no wrap, ratios[0] unused); it moves to level k + 1, entered
+ * at period j; ALL E of its envs re-enter through reset; where the ensemble has team n-step windows, every one of those envs' windows is emptied (a frozen
+ * team's windows are generally not empty, and their entries belong to the episodes the reset abandons: what dql_ensemble_set_level does for everyone); its
+ * per-level episode count, promotion ring, promotion record and frozen flag are cleared.  Each launch flies the live teams regrouped by level, 64 / E teams
+ * to a wave and one level to a wave, so a frozen team costs nothing after the launch it froze in.  A team's period is the team period of the barrier mode,
+ * with the one-step update (team_nstep = 0) or the per-env windows (1 <= team_nstep <= DQL_NSTEP_MAX), at the team's level: that level's MDP constants and
+ * the schedules dql_ensemble_set_level_schedules installed for it; the learning rates stay dql_ensemble_set_schedules'.  A team's results do not depend on
+ * the other teams of the ensemble, nor on how a run is split into calls.  With E = 1 and transfer_order 0 every output equals the same ensemble's under
+ * dql_ensemble_set_curriculum.  dql_ensemble_n_unfinished, dql_ensemble_get_levels and dql_diag_ensemble_launches answer as they do in that mode.
+ * Teams have no recipes: dql_ensemble_set_recipes stays refused for E > 1.
+ * DQL_EINVAL, nothing changed, nothing launched, each with its own sentence: an ensemble not made by dql_ensemble_create_teams; advance_every outside
+ * 0..4096; per-learner curriculum mode on or recipes installed (E = 1 only); with advance_every = 0 (the mode off, the barrier launch again) while teams
+ * stand on different levels; null or non-finite ratios; advance_exhausted or transfer_order outside {0, 1}; last_level below a team's level or above 4.
+ * While the mode is on, dql_ensemble_set_curriculum and dql_ensemble_set_recipes are refused on that ensemble, dql_ensemble_set_level holds k <= last_level,
+ * and dql_ensemble_run refuses while a level on a team's way up to last_level has no schedules.  dql_ensemble_set_team_nstep is accepted before and after
+ * the mode is switched on, under its own rule (no env's window holds entries). */
+int dql_ensemble_set_team_curriculum(dql_ensemble* ens, int32_t last_level, int32_t advance_every, const double* ratios, int32_t advance_exhausted, int32_t transfer_order);
 
 #ifdef __cplusplus
 }

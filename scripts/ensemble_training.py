@@ -4,7 +4,8 @@ one learner per GPU lane (dql_multirotor_landing_amd/ensemble.py).
 
     python scripts/ensemble_training.py --learners 4096 --seed 42 [--launched] [--levels 5] [--episodes 50000] [--score ENVS] --out run.npz
                                         [--per-learner [--advance-every E] [--drop-exhausted] [--max-periods N]] [--recipes FILE.json]
-                                        [--envs-per-learner E [--team-nstep N]] [--score-map] [--preset reference|paper]
+                                        [--envs-per-learner E [--team-nstep N] [--per-team [--advance-every E] [--drop-exhausted] [--max-periods N]]]
+                                        [--score-map] [--preset reference|paper]
                                         [--score-grid FIELD=v1,v2,... [--score-grid ...]]
 
 --launched: the parameters the reference's manager node ran with under roslaunch (config.as_launched_config) instead of the launch file's.
@@ -31,11 +32,16 @@ of the given DqlConfig fields around the simulation flavour's config, all scenar
 section 20).  The report gains `grid`: per scenario its label and the quantiles over learners of the touchdown rate, and the share of learners whose worst
 scenario it is; the .npz gains `grid_touchdown_rate` [scenarios, learners] and `grid_touch_hist` [scenarios, learners, 8].
 --envs-per-learner E: every learner owns a team of E envs (1, 2, 4, ..., 64) and applies the reference's update to their transitions in env order (DESIGN.md
-section 17), so it collects E episodes in the time of one; --learners times E is at most 2^20.  Teams fly the level-by-level driver only: the flag is refused
-together with --per-learner and --recipes.
+section 17), so it collects E episodes in the time of one; --learners times E is at most 2^20.  Teams fly the level-by-level driver or, with --per-team, walk
+the levels by themselves; they have no per-learner curriculum and no recipes: the flag is refused together with --per-learner and --recipes.
+--per-team (with --envs-per-learner; E = 1 flies teams of one): every team walks the levels by itself (ensemble.curriculum_per_team) instead
+of waiting at each level for the slowest team of the ensemble; a team advances at the next period index that is a multiple of E (--advance-every), all of its
+envs re-entering through reset, and each launch carries the live teams only.  Works with --advance-every, --drop-exhausted, --max-periods, --team-nstep and
+--preset paper (the config's quirk word becomes evaluation.Q_PAPER and the transfer order the paper's); refused together with --per-learner, --recipes and
+--nstep.  The .npz records each team's level, the episodes it spent at each level and the period index at which it entered it.
 --team-nstep N (with --envs-per-learner above 1): the team learners update with the uncorrected N-step Double-Q return, 1..16, one pending window per env, the
 E transitions of a period still taken in env order (SequentialEnsemble.set_team_nstep); 0, the default, is the one-step team update.
-Refused together with --nstep, --per-learner and --recipes; N is recorded in the .npz as `team_nstep`.
+Refused together with --nstep, --per-learner and --recipes; works with --per-team; N is recorded in the .npz as `team_nstep`.
 Writes every learner's tables and, per level, its first-promotion episode (-1: the episode budget ran out first); with --per-learner also each learner's level,
 the episodes it spent at each level and the period index at which it entered it."""
 import argparse
@@ -50,7 +56,7 @@ sys.path.insert(0, str(ROOT))
 from dql_multirotor_landing_amd.config import F32, F64, Q_REFERENCE, as_launched_config, training_config  # noqa: E402
 from dql_multirotor_landing_amd import evaluation  # noqa: E402
 from dql_multirotor_landing_amd.ensemble import (LevelSchedule, NSTEP_MAX, ORDER_PAPER, ORDER_REFERENCE, REFERENCE_RATIOS, Recipe, SequentialEnsemble, TEAM_SIZES, curriculum,  # noqa: E402
-                                                 curriculum_per_learner, curriculum_recipes, exploration_rates, min_successes_for, train_level)
+                                                 curriculum_per_learner, curriculum_per_team, curriculum_recipes, exploration_rates, min_successes_for, train_level)
 
 RECIPE_KEYS = {"preset", "name", "quirks", "transfer_order", "ratios", "last_level", "advance_exhausted", "alpha_table", "alpha_min", "levels", "nstep"}
 LEVEL_KEYS = {"eps", "window", "min_successes", "max_episodes"}
@@ -237,8 +243,15 @@ def main():
     ap.add_argument("--preset", default="reference", choices=["reference", "paper"], help="quirks and transfer order of the level-by-level driver (not with --per-learner / --recipes)")
     ap.add_argument("--nstep", type=int, default=0, metavar="N", help="n-step Double-Q targets, 1..16 (0: the reference's one-step update; not with --per-learner / --recipes / --envs-per-learner above 1; with --recipes give each recipe its own \"nstep\" in the file)")
     ap.add_argument("--team-nstep", type=int, default=0, metavar="N", help="with --envs-per-learner above 1: n-step Double-Q targets for the team learners, 1..16, one pending window per env (0: the one-step team update; not with --nstep / --per-learner / --recipes)")
+    ap.add_argument("--per-team", action="store_true", help="every team advances through the levels by itself (with --envs-per-learner; takes --advance-every, --drop-exhausted, --max-periods, --team-nstep and --preset paper; not with --per-learner / --recipes / --nstep)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
+    if a.per_team and a.per_learner:
+        ap.error("--per-team cannot be combined with --per-learner: --per-learner is the plain ensemble's driver (one env per learner), --per-team the team ensemble's")
+    if a.per_team and a.recipes:
+        ap.error("--per-team cannot be combined with --recipes: teams have no recipes; --preset paper gives the team driver the paper's quirk word and transfer order")
+    if a.per_team and a.nstep:
+        ap.error("--per-team cannot be combined with --nstep: --nstep is the plain ensemble's switch; the team learners take --team-nstep")
     if a.preset != "reference" and (a.per_learner or a.recipes):
         ap.error("--preset belongs to the level-by-level driver: with --recipes name the preset in the recipes file")
     if a.score_map and not a.score:
@@ -263,13 +276,13 @@ def main():
         ap.error("--team-nstep cannot be combined with --per-learner: teams fly the level-by-level (barrier) driver only")
     if a.team_nstep and a.recipes:
         ap.error("--team-nstep cannot be combined with --recipes: teams fly the level-by-level (barrier) driver only; give each recipe its own \"nstep\" in the file instead")
-    if a.team_nstep and a.envs_per_learner < 2:
+    if a.team_nstep and a.envs_per_learner < 2 and not a.per_team:
         ap.error("--team-nstep needs a team ensemble: give --envs-per-learner above 1 (with one env per learner use --nstep)")
     dtype = F64 if a.f64 else F32
     quirks = evaluation.Q_PAPER if a.preset == "paper" else Q_REFERENCE
     cfg = as_launched_config(dtype=dtype, quirks=quirks) if a.launched else training_config(0, dtype=dtype, quirks=quirks)
     ens = SequentialEnsemble(cfg, a.learners, seed=a.seed, device=a.device, max_episodes=a.episodes, envs_per_learner=a.envs_per_learner, nstep=a.nstep,
-                             team_nstep=a.team_nstep)
+                             team_nstep=a.team_nstep, teams=True if a.per_team else None)
     try:
         def report(e, h):
             p = h["promotion_episode"]
@@ -289,6 +302,11 @@ def main():
             recipe_nstep = [int(r.nstep) for r in ens.recipes()[0]]  # as the library holds them
             extra = {"level": h["level"], "episodes_at": h["episodes_at"], "entered_period": h["entered_period"], "recipe_of": recipe_of,
                      "recipe_nstep": np.asarray(recipe_nstep, np.int32)}
+        elif a.per_team:
+            h = curriculum_per_team(ens, last_level=a.levels - 1, advance_every=a.advance_every, advance_exhausted=not a.drop_exhausted,
+                                    transfer_order=ORDER_PAPER if a.preset == "paper" else ORDER_REFERENCE, max_episodes=a.episodes, max_periods=a.max_periods, on_chunk=progress)
+            hist = [{"promotion_episode": h["promoted_at"][k], "periods": h["periods"]} for k in range(a.levels)]
+            extra = {"level": h["level"], "episodes_at": h["episodes_at"], "entered_period": h["entered_period"], "per_team": np.int32(1)}
         elif a.per_learner:
             h = curriculum_per_learner(ens, last_level=a.levels - 1, advance_every=a.advance_every, advance_exhausted=not a.drop_exhausted, max_episodes=a.episodes,
                                        max_periods=a.max_periods, on_chunk=progress)
