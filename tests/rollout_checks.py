@@ -45,9 +45,15 @@ def case_config(case_id):
     raise KeyError(case_id)
 
 
-def stepwise_first_episodes(stepper, tables, max_steps, trace_envs=0):
+def pack_decision(idx_x, idx_y, action):
+    """one non-negative word per env and period of what the agent saw and chose: 10 bits each for idx_x and idx_y (945 states; -1 becomes 1023), 2 for the action"""
+    return ((idx_x.astype(np.int32) & 0x3FF) << 12) | ((idx_y.astype(np.int32) & 0x3FF) << 2) | (action.astype(np.int32) & 3)
+
+
+def stepwise_first_episodes(stepper, tables, max_steps, trace_envs=0, decisions=False):
     """{"code", "steps" int32 [n], <record field> float64 [n], "trace" [max_steps + 1][n_trace][trace_envs] or None} of `stepper`'s first episodes.
-    `stepper`: a fresh Engine or Oracle (step index 0, no period flown)."""
+    `stepper`: a fresh Engine or Oracle (step index 0, no period flown).  With `decisions`, also "decisions": int32 [max_steps + 1][n], pack_decision() of
+    every period the env flew (the one its episode ended in included), -1 after."""
     qa, qb = tables
     stepper.set_tables(qa, qb, None)
     rn, inames = stepper.field_names(False), stepper.field_names(True)
@@ -62,6 +68,9 @@ def stepwise_first_episodes(stepper, tables, max_steps, trace_envs=0):
             code = np.full(n, -1, np.int32); steps = np.zeros(n, np.int32); rec = np.zeros((len(RECORD_FIELDS), n))
             flying = np.ones(n, bool)
             trace = np.full((max_steps + 1, len(TRACE_FIELDS), trace_envs), np.nan) if trace_envs else None
+            words = np.full((max_steps + 1, n), -1, np.int32) if decisions else None
+        if decisions:
+            words[j][flying] = pack_decision(ints[ii["idx_x"]], ints[ii["idx_y"]], ints[ii["action"]])[flying]
         if trace_envs:
             m = flying[:trace_envs]
             row = np.concatenate([reals[ri][:, :trace_envs], ints[[ii["action"], ii["idx_x"], ii["idx_y"]]][:, :trace_envs].astype(np.float64)])
@@ -73,6 +82,8 @@ def stepwise_first_episodes(stepper, tables, max_steps, trace_envs=0):
             break
     steps[flying] = ints[ii["step_count"]][flying]; rec[:, flying] = reals[ri][:, flying]  # still flying: the state after the last period
     out = {"code": code, "steps": steps, "trace": trace}
+    if decisions:
+        out["decisions"] = words
     out.update({f: rec[k] for k, f in enumerate(RECORD_FIELDS)})
     return out
 

@@ -5,7 +5,13 @@ the numbers tests/test_gpu_parity.py's tolerances are set from.  usage: python t
 `python tools/exp_f32_vs_f64.py flavours [oracle|hip]`: the flavours of tests/f32_step_checks.py instead (simulation / training at levels 2 and 4, paper
 mode, greedy on the stage-4 tables, handed over so that the 16 periods contain the episode ends), one period per call, with the float32 CPU oracle
 (default: needs no GPU; it is bit-identical to the kernel) or the HIP engine as the float32 side; then the G13 flights in float32 against the recording:
-max error per signal column, and the bound the tests assert (4 x the maximum, rounded up to one significant digit).  -> profiles/f32_step_vs_f64_flavours.jsonl"""
+max error per signal column, and the bound the tests assert (4 x the maximum, rounded up to one significant digit).  -> profiles/f32_step_vs_f64_flavours.jsonl
+
+`python tools/exp_f32_vs_f64.py episodes [out.jsonl]`: whole first episodes of 4 096 envs in float32 against their float64 twins on the CPU oracle, greedy on the
+stage-4 tables, for every flavour and seed of tests/episode_dtype_checks.py (needs no GPU): per pair the decision counts, the terminal codes, McNemar's
+counts, the paired means, the maxima per field group at the terminal of the decision-concordant envs and those envs' mean difference of the return; then
+the two tables of bounds that module asserts.
+-> profiles/f32_episodes_vs_f64.jsonl"""
 import json
 import sys
 from pathlib import Path
@@ -13,7 +19,7 @@ from pathlib import Path
 import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-from dql_multirotor_landing_amd.config import DqlConfig, F32, F64  # noqa: E402
+from dql_multirotor_landing_amd.config import CHECK_NAMES, DqlConfig, F32, F64  # noqa: E402
 from dql_multirotor_landing_amd.engine import Engine  # noqa: E402
 from dql_multirotor_landing_amd.state_layout import to_f32_filter_state  # noqa: E402
 from oracle.oracle import Oracle  # noqa: E402
@@ -71,9 +77,45 @@ def flavours(side):
                       "asserted_bound_4x_one_digit_up": {k: one_digit_up(4 * w) for k, w in zip(sc.G13_SIGNALS, worst.tolist())}}), flush=True)
 
 
+def episodes(out_path):
+    import time
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tests"))
+    import episode_dtype_checks as ec
+    import rollout_checks as rc
+    make = lambda cfg, n, seed: Oracle(cfg, n, seed=seed, n_threads=16)
+    tables = rc.stage4_tables()
+    lines = []
+    for name, (make_cfg, kind) in ec.FLAVOURS.items():
+        for seed in ec.SEEDS:
+            t0 = time.perf_counter()
+            pair = ec.paired_flights(make, make_cfg, tables, ec.N_ENVS, seed, ec.MAX_STEPS)
+            seconds = time.perf_counter() - t0
+            m = ec.compare(pair)
+            bal = ec.balance(pair, kind, make_cfg(F64).two_axis, ~m["concordant"])
+            b, c = bal["landing_f32_only"], bal["landing_f64_only"]
+            row = {"flavour": name, "seed": seed, "n": m["n"], "max_steps": ec.MAX_STEPS, "f32_side": "oracle", "seconds_for_the_pair": round(seconds, 2),
+                   "f64_terminal_codes": rc.histogram(pair[F64]["code"]), "envs_with_a_differing_decision": m["discordant_envs"],
+                   "differing_period_slots": m["differing_slots"], "f64_periods_flown": m["f64_periods_flown"],
+                   "envs_with_a_differing_decision_while_both_fly": m["discordant_while_both_fly"], "terminal_code_differs": m["terminal_code_differs"],
+                   "concordant_envs_with_another_code_or_step_count": int(m["strict_exceptions"].size), "landing_outcome": CHECK_NAMES[ec.landing_code(kind)],
+                   "landing_f32_only": b, "landing_f64_only": c, "mcnemar_z": (abs(b - c) / (b + c) ** 0.5 if b + c else 0.0),
+                   "paired_mean_standard_error_and_flights_that_part": bal["paired"], "paired_mean_z": {f: (abs(v[0]) / v[1] if v[1] else 0.0) for f, v in bal["paired"].items()},
+                   "paired_mean_z_of_all_pairs_unasserted": {f: (abs(v[0]) / v[1] if v[1] else 0.0) for f, v in bal["paired_raw"].items()},
+                   "max_abs_at_terminal": m["max_abs_at_terminal"], "max_abs_per_field": m["max_abs_per_field"],
+                   "concordant_mean_difference": m["concordant_mean_difference"], "concordant_return_difference_vs_terminal_offset": ec.return_vs_offset(pair, m, make_cfg(F64))}
+            lines.append(json.dumps(row))
+            print(lines[-1], flush=True)
+    Path(out_path).write_text("\n".join(lines) + "\n")
+    bounds, _ = ec.bounds_from_profile(out_path)
+    print("episode_dtype_checks.BOUNDS (4 x the maxima, one digit up):", bounds, flush=True)
+    print("episode_dtype_checks.CONCORDANT_MEAN_BOUNDS (4 x the larger seed, one digit up):", ec.concordant_mean_bounds_from_profile(out_path), flush=True)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "flavours":
         return flavours(sys.argv[2] if len(sys.argv) > 2 else "oracle")
+    if len(sys.argv) > 1 and sys.argv[1] == "episodes":
+        return episodes(sys.argv[2] if len(sys.argv) > 2 else Path(__file__).resolve().parent.parent / "profiles" / "f32_episodes_vs_f64.jsonl")
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
     for case, kw in CASES.items():
         for periods in (1, 16):
