@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 from pathlib import Path
 
 from .config import DqlConfigC, N_CHECK_CODES
@@ -22,6 +23,14 @@ OP_SUM, OP_MAX = 0, 1
 class DqlStatsC(C.Structure):
     _fields_ = [("agent_steps", C.c_int64), ("decisions", C.c_int64), ("episodes", C.c_int64),
                 ("by_code", C.c_int64 * N_CHECK_CODES), ("reward_sum", C.c_double), ("physics_ticks", C.c_int64)]
+
+
+VIEW_OBS = 8  # include/dql.h DQL_VIEW_OBS
+VIEW_POINTERS = ("obs", "reward", "cumulative_reward", "idx_x", "idx_y", "step_count", "done", "was_reset", "code", "bad_actions")
+
+
+class DqlViewC(C.Structure):  # include/dql.h dql_view
+    _fields_ = [("real_dtype", C.c_int32), ("reserved", C.c_int32)] + [(k, C.c_void_p) for k in VIEW_POINTERS]
 
 
 # every symbol include/dql.h and include/dql_diag.h (dql_diag_*: measurement and self-test, not part of the drop-in boundary) declare: name -> (restype, argtypes)
@@ -43,6 +52,8 @@ SYMBOLS = {
     "dql_step": (C.c_int, [_vp, _vp]),
     "dql_step_dev": (C.c_int, [_vp, _vp]),
     "dql_step_outputs": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dql_view_dev": (C.c_int, [_vp, C.POINTER(DqlViewC)]),
+    "dql_reset_dev": (C.c_int, [_vp, _vp]),
     "dql_train_steps": (C.c_int, [_vp, _i32, _dbl]),
     "dql_eval_steps": (C.c_int, [_vp, _i32]),
     "dql_get_states": (C.c_int, [_vp, _vp, _vp]),
@@ -208,11 +219,12 @@ SYMBOLS = {
 MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS
 
 _lib = None
+torch_came_first = None  # was torch already imported when the library was loaded?  (tensor_env: torch's HIP runtime has to be the process's)
 
 
 def load():
     """Load the HIP library; raise if it has not been built (python -c 'import __graft_entry__ as g; g.build()')."""
-    global _lib
+    global _lib, torch_came_first
     if _lib is None:
         if not LIB_PATH.exists():
             raise RuntimeError(f"{LIB_PATH} not found: build the HIP extension first (__graft_entry__.build()); there is no CPU fallback")
@@ -223,6 +235,7 @@ def load():
             fn.argtypes = args
         if lib.dql_abi_version() != ABI_VERSION:
             raise RuntimeError("libdql_hip.so ABI version mismatch")
+        torch_came_first = "torch" in sys.modules
         _lib = lib
     return _lib
 

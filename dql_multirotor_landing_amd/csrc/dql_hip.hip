@@ -47,6 +47,7 @@
 #include "dql_nstep.hpp"
 #include "dql_team_nstep.hpp"
 #include "dql_team_levels.hpp"
+#include "dql_view.hpp"
 #include "../../include/dql_diag.h"
 
 using namespace dql;
@@ -2088,5 +2089,6 @@ int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
 #include "dql_model.inc"
 #include "dql_returns.inc"
 #include "dql_score_grid.inc"
+#include "dql_view.inc"
 #include "dql_agent.inc"
 #include "dql_comm.inc"

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .config import ACC_LEN, CHECK_NAMES, DqlConfig, N_CELLS, TABLE_SHAPE
+from .config import ACC_LEN, CHECK_NAMES, DqlConfig, F32, F64, N_CELLS, TABLE_SHAPE
 
 
 def _p(a):
@@ -66,6 +66,34 @@ class Engine:
     def step_dev(self, dev_ptr: int):
         """one agent step with actions that already live in device memory (n uint8, e.g. written by the caller's own policy kernel)"""
         _lib.check(self.lib.dql_step_dev(self._h, C.c_void_p(int(dev_ptr))))
+
+    # the observation row of view_dev, by the names of field_names()
+    VIEW_OBS_FIELDS = ("obs_p_x", "obs_v_x", "obs_a_x", "pitch_sp", "obs_p_y", "obs_v_y", "obs_a_y", "roll_sp")
+
+    def view_dev(self, *, real_dtype: int = F32, obs: int = 0, reward: int = 0, cumulative_reward: int = 0, idx_x: int = 0, idx_y: int = 0, step_count: int = 0,
+                 done: int = 0, was_reset: int = 0, code: int = 0, bad_actions: int = 0):
+        """what `step_outputs` returns plus the continuous observation, written into the CALLER'S device buffers by one kernel on the engine's stream; returns
+        without waiting (include/dql.h dql_view_dev).  Every argument is an integer device address, 0 = skip that output: obs [n, 8] rows of VIEW_OBS_FIELDS
+        (16-byte aligned), reward / cumulative_reward [n], all three of `real_dtype` (F32 / F64, whatever the engine's dtype); idx_x, idx_y, step_count int32 [n];
+        done, was_reset uint8 [n]; code int8 [n]; bad_actions one uint64 (the count as it stands, not cleared).  The buffers must outlive the kernel."""
+        ptrs = {"obs": obs, "reward": reward, "cumulative_reward": cumulative_reward, "idx_x": idx_x, "idx_y": idx_y, "step_count": step_count, "done": done,
+                "was_reset": was_reset, "code": code, "bad_actions": bad_actions}
+        if real_dtype not in (F32, F64):
+            raise ValueError("real_dtype must be F32 (0) or F64 (1), the element type of obs, reward and cumulative_reward")
+        for k, p in ptrs.items():
+            if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 0 <= int(p) < 1 << 64:
+                raise ValueError(f"{k} must be a device address given as a non-negative integer (0 = skip this output)")
+            ptrs[k] = int(p)
+        if ptrs["obs"] % 16:
+            raise ValueError("obs must be 16-byte aligned: its rows are written as 16-byte vectors")
+        v = _lib.DqlViewC(real_dtype=int(real_dtype), reserved=0, **{k: (p or None) for k, p in ptrs.items()})
+        _lib.check(self.lib.dql_view_dev(self._h, C.byref(v)))
+
+    def reset_dev(self, dev_ptr: int):
+        """`reset(mask)` with a mask that already lives in device memory (n uint8, non-zero = reset): no copy and no wait; the buffer must outlive the kernel"""
+        if isinstance(dev_ptr, bool) or not isinstance(dev_ptr, (int, np.integer)) or not 0 < int(dev_ptr) < 1 << 64:
+            raise ValueError("dev_ptr must be the device address of an n-byte mask; reset(None) marks every env")
+        _lib.check(self.lib.dql_reset_dev(self._h, C.c_void_p(int(dev_ptr))))
 
     def reset(self, mask=None):
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)

@@ -180,6 +180,30 @@ int dql_step_outputs(dql_ctx* ctx, int32_t* idx_x, int32_t* idx_y, double* rewar
 /* same with the actions already in device memory (n_envs bytes, readable on the context's device): no copy, no host-side
  * validation, fully asynchronous (the buffer must stay valid until the step has run); values other than 0 / 1 act as "hold" */
 int dql_step_dev(dql_ctx* ctx, const uint8_t* dev_actions);
+/* Device-resident step outputs: what dql_step_outputs returns, plus the continuous observation, written into CALLER-OWNED DEVICE buffers by one kernel
+ * on the context's stream.  The call returns without waiting; the buffers must stay valid until the kernel has run.  Every pointer is a device address
+ * readable and writable on the context's device, and every pointer may be NULL: that output is skipped.  The view reports the state as it stands after
+ * the stream's earlier work (dql_step_dev, dql_step, dql_train_steps, dql_eval_steps).
+ * An obs row holds the state fields obs_p_x, obs_v_x, obs_a_x, pitch_sp, obs_p_y, obs_v_y, obs_a_y, roll_sp; reward is the field reward,
+ * cumulative_reward is cum_x; the integer and byte outputs are what dql_step_outputs decodes from the same words.
+ * Conversion of a context element to real_dtype: the same type keeps the bits, float -> double is exact, double -> float is one round-to-nearest-even
+ * cast.  DQL_EINVAL (nothing launched, no buffer touched): a null ctx or view, real_dtype neither DQL_F32 nor DQL_F64, reserved != 0, obs not 16-byte
+ * aligned, a population context.  A view whose pointers are all NULL returns DQL_OK and launches nothing. */
+#define DQL_VIEW_OBS 8
+typedef struct dql_view {
+  int32_t real_dtype;          /* DQL_F32 or DQL_F64: element type of obs, reward, cumulative_reward — independent of the context's dtype */
+  int32_t reserved;            /* must be 0 */
+  void*    obs;                /* [n_envs][DQL_VIEW_OBS] row-major, 16-byte aligned */
+  void*    reward;             /* [n_envs] */
+  void*    cumulative_reward;  /* [n_envs] */
+  int32_t* idx_x; int32_t* idx_y; int32_t* step_count;   /* [n_envs] each */
+  uint8_t* done; uint8_t* was_reset; int8_t* code;       /* [n_envs] each */
+  uint64_t* bad_actions;       /* one word: the count of out-of-range external actions as it stands, NOT cleared (dql_step_outputs / dql_stats_get report and clear it) */
+} dql_view;
+int dql_view_dev(dql_ctx* ctx, const dql_view* view);
+/* dql_reset with a mask that already lives in device memory (n_envs bytes, non-zero = reset): read by the marking kernel itself, no copy and no
+ * wait; the buffer must stay valid until the kernel has run.  NULL is refused (dql_reset with NULL marks every env). */
+int dql_reset_dev(dql_ctx* ctx, const uint8_t* dev_mask);
 /* n fused agent steps: on-device eps-greedy guess + step + TD-target accumulation + table apply
  * (pkg/trainer.py:191-212 loop body for all envs at once) */
 int dql_train_steps(dql_ctx* ctx, int32_t n_steps, double eps);
