@@ -132,6 +132,8 @@ SYMBOLS = {
     "dql_diag_score_map_last": (C.c_int, [C.POINTER(_dbl), _vp]),
     "dql_model": (C.c_int, [_cfgp, C.c_int, _i32, _i64, _i32, _u64, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dql_diag_model_last": (C.c_int, [C.POINTER(_dbl), _vp]),
+    "dql_model_split": (C.c_int, [_cfgp, C.c_int, _i32, _i64, _i32, _u64, _i32, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dql_diag_model_split_last": (C.c_int, [C.POINTER(_dbl), _vp]),
     "dql_returns": (C.c_int, [_cfgp, C.c_int, _i32, _i64, _i32, _u64, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dql_diag_returns_last": (C.c_int, [C.POINTER(_dbl), C.POINTER(_dbl), _vp]),
     "dql_score_grid": (C.c_int, [_vp, _i32, C.c_int, _i64, _i64, _i32, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -189,6 +191,7 @@ SYMBOLS = {
     "dql_ensemble_score": (C.c_int, [_vp, _cfgp, _i64, _i64, _i64, _i32, _u64, _i32, _vp, _vp, _vp, _vp]),
     "dql_ensemble_score_map": (C.c_int, [_vp, _cfgp, _i64, _i64, _i64, _i32, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dql_ensemble_model": (C.c_int, [_vp, _cfgp, _i64, _i64, _i64, _i32, _u64, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "dql_ensemble_model_split": (C.c_int, [_vp, _cfgp, _i64, _i64, _i64, _i32, _u64, _i32, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dql_ensemble_returns": (C.c_int, [_vp, _cfgp, _i64, _i64, _i64, _i32, _u64, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp]),
     "dql_ensemble_score_grid": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _i64, _i32, _u64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "dql_diag_ensemble_last": (C.c_int, [_vp, C.POINTER(_dbl)]),

@@ -523,6 +523,21 @@ class SequentialEnsemble:
                                                _p(steps_sum)))
         return ops.model_result(self.lib, pairs, reward_fx, terminal, by_code, steps_sum, timing)
 
+    def split_model(self, eval_cfg: DqlConfig, feature, cut, envs_per_learner: int = 64, seed: int = 123, eps: float = 0.1, episodes: int = 1, max_steps: int = 600,
+                    first: int = 0, count: Optional[int] = None, timing: dict = None):
+        """`ops.split_model` of learners first .. first + count - 1 on their tables where they live (no host copy).  The ensemble is left as it was.  At most
+        ops.MODEL_SPLIT_MAX_TABLES learners per call (21.4 MB of pair table per learner): slice with first / count."""
+        from . import ops
+        feature, cut = ops.split_feature_code(feature), ops.split_cut_array(cut)
+        first, count = self._slice(first, count)
+        n, episodes, max_steps, eps = int(envs_per_learner), int(episodes), int(max_steps), float(eps)
+        ops.split_model_check_args(eval_cfg, count, n, episodes, max_steps, eps)
+        pairs, reward_fx, terminal, feat_sum_fx, by_code, steps_sum = ops.split_model_buffers(count)
+        c = eval_cfg.to_c()
+        _lib.check(self.lib.dql_ensemble_model_split(self._h, C.byref(c), first, count, n, episodes, int(seed), max_steps, eps, feature, _p(cut), _p(pairs), _p(reward_fx),
+                                                     _p(terminal), _p(feat_sum_fx), _p(by_code), _p(steps_sum)))
+        return ops.split_model_result(self.lib, feature, cut, pairs, reward_fx, terminal, feat_sum_fx, by_code, steps_sum, timing)
+
     def returns_map(self, eval_cfg: DqlConfig, envs_per_learner: int = 64, seed: int = 123, eps: float = 0.1, gamma: float = 0.99, episodes: int = 1, max_steps: int = 600,
                     first: int = 0, count: Optional[int] = None, timing: dict = None):
         """`ops.returns_map` of learners first .. first + count - 1 on their tables where they live (no host copy).  The ensemble is left as it was.  At most

@@ -315,6 +315,82 @@ def model_divergence(pairs_a, terminal_a, pairs_b, terminal_b, min_visits: int =
     return np.where(ok, tv, np.nan)
 
 
+# the transition model split by a hidden variable (ops.split_model, include/dql.h dql_model_split): pure numpy readers of its result
+SPLIT_FRAC_BITS = 20  # include/dql.h DQL_SPLIT_FRAC_BITS
+
+
+def _state_visits(result):
+    pairs, terminal = np.asarray(result["pairs"]), np.asarray(result["terminal"])
+    if pairs.ndim != 4 or pairs.shape[1:] != (2, N_CELLS, N_STATES) or terminal.ndim != 4 or terminal.shape[:3] != pairs.shape[:3]:
+        raise ValueError("a split-model result: pairs [K, 2, 2835, 945] and terminal [K, 2, 2835, codes]")
+    visits = pairs.sum(axis=-1, dtype=np.int64) + terminal.sum(axis=-1, dtype=np.int64)  # [K, 2, 2835]
+    return visits, visits.sum(axis=1).reshape(len(visits), N_STATES, 3).sum(axis=-1)
+
+
+def feature_means(result):
+    """float64 [K, 945]: per state the mean of the split feature over the counted decisions taken in it, feat_sum_fx / 2^20 / visits of the state.  An unvisited
+    state gets +inf, which is a valid cut (nothing is in its half 1)."""
+    _, sv = _state_visits(result)
+    fs = np.asarray(result["feat_sum_fx"])
+    if fs.shape != sv.shape:
+        raise ValueError("feat_sum_fx [K, 945]")
+    return np.where(sv > 0, fs.astype(np.float64) / float(1 << SPLIT_FRAC_BITS) / np.where(sv > 0, sv, 1), np.inf)
+
+
+def split_divergence(result, min_visits: int = 30):
+    """float64 [K, 2835]: per cell the total-variation distance between the next-outcome distributions of the two halves (`model_divergence` of half 0 against
+    half 1: next states and terminal codes as one alphabet).  NaN where either half has fewer than `min_visits` (>= 1) visits."""
+    _state_visits(result)
+    pairs, terminal = np.asarray(result["pairs"]), np.asarray(result["terminal"])
+    return np.stack([model_divergence(pairs[k, 0], terminal[k, 0], pairs[k, 1], terminal[k, 1], min_visits) for k in range(len(pairs))])
+
+
+def _weighted_quantile(x, w, q):
+    """the smallest x at which the cumulative weight reaches q of the total (x, w 1-d, w > 0)"""
+    order = np.argsort(x, kind="stable")
+    x, cw = x[order], np.cumsum(w[order])
+    return float(x[min(int(np.searchsorted(cw, q * cw[-1], side="left")), len(x) - 1)])
+
+
+def aliasing_table(by_feature, coin, min_visits: int = 30):
+    """One row per feature: is it hidden state of the discretised MDP?  `by_feature`: name -> the `ops.split_model` result taken at that feature's mean cut;
+    `coin`: the coin's result over the same flights (cut 0.5).  All table sets of a result are read together.  A cell is COMPARED for a feature if both halves
+    have `min_visits` under the feature AND under the coin, so that both distances are taken over the same cells.  Per feature a dict:
+      cells             cells compared
+      median            the visit-weighted median distance between the feature's halves over them (the smallest distance at which the cumulative visits reach half)
+      coin_median       the coin's, weighted the same way over the same cells
+      coin_p95          the coin's 95th percentile over the same cells (unweighted, numpy's linear interpolation)
+      above_coin_p95    the share of the compared cells whose distance lies above coin_p95
+      half1_share       the share of all counted decisions that fell in half 1
+    NaN where no cell is compared.  A variable is hidden state if its halves lie further apart than the coin's do."""
+    d_coin = split_divergence(coin, min_visits).ravel()
+    out = {}
+    for name, r in by_feature.items():
+        visits, _ = _state_visits(r)
+        d = split_divergence(r, min_visits).ravel()
+        if d.shape != d_coin.shape:
+            raise ValueError(f"{name}: as many table sets as the coin's result")
+        both = ~np.isnan(d) & ~np.isnan(d_coin)
+        w = visits.sum(axis=1).ravel()[both].astype(np.float64)
+        row = {"cells": int(both.sum()), "half1_share": float(visits[:, 1].sum() / max(int(visits.sum()), 1))}
+        if row["cells"]:
+            p95 = float(np.percentile(d_coin[both], 95))
+            row.update(median=_weighted_quantile(d[both], w, 0.5), coin_median=_weighted_quantile(d_coin[both], w, 0.5), coin_p95=p95,
+                       above_coin_p95=float((d[both] > p95).mean()))
+        else:
+            row.update(median=float("nan"), coin_median=float("nan"), coin_p95=float("nan"), above_coin_p95=float("nan"))
+        out[name] = row
+    return out
+
+
+def format_aliasing_table(table):
+    """the rows of `aliasing_table` as text, one line per feature"""
+    lines = [f"{'feature':<12} {'cells':>6} {'median':>8} {'coin med':>9} {'coin p95':>9} {'> p95':>7} {'half 1':>7}"]
+    for name, r in table.items():
+        lines.append(f"{name:<12} {r['cells']:>6d} {r['median']:>8.4f} {r['coin_median']:>9.4f} {r['coin_p95']:>9.4f} {r['above_coin_p95']:>7.3f} {r['half1_share']:>7.3f}")
+    return "\n".join(lines)
+
+
 def value_calibration(qa, qb, visits, return_fx, greedy=None, min_visits: int = 30):
     """The tables' values held against the realised returns of `ops.returns_map` (one table set), pure numpy.  `qa`, `qb`: float64 [2835]; `visits`, `return_fx`:
     int64 [2835]; `greedy`: the tables' greedy action per state, [945] (ops' predict), or None.  Returns a dict.  Per cell, float64 [2835]:

@@ -446,6 +446,78 @@ def transition_model(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, eps
     return model_result(lib, pairs, reward_fx, terminal, by_code, steps_sum, timing)
 
 
+MODEL_SPLIT_MAX_TABLES, SPLIT_FRAC_BITS = 8, 20  # include/dql.h DQL_MODEL_SPLIT_MAX_TABLES (21.4 MB of pair table per set), DQL_SPLIT_FRAC_BITS
+# include/dql.h DQL_SPLIT_*: a feature's code is its place in this tuple
+SPLIT_FEATURES = ("coin", "obs_p_x", "obs_v_x", "obs_a_x", "pitch_sp", "mp_phase", "mp_u", "altitude", "v_z", "step", "prev_action")
+
+
+def split_feature_code(feature) -> int:
+    """a DQL_SPLIT_* code from a code or a name ("pitch_sp", "PITCH_SP", "DQL_SPLIT_PITCH_SP")"""
+    if isinstance(feature, str):
+        name = feature.lower()
+        name = name[len("dql_split_"):] if name.startswith("dql_split_") else name
+        if name not in SPLIT_FEATURES:
+            raise ValueError(f"no split feature named {feature!r}: one of {', '.join(SPLIT_FEATURES)}")
+        return SPLIT_FEATURES.index(name)
+    if isinstance(feature, (bool, float)) or not isinstance(feature, (int, np.integer)) or not 0 <= int(feature) < len(SPLIT_FEATURES):
+        raise ValueError(f"a split feature is a name or a code in 0..{len(SPLIT_FEATURES) - 1}, not {feature!r}")
+    return int(feature)
+
+
+def split_cut_array(cut):
+    """the per-state cut as the C calls take it: float64 [945] from a scalar or a [945] array; no NaN (+-inf are meaningful)"""
+    c = np.asarray(cut, np.float64)
+    if c.ndim == 0:
+        c = np.full(N_STATES, float(c))
+    if c.shape != (N_STATES,):
+        raise ValueError(f"cut must be a scalar or have shape ({N_STATES},), not {c.shape}")
+    if np.isnan(c).any():
+        raise ValueError("cut holds a NaN (+-inf are allowed: with +inf everything is in half 0)")
+    return np.ascontiguousarray(c)
+
+
+def split_model_check_args(cfg: DqlConfig, n_tables: int, envs_per_table: int, episodes: int, max_steps: int, eps: float):
+    """the argument checks of dql_model_split / dql_ensemble_model_split beyond feature and cut, made before the library is touched"""
+    if not 1 <= n_tables <= MODEL_SPLIT_MAX_TABLES:
+        raise ValueError(f"between 1 and {MODEL_SPLIT_MAX_TABLES} table sets per split-model call, not {n_tables}: slice the sets")
+    model_check_args(cfg, n_tables, envs_per_table, episodes, max_steps, eps)
+    if envs_per_table * (max_steps + 1) >= 1 << 30:
+        raise ValueError(f"envs_per_table * (max_steps + 1) must be below 2^30 (a 64-bit feature sum), not {envs_per_table * (max_steps + 1)}")
+
+
+def split_model_buffers(n_tables: int):
+    """(pairs, reward_fx, terminal, feat_sum_fx, by_code, steps_sum) as the C calls fill them"""
+    return (np.zeros((n_tables, 2, N_CELLS, N_STATES), np.uint32), np.zeros((n_tables, 2, N_CELLS), np.int64), np.zeros((n_tables, 2, N_CELLS, len(CHECK_NAMES)), np.int64),
+            np.zeros((n_tables, N_STATES), np.int64), np.zeros((n_tables, len(SCORE_COLUMNS)), np.int64), np.zeros(n_tables, np.int64))
+
+
+def split_model_result(lib, feature, cut, pairs, reward_fx, terminal, feat_sum_fx, by_code, steps_sum, timing):
+    _last_call(lib, "model_split", "k_model_split", timing)
+    visits = pairs.sum(axis=-1, dtype=np.int64) + terminal.sum(axis=-1)
+    return {"pairs": pairs, "reward_fx": reward_fx, "terminal": terminal, "feat_sum_fx": feat_sum_fx, "by_code": by_code, "steps_sum": steps_sum, "columns": SCORE_COLUMNS,
+            "visits": visits, "state_visits": visits.sum(axis=1).reshape(len(visits), N_STATES, 3).sum(axis=-1), "feature": SPLIT_FEATURES[feature], "cut": cut}
+
+
+def split_model(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, eps: float, feature, cut, episodes: int = 1, max_steps: int = 600, device: int = 0, timing: dict = None):
+    """`transition_model` with every counted decision sent to one of two halves by one bit of hidden state (include/dql.h dql_model_split).
+
+    The flights are `transition_model`'s for the same arguments; `feature` (a name of SPLIT_FEATURES or its code) and `cut` (a scalar or float64 [945], per state
+    before the period; no NaN, +-inf allowed) touch none.  value = the feature read from the env as it stands before the period, half = value >= cut[state].
+    `pairs` uint32 [K, 2, 2835, 945], `terminal` int64 [K, 2, 2835, codes] and `reward_fx` int64 [K, 2, 2835] are `transition_model`'s with the half as the second
+    index (the halves sum to them); `feat_sum_fx` int64 [K, 945] sums rint(value * 2^20) per state; `by_code`, `steps_sum` as there.  Derived: `visits` int64
+    [K, 2, 2835], `state_visits` int64 [K, 945].  K up to MODEL_SPLIT_MAX_TABLES.  Integer sums: bit-reproducible.  `timing`: receives `kernel_ms` and `instance`."""
+    feature, cut = split_feature_code(feature), split_cut_array(cut)
+    qa, qb = _table_pair(qa, qb)
+    K, n, episodes, max_steps, eps = len(qa), int(envs_per_table), int(episodes), int(max_steps), float(eps)
+    split_model_check_args(cfg, K, n, episodes, max_steps, eps)
+    lib = _lib.load()
+    pairs, reward_fx, terminal, feat_sum_fx, by_code, steps_sum = split_model_buffers(K)
+    c = cfg.to_c()
+    _lib.check(lib.dql_model_split(C.byref(c), device, K, n, episodes, int(seed), max_steps, eps, feature, _p(cut), _p(qa), _p(qb), _p(pairs), _p(reward_fx), _p(terminal),
+                                   _p(feat_sum_fx), _p(by_code), _p(steps_sum)))
+    return split_model_result(lib, feature, cut, pairs, reward_fx, terminal, feat_sum_fx, by_code, steps_sum, timing)
+
+
 GRID_MAX_SCENARIOS, GRID_TOUCH_BINS = 1024, 8  # include/dql.h DQL_GRID_MAX_SCENARIOS, DQL_GRID_TOUCH_BINS
 GRID_SHARED_FIELDS = ("dtype", "two_axis", "f_ag", "dt", "manager_div")  # what one launch must share: the kernel instance and the tick schedule
 

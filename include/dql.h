@@ -482,6 +482,38 @@ int dql_score_map(const dql_config* cfg, int device, int64_t n_tables, int64_t e
 #define DQL_MODEL_MAX_TABLES 16
 int dql_model(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps, double eps,
               const double* qa, const double* qb, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code, int64_t* steps_sum);
+/* ---- the transition model split by one bit of hidden state ----
+ * dql_model_split flies exactly what dql_model flies with the same arguments — the envs and their RNG keys, period_begin's own eps-greedy rule, which periods
+ * count — and `feature` and `cut` have no influence on any flight.  For every counted decision of an env, `value` is the selected feature read from the env AS
+ * IT STANDS BEFORE THE PERIOD (the state the decision was taken in), widened to double (a float32 value widens exactly), and half = (value >= cut[idx_x before
+ * the period]) ? 1 : 0, compared in double.  The outputs, all integer sums, bit-reproducible whatever order the lanes arrive in:
+ *   pairs        uint32 [n_tables][2][DQL_N_CELLS][DQL_N_STATES]      as dql_model's, the half as the second index
+ *   terminal     int64 [n_tables][2][DQL_N_CELLS][DQL_N_CHECK_CODES]  as dql_model's, the half as the second index
+ *   reward_fx    int64 [n_tables][2][DQL_N_CELLS]                     as dql_model's, the half as the second index
+ *   feat_sum_fx  int64 [n_tables][DQL_N_STATES]                       per state before the period and per counted decision, rint(value * 2^DQL_SPLIT_FRAC_BITS):
+ *                the product is exact in double, the rounding is to nearest even; the per-state mean is feat_sum_fx / 2^20 / visits of the state
+ *   by_code / steps_sum: as dql_model's
+ * The two halves of pairs, terminal and reward_fx sum to dql_model's.  The features (the names in parentheses are dql_field_name's):
+ *   DQL_SPLIT_COIN 0         0.0 or 1.0, a coin that reads nothing of the env (use cut = 0.5 everywhere): with j the period's index, x = env_id * 0x9E3779B1 +
+ *                            (uint32)j * 0x85EBCA77 + (uint32)seed in 32-bit unsigned arithmetic, then x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13;
+ *                            x *= 0xC2B2AE35; x ^= x >> 16; the value is x >> 31.  It gives the sampling floor for exactly the same sample sizes
+ *   DQL_SPLIT_OBS_P_X 1 (obs_p_x)   DQL_SPLIT_OBS_V_X 2 (obs_v_x)   DQL_SPLIT_OBS_A_X 3 (obs_a_x)   DQL_SPLIT_PITCH_SP 4 (pitch_sp: the continuous set-point)
+ *   DQL_SPLIT_MP_PHASE 5 (mp_phase) DQL_SPLIT_MP_U 6 (mp_u)         DQL_SPLIT_ALTITUDE 7 (pz)       DQL_SPLIT_V_Z 8 (vz)
+ *   DQL_SPLIT_STEP 9         step_count & 0xffff
+ *   DQL_SPLIT_PREV_ACTION 10 action & 3 as it stands: the previous decision's action, or whatever reset left
+ * A value that is not finite or has |value| >= 8192, or a half outside {0, 1}, is a fault like an index out of range: the period's whole contribution is
+ * dropped and counted, and the call returns DQL_ESTATE and no result.
+ * DQL_EINVAL (and no launch, no buffer touched): everything dql_model refuses, with n_tables outside 1..DQL_MODEL_SPLIT_MAX_TABLES (21.4 MB of pair table per
+ * set) and envs_per_table * (max_steps + 1) >= 2^30 (below that feat_sum_fx cannot overflow: 2^33 * 2^30) in place of dql_model's bounds; feature outside
+ * 0..10; a null cut or feat_sum_fx; a NaN in cut (+-inf are allowed and meaningful: with +inf everything is in half 0). */
+#define DQL_MODEL_SPLIT_MAX_TABLES 8
+#define DQL_SPLIT_FRAC_BITS 20
+#define DQL_SPLIT_N_FEATURES 11
+enum { DQL_SPLIT_COIN = 0, DQL_SPLIT_OBS_P_X = 1, DQL_SPLIT_OBS_V_X = 2, DQL_SPLIT_OBS_A_X = 3, DQL_SPLIT_PITCH_SP = 4, DQL_SPLIT_MP_PHASE = 5, DQL_SPLIT_MP_U = 6,
+       DQL_SPLIT_ALTITUDE = 7, DQL_SPLIT_V_Z = 8, DQL_SPLIT_STEP = 9, DQL_SPLIT_PREV_ACTION = 10 };
+int dql_model_split(const dql_config* cfg, int device, int32_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps, double eps,
+                    int32_t feature, const double* cut /* [DQL_N_STATES] */, const double* qa, const double* qb, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal,
+                    int64_t* feat_sum_fx, int64_t* by_code, int64_t* steps_sum);
 /* ---- realised discounted returns per (state, action) cell, to be held against the Q tables ----
  * dql_returns flies exactly what dql_model flies, counted the same way: table set k, env i with the RNG key (i, seed), periods 0 .. max_steps, the eps-greedy
  * rule of dql_model's contract on the fixed tables (eps = 0: the greedy policy), and an env counts in a period as in dql_score_map.  Take the counted decisions
@@ -667,6 +699,11 @@ int dql_ensemble_score_map(dql_ensemble* ens, const dql_config* eval_cfg, int64_
 int dql_ensemble_model(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
                        uint64_t seed, int32_t max_steps, double eps, uint32_t* pairs, int64_t* reward_fx, int64_t* terminal, int64_t* by_code,
                        int64_t* steps_sum);
+/* dql_model_split on the tables of learners [first, first + count): outputs and refusals as for dql_model_split (count in place of n_tables, so count <=
+ * DQL_MODEL_SPLIT_MAX_TABLES; the slice must lie inside the ensemble).  The ensemble is left exactly as it was. */
+int dql_ensemble_model_split(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
+                             uint64_t seed, int32_t max_steps, double eps, int32_t feature, const double* cut, uint32_t* pairs, int64_t* reward_fx,
+                             int64_t* terminal, int64_t* feat_sum_fx, int64_t* by_code, int64_t* steps_sum);
 /* dql_returns on the tables of learners [first, first + count): outputs and refusals as for dql_returns (count in place of n_tables; the slice must lie
  * inside the ensemble).  The ensemble is left exactly as it was. */
 int dql_ensemble_returns(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,

@@ -46,6 +46,9 @@ int dql_diag_score_last(double* kernel_ms, int32_t* inst3);
 int dql_diag_score_map_last(double* kernel_ms, int32_t* inst3);
 /* the same for the calling thread's latest completed dql_model or dql_ensemble_model: the template arguments of k_model's name */
 int dql_diag_model_last(double* kernel_ms, int32_t* inst3);
+/* the same for the calling thread's latest completed dql_model_split or dql_ensemble_model_split: the template arguments of k_model_split's name.  A refused
+ * call leaves the record as it was */
+int dql_diag_model_split_last(double* kernel_ms, int32_t* inst3);
 /* the calling thread's latest completed dql_returns or dql_ensemble_returns: the device durations of its two kernels (k_returns_fly, then k_returns_sweep) and
  * the template arguments of k_returns_fly's name.  A refused call leaves the record as it was */
 int dql_diag_returns_last(double* fly_ms, double* sweep_ms, int32_t* inst3);

@@ -6,6 +6,7 @@ pair of Q tables in the vectorised simulator and reports how the episodes end.
                                  [--rollout] [--report] [--trace-out FILE.npz [--trace-envs 8]] [--map-out FILE.npz [--map-episodes 1]]
                                  [--model-out FILE.npz [--model-eps 0.1]] [--grid-out FILE.npz --grid FIELD=v1,v2,... [--grid ...]]
                                  [--returns-out FILE.npz [--returns-eps 0.1] [--returns-gamma 0.99]]
+                                 [--split-out FILE.npz --split-by NAME[,NAME...]|all [--split-eps 0.1] [--split-seeds 1]]
 Default tables: tests/golden/assets (a data copy of the reference's stage-4 policy).
 --rollout flies all first episodes in one launch (dql_rollout) instead of one launch per agent period; --report prints what the episodes looked like at
 their end (the counterpart of the `info` dictionary the reference prints per episode, scripts/simulation.py:52-56) and --trace-out saves the per-period
@@ -19,6 +20,10 @@ episodes per env).
 (dql_returns): `visits` [2835] and `return_fx` [2835] (the returns-to-go of the finished episodes' decisions, summed, in units of 2^-26),
 `cut_decisions`, `by_code`, `columns`, `steps_sum`, `eps`, `gamma`, and `evaluation.value_calibration`'s per-cell arrays `mean_return`, `bias_a`, `bias_b`,
 `bias_mean` (Q minus mean return; NaN below 30 visits); the report carries its summary (--map-episodes episodes per env).
+--split-out asks which variable is hidden state of the 945 states (dql_model_split): per --split-by feature (names of ops.SPLIT_FEATURES,
+e.g. pitch_sp,mp_phase,prev_action, or `all`) three passes over identical flights — cut = +inf for the feature's per-state means, the split at the means, and one
+coin pass for the sampling floor (--split-seeds seeds summed, --map-episodes episodes per env).  The file holds per feature `pairs_NAME` [2, 2835, 945],
+`terminal_NAME`, `reward_fx_NAME`, `feat_sum_fx_NAME` [945] and `cut_NAME` [945], and the coin's; `evaluation.aliasing_table`'s rows are printed and reported.
 --grid-out scores the tables over the Cartesian product of the --grid axes in ONE launch (dql_score_grid): `--grid mp_t_x=0.8,1.2,1.6 --grid
 trajectory=0,1` flies six scenarios that differ from the flavour's config in those fields only (the first axis varies slowest).  The file holds `by_code`
 [S, codes + 1], `steps_sum` [S], `touch_hist` [S, 8] (touchdowns by their offset from the platform centre), `touch_edges` [S, 7], `columns`, one array per
@@ -74,6 +79,42 @@ def evaluate_model(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dt
     return out
 
 
+def evaluate_split(tables_dir, features, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, episodes=1, eps=0.1, n_seeds=1, min_visits=30,
+                   **cfg_kw):
+    """Which variable is hidden state of the 945 states: per named feature the transition model split at the feature's per-state mean, over identical flights
+    (seeds seed .. seed + n_seeds - 1, summed): pass 1 with cut = +inf gives the means, pass 2 splits at them, one coin pass gives the sampling floor.  Returns
+    (arrays for the .npz, evaluation.aliasing_table's rows; with two or more seeds also the row of the odd seeds' coin against the even seeds' coin)."""
+    import numpy as np
+    from dql_multirotor_landing_amd import evaluation, ops
+    from dql_multirotor_landing_amd.double_q_learning import DoubleQLearningAgent
+    qa, qb, _ = DoubleQLearningAgent.load(Path(tables_dir))._padded()
+    cfg = evaluation._flavour_config(flavour, level, dtype, cfg_kw)
+    summed = ("pairs", "reward_fx", "terminal", "feat_sum_fx", "by_code", "steps_sum")
+
+    def fly(feature, cut, seeds):
+        total = None
+        for s in seeds:
+            r = ops.split_model(cfg, qa, qb, n_envs, s, eps, feature, cut, episodes=episodes, max_steps=max_steps, device=device)
+            total = {f: r[f].copy() for f in summed} if total is None else {f: total[f] + r[f] for f in summed}
+        return total
+
+    seeds = [seed + k for k in range(n_seeds)]
+    by_feature, out = {}, {"eps": np.float64(eps), "seeds": np.array(seeds), "features": np.array(list(features))}
+    for name in features:
+        cut = evaluation.feature_means(fly(name, np.inf, seeds))[0]
+        by_feature[name] = fly(name, cut, seeds)
+        out[f"cut_{name}"] = cut
+        out.update({f"{f}_{name}": by_feature[name][f][0] for f in ("pairs", "reward_fx", "terminal", "feat_sum_fx")})
+    coins = [fly("coin", 0.5, seeds[k::2]) for k in range(min(2, n_seeds))]
+    coin = coins[0] if len(coins) == 1 else {f: coins[0][f] + coins[1][f] for f in summed}
+    out.update({f"{f}_coin": coin[f][0] for f in ("pairs", "reward_fx", "terminal")})
+    out.update({"by_code": coin["by_code"][0], "steps_sum": coin["steps_sum"][0]})
+    table = evaluation.aliasing_table(by_feature, coin, min_visits)
+    if len(coins) == 2:
+        table["coin (odd seeds)"] = evaluation.aliasing_table({"coin": coins[1]}, coins[0], min_visits)["coin"]
+    return out, table
+
+
 def evaluate_returns(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, episodes=1, eps=0.1, gamma=0.99, **cfg_kw):
     """The realised returns of the same flights under the tables' eps-greedy policy and the calibration of the tables against them; returns (arrays, summary)."""
     import numpy as np
@@ -125,9 +166,15 @@ if __name__ == "__main__":
     ap.add_argument("--returns-out", default=None, metavar="FILE.npz", help="save the realised returns per cell of the tables' eps-greedy policy and the tables' calibration (dql_returns)")
     ap.add_argument("--returns-eps", type=float, default=0.1, help="exploration rate of the --returns-out launch, in [0, 1]")
     ap.add_argument("--returns-gamma", type=float, default=0.99, help="discount of the --returns-out returns, in [0, 1]")
+    ap.add_argument("--split-out", default=None, metavar="FILE.npz", help="save the transition model split by each --split-by feature at its per-state mean, and print the aliasing table (dql_model_split)")
+    ap.add_argument("--split-by", default=None, metavar="NAME[,NAME...]", help="the hidden variables to split by: names of ops.SPLIT_FEATURES, or `all`")
+    ap.add_argument("--split-eps", type=float, default=0.1, help="exploration rate of the --split-out launches, in [0, 1]")
+    ap.add_argument("--split-seeds", type=int, default=1, help="how many seeds' flights are summed per pass (123, 124, ...)")
     ap.add_argument("--grid-out", default=None, metavar="FILE.npz", help="save the tables' score over the grid of --grid scenarios, flown in one launch (dql_score_grid)")
     ap.add_argument("--grid", action="append", default=[], metavar="FIELD=v1,v2,...", help="one axis of the --grid-out scenarios: a DqlConfig field and its values (repeatable)")
     a = ap.parse_args()
+    if bool(a.split_out) != bool(a.split_by):
+        ap.error("--split-out FILE.npz and --split-by NAME[,NAME...] belong together")
     if bool(a.grid_out) != bool(a.grid):
         ap.error("--grid-out FILE.npz and at least one --grid FIELD=v1,v2,... belong together")
     import __graft_entry__ as g
@@ -170,6 +217,15 @@ if __name__ == "__main__":
         as_json = lambda v: {k: as_json(x) for k, x in v.items()} if isinstance(v, dict) else ([round(float(x), 4) for x in v] if isinstance(v, np.ndarray) else v)
         out["returns"] = {"file": a.returns_out, "eps": a.returns_eps, "gamma": a.returns_gamma, "episodes_per_env": a.map_episodes, "decisions_kept": int(m["visits"].sum()),
                           "decisions_cut": int(m["cut_decisions"]), "cells_visited": int((m["visits"] > 0).sum()), "calibration": as_json(summary)}
+    if a.split_out:
+        import numpy as np
+        from dql_multirotor_landing_amd import evaluation, ops
+        names = [f for f in ops.SPLIT_FEATURES if f != "coin"] if a.split_by == "all" else [ops.SPLIT_FEATURES[ops.split_feature_code(f)] for f in a.split_by.split(",")]
+        m, table = evaluate_split(a.tables, names, n, a.level, flavour=a.flavour, episodes=a.map_episodes, eps=a.split_eps, n_seeds=a.split_seeds, quirks=quirks)
+        np.savez_compressed(a.split_out, **m)
+        print(evaluation.format_aliasing_table(table), file=sys.stderr)
+        out["split"] = {"file": a.split_out, "eps": a.split_eps, "episodes_per_env": a.map_episodes, "seeds": a.split_seeds, "decisions": int(m["pairs_coin"].sum() + m["terminal_coin"].sum()),
+                        "table": {k: {f: (v if isinstance(v, int) else round(v, 4)) for f, v in row.items()} for k, row in table.items()}}
     if a.grid_out:
         import numpy as np
         from dql_multirotor_landing_amd.config import parse_grid_axes
