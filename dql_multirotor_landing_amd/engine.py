@@ -296,12 +296,23 @@ class Engine:
     def stats(self):
         s = _lib.DqlStatsC()
         _lib.check(self.lib.dql_stats_get(self._h, C.byref(s)))
-        return {"agent_steps": s.agent_steps, "decisions": s.decisions, "episodes": s.episodes,
-                "by_code": {CHECK_NAMES[i]: s.by_code[i] for i in range(len(CHECK_NAMES))},
-                "reward_sum": s.reward_sum, "physics_ticks": s.physics_ticks}
+        d = {"agent_steps": s.agent_steps, "decisions": s.decisions, "episodes": s.episodes,
+             "by_code": {CHECK_NAMES[i]: s.by_code[i] for i in range(len(CHECK_NAMES))},
+             "reward_sum": s.reward_sum, "physics_ticks": s.physics_ticks}
+        base = self.__dict__.get("_stats_base")
+        if base is not None:
+            d = {k: ({c: v[c] + base[k].get(c, 0) for c in v} if k == "by_code" else v + base.get(k, 0)) for k, v in d.items()}
+        return d
+
+    def set_stats(self, stats):
+        """checkpoint / resume: the counters go on from `stats` (a stats() of the interrupted run).  The device's own counters are cleared and the
+        checkpointed ones are added on the host (reward_sum is a sum of fixed-point targets, so the addition is exact)."""
+        self.stats_reset()
+        self._stats_base = {k: (dict(v) if k == "by_code" else v) for k, v in stats.items() if k != "physics_ticks"}  # (a function of the period index)
 
     def stats_reset(self):
         _lib.check(self.lib.dql_stats_reset(self._h))
+        self._stats_base = None
 
     def timer_start(self):
         _lib.check(self.lib.dql_diag_timer_start(self._h))

@@ -54,7 +54,10 @@ Checkpoints: trainer state as JSON (never pickle) + the three `.npy` tables in t
 `checkpoint_env_state`) every env's simulator state, the engine's period index and the promotion bookkeeping, so that
 `Trainer.load(dir).curriculum_training()` continues the interrupted level where it stopped — same history and tables as the
 uninterrupted run with the same checkpoint schedule (a checkpoint is a table barrier: pending updates are folded and the acting
-tables refreshed, in both).  The reference's resume path is broken (B12)."""
+tables refreshed, in both).  That holds for a checkpoint of either kind, inside a level or between two, and wherever restarts and steps back
+have taken the run: a checkpoint also carries the run's bookkeeping (`_run_state`: the level the run started at, steps back, the level being
+learnt again, best attempts and promoted tables in curriculum_state.npz) and, between two levels too, the engine the next level inherits
+(DESIGN.md section 33).  The reference's resume path is broken (B12)."""
 from __future__ import annotations
 
 import csv
@@ -196,6 +199,14 @@ class Trainer:
         self._engine: Optional[Engine] = None
         self._progress: Optional[Dict[str, Any]] = None  # bookkeeping of the level in flight (what a checkpoint has to carry)
         self._resume: Optional[Dict[str, Any]] = None    # set by load(): progress to continue from
+        # bookkeeping of the RUN (what a checkpoint of either kind has to carry; _run_state() / _resume_run): the level the run started at, steps back
+        # taken, the level being learnt again after one, when a level was first promoted, the best attempt given up so far (of the level in flight: rate,
+        # qa, qb, count; of a level that stepped back: per level) and what a level was promoted with (tables, history entry)
+        self._first_level = initial_curriculum_step
+        self._step_backs, self._relearning = 0, None
+        self._first_promotion_wall: Dict[int, float] = {}
+        self._best_attempt, self._best_of_level, self._promoted_snap = None, {}, {}
+        self._resume_run: Optional[Dict[str, Any]] = None  # set by load(): the same, as checkpointed
         self._alpha_cum = None
 
     # ---- schedules: pkg/trainer.py:88-138 ----
@@ -238,39 +249,86 @@ class Trainer:
                 "scale_modification_value": self._scale_modification_value, "t_max": self._t_max, "z_init": self._z_init,
                 "f_ag": self._f_ag, "p_max": self._p_max, "success_rate": self._success_rate,
                 "successive_successful_episodes": self._successive_successful_episodes, "max_num_episodes": self._max_num_episodes,
-                "build": build, "world": self._world, "history": self.history, "progress": self._progress}
+                "build": build, "world": self._world, "history": self.history, "progress": self._progress,
+                "save_generation": self._save_generation}
 
     def _env_state_file(self, rank: int) -> Path:
         return self._save_path / f"env_state_rank{rank}.npz"
 
     def _checkpoint_tag(self):
         """What ties the files of ONE checkpoint together: every rank is at the same (level, agent periods, chunk) when it saves, and
-        counts the same checkpoints.  Stored in every env_state_rank*.npz and in trainer.json's progress."""
-        pr = self._progress or {}
+        counts the same checkpoints (a resumed run counts on).  Stored in every env_state_rank*.npz, in curriculum_state.npz and in
+        trainer.json (progress and curriculum).  Between two levels: the level that comes next, no agent periods, no chunk."""
+        pr = self._progress or {"level": self._working_curriculum_step}
         return {"level": int(pr.get("level", -1)), "steps": int(pr.get("steps", -1)), "chunk_i": int(pr.get("chunk_i", -1)),
                 "world": int(self._world), "generation": int(self._save_generation)}
 
+    _RUN_TABLES = ("qa", "qb", "count")
+
+    def _run_state(self):
+        """The run's restart and step-back bookkeeping as a checkpoint carries it: scalars (trainer.json, "curriculum") and tables
+        (curriculum_state.npz: `best_attempt_*` of the level in flight, `best_of_level<k>_*`, `promoted<k>_*`, each qa / qb / count)."""
+        arrays = {}
+        def put(prefix, tables):
+            for n, t in zip(self._RUN_TABLES, tables):
+                arrays[f"{prefix}_{n}"] = np.asarray(t, dtype=np.float64).reshape(-1)
+        best = self._best_attempt if self._progress is not None else None  # between two levels no level is in flight
+        if best is not None:
+            put("best_attempt", best[1:])
+        for k, b in self._best_of_level.items():
+            put(f"best_of_level{k}", b[1:])
+        for k, (tables, _) in self._promoted_snap.items():
+            put(f"promoted{k}", tables)
+        scalars = {"first_level": int(self._first_level), "step_backs": int(self._step_backs), "relearning": self._relearning,
+                   "first_promotion_wall": {str(k): float(v) for k, v in self._first_promotion_wall.items()},
+                   "best_attempt": None if best is None else float(best[0]),
+                   "best_of_level": {str(k): float(b[0]) for k, b in self._best_of_level.items()},
+                   "promoted_snap": {str(k): entry for k, (_, entry) in self._promoted_snap.items()}}
+        return scalars, arrays
+
+    def _save_npz(self, f: Path, tag, **arrays):
+        tmp = f.with_name(f".{f.name}.{os.getpid()}.tmp.npz")
+        np.savez(tmp, **arrays, **{f"tag_{k}": np.int64(v) for k, v in tag.items()})
+        os.replace(tmp, f)
+
+    @staticmethod
+    def _npz_tag(z):
+        return {k[4:]: int(z[k]) for k in z.files if k.startswith("tag_")}
+
     def save(self) -> None:
-        """One checkpoint = env_state_rank<r>.npz of every rank + the three .npy tables + trainer.json, every file written as temp +
-        os.replace, trainer.json LAST (and, with several ranks, after a barrier): a run killed anywhere in between leaves the previous
-        trainer.json, whose tag the newer env-state files do not match — `load()` then resumes the level from its tables without them."""
+        """One checkpoint = env_state_rank<r>.npz of every rank (+ the .npy of real fields it names) + the three .npy tables + curriculum_state.npz + trainer.json, every file
+        written as temp + os.replace, trainer.json LAST (and, with several ranks, after a barrier): a run killed anywhere in between leaves
+        the previous trainer.json, whose tag the newer files do not match — `load()` then resumes the level from its tables without them.
+        The rank's shard holds the simulator state of its envs, the period index and the engine's counters — between two levels as well:
+        the next level inherits the engine (every env re-enters through reset, which draws on the period it happens in and leaves the rotor
+        speeds, the PIDs' filter states and the platform where they are: DESIGN.md section 33)."""
         eng = self._engine
         if eng is not None and hasattr(eng, "publish_tables"):
             eng.publish_tables()  # checkpoint = table barrier: pending updates folded, acting tables = master tables (a resumed run starts so)
         self._pull_tables()
         self._save_generation += 1
         tag = self._checkpoint_tag()
-        if eng is not None and self._checkpoint_env_state and self._progress is not None and hasattr(eng, "get_fields"):
+        if (eng is not None and self._checkpoint_env_state and hasattr(eng, "get_fields")
+                and (self._progress is not None or self._working_curriculum_step < self._curriculum_steps)):  # (after the last level nothing inherits the engine)
             # every rank writes its own shard: simulator state of every env + the period index the RNG and tick schedule hang on
             self._save_path.mkdir(parents=True, exist_ok=True)
             reals, ints = eng.get_fields()
-            f = self._env_state_file(self._rank)
-            tmp = f.with_name(f".{f.name}.{os.getpid()}.tmp.npz")
             # dtype + state_layout: the two PIDs' filter fields mean different things per dtype (state_layout.py); a shard is only flown by a
             # context it was written for, or after the one mapping that exists (float64 histories -> float32 transposed states)
-            np.savez(tmp, reals=reals.astype(np.float32 if self._dtype == F32 else np.float64), ints=ints, step_index=np.int64(eng.step_index()),
-                     dtype=np.int64(self._dtype), state_layout=np.int64(STATE_LAYOUT_VERSION), **{f"tag_{k}": np.int64(v) for k, v in tag.items()})
-            os.replace(tmp, f)
+            # The real fields — nearly all of the bytes — go into a plain .npy BESIDE the shard (a zip member costs a CRC pass: 9 of the 15 ms a
+            # 32 768-env shard took, at every level's end), named by this checkpoint's generation, which the tagged shard names in turn; the file
+            # before it stays until the next checkpoint (the trainer.json on disk may still be of the checkpoint that names it)
+            f = self._env_state_file(self._rank)
+            reals_file = f.with_name(f"{f.stem}.reals.g{tag['generation']}.npy")
+            tmp = reals_file.with_name(f".{reals_file.name}.{os.getpid()}.tmp")
+            with open(tmp, "wb") as fh:
+                np.save(fh, reals.astype(np.float32 if self._dtype == F32 else np.float64))
+            os.replace(tmp, reals_file)
+            self._save_npz(f, tag, step_index=np.int64(eng.step_index()), stats=np.array(json.dumps(eng.stats())), dtype=np.int64(self._dtype),
+                           state_layout=np.int64(STATE_LAYOUT_VERSION), reals_file=np.array(reals_file.name), ints=ints)
+            older = sorted(f.parent.glob(f"{f.stem}.reals.g*.npy"), key=lambda q: int(q.name.rsplit(".g", 1)[1][:-4]))[:-2]
+            for q in older:
+                q.unlink()
         if self._comm is not None and self._world > 1:
             self._comm.barrier()  # every rank's shard of this checkpoint is on disk before rank 0 publishes it
         if self._rank != 0:  # table replicas are identical after a sync: rank 0 writes
@@ -287,10 +345,13 @@ class Trainer:
         write_tag(dict(tag, in_progress=1))
         self._double_q_learning_agent.save(self._save_path)
         self._double_q_learning_agent.save(self._save_path / "..")
+        run_scalars, run_tables = self._run_state()
+        self._save_npz(self._save_path / "curriculum_state.npz", tag, **run_tables)
         write_tag(tag)
         st = self._state_dict()
         if st["progress"] is not None:
             st["progress"] = dict(st["progress"], tag=tag)
+        st["curriculum"] = dict(run_scalars, tag=tag)
         tmp = self._save_path / f".trainer.json.{os.getpid()}.tmp"
         with open(tmp, "w") as fh:
             json.dump(st, fh, indent=1)
@@ -335,7 +396,42 @@ class Trainer:
         tr._resume = st.get("progress")
         if tr._resume is not None and st.get("world", 1) != tr._world:
             raise ValueError(f"checkpoint was written by {st.get('world', 1)} rank(s), this job has {tr._world}: env shards would not line up")
+        tr._save_generation = int(st.get("save_generation", 0))  # checkpoints go on being counted: no two of a run directory share a tag
+        tr._resume_run = Trainer._load_run_state(run, st)
         return tr
+
+    @staticmethod
+    def _load_run_state(run: Path, st):
+        """The run's restart and step-back bookkeeping (`_run_state`) from trainer.json + curriculum_state.npz, or None for a trainer.json
+        written before checkpoints carried it.  A curriculum_state.npz of ANOTHER checkpoint (the run was stopped between it and
+        trainer.json) is not used: the scalars stand, the best attempts and promoted tables — which are nothing without their tables —
+        start afresh, with a warning, as a level resumes without an env-state shard of another checkpoint."""
+        cur = st.get("curriculum")
+        if cur is None:
+            if st["working_curriculum_step"] < st["curriculum_steps"]:
+                warnings.warn(f"trainer.json in {run.name} was written before checkpoints carried the restart and step-back bookkeeping: it starts afresh "
+                              "(steps back taken, best attempts and promoted tables are forgotten; the next level's engine starts at period 0)", RuntimeWarning)
+            return None
+        out = {"first_level": int(cur["first_level"]), "step_backs": int(cur["step_backs"]), "relearning": cur["relearning"], "tag": cur.get("tag"),
+               "first_promotion_wall": {int(k): float(v) for k, v in cur["first_promotion_wall"].items()},
+               "best_attempt": None, "best_of_level": {}, "promoted_snap": {}}
+        want = {k: int(v) for k, v in (cur.get("tag") or {}).items()}
+        try:
+            z = np.load(run / "curriculum_state.npz", allow_pickle=False)
+            have = Trainer._npz_tag(z)
+        except (OSError, ValueError):
+            z, have = None, None
+        if z is None or have != want:
+            if cur["best_attempt"] is not None or cur["best_of_level"] or cur["promoted_snap"]:
+                warnings.warn(f"curriculum_state.npz in {run.name} {'is missing' if z is None else f'belongs to checkpoint {have}'}, trainer.json to {want}: resuming "
+                              "without the best attempts and the promoted tables it holds (they start afresh; steps back taken still count)", RuntimeWarning)
+            return out
+        tables = lambda prefix: tuple(np.array(z[f"{prefix}_{n}"], dtype=np.float64) for n in Trainer._RUN_TABLES)
+        if cur["best_attempt"] is not None:
+            out["best_attempt"] = (float(cur["best_attempt"]),) + tables("best_attempt")
+        out["best_of_level"] = {int(k): (float(r),) + tables(f"best_of_level{k}") for k, r in cur["best_of_level"].items()}
+        out["promoted_snap"] = {int(k): (tables(f"promoted{k}"), entry) for k, entry in cur["promoted_snap"].items()}
+        return out
 
     # ---- device plumbing ----
     def _config(self, level: int) -> DqlConfig:
@@ -445,20 +541,27 @@ class Trainer:
             warnings.warn(f"{f.name} belongs to checkpoint {have or 'without a tag'}, trainer.json to {want}: resuming level {progress.get('level')} "
                           "from its tables without the saved simulator state", RuntimeWarning)
             return None
+        z = {k: z[k] for k in z.files}
+        if "reals" not in z:  # (shards written before the real fields moved out of the zip hold them themselves)
+            try:
+                z["reals"] = np.load(f.with_name(str(z["reals_file"])), allow_pickle=False)
+            except (OSError, ValueError):
+                warnings.warn(f"{z['reals_file']}, which {f.name} names, cannot be read: resuming level {progress.get('level')} from its tables without the "
+                              "saved simulator state", RuntimeWarning)
+                return None
+        if z["reals"].shape[1] != eng.n:  # raised by _restore_env_state on EVERY rank, after the vote (a lone raise here would leave the others in the collective)
+            self._env_state_error = f"{f} holds {z['reals'].shape[1]} envs, this rank's shard has {eng.n}"
+            return None
         # which dtype's layout the shard holds (files written before round 5 carry no field: the array's own dtype, layout 1 = histories everywhere)
-        src_dtype = int(z["dtype"]) if "dtype" in z.files else (F32 if z["reals"].dtype == np.float32 else 1)
-        src_layout = int(z["state_layout"]) if "state_layout" in z.files else 1
+        src_dtype = int(z["dtype"]) if "dtype" in z else (F32 if z["reals"].dtype == np.float32 else 1)
+        src_layout = int(z["state_layout"]) if "state_layout" in z else 1
         reals = convert_env_state(z["reals"].astype(np.float64), eng.field_names(), src_dtype, self._dtype, src_layout, bw_c=self._env_kw.get("bw_c", 1.0))
         if reals is None:
             warnings.warn(f"{f.name} holds the simulator state of a {'float32' if src_dtype == F32 else 'float64'} context (layout {src_layout}) and this run is "
                           f"{'float32' if self._dtype == F32 else 'float64'}: the float32 filter states do not determine the float64 histories — resuming level "
                           f"{progress.get('level')} from its tables without the saved simulator state", RuntimeWarning)
             return None
-        z = {"reals": reals, "ints": z["ints"], "step_index": z["step_index"]}
-        if z["ints"].shape[1] != eng.n:  # raised by _restore_env_state on EVERY rank, after the vote (a lone raise here would leave the others in the collective)
-            self._env_state_error = f"{f} holds {z['ints'].shape[1]} envs, this rank's shard has {eng.n}"
-            return None
-        return z
+        return {"reals": reals, "ints": z["ints"], "step_index": z["step_index"], "stats": json.loads(str(z["stats"])) if "stats" in z else None}
 
     def _restore_env_state(self, eng, progress):
         """Simulator state of the envs from the checkpoint `progress` belongs to — on every rank, or on none (then the level's envs
@@ -476,8 +579,14 @@ class Trainer:
         if not ok:
             return False
         eng.set_fields(np.asarray(z["reals"], dtype=np.float64), z["ints"])
-        eng.set_step_index(int(z["step_index"]))
+        self._restore_engine_counters(eng, z["step_index"], z["stats"])
         return True
+
+    @staticmethod
+    def _restore_engine_counters(eng, step_index, stats):
+        eng.set_step_index(int(step_index))
+        if stats is not None and hasattr(eng, "set_stats"):
+            eng.set_stats(stats)  # the counters go on where the interrupted run's stood (the loop itself reads differences only)
 
     def curriculum_training(self):
         if self._working_curriculum_step >= self._curriculum_steps:  # Trainer.load() of a finished run: nothing left to train
@@ -499,23 +608,34 @@ class Trainer:
         if read_log is not None and "words" in inspect.signature(read_log).parameters:
             read_log = lambda: eng.episode_log_read(words=(j_cnt + 63) // 64)
         order = EpisodeOrder(j_valid.size, j_valid)
-        first_level = self._working_curriculum_step
-        k_next = first_level
-        first_promotion_wall: Dict[int, float] = {}
-        step_backs, best_of_level = 0, {}  # (step_back_after) steps back taken so far; best attempt of a level over its lineages
-        promoted_snap: Dict[int, Any] = {}  # level -> (tables, history entry) when the rule promoted it: what a failed re-learning of the level falls back to
-        relearning = None                   # the level being learnt again after a step back (it never steps back itself, and gets a short budget)
+        start_level = self._working_curriculum_step  # of THIS call; the run's first level is another one after a resume
+        k_next = start_level
+        run, self._resume_run = self._resume_run, None
+        self._first_level = start_level
+        self._step_backs = 0        # (step_back_after) steps back taken so far
+        self._relearning = None     # the level being learnt again after a step back (it never steps back itself, and gets a short budget)
+        self._best_attempt = None   # (population success rate, tables) of the best attempt the level in flight has given up so far
+        self._first_promotion_wall, self._best_of_level, self._promoted_snap = {}, {}, {}
+        if run is not None:  # the interrupted run's bookkeeping: whatever it would still have read
+            self._first_level, self._step_backs, self._relearning = run["first_level"], run["step_backs"], run["relearning"]
+            self._first_promotion_wall, self._best_of_level, self._promoted_snap = run["first_promotion_wall"], run["best_of_level"], run["promoted_snap"]
+            if resume is None:
+                # stopped BETWEEN two levels: the next level inherits the engine of the level before (its set_curriculum marks every env for reset)
+                self._restore_env_state(eng, {"tag": run["tag"], "level": start_level})
+        first_level = self._first_level
+        first_promotion_wall = self._first_promotion_wall
+        best_of_level = self._best_of_level  # best attempt of a level over its lineages
+        promoted_snap = self._promoted_snap  # level -> (tables, history entry) when the rule promoted it: what a failed re-learning of the level falls back to
         while k_next < self._curriculum_steps:
             self._working_curriculum_step = k = k_next
             k_next = k + 1
-            resumed = resume is not None and k == first_level and resume.get("level") == k
-            resume = resume if resumed else None  # (a level entered again after a step back starts afresh)
+            resumed = resume is not None and k == start_level and resume.get("level") == k
+            pr, resume = resume, None  # (a level entered again after a step back starts afresh)
             if resumed:
                 # continue the interrupted level: no transfer (it was applied when the level started), tables as checkpointed
-                have_envs = self._restore_env_state(eng, resume)
+                have_envs = self._restore_env_state(eng, pr)
                 if not have_envs:
                     eng.set_curriculum(k)  # no simulator state saved: the level's envs start over, its bookkeeping does not
-                pr = resume
                 window = deque(tuple(w) for w in pr["window"])
                 pw.reset(); order.reset()
                 if have_envs:
@@ -537,12 +657,12 @@ class Trainer:
             promoted = False
             promoted_at = None
             restarts, restart_base = (int(pr.get("restarts", 0)), int(pr.get("restart_base", 0))) if resumed else (0, 0)
-            best_attempt = best_of_level.get(k)  # (population success rate, tables) of the best attempt given up so far (not checkpointed: a resumed run starts collecting again)
+            self._best_attempt = run["best_attempt"] if resumed and run is not None else best_of_level.get(k)
             stalled = False
-            info: Dict[str, Any] = {}
+            info: Dict[str, Any] = {"Success rate": pr.get("success_rate")} if resumed else {}
             # a level learnt AGAIN after a step back gets (step_back_after + 1) restart windows, not the whole budget: it has been promoted from these tables before
             level_budget = self._max_num_episodes
-            if relearning == k and not resumed:
+            if self._relearning == k:
                 level_budget = min(level_budget, int((self._step_back_after + 1) * self._restart_after * self._n_envs))
             while episodes < level_budget:
                 sched_episode = int(episodes / self._eps_episode_scale)
@@ -585,10 +705,10 @@ class Trainer:
                         and episodes - restart_base >= self._restart_after * self._n_envs and episodes < level_budget):
                     # start the level over (see __init__): every rank does the same, at a chunk boundary = on synchronised tables
                     qa_, qb_, cnt = (np.asarray(t, dtype=np.float64).reshape(-1).copy() for t in eng.get_tables())
-                    if best_attempt is None or rate > best_attempt[0]:  # the attempt given up may still be the best one the budget buys
-                        best_attempt = (rate, qa_, qb_, cnt.copy())
-                    if (self._step_back_after is not None and k >= 2 and k - 1 >= first_level and restarts >= self._step_back_after and step_backs < self._max_step_backs
-                            and relearning is None):
+                    if self._best_attempt is None or rate > self._best_attempt[0]:  # the attempt given up may still be the best one the budget buys
+                        self._best_attempt = (rate, qa_, qb_, cnt.copy())
+                    if (self._step_back_after is not None and k >= 2 and k - 1 >= first_level and restarts >= self._step_back_after and self._step_backs < self._max_step_backs
+                            and self._relearning is None):
                         stalled = True  # every redraw from this table of level k - 1 failed: step back instead of restarting again (see __init__)
                         break
                     per_level = cnt.size // 5
@@ -602,7 +722,8 @@ class Trainer:
                     restarts += 1; restart_base = episodes
                 if chunk_i % self._checkpoint_every == 0 and not done_level:
                     self._progress = {"level": k, "episodes": episodes, "steps": steps, "chunk_i": chunk_i, "window": [list(w) for w in window],
-                                      "pw": pw.get_state(), "order": order.get_state(), "restarts": restarts, "restart_base": restart_base}
+                                      "pw": pw.get_state(), "order": order.get_state(), "restarts": restarts, "restart_base": restart_base,
+                                      "success_rate": rate}  # (a checkpoint at the chunk that ends the budget: the resumed level flies no chunk of its own)
                     self.save()
                 self.log(info)
                 if done_level:
@@ -614,8 +735,8 @@ class Trainer:
                 if self._max_steps_per_level is not None and steps >= self._max_steps_per_level:
                     break
             if stalled:
-                best_of_level[k] = best_attempt
-                step_backs += 1
+                best_of_level[k] = self._best_attempt
+                self._step_backs += 1
                 cnt = np.asarray(eng.get_tables()[2], dtype=np.float64).reshape(-1).copy()
                 per_level = cnt.size // 5
                 cnt[(k - 1) * per_level:(k + 1) * per_level] = 0.0  # levels k - 1 and k learn again from fresh counters; their slices are rewritten by the transfers
@@ -623,28 +744,28 @@ class Trainer:
                 while self.history and self.history[-1]["level"] >= k - 1:  # one entry per level: level k - 1's is written again when it ends again
                     self.history.pop()
                 self._progress = None
-                relearning = k - 1
+                self._relearning = k - 1
                 k_next = k - 1
                 continue
             exhausted = not promoted and episodes >= level_budget
-            if exhausted and best_attempt is not None and best_attempt[0] > (info.get("Success rate") or 0.0):
+            if exhausted and self._best_attempt is not None and self._best_attempt[0] > (info.get("Success rate") or 0.0):
                 # the budget ran out in a later, worse attempt: the level hands over the tables of its best one (same rule as the reference's budget
                 # hand-over, pkg/trainer.py:187 — it just does not hand over a restart that had barely begun)
-                eng.set_tables(best_attempt[1], best_attempt[2], best_attempt[3])
-                info["Success rate"] = best_attempt[0]
+                eng.set_tables(*self._best_attempt[1:])
+                info["Success rate"] = self._best_attempt[0]
             if promoted and k not in first_promotion_wall:
                 first_promotion_wall[k] = time.perf_counter() - t_start
             fell_back = False
-            if relearning == k:
-                relearning = None
+            if self._relearning == k:
+                self._relearning = None
                 if not promoted and k in promoted_snap:
                     # learnt again and not promoted within its short budget: the level keeps the tables (and the history entry) it WAS promoted with; the level
                     # above goes on from those with plain restarts
                     eng.set_tables(*promoted_snap[k][0])
-                    self.history.append(dict(promoted_snap[k][1], step_backs=step_backs, wall_since_start_s=time.perf_counter() - t_start))
+                    self.history.append(dict(promoted_snap[k][1], step_backs=self._step_backs, wall_since_start_s=time.perf_counter() - t_start))
                     promoted, exhausted, fell_back = True, False, True
             if not fell_back:
-                entry = {"level": k, "promoted": promoted, "exhausted": exhausted, "promoted_at": promoted_at, "restarts": restarts, "step_backs": step_backs, "episodes": episodes,
+                entry = {"level": k, "promoted": promoted, "exhausted": exhausted, "promoted_at": promoted_at, "restarts": restarts, "step_backs": self._step_backs, "episodes": episodes,
                          "agent_periods": steps, "success_rate": info.get("Success rate"),
                          "wall_s": time.perf_counter() - t_level, "wall_since_start_s": time.perf_counter() - t_start,
                          # (with step backs a level can end more than once: when the rule FIRST promoted it — "stage k + 1 entered")
@@ -656,7 +777,7 @@ class Trainer:
                 # transfer AFTER finishing level k: Q[k] = Q[k-1] * ratio, k = 0 wraps (B6, pkg/trainer.py:237-243)
                 eng.transfer(k, self.transfer_learning_ratio(k))
             self._progress = None  # between levels: a resumed run starts the next level from its beginning
-            try:  # this level's simulator state is of no use to the next one
+            try:  # this level's simulator state is of no use to the next one (save() writes the shard of a between-levels checkpoint in its place)
                 self._env_state_file(self._rank).unlink()
             except OSError:
                 pass

@@ -113,7 +113,7 @@ TR_KW = dict(curriculum_steps=3, n_envs=96, chunk_steps=8, sync_period=2, checkp
 
 
 def _oracle_engine_class():
-    from dql_multirotor_landing_amd.config import CHECK_NAMES
+    from dql_multirotor_landing_amd.config import CHECK_NAMES, TARGET_FRAC_BITS
     from oracle.oracle import Oracle
 
     class OracleEngine:  # the Engine surface the Trainer uses, computed by the CPU oracle (tests only)
@@ -132,6 +132,11 @@ def _oracle_engine_class():
             d = self.o.stats_dict()
             d["by_code"] = {CHECK_NAMES[i]: d["by_code"][i] for i in range(len(CHECK_NAMES))}
             return d
+        def set_stats(self, d):  # checkpoint / resume: the counters go on from a stats() of the interrupted run
+            s = self.o.stats
+            s[0], s[1] = d["decisions"], d["episodes"]
+            s[2:2 + len(CHECK_NAMES)] = [d["by_code"][c] for c in CHECK_NAMES]
+            s[11] = round(d["reward_sum"] * (1 << TARGET_FRAC_BITS))
     return OracleEngine
 
 
@@ -219,6 +224,63 @@ def test_trainer_resume_equals_uninterrupted_run(tmp_path, monkeypatch):
         assert json.loads(json.dumps(h_back)) == json.loads(json.dumps(h_full))
         for a, b in zip(back._engine.get_tables(), full._engine.get_tables()):
             np.testing.assert_array_equal(a, b)
+
+
+def _resume_worker(rank, world, port, out_dir):
+    """scenario P on the windowed schedule, sharded: cut off on both ranks right after the checkpoint between levels 0 and 1, loaded and finished by both"""
+    sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
+    import json
+    import torch.distributed as dist
+    from _torch_comm import TorchComm
+    import dql_multirotor_landing_amd.trainer as T
+    import trainer_resume_checks as H
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    T.Engine = _oracle_engine_class()
+    run = Path(out_dir) / "two" / H.RUN_NAME
+    part = T.Trainer(save_path=run, comm=TorchComm(), **H.SCENARIOS["P2"])
+    assert part._world == 2 and part._rank == rank
+    real_save = part.save
+    def save():
+        real_save()
+        if part._progress is None and part._working_curriculum_step == 1:
+            raise H.PowerCut()
+    part.save = save
+    try:
+        part.curriculum_training()
+        raise AssertionError("the run was not cut off")
+    except H.PowerCut:
+        pass
+    H.close(part)
+    dist.barrier()   # (rank 1 leaves save() before rank 0 has written trainer.json)
+    assert (run / f"env_state_rank{rank}.npz").exists() and json.loads((run / "trainer.json").read_text())["progress"] is None
+    back = T.Trainer.load(Path(out_dir) / "two", comm=TorchComm())
+    assert back._world == 2 and back._working_curriculum_step == 1 and back._resume is None and back._resume_run is not None
+    out = H.finish(back)
+    np.savez(Path(out_dir) / f"resumed_rank{rank}.npz", qa=out["tables"][0], qb=out["tables"][1], count=out["tables"][2], step_index=out["engine"]["step_index"])
+    (Path(out_dir) / f"resumed_hist{rank}.json").write_text(json.dumps(out["history"]))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_trainer_resume_between_levels_on_two_ranks_equals_single_process_uninterrupted_run(tmp_path, monkeypatch):
+    """Two ranks stopped BETWEEN levels 0 and 1 (every rank's shard carries its envs and the period index across the level switch) and resumed with
+    two ranks: the history, the tables and the period index of one process flying the same keywords without interruption."""
+    import json
+    import torch.multiprocessing as mp
+    import dql_multirotor_landing_amd.trainer as T
+    import trainer_resume_checks as H
+    mp.spawn(_resume_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    h0, h1 = (json.loads((tmp_path / f"resumed_hist{r}.json").read_text()) for r in range(2))
+    monkeypatch.setattr(T, "Engine", _oracle_engine_class())
+    with H.scenario(T, "P2") as (make, _):
+        full, rows = H.record(make, tmp_path / "single")
+    assert h0 == h1 == full["history"] and [h["level"] for h in h0] == [0, 1, 2] and any(h["promoted"] for h in h0)
+    assert ("between", 1, False, 0, False) in H.first_of_each_class(rows)
+    for r in range(2):
+        z = np.load(tmp_path / f"resumed_rank{r}.npz")
+        for name, t in zip(("qa", "qb", "count"), full["tables"]):
+            np.testing.assert_array_equal(z[name], t)
+        assert int(z["step_index"]) == full["engine"]["step_index"]
 
 
 def test_checkpoint_files_carry_one_tag_and_a_mixed_checkpoint_is_not_resumed(tmp_path, monkeypatch):
@@ -395,7 +457,7 @@ def test_level_restart_on_plateau(tmp_path, monkeypatch):
     the tables of its BEST attempt.  The promotion rule itself is untouched (an unreachable success rate never promotes); None = the reference."""
     import dql_multirotor_landing_amd.trainer as T
     monkeypatch.setattr(T, "Engine", _oracle_engine_class())
-    kw = dict(curriculum_steps=2, n_envs=48, chunk_steps=8, checkpoint_every=10**9, max_num_episodes=400, t_max=3, mode="paper", judge_envs=16,
+    kw = dict(curriculum_steps=2, n_envs=48, chunk_steps=8, checkpoint_every=3, max_num_episodes=400, t_max=3, mode="paper", judge_envs=16,
               successive_successful_episodes=10, eps_floor=0.3)
     a = T.Trainer(save_path=tmp_path / "a", success_rate=2.0, restart_after=1.5, **kw)
     ha = a.curriculum_training()
@@ -415,7 +477,7 @@ def test_step_back_after_failed_restarts(tmp_path, monkeypatch):
     path, `step_backs` counts them, at most `max_step_backs` per run; level 1 never steps back (level 0 is not restarted); without the keyword nothing changes."""
     import dql_multirotor_landing_amd.trainer as T
     monkeypatch.setattr(T, "Engine", _oracle_engine_class())
-    kw = dict(curriculum_steps=3, n_envs=48, chunk_steps=8, checkpoint_every=10**9, max_num_episodes=500, t_max=3, mode="paper", judge_envs=16,
+    kw = dict(curriculum_steps=3, n_envs=48, chunk_steps=8, checkpoint_every=3, max_num_episodes=500, t_max=3, mode="paper", judge_envs=16,
               successive_successful_episodes=10, eps_floor=0.3, success_rate=2.0, restart_after=1.5)
     a = T.Trainer(save_path=tmp_path / "a", step_back_after=1, max_step_backs=2, **kw)
     ha = a.curriculum_training()
@@ -435,20 +497,12 @@ def test_step_back_falls_back_to_the_promoted_tables_when_the_relearning_fails(t
     the level WAS promoted with: its history entry stays the promoted one.  Scripted promotion window: levels 0 and 1 pass on their first attempt, nothing passes after."""
     import dql_multirotor_landing_amd.trainer as T
     monkeypatch.setattr(T, "Engine", _oracle_engine_class())
-    real = T.PromotionWindow
-
-    class Scripted(real):
-        resets = 0
-        def reset(self):
-            Scripted.resets += 1
-            return super().reset()
-        def push_flags(self, flags):
-            super().push_flags(flags)
-            return 0 if Scripted.resets <= 3 and len(flags) else None   # resets 1 (constructor's level-0 start), 2 (level 0), 3 (level 1): see the asserts below
+    from trainer_resume_checks import scripted_window
+    Scripted = scripted_window(T)   # levels 0 and 1 pass until the run has stepped back: a script of (working level, steps back), which a checkpoint carries
     monkeypatch.setattr(T, "PromotionWindow", Scripted)
-    kw = dict(curriculum_steps=3, n_envs=48, chunk_steps=8, checkpoint_every=10**9, max_num_episodes=600, t_max=3, mode="paper", judge_envs=16,
+    kw = dict(curriculum_steps=3, n_envs=48, chunk_steps=8, checkpoint_every=3, max_num_episodes=600, t_max=3, mode="paper", judge_envs=16,
               successive_successful_episodes=10, eps_floor=0.3, restart_after=1.5, step_back_after=1, max_step_backs=2)
-    tr = T.Trainer(save_path=tmp_path / "a", **kw)
+    tr = Scripted.trainer = T.Trainer(save_path=tmp_path / "a", **kw)
     h = tr.curriculum_training()
     assert [x["level"] for x in h] == [0, 1, 2]
     assert h[0]["promoted"] and h[1]["promoted"] and not h[2]["promoted"] and h[2]["exhausted"]
