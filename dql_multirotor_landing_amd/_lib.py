@@ -218,6 +218,14 @@ SYMBOLS = {
     "dql_ensemble_get_team_nstep": (C.c_int, [_vp, C.POINTER(_i32), _vp]),
     # team curriculum mode (include/dql.h)
     "dql_ensemble_set_team_curriculum": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32]),
+    # a state split by one bit of hidden state (include/dql.h)
+    "dql_ensemble_set_refinement": (C.c_int, [_vp, _i32, _vp]),
+    "dql_ensemble_get_refinement": (C.c_int, [_vp, C.POINTER(_i32), _vp]),
+    "dql_ensemble_get_refined_tables": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "dql_ensemble_set_refined_tables": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "dql_score_refined": (C.c_int, [_cfgp, C.c_int, _i64, _i64, _i32, _u64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dql_ensemble_score_refined": (C.c_int, [_vp, _cfgp, _i64, _i64, _i64, _i32, _u64, _i32, _vp, _vp, _vp, _vp]),
+    "dql_diag_score_refined_last": (C.c_int, [C.POINTER(_dbl), _vp]),
 }
 MAX_AGENTS = 16  # include/dql.h DQL_MAX_AGENTS
 

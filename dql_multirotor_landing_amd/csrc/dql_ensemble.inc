@@ -155,9 +155,17 @@ struct dql_ensemble {
   // transfer and level change is RecipeRule's; the worklist of teams is allocated by the first dql_ensemble_set_team_curriculum that switches the mode on
   int team_every = 0, team_order = RCP_ORDER_REFERENCE;
   EnsWorklist twl;                                            // by level, 64 / E team slots per wave (capacity: team_worklist_capacity)
+  // the refinement (DESIGN.md section 34, dql_refined.inc); refine_feature = -1: none, and every call is as it was.  Installed once by dql_ensemble_set_refinement:
+  // the learners' tables are then rq_a / rq_b / rq_count [n][2][DQL_N_CELLS] (mem.qa / qb / count stay allocated and are never read again), d_cut [DQL_N_STATES]
+  // is the cut on the device and h_cut its host copy, d_half [n] the byte a learner carries across launches (RefinedMem::half)
+  int refine_feature = -1;
+  double *rq_a = nullptr, *rq_b = nullptr, *rq_count = nullptr, *d_cut = nullptr;
+  uint8_t* d_half = nullptr;
+  double h_cut[DQL_N_STATES]{};
 };
-// which of the nine learner kernels a launch flies (ens_kernel_of decides, ens_fly switches)
-enum EnsKernel { ENS_K_LEARN, ENS_K_TEAM, ENS_K_TEAM_NSTEP, ENS_K_NSTEP, ENS_K_LEVELS, ENS_K_RECIPES, ENS_K_RECIPES_NSTEP, ENS_K_TEAM_LEVELS, ENS_K_TEAM_LEVELS_NSTEP };
+// which of the ten learner kernels a launch flies (ens_kernel_of decides, ens_fly switches)
+enum EnsKernel { ENS_K_LEARN, ENS_K_TEAM, ENS_K_TEAM_NSTEP, ENS_K_NSTEP, ENS_K_LEVELS, ENS_K_RECIPES, ENS_K_RECIPES_NSTEP, ENS_K_TEAM_LEVELS, ENS_K_TEAM_LEVELS_NSTEP,
+                 ENS_K_LEARN_REFINED };
 // of dql_recipes.inc: the installed recipes let go, the rule learner l advances by, the smallest last_level of the populated recipes, whether a recipe that has
 // a member has n >= 1, the device copy of the recipes' n (null until one was set), dql_ensemble_run's part with recipes installed
 static void ens_recipes_release(dql_ensemble* x);
@@ -175,14 +183,21 @@ template <typename T> static void launch_learn_team_nstep(dql_ensemble* x, int k
 template <typename T> static void launch_learn_recipes_nstep(dql_ensemble* x, int k, int n_waves);  // dql_nstep_recipes.inc
 template <typename T> static void launch_learn_team_levels(dql_ensemble* x, int k, int n_waves);        // dql_team_levels.inc
 template <typename T> static void launch_learn_team_levels_nstep(dql_ensemble* x, int k, int n_waves);  // dql_team_levels.inc
+template <typename T> static void launch_learn_refined(dql_ensemble* x, int k, int n_waves);            // dql_refined.inc
 #define ENS_NSTEP_REFUSED(who) "" who ": n-step targets (dql_ensemble_set_nstep with n >= 1) are for the plain mode, where every learner flies the config's level; set n = 0 first; nothing was changed and nothing was launched"
 #define ENS_TEAM_NSTEP_REFUSED(who) "" who ": team n-step targets (dql_ensemble_set_team_nstep with n >= 1) are for the barrier mode, where every learner flies the config's level: a team ensemble of one env per learner has no per-learner curriculum and no recipes while they are on; set n = 0 first; nothing was changed and nothing was launched"
 #define ENS_TEAMS_REFUSED(who) "" who ": an ensemble with more than one env per learner flies the barrier mode only (teams have no per-learner curriculum and no recipes); nothing was changed and nothing was launched"
 #define ENS_TEAM_LEVELS_REFUSED(who) "" who ": team curriculum mode (dql_ensemble_set_team_curriculum) is on: a team ensemble of one env per learner flies one of the two curriculum modes at a time; switch it off first (advance_every = 0); nothing was changed and nothing was launched"
+// a refined ensemble (dql_ensemble_set_refinement) refuses every call that reads or writes the plain tables or installs another mode; `instead`: what to call
+#define ENS_REFINED_REFUSED(x, who, instead) do { if ((x)->refine_feature >= 0) return fail(DQL_EINVAL, "" who ": the ensemble has a refinement (dql_ensemble_set_refinement), its tables are [n][2][DQL_N_CELLS] and its learners fly the plain mode only; " instead "; nothing was changed and nothing was launched"); } while (0)
+#define ENS_REFINED_GREEDY "use dql_ensemble_score_refined, or fetch the tables with dql_ensemble_get_refined_tables and hand one half to the plain call"
+#define ENS_REFINED_MODES "use dql_ensemble_set_schedules, dql_ensemble_set_level, dql_ensemble_run and dql_ensemble_transfer level by level"
 #define CHECK_ENS(e) do { if (!(e)) return fail(DQL_EINVAL, "null ensemble"); } while (0)
 // the tables of learners [first, first + count) where they live, for the dql_ensemble_* twins of the greedy family (TableSets of dql_greedy.inc; count >= 1 is the
 // twin's own check): the ensemble's device becomes the current one, nothing is copied
 static int tables_of_slice(const char* who, dql_ensemble* x, int64_t first, int64_t count, TableSets& q) {
+  if (x->refine_feature >= 0)
+    return fail(DQL_EINVAL, std::string(who) + ": the ensemble has a refinement (dql_ensemble_set_refinement), its tables are [n][2][DQL_N_CELLS] and its learners fly the plain mode only; " ENS_REFINED_GREEDY "; nothing was changed and nothing was launched");
   if (first < 0 || first > x->n || count > x->n - first)
     return fail(DQL_EINVAL, std::string(who) + ": the slice [first, first + count) must lie inside [0, n_learners); nothing was launched");
   HIP_TRY(hipSetDevice(x->device));
@@ -294,6 +309,7 @@ template <typename T> static void launch_learn_levels(dql_ensemble* x, int k, in
 static EnsKernel ens_kernel_of(const dql_ensemble* x, bool by_level) {
   if (x->team_every) return x->team_nstep ? ENS_K_TEAM_LEVELS_NSTEP : ENS_K_TEAM_LEVELS;
   if (by_level) return !x->rcp ? ENS_K_LEVELS : ens_recipes_any_nstep(x) ? ENS_K_RECIPES_NSTEP : ENS_K_RECIPES;
+  if (x->refine_feature >= 0) return ENS_K_LEARN_REFINED;  // (a refinement refuses teams, n-step targets and both curriculum modes, and they refuse it)
   return x->teams ? (x->team_nstep ? ENS_K_TEAM_NSTEP : ENS_K_TEAM) : x->nstep ? ENS_K_NSTEP : ENS_K_LEARN;
 }
 // The one launch path of the learners: k periods from period x->j on n_waves waves.  The tick schedule, the kernel, its completion, the launch accounting
@@ -318,6 +334,7 @@ static int ens_fly(dql_ensemble* x, EnsKernel kern, int k, int n_waves) {
       case ENS_K_RECIPES_NSTEP: launch_learn_recipes_nstep<T>(x, k, n_waves); break;
       case ENS_K_TEAM_LEVELS: launch_learn_team_levels<T>(x, k, n_waves); break;
       case ENS_K_TEAM_LEVELS_NSTEP: launch_learn_team_levels_nstep<T>(x, k, n_waves); break;
+      case ENS_K_LEARN_REFINED: launch_learn_refined<T>(x, k, n_waves); break;
     }
   });
   HIP_TRY(hipGetLastError());
@@ -549,6 +566,7 @@ int dql_ensemble_run(dql_ensemble* x, int64_t periods) {
 // ---- per-learner curriculum levels (DESIGN.md section 14) ----
 int dql_ensemble_set_curriculum(dql_ensemble* x, int32_t last_level, int32_t advance_every, const double* ratios, int32_t advance_exhausted) {
   CHECK_ENS(x);
+  ENS_REFINED_REFUSED(x, "dql_ensemble_set_curriculum", ENS_REFINED_MODES);
   if (x->envs_per_learner > 1) return fail(DQL_EINVAL, ENS_TEAMS_REFUSED("dql_ensemble_set_curriculum"));
   if (x->team_every) return fail(DQL_EINVAL, ENS_TEAM_LEVELS_REFUSED("dql_ensemble_set_curriculum"));
   if (advance_every < 0 || advance_every > ADV_MAX_EVERY) return fail(DQL_EINVAL, "dql_ensemble_set_curriculum: advance_every must be in 0..4096 (0 turns the mode off); nothing was changed");
@@ -640,8 +658,10 @@ int dql_ensemble_transfer(dql_ensemble* x, int32_t k, double ratio) {
   CHECK_ENS(x);
   if (k < 0 || k >= DQL_MAX_LEVELS) return fail(DQL_EINVAL, "dql_ensemble_transfer: curriculum step must be in 0..4");
   HIP_TRY(hipSetDevice(x->device));
-  const long long total = x->n * DQL_CELLS_PER_LEVEL;
-  hipLaunchKernelGGL(k_ens_transfer, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, x->mem.qa, x->mem.qb, (long long)x->n, (int)k,
+  // a refined ensemble: both halves of every learner, as 2 n table sets of the same kernel
+  const bool refined = x->refine_feature >= 0;
+  const long long sets = refined ? 2 * x->n : x->n, total = sets * DQL_CELLS_PER_LEVEL;
+  hipLaunchKernelGGL(k_ens_transfer, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, refined ? x->rq_a : x->mem.qa, refined ? x->rq_b : x->mem.qb, sets, (int)k,
                      (int)((k - 1 + DQL_MAX_LEVELS) % DQL_MAX_LEVELS), ratio);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
@@ -653,6 +673,7 @@ static int ens_slice(dql_ensemble* x, int64_t first, int64_t count, const char* 
 }
 int dql_ensemble_get_tables(dql_ensemble* x, int64_t first, int64_t count, double* qa_or_null, double* qb_or_null, double* count_or_null) {
   CHECK_ENS(x);
+  ENS_REFINED_REFUSED(x, "dql_ensemble_get_tables", "use dql_ensemble_get_refined_tables");
   int rc = ens_slice(x, first, count, "dql_ensemble_get_tables"); if (rc) return rc;
   HIP_TRY(hipSetDevice(x->device));
   const size_t off = (size_t)first * DQL_N_CELLS, bytes = (size_t)count * DQL_N_CELLS * sizeof(double);
@@ -663,6 +684,7 @@ int dql_ensemble_get_tables(dql_ensemble* x, int64_t first, int64_t count, doubl
 }
 int dql_ensemble_set_tables(dql_ensemble* x, int64_t first, int64_t count, const double* qa_or_null, const double* qb_or_null, const double* count_or_null) {
   CHECK_ENS(x);
+  ENS_REFINED_REFUSED(x, "dql_ensemble_set_tables", "use dql_ensemble_set_refined_tables");
   int rc = ens_slice(x, first, count, "dql_ensemble_set_tables"); if (rc) return rc;
   if (count_or_null)  // the counters index the learning-rate table on the device
     for (size_t i = 0; i < (size_t)count * DQL_N_CELLS; ++i)

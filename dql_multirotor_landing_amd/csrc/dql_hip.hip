@@ -43,6 +43,7 @@
 #include "dql_score_map.hpp"
 #include "dql_model.hpp"
 #include "dql_model_split.hpp"
+#include "dql_refined.hpp"
 #include "dql_returns.hpp"
 #include "dql_score_grid.hpp"
 #include "dql_nstep.hpp"
@@ -2089,6 +2090,7 @@ int dql_pop_index_faults(dql_ctx* x, int32_t agent, int64_t* n) {
 #include "dql_score_map.inc"
 #include "dql_model.inc"
 #include "dql_model_split.inc"
+#include "dql_refined.inc"
 #include "dql_returns.inc"
 #include "dql_score_grid.inc"
 #include "dql_view.inc"

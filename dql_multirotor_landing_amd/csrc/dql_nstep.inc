@@ -59,6 +59,7 @@ static int ens_alloc_windows(dql_ensemble* x) {
 extern "C" {
 int dql_ensemble_set_nstep(dql_ensemble* x, int32_t n) {
   CHECK_ENS(x);
+  ENS_REFINED_REFUSED(x, "dql_ensemble_set_nstep", ENS_REFINED_MODES);
   if (n < 0 || n > DQL_NSTEP_MAX) return fail(DQL_EINVAL, "dql_ensemble_set_nstep: n must be in 0..16 (DQL_NSTEP_MAX; 0: the one-step kernel); nothing was changed");
   if (n >= 1 && (x->teams || x->envs_per_learner > 1))
     return fail(DQL_EINVAL, "dql_ensemble_set_nstep: a team ensemble (dql_ensemble_create_teams) has the one-step update only; nothing was changed");

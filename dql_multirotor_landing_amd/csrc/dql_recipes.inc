@@ -122,6 +122,7 @@ static int ens_recipes_windows_empty(dql_ensemble* x) {
 extern "C" {
 int dql_ensemble_set_recipes(dql_ensemble* x, int32_t n_recipes, const int32_t* recipe_of) {
   CHECK_ENS(x);
+  ENS_REFINED_REFUSED(x, "dql_ensemble_set_recipes", ENS_REFINED_MODES);
   if (x->envs_per_learner > 1) return fail(DQL_EINVAL, ENS_TEAMS_REFUSED("dql_ensemble_set_recipes"));
   if (x->team_every) return fail(DQL_EINVAL, ENS_TEAM_LEVELS_REFUSED("dql_ensemble_set_recipes"));
   if (n_recipes < 0 || n_recipes > RCP_MAX) return fail(DQL_EINVAL, "dql_ensemble_set_recipes: n_recipes must be in 0..64 (0 uninstalls); nothing was changed");
@@ -161,7 +162,7 @@ int dql_ensemble_set_recipes(dql_ensemble* x, int32_t n_recipes, const int32_t* 
   x->rcp = q;
   return DQL_OK;
 }
-#define CHECK_RECIPE(who, x, r) do { CHECK_ENS(x); \
+#define CHECK_RECIPE(who, x, r) do { CHECK_ENS(x); ENS_REFINED_REFUSED(x, who, ENS_REFINED_MODES); \
     if (!(x)->rcp) return fail(DQL_EINVAL, std::string(who) + ": no recipes are installed (dql_ensemble_set_recipes first); nothing was changed"); \
     if ((r) < 0 || (r) >= (x)->rcp->n) return fail(DQL_EINVAL, std::string(who) + ": the recipe must be in 0..n_recipes - 1; nothing was changed"); } while (0)
 int dql_ensemble_set_recipe(dql_ensemble* x, int32_t r, uint32_t quirks, const double* alpha, int32_t n_alpha, double alpha_min, const double* ratios, int32_t last_level,

@@ -126,6 +126,7 @@ static int ens_run_team_levels(dql_ensemble* x, int64_t periods, EnsKernel kern)
 extern "C" {
 int dql_ensemble_set_team_curriculum(dql_ensemble* x, int32_t last_level, int32_t advance_every, const double* ratios, int32_t advance_exhausted, int32_t transfer_order) {
   if (!x) return fail(DQL_EINVAL, "dql_ensemble_set_team_curriculum: null ensemble; nothing was changed");
+  ENS_REFINED_REFUSED(x, "dql_ensemble_set_team_curriculum", ENS_REFINED_MODES);
   if (!x->teams) return fail(DQL_EINVAL, "dql_ensemble_set_team_curriculum: the ensemble was not made by dql_ensemble_create_teams (a plain ensemble takes dql_ensemble_set_curriculum); nothing was changed");
   if (advance_every < 0 || advance_every > ADV_MAX_EVERY) return fail(DQL_EINVAL, "dql_ensemble_set_team_curriculum: advance_every must be in 0..4096 (0 turns the mode off); nothing was changed");
   if (x->advance_every || x->rcp)

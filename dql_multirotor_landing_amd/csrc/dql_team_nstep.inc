@@ -49,6 +49,7 @@ template <typename T> static void launch_learn_team_nstep(dql_ensemble* x, int k
 extern "C" {
 int dql_ensemble_set_team_nstep(dql_ensemble* x, int32_t n) {
   if (!x) return fail(DQL_EINVAL, "dql_ensemble_set_team_nstep: null ensemble; nothing was changed");
+  ENS_REFINED_REFUSED(x, "dql_ensemble_set_team_nstep", ENS_REFINED_MODES);
   if (n < 0 || n > DQL_NSTEP_MAX) return fail(DQL_EINVAL, "dql_ensemble_set_team_nstep: n must be in 0..16 (DQL_NSTEP_MAX; 0: the one-step team kernel); nothing was changed");
   if (!x->teams) return fail(DQL_EINVAL, "dql_ensemble_set_team_nstep: the ensemble was not made by dql_ensemble_create_teams (a plain ensemble takes dql_ensemble_set_nstep); nothing was changed");
   if (n >= 1 && (x->advance_every || x->rcp))

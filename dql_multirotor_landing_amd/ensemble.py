@@ -481,6 +481,73 @@ class SequentialEnsemble:
         first, n = self._slice(first, given[0].shape[0])
         _lib.check(self.lib.dql_ensemble_set_tables(self._h, first, n, *(_p(a) for a in arrs)))
 
+    # ---- a state split by one bit of hidden state (include/dql.h dql_ensemble_set_refinement) ----
+    def set_refinement(self, feature, cut):
+        """From now on every learner learns on the refined state half * 945 + idx_x, half = value >= cut[idx_x] with value the `feature` (a name of
+        `ops.SPLIT_FEATURES` or its code) read from the env as it stands before the period — `split_model`'s half, decision for decision.  `cut`: a scalar or
+        float64 [945], no NaN; +inf keeps everything in half 0, which then equals a plain ensemble bit for bit.  Accepted once, on a plain ensemble (no teams)
+        before its first `run`, with no recipes, curriculum mode or n-step targets; the tables are then `get_refined_tables` / `set_refined_tables`'s
+        [L][2][2835] and scoring is `score_refined`.  A bad name, shape or NaN raises ValueError before the library is touched."""
+        from . import ops
+        feature, cut = ops.split_feature_code(feature), ops.split_cut_array(cut)
+        if self.teams or self.envs_per_learner > 1:
+            raise ValueError("a refinement is for a plain ensemble: one env per learner, no teams")
+        if self._nstep or self._advance_every or self._team_nstep or self._team_every or self.__dict__.get("_recipes", []):
+            raise ValueError("refined learners fly the plain mode only: no recipes, no curriculum mode, no n-step targets may be installed")
+        _lib.check(self.lib.dql_ensemble_set_refinement(self._h, feature, _p(cut)))
+
+    def refinement(self):
+        """(feature name, cut float64 [945]) of the installed refinement, or None"""
+        from . import ops
+        f, cut = C.c_int32(), np.zeros(N_CELLS // 3, dtype=np.float64)
+        _lib.check(self.lib.dql_ensemble_get_refinement(self._h, C.byref(f), _p(cut)))
+        return None if f.value < 0 else (ops.SPLIT_FEATURES[f.value], cut)
+
+    def get_refined_tables(self, first: int = 0, count: Optional[int] = None):
+        """(Q_table_a, Q_table_b, state_action_counter), float64 [count][2][N_CELLS] each, of learners first .. first + count - 1: the half is the slow index"""
+        first, count = self._slice(first, count)
+        qa, qb, cnt = (np.empty((count, 2, N_CELLS), dtype=np.float64) for _ in range(3))
+        _lib.check(self.lib.dql_ensemble_get_refined_tables(self._h, first, count, _p(qa), _p(qb), _p(cnt)))
+        return qa, qb, cnt
+
+    def set_refined_tables(self, qa=None, qb=None, count=None, first: int = 0):
+        """`set_tables` for a refined ensemble: each array float64 [K][2][N_CELLS] (or None), for learners first .. first + K - 1"""
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (qa, qb, count)]
+        given = [a for a in arrs if a is not None]
+        if not given:
+            raise ValueError("no table given")
+        if any(a.ndim != 3 or a.shape[1:] != (2, N_CELLS) for a in given):
+            raise ValueError(f"refined tables are [K][2][{N_CELLS}] arrays: the half is the slow index")
+        if len({a.shape[0] for a in given}) != 1:
+            raise ValueError("the tables must cover the same learners")
+        first, n = self._slice(first, given[0].shape[0])
+        _lib.check(self.lib.dql_ensemble_set_refined_tables(self._h, first, n, *(_p(a) for a in arrs)))
+
+    def score_refined(self, eval_cfg: DqlConfig, envs_per_learner: int = 64, seed: int = 123, episodes: int = 1, max_steps: int = 600, log: bool = False, first: int = 0,
+                      count: Optional[int] = None, timing: dict = None):
+        """`ops.score_refined` of learners first .. first + count - 1 on their refined tables where they live (no host copy), with the ensemble's own feature
+        and cut, under `eval_cfg`.  The ensemble is left as it was.  Returns what `ops.score_refined` returns, table set k = learner first + k."""
+        from . import ops
+        first, count = self._slice(first, count)
+        n, episodes, max_steps = int(envs_per_learner), int(episodes), int(max_steps)
+        ops.score_refined_check_args(eval_cfg, count, n, episodes, max_steps, max_tables=ops.SCORE_MAX_TABLES)
+        r = self.refinement()
+        if r is None:
+            raise ValueError("the ensemble has no refinement: set_refinement first, or use score")
+        by_code, steps_sum, ep_code, ep_steps = ops.score_buffers(count, n, episodes, log)
+        c = eval_cfg.to_c()
+        _lib.check(self.lib.dql_ensemble_score_refined(self._h, C.byref(c), first, count, n, episodes, int(seed), max_steps, _p(by_code), _p(steps_sum), _p(ep_code),
+                                                       _p(ep_steps)))
+        return ops.score_refined_result(self.lib, ops.SPLIT_FEATURES.index(r[0]), r[1], by_code, steps_sum, ep_code, ep_steps, timing)
+
+    def refined_landing_rates(self, n_envs: int = 4096, episodes: int = 1, level: int = 4, seed: int = 123, dtype=None, quirks=None, max_steps: int = 600, first: int = 0,
+                              count: Optional[int] = None, timing: dict = None):
+        """`landing_rates` of a refined ensemble: `touchdown_rate` and `goal_hold_rate` per learner through `score_refined`, two launches"""
+        from . import evaluation
+        quirks = evaluation.Q_PAPER if quirks is None else quirks
+        return evaluation.landing_rates_with(lambda cfg, n, sd, ep, ms, t: self.score_refined(cfg, n, sd, ep, ms, first=first, count=count, timing=t),
+                                             n_envs, episodes, level, seed, dtype, quirks, max_steps, timing)
+
     # ---- greedy scoring of the resident tables (include/dql.h dql_ensemble_score) ----
     def score(self, eval_cfg: DqlConfig, envs_per_learner: int = 64, seed: int = 123, episodes: int = 1, max_steps: int = 600, log: bool = False, first: int = 0,
               count: Optional[int] = None, timing: dict = None):

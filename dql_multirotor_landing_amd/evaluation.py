@@ -337,6 +337,32 @@ def feature_means(result):
     return np.where(sv > 0, fs.astype(np.float64) / float(1 << SPLIT_FRAC_BITS) / np.where(sv > 0, sv, 1), np.inf)
 
 
+STATES_PER_LEVEL = N_STATES // 5  # a state's curriculum level is idx_x // 189
+
+
+def refinement_cut(results_by_level):
+    """float64 [945]: the cut of `SequentialEnsemble.set_refinement` from one `ops.split_model` pass per curriculum level (cut = +inf, any eps), merged.  Level k's
+    block of states [189 k, 189 (k + 1)) takes the per-state means of the split feature from level k's pass, pooled over its table sets:
+    sum feat_sum_fx / 2^20 / sum visits.  A state that is unvisited at its own level stays at +inf (nothing is in its half 1).  `results_by_level`: {level: result}
+    or a sequence indexed by level; a level without a pass keeps +inf throughout."""
+    items = results_by_level.items() if hasattr(results_by_level, "items") else enumerate(results_by_level)
+    cut = np.full(N_STATES, np.inf)
+    for k, result in items:
+        k = int(k)
+        if not 0 <= k < N_STATES // STATES_PER_LEVEL:
+            raise ValueError(f"a curriculum level is in 0..4, not {k}")
+        if result is None:
+            continue
+        _, sv = _state_visits(result)
+        fs = np.asarray(result["feat_sum_fx"])
+        if fs.shape != sv.shape:
+            raise ValueError("feat_sum_fx [K, 945]")
+        fs, sv = fs.sum(axis=0, dtype=np.int64), sv.sum(axis=0, dtype=np.int64)
+        blk = slice(k * STATES_PER_LEVEL, (k + 1) * STATES_PER_LEVEL)
+        cut[blk] = np.where(sv[blk] > 0, fs[blk].astype(np.float64) / float(1 << SPLIT_FRAC_BITS) / np.where(sv[blk] > 0, sv[blk], 1), np.inf)
+    return cut
+
+
 def split_divergence(result, min_visits: int = 30):
     """float64 [K, 2835]: per cell the total-variation distance between the next-outcome distributions of the two halves (`model_divergence` of half 0 against
     half 1: next states and terminal codes as one alphabet).  NaN where either half has fewer than `min_visits` (>= 1) visits."""

@@ -518,6 +518,57 @@ def split_model(cfg: DqlConfig, qa, qb, envs_per_table: int, seed: int, eps: flo
     return split_model_result(lib, feature, cut, pairs, reward_fx, terminal, feat_sum_fx, by_code, steps_sum, timing)
 
 
+SCORE_REFINED_MAX_TABLES = 4096  # include/dql.h DQL_SCORE_REFINED_MAX_TABLES: 90 720 B of tables are uploaded per refined set
+
+
+def refined_table_pair(qa, qb):
+    """`qa`, `qb` as float64 [K, 2, 2835] arrays of the same K (one set: [2, 2835]), checked: refined table sets, the half the slow index"""
+    qa, qb = _f64(qa), _f64(qb)
+    if qa.ndim == 2:
+        qa = qa[None]
+    if qb.ndim == 2:
+        qb = qb[None]
+    if qa.ndim != 3 or qa.shape[1:] != (2, N_CELLS) or qb.shape != qa.shape:
+        raise ValueError("qa and qb must be [K, 2, 2835] arrays of the same K: refined table sets, the half the slow index")
+    return np.ascontiguousarray(qa), np.ascontiguousarray(qb)
+
+
+def score_refined_check_args(cfg: DqlConfig, n_tables: int, envs_per_table: int, episodes: int, max_steps: int, max_tables: int = SCORE_REFINED_MAX_TABLES):
+    """the argument checks of dql_score_refined / dql_ensemble_score_refined beyond feature and cut, made before the library is touched"""
+    if not 1 <= n_tables <= max_tables:
+        raise ValueError(f"between 1 and {max_tables} refined table sets per call, not {n_tables}: slice the sets")
+    score_check_args(n_tables, envs_per_table, episodes, max_steps)
+    if cfg.two_axis:
+        raise ValueError("two-axis configs are refused: the refinement is the x MDP's")
+    if cfg.trajectory != 0:
+        raise ValueError("the figure-eight trajectory is refused: the refinement is the x MDP's, as the learners are")
+
+
+def score_refined_result(lib, feature, cut, by_code, steps_sum, ep_code, ep_steps, timing):
+    _last_call(lib, "score_refined", "k_score_refined", timing)
+    return {"by_code": by_code, "steps_sum": steps_sum, "ep_code": ep_code, "ep_steps": ep_steps, "columns": SCORE_COLUMNS, "feature": SPLIT_FEATURES[feature], "cut": cut}
+
+
+def score_refined(cfg: DqlConfig, qa, qb, feature, cut, envs_per_table: int, seed: int, episodes: int = 1, max_steps: int = 600, log: bool = False, device: int = 0,
+                  timing: dict = None):
+    """`score` of K REFINED table sets (include/dql.h dql_score_refined): `qa`, `qb` float64 [K, 2, 2835], the half the slow index.
+
+    The envs and periods are `score`'s for the same arguments; the greedy row of a decision is that of the refined state half * 945 + idx_x, with
+    half = value >= cut[idx_x] and value the `feature` (a name of SPLIT_FEATURES or its code) read from the env as it stands before the period — `split_model`'s
+    half, decision for decision.  `cut`: a scalar or float64 [945], no NaN; +inf flies half 0's tables and -inf half 1's.  Returns `score`'s dict plus `feature`
+    and `cut`.  K up to SCORE_REFINED_MAX_TABLES.  `timing`: receives `kernel_ms` and `instance`."""
+    feature, cut = split_feature_code(feature), split_cut_array(cut)
+    qa, qb = refined_table_pair(qa, qb)
+    K, n, episodes, max_steps = len(qa), int(envs_per_table), int(episodes), int(max_steps)
+    score_refined_check_args(cfg, K, n, episodes, max_steps)
+    lib = _lib.load()
+    by_code, steps_sum, ep_code, ep_steps = score_buffers(K, n, episodes, log)
+    c = cfg.to_c()
+    _lib.check(lib.dql_score_refined(C.byref(c), device, K, n, episodes, int(seed), max_steps, feature, _p(cut), _p(qa), _p(qb), _p(by_code), _p(steps_sum),
+                                     None if ep_code is None else _p(ep_code), None if ep_steps is None else _p(ep_steps)))
+    return score_refined_result(lib, feature, cut, by_code, steps_sum, ep_code, ep_steps, timing)
+
+
 GRID_MAX_SCENARIOS, GRID_TOUCH_BINS = 1024, 8  # include/dql.h DQL_GRID_MAX_SCENARIOS, DQL_GRID_TOUCH_BINS
 GRID_SHARED_FIELDS = ("dtype", "two_axis", "f_ag", "dt", "manager_div")  # what one launch must share: the kernel instance and the tick schedule
 

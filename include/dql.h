@@ -715,6 +715,46 @@ int dql_ensemble_score_grid(dql_ensemble* ens, const dql_config* eval_cfgs /* [n
                             int64_t envs_per_learner, int32_t episodes_per_env, uint64_t seed, int32_t max_steps, int64_t* by_code, int64_t* steps_sum,
                             int64_t* touch_hist_or_null, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null);
 
+/* ---- a state split by one bit of hidden state: refined learners and their greedy scoring ----
+ * The refined state is r = half * DQL_N_STATES + idx_x and its cell r * 3 + action: a refined table set is double [2][DQL_N_CELLS], the half the slow index
+ * (DQL_N_STATES is a multiple of 189 and of 63, so (r / 63) % 3 is still the position bin, and dql_agent_update / dql_agent_predict on tables of
+ * 2 * DQL_N_CELLS entries are the yardstick).  The half of the decision taken in period j is dql_model_split's, decision for decision:
+ *   value = the feature (DQL_SPLIT_*) read from the env as it stands BEFORE period j, widened to double; the coin's j is the period index truncated to 32
+ *           bits, its env id the learner's or env's index, its seed the low 32 bits of the seed
+ *   half  = value >= cut[idx_x before period j] ? 1 : 0, compared in double
+ * so after period j ends (reset periods included) the half of the state the env is now in follows from the env as it stands, with j + 1.  A value that is not
+ * finite or has |value| >= 8192 is a fault: a learner takes the half as 0, drops the update of the decision taken in that state and counts it in
+ * dql_ensemble_index_faults; a scoring call returns DQL_ESTATE and no result.
+ *
+ * dql_ensemble_set_refinement: accepted only on an ensemble made by dql_ensemble_create (no teams), at period index 0, with no recipes, curriculum mode or n-step
+ * targets installed, and once; feature in 0..10, cut double[DQL_N_STATES] without NaN (+-inf are meaningful: +inf puts everything in half 0, -inf in half 1).
+ * It allocates zeroed refined tables and counts, [n_learners][2][DQL_N_CELLS] each; the plain arrays stay allocated and are never read again.  From then on
+ * dql_ensemble_run flies the refined learner: the eps-greedy choice reads the row of r, the update is DoubleQLearningAgent.update on cell r * 3 + action with
+ * the row of r' read before the write and the learning rate at the refined cell's pre-increment count; coin, quirks, mask, books, ring, freeze and log are the
+ * plain learner's, and two runs of a and b periods still equal one run of a + b.  dql_ensemble_set_schedules, _set_level, _rearm, _run, _get_counters,
+ * _get_episode_log, _get_state, _n_live and _get_period_index work unchanged; dql_ensemble_transfer applies its arithmetic to both halves.
+ * Refused on a refined ensemble with DQL_EINVAL and a sentence that names the call to use (nothing launched, no buffer touched): dql_ensemble_get_tables /
+ * _set_tables, _score, _score_map, _model, _model_split, _returns, _score_grid, _set_curriculum, _set_recipes and the per-recipe calls, _set_nstep, _set_team_nstep
+ * and _set_team_curriculum.  dql_ensemble_score_refined, _get_refined_tables and _set_refined_tables are refused on an ensemble without a refinement.
+ * dql_ensemble_get_refinement: the feature, or -1 without a refinement; cut_or_null receives the cut when there is one. */
+#define DQL_SCORE_REFINED_MAX_TABLES 4096 /* dql_score_refined uploads 2 x 2 x 22 680 B per table set: 372 MB at the bound */
+int dql_ensemble_set_refinement(dql_ensemble* ens, int32_t feature, const double* cut /* [DQL_N_STATES] */);
+int dql_ensemble_get_refinement(dql_ensemble* ens, int32_t* feature_or_minus1, double* cut_or_null /* [DQL_N_STATES] */);
+/* the refined tables of learners [first, first + count), double [count][2][DQL_N_CELLS] each, sliced like dql_ensemble_get_tables / _set_tables; each array optional */
+int dql_ensemble_get_refined_tables(dql_ensemble* ens, int64_t first, int64_t count, double* qa_or_null, double* qb_or_null, double* count_or_null);
+int dql_ensemble_set_refined_tables(dql_ensemble* ens, int64_t first, int64_t count, const double* qa_or_null, const double* qb_or_null,
+                                    const double* count_or_null);
+/* dql_score on refined table sets qa / qb double [n_tables][2][DQL_N_CELLS]: the same envs (key (i, seed), periods 0..max_steps, episodes through reset), the
+ * greedy row that of r by the half rule above.  Outputs and refusals are dql_score's, plus DQL_EINVAL for a two-axis config, the figure-eight trajectory (the
+ * ensembles refuse both: the refinement is the x MDP's), a feature outside 0..10, a null cut or a NaN in it, and n_tables above DQL_SCORE_REFINED_MAX_TABLES. */
+int dql_score_refined(const dql_config* cfg, int device, int64_t n_tables, int64_t envs_per_table, int32_t episodes_per_env, uint64_t seed, int32_t max_steps,
+                      int32_t feature, const double* cut /* [DQL_N_STATES] */, const double* qa, const double* qb, int64_t* by_code, int64_t* steps_sum,
+                      uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null);
+/* dql_score_refined on the refined tables of learners [first, first + count) where they live, with the ensemble's own feature and cut (count in place of
+ * n_tables, up to DQL_SCORE_MAX_TABLES: nothing is uploaded; the slice must lie inside the ensemble).  The ensemble is left byte for byte as it was. */
+int dql_ensemble_score_refined(dql_ensemble* ens, const dql_config* eval_cfg, int64_t first, int64_t count, int64_t envs_per_learner, int32_t episodes_per_env,
+                               uint64_t seed, int32_t max_steps, int64_t* by_code, int64_t* steps_sum, uint8_t* ep_code_or_null, uint16_t* ep_steps_or_null);
+
 /* ---- per-learner curriculum levels ----
  * Every learner has its own working level (it starts at the config's working_curriculum_step; dql_ensemble_set_level sets everybody's and clears the history
  * from that level on).  CURRICULUM MODE — off by default, and while it is off every call above behaves as described there — lets a learner walk the levels by

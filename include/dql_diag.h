@@ -55,6 +55,9 @@ int dql_diag_returns_last(double* fly_ms, double* sweep_ms, int32_t* inst3);
 /* the same for the calling thread's latest completed dql_score_grid or dql_ensemble_score_grid: the template arguments of k_score_grid's name.  A refused
  * call leaves the record as it was */
 int dql_diag_score_grid_last(double* kernel_ms, int32_t* inst3);
+/* the same for the calling thread's latest completed dql_score_refined or dql_ensemble_score_refined: the template arguments of k_score_refined's name.  A
+ * refused call leaves the record as it was, and dql_diag_score_last keeps its meaning */
+int dql_diag_score_refined_last(double* kernel_ms, int32_t* inst3);
 
 /* wall duration on the device (HIP events around all launches) of the ensemble's latest completed dql_ensemble_run */
 int dql_diag_ensemble_last(dql_ensemble* ens, double* run_ms);

@@ -7,6 +7,7 @@ one learner per GPU lane (dql_multirotor_landing_amd/ensemble.py).
                                         [--envs-per-learner E [--team-nstep N] [--per-team [--advance-every E] [--drop-exhausted] [--max-periods N]]]
                                         [--score-map] [--preset reference|paper]
                                         [--score-grid FIELD=v1,v2,... [--score-grid ...]]
+                                        [--refine FEATURE --refine-cut FILE.npy|FLOAT]
 
 --launched: the parameters the reference's manager node ran with under roslaunch (config.as_launched_config) instead of the launch file's.
 --score ENVS: after the curriculum, fly every learner's tables greedily where they live (SequentialEnsemble.landing_rates: ENVS envs per learner and flavour,
@@ -42,6 +43,11 @@ envs re-entering through reset, and each launch carries the live teams only.  Wo
 --team-nstep N (with --envs-per-learner above 1): the team learners update with the uncorrected N-step Double-Q return, 1..16, one pending window per env, the
 E transitions of a period still taken in env order (SequentialEnsemble.set_team_nstep); 0, the default, is the one-step team update.
 Refused together with --nstep, --per-learner and --recipes; works with --per-team; N is recorded in the .npz as `team_nstep`.
+--refine FEATURE --refine-cut FILE.npy|FLOAT (level-by-level driver only, with --preset reference or paper): every learner learns on the state split by one bit of
+hidden state, half = FEATURE >= cut[state] (SequentialEnsemble.set_refinement).  FEATURE is a name of ops.SPLIT_FEATURES ("pitch_sp", "coin",
+...); the cut is one number for every state or a float64 [945] array (scripts/simulation.py --cut-out writes one).  Refused together with --per-learner, --per-team,
+--recipes, --nstep, --team-nstep, --envs-per-learner above 1, --score-map and --score-grid.  --score ENVS then flies the refined tables (score_refined), and the .npz
+holds the refined tables [learners, 2, 2835], `refine_feature` and `refine_cut` instead of the plain tables.
 Writes every learner's tables and, per level, its first-promotion episode (-1: the episode budget ran out first); with --per-learner also each learner's level,
 the episodes it spent at each level and the period index at which it entered it."""
 import argparse
@@ -175,13 +181,15 @@ def score_report(ens, a):
     level = a.levels - 1
     kw = dict(n_envs=a.score, episodes=a.score_episodes, level=level, seed=a.score_seed)
     t = {}
-    r = flight_maps_sliced(ens, t, **kw) if a.score_map else ens.landing_rates(timing=t, **kw)
+    r = flight_maps_sliced(ens, t, **kw) if a.score_map else ens.refined_landing_rates(timing=t, **kw) if a.refine is not None else ens.landing_rates(timing=t, **kw)
     td, gh = r["touchdown_rate"], r["goal_hold_rate"]
     rep = {"what": "ensemble_landing_rates", "learners": int(td.size), "envs_per_learner": a.score, "episodes_per_env": a.score_episodes, "level": level,
            "levels_trained": a.levels, "episode_budget_per_level": a.episodes, "launched": bool(a.launched), "seed": a.score_seed, "bar": evaluation.LANDING_BAR, "learners_at_or_above_bar": int((td >= evaluation.LANDING_BAR).sum()),
            "share_at_or_above_bar": float((td >= evaluation.LANDING_BAR).mean()), "touchdown_rate": rate_summary(td), "goal_hold_rate": rate_summary(gh),
            "unfinished_episodes": {"simulation": int(r["simulation_by_code"][:, -1].sum()), "training": int(r["training_by_code"][:, -1].sum())},
            "kernel_ms": t["kernel_ms"], "instance": t["instance"], "reference_tables": None}
+    if a.refine is not None:
+        rep["refine"] = {"feature": a.refine, "cut": a.refine_cut}
     ref = Path(a.reference_tables)
     if (ref / "Q_table_a.npy").exists() and (ref / "Q_table_b.npy").exists():
         qa, qb = (np.load(ref / f).ravel().astype(np.float64) for f in ("Q_table_a.npy", "Q_table_b.npy"))
@@ -244,8 +252,28 @@ def main():
     ap.add_argument("--nstep", type=int, default=0, metavar="N", help="n-step Double-Q targets, 1..16 (0: the reference's one-step update; not with --per-learner / --recipes / --envs-per-learner above 1; with --recipes give each recipe its own \"nstep\" in the file)")
     ap.add_argument("--team-nstep", type=int, default=0, metavar="N", help="with --envs-per-learner above 1: n-step Double-Q targets for the team learners, 1..16, one pending window per env (0: the one-step team update; not with --nstep / --per-learner / --recipes)")
     ap.add_argument("--per-team", action="store_true", help="every team advances through the levels by itself (with --envs-per-learner; takes --advance-every, --drop-exhausted, --max-periods, --team-nstep and --preset paper; not with --per-learner / --recipes / --nstep)")
+    ap.add_argument("--refine", default=None, metavar="FEATURE", help="learn on the state split by FEATURE >= cut[state] (a name of ops.SPLIT_FEATURES; needs --refine-cut; level-by-level driver with one env per learner only)")
+    ap.add_argument("--refine-cut", default=None, metavar="FILE.npy|FLOAT", help="with --refine: the cut, one number for every state or a float64 [945] array")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
+    refine_cut = None
+    if (a.refine is None) != (a.refine_cut is None):
+        ap.error("--refine FEATURE and --refine-cut FILE.npy|FLOAT go together")
+    if a.refine is not None:
+        for flag, on in (("--per-learner", a.per_learner), ("--per-team", a.per_team), ("--recipes", a.recipes), ("--nstep", a.nstep), ("--team-nstep", a.team_nstep),
+                         ("--envs-per-learner above 1", a.envs_per_learner > 1), ("--score-map", a.score_map), ("--score-grid", a.score_grid)):
+            if on:
+                ap.error(f"--refine cannot be combined with {flag}: refined learners fly the level-by-level (barrier) driver with one env per learner and the one-step update, and are scored with score_refined")
+        from dql_multirotor_landing_amd import ops
+        try:
+            ops.split_feature_code(a.refine)
+            try:
+                refine_cut = float(a.refine_cut)
+            except ValueError:
+                refine_cut = np.load(a.refine_cut)
+            refine_cut = ops.split_cut_array(refine_cut)
+        except (ValueError, OSError) as e:
+            ap.error(f"--refine / --refine-cut: {e}")
     if a.per_team and a.per_learner:
         ap.error("--per-team cannot be combined with --per-learner: --per-learner is the plain ensemble's driver (one env per learner), --per-team the team ensemble's")
     if a.per_team and a.recipes:
@@ -284,6 +312,8 @@ def main():
     ens = SequentialEnsemble(cfg, a.learners, seed=a.seed, device=a.device, max_episodes=a.episodes, envs_per_learner=a.envs_per_learner, nstep=a.nstep,
                              team_nstep=a.team_nstep, teams=True if a.per_team else None)
     try:
+        if a.refine is not None:
+            ens.set_refinement(a.refine, refine_cut)
         def report(e, h):
             p = h["promotion_episode"]
             print(json.dumps({"level": h["level"], "periods": h["periods"], "promoted": int((p >= 0).sum()), "of": int(p.size),
@@ -338,7 +368,9 @@ def main():
                   + ("not found" if ref is None else f"touchdown {ref['touchdown_rate']:.4f}, goal hold {ref['goal_hold_rate']:.4f}"), flush=True)
             if a.score_json:
                 Path(a.score_json).write_text(json.dumps(rep) + "\n")
-        qa, qb, cnt = ens.get_tables()
+        if a.refine is not None:
+            extra.update({"refine_feature": np.str_(ens.refinement()[0]), "refine_cut": ens.refinement()[1]})
+        qa, qb, cnt = ens.get_refined_tables() if a.refine is not None else ens.get_tables()
         np.savez_compressed(a.out, Q_table_a=qa, Q_table_b=qb, state_action_counter=cnt, nstep=np.int32(a.nstep), team_nstep=np.int32(a.team_nstep), **extra,
                             promotion_episode=np.stack([h["promotion_episode"] for h in hist]), periods=np.array([h["periods"] for h in hist]))
     finally:

@@ -7,6 +7,7 @@ pair of Q tables in the vectorised simulator and reports how the episodes end.
                                  [--model-out FILE.npz [--model-eps 0.1]] [--grid-out FILE.npz --grid FIELD=v1,v2,... [--grid ...]]
                                  [--returns-out FILE.npz [--returns-eps 0.1] [--returns-gamma 0.99]]
                                  [--split-out FILE.npz --split-by NAME[,NAME...]|all [--split-eps 0.1] [--split-seeds 1]]
+                                 [--cut-out FILE.npy --cut-by FEATURE [--cut-eps 0.1]]
 Default tables: tests/golden/assets (a data copy of the reference's stage-4 policy).
 --rollout flies all first episodes in one launch (dql_rollout) instead of one launch per agent period; --report prints what the episodes looked like at
 their end (the counterpart of the `info` dictionary the reference prints per episode, scripts/simulation.py:52-56) and --trace-out saves the per-period
@@ -24,6 +25,9 @@ episodes per env).
 e.g. pitch_sp,mp_phase,prev_action, or `all`) three passes over identical flights — cut = +inf for the feature's per-state means, the split at the means, and one
 coin pass for the sampling floor (--split-seeds seeds summed, --map-episodes episodes per env).  The file holds per feature `pairs_NAME` [2, 2835, 945],
 `terminal_NAME`, `reward_fx_NAME`, `feat_sum_fx_NAME` [945] and `cut_NAME` [945], and the coin's; `evaluation.aliasing_table`'s rows are printed and reported.
+--cut-out writes the cut a refined ensemble is trained with (scripts/ensemble_training.py --refine FEATURE --refine-cut FILE.npy): the tables
+are flown at each of the levels 0 .. 4 in the training flavour with one dql_model_split pass per level (cut = +inf, --cut-eps, --map-episodes episodes per env), and
+`evaluation.refinement_cut` merges the per-state means of --cut-by into one float64 [945] array; a state that is unvisited at its own level stays at +inf.
 --grid-out scores the tables over the Cartesian product of the --grid axes in ONE launch (dql_score_grid): `--grid mp_t_x=0.8,1.2,1.6 --grid
 trajectory=0,1` flies six scenarios that differ from the flavour's config in those fields only (the first axis varies slowest).  The file holds `by_code`
 [S, codes + 1], `steps_sum` [S], `touch_hist` [S, 8] (touchdowns by their offset from the platform centre), `touch_edges` [S, 7], `columns`, one array per
@@ -115,6 +119,19 @@ def evaluate_split(tables_dir, features, n_envs=4096, level=4, max_steps=600, se
     return out, table
 
 
+def evaluate_cut(tables_dir, feature, n_envs=4096, max_steps=600, seed=123, dtype=None, flavour="training", device=0, episodes=1, eps=0.1, **cfg_kw):
+    """The cut of a refinement by `feature`: one split-model pass per level 0 .. 4 (cut = +inf) over the tables' eps-greedy flights, merged by
+    `evaluation.refinement_cut`; returns (cut float64 [945], states visited per level)."""
+    import numpy as np
+    from dql_multirotor_landing_amd import evaluation, ops
+    from dql_multirotor_landing_amd.double_q_learning import DoubleQLearningAgent
+    qa, qb, _ = DoubleQLearningAgent.load(Path(tables_dir))._padded()
+    results = [ops.split_model(evaluation._flavour_config(flavour, level, dtype, cfg_kw), qa, qb, n_envs, seed, eps, feature, np.inf, episodes=episodes, max_steps=max_steps,
+                               device=device) for level in range(5)]
+    cut = evaluation.refinement_cut(results)
+    return cut, [int(np.isfinite(cut[189 * k:189 * (k + 1)]).sum()) for k in range(5)]
+
+
 def evaluate_returns(tables_dir, n_envs=4096, level=4, max_steps=600, seed=123, dtype=None, flavour="simulation", device=0, episodes=1, eps=0.1, gamma=0.99, **cfg_kw):
     """The realised returns of the same flights under the tables' eps-greedy policy and the calibration of the tables against them; returns (arrays, summary)."""
     import numpy as np
@@ -172,7 +189,12 @@ if __name__ == "__main__":
     ap.add_argument("--split-seeds", type=int, default=1, help="how many seeds' flights are summed per pass (123, 124, ...)")
     ap.add_argument("--grid-out", default=None, metavar="FILE.npz", help="save the tables' score over the grid of --grid scenarios, flown in one launch (dql_score_grid)")
     ap.add_argument("--grid", action="append", default=[], metavar="FIELD=v1,v2,...", help="one axis of the --grid-out scenarios: a DqlConfig field and its values (repeatable)")
+    ap.add_argument("--cut-out", default=None, metavar="FILE.npy", help="save the per-state means of --cut-by over the tables' flights at levels 0 .. 4: the cut of a refined ensemble (dql_model_split)")
+    ap.add_argument("--cut-by", default=None, metavar="FEATURE", help="the hidden variable of --cut-out: a name of ops.SPLIT_FEATURES")
+    ap.add_argument("--cut-eps", type=float, default=0.1, help="exploration rate of the --cut-out launches, in [0, 1]")
     a = ap.parse_args()
+    if bool(a.cut_out) != bool(a.cut_by):
+        ap.error("--cut-out FILE.npy and --cut-by FEATURE belong together")
     if bool(a.split_out) != bool(a.split_by):
         ap.error("--split-out FILE.npz and --split-by NAME[,NAME...] belong together")
     if bool(a.grid_out) != bool(a.grid):
@@ -226,6 +248,13 @@ if __name__ == "__main__":
         print(evaluation.format_aliasing_table(table), file=sys.stderr)
         out["split"] = {"file": a.split_out, "eps": a.split_eps, "episodes_per_env": a.map_episodes, "seeds": a.split_seeds, "decisions": int(m["pairs_coin"].sum() + m["terminal_coin"].sum()),
                         "table": {k: {f: (v if isinstance(v, int) else round(v, 4)) for f, v in row.items()} for k, row in table.items()}}
+    if a.cut_out:
+        import numpy as np
+        from dql_multirotor_landing_amd import ops
+        name = ops.SPLIT_FEATURES[ops.split_feature_code(a.cut_by)]
+        cut, visited = evaluate_cut(a.tables, name, n, episodes=a.map_episodes, eps=a.cut_eps, quirks=quirks)
+        np.save(a.cut_out, cut)
+        out["cut"] = {"file": a.cut_out, "feature": name, "eps": a.cut_eps, "episodes_per_env": a.map_episodes, "states_visited_per_level": visited}
     if a.grid_out:
         import numpy as np
         from dql_multirotor_landing_amd.config import parse_grid_axes
